@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: optimisation iterations/s of the PBR shading hot path at 512x512.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`--dump-outputs`: then writes what the timed phase computed
+in its last step).  Everything else it can measure (`cpu_baseline`, `modes`, `host_enqueue`, `roofline`, PSNR, the cold first-process
+rate) runs under `--full`.
 
 With N > 1 and no torchrun environment, this process only LAUNCHES the ranks (`python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`, one rank per GPU over RCCL) and exits with their code; it never
@@ -10,7 +14,7 @@ touches the GPU itself.  Under torchrun (RANK / LOCAL_RANK / WORLD_SIZE set) it 
 One "step" = one optimisation iteration (epoch) of hot loop B of BASELINE configs[1] (`--model_name pos_mlp --opt_order 'rm a'`,
 inverse_img_w_mi.py:470-590): material maps from the residual PosMLP (f32-MFMA sine-layer kernels of libmatpbr.so) -> render
 (GGX-lobe samples; diffuse-lobe coefficients cached for the phase) -> gamma-2.2 MSE/L1 loss with mean-ratio scaling ->
-streaming backward -> AdamW, everything downstream of the maps in libmatpbr.so, inputs resident in HBM.  `modes` reports the
+streaming backward -> AdamW, everything downstream of the maps in libmatpbr.so, inputs resident in HBM.  `modes` (--full) reports the
 other loops of the pipeline measured in the same run: `fused` (`--model_name none`, whole iteration in libmatpbr.so), `fused_b8`
 (BASELINE configs[2]'s per-GPU shard: 8 images x 512x512 in the kernels' batch dimension), `env` (hot loop A on the radiance
 transfer).  Images are independent, so ranks never communicate inside the timed region (weak scaling: `images_per_gpu` per rank).
@@ -99,9 +103,15 @@ def parse(argv=None):
     ap.add_argument("--mlp-lds-dma", type=int, choices=[0, 1, 2, 3], default=None,
                     help="main loop of the split-operand layer kernels: 2 (default) operands by LDS-DMA, two 256-thread workgroups per CU; "
                          "1 LDS-DMA, one 512-thread workgroup per CU; 0 register-staged (same bits; A/B switch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-relight", action="store_true", help="skip the 2048x2048 relighting measurement (1.3 GB transfer buffer)")
-    ap.add_argument("--no-extras", action="store_true", help="headline mode only (no other loops, no kernel roofline legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: cpu_baseline, the cold first-process rate, PSNR, the other loops (modes), "
+                         "host_enqueue and the roofline legs (without it: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed phase computed in its last step as DIR/<name>.npy (float32, at most 64 MB "
+                         "in all: a fixed, seeded sample of the pixels of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-relight", action="store_true", help="with --full: skip the 2048x2048 relighting measurement (1.3 GB transfer buffer)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline mode only (no other loops, no kernel roofline legs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) even at world size 1 and run the barrier / all_gather of the timing protocol: "
@@ -109,6 +119,43 @@ def parse(argv=None):
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="exercise the launcher and the timing protocol with a CPU stand-in step over gloo (tests/test_bench_launcher.py)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT = 64 * 2 ** 20       # bytes of --dump-outputs in all
+
+
+def dump_outputs(phase, out_dir: str) -> dict:
+    """What a caller of the timed phase receives after its last step, as float32 .npy files: the maps of the current parameters, the render,
+    SaveBest's image and the loss statistics.  Larger than DUMP_LIMIT in all: every large array keeps the same share of its rows (first axes
+    flattened), at indices drawn from a fixed seed, so that two builds given the same arguments write the same elements."""
+    import numpy as np
+    import torch
+
+    arrays = {f"maps_{k}": v for k, v in phase.current_maps().items() if isinstance(v, torch.Tensor)}
+    for name in ("pred", "best_img", "stats"):
+        v = getattr(phase, name, None)
+        if isinstance(v, torch.Tensor):
+            arrays[name] = v
+    for k, v in (getattr(phase, "last", None) or {}).items():
+        if isinstance(v, torch.Tensor):
+            arrays[f"last_{k}"] = v
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    large = sum(a.nbytes for a in arrays.values() if a.nbytes > 2 ** 20)
+    budget = DUMP_LIMIT - 2 ** 16                    # (room for the .npy headers)
+    share = (budget - (total - large)) / large if total > budget else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, a in sorted(arrays.items()):
+        if share < 1.0 and a.nbytes > 2 ** 20:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            n = max(1, int(rows.shape[0] * share))
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], n, replace=False))
+            a = rows[idx]
+            k = f"{k}_sample"
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[k] = list(a.shape)
+    return written
 
 
 def launch_ranks(n: int, argv) -> int:
@@ -263,7 +310,8 @@ def main(argv=None):
     pinned = pin_rank_cores()          # the ranks of a node on disjoint core sets (before any thread pool starts)
     # the CPU baseline runs BEFORE the GPU legs (rank 0, N = 1 only): the GPU work then sits at the end of the run
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    extras = args.full and not args.no_extras        # everything beyond the headline runs under --full only
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.size, args.spp, args.cpu_seconds)
     use_dist = world > 1 or args.force_dist
     if use_dist:
@@ -384,16 +432,20 @@ def main(argv=None):
     stepper = lambda p: getattr(p, "bench_step", p.step)
     # the same protocol on a process whose GPU has done nothing yet (no device warm-up): what the driver's first process on an idle box
     # would see without the throw-away phase below -- reported, never the headline
-    c_el, _ = proto.timed(stepper(wl.phase(mode)), args.warmup, min(args.steps, 20))
-    cold = min(args.steps, 20) * B * world / c_el
+    cold = None
+    if args.full:
+        c_el, _ = proto.timed(stepper(wl.phase(mode)), args.warmup, min(args.steps, 20))
+        cold = min(args.steps, 20) * B * world / c_el
     # Device warm-up, outside the protocol's W + K steps: a throw-away phase of the same mode runs for ~0.5 s.  The first GPU work of a fresh
     # process on an idle MI355X runs below its sustained clocks for some tens of milliseconds (measured: --steps 20 --warmup 5 as the box's
     # first process 256-284 it/s, the same command right after it 407-420); W = 5 iterations (12 ms) do not cover that.  Reported in the line.
     # The phase that is timed is BUILT first (its 1.8 GB of buffers, its diffuse cache) and the warm-up runs right before its W + K steps:
     # built after the warm-up (rounds 2-4), the allocations left the GPU idle for ~0.1 s and the protocol's first iterations ran on clocks that
     # had dropped again (--steps 20 --warmup 5 read 3 % below --steps 300 on the same box).
+    torch.manual_seed(0)                              # the networks' initial weights: the same inputs in every run with the same arguments
     phase = wl.phase(mode)
-    psnr0 = float(loop._loss.psnr(render.render_w_brdf(wl.scene, *[phase.current_maps()[k].detach() for k in ("albedo", "roughness", "metallic")], None, args.spp), wl.gt_image).mean())
+    if args.full:
+        psnr0 = float(loop._loss.psnr(render.render_w_brdf(wl.scene, *[phase.current_maps()[k].detach() for k in ("albedo", "roughness", "metallic")], None, args.spp), wl.gt_image).mean())
     t_w = time.perf_counter()
     warm = wl.phase(mode)
     wstep = getattr(warm, "bench_step", warm.step)
@@ -407,15 +459,17 @@ def main(argv=None):
     elapsed, per_rank = proto.timed(stepper(phase), args.warmup, args.steps)
     del warm, wstep
     value = args.steps * B * world / elapsed
-    m = phase.current_maps()
-    with torch.no_grad():
-        final = render.render_w_brdf(wl.scene, m["albedo"].detach(), m["roughness"].detach(), m["metallic"].detach(), None, args.spp)
-    psnr1 = float(loop._loss.psnr(final, wl.gt_image).mean())
+    dumped = dump_outputs(phase, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    if args.full:
+        m = phase.current_maps()
+        with torch.no_grad():
+            final = render.render_w_brdf(wl.scene, m["albedo"].detach(), m["roughness"].detach(), m["metallic"].detach(), None, args.spp)
+        psnr1 = float(loop._loss.psnr(final, wl.gt_image).mean())
 
     # the other loops of the same pipeline, for the record (same fences; whole-job rates over all ranks)
     modes = {mode: {"it_per_s": value, "ms_per_step": elapsed / args.steps * 1e3, "images_per_gpu": B}}
     wl8 = None
-    if not args.no_extras and mode != "torch":
+    if extras and mode != "torch":
         for extra, steps in (("fused", 2000), ("fused_a", 2000), ("fused_exact", 500), ("torch", 300), ("pos_mlp", 100), ("env", 500), ("env_texels", 1000), ("fused_n", 300), ("pos_mlp_n", 100)):
             if extra == mode or (not extra.startswith("fused") and B > 1):
                 continue
@@ -476,7 +530,7 @@ def main(argv=None):
     # Measured as the wall time per step() of the same phase classes on images so small that the GPU side is far shorter than the host side
     # (64 x 64 / 128 x 128: the launches and their arguments are the same); eight ranks on one node need that many microseconds of a core each
     host_enqueue = None
-    if not args.no_extras and mode != "torch":
+    if extras and mode != "torch":
         host_enqueue = {}
         for name, hb, hsize, hmode in (("PipelinedBrdfPhase_b8_rm", 8, 64, "fused"), ("FusedBrdfPhase_b1_rm", 1, 64, "fused"), ("ArmMlpPhase_rm", 1, 128, "pos_mlp")):
             try:
@@ -561,7 +615,7 @@ def main(argv=None):
         return e0.elapsed_time(e1) / reps
 
     roof = None
-    if not args.no_extras:
+    if extras:
         def kernel_times(w):
             """The BRDF fwd / bwd kernels on workload w: in-loop pair (cached diffuse lobe + jac, streaming loss backward) and the
             stand-alone operator pair (everything in-kernel)."""
@@ -749,7 +803,7 @@ def main(argv=None):
     # kernels of libmatpbr.so (epilogues included): the split-operand kernels on the bf16 matrix pipe (what the iteration runs),
     # the exact-f32 MFMA kernels and the BLAS product of the same shape beside them
     gemm = None
-    if B == 1 and not args.no_extras:
+    if B == 1 and extras:
         from materialist_amd import posmlp as _pm
 
         Mg = H * W
@@ -831,7 +885,7 @@ def main(argv=None):
 
     # BASELINE configs[4]: forward-only relighting, 2048x2048, 360 lights, through the precomputed transfer (HBM-bound kernel)
     relight = None
-    if B == 1 and not args.no_relight and not args.no_extras:
+    if B == 1 and not args.no_relight and extras:
         RS = 2048
         scr = synthetic.make_scene(wl.lo, RS, RS)
         tr = lambda x: torch.from_numpy(x).to(dev)
@@ -887,8 +941,11 @@ def main(argv=None):
                                           if _posmlp._PosMlpHipFn.PRODUCTS else "exact-f32 MFMA kernels (v_mfma_f32_32x32x2_f32)")},
             "ranks": [{"rank": r, "it_per_s": args.steps * B / t} for r, t in enumerate(per_rank)],
             "modes": modes,
-            "psnr_db": {"initial_guess": psnr0, "after_timed_steps": psnr1, "vs": "own HIP render of the synthetic ground truth (Mitsuba cannot run, SURVEY F3)"},
         }
+        if args.full:
+            out["psnr_db"] = {"initial_guess": psnr0, "after_timed_steps": psnr1, "vs": "own HIP render of the synthetic ground truth (Mitsuba cannot run, SURVEY F3)"}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if pinned is not None:
             out["rank_core_pinning"] = pinned
         if host_enqueue is not None:

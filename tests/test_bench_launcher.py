@@ -54,3 +54,44 @@ def test_bench_line_is_compact_and_carries_the_contract_keys():
     # a record with hundreds of modes still yields a parseable line (the optional blocks are dropped first)
     full["modes"] = {f"mode_{i}": {"it_per_s": 1.0 + i} for i in range(600)}
     assert len(bench.compact_line(full)) < 4096
+
+
+def test_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs`: small outputs are written whole; outputs larger than bench.DUMP_LIMIT in all keep the same seeded rows in
+    every run (two builds compare element for element), float32, at most DUMP_LIMIT bytes."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Phase:
+        def __init__(self, B):
+            g = torch.Generator().manual_seed(B)
+            self.pred = torch.rand(B, 512, 512, 3, generator=g)
+            self.stats = torch.rand(B, 16, generator=g, dtype=torch.float64)
+            self._maps = {"albedo": torch.rand(B, 512, 512, 3, generator=g), "roughness": torch.rand(B, 512, 512, 1, generator=g), "normal": None}
+
+        def current_maps(self):
+            return self._maps
+
+    small = bench.dump_outputs(Phase(1), str(tmp_path / "small"))
+    assert small == {"maps_albedo": [1, 512, 512, 3], "maps_roughness": [1, 512, 512, 1], "pred": [1, 512, 512, 3], "stats": [1, 16]}
+    ph = Phase(1)
+    assert np.array_equal(np.load(tmp_path / "small" / "pred.npy"), ph.pred.numpy())
+    assert np.load(tmp_path / "small" / "stats.npy").dtype == np.float32
+
+    big = Phase(12)                                       # 12 x (3 + 1 + 3) x 1 MB floats = 84 MB
+    big.pred[..., 0] = torch.arange(12 * 512 * 512, dtype=torch.float32).reshape(12, 512, 512)      # each row carries its index
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["maps_albedo_sample.npy", "maps_roughness_sample.npy", "pred_sample.npy", "stats.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    rows = np.load(tmp_path / "a" / "pred_sample.npy")   # whole pixels of the output, in their order
+    flat = big.pred.numpy().reshape(-1, 3)
+    idx = rows[:, 0].astype(np.int64)
+    assert rows.shape[1] == 3 and len(rows) > len(flat) // 2 and (np.diff(idx) > 0).all() and np.array_equal(rows, flat[idx])

@@ -423,7 +423,7 @@ def test_rccl_path_of_the_bench_at_world_size_one():
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--force-dist", "--gpus", "1", "--mode", "fused", "--images-per-gpu", "8", "--no-extras", "--no-cpu-baseline",
+           os.path.join(root, "bench.py"), "--full", "--force-dist", "--gpus", "1", "--mode", "fused", "--images-per-gpu", "8", "--no-extras", "--no-cpu-baseline",
            "--steps", "300", "--warmup", "10"]           # the default line's `fused_b8` protocol (a phase's first iterations re-sample the most)
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)      # a child process: never an exec from a GPU-initialised one
     assert res.returncode == 0, res.stderr[-2000:]
@@ -437,8 +437,8 @@ def test_rccl_path_of_the_bench_at_world_size_one():
     assert out["value"] == pytest.approx(300 * 8 / (out["ms_per_step"] * 300 * 1e-3), rel=1e-6)     # image-iterations/s over all ranks
     assert len(out["ranks"]) == 1 and out["value"] > 1000
     assert out["cold_first_process_it_per_s"] > 0
-    # the same workload is `modes.fused_b8` of the default line (one rank, no RCCL): the two agree up to the run-to-run spread of a box
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-relight", "--steps", "5", "--warmup", "2"], env=env,
+    # the same workload is `modes.fused_b8` of the --full line (one rank, no RCCL): the two agree up to the run-to-run spread of a box
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-relight", "--steps", "5", "--warmup", "2"], env=env,
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     brief = json.loads(res.stdout.splitlines()[-1])
@@ -450,6 +450,30 @@ def test_rccl_path_of_the_bench_at_world_size_one():
     # the boxes of the pool are not all alike
     assert b8["images_per_gpu"] == 8 and b8["it_per_s"] > 0 and b8["it_per_s"] == pytest.approx(8e3 / b8["ms_per_step"], rel=1e-3)
     assert 0 < default["roofline"]["frac"] < 1 and default["cold_first_process_it_per_s"] > 0
+
+
+def test_plain_bench_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline loop alone (no roofline, cpu_baseline, other loops or PSNR), K timed
+    steps, and with --dump-outputs what the timed phase holds after its last step: float32 .npy files, the same in two runs."""
+    import json
+    import subprocess
+    import sys
+
+    _cuda()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for k in range(2):
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs",
+                              str(tmp_path / f"d{k}")], capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads(res.stdout.splitlines()[-1])
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "it/s" and line["dtype"] == "f32"
+        assert line["value"] == pytest.approx(7 / (line["ms_per_step"] * 7 * 1e-3), rel=1e-4)
+        assert not {"roofline", "cpu_baseline", "psnr_db"} & set(line) and list(line["modes_it_per_s"]) == [line["config"]["mode"]]
+        outs.append({f: np.load(tmp_path / f"d{k}" / f) for f in sorted(os.listdir(tmp_path / f"d{k}"))})
+    assert {"maps_albedo.npy", "maps_roughness.npy", "maps_metallic.npy", "pred.npy", "stats.npy"} <= set(outs[0])
+    assert outs[0]["pred.npy"].shape == (512, 512, 3) and all(a.dtype == np.float32 for a in outs[0].values())
+    assert list(outs[0]) == list(outs[1]) and all(np.array_equal(outs[0][f], outs[1][f]) for f in outs[0])
 
 
 @pytest.mark.parametrize("model_name,epochs", [("none", 5000), ("pos_mlp", 150)])
