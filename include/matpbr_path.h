@@ -1,0 +1,80 @@
+/*
+ * matpbr_path.h -- C ABI of libmatpbr_path.so: a forward-only path-traced re-render of the depth mesh (MI355X, gfx950).
+ *
+ * The integrator is Mitsuba 3's `path` as the reference configures it for its final images (render_final.py:35-96,
+ * inverse_img_w_mi.py:49-52: `max_depth` 4, MatDiffBSDF on the `.ply` depth mesh, equirectangular envmap emitter); its
+ * definition and the ways it differs from Mitsuba are DESIGN.md section 1.4.  It is a separate library so that
+ * libmatpbr.so's sources (and the digest the traffic profile is tied to) stay untouched.
+ *
+ * Conventions (those of matpbr.h)
+ *   - Host pointers are named *_host or belong to the *_host / build entry points; matpbr_path_render takes DEVICE pointers.
+ *   - Maps a[H,W,3] r[H,W,1] m[H,W,1], envmap env[He,W_e,3], output out[H,W,3]: fp32, contiguous, row-major HWC.
+ *   - `stream` is the caller's hipStream_t (NULL = default stream); the render only enqueues work.
+ *   - Return value: 0 = MATPBR_OK, negative = error (matpbr_path_strerror); nothing throws.
+ */
+#ifndef MATPBR_PATH_H
+#define MATPBR_PATH_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MATPBR_PATH_VERSION 1
+#define MATPBR_PATH_MAX_BVH_DEPTH 40 /* node levels below the root the builder may create; the kernel's traversal stack has this many entries */
+#define MATPBR_PATH_MAX_MAX_DEPTH 16 /* largest `max_depth` matpbr_path_render accepts */
+#define MATPBR_PATH_NODE_BYTES 64    /* one node: both children's boxes (2 x 24 B) + two child words + two counts */
+#define MATPBR_PATH_TRI_BYTES 48     /* one triangle in leaf order: (v0, id) (e1, 0) (e2, 0) as float4; e1 x e2 faces the camera */
+
+enum {
+    MATPBR_PATH_OK = 0,
+    MATPBR_PATH_ERR_INVALID_ARG = -1,
+    MATPBR_PATH_ERR_LAUNCH = -3,
+    MATPBR_PATH_ERR_CAPACITY = -4,
+};
+
+int matpbr_path_version(void);
+const char* matpbr_path_strerror(int code);
+
+/* Upper bounds of the BVH buffers for `n_tri` triangles: *max_nodes nodes of MATPBR_PATH_NODE_BYTES, n_tri triangles of
+ * MATPBR_PATH_TRI_BYTES. */
+int matpbr_path_bvh_size(long n_tri, long* max_nodes);
+
+/* Binned-SAH BVH2 over triangles tri[n_tri,3] (int32 indices into vert[n_vert,3], float64) -> nodes (node 0 = root), triangles in
+ * leaf order.  Host only; `nodes` holds `max_nodes` nodes (matpbr_path_bvh_size), `tris` n_tri triangles.  Writes the node count,
+ * the deepest node level (<= MATPBR_PATH_MAX_BVH_DEPTH) and the number of leaves.  Triangles with an index outside the vertex
+ * array are an error. */
+int matpbr_path_bvh_build(const double* vert, long n_vert, const int32_t* tri, long n_tri, void* nodes, long max_nodes, void* tris,
+                          long* n_nodes, int* depth, long* n_leaves);
+
+/* Closest hit of N rays (origin o[N,3], direction d[N,3], hits with tmin < t < tmax) on the CPU, with the routine the kernel runs:
+ * t_hit[N] (tmax where there is no hit), tri_hit[N] = triangle index of the input mesh or -1. */
+int matpbr_path_trace_host(const void* nodes, const void* tris, const float* o, const float* d, long N, float tmin, float tmax,
+                           float* t_hit, int32_t* tri_hit);
+
+/* Importance-sampling tables of an equirectangular envmap env[He,We,3] (host, built in fp64, stored fp32): row_cdf[He+1] (marginal
+ * over rows of luminance x texel solid angle), col_cdf[He,We+1] (conditional over the columns of each row), pdf[He,We] = the
+ * solid-angle density of a direction in each texel's cell.  An envmap of zero luminance gets all-zero tables (no emitter
+ * sampling).  *total = sum of luminance x solid angle. */
+int matpbr_path_env_tables(const float* env, int He, int We, float* row_cdf, float* col_cdf, float* pdf, double* total);
+
+/* The render's emitter sampler on the CPU: u[N,4] -> dir[N,3], pdf_out[N], texel[N] (row * We + col; -1 without tables). */
+int matpbr_path_env_sample_host(const float* row_cdf, const float* col_cdf, const float* pdf, int He, int We, const float* u, long N,
+                                float* dir, float* pdf_out, int32_t* texel);
+
+/* The render: `spp` samples per pixel, accumulated in a fixed order per pixel (no atomics) and enqueued as launches of at most
+ * `spp_per_launch` samples; every split gives the same bits.  out[H,W,3] = linear radiance (mean over samples).  `max_depth` is
+ * Mitsuba's (1 = emission only, 2 = direct light with shadows, 4 = up to three surface vertices).  `nodes`/`tris` are the
+ * builder's output copied to the device; env + its three tables as matpbr_path_env_tables made them.  `rays` (nullable, [H,W]):
+ * the number of rays each pixel traced (camera, bounce and shadow rays) is ADDED to it. */
+int matpbr_path_render(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
+                       const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
+                       int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MATPBR_PATH_H */

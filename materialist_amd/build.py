@@ -74,5 +74,37 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
+# libmatpbr_path.so (the path-traced re-render, include/matpbr_path.h): a library of its own, so that the sources above -- and the
+# digest profiles/pmc_traffic.json is tied to -- stay untouched.  It includes matpbr_device.hpp for the BRDF arithmetic.
+PATH_LIB_PATH = os.path.join(_HERE, "libmatpbr_path.so")
+PATH_SOURCES = ["matpbr_path.hip"]
+PATH_HEADERS = [os.path.join("..", "..", "include", "matpbr_path.h"), "matpbr_device.hpp"]
+
+
+def path_is_stale() -> bool:
+    if not os.path.exists(PATH_LIB_PATH):
+        return True
+    t = os.path.getmtime(PATH_LIB_PATH)
+    deps = [os.path.join(CSRC, s) for s in PATH_SOURCES] + [os.path.normpath(os.path.join(CSRC, h)) for h in PATH_HEADERS] + [__file__]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_path_library(force: bool = False, verbose: bool = False) -> str:
+    """Compile matpbr_path.hip into materialist_amd/libmatpbr_path.so with the flags of libmatpbr.so (one source: one hipcc call).
+    Rebuilt when the source, a header or this recipe is newer than the library.  Cross-compiles without a GPU."""
+    if not force and not path_is_stale():
+        return PATH_LIB_PATH
+    tmp = PATH_LIB_PATH + f".tmp{os.getpid()}"                # a concurrent loader never sees a half-written library
+    cmd = [_hipcc(), *HIPCC_FLAGS, *[os.path.join(CSRC, s) for s in PATH_SOURCES], "-o", tmp]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)
+    if verbose:
+        print(res.stderr)
+    os.replace(tmp, PATH_LIB_PATH)
+    return PATH_LIB_PATH
+
+
 if __name__ == "__main__":
     print(build_library(force=True, verbose=True))
+    print(build_path_library(force=True, verbose=True))

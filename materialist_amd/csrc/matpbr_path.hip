@@ -1,0 +1,686 @@
+// matpbr_path.hip -- libmatpbr_path.so: the path-traced re-render of the depth mesh (include/matpbr_path.h).
+//
+//   * host: a binned-SAH BVH2 over the mesh's triangles (every node holds both children's boxes, so one 64-byte node read tests
+//     two boxes), triangles stored in leaf order as precomputed (v0, e1, e2); the envmap's importance-sampling tables (fp64 -> fp32);
+//   * device: one thread per pixel loops over its samples in order and accumulates them in a fixed order (no atomics: the image is
+//     bit-reproducible, and so is every split of a frame into launches); the traversal stack lives in LDS, one column per lane;
+//   * the closest-hit routine and the emitter sampler are __host__ __device__: the CPU entry points run the same code as the kernel.
+// The BRDF arithmetic is matpbr_device.hpp's (pixel_const, brdf_core, ggx_den_stable, frame, to_world), unchanged.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../include/matpbr_path.h"
+#include "matpbr_device.hpp"
+
+using namespace matpbr;
+
+namespace {
+
+constexpr int kMaxBvhDepth = MATPBR_PATH_MAX_BVH_DEPTH;
+constexpr int kStack = kMaxBvhDepth;   // at most one pushed sibling per inner level of the path from the root
+constexpr int kLeafMax = 4;            // triangles per leaf the builder aims for
+constexpr int kBins = 16;              // SAH bins per axis
+constexpr int kTileX = 16, kTileY = 8; // one workgroup = a 16 x 8 pixel tile (a wave = 16 x 4): neighbouring rays share nodes
+constexpr int kBlock = kTileX * kTileY;
+constexpr int kDims = 16;              // random dimensions reserved per path vertex (RNG counter layout below)
+
+// ---- node / triangle layout ------------------------------------------------------------------------------------------------
+// node = 4 x float4: box0 lo, box0 hi, box1 lo, box1 hi (12 floats), then child[2], count[2] as int.  count < 0: the child is the
+// inner node `child`; count >= 0: a leaf of triangles [child, child + count) (count 0 = an empty slot, only a root's).
+struct BNode {
+    float b[12];
+    int32_t child[2];
+    int32_t count[2];
+};
+static_assert(sizeof(BNode) == MATPBR_PATH_NODE_BYTES, "node layout");
+static_assert(3 * sizeof(float4) == MATPBR_PATH_TRI_BYTES, "triangle layout");
+
+__host__ __device__ inline float dot3h(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+__host__ __device__ inline void cross3(const float a[3], const float b[3], float c[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// slab test of one box: entry distance in `tn`; the exit distance is widened by 2 ulp-ish so that rounding never culls a box
+// the triangle test would hit
+__host__ __device__ inline bool box_hit(float lx, float ly, float lz, float hx, float hy, float hz, const float inv[3], const float oi[3],
+                                        float tmin, float tmax, float& tn) {
+    const float ax = lx * inv[0] - oi[0], bx = hx * inv[0] - oi[0];
+    const float ay = ly * inv[1] - oi[1], by = hy * inv[1] - oi[1];
+    const float az = lz * inv[2] - oi[2], bz = hz * inv[2] - oi[2];
+    const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin));
+    const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax)) * 1.0000004f;
+    tn = t0;
+    return t0 <= t1;
+}
+
+// Moller-Trumbore on (v0, e1, e2); updates t / k where tmin < t' < t
+__host__ __device__ inline void tri_test(const float4* tris, int k, const float o[3], const float d[3], float tmin, float& t, int& hit) {
+    const float4 A = tris[3 * k], B = tris[3 * k + 1], C = tris[3 * k + 2];
+    const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+    float pv[3];
+    cross3(d, e2, pv);
+    const float det = dot3h(e1, pv);
+    if (det == 0.0f) return;
+    const float idet = 1.0f / det;
+    const float tv[3] = {o[0] - A.x, o[1] - A.y, o[2] - A.z};
+    const float u = dot3h(tv, pv) * idet;
+    if (!(u >= 0.0f && u <= 1.0f)) return;
+    float qv[3];
+    cross3(tv, e1, qv);
+    const float v = dot3h(d, qv) * idet;
+    if (!(v >= 0.0f && u + v <= 1.0f)) return;
+    const float tt = dot3h(e2, qv) * idet;
+    if (tt > tmin && tt < t) { t = tt; hit = k; }
+}
+
+// Closest hit (ANY = false) or any hit (ANY = true, shadow rays) of the ray o + t d, tmin < t < t_in.  Returns the leaf-order index
+// of the triangle hit (-1: none) and its distance in t.  `stk` is the traversal stack (kStack entries): LDS on the device, an
+// array on the host.  Pushes beyond kStack are dropped: only a BVH deeper than the builder makes could reach that.
+template <bool ANY, class Stack>
+__host__ __device__ inline int trace(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float o[3], const float d[3],
+                                     float tmin, float& t, Stack& stk) {
+    float inv[3], oi[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float dc = fabsf(d[c]) < 1e-30f ? copysignf(1e-30f, d[c]) : d[c];
+        inv[c] = 1.0f / dc;
+        oi[c] = o[c] * inv[c];
+    }
+    int hit = -1, node = 0, sp = 0;
+    while (true) {
+        const float4* np = nodes + 4 * node;
+        const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3f = np[3];
+        const int4 q3 = *reinterpret_cast<const int4*>(&q3f);
+        float tn0, tn1;
+        bool h0 = box_hit(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, inv, oi, tmin, t, tn0);
+        bool h1 = box_hit(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, inv, oi, tmin, t, tn1);
+        if (h0 && q3.z >= 0) {
+            for (int k = q3.x, e = q3.x + q3.z; k < e; ++k) tri_test(tris, k, o, d, tmin, t, hit);
+            h0 = false;
+            if (ANY && hit >= 0) return hit;
+        }
+        if (h1 && q3.w >= 0) {
+            for (int k = q3.y, e = q3.y + q3.w; k < e; ++k) tri_test(tris, k, o, d, tmin, t, hit);
+            h1 = false;
+            if (ANY && hit >= 0) return hit;
+        }
+        if (h0 && h1) {
+            const bool first0 = tn0 <= tn1;
+            node = first0 ? q3.x : q3.y;
+            if (sp < kStack) stk[sp++] = first0 ? q3.y : q3.x;
+        } else if (h0) {
+            node = q3.x;
+        } else if (h1) {
+            node = q3.y;
+        } else {
+            if (sp == 0) break;
+            node = stk[--sp];
+        }
+    }
+    return hit;
+}
+
+struct HostStack {
+    int s[kStack];
+    int& operator[](int i) { return s[i]; }
+};
+struct LdsStack {  // entry i of this lane at p[i * kBlock]: the 64 lanes of a wave hit 64 consecutive words (no bank conflicts)
+    int* p;
+    __device__ int& operator[](int i) { return p[i * kBlock]; }
+};
+
+// ---- RNG: the PCG hash (Jarzynski & Olano 2020, "Hash Functions for GPU Rendering"), chained over the counter ---------------
+// u(seed, pixel, sample, vertex, dim) = (h >> 8) * 2^-24,  h = pcg(pcg(pcg(pcg(seed) + pixel) + sample) + vertex * 16 + dim)
+// (uint32 arithmetic throughout; tests/test_gpu_path.py restates it in numpy)
+__host__ __device__ inline uint32_t pcg_hash(uint32_t v) {
+    const uint32_t s = v * 747796405u + 2891336453u;
+    const uint32_t w = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
+    return (w >> 22u) ^ w;
+}
+__host__ __device__ inline float rng_u(uint32_t base, int vertex, int dim) {
+    return (float)(pcg_hash(base + (uint32_t)(vertex * kDims + dim)) >> 8) * 5.9604644775390625e-8f;
+}
+// dims of a vertex: 0-1 pixel jitter (vertex 0), 2-5 emitter sample (row, column, cos theta, phi), 6-8 BSDF sample (lobe, u0, u1)
+
+// ---- envmap: equirectangular, theta = acos(y), phi = atan2(x, -z) in [0, 2 pi) (materialist_amd/sh.py) --------------------
+__host__ __device__ inline int env_texel(const float d[3], int He, int We) {
+    const float kPiF = 3.14159265358979323846f;
+    const float th = acosf(fminf(fmaxf(d[1], -1.0f), 1.0f));
+    float ph = atan2f(d[0], -d[2]);
+    if (ph < 0.0f) ph += 2.0f * kPiF;
+    const int row = std::min(std::max((int)(th * ((float)He / kPiF)), 0), He - 1);
+    const int col = std::min(std::max((int)(ph * ((float)We / (2.0f * kPiF))), 0), We - 1);
+    return row * We + col;
+}
+// largest i in [0, n) with cdf[i] <= u (cdf[0] = 0, cdf[n] = 1): zero-weight entries are never returned
+__host__ __device__ inline int cdf_find(const float* cdf, int n, float u) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid] <= u) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// emitter sample: texel by luminance x solid angle (row from the marginal, column from the row's conditional), then uniform in
+// cos theta and phi inside the texel's cell.  Returns the texel; dir / pdf (solid angle) written.
+__host__ __device__ inline int env_sample(const float* row_cdf, const float* col_cdf, const float* pdf_tab, int He, int We, float u0, float u1,
+                                          float u2, float u3, float dir[3], float& pdf) {
+    const float kPiF = 3.14159265358979323846f;
+    const int row = cdf_find(row_cdf, He, u0);
+    const int col = cdf_find(col_cdf + (long)row * (We + 1), We, u1);
+    const float c0 = cosf((float)row * (kPiF / (float)He)), c1 = cosf((float)(row + 1) * (kPiF / (float)He));
+    const float ct = c0 + (c1 - c0) * u2;
+    const float st = sqrtf(fmaxf(1.0f - ct * ct, 0.0f));
+    const float ph = ((float)col + u3) * (2.0f * kPiF / (float)We);
+    const float sp = sinf(ph), cp = cosf(ph);
+    dir[0] = st * sp; dir[1] = ct; dir[2] = -st * cp;
+    pdf = pdf_tab[row * We + col];
+    return row * We + col;
+}
+
+// ---- BSDF: MatDiffBSDF.eval_brdf / sample_brdf (myutils/mi_plugin.py:1296-1341,1372-1427) ------------------------------------
+// These restate matpbr_kernels.hip's lane_setup and the sampler inside sample_brdf_kernel (the same formulas, the same
+// matpbr_device.hpp helpers).  They are copied rather than shared because moving them into a header would change the sources
+// build.sources_digest() hashes (and with it the traffic profile bench.py checks); tests/test_gpu_path.py pins them against the
+// fp64 oracle's sample_brdf / eval_brdf.
+struct PLane {
+    PixelConst<float> pc;
+    float NoL_raw, NoH, VoH, den;
+};
+__device__ __forceinline__ void path_lane(PLane& ln, const float wi[3], const float wo[3], const float n[3], const float a[3], float r, float m) {
+    float h[3] = {wi[0] + wo[0], wi[1] + wo[1], wi[2] + wo[2]};
+    const float il = rsq(dot3(h, h));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) h[c] *= il;
+    pixel_const<float>(ln.pc, a, r, m, dot3(n, wo));
+    ln.NoL_raw = dot3(n, wi);
+    ln.VoH = fmaxf(dot3(wo, h), 0.0f);
+    const float nh_raw = dot3(n, h);
+    ln.NoH = fmaxf(nh_raw, 0.0f);
+    const float nn = dot3(n, n);
+    if (fabsf(nn - 1.0f) < 1e-5f && nh_raw > 0.0f) {
+        const float cx = n[1] * h[2] - n[2] * h[1], cy = n[2] * h[0] - n[0] * h[2], cz = n[0] * h[1] - n[1] * h[0];
+        ln.den = ggx_den_stable(ln.pc, fmaf(cx, cx, fmaf(cy, cy, cz * cz)));
+    } else {
+        ln.den = ggx_den_literal(ln.pc, ln.NoH);
+    }
+}
+// eval_brdf(wi, wo) -> f (RGB, with the trailing cosine) and the mixture pdf
+__device__ __forceinline__ void path_eval(const float wi[3], const float wo[3], const float n[3], const float a[3], float r, float m, float f[3],
+                                          float& pdf) {
+    PLane ln;
+    path_lane(ln, wi, wo, n, a, r, m);
+    BrdfState<float> st;
+    brdf_core(ln.pc, ln.NoL_raw, ln.NoH, ln.VoH, ln.den, st, f, pdf);
+}
+// sample_brdf: lobe by sample1 > 0.5 (diffuse) else GGX; weight = f/(pdf + 1e-6) where pdf > 1e-6, else 0
+__device__ __forceinline__ void path_sample(float sample1, float u0, float u1, const float wo[3], const float n[3], const float a[3], float r,
+                                            float m, float wi[3], float w[3], float& pdf_out) {
+    float s[3], t[3];
+    frame(n, s, t);
+    float sp, cp;
+    sincosf(2.0f * kPi * u1, &sp, &cp);
+    float sin2_h = -1.0f, cos_h = 0.0f;
+    if (sample1 > 0.5f) {  // diffuse lobe (mi_plugin.py:1328-1329)
+        const float st_ = fsqrt(fmaxf(u0, 0.0f)), ct = fsqrt(fmaxf(1.0f - u0, 0.0f));
+        to_world(s, t, n, st_ * cp, st_ * sp, ct, wi);
+    } else {  // GGX lobe (mi_plugin.py:1330-1331)
+        const float alpha2 = pow4(r);
+        const float q = rcp(fmaf(u0, alpha2 - 1.0f, 1.0f));
+        const float ct = fsqrt(fmaxf((1.0f - u0) * q, 0.0f)), st_ = fsqrt(fmaxf(u0 * alpha2 * q, 0.0f));
+        float wh[3];
+        to_world(s, t, n, st_ * cp, st_ * sp, ct, wh);
+        const float d = 2.0f * dot3(wo, wh);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) wi[c] = fmaf(d, wh[c], -wo[c]);
+        const float il = rsq(dot3(wi, wi));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) wi[c] *= il;
+        if (d > 0.0f) { sin2_h = u0 * alpha2 * q; cos_h = ct; }
+    }
+    PLane ln;
+    path_lane(ln, wi, wo, n, a, r, m);
+    if (sin2_h >= 0.0f) {  // same value as the literal form, without the fp32 cancellation at the GGX peak
+        ln.NoH = cos_h;
+        ln.den = ggx_den_stable(ln.pc, sin2_h);
+    }
+    BrdfState<float> st;
+    float f[3], p;
+    brdf_core(ln.pc, ln.NoL_raw, ln.NoH, ln.VoH, ln.den, st, f, p);
+    const float ip = p > 1e-6f ? 1.0f / (p + 1e-6f) : 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w[c] = f[c] * ip;
+    pdf_out = p > 0.0f ? p : 0.0f;
+}
+
+// power heuristic (Mitsuba 3 path: mis_weight), 0 where it is not finite
+__device__ __forceinline__ float mis_weight(float a, float b) {
+    const float a2 = a * a, w = a2 / (a2 + b * b);
+    return isfinite(w) ? w : 0.0f;
+}
+
+struct PathArgs {
+    const float4* nodes;
+    const float4* tris;
+    const float *a, *r, *m;
+    const float *env, *row_cdf, *col_cdf, *env_pdf;
+    float* out;
+    uint32_t* rays;        // nullable: rays traced per pixel, added to (a count for reporting rates)
+    int H, W, He, We, spp, max_depth;
+    float f_pix, cx, cy;   // camera rays: ((x - cx)/f_pix, -(y - cy)/f_pix, -1)
+    float f_ndc, aspect;   // world_to_screen (a6): 1/tan(fov/2), W/H
+    uint32_t seed_hash;    // pcg(seed)
+};
+
+// spawn offset along the (camera-side) face normal, relative to the point's magnitude
+__device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1.0f + fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]))); }
+
+// samples [s0, s1) of every pixel added to out (first: start from 0; last: divide by spp)
+__global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last) {
+    __shared__ int s_stack[kStack * kBlock];
+    const int tid = threadIdx.y * kTileX + threadIdx.x;
+    const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
+    if (i >= q.H || j >= q.W) return;   // no barriers below: each lane's stack column is its own
+    LdsStack stk{s_stack + tid};
+    const long pix = (long)i * q.W + j;
+    const bool have_tab = q.row_cdf[q.He] > 0.0f;   // an envmap of zero luminance has no emitter sampling
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (!first) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = q.out[3 * pix + c];
+    }
+    const uint32_t pix_hash = pcg_hash(q.seed_hash + (uint32_t)pix);
+    uint32_t n_rays = 0;
+    for (int s = s0; s < s1; ++s) {
+        const uint32_t base = pcg_hash(pix_hash + (uint32_t)s);
+        float L[3] = {0.0f, 0.0f, 0.0f}, thr[3] = {1.0f, 1.0f, 1.0f};
+        // camera ray through a uniformly jittered position of the pixel (box filter)
+        const float x = (float)j - 0.5f + rng_u(base, 0, 0), y = (float)i - 0.5f + rng_u(base, 0, 1);
+        float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {(x - q.cx) / q.f_pix, -(y - q.cy) / q.f_pix, -1.0f};
+        {
+            const float il = rsq(dot3(d, d));
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] *= il;
+        }
+        float prev_pdf = 0.0f;
+        for (int depth = 0;; ++depth) {
+            float t = FLT_MAX;
+            ++n_rays;
+            const int k = trace<false>(q.nodes, q.tris, o, d, 0.0f, t, stk);
+            if (k < 0) {   // escaped: the envmap, MIS-weighted against emitter sampling after a BSDF sample
+                const int tx = env_texel(d, q.He, q.We);
+                const float w = depth == 0 ? 1.0f : mis_weight(prev_pdf, have_tab ? q.env_pdf[tx] : 0.0f);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) L[c] += thr[c] * (q.env[3 * tx + c] * w);
+                break;
+            }
+            if (depth + 1 >= q.max_depth) break;   // Mitsuba's active_next: the surfaces emit nothing
+            const float4 B = q.tris[3 * k + 1], C = q.tris[3 * k + 2];
+            const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+            float n[3];
+            cross3(e1, e2, n);   // the face normal, oriented to the camera side by the builder
+            {
+                const float il = rsq(dot3(n, n));
+#pragma unroll
+                for (int c = 0; c < 3; ++c) n[c] *= il;
+            }
+            const float wo[3] = {-d[0], -d[1], -d[2]};
+            if (!(dot3(n, wo) > 0.0f)) break;      // a hit on the back of a triangle ends the path
+            float p[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p[c] = fmaf(t, d[c], o[c]);
+            // material: the texel the hit point projects to (a6 world_to_screen, floor, clamped to the image: MatDiffBSDF)
+            const float ndc0 = (q.f_ndc / q.aspect) * (-p[0]) / p[2], ndc1 = q.f_ndc * p[1] / p[2];
+            const float sx = (ndc0 + 1.0f) * 0.5f * (float)q.W, sy = (ndc1 + 1.0f) * 0.5f * (float)q.H;
+            const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
+            const long tp = (long)ty * q.W + tx;
+            const float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+            const float eps = spawn_eps(p);
+            float po[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
+            // emitter sample with a shadow ray
+            if (have_tab) {
+                float wl[3], pdf_e;
+                const int te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
+                                          rng_u(base, depth, 4), rng_u(base, depth, 5), wl, pdf_e);
+                if (pdf_e > 0.0f && dot3(n, wl) > 0.0f) {
+                    float f[3], pdf_b;
+                    path_eval(wl, wo, n, av, rv, mv, f, pdf_b);
+                    if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
+                        float ts = FLT_MAX;
+                        ++n_rays;
+                        if (trace<true>(q.nodes, q.tris, po, wl, 0.0f, ts, stk) < 0) {
+                            const float w = mis_weight(pdf_e, pdf_b) / pdf_e;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) L[c] += thr[c] * (f[c] * (q.env[3 * te + c] * w));
+                        }
+                    }
+                }
+            }
+            // BSDF sample: the next ray
+            float wi[3], wgt[3], pdf_s;
+            path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, wgt, pdf_s);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) thr[c] *= wgt[c];
+            if (!(thr[0] > 0.0f || thr[1] > 0.0f || thr[2] > 0.0f)) break;
+            prev_pdf = pdf_s;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { o[c] = po[c]; d[c] = wi[c]; }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += L[c];
+    }
+    const float sc = last ? 1.0f / (float)q.spp : 1.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q.out[3 * pix + c] = last ? acc[c] * sc : acc[c];
+    if (q.rays) q.rays[pix] += n_rays;
+}
+
+// ---- host: binned-SAH builder --------------------------------------------------------------------------------------------
+struct Box {
+    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    void grow(const Box& b) {
+        for (int c = 0; c < 3; ++c) { lo[c] = std::min(lo[c], b.lo[c]); hi[c] = std::max(hi[c], b.hi[c]); }
+    }
+    double area() const {
+        if (lo[0] > hi[0]) return 0.0;
+        const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+        return dx * dy + dy * dz + dz * dx;
+    }
+};
+
+struct Builder {
+    std::vector<Box> tb;            // per-triangle box (padded)
+    std::vector<float> cen;         // per-triangle centroid [3N]
+    std::vector<int32_t> idx;       // permutation: leaf order
+    BNode* nodes;
+    long max_nodes, n_nodes = 0, n_leaves = 0;
+    int depth = 0;
+
+    Box range_box(int b, int e) const {
+        Box r;
+        for (int k = b; k < e; ++k) r.grow(tb[idx[k]]);
+        return r;
+    }
+    // split [b, e) in two non-empty halves: the binned-SAH plane, or the middle when every centroid coincides
+    int split(int b, int e) {
+        float clo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, chi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+        for (int k = b; k < e; ++k)
+            for (int c = 0; c < 3; ++c) { clo[c] = std::min(clo[c], cen[3 * idx[k] + c]); chi[c] = std::max(chi[c], cen[3 * idx[k] + c]); }
+        double best = DBL_MAX;
+        int best_axis = -1, best_plane = 0;
+        for (int ax = 0; ax < 3; ++ax) {
+            const float ext = chi[ax] - clo[ax];
+            if (!(ext > 0.0f)) continue;
+            const float scale = (float)kBins / ext;
+            Box bb[kBins];
+            int bn[kBins] = {0};
+            for (int k = b; k < e; ++k) {
+                const int t = idx[k];
+                const int bi = std::min(kBins - 1, (int)((cen[3 * t + ax] - clo[ax]) * scale));
+                bb[bi].grow(tb[t]);
+                ++bn[bi];
+            }
+            double right_cost[kBins];
+            Box acc;
+            int cnt = 0;
+            for (int p = kBins - 1; p > 0; --p) {   // plane p: bins [0,p) left, [p,kBins) right
+                acc.grow(bb[p]);
+                cnt += bn[p];
+                right_cost[p] = cnt ? acc.area() * cnt : 0.0;
+            }
+            Box lacc;
+            int lcnt = 0;
+            for (int p = 1; p < kBins; ++p) {
+                lacc.grow(bb[p - 1]);
+                lcnt += bn[p - 1];
+                if (lcnt == 0 || lcnt == e - b) continue;
+                const double cost = lacc.area() * lcnt + right_cost[p];
+                if (cost < best) { best = cost; best_axis = ax; best_plane = p; }
+            }
+        }
+        if (best_axis < 0) return b + (e - b) / 2;
+        const float lo = clo[best_axis], scale = (float)kBins / (chi[best_axis] - clo[best_axis]);
+        int32_t* mid = std::partition(idx.data() + b, idx.data() + e, [&](int32_t t) {
+            return std::min(kBins - 1, (int)((cen[3 * t + best_axis] - lo) * scale)) < best_plane;
+        });
+        return (int)(mid - idx.data());
+    }
+    struct Item { long node; int slot, b, e, level; };
+    bool build(int N) {
+        if (max_nodes < 1) return false;
+        n_nodes = 1;
+        std::memset(&nodes[0], 0, sizeof(BNode));
+        std::vector<Item> work;
+        if (N <= kLeafMax) {
+            work.push_back({0, 0, 0, N, 1});
+            work.push_back({0, 1, N, N, 1});
+        } else {
+            const int m = split(0, N);
+            work.push_back({0, 1, m, N, 1});
+            work.push_back({0, 0, 0, m, 1});
+        }
+        while (!work.empty()) {
+            const Item it = work.back();
+            work.pop_back();
+            depth = std::max(depth, it.level);
+            BNode& nd = nodes[it.node];
+            const Box bx = range_box(it.b, it.e);
+            if (it.e == it.b) {   // empty slot (root of a mesh of <= kLeafMax triangles): a point box, a leaf without triangles
+                for (int c = 0; c < 6; ++c) nd.b[6 * it.slot + c] = 0.0f;
+            } else {
+                for (int c = 0; c < 3; ++c) { nd.b[6 * it.slot + c] = bx.lo[c]; nd.b[6 * it.slot + 3 + c] = bx.hi[c]; }
+            }
+            if (it.e - it.b <= kLeafMax || it.level >= kMaxBvhDepth) {
+                nd.child[it.slot] = it.b;
+                nd.count[it.slot] = it.e - it.b;
+                ++n_leaves;
+                continue;
+            }
+            if (n_nodes >= max_nodes) return false;
+            const long q = n_nodes++;
+            nd.child[it.slot] = (int32_t)q;
+            nd.count[it.slot] = -1;
+            std::memset(&nodes[q], 0, sizeof(BNode));
+            const int m = split(it.b, it.e);
+            work.push_back({q, 1, m, it.e, it.level + 1});
+            work.push_back({q, 0, it.b, m, it.level + 1});
+        }
+        return true;
+    }
+};
+
+}  // namespace
+
+// =================================================================================================================================
+// C ABI
+// =================================================================================================================================
+extern "C" {
+
+int matpbr_path_version(void) { return MATPBR_PATH_VERSION; }
+
+const char* matpbr_path_strerror(int code) {
+    switch (code) {
+        case MATPBR_PATH_OK: return "ok";
+        case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, or max_depth outside 1..16)";
+        case MATPBR_PATH_ERR_LAUNCH: return "HIP kernel launch failed";
+        case MATPBR_PATH_ERR_CAPACITY: return "node buffer smaller than matpbr_path_bvh_size() asks for";
+        default: return "unknown error";
+    }
+}
+
+int matpbr_path_bvh_size(long n_tri, long* max_nodes) {
+    if (n_tri < 0 || n_tri > INT32_MAX / 3 || !max_nodes) return MATPBR_PATH_ERR_INVALID_ARG;
+    *max_nodes = std::max(1L, n_tri);   // inner nodes of a binary tree with non-empty leaves: <= n_tri - 1 (+ the root)
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_bvh_build(const double* vert, long n_vert, const int32_t* tri, long n_tri, void* nodes, long max_nodes, void* tris,
+                          long* n_nodes, int* depth, long* n_leaves) {
+    if (!vert || !tri || !nodes || !tris || !n_nodes || !depth || !n_leaves || n_vert <= 0 || n_tri < 0 || n_tri > INT32_MAX / 3)
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    long need = 0;
+    matpbr_path_bvh_size(n_tri, &need);
+    if (max_nodes < need) return MATPBR_PATH_ERR_CAPACITY;
+    for (long k = 0; k < 3 * n_tri; ++k)
+        if (tri[k] < 0 || tri[k] >= n_vert) return MATPBR_PATH_ERR_INVALID_ARG;
+    const int N = (int)n_tri;
+    double S = 0.0;   // scene scale: boxes are padded by 1e-6 of it so that fp32 rounding of (v0, e1, e2) stays inside
+    for (long k = 0; k < 3 * n_vert; ++k) S = std::max(S, std::fabs(vert[k]));
+    const float pad = (float)(1e-6 * S);
+    Builder bld;
+    bld.nodes = static_cast<BNode*>(nodes);
+    bld.max_nodes = max_nodes;
+    bld.tb.resize(N);
+    bld.cen.resize(3 * (size_t)N);
+    bld.idx.resize(N);
+    for (int t = 0; t < N; ++t) {
+        Box b;
+        for (int c = 0; c < 3; ++c) {
+            double lo = DBL_MAX, hi = -DBL_MAX;
+            for (int v = 0; v < 3; ++v) { lo = std::min(lo, vert[3 * (long)tri[3 * t + v] + c]); hi = std::max(hi, vert[3 * (long)tri[3 * t + v] + c]); }
+            b.lo[c] = (float)lo - pad;
+            b.hi[c] = (float)hi + pad;
+            bld.cen[3 * t + c] = (float)(0.5 * (lo + hi));
+        }
+        bld.tb[t] = b;
+        bld.idx[t] = t;
+    }
+    if (!bld.build(N)) return MATPBR_PATH_ERR_CAPACITY;
+    float4* T = static_cast<float4*>(tris);
+    for (int k = 0; k < N; ++k) {
+        const int t = bld.idx[k];
+        const double* v0 = vert + 3 * (long)tri[3 * t];
+        const double* v1 = vert + 3 * (long)tri[3 * t + 1];
+        const double* v2 = vert + 3 * (long)tri[3 * t + 2];
+        double e1[3], e2[3];
+        for (int c = 0; c < 3; ++c) { e1[c] = v1[c] - v0[c]; e2[c] = v2[c] - v0[c]; }
+        const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+        if (nx * v0[0] + ny * v0[1] + nz * v0[2] > 0.0) std::swap(e1, e2);   // e1 x e2 faces the camera at the origin
+        int32_t id = t;
+        float idf;
+        std::memcpy(&idf, &id, 4);
+        T[3 * k] = make_float4((float)v0[0], (float)v0[1], (float)v0[2], idf);
+        T[3 * k + 1] = make_float4((float)e1[0], (float)e1[1], (float)e1[2], 0.0f);
+        T[3 * k + 2] = make_float4((float)e2[0], (float)e2[1], (float)e2[2], 0.0f);
+    }
+    *n_nodes = bld.n_nodes;
+    *depth = bld.depth;
+    *n_leaves = bld.n_leaves;
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_trace_host(const void* nodes, const void* tris, const float* o, const float* d, long N, float tmin, float tmax,
+                           float* t_hit, int32_t* tri_hit) {
+    if (!nodes || !tris || !o || !d || !t_hit || !tri_hit || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    const float4* T = static_cast<const float4*>(tris);
+    for (long k = 0; k < N; ++k) {
+        HostStack stk;
+        float t = tmax;
+        const int h = trace<false>(static_cast<const float4*>(nodes), T, o + 3 * k, d + 3 * k, tmin, t, stk);
+        t_hit[k] = t;
+        int32_t id = -1;
+        if (h >= 0) std::memcpy(&id, &T[3 * h].w, 4);
+        tri_hit[k] = id;
+    }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_env_tables(const float* env, int He, int We, float* row_cdf, float* col_cdf, float* pdf, double* total) {
+    if (!env || !row_cdf || !col_cdf || !pdf || !total || He <= 0 || We <= 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    const double pi = 3.14159265358979323846;
+    std::vector<double> w((size_t)He * We), row_w(He, 0.0);
+    double tot = 0.0;
+    for (int r = 0; r < He; ++r) {
+        const double omega = (std::cos(r * pi / He) - std::cos((r + 1) * pi / He)) * (2.0 * pi / We);   // sh.envmap_solid_angles
+        for (int c = 0; c < We; ++c) {
+            const float* e = env + 3 * ((size_t)r * We + c);
+            const double lum = std::max(0.0, 0.2126 * e[0] + 0.7152 * e[1] + 0.0722 * e[2]);
+            w[(size_t)r * We + c] = lum;
+            row_w[r] += lum * omega;
+        }
+        tot += row_w[r];
+    }
+    *total = tot;
+    if (!(tot > 0.0) || !std::isfinite(tot)) {
+        std::fill(row_cdf, row_cdf + He + 1, 0.0f);
+        std::fill(col_cdf, col_cdf + (size_t)He * (We + 1), 0.0f);
+        std::fill(pdf, pdf + (size_t)He * We, 0.0f);
+        return MATPBR_PATH_OK;
+    }
+    double run = 0.0;
+    row_cdf[0] = 0.0f;
+    for (int r = 0; r < He; ++r) {
+        run += row_w[r];
+        row_cdf[r + 1] = (float)(run / tot);
+        float* cc = col_cdf + (size_t)r * (We + 1);
+        double rs = 0.0, rsum = 0.0;
+        for (int c = 0; c < We; ++c) rsum += w[(size_t)r * We + c];
+        cc[0] = 0.0f;
+        for (int c = 0; c < We; ++c) {
+            rs += w[(size_t)r * We + c];
+            cc[c + 1] = rsum > 0.0 ? (float)(rs / rsum) : (float)(c + 1) / (float)We;
+            pdf[(size_t)r * We + c] = (float)(w[(size_t)r * We + c] / tot);
+        }
+        cc[We] = 1.0f;
+    }
+    row_cdf[He] = 1.0f;
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_env_sample_host(const float* row_cdf, const float* col_cdf, const float* pdf, int He, int We, const float* u, long N,
+                                float* dir, float* pdf_out, int32_t* texel) {
+    if (!row_cdf || !col_cdf || !pdf || !u || !dir || !pdf_out || !texel || He <= 0 || We <= 0 || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    const bool have = row_cdf[He] > 0.0f;
+    for (long k = 0; k < N; ++k) {
+        if (!have) {
+            dir[3 * k] = dir[3 * k + 1] = dir[3 * k + 2] = 0.0f;
+            pdf_out[k] = 0.0f;
+            texel[k] = -1;
+            continue;
+        }
+        texel[k] = env_sample(row_cdf, col_cdf, pdf, He, We, u[4 * k], u[4 * k + 1], u[4 * k + 2], u[4 * k + 3], dir + 3 * k, pdf_out[k]);
+    }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_render(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
+                       const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
+                       int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream) {
+    if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !out || H <= 0 || W <= 0 || He <= 0 || We <= 0 ||
+        spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    PathArgs q{};
+    q.nodes = static_cast<const float4*>(nodes);
+    q.tris = static_cast<const float4*>(tris);
+    q.a = a; q.r = r; q.m = m;
+    q.env = env; q.row_cdf = row_cdf; q.col_cdf = col_cdf; q.env_pdf = env_pdf;
+    q.out = out;
+    q.rays = rays;
+    q.H = H; q.W = W; q.He = He; q.We = We; q.spp = spp; q.max_depth = max_depth;
+    const double th = std::tan(0.5 * (double)fov_x_deg * 3.14159265358979323846 / 180.0);
+    q.f_pix = (float)((0.5 * W) / th);                       // f = (W/2)/tan(fov/2), c = (W-1)/2, (H-1)/2
+    q.cx = 0.5f * (float)(W - 1);
+    q.cy = 0.5f * (float)(H - 1);
+    q.f_ndc = (float)(1.0 / th);                             // perspective_projection_matrix (mi_plugin.py:585-595)
+    q.aspect = (float)W / (float)H;
+    q.seed_hash = pcg_hash(seed);
+    const dim3 grid((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((H + kTileY - 1) / kTileY));
+    for (int s0 = 0; s0 < spp; s0 += spp_per_launch) {
+        const int s1 = std::min(spp, s0 + spp_per_launch);
+        hipLaunchKernelGGL(path_kernel, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, s0 == 0 ? 1 : 0, s1 == spp ? 1 : 0);
+        if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    return MATPBR_PATH_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,9 @@ frame is a 75-term dot product per pixel (`matpbr_relight`, HBM-bound).  Rolling
 SH rotation about +y by the same angle (`sh.rotate_y_matrix`), so no envmap is ever re-projected or written to disk.
 Material editing inside `best_results/mask.png` (`edit=` of `render_w_mi`, :143-181) is applied to the maps before the
 transfer is computed.  Object insertion (`--mode oi`, :100-141,207-237) needs extra meshes and is not part of this build.
+`integrator="path"` renders instead with the path tracer (materialist_amd/pathtrace.py), the integrator the
+reference's final images come from: the `.ply` mesh, shadows, inter-reflection, the envmap's texels as the light; rolling frames
+roll the envmap's texel columns.
 """
 from __future__ import annotations
 
@@ -157,15 +160,49 @@ def _scene_normal(scene_dir: str, mat: Dict[str, torch.Tensor], save_name: str, 
     return ops.normals_from_depth(torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(device))
 
 
+def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], device):
+    """PathTracer on the scene's `<save_name>.ply`; without one, the mesh the pipeline would write (depthPred.exr -> 2 max - d,
+    mesh_mask.png pixels removed, mesh.reference_mesh: inverse_img_w_mi.py:721-727)."""
+    from . import mesh as _mesh
+    from .pathtrace import PathTracer
+    from .render import DEFAULT_FOV
+
+    H, W = mat["albedo"].shape[0], mat["albedo"].shape[1]
+    ply = os.path.join(scene_dir, f"{save_name}.ply")
+    if os.path.exists(ply):
+        V, T = _mesh.read_ply(ply)
+    else:
+        depth = read_exr(os.path.join(scene_dir, "depthPred.exr"))[..., 0]
+        depth = np.array(2 * depth.max() - depth, dtype=np.float32)
+        mm = _mesh_mask(scene_dir)
+        if mm is not None:
+            depth[mm.numpy()] = 0.0
+        rm = _mesh.reference_mesh(depth, DEFAULT_FOV)
+        V, T = rm["vertices"], rm["triangles"]
+    return PathTracer(V, T, H, W, DEFAULT_FOV, device=device)
+
+
+def _check_integrator(integrator: str) -> None:
+    if integrator not in ("sh", "path"):
+        raise ValueError(f"integrator must be 'sh' or 'path', got {integrator!r}")
+
+
 def render_real(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
-                spp: int = 64, device="cuda", edit: Optional[Dict[str, object]] = None) -> str:
-    """render_final.py:148-203,241-260: one re-render under `env_path` -> mi_<name>_<env>_<edit flag>.exr / .png."""
+                spp: int = 64, device="cuda", edit: Optional[Dict[str, object]] = None, integrator: str = "sh", max_depth: int = 4,
+                seed: int = 0) -> str:
+    """render_final.py:148-203,241-260: one re-render under `env_path` -> mi_<name>_<env>_<edit flag>.exr / .png.
+    integrator "sh": the deterministic render (SH25 light, direct, unshadowed); "path": the path tracer, `max_depth` / `seed`."""
+    _check_integrator(integrator)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
     edit_flag = apply_edit(mat, edit)
-    rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))
-    img = rl.frames(envmap_to_light(load_image(env_path))[None])[0]
+    if integrator == "path":
+        img = _path_tracer(scene_dir, save_name, mat, device).render(mat["albedo"], mat["roughness"], mat["metallic"],
+                                                                     load_image(env_path), spp, max_depth, seed)
+    else:
+        rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))
+        img = rl.frames(envmap_to_light(load_image(env_path))[None])[0]
     env_id = os.path.basename(env_path)[:-4]
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
@@ -177,20 +214,27 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
 
 def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int = 36, rotation_step: float = 10.0,
                           input_path: Optional[str] = None, save_path: Optional[str] = None, spp: int = 64, device="cuda",
-                          write_frames: bool = True, edit: Optional[Dict[str, object]] = None) -> Dict[str, object]:
-    """render_final.py:300-418: `frames` renders, the envmap rolled by int(angle/360*W) columns per frame."""
+                          write_frames: bool = True, edit: Optional[Dict[str, object]] = None, integrator: str = "sh",
+                          max_depth: int = 4, seed: int = 0) -> Dict[str, object]:
+    """render_final.py:300-418: `frames` renders, the envmap rolled by int(angle/360*W) columns per frame.  integrator "sh": the
+    rolled light is the SH rotation of the projected envmap; "path": the path tracer renders the rolled texels themselves."""
+    _check_integrator(integrator)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
     env = load_image(env_path)
     We = env.shape[1]
     light0 = envmap_to_light(env)
-    lights = []
-    for f in range(frames):
-        shift = int((f * rotation_step / 360.0) * We)                # rotate_envmap (:290-298)
-        lights.append(_sh.rotate_y_matrix(2 * np.pi * shift / We) @ light0)
+    shifts = [int((f * rotation_step / 360.0) * We) for f in range(frames)]   # rotate_envmap (:290-298)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
     apply_edit(mat, edit)
-    rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))
+    if integrator == "path":
+        pt = _path_tracer(scene_dir, save_name, mat, device)
+        render_frames = lambda f0, f1: torch.stack([pt.render(mat["albedo"], mat["roughness"], mat["metallic"], np.roll(env, shifts[f], axis=1),
+                                                              spp, max_depth, seed) for f in range(f0, f1)])
+    else:
+        lights = [_sh.rotate_y_matrix(2 * np.pi * s / We) @ light0 for s in shifts]
+        rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))
+        render_frames = lambda f0, f1: rl.frames(np.stack(lights[f0:f1]))
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     anim_dir = os.path.join(out_dir, "rolling_envmap_animation")
     os.makedirs(anim_dir, exist_ok=True)
@@ -198,7 +242,7 @@ def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int =
     paths: List[str] = []
     imgs = []
     for f0 in range(0, frames, 24):                                  # matpbr_relight's chunk: the transfer is read once per 24 frames
-        batch = rl.frames(np.stack(lights[f0:f0 + 24]))
+        batch = render_frames(f0, min(f0 + 24, frames))
         if write_frames:
             srgb = _loss.linear_to_srgb(batch.clamp_min(0)).clamp(0, 1).cpu().numpy()
             for k in range(srgb.shape[0]):

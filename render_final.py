@@ -22,6 +22,11 @@ def parse_args(argv=None):
                     help="HSV shift of the albedo inside best_results/mask.png (the reference's `edit` dict, hard-wired to None in its CLI)")
     ap.add_argument("--edit_roughness", type=float, default=None, help="constant roughness inside the mask")
     ap.add_argument("--edit_metallic", type=float, default=None, help="constant metallic inside the mask")
+    ap.add_argument("--integrator", choices=("sh", "path"), default="sh",
+                    help="sh: the deterministic render (direct light under SH25, no shadows); path: the path tracer on the scene's .ply "
+                         "(Mitsuba's `path` as the reference renders its final images: shadows, inter-reflection, the envmap's texels)")
+    ap.add_argument("--max_depth", type=int, default=4, help="--integrator path: Mitsuba's max_depth (1 emission, 2 direct + shadows, 4 the reference's)")
+    ap.add_argument("--seed", type=int, default=0, help="--integrator path: random seed")
     return ap.parse_args(argv)
 
 
@@ -30,10 +35,12 @@ def main(argv=None):
     from materialist_amd import relight
 
     edit = {"albedo": a.edit_albedo, "roughness": a.edit_roughness, "metallic": a.edit_metallic}
+    it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed}
     if a.mode == "real":
-        print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit))
+        print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it))
     elif a.mode == "rolling":
-        res = relight.render_rolling_envmap(a.save_name, a.env_path, a.frames, a.rotation_step, a.input_path, a.save_path, a.spp, edit=edit)
+        res = relight.render_rolling_envmap(a.save_name, a.env_path, a.frames, a.rotation_step, a.input_path, a.save_path, a.spp, edit=edit,
+                                            **it)
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
         raise NotImplementedError("object insertion (render_final.py:100-141,207-237) is not part of this build")

@@ -1,0 +1,387 @@
+"""The path-traced re-render on the GPU (libmatpbr_path.so): per-path parity with an fp64 numpy restatement,
+agreement with the pinned deterministic render where the two must agree, Mitsuba's max_depth semantics, bit-reproducibility, the
+reference's own Mitsuba render, and the render_final.py command line."""
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+pytestmark = pytest.mark.gpu
+
+FOV = 35.0
+
+
+@pytest.fixture(scope="module")
+def pt():
+    from materialist_amd import build, pathtrace
+
+    build.build_path_library()
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return pathtrace
+
+
+def _report(what, value):
+    print(f"[path] {what}: {value}")
+    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"test_gpu_path\t{what}\t{value}\n")
+
+
+# ---- fp64 restatement of the integrator ----------------------------------------------------------------------------------------
+def pcg(v):
+    v = np.atleast_1d(np.asarray(v, dtype=np.uint32))
+    s = v * np.uint32(747796405) + np.uint32(2891336453)
+    w = ((s >> ((s >> np.uint32(28)) + np.uint32(4))) ^ s) * np.uint32(277803737)
+    return (w >> np.uint32(22)) ^ w
+
+
+def rng_u(base, vertex, dim):
+    return (pcg(base + np.uint32(vertex * 16 + dim)) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
+def brute(P, o, d):
+    """closest hit of rays o[N,3] + t d[N,3] (t > 0) on triangles P[T,3,3] -> t (inf = miss), index (-1)."""
+    e1, e2 = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
+    pv = np.cross(d[:, None], e2[None])
+    det = (e1[None] * pv).sum(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tv = o[:, None] - P[None, :, 0]
+        u = (tv * pv).sum(-1) / det
+        qv = np.cross(tv, e1[None])
+        v = (d[:, None] * qv).sum(-1) / det
+        t = (e2[None] * qv).sum(-1) / det
+    t = np.where((det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t > 0), t, np.inf)
+    k = t.argmin(1)
+    tk = t[np.arange(k.shape[0]), k]
+    return tk, np.where(np.isfinite(tk), k, -1)
+
+
+def env_texel(d, He, We):
+    th = np.arccos(np.clip(d[:, 1], -1, 1))
+    ph = np.mod(np.arctan2(d[:, 0], -d[:, 2]), 2 * np.pi)
+    return np.minimum((th * He / np.pi).astype(np.int64), He - 1) * We + np.minimum((ph * We / (2 * np.pi)).astype(np.int64), We - 1)
+
+
+def mis(a, b):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = a * a / (a * a + b * b)
+    return np.where(np.isfinite(w), w, 0.0)
+
+
+def reference_paths(o64, V, T, a, r, m, env, tab, H, W, max_depth, seed):
+    """One sample per pixel of the integrator of DESIGN.md section 1.4, in fp64, from the oracle's sample_brdf / eval_brdf /
+    world_to_screen, a brute-force intersection, the restated RNG and the same fp32 envmap tables the kernel reads."""
+    He, We = env.shape[:2]
+    envf = env.reshape(-1, 3).astype(np.float64)
+    pdf_tab = tab["pdf"].reshape(-1).astype(np.float64)
+    row_cdf, col_cdf = tab["row_cdf"], tab["col_cdf"]
+    P = V[T]
+    nrm = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    nrm *= np.where((nrm * P[:, 0]).sum(-1, keepdims=True) > 0, -1.0, 1.0)
+    nrm /= np.maximum(np.linalg.norm(nrm, axis=-1, keepdims=True), 1e-300)
+    N = H * W
+    pix = np.arange(N, dtype=np.uint32)
+    base = pcg(pcg(pcg(np.uint32(seed)) + pix) + np.uint32(0))
+    ii, jj = pix // W, pix % W
+    f = (W / 2.0) / math.tan(math.radians(FOV) / 2.0)
+    x = jj - 0.5 + rng_u(base, 0, 0)
+    y = ii - 0.5 + rng_u(base, 0, 1)
+    d = np.stack([(x - (W - 1) / 2) / f, -(y - (H - 1) / 2) / f, -np.ones(N)], -1)
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    o = np.zeros((N, 3))
+    L, thr, prev = np.zeros((N, 3)), np.ones((N, 3)), np.zeros(N)
+    alive = np.ones(N, bool)
+    A, R, M = a.reshape(-1, 3).astype(np.float64), r.reshape(-1).astype(np.float64), m.reshape(-1).astype(np.float64)
+    for depth in range(max_depth + 1):
+        idx = np.nonzero(alive)[0]
+        if idx.size == 0:
+            break
+        t, k = brute(P, o[idx], d[idx])
+        miss = k < 0
+        im = idx[miss]
+        if im.size:
+            tx = env_texel(d[im], He, We)
+            w = np.ones(im.size) if depth == 0 else mis(prev[im], pdf_tab[tx] if tab["row_cdf"][-1] > 0 else 0.0)
+            L[im] += thr[im] * envf[tx] * w[:, None]
+        alive[im] = False
+        if depth + 1 >= max_depth:
+            alive[:] = False
+            break
+        idx, t, k = idx[~miss], t[~miss], k[~miss]
+        n = nrm[k]
+        wo = -d[idx]
+        front = (n * wo).sum(-1) > 0
+        alive[idx[~front]] = False
+        idx, t, k, n, wo = idx[front], t[front], k[front], n[front], wo[front]
+        if idx.size == 0:
+            continue
+        p = o[idx] + t[:, None] * d[idx]
+        tp = np.empty(idx.size, np.int64)
+        for q in range(idx.size):
+            s = o64.world_to_screen(p[q], np.deg2rad(FOV), W / H, 0.01, 10000.0, W, H)
+            tp[q] = int(np.clip(np.floor(s[1]), 0, H - 1)) * W + int(np.clip(np.floor(s[0]), 0, W - 1))
+        av, rv, mv = A[tp], R[tp], M[tp]
+        po = p + (1e-5 * (1 + np.abs(p).max(-1)))[:, None] * n
+        b = base[idx]
+        if tab["row_cdf"][-1] > 0:
+            u0, u1, u2, u3 = (rng_u(b, depth, c) for c in (2, 3, 4, 5))
+            row = np.searchsorted(row_cdf[:He], u0, side="right") - 1
+            col = np.array([np.searchsorted(col_cdf[rr, :We], uu, side="right") - 1 for rr, uu in zip(row, u1)])
+            c0, c1 = np.cos(row * np.pi / He), np.cos((row + 1) * np.pi / He)
+            ct = c0 + (c1 - c0) * u2
+            st = np.sqrt(np.maximum(1 - ct * ct, 0))
+            ph = (col + u3) * 2 * np.pi / We
+            wl = np.stack([st * np.sin(ph), ct, -st * np.cos(ph)], -1)
+            te = row * We + col
+            pe = pdf_tab[te]
+            fb, pb = o64.eval_brdf(wl, wo, n, av, rv, mv)
+            ok = (pe > 0) & ((n * wl).sum(-1) > 0) & (fb > 0).any(-1)
+            if ok.any():
+                ts, _ = brute(P, po[ok], wl[ok])
+                vis = np.zeros(idx.size, bool)
+                vis[np.nonzero(ok)[0]] = ~np.isfinite(ts)
+                w = np.where(vis, mis(pe, pb) / np.where(pe > 0, pe, 1.0), 0.0)
+                L[idx] += thr[idx] * fb * envf[te] * w[:, None]
+        s1, s2a, s2b = (rng_u(b, depth, c) for c in (6, 7, 8))
+        wi, pdf, wgt = o64.sample_brdf(s1, np.stack([s2a, s2b], -1), wo, n, av, rv, mv)
+        thr[idx] *= wgt
+        dead = ~(thr[idx] > 0).any(-1)
+        alive[idx[dead]] = False
+        prev[idx] = pdf
+        o[idx], d[idx] = po, wi
+    return L.reshape(H, W, 3)
+
+
+def groove_scene(H=24, W=24):
+    """A V-groove (walls facing each other: occlusion and inter-reflection) with a step across its lower rows."""
+    i, j = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    d = 2.0 + 0.07 * (W / 2 - np.abs(j - (W - 1) / 2))
+    d[2 * H // 3:] -= 0.35
+    return d.astype(np.float32)
+
+
+def _maps(H, W, rng):
+    a = rng.uniform(0.2, 0.9, (H, W, 3)).astype(np.float32)
+    r = rng.uniform(0.25, 0.9, (H, W, 1)).astype(np.float32)
+    m = rng.uniform(0.0, 1.0, (H, W, 1)).astype(np.float32)
+    return a, r, m
+
+
+def _env(rng, He=8, We=16):
+    env = rng.gamma(2.0, 0.4, (He, We, 3)).astype(np.float32)
+    env[1, 3] = [30.0, 28.0, 25.0]     # a sun: emitter sampling matters
+    return env
+
+
+@pytest.fixture(scope="module")
+def groove(pt):
+    from materialist_amd import mesh
+
+    H = W = 24
+    rm = mesh.reference_mesh(groove_scene(H, W), FOV)
+    rng = np.random.default_rng(11)
+    a, r, m = _maps(H, W, rng)
+    env = _env(rng)
+    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV)
+    return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "tracer": tracer, "H": H, "W": W}
+
+
+def test_every_path_matches_an_fp64_restatement(pt, groove, oracle64):
+    g = groove
+    H, W = g["H"], g["W"]
+    tab = pt.env_tables(g["env"])
+    V = g["rm"]["vertices"].astype(np.float32).astype(np.float64)
+    worst = []
+    for seed in (0, 1, 2):
+        got = g["tracer"].render(g["a"], g["r"], g["m"], g["env"], spp=1, max_depth=4, seed=seed).cpu().numpy().astype(np.float64)
+        assert np.isfinite(got).all()
+        ref = reference_paths(oracle64, V, g["rm"]["triangles"], g["a"], g["r"], g["m"], g["env"], tab, H, W, 4, seed)
+        scale = np.abs(ref).mean()
+        err = (np.abs(got - ref) / np.maximum(np.abs(ref), scale)).max(-1)
+        frac = float((err <= 1e-3).mean())
+        worst.append(frac)
+        _report(f"per-path parity seed {seed}: share of pixels within 1e-3", f"{frac:.4f} ({int((err > 1e-3).sum())} flipped paths, "
+                f"max err {err.max():.3e})")
+        assert frac >= 0.99, (seed, frac, np.argwhere(err > 1e-3)[:10])
+    # the scene exercises what it is meant to: light arrives after more than one bounce
+    d2 = g["tracer"].render(g["a"], g["r"], g["m"], g["env"], spp=16, max_depth=2, seed=5).cpu().numpy()
+    d4 = g["tracer"].render(g["a"], g["r"], g["m"], g["env"], spp=16, max_depth=4, seed=5).cpu().numpy()
+    assert (d4 - d2).mean() > 1e-3 * d4.mean()
+
+
+def test_plane_agrees_with_the_deterministic_render(pt):
+    """A camera-facing plane cannot occlude or reflect onto itself, and a constant envmap is exact in SH25: the path render converges
+    to the deterministic render's integral.  Bound: K independent renders (seeds) give per-pixel estimates X_k; per 8 x 8 block b the
+    mean over its 64 pixels and the K renders has standard error sigma_b = sd(X) / sqrt(64 K) (pixels and seeds use disjoint RNG
+    streams, so the 64 K estimates are independent).  The deterministic render has its own quadrature error; its size is bounded by
+    the difference of its spp-64 and spp-128 rules, delta_b.  Every block must agree within 4 sigma_b + delta_b (a block fails by
+    chance with p < 1e-4), and the image mean within 0.5 %."""
+    from materialist_amd import mesh, render
+
+    dev = torch.device("cuda:0")
+    H = W = 48
+    depth = np.full((H, W), 2.0, np.float32)
+    rm = mesh.reference_mesh(depth, FOV)
+    rng = np.random.default_rng(5)
+    a, r, m = _maps(H, W, rng)
+    env = np.full((16, 32, 3), 0.8, np.float32)
+    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV)
+    K = 8
+    X = np.stack([tracer.render(a, r, m, env, spp=256, max_depth=4, seed=100 + k).cpu().numpy().astype(np.float64) for k in range(K)])
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+    scene = render.load_estimated_mesh(t(depth), use_mesh_normal=True)
+    scene._set("emitter.data", t(env))
+    with torch.no_grad():
+        det = {s: render.render_w_brdf(scene, t(a), t(r), t(m), None, s).cpu().numpy().astype(np.float64) for s in (64, 128)}
+    inner = (slice(8, H - 8), slice(8, W - 8))       # away from the mesh border (jittered rays off its last half pixel see the sky)
+    blk = lambda z: z[..., inner[0], inner[1], :].reshape(*z.shape[:-3], 4, 8, 4, 8, 3).mean(axis=(-4, -2))
+    path_b = blk(X).mean(0)
+    sigma = np.sqrt(blk(X.var(0, ddof=1)[None])[0] / (64 * K))
+    det_b, delta = blk(det[128]), np.abs(blk(det[128]) - blk(det[64]))
+    z = np.abs(path_b - det_b) / (4 * sigma + delta)
+    rel_mean = abs(X.mean(0)[inner].mean() / det[128][inner].mean() - 1)
+    _report("plane vs deterministic render: max block |diff| / (4 sigma + delta)", f"{z.max():.3f}")
+    _report("plane vs deterministic render: image-mean relative difference", f"{rel_mean:.2e}")
+    assert z.max() <= 1.0, (z.max(), np.unravel_index(z.argmax(), z.shape))
+    assert rel_mean <= 5e-3
+
+
+def test_max_depth_semantics(pt, groove):
+    g = groove
+    args = (g["a"], g["r"], g["m"], g["env"])
+    d1 = g["tracer"].render(*args, spp=4, max_depth=1, seed=3).cpu().numpy()
+    d2 = g["tracer"].render(*args, spp=4, max_depth=2, seed=3).cpu().numpy()
+    d4 = g["tracer"].render(*args, spp=4, max_depth=4, seed=3).cpu().numpy()
+    # every pixel of the groove has geometry under all its jittered rays except the outermost half-pixel ring
+    assert np.all(d1[1:-1, 1:-1] == 0.0)
+    assert np.all(d4 >= d2), np.argwhere(d4 < d2)[:5]
+    assert np.all(d2 >= d1)
+    assert (d2.sum(-1) > 0).mean() > 0.9          # direct light with shadows reaches most pixels at spp 4
+
+
+def test_same_bits_for_every_split_and_seed(pt, groove):
+    g = groove
+    args = (g["a"], g["r"], g["m"], g["env"])
+    x8 = g["tracer"].render(*args, spp=64, seed=7, spp_per_launch=8).cpu().numpy()
+    x64 = g["tracer"].render(*args, spp=64, seed=7, spp_per_launch=64).cpu().numpy()
+    x8b = g["tracer"].render(*args, spp=64, seed=7, spp_per_launch=8).cpu().numpy()
+    x5 = g["tracer"].render(*args, spp=64, seed=7, spp_per_launch=5).cpu().numpy()
+    other = g["tracer"].render(*args, spp=64, seed=8, spp_per_launch=8).cpu().numpy()
+    assert np.array_equal(x8.view(np.uint32), x8b.view(np.uint32))
+    assert np.array_equal(x8.view(np.uint32), x64.view(np.uint32))
+    assert np.array_equal(x8.view(np.uint32), x5.view(np.uint32))
+    assert not np.array_equal(x8, other)
+
+
+def test_against_mitsuba_on_the_references_final_maps(pt, golden_dir):
+    """tests/golden/indoor2.npz: the reference's final maps, MaterialNet's depth, the 16 x 32 envmap and Mitsuba's `path` render of
+    them (max_depth 4, spp 64).  The path render and the deterministic render of the same maps, both against it."""
+    from materialist_amd import mesh, render
+
+    dev = torch.device("cuda:0")
+    z = np.load(os.path.join(golden_dir, "indoor2.npz"))
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+    a = t(z["ref_albedo_u8"].astype(np.float32) / 255.0)
+    r = t(z["ref_roughness_u8"].astype(np.float32)[..., None] / 255.0).clamp(0.07, 1.0)
+    m = t(z["ref_metallic_u8"].astype(np.float32)[..., None] / 255.0)
+    env = z["ref_envmap_f32"]
+    ref = z["ref_render_f16"].astype(np.float64)
+    depth = z["depth_pred_f32"]
+    depth = 2 * depth.max() - depth                                                  # inverse_img_w_mi.py:722
+    H, W = depth.shape
+    rm = mesh.reference_mesh(depth, FOV)
+    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV)
+    _report("BVH of indoor2 (triangles, nodes, depth, MB, build ms)",
+            f"{tracer.stats['n_tris']}, {tracer.stats['n_nodes']}, {tracer.stats['depth']}, {tracer.stats['bytes'] / 2**20:.1f}, "
+            f"{tracer.stats['build_s'] * 1e3:.0f}")
+    img = tracer.render(a, r, m, env, spp=256, max_depth=4, seed=0).cpu().numpy().astype(np.float64)
+    assert np.isfinite(img).all()
+    scene = render.load_estimated_mesh(t(depth), use_mesh_normal=True)
+    scene._set("emitter.data", t(env))
+    with torch.no_grad():
+        direct = render.render_w_brdf(scene, a, r, m, None, 64).cpu().numpy().astype(np.float64)
+    g = lambda x: np.clip(x, 0, 1) ** (1 / 2.2)
+    psnr = lambda x, y: -10 * np.log10(np.mean((g(x) - g(y)) ** 2))
+    res = {}
+    for name, x in (("path", img), ("direct", direct)):
+        res[name] = (psnr(x, ref), psnr(x * (ref.mean() / x.mean()), ref))
+        _report(f"{name} render vs Mitsuba (indoor2), dB raw / mean-matched", f"{res[name][0]:.2f} / {res[name][1]:.2f}")
+    assert res["path"][0] > 20.5 and res["path"][1] > 24.5, res
+    # one 512 x 512 frame at spp 64, max_depth 4: hip events around the enqueued launches, rays counted by the kernel
+    for _ in range(2):
+        tracer.render(a, r, m, env, spp=64, max_depth=4, seed=1)
+    rays = torch.zeros(H, W, dtype=torch.int32, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    tracer.render(a, r, m, env, spp=64, max_depth=4, seed=1, rays=rays)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1)
+    n_rays = float(rays.to(torch.float64).sum())
+    _report("512x512 spp 64 max_depth 4 frame: ms, Mrays, Mrays/s", f"{ms:.1f}, {n_rays / 1e6:.1f}, {n_rays / 1e3 / ms:.0f}")
+    assert ms < 5000.0
+
+
+def _synthetic_output(tmp, name="case", H=64, W=64):
+    from materialist_amd import mesh
+    from materialist_amd.imageio_exr import write_exr
+    from materialist_amd.imageio_hdr import write_hdr
+
+    rng = np.random.default_rng(2)
+    scene = os.path.join(tmp, name)
+    br = os.path.join(scene, "best_results")
+    os.makedirs(br)
+    a, r, m = _maps(H, W, rng)
+    write_exr(os.path.join(br, "albedo.exr"), a)
+    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
+    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
+    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
+    write_hdr(os.path.join(br, "envmap.hdr"), _env(rng))
+    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)         # depthPred.exr: the pipeline flips it to 2 max - d
+    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
+    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
+    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
+    return scene
+
+
+def test_render_final_cli_with_the_path_integrator(pt, tmp_path):
+    from materialist_amd.imageio_exr import read_exr
+
+    tmp = str(tmp_path)
+    _synthetic_output(tmp)
+    cli = [sys.executable, os.path.join(ROOT, "render_final.py"), "--save_name", "case", "--input_path", tmp, "--save_path", tmp,
+           "--spp", "8", "--integrator", "path"]
+    res = subprocess.run(cli + ["--mode", "real"], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    exr = os.path.join(tmp, "case", "mi_case_envmap_.exr")
+    assert os.path.exists(exr) and os.path.exists(exr[:-4] + ".png")
+    img = read_exr(exr)
+    assert img.shape[:2] == (64, 64) and np.isfinite(img).all() and img.mean() > 0
+    res = subprocess.run(cli + ["--mode", "rolling", "--frames", "3", "--rotation_step", "90", "--max_depth", "3",
+                               "--seed", "4"], capture_output=True, text=True,
+                         timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    anim = os.path.join(tmp, "case", "rolling_envmap_animation")
+    assert sorted(os.listdir(anim)) == ["frame_0000.png", "frame_0001.png", "frame_0002.png"]
+    for ext in ("gif", "mp4"):
+        assert os.path.getsize(os.path.join(tmp, "case", f"rolling_envmap_case_envmap.{ext}")) > 0
+    from PIL import Image
+
+    frames = [np.asarray(Image.open(os.path.join(anim, f))) for f in sorted(os.listdir(anim))]
+    assert all(np.isfinite(f).all() for f in frames) and not np.array_equal(frames[0], frames[2])
+    # without a .ply the scene is meshed from depthPred.exr as the pipeline does: the same mesh, the same image
+    os.remove(os.path.join(tmp, "case", "case.ply"))
+    res = subprocess.run(cli + ["--mode", "real"], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert np.array_equal(read_exr(exr), img)
