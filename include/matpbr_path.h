@@ -1,5 +1,5 @@
 /*
- * matpbr_path.h -- C ABI of libmatpbr_path.so: a forward-only path-traced re-render of the depth mesh (MI355X, gfx950).
+ * matpbr_path.h -- C ABI of libmatpbr_path.so: a path-traced re-render of the depth mesh and its backward pass (MI355X, gfx950).
  *
  * The integrator is Mitsuba 3's `path` as the reference configures it for its final images (render_final.py:35-96,
  * inverse_img_w_mi.py:49-52: `max_depth` 4, MatDiffBSDF on the `.ply` depth mesh, equirectangular envmap emitter); its
@@ -22,9 +22,10 @@
 extern "C" {
 #endif
 
-#define MATPBR_PATH_VERSION 1
+#define MATPBR_PATH_VERSION 2
 #define MATPBR_PATH_MAX_BVH_DEPTH 40 /* node levels below the root the builder may create; the kernel's traversal stack has this many entries */
-#define MATPBR_PATH_MAX_MAX_DEPTH 16 /* largest `max_depth` matpbr_path_render accepts */
+#define MATPBR_PATH_MAX_MAX_DEPTH 16 /* largest `max_depth` matpbr_path_render / matpbr_path_render_bwd accept */
+#define MATPBR_PATH_BWD_MAX_ENV_TEXELS 1024 /* largest He * We matpbr_path_render_bwd takes with d_env */
 #define MATPBR_PATH_NODE_BYTES 64    /* one node: both children's boxes (2 x 24 B) + two child words + two counts */
 #define MATPBR_PATH_TRI_BYTES 48     /* one triangle in leaf order: (v0, id) (e1, 0) (e2, 0) as float4; e1 x e2 faces the camera */
 
@@ -72,6 +73,23 @@ int matpbr_path_env_sample_host(const float* row_cdf, const float* col_cdf, cons
 int matpbr_path_render(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
                        const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                        int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream);
+
+/* Workspace of matpbr_path_render_bwd for an H x W image and an He x We envmap, in bytes (0 for a non-positive size). */
+size_t matpbr_path_render_bwd_workspace_bytes(int H, int W, int He, int We);
+
+/* The backward pass of matpbr_path_render with the same arguments (`spp`, `max_depth`, `seed`, `spp_per_launch` mean the same):
+ * the exact derivative of the fixed-seed estimator with the sampling detached: directions, pdfs, MIS
+ * weights, lobe choices and the envmap tables are constants; the gradient flows through the BSDF value at every vertex, to the
+ * texel the vertex reads its material from, and through the envmap texels.  d_out[H,W,3] = d loss / d out.  The gradients are
+ * ADDED to d_a[H,W,3], d_r[H,W,1], d_m[H,W,1], d_env[He,We,3] (device pointers); a null one is not computed and its buffer is not
+ * touched.  Sums are 64-bit fixed point: the result is bit-identical from run to run and for every `spp_per_launch`.  d_env needs
+ * He * We <= MATPBR_PATH_BWD_MAX_ENV_TEXELS.  `workspace`: device memory of matpbr_path_render_bwd_workspace_bytes(H, W, He, We)
+ * bytes, 8-byte aligned, used by the enqueued work until it has run.  `rays` (nullable, [H,W]): the rays both replays of each
+ * pixel traced are ADDED to it.  d_out must be finite. */
+int matpbr_path_render_bwd(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
+                           const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
+                           int max_depth, uint32_t seed, int spp_per_launch, const float* d_out, float* d_a, float* d_r, float* d_m,
+                           float* d_env, void* workspace, size_t workspace_bytes, uint32_t* rays, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Command line of the inverse-rendering pipeline, same flags as the reference's inverse_img_w_mi.py (:771-801) plus
-`--size`, `--spp`, `--num_epochs`, `--pred_dir`.  Runs on libmatpbr.so (MI355X); see materialist_amd/pipeline.py."""
+`--size`, `--spp`, `--num_epochs`, `--pred_dir`, `--integrator` / `--max_depth` / `--seed`.  Runs on libmatpbr.so (MI355X); see materialist_amd/pipeline.py."""
 import argparse
 import os
 import sys
@@ -27,7 +27,17 @@ def parse_args(argv=None):
     ap.add_argument("--geometry", type=str, default="mesh", choices=["mesh", "depth"],
                     help="per-pixel geometric normals: from the reference's mesh of the depth map, gap closing at depth edges included (mesh_recon.py, "
                          "default), or central differences of the depth map itself")
-    return ap.parse_args(argv)
+    ap.add_argument("--integrator", choices=("sh", "path"), default="sh",
+                    help="render the fit goes through: sh = the deterministic render (direct light, SH25, default); path = the path-traced "
+                         "render of the depth mesh with its backward pass (shadows and inter-reflection, as the reference's Mitsuba `path`)")
+    ap.add_argument("--max_depth", type=int, default=4, help="--integrator path: Mitsuba's max_depth (1 emission, 2 direct + shadows, 4 the reference's)")
+    ap.add_argument("--seed", type=int, default=0, help="--integrator path: seed of the sequence each render draws its seed from")
+    args = ap.parse_args(argv)
+    if args.integrator == "path" and "n" in "".join(args.opt_order):
+        ap.error(f"--integrator path shades with the mesh's face normals: it cannot optimise normals ('n' in --opt_order {' '.join(args.opt_order)})")
+    if args.integrator == "path" and not 1 <= args.max_depth <= 16:
+        ap.error("--max_depth must lie in 1..16")
+    return args
 
 
 def main(argv=None):
@@ -36,7 +46,8 @@ def main(argv=None):
 
     res = inverse_image(args.img_inverse_path, args.save_name, args.opt_src, args.opt_order, args.use_mask, args.opt_env_from,
                         args.save_path, args.model_name, size=args.size, spp=args.spp, num_epochs=args.num_epochs, pred_dir=args.pred_dir,
-                        matnet_weights=args.matnet_weights, geometry=args.geometry)
+                        matnet_weights=args.matnet_weights, geometry=args.geometry, integrator=args.integrator, max_depth=args.max_depth,
+                        seed=args.seed)
     print(f"done: PSNR {res['psnr']:.2f} dB, best loss_mse {res['best_loss']:.6f}, outputs in {res['output_dir']}")
 
 

@@ -4,7 +4,8 @@
 //     two boxes), triangles stored in leaf order as precomputed (v0, e1, e2); the envmap's importance-sampling tables (fp64 -> fp32);
 //   * device: one thread per pixel loops over its samples in order and accumulates them in a fixed order (no atomics: the image is
 //     bit-reproducible, and so is every split of a frame into launches); the traversal stack lives in LDS, one column per lane;
-//   * the closest-hit routine and the emitter sampler are __host__ __device__: the CPU entry points run the same code as the kernel.
+//   * the closest-hit routine and the emitter sampler are __host__ __device__: the CPU entry points run the same code as the kernel;
+//   * backward (matpbr_path_render_bwd): path replay with the sampling detached, 64-bit fixed-point sums (see "backward pass" below).
 // The BRDF arithmetic is matpbr_device.hpp's (pixel_const, brdf_core, ggx_den_stable, frame, to_world), unchanged.
 #include <hip/hip_runtime.h>
 
@@ -221,9 +222,15 @@ __device__ __forceinline__ void path_eval(const float wi[3], const float wo[3], 
     BrdfState<float> st;
     brdf_core(ln.pc, ln.NoL_raw, ln.NoH, ln.VoH, ln.den, st, f, pdf);
 }
-// sample_brdf: lobe by sample1 > 0.5 (diffuse) else GGX; weight = f/(pdf + 1e-6) where pdf > 1e-6, else 0
-__device__ __forceinline__ void path_sample(float sample1, float u0, float u1, const float wo[3], const float n[3], const float a[3], float r,
-                                            float m, float wi[3], float w[3], float& pdf_out) {
+// path_eval keeping what the backward pass needs (brdf_core_grad reads the lane constants and the state)
+__device__ __forceinline__ void path_eval_st(const float wi[3], const float wo[3], const float n[3], const float a[3], float r, float m, PLane& ln,
+                                             BrdfState<float>& st, float f[3], float& pdf) {
+    path_lane(ln, wi, wo, n, a, r, m);
+    brdf_core(ln.pc, ln.NoL_raw, ln.NoH, ln.VoH, ln.den, st, f, pdf);
+}
+// sample_brdf's direction and the BSDF value / mixture pdf there (f and p before the weight is formed; ln / st for the backward pass)
+__device__ __forceinline__ void path_sample_st(float sample1, float u0, float u1, const float wo[3], const float n[3], const float a[3], float r,
+                                               float m, float wi[3], PLane& ln, BrdfState<float>& st, float f[3], float& p) {
     float s[3], t[3];
     frame(n, s, t);
     float sp, cp;
@@ -246,15 +253,20 @@ __device__ __forceinline__ void path_sample(float sample1, float u0, float u1, c
         for (int c = 0; c < 3; ++c) wi[c] *= il;
         if (d > 0.0f) { sin2_h = u0 * alpha2 * q; cos_h = ct; }
     }
-    PLane ln;
     path_lane(ln, wi, wo, n, a, r, m);
     if (sin2_h >= 0.0f) {  // same value as the literal form, without the fp32 cancellation at the GGX peak
         ln.NoH = cos_h;
         ln.den = ggx_den_stable(ln.pc, sin2_h);
     }
+    brdf_core(ln.pc, ln.NoL_raw, ln.NoH, ln.VoH, ln.den, st, f, p);
+}
+// sample_brdf: lobe by sample1 > 0.5 (diffuse) else GGX; weight = f/(pdf + 1e-6) where pdf > 1e-6, else 0
+__device__ __forceinline__ void path_sample(float sample1, float u0, float u1, const float wo[3], const float n[3], const float a[3], float r,
+                                            float m, float wi[3], float w[3], float& pdf_out) {
+    PLane ln;
     BrdfState<float> st;
     float f[3], p;
-    brdf_core(ln.pc, ln.NoL_raw, ln.NoH, ln.VoH, ln.den, st, f, p);
+    path_sample_st(sample1, u0, u1, wo, n, a, r, m, wi, ln, st, f, p);
     const float ip = p > 1e-6f ? 1.0f / (p + 1e-6f) : 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) w[c] = f[c] * ip;
@@ -385,6 +397,257 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     if (q.rays) q.rays[pix] += n_rays;
 }
 
+// ---- backward pass ("Gradients") ------------------------------------------------------------------------
+// The exact derivative of the fixed-seed estimator with the sampling detached: directions, pdfs, MIS weights, lobe choices and the
+// envmap tables are constants; the gradient flows through the BSDF value f (trailing cosine included) at every vertex and through
+// the envmap texels Le.  Path replay (Vicini et al. 2021, "Path Replay Backpropagation"): pass 1 replays a sample to get its
+// radiance L; pass 2 replays it again carrying the radiance still to come, `rem`.  At a vertex, the emitter term E = thr f_e Le w
+// gives d/d theta through f_e with upstream g thr Le w; after E is taken off, `rem` is exactly the part of L that carries the
+// vertex's BSDF-sample factor f_s / (pdf_s + 1e-6), so its upstream through f_s is g rem / f_s.
+//
+// Determinism: every gradient is summed as 64-bit fixed point, integer addition being associative.  The quantum is a power of two
+// derived on the device from max|d_out| (path_bwd_scale_kernel): q = 2^(e - 24) with max|d_out| < 2^e.  A contribution is rounded
+// to the nearest multiple of q (error <= q/2 <= 2^-24 max|d_out|) and clamped to +-2^46 q (over 2^22 max|d_out|); the sum of an
+// element's n contributions is then off by at most n q / 2 before the final division by spp, and 2^17 clamped contributions still
+// fit in 63 bits.  Maps: the vertex a lane shades on its own texel (the camera vertex, nearly always) goes to the lane's registers,
+// one integer atomic per launch; the other vertices scatter with integer atomics.  Envmap: per workgroup in LDS (integer LDS
+// atomics), one row per workgroup in the workspace, and the rows are added in a small second launch.
+constexpr int kBwdMaxEnvTexels = MATPBR_PATH_BWD_MAX_ENV_TEXELS;   // the workgroup's LDS row: 3 x 8 bytes per texel
+constexpr float kFixClamp = 70368744177664.0f;   // 2^46 quanta
+constexpr float kRemFloor = 9.5367431640625e-7f;  // 2^-20: below kRemFloor * max_depth * L the radiance still to come is rounding
+
+struct BwdArgs {
+    const float* d_out;
+    unsigned long long* acc;       // [H*W, 5] fixed point: a (3), r, m
+    unsigned long long* env_rows;  // [n_wg, He*We*3] fixed point
+    const float* scale;            // [0] = 1/q, [1] = q (path_bwd_scale_kernel)
+    int want_a, want_r, want_m, want_env;
+};
+
+__device__ __forceinline__ long long to_fix(float v, float inv_q) {
+    return __float2ll_rn(fminf(fmaxf(v * inv_q, -kFixClamp), kFixClamp));
+}
+
+// one vertex's material gradient to its texel: the lane's own texel in registers, any other with integer atomics
+__device__ __forceinline__ void put_material(const BwdArgs& b, const BrdfGrad<float>& gv, long tp, long pix, float inv_q, long long own[5]) {
+    const float v[5] = {gv.d_a[0], gv.d_a[1], gv.d_a[2], gv.d_r, gv.d_m};
+    const int want[5] = {b.want_a, b.want_a, b.want_a, b.want_r, b.want_m};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        if (!want[k]) continue;
+        const long long x = to_fix(v[k], inv_q);
+        if (x == 0) continue;
+        if (tp == pix) own[k] += x;
+        else atomicAdd(b.acc + 5 * tp + k, (unsigned long long)x);
+    }
+}
+__device__ __forceinline__ void put_env(unsigned long long* s_env, int tx, const float v[3], float inv_q) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const long long x = to_fix(v[c], inv_q);
+        if (x != 0) atomicAdd(s_env + 3 * tx + c, (unsigned long long)x);
+    }
+}
+
+// One sample of pixel (i, j): GRAD = false adds its radiance to L (the forward kernel's walk, statement for statement); GRAD = true
+// replays it with rem = that radiance and sends the gradients of g . L to the sinks.
+template <bool GRAD>
+__device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint32_t base, int i, int j, long pix, bool have_tab, LdsStack& stk,
+                                       float L[3], const float g[3], float inv_q, long long own[5], unsigned long long* s_env, uint32_t& n_rays) {
+    float thr[3] = {1.0f, 1.0f, 1.0f};
+    float rem[3] = {L[0], L[1], L[2]};
+    const float x = (float)j - 0.5f + rng_u(base, 0, 0), y = (float)i - 0.5f + rng_u(base, 0, 1);
+    float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {(x - q.cx) / q.f_pix, -(y - q.cy) / q.f_pix, -1.0f};
+    {
+        const float il = rsq(dot3(d, d));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] *= il;
+    }
+    const bool want_mat = b.want_a || b.want_r || b.want_m;
+    float prev_pdf = 0.0f;
+    for (int depth = 0;; ++depth) {
+        float t = FLT_MAX;
+        ++n_rays;
+        const int k = trace<false>(q.nodes, q.tris, o, d, 0.0f, t, stk);
+        if (k < 0) {
+            const int tx = env_texel(d, q.He, q.We);
+            const float w = depth == 0 ? 1.0f : mis_weight(prev_pdf, have_tab ? q.env_pdf[tx] : 0.0f);
+            if (GRAD) {
+                if (b.want_env) {
+                    const float v[3] = {g[0] * (thr[0] * w), g[1] * (thr[1] * w), g[2] * (thr[2] * w)};
+                    put_env(s_env, tx, v, inv_q);
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) L[c] += thr[c] * (q.env[3 * tx + c] * w);
+            }
+            break;
+        }
+        if (depth + 1 >= q.max_depth) break;
+        const float4 B = q.tris[3 * k + 1], C = q.tris[3 * k + 2];
+        const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+        float n[3];
+        cross3(e1, e2, n);
+        {
+            const float il = rsq(dot3(n, n));
+#pragma unroll
+            for (int c = 0; c < 3; ++c) n[c] *= il;
+        }
+        const float wo[3] = {-d[0], -d[1], -d[2]};
+        if (!(dot3(n, wo) > 0.0f)) break;
+        float p[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = fmaf(t, d[c], o[c]);
+        const float ndc0 = (q.f_ndc / q.aspect) * (-p[0]) / p[2], ndc1 = q.f_ndc * p[1] / p[2];
+        const float sx = (ndc0 + 1.0f) * 0.5f * (float)q.W, sy = (ndc1 + 1.0f) * 0.5f * (float)q.H;
+        const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
+        const long tp = (long)ty * q.W + tx;
+        const float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+        const float eps = spawn_eps(p);
+        float po[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
+        BrdfGrad<float> gv;
+        brdf_grad_zero(gv);
+        float gl, gh;   // (cosine gradients: not asked for)
+        if (have_tab) {
+            float wl[3], pdf_e;
+            const int te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
+                                      rng_u(base, depth, 4), rng_u(base, depth, 5), wl, pdf_e);
+            if (pdf_e > 0.0f && dot3(n, wl) > 0.0f) {
+                float f[3], pdf_b;
+                PLane ln;
+                BrdfState<float> st;
+                path_eval_st(wl, wo, n, av, rv, mv, ln, st, f, pdf_b);
+                if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
+                    float ts = FLT_MAX;
+                    ++n_rays;
+                    if (trace<true>(q.nodes, q.tris, po, wl, 0.0f, ts, stk) < 0) {
+                        const float w = mis_weight(pdf_e, pdf_b) / pdf_e;
+                        if (GRAD) {
+                            float ge[3], ve[3];
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                const float Le = q.env[3 * te + c];
+                                rem[c] -= thr[c] * (f[c] * (Le * w));
+                                ge[c] = g[c] * (thr[c] * (Le * w));
+                                ve[c] = g[c] * (thr[c] * (f[c] * w));
+                            }
+                            if (want_mat) brdf_core_grad<float, false>(ln.pc, st, ge, gv, gl, gh);
+                            if (b.want_env) put_env(s_env, te, ve, inv_q);
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) L[c] += thr[c] * (f[c] * (q.env[3 * te + c] * w));
+                        }
+                    }
+                }
+            }
+        }
+        float wi[3], fs[3], ps;
+        PLane ln;
+        BrdfState<float> st;
+        path_sample_st(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, ln, st, fs, ps);
+        const float ip = ps > 1e-6f ? 1.0f / (ps + 1e-6f) : 0.0f;
+        if (GRAD && want_mat) {
+            if (ip > 0.0f) {   // d (f_s / (pdf_s + 1e-6)) / d theta carried by everything after this vertex: rem / f_s per channel
+                // rem is L minus at most 2 max_depth fp32 terms, each off by <= ulp(L)/2 <= 2^-24 L: a rem below 2^-20 max_depth L is
+                // that rounding (the path gathers nothing more), and dividing it by a small f_s (a black metal) would make it a gradient
+                float gs[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    gs[c] = fs[c] > 0.0f && rem[c] > kRemFloor * (float)q.max_depth * L[c] ? g[c] * (rem[c] / fs[c]) : 0.0f;
+                brdf_core_grad<float, false>(ln.pc, st, gs, gv, gl, gh);
+            }
+            put_material(b, gv, tp, pix, inv_q, own);
+        }
+        (void)gl; (void)gh;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) thr[c] *= fs[c] * ip;
+        if (!(thr[0] > 0.0f || thr[1] > 0.0f || thr[2] > 0.0f)) break;
+        prev_pdf = ps > 0.0f ? ps : 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { o[c] = po[c]; d[c] = wi[c]; }
+    }
+}
+
+// samples [s0, s1) of every pixel: both passes per sample; the lane's own-texel sums and the workgroup's envmap row go out at the end
+__global__ __launch_bounds__(kBlock) void path_bwd_kernel(const PathArgs q, const BwdArgs b, int s0, int s1) {
+    __shared__ int s_stack[kStack * kBlock];
+    extern __shared__ unsigned long long s_env[];   // [He*We*3] when d_env is asked for
+    const int tid = threadIdx.y * kTileX + threadIdx.x;
+    const int n_env = b.want_env ? 3 * q.He * q.We : 0;
+    for (int k = tid; k < n_env; k += kBlock) s_env[k] = 0ull;
+    __syncthreads();
+    const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
+    if (i < q.H && j < q.W) {
+        LdsStack stk{s_stack + tid};
+        const long pix = (long)i * q.W + j;
+        const bool have_tab = q.row_cdf[q.He] > 0.0f;
+        const float inv_q = b.scale[0];
+        const float g[3] = {b.d_out[3 * pix], b.d_out[3 * pix + 1], b.d_out[3 * pix + 2]};
+        long long own[5] = {0, 0, 0, 0, 0};
+        const uint32_t pix_hash = pcg_hash(q.seed_hash + (uint32_t)pix);
+        uint32_t n_rays = 0;
+        for (int s = s0; s < s1; ++s) {
+            const uint32_t base = pcg_hash(pix_hash + (uint32_t)s);
+            float L[3] = {0.0f, 0.0f, 0.0f};
+            replay<false>(q, b, base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
+            replay<true>(q, b, base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (own[k] != 0) atomicAdd(b.acc + 5 * pix + k, (unsigned long long)own[k]);
+        if (q.rays) q.rays[pix] += n_rays;
+    }
+    __syncthreads();
+    unsigned long long* row = b.env_rows + (long)(blockIdx.y * gridDim.x + blockIdx.x) * n_env;
+    for (int k = tid; k < n_env; k += kBlock) row[k] += s_env[k];   // each workgroup owns its row; launches follow each other on the stream
+}
+
+// the quantum: q = 2^(e - 24) with max|d_out| < 2^e (1 when d_out is all zero)
+__global__ __launch_bounds__(1024) void path_bwd_scale_kernel(const float* __restrict__ d_out, long n, float* scale) {
+    __shared__ float s_max[1024];
+    float mx = 0.0f;
+    for (long k = threadIdx.x; k < n; k += 1024) mx = fmaxf(mx, fabsf(d_out[k]));
+    s_max[threadIdx.x] = mx;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s_max[threadIdx.x] = fmaxf(s_max[threadIdx.x], s_max[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float m = s_max[0];
+        int e = 24;
+        if (m > 0.0f && isfinite(m)) frexpf(m, &e);
+        scale[0] = ldexpf(1.0f, 24 - e);
+        scale[1] = ldexpf(1.0f, e - 24);
+    }
+}
+
+// fixed point -> fp32, ADDED to the caller's maps: d_x += sum * q / spp
+__global__ __launch_bounds__(256) void path_bwd_maps_kernel(const unsigned long long* __restrict__ acc, const float* __restrict__ scale, long P,
+                                                            int spp, float* d_a, float* d_r, float* d_m) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const double s = (double)scale[1] / (double)spp;
+    const unsigned long long* e = acc + 5 * p;
+    if (d_a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d_a[3 * p + c] += (float)((double)(long long)e[c] * s);
+    }
+    if (d_r) d_r[p] += (float)((double)(long long)e[3] * s);
+    if (d_m) d_m[p] += (float)((double)(long long)e[4] * s);
+}
+// the workgroups' envmap rows, added in row order, -> d_env += sum * q / spp
+__global__ __launch_bounds__(256) void path_bwd_env_kernel(const unsigned long long* __restrict__ rows, const float* __restrict__ scale, int n_env,
+                                                           int n_rows, int spp, float* d_env) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_env) return;
+    unsigned long long sum = 0ull;
+    for (int w = 0; w < n_rows; ++w) sum += rows[(long)w * n_env + k];
+    d_env[k] += (float)((double)(long long)sum * ((double)scale[1] / (double)spp));
+}
+
 // ---- host: binned-SAH builder --------------------------------------------------------------------------------------------
 struct Box {
     float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
@@ -511,7 +774,8 @@ int matpbr_path_version(void) { return MATPBR_PATH_VERSION; }
 const char* matpbr_path_strerror(int code) {
     switch (code) {
         case MATPBR_PATH_OK: return "ok";
-        case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, or max_depth outside 1..16)";
+        case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, max_depth outside 1..16, "
+                                                  "a workspace too small, or an envmap of more than 1024 texels with d_env)";
         case MATPBR_PATH_ERR_LAUNCH: return "HIP kernel launch failed";
         case MATPBR_PATH_ERR_CAPACITY: return "node buffer smaller than matpbr_path_bvh_size() asks for";
         default: return "unknown error";
@@ -678,6 +942,70 @@ int matpbr_path_render(const void* nodes, const void* tris, const float* a, cons
     for (int s0 = 0; s0 < spp; s0 += spp_per_launch) {
         const int s1 = std::min(spp, s0 + spp_per_launch);
         hipLaunchKernelGGL(path_kernel, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, s0 == 0 ? 1 : 0, s1 == spp ? 1 : 0);
+        if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    return MATPBR_PATH_OK;
+}
+
+size_t matpbr_path_render_bwd_workspace_bytes(int H, int W, int He, int We) {
+    if (H <= 0 || W <= 0 || He <= 0 || We <= 0) return 0;
+    const size_t n_wg = (size_t)((W + kTileX - 1) / kTileX) * (size_t)((H + kTileY - 1) / kTileY);
+    return 256 + (size_t)H * W * 5 * 8 + n_wg * (size_t)He * We * 3 * 8;
+}
+
+int matpbr_path_render_bwd(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
+                           const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
+                           int max_depth, uint32_t seed, int spp_per_launch, const float* d_out, float* d_a, float* d_r, float* d_m,
+                           float* d_env, void* workspace, size_t workspace_bytes, uint32_t* rays, void* stream) {
+    if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !d_out || !workspace || H <= 0 || W <= 0 ||
+        He <= 0 || We <= 0 || spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH ||
+        !(fov_x_deg > 0.0f && fov_x_deg < 180.0f) || (d_env && (long)He * We > kBwdMaxEnvTexels) ||
+        workspace_bytes < matpbr_path_render_bwd_workspace_bytes(H, W, He, We) || ((uintptr_t)workspace & 7))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    if (!d_a && !d_r && !d_m && !d_env) return MATPBR_PATH_OK;
+    PathArgs q{};
+    q.nodes = static_cast<const float4*>(nodes);
+    q.tris = static_cast<const float4*>(tris);
+    q.a = a; q.r = r; q.m = m;
+    q.env = env; q.row_cdf = row_cdf; q.col_cdf = col_cdf; q.env_pdf = env_pdf;
+    q.out = nullptr;
+    q.rays = rays;
+    q.H = H; q.W = W; q.He = He; q.We = We; q.spp = spp; q.max_depth = max_depth;
+    const double th = std::tan(0.5 * (double)fov_x_deg * 3.14159265358979323846 / 180.0);
+    q.f_pix = (float)((0.5 * W) / th);
+    q.cx = 0.5f * (float)(W - 1);
+    q.cy = 0.5f * (float)(H - 1);
+    q.f_ndc = (float)(1.0 / th);
+    q.aspect = (float)W / (float)H;
+    q.seed_hash = pcg_hash(seed);
+    const dim3 grid((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((H + kTileY - 1) / kTileY));
+    const int n_wg = (int)(grid.x * grid.y);
+    const long P = (long)H * W;
+    const int n_env = d_env ? 3 * He * We : 0;
+    char* ws = static_cast<char*>(workspace);
+    BwdArgs b{};
+    b.d_out = d_out;
+    b.scale = reinterpret_cast<float*>(ws);
+    b.acc = reinterpret_cast<unsigned long long*>(ws + 256);
+    b.env_rows = b.acc + 5 * P;
+    b.want_a = d_a != nullptr; b.want_r = d_r != nullptr; b.want_m = d_m != nullptr; b.want_env = d_env != nullptr;
+    const hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws + 256, 0, (size_t)P * 5 * 8 + (size_t)n_wg * n_env * 8, st) != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    hipLaunchKernelGGL(path_bwd_scale_kernel, dim3(1), dim3(1024), 0, st, d_out, 3 * P, reinterpret_cast<float*>(ws));
+    if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    for (int s0 = 0; s0 < spp; s0 += spp_per_launch) {
+        const int s1 = std::min(spp, s0 + spp_per_launch);
+        hipLaunchKernelGGL(path_bwd_kernel, grid, dim3(kTileX, kTileY), (size_t)n_env * 8, st, q, b, s0, s1);
+        if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    if (d_a || d_r || d_m) {
+        hipLaunchKernelGGL(path_bwd_maps_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)b.acc, b.scale, P, spp,
+                           d_a, d_r, d_m);
+        if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    if (d_env) {
+        hipLaunchKernelGGL(path_bwd_env_kernel, dim3((unsigned)((n_env + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)b.env_rows, b.scale,
+                           n_env, n_wg, spp, d_env);
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
     }
     return MATPBR_PATH_OK;

@@ -133,7 +133,13 @@ def optimize_envmap_ARMN(scene: _render.Scene, mat: Dict[str, torch.Tensor], opt
         state["last_mse"] = mse
         return done - 1, stop, mse
 
+    path = scene.integrator == "path"     # the path-traced render: every part on the operator face (its autograd compositions)
+
     def env_phase_runner(loop_num: int, lr_of, patience: int, min_delta: float, max_epochs: int):
+        if path:
+            say(f"loop {loop_num}: env phase runs the autograd composition on the operator face (EnvHeadPhase) under the path-traced render "
+                f"(--integrator path, max_depth {scene.path['max_depth']}): the fused env phase models the deterministic render only")
+            return env_phase_runner_background(loop_num, lr_of, patience, min_delta, max_epochs)
         if background and gt.ndim != 3 and model_name == "pos_mlp":
             return env_phase_runner_background(loop_num, lr_of, patience, min_delta, max_epochs)
         graph = max_epochs > 8 and gt.is_cuda
@@ -262,8 +268,9 @@ def optimize_envmap_ARMN(scene: _render.Scene, mat: Dict[str, torch.Tensor], opt
     def brdf_part_runner_normal(loop_num: int, part: str, patience: int, min_delta: float, n_epochs: int):
         """Parts that optimise the normal map (output_type 'armn', use_mesh_normal False; :335-340,378-379,406-409), and `--use_mask` on
         predicted normals: the autograd render with the torch-composed loss (BrdfPhase) and the reference's per-epoch host EarlyStopping."""
-        say(f"loop {loop_num}: part {part!r} runs the autograd composition on the operator face (a mask under predicted normals, or 'n' alone under "
-            "the geometric normals): several times slower than the fused phases")
+        if not path:
+            say(f"loop {loop_num}: part {part!r} runs the autograd composition on the operator face (a mask under predicted normals, or 'n' alone under "
+                "the geometric normals): several times slower than the fused phases")
         ph = _loop.BrdfPhase(scene, gt, mat["albedo"], mat["roughness"], mat["metallic"], None if scene.use_mesh_normal else mat["normal"],
                              optimize_part=part, spp=spp, scale_delta=scale_delta, saver=_loop.DeviceSaveBest(), mask=mask,
                              originals=originals)
@@ -296,10 +303,10 @@ def optimize_envmap_ARMN(scene: _render.Scene, mat: Dict[str, torch.Tensor], opt
         fixed_keys = ("albedo", "roughness", "metallic") + (() if scene.use_mesh_normal else ("normal",))
         ph = _loop.PosMlpNormalPhase(scene, gt, brdf_net, start_arm, {k: mat[k] for k in fixed_keys},
                                      optimize_part=part, spp=spp, scale_delta=scale_delta, saver=_loop.DeviceSaveBest(), mask=mask)
-        if ph.engine is not None:
+        if not path and ph.engine is not None:
             say(f"loop {loop_num}: part {part!r} (pos_mlp, armn) runs launch by launch on the C ABI (PosMlpNormalPhase with armhead.MlpEngine: render, losses, "
                 "the network's layer products and AdamW; no autograd)")
-        else:
+        elif not path:
             say(f"loop {loop_num}: part {part!r} (pos_mlp) runs PosMlpNormalPhase with the network under autograd (render, losses and layer products on the C "
                 f"ABI), not a launch-by-launch phase: {ArmMlpPhase.why_not(scene, gt, brdf_net, part, mask)}")
         if saver.best_loss is not None:
@@ -328,6 +335,13 @@ def optimize_envmap_ARMN(scene: _render.Scene, mat: Dict[str, torch.Tensor], opt
         return it, ph.opt.param_groups[0]["lr"], stop
 
     def brdf_part_runner(loop_num: int, part: str, patience: int, min_delta: float, n_epochs: int):
+        if path:
+            say(f"loop {loop_num}: part {part!r} runs the autograd composition on the operator face "
+                f"({'PosMlpNormalPhase with the network under autograd' if model_name == 'pos_mlp' else 'BrdfPhase'}) under the path-traced render "
+                f"(--integrator path, max_depth {scene.path['max_depth']}): the fused phases model the deterministic render only")
+            if model_name == "pos_mlp":
+                return brdf_part_runner_mlp_normal(loop_num, part, patience, min_delta, n_epochs)
+            return brdf_part_runner_normal(loop_num, part, patience, min_delta, n_epochs)
         if model_name == "pos_mlp":
             from .armhead import ArmMlpPhase
 

@@ -3,7 +3,8 @@
 The deterministic render is direct light, unshadowed, under SH25.  The reference's *final* images come from
 Mitsuba's `path` integrator, `max_depth` 4, on the `.ply` mesh under the texel envmap (render_final.py:35-96, inverse_img_w_mi.py:
 49-52).  `PathTracer` is that render on the GPU: shadows, inter-reflection, the envmap's texels as the light.
-Forward only: no autograd.  There is no fallback: a missing or failing library raises.
+`PathTracer.render_bwd` is its backward pass (the fixed-seed estimator's derivative with the sampling detached) and `PathRenderFn`
+puts both behind autograd.  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -35,7 +36,12 @@ SIGNATURES = {
     "matpbr_path_env_sample_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_render": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                            [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P]),
+    "matpbr_path_render_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "matpbr_path_render_bwd": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
+                               [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P]),
 }
+VERSION = 2
+MAX_BWD_ENV_TEXELS = 1024
 
 
 class PathError(RuntimeError):
@@ -53,6 +59,8 @@ def load() -> ctypes.CDLL:
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
+        if lib.matpbr_path_version() != VERSION:
+            raise PathError(f"libmatpbr_path.so is version {lib.matpbr_path_version()}, this binding needs {VERSION}")
         _lib = lib
         return lib
 
@@ -136,24 +144,42 @@ class PathTracer:
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
+        self._ws: Optional[torch.Tensor] = None      # render_bwd's workspace, kept between calls
 
     def _tables(self, env: torch.Tensor):
         tab = env_tables(env.cpu().numpy())          # host, fp64 -> fp32: microseconds for the 16 x 32 maps of the pipeline
         return (env.contiguous(), *(torch.from_numpy(np.ascontiguousarray(tab[k])).to(self.device) for k in ("row_cdf", "col_cdf", "pdf")))
 
-    @torch.no_grad()
-    def render(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
-               seed: int = 0, spp_per_launch: int = 8, out: Optional[torch.Tensor] = None, rays: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """-> linear radiance [H,W,3] on the current torch stream.  albedo [H,W,3], roughness / metallic [H,W] or [H,W,1], envmap
-        [He,We,3] (tensor or array, the `sh.py` equirectangular convention).  Every split into launches of `spp_per_launch` samples gives
-        the same bits.  `rays` (optional int32 [H,W] on the device): the rays each pixel traced are added to it."""
+    def tables(self, envmap) -> tuple:
+        """(env, row_cdf, col_cdf, pdf) on the device for `render` / `render_bwd`'s `tables=`: hold them fixed across calls."""
+        env = torch.as_tensor(envmap).to(self.device, torch.float32)
+        if env.dim() != 3 or env.shape[2] != 3:
+            raise ValueError(f"envmap must be [He,We,3], got {tuple(env.shape)}")
+        return self._tables(env)
+
+    def _inputs(self, albedo, roughness, metallic, envmap, tables):
         H, W, dev = self.H, self.W, self.device
         f = lambda x, c: torch.as_tensor(x).to(dev, torch.float32).reshape(H, W, c).contiguous()
         a, r, m = f(albedo, 3), f(roughness, 1), f(metallic, 1)
-        env = torch.as_tensor(envmap).to(dev, torch.float32)
-        if env.dim() != 3 or env.shape[2] != 3:
-            raise ValueError(f"envmap must be [He,We,3], got {tuple(env.shape)}")
-        env, row, col, pdf = self._tables(env)
+        if tables is None:
+            env, row, col, pdf = self.tables(envmap)
+        else:
+            _, row, col, pdf = tables
+            env = torch.as_tensor(envmap).to(dev, torch.float32).contiguous()
+            if tuple(env.shape) != tuple(pdf.shape) + (3,):
+                raise ValueError(f"envmap {tuple(env.shape)} does not match its tables {tuple(pdf.shape)}")
+        return a, r, m, env, row, col, pdf
+
+    @torch.no_grad()
+    def render(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
+               seed: int = 0, spp_per_launch: int = 8, out: Optional[torch.Tensor] = None, rays: Optional[torch.Tensor] = None,
+               tables: Optional[tuple] = None) -> torch.Tensor:
+        """-> linear radiance [H,W,3] on the current torch stream.  albedo [H,W,3], roughness / metallic [H,W] or [H,W,1], envmap
+        [He,We,3] (tensor or array, the `sh.py` equirectangular convention).  Every split into launches of `spp_per_launch` samples gives
+        the same bits.  `rays` (optional int32 [H,W] on the device): the rays each pixel traced are added to it.  `tables`: what
+        `tables(envmap)` returned (default: built from `envmap` now)."""
+        H, W, dev = self.H, self.W, self.device
+        a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
         if out is None:
             out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -164,3 +190,80 @@ class PathTracer:
                                       rays.data_ptr() if rays is not None else None, stream)
         check(code, "matpbr_path_render")
         return out
+
+    @torch.no_grad()
+    def render_bwd(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, d_out: torch.Tensor, spp: int = 64,
+                   max_depth: int = 4, seed: int = 0, spp_per_launch: int = 8, want=("a", "r", "m", "env"), grads: Optional[dict] = None,
+                   tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The backward pass of `render` with the same arguments: d loss / d {"a" [H,W,3], "r" [H,W,1], "m" [H,W,1], "env" [He,We,3]}
+        for d_out = d loss / d render [H,W,3], for the keys in `want`.  The derivative of the fixed-seed estimator with the sampling
+        detached; bit-identical for every `spp_per_launch`.  `grads`: device buffers to ADD to (by key; the
+        missing ones start from zero).  `rays` (optional int32 [H,W]): the rays both replays traced are added to it."""
+        H, W, dev = self.H, self.W, self.device
+        a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
+        He, We = int(env.shape[0]), int(env.shape[1])
+        d_out = torch.as_tensor(d_out).to(dev, torch.float32).reshape(H, W, 3).contiguous()
+        shapes = {"a": (H, W, 3), "r": (H, W, 1), "m": (H, W, 1), "env": (He, We, 3)}
+        grads = dict(grads or {})
+        for k in want:
+            if k not in shapes:
+                raise ValueError(f"want: keys of {tuple(shapes)}, got {k!r}")
+            if k not in grads:
+                grads[k] = torch.zeros(shapes[k], device=dev, dtype=torch.float32)
+            g = grads[k]
+            if tuple(g.shape) != shapes[k] or g.dtype != torch.float32 or not g.is_contiguous() or g.device.type != dev.type:
+                raise ValueError(f"grads[{k!r}] must be contiguous float32 {shapes[k]} on {dev}")
+        if "env" in want and He * We > MAX_BWD_ENV_TEXELS:
+            raise ValueError(f"the envmap gradient needs He * We <= {MAX_BWD_ENV_TEXELS}, got {He} x {We}")
+        lib = load()
+        nbytes = int(lib.matpbr_path_render_bwd_workspace_bytes(H, W, He, We))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        ptr = lambda k: grads[k].data_ptr() if k in want else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        code = lib.matpbr_path_render_bwd(self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
+                                          env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), He, We, int(spp), int(max_depth),
+                                          int(seed) & 0xFFFFFFFF, int(spp_per_launch), d_out.data_ptr(), ptr("a"), ptr("r"), ptr("m"), ptr("env"),
+                                          self._ws.data_ptr(), nbytes, rays.data_ptr() if rays is not None else None, stream)
+        check(code, "matpbr_path_render_bwd")
+        return {k: grads[k] for k in want}
+
+
+class PathRenderFn(torch.autograd.Function):
+    """out = PathTracer.render(a, r, m, env) (bit for bit), differentiable in a [H,W,3], r [H,W,1], m [H,W,1] and env [He,We,3] by
+    `render_bwd` with the forward's seed.  `ctx_in`: {"tracer", "spp", "max_depth", "seed", "spp_per_launch"} and the envmap-table cache
+    `PathTables`."""
+
+    @staticmethod
+    def forward(ctx, a, r, m, env, ctx_in):
+        tracer = ctx_in["tracer"]
+        tabs = ctx_in["tables"].get(tracer, env)
+        kw = {k: ctx_in[k] for k in ("spp", "max_depth", "seed", "spp_per_launch")}
+        out = tracer.render(a.detach(), r.detach(), m.detach(), env.detach(), tables=tabs, **kw)
+        ctx.save_for_backward(a, r, m, env)
+        ctx.tracer, ctx.tabs, ctx.kw = tracer, tabs, kw
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        a, r, m, env = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = [k for k, n in zip(("a", "r", "m", "env"), need[:4]) if n]
+        g = ctx.tracer.render_bwd(a.detach(), r.detach(), m.detach(), env.detach(), d_out, want=want, tables=ctx.tabs, **ctx.kw) if want else {}
+        return (g["a"].reshape(a.shape) if need[0] else None, g["r"].reshape(r.shape) if need[1] else None,
+                g["m"].reshape(m.shape) if need[2] else None, g["env"].reshape(env.shape) if need[3] else None, None)
+
+
+class PathTables:
+    """The envmap's sampling tables, rebuilt only when the envmap tensor is another object or its version counter moved (an in-place
+    optimiser step)."""
+
+    def __init__(self):
+        self._key, self._tabs = None, None
+
+    def get(self, tracer: PathTracer, env: torch.Tensor) -> tuple:
+        key = (env, env._version, tuple(env.shape))
+        if self._key is None or self._key[0] is not env or self._key[1:] != key[1:]:
+            self._tabs = tracer.tables(env.detach())
+            self._key = key
+        return self._tabs
