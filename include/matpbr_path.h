@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define MATPBR_PATH_VERSION 2
+#define MATPBR_PATH_VERSION 3
 #define MATPBR_PATH_MAX_BVH_DEPTH 40 /* node levels below the root the builder may create; the kernel's traversal stack has this many entries */
 #define MATPBR_PATH_MAX_MAX_DEPTH 16 /* largest `max_depth` matpbr_path_render / matpbr_path_render_bwd accept */
 #define MATPBR_PATH_BWD_MAX_ENV_TEXELS 1024 /* largest He * We matpbr_path_render_bwd takes with d_env */

@@ -140,7 +140,7 @@ struct LdsStack {  // entry i of this lane at p[i * kBlock]: the 64 lanes of a w
 
 // ---- RNG: the PCG hash (Jarzynski & Olano 2020, "Hash Functions for GPU Rendering"), chained over the counter ---------------
 // u(seed, pixel, sample, vertex, dim) = (h >> 8) * 2^-24,  h = pcg(pcg(pcg(pcg(seed) + pixel) + sample) + vertex * 16 + dim)
-// (uint32 arithmetic throughout; tests/test_gpu_path.py restates it in numpy)
+// (uint32 arithmetic throughout; tests/path_fp64.py restates it in numpy)
 __host__ __device__ inline uint32_t pcg_hash(uint32_t v) {
     const uint32_t s = v * 747796405u + 2891336453u;
     const uint32_t w = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
@@ -288,7 +288,7 @@ struct PathArgs {
     uint32_t* rays;        // nullable: rays traced per pixel, added to (a count for reporting rates)
     int H, W, He, We, spp, max_depth;
     float f_pix, cx, cy;   // camera rays: ((x - cx)/f_pix, -(y - cy)/f_pix, -1)
-    float f_ndc, aspect;   // world_to_screen (a6): 1/tan(fov/2), W/H
+    float f_ndc, aspect;   // texel lookup: 1/tan(fov_x/2), W/H (ndc0 = f_ndc x/(-z), ndc1 = f_ndc aspect y/z)
     uint32_t seed_hash;    // pcg(seed)
 };
 
@@ -349,8 +349,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             float p[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) p[c] = fmaf(t, d[c], o[c]);
-            // material: the texel the hit point projects to (a6 world_to_screen, floor, clamped to the image: MatDiffBSDF)
-            const float ndc0 = (q.f_ndc / q.aspect) * (-p[0]) / p[2], ndc1 = q.f_ndc * p[1] / p[2];
+            // material: the texel the hit point projects to by the inverse of the camera above (one focal length for both axes; a6
+            // world_to_screen when H = W), floor, clamped to the image (MatDiffBSDF)
+            const float ndc0 = q.f_ndc * (-p[0]) / p[2], ndc1 = (q.f_ndc * q.aspect) * p[1] / p[2];
             const float sx = (ndc0 + 1.0f) * 0.5f * (float)q.W, sy = (ndc1 + 1.0f) * 0.5f * (float)q.H;
             const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
             const long tp = (long)ty * q.W + tx;
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
 // atomics), one row per workgroup in the workspace, and the rows are added in a small second launch.
 constexpr int kBwdMaxEnvTexels = MATPBR_PATH_BWD_MAX_ENV_TEXELS;   // the workgroup's LDS row: 3 x 8 bytes per texel
 constexpr float kFixClamp = 70368744177664.0f;   // 2^46 quanta
-constexpr float kRemFloor = 9.5367431640625e-7f;  // 2^-20: below kRemFloor * max_depth * L the radiance still to come is rounding
+constexpr double kRemFloor = 1.7763568394002505e-15;  // 2^-49: below kRemFloor * max_depth * L the radiance still to come is rounding
 
 struct BwdArgs {
     const float* d_out;
@@ -449,13 +450,15 @@ __device__ __forceinline__ void put_env(unsigned long long* s_env, int tx, const
     }
 }
 
-// One sample of pixel (i, j): GRAD = false adds its radiance to L (the forward kernel's walk, statement for statement); GRAD = true
-// replays it with rem = that radiance and sends the gradients of g . L to the sinks.
+// One sample of pixel (i, j): GRAD = false adds its radiance to L (the forward kernel's walk, statement for statement, each fp32 term
+// added in fp64); GRAD = true replays it with rem = that radiance, takes the same fp32 terms off in fp64, and sends the gradients of
+// g . L to the sinks.  In fp32, rem = L - (terms so far) would be off by ~2^-24 L per term: at a black metal under a sun, where the
+// radiance still to come is a small part of L and is divided by a tiny f_s, that cancellation alone made d_a several % wrong.
 template <bool GRAD>
 __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint32_t base, int i, int j, long pix, bool have_tab, LdsStack& stk,
-                                       float L[3], const float g[3], float inv_q, long long own[5], unsigned long long* s_env, uint32_t& n_rays) {
+                                       double L[3], const float g[3], float inv_q, long long own[5], unsigned long long* s_env, uint32_t& n_rays) {
     float thr[3] = {1.0f, 1.0f, 1.0f};
-    float rem[3] = {L[0], L[1], L[2]};
+    double rem[3] = {L[0], L[1], L[2]};
     const float x = (float)j - 0.5f + rng_u(base, 0, 0), y = (float)i - 0.5f + rng_u(base, 0, 1);
     float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {(x - q.cx) / q.f_pix, -(y - q.cy) / q.f_pix, -1.0f};
     {
@@ -479,7 +482,7 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
                 }
             } else {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) L[c] += thr[c] * (q.env[3 * tx + c] * w);
+                for (int c = 0; c < 3; ++c) L[c] += (double)(thr[c] * (q.env[3 * tx + c] * w));
             }
             break;
         }
@@ -498,7 +501,7 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
         float p[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) p[c] = fmaf(t, d[c], o[c]);
-        const float ndc0 = (q.f_ndc / q.aspect) * (-p[0]) / p[2], ndc1 = q.f_ndc * p[1] / p[2];
+        const float ndc0 = q.f_ndc * (-p[0]) / p[2], ndc1 = (q.f_ndc * q.aspect) * p[1] / p[2];
         const float sx = (ndc0 + 1.0f) * 0.5f * (float)q.W, sy = (ndc1 + 1.0f) * 0.5f * (float)q.H;
         const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
         const long tp = (long)ty * q.W + tx;
@@ -529,7 +532,7 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
 #pragma unroll
                             for (int c = 0; c < 3; ++c) {
                                 const float Le = q.env[3 * te + c];
-                                rem[c] -= thr[c] * (f[c] * (Le * w));
+                                rem[c] -= (double)(thr[c] * (f[c] * (Le * w)));
                                 ge[c] = g[c] * (thr[c] * (Le * w));
                                 ve[c] = g[c] * (thr[c] * (f[c] * w));
                             }
@@ -537,7 +540,7 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
                             if (b.want_env) put_env(s_env, te, ve, inv_q);
                         } else {
 #pragma unroll
-                            for (int c = 0; c < 3; ++c) L[c] += thr[c] * (f[c] * (q.env[3 * te + c] * w));
+                            for (int c = 0; c < 3; ++c) L[c] += (double)(thr[c] * (f[c] * (q.env[3 * te + c] * w)));
                         }
                     }
                 }
@@ -550,12 +553,13 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
         const float ip = ps > 1e-6f ? 1.0f / (ps + 1e-6f) : 0.0f;
         if (GRAD && want_mat) {
             if (ip > 0.0f) {   // d (f_s / (pdf_s + 1e-6)) / d theta carried by everything after this vertex: rem / f_s per channel
-                // rem is L minus at most 2 max_depth fp32 terms, each off by <= ulp(L)/2 <= 2^-24 L: a rem below 2^-20 max_depth L is
-                // that rounding (the path gathers nothing more), and dividing it by a small f_s (a black metal) would make it a gradient
+                // rem is L minus at most 2 max_depth fp32 terms in fp64, off by <= 2 max_depth 2^-53 L: a rem below kRemFloor
+                // max_depth L is that rounding (the path gathers nothing more), and dividing it by a small f_s (a black metal) would
+                // make it a gradient
                 float gs[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
-                    gs[c] = fs[c] > 0.0f && rem[c] > kRemFloor * (float)q.max_depth * L[c] ? g[c] * (rem[c] / fs[c]) : 0.0f;
+                    gs[c] = fs[c] > 0.0f && rem[c] > kRemFloor * (double)q.max_depth * L[c] ? g[c] * ((float)rem[c] / fs[c]) : 0.0f;
                 brdf_core_grad<float, false>(ln.pc, st, gs, gv, gl, gh);
             }
             put_material(b, gv, tp, pix, inv_q, own);
@@ -590,7 +594,7 @@ __global__ __launch_bounds__(kBlock) void path_bwd_kernel(const PathArgs q, cons
         uint32_t n_rays = 0;
         for (int s = s0; s < s1; ++s) {
             const uint32_t base = pcg_hash(pix_hash + (uint32_t)s);
-            float L[3] = {0.0f, 0.0f, 0.0f};
+            double L[3] = {0.0, 0.0, 0.0};
             replay<false>(q, b, base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
             replay<true>(q, b, base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
         }

@@ -40,7 +40,7 @@ SIGNATURES = {
     "matpbr_path_render_bwd": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P]),
 }
-VERSION = 2
+VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
 
 

@@ -1,7 +1,6 @@
 """The path-traced re-render on the GPU (libmatpbr_path.so): per-path parity with an fp64 numpy restatement,
 agreement with the pinned deterministic render where the two must agree, Mitsuba's max_depth semantics, bit-reproducibility, the
 reference's own Mitsuba render, and the render_final.py command line."""
-import math
 import os
 import subprocess
 import sys
@@ -13,10 +12,14 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import path_fp64 as pf  # noqa: E402  (the fp64 restatement of the integrator)
 
 pytestmark = pytest.mark.gpu
 
-FOV = 35.0
+FOV = pf.FOV
+groove_scene, _maps, _env = pf.groove_scene, pf.groove_maps, pf.groove_env
 
 
 @pytest.fixture(scope="module")
@@ -35,152 +38,6 @@ def _report(what, value):
     if path:
         with open(path, "a") as f:
             f.write(f"test_gpu_path\t{what}\t{value}\n")
-
-
-# ---- fp64 restatement of the integrator ----------------------------------------------------------------------------------------
-def pcg(v):
-    v = np.atleast_1d(np.asarray(v, dtype=np.uint32))
-    s = v * np.uint32(747796405) + np.uint32(2891336453)
-    w = ((s >> ((s >> np.uint32(28)) + np.uint32(4))) ^ s) * np.uint32(277803737)
-    return (w >> np.uint32(22)) ^ w
-
-
-def rng_u(base, vertex, dim):
-    return (pcg(base + np.uint32(vertex * 16 + dim)) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
-
-
-def brute(P, o, d):
-    """closest hit of rays o[N,3] + t d[N,3] (t > 0) on triangles P[T,3,3] -> t (inf = miss), index (-1)."""
-    e1, e2 = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
-    pv = np.cross(d[:, None], e2[None])
-    det = (e1[None] * pv).sum(-1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        tv = o[:, None] - P[None, :, 0]
-        u = (tv * pv).sum(-1) / det
-        qv = np.cross(tv, e1[None])
-        v = (d[:, None] * qv).sum(-1) / det
-        t = (e2[None] * qv).sum(-1) / det
-    t = np.where((det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t > 0), t, np.inf)
-    k = t.argmin(1)
-    tk = t[np.arange(k.shape[0]), k]
-    return tk, np.where(np.isfinite(tk), k, -1)
-
-
-def env_texel(d, He, We):
-    th = np.arccos(np.clip(d[:, 1], -1, 1))
-    ph = np.mod(np.arctan2(d[:, 0], -d[:, 2]), 2 * np.pi)
-    return np.minimum((th * He / np.pi).astype(np.int64), He - 1) * We + np.minimum((ph * We / (2 * np.pi)).astype(np.int64), We - 1)
-
-
-def mis(a, b):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        w = a * a / (a * a + b * b)
-    return np.where(np.isfinite(w), w, 0.0)
-
-
-def reference_paths(o64, V, T, a, r, m, env, tab, H, W, max_depth, seed):
-    """One sample per pixel of the integrator of DESIGN.md section 1.4, in fp64, from the oracle's sample_brdf / eval_brdf /
-    world_to_screen, a brute-force intersection, the restated RNG and the same fp32 envmap tables the kernel reads."""
-    He, We = env.shape[:2]
-    envf = env.reshape(-1, 3).astype(np.float64)
-    pdf_tab = tab["pdf"].reshape(-1).astype(np.float64)
-    row_cdf, col_cdf = tab["row_cdf"], tab["col_cdf"]
-    P = V[T]
-    nrm = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
-    nrm *= np.where((nrm * P[:, 0]).sum(-1, keepdims=True) > 0, -1.0, 1.0)
-    nrm /= np.maximum(np.linalg.norm(nrm, axis=-1, keepdims=True), 1e-300)
-    N = H * W
-    pix = np.arange(N, dtype=np.uint32)
-    base = pcg(pcg(pcg(np.uint32(seed)) + pix) + np.uint32(0))
-    ii, jj = pix // W, pix % W
-    f = (W / 2.0) / math.tan(math.radians(FOV) / 2.0)
-    x = jj - 0.5 + rng_u(base, 0, 0)
-    y = ii - 0.5 + rng_u(base, 0, 1)
-    d = np.stack([(x - (W - 1) / 2) / f, -(y - (H - 1) / 2) / f, -np.ones(N)], -1)
-    d /= np.linalg.norm(d, axis=-1, keepdims=True)
-    o = np.zeros((N, 3))
-    L, thr, prev = np.zeros((N, 3)), np.ones((N, 3)), np.zeros(N)
-    alive = np.ones(N, bool)
-    A, R, M = a.reshape(-1, 3).astype(np.float64), r.reshape(-1).astype(np.float64), m.reshape(-1).astype(np.float64)
-    for depth in range(max_depth + 1):
-        idx = np.nonzero(alive)[0]
-        if idx.size == 0:
-            break
-        t, k = brute(P, o[idx], d[idx])
-        miss = k < 0
-        im = idx[miss]
-        if im.size:
-            tx = env_texel(d[im], He, We)
-            w = np.ones(im.size) if depth == 0 else mis(prev[im], pdf_tab[tx] if tab["row_cdf"][-1] > 0 else 0.0)
-            L[im] += thr[im] * envf[tx] * w[:, None]
-        alive[im] = False
-        if depth + 1 >= max_depth:
-            alive[:] = False
-            break
-        idx, t, k = idx[~miss], t[~miss], k[~miss]
-        n = nrm[k]
-        wo = -d[idx]
-        front = (n * wo).sum(-1) > 0
-        alive[idx[~front]] = False
-        idx, t, k, n, wo = idx[front], t[front], k[front], n[front], wo[front]
-        if idx.size == 0:
-            continue
-        p = o[idx] + t[:, None] * d[idx]
-        tp = np.empty(idx.size, np.int64)
-        for q in range(idx.size):
-            s = o64.world_to_screen(p[q], np.deg2rad(FOV), W / H, 0.01, 10000.0, W, H)
-            tp[q] = int(np.clip(np.floor(s[1]), 0, H - 1)) * W + int(np.clip(np.floor(s[0]), 0, W - 1))
-        av, rv, mv = A[tp], R[tp], M[tp]
-        po = p + (1e-5 * (1 + np.abs(p).max(-1)))[:, None] * n
-        b = base[idx]
-        if tab["row_cdf"][-1] > 0:
-            u0, u1, u2, u3 = (rng_u(b, depth, c) for c in (2, 3, 4, 5))
-            row = np.searchsorted(row_cdf[:He], u0, side="right") - 1
-            col = np.array([np.searchsorted(col_cdf[rr, :We], uu, side="right") - 1 for rr, uu in zip(row, u1)])
-            c0, c1 = np.cos(row * np.pi / He), np.cos((row + 1) * np.pi / He)
-            ct = c0 + (c1 - c0) * u2
-            st = np.sqrt(np.maximum(1 - ct * ct, 0))
-            ph = (col + u3) * 2 * np.pi / We
-            wl = np.stack([st * np.sin(ph), ct, -st * np.cos(ph)], -1)
-            te = row * We + col
-            pe = pdf_tab[te]
-            fb, pb = o64.eval_brdf(wl, wo, n, av, rv, mv)
-            ok = (pe > 0) & ((n * wl).sum(-1) > 0) & (fb > 0).any(-1)
-            if ok.any():
-                ts, _ = brute(P, po[ok], wl[ok])
-                vis = np.zeros(idx.size, bool)
-                vis[np.nonzero(ok)[0]] = ~np.isfinite(ts)
-                w = np.where(vis, mis(pe, pb) / np.where(pe > 0, pe, 1.0), 0.0)
-                L[idx] += thr[idx] * fb * envf[te] * w[:, None]
-        s1, s2a, s2b = (rng_u(b, depth, c) for c in (6, 7, 8))
-        wi, pdf, wgt = o64.sample_brdf(s1, np.stack([s2a, s2b], -1), wo, n, av, rv, mv)
-        thr[idx] *= wgt
-        dead = ~(thr[idx] > 0).any(-1)
-        alive[idx[dead]] = False
-        prev[idx] = pdf
-        o[idx], d[idx] = po, wi
-    return L.reshape(H, W, 3)
-
-
-def groove_scene(H=24, W=24):
-    """A V-groove (walls facing each other: occlusion and inter-reflection) with a step across its lower rows."""
-    i, j = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
-    d = 2.0 + 0.07 * (W / 2 - np.abs(j - (W - 1) / 2))
-    d[2 * H // 3:] -= 0.35
-    return d.astype(np.float32)
-
-
-def _maps(H, W, rng):
-    a = rng.uniform(0.2, 0.9, (H, W, 3)).astype(np.float32)
-    r = rng.uniform(0.25, 0.9, (H, W, 1)).astype(np.float32)
-    m = rng.uniform(0.0, 1.0, (H, W, 1)).astype(np.float32)
-    return a, r, m
-
-
-def _env(rng, He=8, We=16):
-    env = rng.gamma(2.0, 0.4, (He, We, 3)).astype(np.float32)
-    env[1, 3] = [30.0, 28.0, 25.0]     # a sun: emitter sampling matters
-    return env
 
 
 @pytest.fixture(scope="module")
@@ -205,7 +62,7 @@ def test_every_path_matches_an_fp64_restatement(pt, groove, oracle64):
     for seed in (0, 1, 2):
         got = g["tracer"].render(g["a"], g["r"], g["m"], g["env"], spp=1, max_depth=4, seed=seed).cpu().numpy().astype(np.float64)
         assert np.isfinite(got).all()
-        ref = reference_paths(oracle64, V, g["rm"]["triangles"], g["a"], g["r"], g["m"], g["env"], tab, H, W, 4, seed)
+        ref, _ = pf.replay(oracle64, V, g["rm"]["triangles"], g["a"], g["r"], g["m"], g["env"], tab, H, W, 4, seed)
         scale = np.abs(ref).mean()
         err = (np.abs(got - ref) / np.maximum(np.abs(ref), scale)).max(-1)
         frac = float((err <= 1e-3).mean())
@@ -220,6 +77,17 @@ def test_every_path_matches_an_fp64_restatement(pt, groove, oracle64):
 
 
 def test_plane_agrees_with_the_deterministic_render(pt):
+    _plane_vs_deterministic(pt, 48, 48)
+
+
+def test_plane_agrees_with_the_deterministic_render_when_h_is_not_w(pt):
+    """The same at 32 x 56: the texel a hit reads is the inverse of the camera, so each pixel's path shades
+    with the pixel's own texel, as the deterministic render does (a lookup by a6 world_to_screen with fov_x would read another
+    pixel's texel for nearly every pixel here)."""
+    _plane_vs_deterministic(pt, 32, 56)
+
+
+def _plane_vs_deterministic(pt, H, W):
     """A camera-facing plane cannot occlude or reflect onto itself, and a constant envmap is exact in SH25: the path render converges
     to the deterministic render's integral.  Bound: K independent renders (seeds) give per-pixel estimates X_k; per 8 x 8 block b the
     mean over its 64 pixels and the K renders has standard error sigma_b = sd(X) / sqrt(64 K) (pixels and seeds use disjoint RNG
@@ -229,7 +97,6 @@ def test_plane_agrees_with_the_deterministic_render(pt):
     from materialist_amd import mesh, render
 
     dev = torch.device("cuda:0")
-    H = W = 48
     depth = np.full((H, W), 2.0, np.float32)
     rm = mesh.reference_mesh(depth, FOV)
     rng = np.random.default_rng(5)
@@ -244,14 +111,14 @@ def test_plane_agrees_with_the_deterministic_render(pt):
     with torch.no_grad():
         det = {s: render.render_w_brdf(scene, t(a), t(r), t(m), None, s).cpu().numpy().astype(np.float64) for s in (64, 128)}
     inner = (slice(8, H - 8), slice(8, W - 8))       # away from the mesh border (jittered rays off its last half pixel see the sky)
-    blk = lambda z: z[..., inner[0], inner[1], :].reshape(*z.shape[:-3], 4, 8, 4, 8, 3).mean(axis=(-4, -2))
+    blk = lambda z: z[..., inner[0], inner[1], :].reshape(*z.shape[:-3], (H - 16) // 8, 8, (W - 16) // 8, 8, 3).mean(axis=(-4, -2))
     path_b = blk(X).mean(0)
     sigma = np.sqrt(blk(X.var(0, ddof=1)[None])[0] / (64 * K))
     det_b, delta = blk(det[128]), np.abs(blk(det[128]) - blk(det[64]))
     z = np.abs(path_b - det_b) / (4 * sigma + delta)
     rel_mean = abs(X.mean(0)[inner].mean() / det[128][inner].mean() - 1)
-    _report("plane vs deterministic render: max block |diff| / (4 sigma + delta)", f"{z.max():.3f}")
-    _report("plane vs deterministic render: image-mean relative difference", f"{rel_mean:.2e}")
+    _report(f"plane vs deterministic render {H}x{W}: max block |diff| / (4 sigma + delta)", f"{z.max():.3f}")
+    _report(f"plane vs deterministic render {H}x{W}: image-mean relative difference", f"{rel_mean:.2e}")
     assert z.max() <= 1.0, (z.max(), np.unravel_index(z.argmax(), z.shape))
     assert rel_mean <= 5e-3
 

@@ -157,6 +157,12 @@ def test_host_closest_hit_matches_brute_force(mesh_and_bvh, path_lib):
     d = np.concatenate([dc, ds]).astype(np.float32)
     t_h, k_h = path_lib.trace_host(bvh, o, d)
     t_b, k_b, margin = brute_force(P, o.astype(np.float64), d.astype(np.float64))
+    hit_h = _agrees_with_brute_force(P, o, d, t_h, k_h, t_b, k_b, margin)
+    assert hit_h[:4000].mean() > 0.9 and 0.05 < hit_h[4000:].mean() < 0.95
+
+
+def _agrees_with_brute_force(P, o, d, t_h, k_h, t_b, k_b, margin):
+    """trace_host's (t_h, k_h) against the fp64 brute force's (t_b, k_b, margin) of the same rays; -> which rays trace_host hit."""
     hit_h, hit_b = k_h >= 0, k_b >= 0
     near_edge = margin < 1e-5
     # the same misses, except rays that graze an edge within fp32 rounding
@@ -174,7 +180,91 @@ def test_host_closest_hit_matches_brute_force(mesh_and_bvh, path_lib):
         _, _, m_h = brute_force(P[k_h[diff]][:, None].reshape(-1, 3, 3), o[diff].astype(np.float64), d[diff].astype(np.float64))
         tie[diff] = (np.abs(t_h[diff] - t_b[diff]) <= 1e-5 * t_b[diff]) & (near_edge[diff] | (m_h < 1e-5))
     assert not (diff & ~tie).any(), np.nonzero(diff & ~tie)[0][:10]
-    assert hit_h[:4000].mean() > 0.9 and 0.05 < hit_h[4000:].mean() < 0.95
+    return hit_h
+
+
+# ---- real size: the indoor2 mesh (512 x 512 depth, 522 k triangles) ------------------------------------------------------------
+@pytest.fixture(scope="module")
+def indoor2_bvh(path_lib, golden_dir):
+    from materialist_amd import mesh
+
+    depth = np.load(os.path.join(golden_dir, "indoor2.npz"))["depth_pred_f32"]
+    depth = 2 * depth.max() - depth                                                  # inverse_img_w_mi.py:722
+    rm = mesh.reference_mesh(depth, 35.0)
+    return rm["vertices"], rm["triangles"], path_lib.build_bvh(rm["vertices"], rm["triangles"]), depth.shape
+
+
+def test_indoor2_bvh_covers_every_triangle_once_and_nests_its_boxes(indoor2_bvh, path_lib):
+    """The invariants of test_bvh_covers_every_triangle_once_and_nests_its_boxes, vectorised, on a mesh of the pipeline's size."""
+    V, T, bvh, _ = indoor2_bvh
+    boxes, child, count = _nodes(bvh)
+    tf, ids = _tris(bvh)
+    n = bvh["n_nodes"]
+    assert boxes.shape[0] == n and T.shape[0] > 500000
+    inner = count < 0
+    # a tree: every node but the root is the child of exactly one inner slot
+    c = child[inner]
+    assert np.all((c > 0) & (c < n))
+    assert np.array_equal(np.bincount(c, minlength=n), np.r_[0, np.ones(n - 1, np.int64)])
+    # every child box of an inner node lies inside the box its parent stores for it
+    parent_box = boxes[inner]                                      # [n-1, 6]
+    for s2 in range(2):
+        used = count[c, s2] != 0
+        kid = boxes[c, s2]
+        assert np.all(kid[used, :3] >= parent_box[used, :3]) and np.all(kid[used, 3:] <= parent_box[used, 3:]), s2
+    # every triangle in exactly one leaf, inside its leaf's box
+    leaf = ~inner
+    b, cnt = child[leaf].astype(np.int64), count[leaf].astype(np.int64)
+    k = np.repeat(b - np.cumsum(cnt) + cnt, cnt) + np.arange(cnt.sum())
+    assert np.array_equal(np.bincount(ids[k], minlength=T.shape[0]), np.ones(T.shape[0], np.int64)), "every triangle in exactly one leaf"
+    lb = np.repeat(boxes[leaf], cnt, axis=0)
+    v = np.stack([tf[k, 0, :3], tf[k, 0, :3] + tf[k, 1, :3], tf[k, 0, :3] + tf[k, 2, :3]], 1)
+    assert np.all(v >= lb[:, None, :3] - 1e-6) and np.all(v <= lb[:, None, 3:] + 1e-6)
+    # depth: the deepest slot's level, as the builder reports it, within the stack the kernel has
+    level, frontier, max_level = np.zeros(n, np.int64), np.array([0]), 0
+    while frontier.size:
+        max_level = max(max_level, int(level[frontier[0]]) + 1)
+        kids = child[frontier][inner[frontier]]
+        level[kids] = level[frontier[0]] + 1
+        frontier = kids
+    assert max_level == bvh["depth"] <= path_lib.MAX_BVH_DEPTH, (max_level, bvh["depth"])
+    P = V[T[ids]]
+    np.testing.assert_allclose(tf[:, 0, :3], P[:, 0], rtol=1e-6, atol=1e-6)
+    nrm = np.cross(tf[:, 1, :3].astype(np.float64), tf[:, 2, :3].astype(np.float64))
+    assert np.all((nrm * P[:, 0]).sum(-1) <= 1e-12)
+
+
+def test_indoor2_host_closest_hit_matches_brute_force(indoor2_bvh, path_lib):
+    """trace_host on 128 rays against a float64 brute force over all 522 k triangles (tests/path_fp64.TorchBrute, no BVH): camera
+    rays, rays spawned from the surface as the render spawns them, and rays that graze the surface they leave."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import path_fp64 as pf
+
+    V, T, bvh, (H, W) = indoor2_bvh
+    rng = np.random.default_rng(17)
+    P = V[T].astype(np.float32).astype(np.float64)
+    f = (W / 2.0) / math.tan(math.radians(35.0) / 2.0)
+    x, y = rng.uniform(-0.5, W - 0.5, 48), rng.uniform(-0.5, H - 0.5, 48)
+    dc = np.stack([(x - (W - 1) / 2) / f, -(y - (H - 1) / 2) / f, -np.ones_like(x)], -1)
+    dc /= np.linalg.norm(dc, axis=-1, keepdims=True)
+    ks = rng.integers(0, T.shape[0], 80)
+    p = (P[ks] * rng.dirichlet([1, 1, 1], 80)[:, :, None]).sum(1)
+    nrm = np.cross(P[ks, 1] - P[ks, 0], P[ks, 2] - P[ks, 0])
+    nrm /= np.maximum(np.linalg.norm(nrm, axis=-1, keepdims=True), 1e-30)
+    nrm *= np.where((nrm * P[ks, 0]).sum(-1, keepdims=True) > 0, -1.0, 1.0)
+    ds = rng.normal(size=(80, 3))
+    # the last 32: grazing, a tangent of the surface tipped 0.06 to 3 degrees to its front side
+    tan = ds[48:] - (ds[48:] * nrm[48:]).sum(-1, keepdims=True) * nrm[48:]
+    tan /= np.linalg.norm(tan, axis=-1, keepdims=True)
+    ds[48:] = tan + np.tan(np.radians(rng.uniform(0.06, 3.0, 32)))[:, None] * nrm[48:]
+    ds /= np.linalg.norm(ds, axis=-1, keepdims=True)
+    os_ = p + 1e-5 * (1 + np.abs(p).max(-1, keepdims=True)) * np.where((ds * nrm).sum(-1, keepdims=True) > 0, 1.0, -1.0) * nrm
+    o = np.concatenate([np.zeros_like(dc), os_]).astype(np.float32)
+    d = np.concatenate([dc, ds]).astype(np.float32)
+    t_h, k_h = path_lib.trace_host(bvh, o, d)
+    t_b, k_b, margin = pf.TorchBrute(P).hits(o.astype(np.float64), d.astype(np.float64))
+    hit_h = _agrees_with_brute_force(P, o, d, t_h, k_h, t_b, k_b, margin)
+    assert hit_h[:48].mean() > 0.9 and 0.05 < hit_h[48:].mean() < 0.95
 
 
 def test_envmap_tables_integrate_to_one_and_sample_by_luminance(path_lib):
