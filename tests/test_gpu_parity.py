@@ -947,6 +947,9 @@ def test_optimize_envmap_ARMN_smoke():
     assert phases[:3] == [(1, "env", ""), (1, "brdf", "rm"), (1, "brdf", "a")]
     assert out["trace"][2].stop == "skip 'a' in loop 1"
     assert phases[-1][1] == "end"
+    # one image on the GPU, 16 x 32 texels, geometric normals: the texel env phase and the fused BRDF phase, for every phase / part that ran
+    assert [r[:3] for r in out["routes"]] == [p for p, t in zip(phases, out["trace"]) if t.phase != "end" and t.epoch >= 0]
+    assert {r[3] for r in out["routes"]} == {"EnvTexelPhase", "FusedBrdfPhase"}
     # 60 epochs at the reference learning rates (1e-3 / 3e-4) only start the fit; it must move in the right direction
     assert out["psnr"] > psnr0 + 0.3, (psnr0, out["psnr"])
     assert out["albedo"].shape == (H, W, 3) and out["envmap"].shape == (16, 32, 3)
@@ -995,7 +998,7 @@ def test_env_texel_phase_matches_the_framework_composition():
     assert tex.poll()["iters"].tolist() == [12]
     # the fused tail (three launches per iteration: matpbr_env_texel_phase_step) against the seven launches it replaces: the same operations in
     # the same order -- parameters, Adam moments, statistics, history and the best envmap bit for bit, with EarlyStopping armed and firing --
-    # and the same again with the iterations between two polls replayed as one unrolled graph (step_many, what optimize.env_phase_runner calls)
+    # and the same again with the iterations between two polls replayed as one unrolled graph (step_many, what optimize.py's env phase calls)
     runs = {}
     for fused, many in ((True, False), (False, False), (True, True)):
         EnvTexelPhase.FUSED_TAIL = fused
@@ -1350,6 +1353,8 @@ def test_mesh_mask_pixels_show_the_environment_and_feed_the_light(tmp_path):
         res = pipeline.inverse_image(src, model_name, opt_src="arm", opt_order=["rm", "a"], opt_env_from=0, save_path=str(tmp_path), size=32,
                                      spp=8, num_epochs=5, sync_every=5, log=lines.append, model_name=model_name)
         assert any("see the environment directly" in ln for ln in lines)
+        # pixels without geometry: the device env phases model them; pos_mlp's launch-by-launch phase does not take 32 x 32 pixels
+        assert {r[3] for r in res["routes"]} == ({"EnvTexelPhase", "FusedBrdfPhase"} if model_name == "none" else {"EnvMlpPhase", "PosMlpNormalPhase"})
         assert np.isfinite(res["psnr"]) and os.path.exists(os.path.join(res["output_dir"], "best_results", "envmap.hdr"))
 
 
@@ -1370,6 +1375,7 @@ def test_pos_mlp_with_predicted_normals_runs_and_improves(tmp_path):
     res = pipeline.inverse_image(src, "case", opt_src="arm", opt_order=["armn"], opt_env_from=0, save_path=str(tmp_path), size=32, spp=8,
                                  num_epochs=25, sync_every=5, log=lines.append, model_name="pos_mlp")
     assert any("armn" in ln for ln in lines)
+    assert {r[3] for r in res["routes"]} == {"EnvMlpPhase", "PosMlpNormalPhase"}
     n = read_exr(str(tmp_path / "case" / "best_results" / "normal.exr"))
     assert np.abs(np.linalg.norm(n, axis=-1) - 1).max() < 1e-4
     cfg = __import__("json").load(open(tmp_path / "case" / "config.json"))
@@ -1397,6 +1403,7 @@ def test_none_mode_with_n_in_the_order_runs_its_other_parts_fused(tmp_path):
     nn = [ln for ln in lines if "part 'n'" in ln]
     assert rm and all("with normals" not in ln and "normal map" not in ln for ln in rm), lines
     assert nn and all("normal map, on the device" in ln for ln in nn), lines      # NormalBrdfPhase, not the autograd composition
+    assert {(r[2], r[3]) for r in res["routes"]} == {("", "EnvTexelPhase"), ("rm", "FusedBrdfPhase"), ("n", "NormalBrdfPhase")}
     cfg = __import__("json").load(open(tmp_path / "case" / "config.json"))
     assert cfg["use_mesh_normal"] is False
     n = read_exr(str(tmp_path / "case" / "best_results" / "normal.exr"))
@@ -1736,6 +1743,7 @@ def test_use_mask_on_a_batch_is_its_images_alone():
             v = res[k][b].reshape(H, W)[mask[b]]
             assert float(v.max() - v.min()) == 0.0, (b, k)
     assert len(res["psnr_per_image"]) == B
+    assert {r[3] for r in res["routes"]} == {"FusedEnvPhase", "MaskedBatchPhase"}
 
 
 @pytest.mark.parametrize("packed", [True, False])
