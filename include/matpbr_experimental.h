@@ -21,7 +21,7 @@ int matpbr_brdf_phase_stages_timed(const MatpbrBrdfPhase* phase, int t, float lr
  *                (mlp_nt_gx; the first-layer form and the head form with stored cosines run as mode 1)
  *   1            operands by LDS-DMA, one 512-thread workgroup per CU (mlp_nt_bx<.., GL>)
  *   0            register-staged operands (mlp_nt_bx)
- *   3            as 2 with the first-layer form on mlp_nt_gx as well (23 spilled registers; measured +0.2 %: not the default)
+ *   3            as 2 with the first-layer form on mlp_nt_gx as well (measured +0.2 % when it still spilled 23 registers: not the default)
  * The three form the same products in the same order: outputs are the same bits (the bias-gradient column sums are grouped per
  * workgroup and agree to rounding).  A measurement switch, process-wide; returns the previous setting. */
 int matpbr_mlp_set_lds_dma(int mode);

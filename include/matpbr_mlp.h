@@ -202,6 +202,10 @@ int matpbr_mlp_first_layer_bwd_blk(const float* g, int ldg, const void* g_tile_m
                                    void* workspace2, size_t workspace2_bytes, long M, int n0, int n_red, MatpbrReduceJob* defer2, void* stream);
 int matpbr_mlp_layer_bwd_weight_blk(const float* g, int ldg, const void* g_tile_max, const float* x, int ldx, float* d_w, int ldw, void* workspace,
                                     size_t workspace_bytes, long M, int N, int K, MatpbrReduceJob* defer, void* stream);
+/* The kernel behind matpbr_mlp_layer_bwd_weight_blk: 1 (default) mlp_wgrad_hx, rows by LDS-DMA and the two waves of a SIMD half a step apart;
+ * 0 mlp_wgrad_bx<3>, register-staged.  Both walk the same rows and form the same products in the same order: partial sums and d_w are the same
+ * bits (tests/test_gpu_wgrad_stagger.py).  Process-wide; returns the previous setting.  (-DMATPBR_WG_HX=0 builds with 0 as the default.) */
+int matpbr_mlp_set_wgrad_kernel(int kernel);
 /* up to 8 splits in one launch (host arrays of n_jobs entries; transposed[j] = the flags of matpbr_mlp_split_weights_fmt for job j:
  * 0 / 1 as before, + MATPBR_WSPLIT_F16X2 for the f16 form): the weights of every layer change together, once per optimiser step */
 int matpbr_mlp_split_weights_multi(const float* const* w, const int* ldw, const int* N, const int* K, const int* transposed,

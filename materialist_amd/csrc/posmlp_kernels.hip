@@ -1678,7 +1678,10 @@ __global__ __launch_bounds__(kGxThreads, 2) void mlp_nt_gx(const NtArgs p, const
     }
     // eight 32 x 32 blocks per wave, b = (row half mi, column block ni); EPI_MULC: the cos operand of block b + 1 is requested
     // before block b is worked on (two sets of four registers quadruples: what one column pair took before)
-    float4 cvb[2][4];
+    // W0: ONE set, requested for block b + 1 once block b has consumed its own (behind the dW0 products): with the dW0 accumulators beside the
+    // 128 of the main product a second set does not fit 256 registers, and the rows are cache hits behind the weight gradient that just read them
+    constexpr int kCvSets = W0 ? 1 : 2;
+    float4 cvb[kCvSets][4];
     auto cv_load = [&](int b, float4 (&dst)[4]) {
       const float* src = p.cmul + (size_t)(row0 + wm * 64 + (b >> 2) * 32 + t_row) * p.ldo + wn * 128 + (b & 3) * 32 + t_col;
 #pragma unroll
@@ -1690,7 +1693,7 @@ __global__ __launch_bounds__(kGxThreads, 2) void mlp_nt_gx(const NtArgs p, const
     for (int b = 0; b < 8; ++b) {
       const int mi = b >> 2, ni = b & 3;
       const size_t o0 = (size_t)(row0 + wm * 64 + mi * 32 + t_row) * p.ldo + wn * 128 + ni * 32 + t_col;
-      if (EPI == EPI_MULC && b + 1 < 8) cv_load(b + 1, cvb[(b + 1) & 1]);
+      if (EPI == EPI_MULC && !W0 && b + 1 < 8) cv_load(b + 1, cvb[(b + 1) & (kCvSets - 1)]);
       if (HEAD && ni == 0) {
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps)
@@ -1714,7 +1717,7 @@ __global__ __launch_bounds__(kGxThreads, 2) void mlp_nt_gx(const NtArgs p, const
       for (int ps = 0; ps < 4; ++ps) {
         float4 v = *reinterpret_cast<const float4*>(scr + (t_row + 8 * ps) * kLd + t_col);
         if (EPI == EPI_MULC) {
-          float4 c4 = cvb[b & 1][ps];
+          float4 c4 = cvb[b & (kCvSets - 1)][ps];
           if (p.cmul_sin) c4 = cos_from_packed_sin(c4);
           v.x *= c4.x; v.y *= c4.y; v.z *= c4.z; v.w *= c4.w;
           csum4[ni].x += v.x; csum4[ni].y += v.y; csum4[ni].z += v.z; csum4[ni].w += v.w;
@@ -1735,12 +1738,15 @@ __global__ __launch_bounds__(kGxThreads, 2) void mlp_nt_gx(const NtArgs p, const
         vrow[ps] = v;
       }
       if (W0) {     // dW0[16 ct + i][j] += sum over the block's 32 rows of G'[row][16 ct + i] x0[row][j]  (A: lane = (i, k), B: lane = (j, k))
+        if (EPI == EPI_MULC && b + 1 < 8) cv_load(b + 1, cvb[0]);
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
+        for (int ct = 0; ct < 2; ++ct) {
 #pragma unroll
           for (int kk = 0; kk < 8; ++kk)
             acc0[ni][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(scr[(4 * kk + (lane >> 4)) * kLd + 16 * ct + (lane & 15)],
                                                                 sx[(mi * 32 + 4 * kk + (lane >> 4)) * 16 + (lane & 15)], acc0[ni][ct], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);                  // one chain's 16 operands at a time: both chains' would not fit beside the accumulators
+        }
       }
       if (HEAD) {
 #pragma unroll
@@ -1846,11 +1852,17 @@ __device__ __forceinline__ void wgrad_bx_body(const float* __restrict__ G, int l
   const int nq = wave >> 1, kq = wave & 1, li = lane & 31, lh = lane >> 5;
   const long m_begin = (long)blockIdx.x * rows_per_slab;
   const long m_end = (m_begin + rows_per_slab < M) ? m_begin + rows_per_slab : M;
-  const int steps = m_begin < m_end ? (int)((m_end - m_begin) / 16) : 0;
+  // NPROD == 3 walks its rows as mlp_wgrad_hx does (the 128-row tiles T - 1 - b, T - 1 - b - grid, ..., each from its last 16 rows to its first; M a
+  // multiple of 128): the same sums in the same order, so that it stays what mlp_wgrad_hx is compared with bit for bit
+  const int t_first = F16 ? (int)(M / kBM) - 1 - (int)blockIdx.x : 0;
+  const int steps = F16 ? (t_first >= 0 ? (t_first / (int)gridDim.x + 1) * (kBM / 16) : 0) : (m_begin < m_end ? (int)((m_end - m_begin) / 16) : 0);
+  auto step_row = [&](int step) -> long {
+    return F16 ? ((long)t_first - (long)(step >> 3) * gridDim.x) * kBM + 16 * (7 - (step & 7)) : m_begin + 16L * step;
+  };
   float g_scale = 1.0f, g_unscale = 1.0f;
   if (F16 && steps > 0) {
     unsigned mb = 0;
-    for (long t = m_begin / kBM; t <= (m_end - 1) / kBM; ++t) mb = g_tmax[t] > mb ? g_tmax[t] : mb;      // magnitudes: bit patterns order as values
+    for (int t = t_first; t >= 0; t -= (int)gridDim.x) mb = g_tmax[t] > mb ? g_tmax[t] : mb;      // magnitudes: bit patterns order as values
     block_scale(mb, g_scale, g_unscale);
   }
 
@@ -1864,14 +1876,14 @@ __device__ __forceinline__ void wgrad_bx_body(const float* __restrict__ G, int l
 
   // staging: this thread's 2 columns (pair cp of the 256 pairs of G | X) and row half sh
   const int cp = tid & 255, sh = tid >> 8;
-  const float* src = (cp >> 7) ? X + (m_begin + 8 * sh) * ldx + 2 * (cp & 127) : G + (m_begin + 8 * sh) * ldg + 2 * (cp & 127);
+  const float* src = (cp >> 7) ? X + (8 * sh) * (long)ldx + 2 * (cp & 127) : G + (8 * sh) * (long)ldg + 2 * (cp & 127);
   const long ld = (cp >> 7) ? ldx : ldg;
   const float my_scale = (F16 && !(cp >> 7)) ? g_scale : 1.0f;
   uint4* sdst = sW + (((cp >> 7) * NP) * 2 + sh) * 256 + ((cp & 127) >> 3) * 16 + (cp & 7);   // + buf * kWgStage + (piece * 2) * 256 + 8 * column
   float2 raw[kWgDepth][8];
   auto load_stage = [&](int slot, int step) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) raw[slot][j] = *reinterpret_cast<const float2*>(src + (16L * step + j) * ld);
+    for (int j = 0; j < 8; ++j) raw[slot][j] = *reinterpret_cast<const float2*>(src + (step_row(step) + j) * ld);
   };
   auto split_store = [&](int slot, int buf) {
 #pragma unroll
@@ -2007,16 +2019,24 @@ __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_bx(const float* __res
 // fold 150-153 us against 158-161 of mlp_wgrad_bx<3> on the same boxes (tools/ab.sh tools/wg_time.py "-DMATPBR_WG_HX=0").
 //   * rows: f32 as they are, 16 rows x [G | X] = 32 KB a stage, 32 one-KB pieces (eight per issuing wave, scalar bases), ring of three stages;
 //   * every thread cuts ITS 2 columns x 8 rows of the NEXT step out of the landed stage (what mlp_wgrad_bx cuts) into mlp_wgrad_bx's fragment
-//     image (one 32 KB buffer), behind the products of the CURRENT step, whose fragments are already in registers;
-//   * two barriers a step: A -- the pieces of this step are written and the rows of the next have landed; B -- everybody holds its
-//     fragments and its rows, the piece buffer and the oldest raw stage may be rewritten.
+//     image (two 32 KB buffers, step st in buffer st & 1);
+//   * the two waves of a SIMD run HALF A STEP APART, in roles fixed for the launch: a step is two half steps with one barrier each.  In the
+//     even half step of step st the loader waves (0..3) issue the DMA, read their fragments of st and their rows of st + 1, cut and store
+//     their share of the pieces of st + 1 -- the memory phase -- while waves 4..7 multiply step st - 1; in the odd half step waves 0..3
+//     multiply step st and waves 4..7 have their memory phase of step st.  So the matrix pipe of a SIMD always has one wave's products beside the
+//     other's LDS traffic and cut, instead of both waves reading together (pipe empty), multiplying together and cutting together.
+//     Hazards, all one barrier apart: the pieces of st + 1 are complete after the odd half step of st and first read in the even half of
+//     st + 1; they replace the pieces of st - 1, last read in the odd half of st - 1.  The rows of st + 1 are last read in the odd half of st;
+//     the DMA of st + 4 into their stage is issued first thing in the even half of st + 1, two steps before it is read.
+//   * 3 x 32 KB of rows + 2 x 32 KB of pieces = 160 KB: the whole LDS of a CU, nothing else lives there.
 // Same pieces, same products in the same order as mlp_wgrad_bx<3>: the same bits.
 #ifndef MATPBR_WG_HX
 #define MATPBR_WG_HX 1                         // (measurement builds: 0 = the register-staged mlp_wgrad_bx<3>)
 #endif
 constexpr int kHxRaw = 16 * 2 * 1024;                      // bytes of a raw stage: [G rows 0..15][X rows 0..15], 1 KB each
-constexpr int kHxPieces = 2 * 2 * 2 * 256;                 // uint4 of the piece buffer: [G|X][piece][row half][column slot]
-constexpr size_t kHxSmem = 3 * kHxRaw + kHxPieces * sizeof(uint4);     // 128 KB
+constexpr int kHxPieces = 2 * 2 * 2 * 256;                 // uint4 of a piece buffer: [G|X][piece][row half][column slot]
+constexpr size_t kHxSmem = 3 * kHxRaw + 2 * kHxPieces * sizeof(uint4);   // 160 KB
+static_assert(kHxSmem <= 160 * 1024, "mlp_wgrad_hx: the LDS of a CU");
 __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_hx(const float* __restrict__ G, int ldg, const float* __restrict__ X, int ldx,
                                                               float* __restrict__ partial, long M, long rows_per_slab, const unsigned* __restrict__ g_tmax) {
   extern __shared__ __align__(16) unsigned char hx_smem[];
@@ -2066,13 +2086,13 @@ __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_hx(const float* __res
     const int cp = tid & 255, sh = tid >> 8;
     const float my_scale = (cp >> 7) ? 1.0f : g_scale;
     const unsigned raw_off = (unsigned)((cp >> 7) * 16 * 1024 + (8 * sh) * 1024 + (cp & 127) * 8);          // + buf * kHxRaw + j * 1024
-    uint4* sdst = sP + (((cp >> 7) * 2) * 2 + sh) * 256 + ((cp & 127) >> 3) * 16 + (cp & 7);                  // + (piece * 2) * 256 + 8 * column
+    uint4* sdst = sP + (((cp >> 7) * 2) * 2 + sh) * 256 + ((cp & 127) >> 3) * 16 + (cp & 7);                  // + pb * kHxPieces + (piece * 2) * 256 + 8 * column
     float2 raw[8];
     auto read_raw = [&](int buf) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) raw[j] = *reinterpret_cast<const float2*>(hx_smem + buf * kHxRaw + raw_off + j * 1024);
     };
-    auto cut_store = [&]() {
+    auto cut_store = [&](int pb) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         uint4 pc[2];
@@ -2083,7 +2103,18 @@ __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_hx(const float* __res
         split2h(MATPBR_COMP(raw[6]) * my_scale, MATPBR_COMP(raw[7]) * my_scale, pc[0].w, pc[1].w);
 #undef MATPBR_COMP
 #pragma unroll
-        for (int piece = 0; piece < 2; ++piece) sdst[(piece * 2) * 256 + 8 * c] = pc[piece];
+        for (int piece = 0; piece < 2; ++piece) sdst[pb * kHxPieces + (piece * 2) * 256 + 8 * c] = pc[piece];
+      }
+    };
+    const uint4* sa = sP + lh * 256 + nq * 64 + li;                      // + pb * kHxPieces + (piece * 2) * 256 + ni * 32
+    const uint4* sb = sP + (2 * 2 + lh) * 256 + kq * 128 + li;           // + pb * kHxPieces + (piece * 2) * 256 + ki * 32
+    auto read_frags = [&](int pb, uint4 (&a)[2][2], uint4 (&b)[2][4]) {
+#pragma unroll
+      for (int piece = 0; piece < 2; ++piece) {
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) a[piece][ni] = sa[pb * kHxPieces + (piece * 2) * 256 + ni * 32];
+#pragma unroll
+        for (int ki = 0; ki < 4; ++ki) b[piece][ki] = sb[pb * kHxPieces + (piece * 2) * 256 + ki * 32];
       }
     };
     auto products = [&](const uint4 (&a)[2][2], const uint4 (&b)[2][4]) {
@@ -2097,36 +2128,47 @@ __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_hx(const float* __res
             acc[ni][ki] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[ia[t]][ni]), __builtin_bit_cast(f16x8, b[ib[t]][ki]), acc[ni][ki], 0, 0, 0);
         }
     };
-    if (loader) { issue(0, 0); issue(1, 1); }
-    if (loader) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    // half-step barrier: this wave's LDS reads have returned and its piece stores are written
+#define MATPBR_HX_BARRIER() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+    if (loader) { issue(0, 0); issue(1, 1); issue(2, 2); }
+    if (loader) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");                              // the rows of step 0 have landed
     read_raw(0);
-    cut_store();
-    if (loader) issue(2, 2);
-    const uint4* sa = sP + lh * 256 + nq * 64 + li;                      // + (piece * 2) * 256 + ni * 32
-    const uint4* sb = sP + (2 * 2 + lh) * 256 + kq * 128 + li;           // + (piece * 2) * 256 + ki * 32
-    int nxt = 1;                                                         // the raw buffer of step st + 1
-    for (int st = 0; st < steps; ++st) {
-      if (loader) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // the rows of st + 1 have landed (st + 2 in flight)
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // A: pieces of st written by everybody
-      uint4 a[2][2], b[2][4];
-#pragma unroll
-      for (int piece = 0; piece < 2; ++piece) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) a[piece][ni] = sa[(piece * 2) * 256 + ni * 32];
-#pragma unroll
-        for (int ki = 0; ki < 4; ++ki) b[piece][ki] = sb[(piece * 2) * 256 + ki * 32];
-      }
-      read_raw(nxt);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // B: everybody holds its fragments and its rows of st + 1
-      if (loader) {
-        issue(st + 3, nxt == 0 ? 2 : nxt - 1);                            // into the buffer of step st (cut during step st - 1)
+    cut_store(0);                                                        // the pieces of step 0, by everybody
+    uint4 a[2][2], b[2][4];
+    int nxt = 1;                                                         // the raw stage of step st + 1
+    if (loader) {
+      for (int st = 0; st < steps; ++st) {
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                 // the rows of st + 1 have landed (st + 2 in flight)
+        MATPBR_HX_BARRIER();                                             // even half step: the pieces of st are complete, the stage of st is free
+        issue(st + 3, nxt == 0 ? 2 : nxt - 1);
         __builtin_amdgcn_sched_barrier(0);
+        read_frags(st & 1, a, b);
+        read_raw(nxt);
+        cut_store((st + 1) & 1);                                         // (beyond the slab: of its last rows, unused)
+        MATPBR_HX_BARRIER();                                             // odd half step
+        products(a, b);
+        nxt = nxt == 2 ? 0 : nxt + 1;
       }
-      products(a, b);
-      cut_store();                                                       // the pieces of step st + 1 (beyond the slab: of its last rows, unused)
-      nxt = nxt == 2 ? 0 : nxt + 1;
+    } else {
+      MATPBR_HX_BARRIER();                                               // even half step of step 0: nothing to multiply yet
+      MATPBR_HX_BARRIER();
+      read_frags(0, a, b);
+      read_raw(1);
+      cut_store(1);
+      nxt = 2;
+      for (int st = 1; st < steps; ++st) {
+        MATPBR_HX_BARRIER();                                             // even half step of st
+        products(a, b);                                                  // step st - 1
+        MATPBR_HX_BARRIER();                                             // odd half step: the pieces of st are complete
+        read_frags(st & 1, a, b);
+        read_raw(nxt);
+        cut_store((st + 1) & 1);
+        nxt = nxt == 2 ? 0 : nxt + 1;
+      }
+      products(a, b);                                                    // the last step
     }
+#undef MATPBR_HX_BARRIER
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     // the look-ahead pieces: nothing may land after the workgroup has ended
   }
   float* out = partial + (long)blockIdx.x * 256 * 256;
@@ -2149,6 +2191,7 @@ constexpr size_t kBxSmemHead = kBxSmem + (5 * 256 + 128 * 2 * 8) * sizeof(float)
 // reported to the caller and retried at the next launch.
 std::atomic<int> g_nt_gl{2};
 std::atomic<int> g_nt_w0_gx{0};   // measurement: mode 3 of matpbr_mlp_set_lds_dma                  // LDS-DMA main loop where the shape allows (matpbr_mlp_set_lds_dma: A/B switch)
+std::atomic<int> g_wg_hx{MATPBR_WG_HX};   // the f16 weight gradient on mlp_wgrad_hx (1) or on mlp_wgrad_bx<3> (0): matpbr_mlp_set_wgrad_kernel
 inline bool gl_ok(const NtArgs& p) {
   return g_nt_gl.load(std::memory_order_relaxed) != 0 && p.K > 32 && (long)kBM * p.lda * 4 < (1l << 31);   // (a ragged K: the rows hold 32-column granules, lda >= 32 ceil(K / 32))
 }
@@ -2732,6 +2775,8 @@ inline void reduce_or_defer(const MatpbrReduceJob& q, MatpbrReduceJob* defer, hi
 
 extern "C" {
 
+int matpbr_mlp_set_wgrad_kernel(int kernel) { return g_wg_hx.exchange(kernel != 0 ? 1 : 0, std::memory_order_relaxed); }
+
 int matpbr_mlp_set_lds_dma(int mode) {
   g_nt_w0_gx.store(mode == 3 ? 1 : 0, std::memory_order_relaxed);
   const int was = g_nt_gl.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode), std::memory_order_relaxed);
@@ -3071,7 +3116,7 @@ static int mlp_layer_bwd_weight_bx_impl(const float* g, int ldg, const float* x,
   int slabs = wgrad_slabs(M);
   long rows = ((M + slabs - 1) / slabs + 15) / 16 * 16;
   slabs = (int)((M + rows - 1) / rows);
-  if (nprod == 3 && MATPBR_WG_HX && (long)ldg * 4 >= 1024 && (long)ldx * 4 >= 1024 && (long)3 * ldg * 4 + 1024 < (1l << 31) && (long)3 * ldx * 4 + 1024 < (1l << 31)) {
+  if (nprod == 3 && g_wg_hx.load(std::memory_order_relaxed) != 0 && (long)ldg * 4 >= 1024 && (long)ldx * 4 >= 1024 && (long)3 * ldg * 4 + 1024 < (1l << 31) && (long)3 * ldx * 4 + 1024 < (1l << 31)) {
     if (!lds_opt_in<&mlp_wgrad_hx>(kHxSmem)) return MATPBR_ERR_LAUNCH;
     hipLaunchKernelGGL(mlp_wgrad_hx, dim3(slabs), dim3(kWgThreads), kHxSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, g_tile_max);
   } else if (nprod == 3) {

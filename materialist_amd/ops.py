@@ -925,6 +925,12 @@ def mlp_layer_bwd_weight_blk(g: torch.Tensor, g_tile_max: torch.Tensor, x: torch
     return d_w
 
 
+def mlp_set_wgrad_kernel(kernel: int) -> int:
+    """The kernel behind `mlp_layer_bwd_weight_blk`: 1 (default) `mlp_wgrad_hx`, 0 the register-staged `mlp_wgrad_bx<3>` -- the same bits.
+    Process-wide; returns the previous setting."""
+    return int(_lib.load().matpbr_mlp_set_wgrad_kernel(int(kernel)))
+
+
 def mlp_reduce_jobs(jobs, n: int, like: torch.Tensor) -> None:
     """Every deferred fold of an iteration's backward pass in one launch (include/matpbr.h `matpbr_mlp_reduce_jobs`); jobs: a `_lib.ReduceJob` array."""
     with torch.cuda.device(like.device):
