@@ -28,6 +28,7 @@ extern "C" {
 #define MATPBR_PATH_BWD_MAX_ENV_TEXELS 1024 /* largest He * We matpbr_path_render_bwd takes with d_env */
 #define MATPBR_PATH_NODE_BYTES 64    /* one node: both children's boxes (2 x 24 B) + two child words + two counts */
 #define MATPBR_PATH_TRI_BYTES 48     /* one triangle in leaf order: (v0, id) (e1, 0) (e2, 0) as float4; e1 x e2 faces the camera */
+#define MATPBR_PATH_MAX_OBJECTS 8    /* inserted meshes matpbr_path_render_objects takes */
 
 enum {
     MATPBR_PATH_OK = 0,
@@ -35,6 +36,21 @@ enum {
     MATPBR_PATH_ERR_LAUNCH = -3,
     MATPBR_PATH_ERR_CAPACITY = -4,
 };
+
+/* BSDF of an inserted mesh ("Inserted objects") */
+enum {
+    MATPBR_PATH_BSDF_DIELECTRIC = 1, /* smooth glass, a delta BSDF: p[0] = int_ior, p[1] = ext_ior (p[2] unused) */
+    MATPBR_PATH_BSDF_DIFFUSE = 2,    /* one-sided Lambertian: p = reflectance RGB in [0, 1] */
+};
+
+/* One inserted mesh: triangles [first_tri, first_tri + n_tri) of the mesh handed to matpbr_path_bvh_build_objects (ids at or
+ * above its n_scene_tri), outward winding. */
+typedef struct MatpbrPathObject {
+    int32_t kind;
+    int32_t first_tri;
+    int32_t n_tri;
+    float p[3];
+} MatpbrPathObject;
 
 int matpbr_path_version(void);
 const char* matpbr_path_strerror(int code);
@@ -49,6 +65,12 @@ int matpbr_path_bvh_size(long n_tri, long* max_nodes);
  * array are an error. */
 int matpbr_path_bvh_build(const double* vert, long n_vert, const int32_t* tri, long n_tri, void* nodes, long max_nodes, void* tris,
                           long* n_nodes, int* depth, long* n_leaves);
+
+/* matpbr_path_bvh_build for a depth mesh with inserted meshes appended: triangles [0, n_scene_tri) are turned to the camera side
+ * as above; triangles [n_scene_tri, n_tri) keep their winding, so that e1 x e2 is the mesh's outward normal.  With n_scene_tri ==
+ * n_tri the output is matpbr_path_bvh_build's, byte for byte. */
+int matpbr_path_bvh_build_objects(const double* vert, long n_vert, const int32_t* tri, long n_tri, long n_scene_tri, void* nodes,
+                                  long max_nodes, void* tris, long* n_nodes, int* depth, long* n_leaves);
 
 /* Closest hit of N rays (origin o[N,3], direction d[N,3], hits with tmin < t < tmax) on the CPU, with the routine the kernel runs:
  * t_hit[N] (tmax where there is no hit), tri_hit[N] = triangle index of the input mesh or -1. */
@@ -73,6 +95,23 @@ int matpbr_path_env_sample_host(const float* row_cdf, const float* col_cdf, cons
 int matpbr_path_render(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
                        const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                        int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream);
+
+/* matpbr_path_render over a BVH made by matpbr_path_bvh_build_objects, forward only.  objects[n_objects] (HOST memory, copied
+ * before the call returns; n_objects <= MATPBR_PATH_MAX_OBJECTS) gives the BSDF of each range of triangle ids; ids in no range
+ * are the depth mesh and shade as in matpbr_path_render.  A dielectric vertex is a delta vertex: no emitter sample, reflection or
+ * refraction chosen by dim 6 against the exact Fresnel reflectance, and the envmap seen by its ray is added unweighted.  Ranges
+ * must not overlap; an unknown kind, an index of refraction <= 0 or a reflectance outside [0, 1] is an invalid argument.  With
+ * n_objects == 0 this is matpbr_path_render, bit for bit.  The camera is assumed to be outside every object. */
+int matpbr_path_render_objects(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                               const MatpbrPathObject* objects, int n_objects);
+
+/* The BSDF sampler of an inserted object on the CPU, with the routine the kernel runs: face normal n[3] (outward), N directions
+ * wo[N,3] towards the viewer, u[N,3] = dims 6, 7, 8 of a vertex -> wi[N,3], weight[N,3] (BSDF x cosine / pdf; 0 = the path ends),
+ * pdf[N] (solid angle; for the dielectric the probability of the chosen event), flags[N] (bit 0: delta, bit 1: transmitted). */
+int matpbr_path_object_sample_host(const MatpbrPathObject* object, const float* n, const float* wo, const float* u, long N, float* wi,
+                                   float* weight, float* pdf, int32_t* flags);
 
 /* Workspace of matpbr_path_render_bwd for an H x W image and an He x We envmap, in bytes (0 for a non-positive size). */
 size_t matpbr_path_render_bwd_workspace_bytes(int H, int W, int He, int We);

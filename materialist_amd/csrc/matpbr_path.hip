@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/matpbr_path.h"
@@ -279,6 +280,89 @@ __device__ __forceinline__ float mis_weight(float a, float b) {
     return isfinite(w) ? w : 0.0f;
 }
 
+// ---- inserted objects ("Inserted objects"): Mitsuba's smooth `dielectric` and `diffuse` ------------------
+// The table travels to the kernel by value.  An id (the triangle's index in the input mesh) in no range is the depth mesh's.
+struct ObjTable {
+    MatpbrPathObject o[MATPBR_PATH_MAX_OBJECTS];
+    int32_t n, min_id;   // min_id: the smallest first_tri, below which no lookup is needed
+};
+struct NoObjects {};   // the kernel's table when there is none
+constexpr int kFlagDelta = 1, kFlagTransmitted = 2;
+
+// kind and parameters of triangle `id` (0: the depth mesh).  Unrolled selects over wave-uniform table reads: no indexed private array.
+__device__ __forceinline__ int object_of(const NoObjects&, int, float[3]) { return 0; }
+__device__ __forceinline__ int object_of(const ObjTable& ot, int id, float p[3]) {
+    int kind = 0;
+    if (id < ot.min_id) return kind;
+#pragma unroll
+    for (int k = 0; k < MATPBR_PATH_MAX_OBJECTS; ++k) {
+        const MatpbrPathObject& ob = ot.o[k];
+        if (k < ot.n && id >= ob.first_tri && id - ob.first_tri < ob.n_tri) {
+            kind = ob.kind;
+            p[0] = ob.p[0]; p[1] = ob.p[1]; p[2] = ob.p[2];
+        }
+    }
+    return kind;
+}
+
+// exact unpolarised Fresnel reflectance of a smooth dielectric: cos_i = |n . wo|, eta_it = n_transmitted side / n_incident side;
+// cos_t written (0 at total internal reflection, where R = 1)
+__host__ __device__ inline float fresnel_dielectric(float cos_i, float eta_it, float& cos_t) {
+    const float eta_ti = 1.0f / eta_it;
+    const float cos_t2 = 1.0f - (eta_ti * eta_ti) * (1.0f - cos_i * cos_i);
+    if (!(cos_t2 > 0.0f)) { cos_t = 0.0f; return 1.0f; }
+    cos_t = sqrtf(cos_t2);
+    const float a_s = (cos_i - eta_it * cos_t) / (cos_i + eta_it * cos_t);
+    const float a_p = (cos_t - eta_it * cos_i) / (cos_t + eta_it * cos_i);
+    return 0.5f * (a_s * a_s + a_p * a_p);
+}
+
+// BSDF sample of an inserted object at a vertex with the outward face normal n and the direction wo towards the viewer; u_lobe, u0,
+// u1 = dims 6, 7, 8.  -> wi, weight = f cos / pdf (0: the path ends), pdf, flags.
+//   dielectric: u_lobe <= R reflects about n (weight 1), else refracts by Snell with weight eta_ti^2 (radiance transport; Mitsuba's
+//     `dielectric`); pdf = the probability of the event chosen.  Both sides shade: n . wo > 0 enters, < 0 leaves.
+//   diffuse: one-sided, cosine-weighted about n (sin^2 = u0, phi = 2 pi u1, the frame of Duff et al. 2017), pdf = cos / pi, weight rho.
+__host__ __device__ inline void object_sample(int kind, const float p[3], const float n[3], const float wo[3], float u_lobe, float u0, float u1,
+                                              float wi[3], float w[3], float& pdf, int& flags) {
+    const float cos_o = dot3h(n, wo);
+    if (kind == MATPBR_PATH_BSDF_DIELECTRIC) {
+        const float eta = p[0] / p[1];
+        const bool entering = cos_o > 0.0f;
+        const float eta_it = entering ? eta : 1.0f / eta, eta_ti = entering ? 1.0f / eta : eta;
+        const float ci = fabsf(cos_o);
+        float ct;
+        const float R = fresnel_dielectric(ci, eta_it, ct);
+        if (u_lobe <= R) {
+            for (int c = 0; c < 3; ++c) wi[c] = 2.0f * cos_o * n[c] - wo[c];
+            w[0] = w[1] = w[2] = 1.0f;
+            pdf = R;
+            flags = kFlagDelta;
+        } else {
+            const float s = (entering ? 1.0f : -1.0f) * (eta_ti * ci - ct);   // along the normal on wo's side
+            for (int c = 0; c < 3; ++c) wi[c] = s * n[c] - eta_ti * wo[c];
+            w[0] = w[1] = w[2] = eta_ti * eta_ti;
+            pdf = 1.0f - R;
+            flags = kFlagDelta | kFlagTransmitted;
+        }
+        return;
+    }
+    flags = 0;
+    if (!(cos_o > 0.0f)) {   // seen from inside
+        wi[0] = wi[1] = wi[2] = 0.0f;
+        w[0] = w[1] = w[2] = 0.0f;
+        pdf = 0.0f;
+        return;
+    }
+    const float st = sqrtf(fmaxf(u0, 0.0f)), ct = sqrtf(fmaxf(1.0f - u0, 0.0f));
+    const float ph = 6.28318530717958647692f * u1;
+    const float x = st * cosf(ph), y = st * sinf(ph);
+    const float sg = copysignf(1.0f, n[2]), a = -1.0f / (sg + n[2]), b = n[0] * n[1] * a;
+    const float s[3] = {1.0f + sg * n[0] * n[0] * a, sg * b, -sg * n[0]}, t[3] = {b, sg + n[1] * n[1] * a, -n[1]};
+    for (int c = 0; c < 3; ++c) wi[c] = s[c] * x + t[c] * y + n[c] * ct;
+    for (int c = 0; c < 3; ++c) w[c] = p[c];
+    pdf = ct * 0.31830988618379067154f;
+}
+
 struct PathArgs {
     const float4* nodes;
     const float4* tris;
@@ -295,8 +379,12 @@ struct PathArgs {
 // spawn offset along the (camera-side) face normal, relative to the point's magnitude
 __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1.0f + fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]))); }
 
-// samples [s0, s1) of every pixel added to out (first: start from 0; last: divide by spp)
-__global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last) {
+// samples [s0, s1) of every pixel added to out (first: start from 0; last: divide by spp).  OBJ: the BVH holds inserted objects
+// (Objects = ObjTable, passed by value); with NoObjects every `if (OBJ ...)` below folds away and the walk is the depth mesh's alone,
+// the code the kernel had before there were objects.
+template <class Objects>
+__global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
+    constexpr bool OBJ = !std::is_empty<Objects>::value;
     __shared__ int s_stack[kStack * kBlock];
     const int tid = threadIdx.y * kTileX + threadIdx.x;
     const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
@@ -323,13 +411,14 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             for (int c = 0; c < 3; ++c) d[c] *= il;
         }
         float prev_pdf = 0.0f;
+        bool prev_delta = false;   // (OBJ) the ray left a delta vertex: no emitter sample competed with it
         for (int depth = 0;; ++depth) {
             float t = FLT_MAX;
             ++n_rays;
             const int k = trace<false>(q.nodes, q.tris, o, d, 0.0f, t, stk);
             if (k < 0) {   // escaped: the envmap, MIS-weighted against emitter sampling after a BSDF sample
                 const int tx = env_texel(d, q.He, q.We);
-                const float w = depth == 0 ? 1.0f : mis_weight(prev_pdf, have_tab ? q.env_pdf[tx] : 0.0f);
+                const float w = depth == 0 || (OBJ && prev_delta) ? 1.0f : mis_weight(prev_pdf, have_tab ? q.env_pdf[tx] : 0.0f);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) L[c] += thr[c] * (q.env[3 * tx + c] * w);
                 break;
@@ -345,7 +434,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 for (int c = 0; c < 3; ++c) n[c] *= il;
             }
             const float wo[3] = {-d[0], -d[1], -d[2]};
-            if (!(dot3(n, wo) > 0.0f)) break;      // a hit on the back of a triangle ends the path
+            int kind = 0;          // (OBJ) 0: the depth mesh; else the inserted object's BSDF and its parameters
+            float op[3] = {0.0f, 0.0f, 0.0f};
+            if (OBJ) kind = object_of(ot, __float_as_int(q.tris[3 * k].w), op);
+            // a hit on the back of a triangle ends the path (glass shades from both sides)
+            if (!(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !(dot3(n, wo) > 0.0f)) break;
             float p[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) p[c] = fmaf(t, d[c], o[c]);
@@ -354,20 +447,26 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             const float ndc0 = q.f_ndc * (-p[0]) / p[2], ndc1 = (q.f_ndc * q.aspect) * p[1] / p[2];
             const float sx = (ndc0 + 1.0f) * 0.5f * (float)q.W, sy = (ndc1 + 1.0f) * 0.5f * (float)q.H;
             const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
-            const long tp = (long)ty * q.W + tx;
+            const long tp = OBJ && kind != 0 ? 0 : (long)ty * q.W + tx;   // an object reads no texel
             const float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
             const float eps = spawn_eps(p);
             float po[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
-            // emitter sample with a shadow ray
-            if (have_tab) {
+            // emitter sample with a shadow ray (none at a delta vertex)
+            if (have_tab && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC)) {
                 float wl[3], pdf_e;
                 const int te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
                                           rng_u(base, depth, 4), rng_u(base, depth, 5), wl, pdf_e);
                 if (pdf_e > 0.0f && dot3(n, wl) > 0.0f) {
                     float f[3], pdf_b;
-                    path_eval(wl, wo, n, av, rv, mv, f, pdf_b);
+                    if (OBJ && kind == MATPBR_PATH_BSDF_DIFFUSE) {   // f cos = rho / pi max(n . wi, 0), pdf = cos / pi
+                        pdf_b = dot3(n, wl) * kInvPi;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) f[c] = op[c] * pdf_b;
+                    } else {
+                        path_eval(wl, wo, n, av, rv, mv, f, pdf_b);
+                    }
                     if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
                         float ts = FLT_MAX;
                         ++n_rays;
@@ -381,7 +480,17 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             }
             // BSDF sample: the next ray
             float wi[3], wgt[3], pdf_s;
-            path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, wgt, pdf_s);
+            if (OBJ && kind != 0) {
+                int flags;
+                object_sample(kind, op, n, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
+                prev_delta = (flags & kFlagDelta) != 0;
+                const float side = dot3(n, wi) > 0.0f ? eps : -eps;   // spawn on the side the new ray leaves on
+#pragma unroll
+                for (int c = 0; c < 3; ++c) po[c] = fmaf(side, n[c], p[c]);
+            } else {
+                path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, wgt, pdf_s);
+                if (OBJ) prev_delta = false;
+            }
 #pragma unroll
             for (int c = 0; c < 3; ++c) thr[c] *= wgt[c];
             if (!(thr[0] > 0.0f || thr[1] > 0.0f || thr[2] > 0.0f)) break;
@@ -397,7 +506,6 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     for (int c = 0; c < 3; ++c) q.out[3 * pix + c] = last ? acc[c] * sc : acc[c];
     if (q.rays) q.rays[pix] += n_rays;
 }
-
 // ---- backward pass ("Gradients") ------------------------------------------------------------------------
 // The exact derivative of the fixed-seed estimator with the sampling detached: directions, pdfs, MIS weights, lobe choices and the
 // envmap tables are constants; the gradient flows through the BSDF value f (trailing cosine included) at every vertex and through
@@ -766,6 +874,32 @@ struct Builder {
     }
 };
 
+// the caller's objects, checked, as the kernel's table
+bool object_valid(const MatpbrPathObject& ob) {
+    if (ob.first_tri < 0 || ob.n_tri < 0 || ob.n_tri > INT32_MAX - ob.first_tri) return false;
+    if (ob.kind == MATPBR_PATH_BSDF_DIELECTRIC) return ob.p[0] > 0.0f && ob.p[1] > 0.0f && std::isfinite(ob.p[0]) && std::isfinite(ob.p[1]);
+    if (ob.kind == MATPBR_PATH_BSDF_DIFFUSE) {
+        for (int c = 0; c < 3; ++c)
+            if (!(ob.p[c] >= 0.0f && ob.p[c] <= 1.0f)) return false;
+        return true;
+    }
+    return false;
+}
+bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot) {
+    if (n_objects < 0 || n_objects > MATPBR_PATH_MAX_OBJECTS || (n_objects > 0 && !objects)) return false;
+    ot.n = n_objects;
+    ot.min_id = INT32_MAX;
+    for (int k = 0; k < n_objects; ++k) {
+        if (!object_valid(objects[k])) return false;
+        for (int j = 0; j < k; ++j)   // ranges may not overlap
+            if (objects[k].first_tri < objects[j].first_tri + objects[j].n_tri && objects[j].first_tri < objects[k].first_tri + objects[k].n_tri)
+                return false;
+        ot.o[k] = objects[k];
+        ot.min_id = std::min(ot.min_id, objects[k].first_tri);
+    }
+    return true;
+}
+
 }  // namespace
 
 // =================================================================================================================================
@@ -779,7 +913,7 @@ const char* matpbr_path_strerror(int code) {
     switch (code) {
         case MATPBR_PATH_OK: return "ok";
         case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, max_depth outside 1..16, "
-                                                  "a workspace too small, or an envmap of more than 1024 texels with d_env)";
+                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, or a bad object table)";
         case MATPBR_PATH_ERR_LAUNCH: return "HIP kernel launch failed";
         case MATPBR_PATH_ERR_CAPACITY: return "node buffer smaller than matpbr_path_bvh_size() asks for";
         default: return "unknown error";
@@ -794,7 +928,13 @@ int matpbr_path_bvh_size(long n_tri, long* max_nodes) {
 
 int matpbr_path_bvh_build(const double* vert, long n_vert, const int32_t* tri, long n_tri, void* nodes, long max_nodes, void* tris,
                           long* n_nodes, int* depth, long* n_leaves) {
-    if (!vert || !tri || !nodes || !tris || !n_nodes || !depth || !n_leaves || n_vert <= 0 || n_tri < 0 || n_tri > INT32_MAX / 3)
+    return matpbr_path_bvh_build_objects(vert, n_vert, tri, n_tri, n_tri, nodes, max_nodes, tris, n_nodes, depth, n_leaves);
+}
+
+int matpbr_path_bvh_build_objects(const double* vert, long n_vert, const int32_t* tri, long n_tri, long n_scene_tri, void* nodes,
+                                  long max_nodes, void* tris, long* n_nodes, int* depth, long* n_leaves) {
+    if (!vert || !tri || !nodes || !tris || !n_nodes || !depth || !n_leaves || n_vert <= 0 || n_tri < 0 || n_tri > INT32_MAX / 3 ||
+        n_scene_tri < 0 || n_scene_tri > n_tri)
         return MATPBR_PATH_ERR_INVALID_ARG;
     long need = 0;
     matpbr_path_bvh_size(n_tri, &need);
@@ -833,7 +973,8 @@ int matpbr_path_bvh_build(const double* vert, long n_vert, const int32_t* tri, l
         double e1[3], e2[3];
         for (int c = 0; c < 3; ++c) { e1[c] = v1[c] - v0[c]; e2[c] = v2[c] - v0[c]; }
         const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
-        if (nx * v0[0] + ny * v0[1] + nz * v0[2] > 0.0) std::swap(e1, e2);   // e1 x e2 faces the camera at the origin
+        // depth mesh: e1 x e2 faces the camera at the origin; an inserted mesh keeps its winding (e1 x e2 = its outward normal)
+        if (t < n_scene_tri && nx * v0[0] + ny * v0[1] + nz * v0[2] > 0.0) std::swap(e1, e2);
         int32_t id = t;
         float idf;
         std::memcpy(&idf, &id, 4);
@@ -921,9 +1062,30 @@ int matpbr_path_env_sample_host(const float* row_cdf, const float* col_cdf, cons
     return MATPBR_PATH_OK;
 }
 
+int matpbr_path_object_sample_host(const MatpbrPathObject* object, const float* n, const float* wo, const float* u, long N, float* wi,
+                                   float* weight, float* pdf, int32_t* flags) {
+    if (!object || !n || !wo || !u || !wi || !weight || !pdf || !flags || N < 0 || !object_valid(*object)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        int fl = 0;
+        object_sample(object->kind, object->p, n, wo + 3 * k, u[3 * k], u[3 * k + 1], u[3 * k + 2], wi + 3 * k, weight + 3 * k, pdf[k], fl);
+        flags[k] = fl;
+    }
+    return MATPBR_PATH_OK;
+}
+
 int matpbr_path_render(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
                        const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                        int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream) {
+    return matpbr_path_render_objects(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
+                                      spp_per_launch, out, rays, stream, nullptr, 0);
+}
+
+int matpbr_path_render_objects(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                               const MatpbrPathObject* objects, int n_objects) {
+    ObjTable ot{};
+    if (!object_table(objects, n_objects, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
     if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !out || H <= 0 || W <= 0 || He <= 0 || We <= 0 ||
         spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f))
         return MATPBR_PATH_ERR_INVALID_ARG;
@@ -945,7 +1107,9 @@ int matpbr_path_render(const void* nodes, const void* tris, const float* a, cons
     const dim3 grid((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((H + kTileY - 1) / kTileY));
     for (int s0 = 0; s0 < spp; s0 += spp_per_launch) {
         const int s1 = std::min(spp, s0 + spp_per_launch);
-        hipLaunchKernelGGL(path_kernel, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, s0 == 0 ? 1 : 0, s1 == spp ? 1 : 0);
+        const int first = s0 == 0 ? 1 : 0, last = s1 == spp ? 1 : 0;
+        if (n_objects > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ot);
+        else hipLaunchKernelGGL(path_kernel<NoObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, NoObjects{});
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
     }
     return MATPBR_PATH_OK;

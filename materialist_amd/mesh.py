@@ -91,6 +91,92 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
     return V.copy(), faces["v"].copy()
 
 
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply_any(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """A PLY somebody else wrote (an inserted object, `oi.ply`) -> (vertices [Nv,3] float64, triangles [Nt,3] int32).  ASCII or
+    binary little-endian; x, y, z of any scalar type, other vertex properties (normals, colours, uv) skipped; faces as one
+    `list uchar|uint8|int ... vertex_indices` of 3 or more vertices, fan-triangulated; elements after the faces are not read.
+    Vertex normals are ignored: inserted meshes shade flat.  Anything else is a ValueError naming the file."""
+    def bad(why):
+        return ValueError(f"{path}: {why}")
+
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise bad("not a PLY file")
+        fmt, elements = None, []                      # elements: [name, count, [(property name, type) | (name, count type, item type)]]
+        while True:
+            raw = fh.readline()
+            if not raw:
+                raise bad("header without end_header")
+            tok = raw.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property":
+                if not elements:
+                    raise bad("property before any element")
+                elements[-1][2].append((tok[-1], tok[2], tok[3]) if tok[1] == "list" else (tok[-1], tok[1]))
+            elif tok[0] == "end_header":
+                break
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise bad(f"format {fmt!r} is not supported (ascii and binary_little_endian are)")
+        V = T = None
+        for name, count, props in elements:
+            for pr in props:
+                if any(t not in _PLY_TYPES for t in pr[1:]):
+                    raise bad(f"property {pr[0]!r} has an unknown type")
+            if name == "vertex":
+                if any(len(pr) != 2 for pr in props) or any(c not in [pr[0] for pr in props] for c in "xyz"):
+                    raise bad("the vertex element needs scalar properties x, y and z")
+                names = [pr[0] for pr in props]
+                if fmt == "ascii":
+                    rows = np.array([fh.readline().split() for _ in range(count)], dtype=np.float64).reshape(count, -1)
+                    if rows.shape[1] < len(props):
+                        raise bad("a vertex line is shorter than its properties")
+                    V = np.stack([rows[:, names.index(c)] for c in "xyz"], -1)
+                else:
+                    dt = np.dtype([(n, "<" + _PLY_TYPES[t]) for n, t in props])
+                    buf = fh.read(count * dt.itemsize)
+                    if len(buf) != count * dt.itemsize:
+                        raise bad("the vertex data ends early")
+                    rec = np.frombuffer(buf, dtype=dt)
+                    V = np.stack([rec[c].astype(np.float64) for c in "xyz"], -1)
+            elif name == "face":
+                if len(props) != 1 or len(props[0]) != 3:
+                    raise bad("the face element must be one list property")
+                ct, it = np.dtype("<" + _PLY_TYPES[props[0][1]]), np.dtype("<" + _PLY_TYPES[props[0][2]])
+                if ct.kind not in "iu" or it.kind not in "iu":
+                    raise bad("the face list must hold integers")
+                tris = []
+                for _ in range(count):
+                    if fmt == "ascii":
+                        tok = fh.readline().split()
+                        n = int(tok[0]) if tok else 0
+                        idx = [int(x) for x in tok[1:1 + n]]
+                    else:
+                        head = fh.read(ct.itemsize)
+                        n = int(np.frombuffer(head, dtype=ct)[0]) if len(head) == ct.itemsize else 0
+                        idx = np.frombuffer(fh.read(n * it.itemsize), dtype=it).tolist()
+                    if n < 3 or len(idx) != n:
+                        raise bad("a face with fewer than 3 vertices, or the face data ends early")
+                    tris.extend((idx[0], idx[k], idx[k + 1]) for k in range(1, n - 1))
+                T = np.array(tris, dtype=np.int64).reshape(-1, 3)
+                break                                  # nothing after the faces is needed
+            else:
+                raise bad(f"element {name!r} before the faces is not supported")
+    if V is None or T is None:
+        raise bad("needs a vertex and a face element")
+    if T.size and (T.min() < 0 or T.max() >= V.shape[0]):
+        raise bad("a face index is outside the vertex array")
+    return V, T.astype(np.int32)
+
+
 def vertex_normals(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:
     """Area-weighted mean of the adjacent face normals per vertex, oriented towards the camera at the origin."""
     V, T = np.asarray(vertices, np.float64), np.asarray(triangles, np.int64)

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes
 import threading
 import time
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -25,17 +25,29 @@ _lock = threading.Lock()
 NODE_BYTES = 64
 TRI_BYTES = 48
 MAX_BVH_DEPTH = 40
+MAX_OBJECTS = 8
+BSDF_DIELECTRIC, BSDF_DIFFUSE = 1, 2
+
+
+class PathObject(ctypes.Structure):
+    """MatpbrPathObject (include/matpbr_path.h): the BSDF of one range of triangle ids."""
+    _fields_ = [("kind", ctypes.c_int32), ("first_tri", ctypes.c_int32), ("n_tri", ctypes.c_int32), ("p", ctypes.c_float * 3)]
+
 
 SIGNATURES = {
     "matpbr_path_version": (ctypes.c_int, []),
     "matpbr_path_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "matpbr_path_bvh_size": (ctypes.c_int, [ctypes.c_long, _P]),
     "matpbr_path_bvh_build": (ctypes.c_int, [_P, ctypes.c_long, _P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _P, _P]),
+    "matpbr_path_bvh_build_objects": (ctypes.c_int, [_P, ctypes.c_long, _P, ctypes.c_long, ctypes.c_long, _P, ctypes.c_long, _P, _P, _P, _P]),
     "matpbr_path_trace_host": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_long, ctypes.c_float, ctypes.c_float, _P, _P]),
     "matpbr_path_env_tables": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "matpbr_path_env_sample_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_render": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                            [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P]),
+    "matpbr_path_render_objects": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
+                                   [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int]),
+    "matpbr_path_object_sample_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 4),
     "matpbr_path_render_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "matpbr_path_render_bwd": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P]),
@@ -75,8 +87,10 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def build_bvh(vertices: np.ndarray, triangles: np.ndarray) -> Dict[str, object]:
-    """Host BVH of a triangle mesh: {"nodes" uint8 [n_nodes*64], "tris" uint8 [T*48], "n_nodes", "depth", "n_leaves", "build_s"}."""
+def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional[int] = None) -> Dict[str, object]:
+    """Host BVH of a triangle mesh: {"nodes" uint8 [n_nodes*64], "tris" uint8 [T*48], "n_nodes", "depth", "n_leaves", "build_s"}.
+    `n_scene_tri`: triangles from this index on belong to inserted meshes and keep their winding (`matpbr_path_bvh_build_objects`);
+    None = every triangle is the depth mesh's (`matpbr_path_bvh_build`)."""
     lib = load()
     V = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
     T = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
@@ -86,11 +100,14 @@ def build_bvh(vertices: np.ndarray, triangles: np.ndarray) -> Dict[str, object]:
     tris = np.zeros(max(T.shape[0], 1) * TRI_BYTES, dtype=np.uint8)
     n_nodes, depth, n_leaves = ctypes.c_long(0), ctypes.c_int(0), ctypes.c_long(0)
     t0 = time.perf_counter()
-    code = lib.matpbr_path_bvh_build(_ptr(V), V.shape[0], _ptr(T), T.shape[0], _ptr(nodes), cap.value, _ptr(tris),
-                                     ctypes.cast(ctypes.byref(n_nodes), _P), ctypes.cast(ctypes.byref(depth), _P),
-                                     ctypes.cast(ctypes.byref(n_leaves), _P))
+    outs = (ctypes.cast(ctypes.byref(n_nodes), _P), ctypes.cast(ctypes.byref(depth), _P), ctypes.cast(ctypes.byref(n_leaves), _P))
+    if n_scene_tri is None:
+        code = lib.matpbr_path_bvh_build(_ptr(V), V.shape[0], _ptr(T), T.shape[0], _ptr(nodes), cap.value, _ptr(tris), *outs)
+    else:
+        code = lib.matpbr_path_bvh_build_objects(_ptr(V), V.shape[0], _ptr(T), T.shape[0], int(n_scene_tri), _ptr(nodes), cap.value, _ptr(tris),
+                                                 *outs)
     build_s = time.perf_counter() - t0
-    check(code, "matpbr_path_bvh_build")
+    check(code, "matpbr_path_bvh_build" if n_scene_tri is None else "matpbr_path_bvh_build_objects")
     return {"nodes": nodes[: n_nodes.value * NODE_BYTES].copy(), "tris": tris, "n_nodes": n_nodes.value, "depth": depth.value,
             "n_leaves": n_leaves.value, "build_s": build_s}
 
@@ -131,16 +148,89 @@ def env_sample_host(tables: Dict[str, object], u: np.ndarray):
     return d, p, k
 
 
+def object_bsdf(bsdf: dict) -> tuple:
+    """{"type": "dielectric", "int_ior", "ext_ior"} | {"type": "diffuse", "reflectance"} -> (kind, (p0, p1, p2)); ValueError when bad."""
+    kind = bsdf.get("type") if isinstance(bsdf, dict) else None
+    if kind == "dielectric":
+        p = (float(bsdf.get("int_ior", 1.49)), float(bsdf.get("ext_ior", 1.000277)), 0.0)
+        if not (p[0] > 0 and p[1] > 0 and np.isfinite(p[:2]).all()):
+            raise ValueError(f"dielectric: int_ior and ext_ior must be positive, got {p[0]}, {p[1]}")
+        return BSDF_DIELECTRIC, p
+    if kind == "diffuse":
+        rho = np.broadcast_to(np.asarray(bsdf.get("reflectance", 0.5), dtype=np.float64), (3,))
+        if not ((rho >= 0) & (rho <= 1)).all():
+            raise ValueError(f"diffuse: reflectance must lie in [0, 1], got {rho.tolist()}")
+        return BSDF_DIFFUSE, tuple(float(x) for x in rho)
+    raise ValueError(f"object bsdf type must be 'dielectric' or 'diffuse', got {kind!r}")
+
+
+def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict]):
+    """The depth mesh with the inserted meshes appended -> (V [Nv,3] float64, T [Nt,3] int32, [PathObject]).  Object k's triangles
+    follow the scene's in the order given; its ids are its range of T."""
+    V = [np.asarray(vertices, dtype=np.float64).reshape(-1, 3)]
+    T = [np.asarray(triangles, dtype=np.int32).reshape(-1, 3)]
+    if len(objects) > MAX_OBJECTS:
+        raise ValueError(f"at most {MAX_OBJECTS} inserted objects, got {len(objects)}")
+    table: List[PathObject] = []
+    nv, nt = V[0].shape[0], T[0].shape[0]
+    for k, ob in enumerate(objects):
+        kind, p = object_bsdf(ob.get("bsdf"))
+        Vo = np.asarray(ob["vertices"], dtype=np.float64)
+        To = np.asarray(ob["triangles"])
+        if Vo.ndim != 2 or Vo.shape[1] != 3 or To.ndim != 2 or To.shape[1] != 3 or To.shape[0] == 0:
+            raise ValueError(f"object {k}: vertices must be [Nv,3] and triangles [Nt,3] (Nt > 0), got {Vo.shape} and {To.shape}")
+        if not np.isfinite(Vo).all():
+            raise ValueError(f"object {k}: vertices must be finite")
+        if not np.issubdtype(To.dtype, np.integer) or To.min() < 0 or To.max() >= Vo.shape[0]:
+            raise ValueError(f"object {k}: triangle indices must be integers in [0, {Vo.shape[0]})")
+        V.append(Vo)
+        T.append((To.astype(np.int64) + nv).astype(np.int32))
+        table.append(PathObject(kind, nt, To.shape[0], (ctypes.c_float * 3)(*p)))
+        nv, nt = nv + Vo.shape[0], nt + To.shape[0]
+    return np.concatenate(V), np.concatenate(T), table
+
+
+def object_sample_host(bsdf: dict, n: np.ndarray, wo: np.ndarray, u: np.ndarray):
+    """The kernel's BSDF sampler of an inserted object on the CPU: outward face normal n [3], wo [N,3], u [N,3] (dims 6, 7, 8) ->
+    (wi [N,3], weight [N,3], pdf [N], flags [N]: bit 0 delta, bit 1 transmitted)."""
+    kind, p = object_bsdf(bsdf)
+    ob = PathObject(kind, 0, 0, (ctypes.c_float * 3)(*p))
+    nn = np.ascontiguousarray(n, dtype=np.float32).reshape(3)
+    WO = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
+    U = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 3)
+    if U.shape[0] != WO.shape[0]:
+        raise ValueError(f"wo and u must have the same rows, got {WO.shape[0]} and {U.shape[0]}")
+    N = WO.shape[0]
+    wi, w = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
+    pdf, flags = np.empty(N, np.float32), np.empty(N, np.int32)
+    check(load().matpbr_path_object_sample_host(ctypes.cast(ctypes.byref(ob), _P), _ptr(nn), _ptr(WO), _ptr(U), N, _ptr(wi), _ptr(w), _ptr(pdf),
+                                                _ptr(flags)), "matpbr_path_object_sample_host")
+    return wi, w, pdf, flags
+
+
 class PathTracer:
     """One mesh in the renderer's frame (camera at the origin looking down -z, `fov_x_deg` horizontal field of view, H x W pixels).
-    The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame."""
+    The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
+    `objects`: meshes inserted into the scene ("Inserted objects"), in the same frame, outward winding, a list
+    of {"vertices" [Nv,3], "triangles" [Nt,3], "bsdf": {"type": "dielectric", "int_ior": 1.49, "ext_ior": 1.000277} or
+    {"type": "diffuse", "reflectance": (r, g, b)}}.  A tracer with objects renders forward only."""
 
-    def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda"):
+    def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
+                 objects: Optional[Sequence[dict]] = None):
         self.H, self.W, self.fov = int(H), int(W), float(fov_x_deg)
         self.device = torch.device(device)
-        bvh = build_bvh(vertices, triangles)
+        n_scene = int(np.asarray(triangles).reshape(-1, 3).shape[0])
+        self.objects = None
+        if objects:
+            vertices, triangles, table = merge_objects(vertices, triangles, objects)
+            self.objects = (PathObject * len(table))(*table)
+            bvh = build_bvh(vertices, triangles, n_scene)
+        else:
+            bvh = build_bvh(vertices, triangles)
         self.stats = {k: bvh[k] for k in ("n_nodes", "depth", "n_leaves", "build_s")}
         self.stats["n_tris"] = int(np.asarray(triangles).reshape(-1, 3).shape[0])
+        self.stats["n_objects"] = len(self.objects) if self.objects is not None else 0
+        self.stats["n_object_tris"] = self.stats["n_tris"] - n_scene
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -184,11 +274,14 @@ class PathTracer:
             out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
         stream = torch.cuda.current_stream(dev).cuda_stream
         lib = load()
-        code = lib.matpbr_path_render(self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
-                                      env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]),
-                                      int(spp), int(max_depth), int(seed) & 0xFFFFFFFF, int(spp_per_launch), out.data_ptr(),
-                                      rays.data_ptr() if rays is not None else None, stream)
-        check(code, "matpbr_path_render")
+        args = (self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
+                env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]),
+                int(spp), int(max_depth), int(seed) & 0xFFFFFFFF, int(spp_per_launch), out.data_ptr(),
+                rays.data_ptr() if rays is not None else None, stream)
+        if self.objects is None:
+            check(lib.matpbr_path_render(*args), "matpbr_path_render")
+        else:
+            check(lib.matpbr_path_render_objects(*args, ctypes.cast(self.objects, _P), len(self.objects)), "matpbr_path_render_objects")
         return out
 
     @torch.no_grad()
@@ -199,6 +292,8 @@ class PathTracer:
         for d_out = d loss / d render [H,W,3], for the keys in `want`.  The derivative of the fixed-seed estimator with the sampling
         detached; bit-identical for every `spp_per_launch`.  `grads`: device buffers to ADD to (by key; the
         missing ones start from zero).  `rays` (optional int32 [H,W]): the rays both replays traced are added to it."""
+        if self.objects is not None:
+            raise ValueError("render_bwd knows no inserted objects: build the PathTracer without `objects` for gradients")
         H, W, dev = self.H, self.W, self.device
         a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
         He, We = int(env.shape[0]), int(env.shape[1])

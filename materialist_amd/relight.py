@@ -6,7 +6,7 @@ deterministic render is linear in the light, so the per-pixel transfer is comput
 frame is a 75-term dot product per pixel (`matpbr_relight`, HBM-bound).  Rolling the envmap by whole texel columns is the
 SH rotation about +y by the same angle (`sh.rotate_y_matrix`), so no envmap is ever re-projected or written to disk.
 Material editing inside `best_results/mask.png` (`edit=` of `render_w_mi`, :143-181) is applied to the maps before the
-transfer is computed.  Object insertion (`--mode oi`, :100-141,207-237) needs extra meshes and is not part of this build.
+transfer is computed.  Object insertion (`--mode oi`, :100-141,207-237,263-288) is `render_oi`: it always path traces.
 `integrator="path"` renders instead with the path tracer (materialist_amd/pathtrace.py), the integrator the
 reference's final images come from: the `.ply` mesh, shadows, inter-reflection, the envmap's texels as the light; rolling frames
 roll the envmap's texel columns.
@@ -160,9 +160,9 @@ def _scene_normal(scene_dir: str, mat: Dict[str, torch.Tensor], save_name: str, 
     return ops.normals_from_depth(torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(device))
 
 
-def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], device):
+def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], device, objects=None):
     """PathTracer on the scene's `<save_name>.ply`; without one, the mesh the pipeline would write (depthPred.exr -> 2 max - d,
-    mesh_mask.png pixels removed, mesh.reference_mesh: inverse_img_w_mi.py:721-727)."""
+    mesh_mask.png pixels removed, mesh.reference_mesh: inverse_img_w_mi.py:721-727).  `objects`: PathTracer's inserted meshes."""
     from . import mesh as _mesh
     from .pathtrace import PathTracer
     from .render import DEFAULT_FOV
@@ -179,7 +179,7 @@ def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], d
             depth[mm.numpy()] = 0.0
         rm = _mesh.reference_mesh(depth, DEFAULT_FOV)
         V, T = rm["vertices"], rm["triangles"]
-    return PathTracer(V, T, H, W, DEFAULT_FOV, device=device)
+    return PathTracer(V, T, H, W, DEFAULT_FOV, device=device, objects=objects)
 
 
 def _check_integrator(integrator: str) -> None:
@@ -207,6 +207,65 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
     base = os.path.join(out_dir, f"mi_{save_name}_{env_id}_{edit_flag}")   # (:199-202)
+    write_exr(base + ".exr", img.cpu().numpy())
+    write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
+    return base + ".png"
+
+
+# Mitsuba's named indices of refraction for the reference's inserted glass (render_final.py:126): "acrylic glass" and "air"
+OI_INT_IOR, OI_EXT_IOR = 1.49, 1.000277
+OI_REFLECTANCE = 0.8                                  # the second inserted mesh: diffuse, reflectance 0.8 (render_final.py:131)
+
+
+def find_envmap_oi(save_name: str, env_path: Optional[str], input_path: Optional[str]) -> str:
+    """render_final.py:263-287: explicit path, else best_results/envmap_opt.hdr before best_results/envmap.hdr, the input tree before
+    the default tree."""
+    if env_path is not None:
+        return env_path
+    roots = ([os.path.join(input_path, save_name)] if input_path is not None else []) + [os.path.join(OUT_DIR, save_name)]
+    for root in roots:
+        for name in ("envmap_opt.hdr", "envmap.hdr"):
+            c = os.path.join(root, "best_results", name)
+            if os.path.exists(c):
+                return c
+    raise ValueError("No envmap found")
+
+
+def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
+              spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda") -> str:
+    """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
+    1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
+    mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
+    The meshes are in the renderer's frame, read by `mesh.read_ply_any`, and shade flat.  `n_iter` renders with seeds seed + i are
+    averaged.  There is no denoiser here: the reference renders spp 32 x 10 and denoises each with OptiX, so
+    the samples do the denoiser's work (default spp 64 x 10)."""
+    from . import mesh as _mesh
+
+    scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
+    plys = [os.path.join(scene_dir, "oi.ply"), os.path.join(scene_dir, "oi2.ply")]
+    bsdfs = [{"type": "dielectric", "int_ior": OI_INT_IOR, "ext_ior": OI_EXT_IOR}, {"type": "diffuse", "reflectance": (OI_REFLECTANCE,) * 3}]
+    have = [(p, b) for p, b in zip(plys, bsdfs) if os.path.exists(p)]
+    if not have:
+        raise FileNotFoundError(f"object insertion needs {plys[0]} (glass) or {plys[1]} (diffuse); neither exists")
+    if n_iter < 1:
+        raise ValueError(f"n_iter must be at least 1, got {n_iter}")
+    env_path = find_envmap_oi(save_name, env_path, input_path)
+    objects = []
+    for p, b in have:
+        V, T = _mesh.read_ply_any(p)
+        objects.append({"vertices": V, "triangles": T, "bsdf": b})
+    mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
+    pt = _path_tracer(scene_dir, save_name, mat, device, objects)
+    env = load_image(env_path)
+    tabs = pt.tables(env)
+    img = torch.zeros_like(mat["albedo"])
+    for i in range(n_iter):
+        img += pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp, max_depth, seed + i, tables=tabs)
+    img /= n_iter
+    env_id = os.path.basename(env_path)[:-4]
+    out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
+    os.makedirs(out_dir, exist_ok=True)
+    base = os.path.join(out_dir, f"mi_oi_{save_name}_{env_id}")              # (:233-236)
     write_exr(base + ".exr", img.cpu().numpy())
     write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
     return base + ".png"

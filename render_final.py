@@ -12,7 +12,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter, description="re-render an optimised scene under new lighting")
     ap.add_argument("--env_path", required=False, default=None, type=str)
     ap.add_argument("--save_name", required=True, type=str)
-    ap.add_argument("--mode", required=True, type=str, help="real, rolling (oi = object insertion is not part of this build)")
+    ap.add_argument("--mode", required=True, type=str, help="real, rolling, or oi (object insertion: <scene>/oi.ply as glass and <scene>/oi2.ply as a diffuse object, path traced)")
     ap.add_argument("--input_path", required=False, default=None, type=str)
     ap.add_argument("--save_path", required=False, default=None, type=str)
     ap.add_argument("--frames", type=int, default=36)
@@ -24,9 +24,12 @@ def parse_args(argv=None):
     ap.add_argument("--edit_metallic", type=float, default=None, help="constant metallic inside the mask")
     ap.add_argument("--integrator", choices=("sh", "path"), default="sh",
                     help="sh: the deterministic render (direct light under SH25, no shadows); path: the path tracer on the scene's .ply "
-                         "(Mitsuba's `path` as the reference renders its final images: shadows, inter-reflection, the envmap's texels)")
+                         "(Mitsuba's `path` as the reference renders its final images: shadows, inter-reflection, the envmap's texels); "
+                         "ignored by --mode oi, which always path traces")
     ap.add_argument("--max_depth", type=int, default=4, help="--integrator path: Mitsuba's max_depth (1 emission, 2 direct + shadows, 4 the reference's)")
-    ap.add_argument("--seed", type=int, default=0, help="--integrator path: random seed")
+    ap.add_argument("--seed", type=int, default=0, help="--integrator path and --mode oi: random seed")
+    ap.add_argument("--oi_iters", type=int, default=10, help="--mode oi: renders averaged (seeds seed, seed + 1, ...)")
+    ap.add_argument("--oi_max_depth", type=int, default=16, help="--mode oi: Mitsuba's max_depth (a camera path through glass needs 5 to see light)")
     return ap.parse_args(argv)
 
 
@@ -43,7 +46,7 @@ def main(argv=None):
                                             **it)
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
-        raise NotImplementedError("object insertion (render_final.py:100-141,207-237) is not part of this build")
+        print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed))
     else:
         raise ValueError("Invalid mode")
 
