@@ -52,6 +52,14 @@ typedef struct MatpbrPathObject {
     float p[3];
 } MatpbrPathObject;
 
+/* Transparency editing ("Transparency editing"): the reference's TransBSDF where the mask is set. */
+typedef struct MatpbrPathTransEdit {
+    float ior;              /* index of refraction of the glass, > 0 (trans_edit.py --ior, default 1.2) */
+    float spec_trans;       /* specTrans in [0, 1] (default 0.4) */
+    float refract_distance; /* the sheet's thickness scale D >= 0: the lookup walks 0.3 D into the glass and D out of it (100) */
+    float reserved;
+} MatpbrPathTransEdit;
+
 int matpbr_path_version(void);
 const char* matpbr_path_strerror(int code);
 
@@ -112,6 +120,28 @@ int matpbr_path_render_objects(const void* nodes, const void* tris, const float*
  * pdf[N] (solid angle; for the dielectric the probability of the chosen event), flags[N] (bit 0: delta, bit 1: transmitted). */
 int matpbr_path_object_sample_host(const MatpbrPathObject* object, const float* n, const float* wo, const float* u, long N, float* wi,
                                    float* weight, float* pdf, int32_t* flags);
+
+/* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
+ * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;
+ * `edit` is HOST memory, copied before the call returns.  Where the texel a vertex reads is masked, the BSDF is the glass of
+ * DESIGN.md section 1.4 over bg at the refracted texel; elsewhere it is matpbr_path_render's value, and at every vertex the pdf
+ * clamps VoH at 1e-4 and the sample weight is f / (pdf + 1e-4).  Invalid arguments: ior <= 0, spec_trans outside [0, 1], a negative
+ * or non-finite refract_distance, a null mask or bg.  There is no variant with inserted objects. */
+int matpbr_path_render_trans(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                             float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                             int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                             const uint8_t* mask, const float* bg, const MatpbrPathTransEdit* edit);
+
+/* The masked branch of the edited BSDF on the CPU, with the routine the kernel runs: per lane the face normal n[N,3], wo[N,3] towards
+ * the viewer, wi[N,3] towards the light (either side of the surface), the texel's a[N,3] r[N] m[N] and bg[N,3] at the refracted
+ * texel -> f[N,3] (with its cosine) and pdf[N]. */
+int matpbr_path_trans_eval_host(const MatpbrPathTransEdit* edit, const float* n, const float* wo, const float* wi, const float* a,
+                                const float* r, const float* m, const float* bg, long N, float* f, float* pdf);
+
+/* The edit's texel lookups on the CPU, with the routine the kernel runs: hit points p[N,3], face normals n[N,3], wo[N,3] in an
+ * H x W image -> texel[N] (the point's own, row * W + col) and texel_refracted[N] (where bg is read). */
+int matpbr_path_trans_lookup_host(const MatpbrPathTransEdit* edit, const float* p, const float* n, const float* wo, long N, int H, int W,
+                                  float fov_x_deg, int32_t* texel, int32_t* texel_refracted);
 
 /* Workspace of matpbr_path_render_bwd for an H x W image and an He x We envmap, in bytes (0 for a non-positive size). */
 size_t matpbr_path_render_bwd_workspace_bytes(int H, int W, int He, int We);

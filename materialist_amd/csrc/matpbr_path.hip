@@ -363,6 +363,96 @@ __host__ __device__ inline void object_sample(int kind, const float p[3], const 
     pdf = ct * 0.31830988618379067154f;
 }
 
+// ---- transparency editing ("Transparency editing"): TransBSDF (myutils/mi_plugin.py:1477-1771) -----------
+// Where mask[tp] is set the depth mesh shades as a sheet of glass in front of the photograph `bg`, read at the texel a ray refracted
+// twice through the sheet lands on.  The edit travels to the kernel by value, in the place of the object table.  The masked-branch
+// arithmetic and the lookup are __host__ __device__ (plain divisions and sqrtf): the CPU entry points run what the kernel runs.
+struct TransEdit {
+    const uint8_t* mask;   // [H,W], non-zero = edited
+    const float* bg;       // [H,W,3]
+    float ior, spec_trans, refract_distance;
+};
+__device__ __forceinline__ int object_of(const TransEdit&, int, float[3]) { return 0; }
+
+// the texel a point projects to ("Material at a hit": floor, clamped to the image; a NaN coordinate clamps to 0)
+__host__ __device__ inline long screen_texel(const float p[3], float f_ndc, float aspect, int H, int W) {
+    const float ndc0 = f_ndc * (-p[0]) / p[2], ndc1 = (f_ndc * aspect) * p[1] / p[2];
+    const float sx = (ndc0 + 1.0f) * 0.5f * (float)W, sy = (ndc1 + 1.0f) * 0.5f * (float)H;
+    const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(H - 1));
+    return (long)ty * W + tx;
+}
+// calculate_refraction (:1494-1501): w refracted about n with the ratio eta, normalised
+__host__ __device__ inline void trans_refract(const float w[3], const float n[3], float eta, float out[3]) {
+    const float c = dot3h(w, n);
+    const float s2 = fmaxf(0.0f, 1.0f - c * c);
+    const float ct = sqrtf(fmaxf(0.0f, 1.0f - eta * eta * s2));
+    for (int k = 0; k < 3; ++k) out[k] = eta * (n[k] * c - w[k]) - n[k] * ct;
+    const float il = 1.0f / sqrtf(dot3h(out, out));
+    for (int k = 0; k < 3; ++k) out[k] *= il;
+}
+// calculate_refracted_screen_coor (:1503-1519): into the sheet for 0.3 D, out of it for D, and the texel of that point
+__host__ __device__ inline long trans_lookup(float ior, float dist, const float p[3], const float n[3], const float wo[3], float f_ndc,
+                                             float aspect, int H, int W) {
+    float d1[3], d2[3], p2[3];
+    trans_refract(wo, n, ior, d1);
+    const float md1[3] = {-d1[0], -d1[1], -d1[2]};
+    trans_refract(md1, n, 1.0f / ior, d2);
+    for (int k = 0; k < 3; ++k) p2[k] = (p[k] + (0.3f * dist) * d1[k]) + dist * d2[k];
+    return screen_texel(p2, f_ndc, aspect, H, W);
+}
+// eval_brdf's masked branch (:1650-1724): f (RGB, with its cosine) and the pdf.  The GGX denominator takes 1 - NoH^2 from n x h
+// where n is a unit vector (ggx_den_stable's form: the literal one loses its digits on the peak).
+__host__ __device__ inline void trans_eval(float ior, float T, const float n[3], const float wo[3], const float wi[3], const float a[3], float r,
+                                           float m, const float bg[3], float f[3], float& pdf) {
+    const float kInvPiF = 0.31830988618379067154f;
+    float h[3] = {wi[0] + wo[0], wi[1] + wo[1], wi[2] + wo[2]};
+    const float il = 1.0f / sqrtf(dot3h(h, h));
+    for (int k = 0; k < 3; ++k) h[k] *= il;
+    const float nh_raw = dot3h(n, h);
+    const float NoL = fmaxf(dot3h(n, wi), 0.0f), NoV = fmaxf(dot3h(n, wo), 0.0f), VoH = fmaxf(dot3h(wo, h), 0.0f), NoH = fmaxf(nh_raw, 0.0f);
+    const float LoH = fmaxf(dot3h(wi, h), 0.0f);
+    const float alpha2 = (r * r) * (r * r);
+    float den;
+    if (fabsf(dot3h(n, n) - 1.0f) < 1e-5f && nh_raw > 0.0f) {
+        float cr[3];
+        cross3(n, h, cr);
+        den = (alpha2 + dot3h(cr, cr) * (1.0f - alpha2)) + 1e-6f;
+    } else {
+        den = (NoH * NoH * (alpha2 - 1.0f) + 1.0f) + 1e-6f;
+    }
+    const float D = alpha2 * kInvPiF / (den * den);
+    pdf = 0.5f * (D / (4.0f * fmaxf(VoH, 1e-4f)) * NoH) + 0.5f * (NoL * kInvPiF);
+    if (!(pdf > 0.0f)) pdf = 0.0f;
+    const float k = (r + 1.0f) * (r + 1.0f) * 0.125f;
+    const float G = (1.0f / (NoL * (1.0f - k) + k + 1e-6f)) * (1.0f / (NoV * (1.0f - k) + k + 1e-6f));
+    const float x = 1.0f - VoH, x5 = (x * x) * (x * x) * x;
+    float glass;   // f_glass without its colour
+    const bool reflect = NoL * NoV > 0.0f;
+    if (reflect) {
+        glass = D * G * 0.25f * (NoL + 1e-6f);
+    } else {   // btdf_glass (:1702-1712), literally: of order 1e-6, not zero
+        const float hw_in = 1.0f / (LoH + 1e-6f), hw_out = 1.0f / (VoH + 1e-6f);
+        const float nw_in = 1.0f / (NoL + 1e-6f), nw_out = 1.0f / (NoV + 1e-6f);
+        const float R_s = (hw_in - ior * hw_out) / (hw_in + ior * hw_out), R_p = (ior * hw_in - hw_out) / (ior * hw_in + hw_out);
+        const float F_glass = 0.5f * (R_s * R_s + R_p * R_p);
+        const float e = 1.0f + 1e-6f, D_hack = kInvPiF / (e * e);   // D_GGX(NoH, 1)
+        const float q = ior * hw_in + hw_out;
+        glass = G * D_hack * (1.0f - F_glass) * (ior * ior * hw_in * hw_out) / (nw_in * nw_out * (q * q));
+    }
+    for (int c = 0; c < 3; ++c) {
+        const float kd = a[c] * (1.0f - m) * (1.0f - T);
+        const float C0 = (1.0f - m) * 0.04f + m * a[c];
+        const float F_m = C0 + (1.0f - C0) * x5;
+        const float bcg = (1.0f - m) * (bg[c] * T);
+        const float v = kd * kInvPiF * NoL + D * G * F_m * 0.25f * NoL + (reflect ? bcg : sqrtf(bcg)) * glass;
+        f[c] = v > 0.0f ? v : 0.0f;
+    }
+}
+// the pdf of the unmasked branch while the edit is on: MatDiffBSDF's mixture with TransBSDF's clamp of VoH, 1e-4 (:1658)
+__device__ __forceinline__ float trans_pdf(const PLane& ln, const BrdfState<float>& st) {
+    return fmaf(0.125f * (st.D * ln.NoH), rcp(fmaxf(ln.VoH, 1e-4f)), (0.5f * kInvPi) * st.NoL);
+}
+
 struct PathArgs {
     const float4* nodes;
     const float4* tris;
@@ -380,11 +470,13 @@ struct PathArgs {
 __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1.0f + fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]))); }
 
 // samples [s0, s1) of every pixel added to out (first: start from 0; last: divide by spp).  OBJ: the BVH holds inserted objects
-// (Objects = ObjTable, passed by value); with NoObjects every `if (OBJ ...)` below folds away and the walk is the depth mesh's alone,
-// the code the kernel had before there were objects.
+// (Objects = ObjTable, passed by value); EDIT: transparency editing (Objects = TransEdit, by value in the table's place).  With
+// NoObjects every `if (OBJ ...)` and `if (EDIT ...)` below folds away and the walk is the depth mesh's alone, the code the kernel had
+// before there were objects; with ObjTable every `if (EDIT ...)` folds away.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool OBJ = !std::is_empty<Objects>::value;
+    constexpr bool OBJ = std::is_same<Objects, ObjTable>::value;
+    constexpr bool EDIT = std::is_same<Objects, TransEdit>::value;
     __shared__ int s_stack[kStack * kBlock];
     const int tid = threadIdx.y * kTileX + threadIdx.x;
     const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
@@ -449,6 +541,16 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
             const long tp = OBJ && kind != 0 ? 0 : (long)ty * q.W + tx;   // an object reads no texel
             const float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+            bool masked = false;   // (EDIT) the vertex reads a masked texel: TransBSDF's glass over bg at the refracted texel
+            float bgv[3] = {0.0f, 0.0f, 0.0f};
+            if constexpr (EDIT) {
+                masked = ot.mask[tp] != 0;
+                if (masked) {
+                    const long tq = trans_lookup(ot.ior, ot.refract_distance, p, n, wo, q.f_ndc, q.aspect, q.H, q.W);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) bgv[c] = ot.bg[3 * tq + c];
+                }
+            }
             const float eps = spawn_eps(p);
             float po[3];
 #pragma unroll
@@ -464,6 +566,13 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                         pdf_b = dot3(n, wl) * kInvPi;
 #pragma unroll
                         for (int c = 0; c < 3; ++c) f[c] = op[c] * pdf_b;
+                    } else if (EDIT && masked) {
+                        if constexpr (EDIT) trans_eval(ot.ior, ot.spec_trans, n, wo, wl, av, rv, mv, bgv, f, pdf_b);
+                    } else if (EDIT) {   // MatDiffBSDF's value, TransBSDF's pdf
+                        PLane ln;
+                        BrdfState<float> st;
+                        path_eval_st(wl, wo, n, av, rv, mv, ln, st, f, pdf_b);
+                        pdf_b = trans_pdf(ln, st);
                     } else {
                         path_eval(wl, wo, n, av, rv, mv, f, pdf_b);
                     }
@@ -487,6 +596,19 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 const float side = dot3(n, wi) > 0.0f ? eps : -eps;   // spawn on the side the new ray leaves on
 #pragma unroll
                 for (int c = 0; c < 3; ++c) po[c] = fmaf(side, n[c], p[c]);
+            } else if (EDIT) {   // MatDiffBSDF's directions; weight f / (pdf + 1e-4) where pdf > 0, masked or not (:1612-1615)
+                PLane ln;
+                BrdfState<float> st;
+                float f[3], pt;
+                path_sample_st(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, ln, st, f, pt);
+                pt = trans_pdf(ln, st);
+                if constexpr (EDIT) {
+                    if (masked) trans_eval(ot.ior, ot.spec_trans, n, wo, wi, av, rv, mv, bgv, f, pt);
+                }
+                const float ip = pt > 0.0f ? 1.0f / (pt + 1e-4f) : 0.0f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) wgt[c] = f[c] > 0.0f ? f[c] * ip : 0.0f;
+                pdf_s = pt > 0.0f ? pt : 0.0f;
             } else {
                 path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, wgt, pdf_s);
                 if (OBJ) prev_delta = false;
@@ -913,7 +1035,7 @@ const char* matpbr_path_strerror(int code) {
     switch (code) {
         case MATPBR_PATH_OK: return "ok";
         case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, max_depth outside 1..16, "
-                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, or a bad object table)";
+                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, a bad object table or a bad transparency edit)";
         case MATPBR_PATH_ERR_LAUNCH: return "HIP kernel launch failed";
         case MATPBR_PATH_ERR_CAPACITY: return "node buffer smaller than matpbr_path_bvh_size() asks for";
         default: return "unknown error";
@@ -1080,12 +1202,11 @@ int matpbr_path_render(const void* nodes, const void* tris, const float* a, cons
                                       spp_per_launch, out, rays, stream, nullptr, 0);
 }
 
-int matpbr_path_render_objects(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
-                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
-                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
-                               const MatpbrPathObject* objects, int n_objects) {
-    ObjTable ot{};
-    if (!object_table(objects, n_objects, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
+// the three renders: `edit` (nullable) selects the transparency-editing instantiation, else n_objects > 0 the object one
+static int render_common(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
+                         const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
+                         int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream, const ObjTable& ot,
+                         int n_objects, const TransEdit* edit) {
     if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !out || H <= 0 || W <= 0 || He <= 0 || We <= 0 ||
         spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f))
         return MATPBR_PATH_ERR_INVALID_ARG;
@@ -1108,9 +1229,57 @@ int matpbr_path_render_objects(const void* nodes, const void* tris, const float*
     for (int s0 = 0; s0 < spp; s0 += spp_per_launch) {
         const int s1 = std::min(spp, s0 + spp_per_launch);
         const int first = s0 == 0 ? 1 : 0, last = s1 == spp ? 1 : 0;
-        if (n_objects > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ot);
+        if (edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, *edit);
+        else if (n_objects > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ot);
         else hipLaunchKernelGGL(path_kernel<NoObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, NoObjects{});
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    return MATPBR_PATH_OK;
+}
+
+static bool trans_edit_valid(const MatpbrPathTransEdit* e) {
+    return e && e->ior > 0.0f && std::isfinite(e->ior) && e->spec_trans >= 0.0f && e->spec_trans <= 1.0f && e->refract_distance >= 0.0f &&
+           std::isfinite(e->refract_distance);
+}
+
+int matpbr_path_render_objects(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                               const MatpbrPathObject* objects, int n_objects) {
+    ObjTable ot{};
+    if (!object_table(objects, n_objects, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
+    return render_common(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out,
+                         rays, stream, ot, n_objects, nullptr);
+}
+
+int matpbr_path_render_trans(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                             float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                             int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                             const uint8_t* mask, const float* bg, const MatpbrPathTransEdit* edit) {
+    if (!mask || !bg || !trans_edit_valid(edit)) return MATPBR_PATH_ERR_INVALID_ARG;
+    const TransEdit te{mask, bg, edit->ior, edit->spec_trans, edit->refract_distance};
+    return render_common(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out,
+                         rays, stream, ObjTable{}, 0, &te);
+}
+
+int matpbr_path_trans_eval_host(const MatpbrPathTransEdit* edit, const float* n, const float* wo, const float* wi, const float* a,
+                                const float* r, const float* m, const float* bg, long N, float* f, float* pdf) {
+    if (!trans_edit_valid(edit) || !n || !wo || !wi || !a || !r || !m || !bg || !f || !pdf || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k)
+        trans_eval(edit->ior, edit->spec_trans, n + 3 * k, wo + 3 * k, wi + 3 * k, a + 3 * k, r[k], m[k], bg + 3 * k, f + 3 * k, pdf[k]);
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_trans_lookup_host(const MatpbrPathTransEdit* edit, const float* p, const float* n, const float* wo, long N, int H, int W,
+                                  float fov_x_deg, int32_t* texel, int32_t* texel_refracted) {
+    if (!trans_edit_valid(edit) || !p || !n || !wo || !texel || !texel_refracted || N < 0 || H <= 0 || W <= 0 ||
+        !(fov_x_deg > 0.0f && fov_x_deg < 180.0f))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    const double th = std::tan(0.5 * (double)fov_x_deg * 3.14159265358979323846 / 180.0);
+    const float f_ndc = (float)(1.0 / th), aspect = (float)W / (float)H;   // as the render sets them
+    for (long k = 0; k < N; ++k) {
+        texel[k] = (int32_t)screen_texel(p + 3 * k, f_ndc, aspect, H, W);
+        texel_refracted[k] = (int32_t)trans_lookup(edit->ior, edit->refract_distance, p + 3 * k, n + 3 * k, wo + 3 * k, f_ndc, aspect, H, W);
     }
     return MATPBR_PATH_OK;
 }

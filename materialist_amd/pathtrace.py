@@ -34,6 +34,11 @@ class PathObject(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("first_tri", ctypes.c_int32), ("n_tri", ctypes.c_int32), ("p", ctypes.c_float * 3)]
 
 
+class PathTransEdit(ctypes.Structure):
+    """MatpbrPathTransEdit (include/matpbr_path.h): the scalars of a transparency edit."""
+    _fields_ = [("ior", ctypes.c_float), ("spec_trans", ctypes.c_float), ("refract_distance", ctypes.c_float), ("reserved", ctypes.c_float)]
+
+
 SIGNATURES = {
     "matpbr_path_version": (ctypes.c_int, []),
     "matpbr_path_strerror": (ctypes.c_char_p, [ctypes.c_int]),
@@ -48,6 +53,10 @@ SIGNATURES = {
     "matpbr_path_render_objects": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                    [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int]),
     "matpbr_path_object_sample_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 4),
+    "matpbr_path_render_trans": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
+                                 [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, _P, _P]),
+    "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
+    "matpbr_path_trans_lookup_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
     "matpbr_path_render_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "matpbr_path_render_bwd": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P]),
@@ -208,6 +217,51 @@ def object_sample_host(bsdf: dict, n: np.ndarray, wo: np.ndarray, u: np.ndarray)
     return wi, w, pdf, flags
 
 
+def trans_edit(ior: float = 1.2, spec_trans: float = 0.4, refract_distance: float = 100.0) -> PathTransEdit:
+    """The scalars of a transparency edit, checked as the library checks them; ValueError when bad."""
+    ior, spec_trans, refract_distance = float(ior), float(spec_trans), float(refract_distance)
+    if not (ior > 0 and np.isfinite(ior)):
+        raise ValueError(f"ior must be positive and finite, got {ior}")
+    if not 0.0 <= spec_trans <= 1.0:
+        raise ValueError(f"spec_trans must lie in [0, 1], got {spec_trans}")
+    if not (refract_distance >= 0 and np.isfinite(refract_distance)):
+        raise ValueError(f"refract_distance must be non-negative and finite, got {refract_distance}")
+    return PathTransEdit(ior, spec_trans, refract_distance, 0.0)
+
+
+def trans_eval_host(n: np.ndarray, wo: np.ndarray, wi: np.ndarray, a: np.ndarray, r: np.ndarray, m: np.ndarray, bg: np.ndarray,
+                    ior: float = 1.2, spec_trans: float = 0.4):
+    """The kernel's masked-branch BSDF (TransBSDF.eval_brdf where the mask is set) on the CPU: n, wo, wi, a, bg [N,3], r, m [N] ->
+    (f [N,3] with its cosine, pdf [N])."""
+    ed = trans_edit(ior, spec_trans)
+    v3 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
+    v1 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    nn, WO, WI, A, BG, R, M = v3(n), v3(wo), v3(wi), v3(a), v3(bg), v1(r), v1(m)
+    N = nn.shape[0]
+    if any(x.shape[0] != N for x in (WO, WI, A, BG, R, M)):
+        raise ValueError("n, wo, wi, a, r, m and bg must have the same rows")
+    f, pdf = np.empty((N, 3), np.float32), np.empty(N, np.float32)
+    check(load().matpbr_path_trans_eval_host(ctypes.cast(ctypes.byref(ed), _P), _ptr(nn), _ptr(WO), _ptr(WI), _ptr(A), _ptr(R), _ptr(M), _ptr(BG),
+                                             N, _ptr(f), _ptr(pdf)), "matpbr_path_trans_eval_host")
+    return f, pdf
+
+
+def trans_lookup_host(p: np.ndarray, n: np.ndarray, wo: np.ndarray, H: int, W: int, ior: float = 1.2, refract_distance: float = 100.0,
+                      fov_x_deg: float = 35.0):
+    """The kernel's texel lookups of a transparency edit on the CPU: hit points p, face normals n, wo [N,3] -> (texel [N] of the
+    point itself, texel [N] the background is read at; row * W + col)."""
+    ed = trans_edit(ior, 0.0, refract_distance)
+    v3 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
+    P, nn, WO = v3(p), v3(n), v3(wo)
+    N = P.shape[0]
+    if nn.shape[0] != N or WO.shape[0] != N:
+        raise ValueError("p, n and wo must have the same rows")
+    tp, tq = np.empty(N, np.int32), np.empty(N, np.int32)
+    check(load().matpbr_path_trans_lookup_host(ctypes.cast(ctypes.byref(ed), _P), _ptr(P), _ptr(nn), _ptr(WO), N, int(H), int(W), float(fov_x_deg),
+                                               _ptr(tp), _ptr(tq)), "matpbr_path_trans_lookup_host")
+    return tp, tq
+
+
 class PathTracer:
     """One mesh in the renderer's frame (camera at the origin looking down -z, `fov_x_deg` horizontal field of view, H x W pixels).
     The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
@@ -282,6 +336,35 @@ class PathTracer:
             check(lib.matpbr_path_render(*args), "matpbr_path_render")
         else:
             check(lib.matpbr_path_render_objects(*args, ctypes.cast(self.objects, _P), len(self.objects)), "matpbr_path_render_objects")
+        return out
+
+    @torch.no_grad()
+    def render_trans(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, mask, bg, ior: float = 1.2,
+                     spec_trans: float = 0.4, refract_distance: float = 100.0, spp: int = 64, max_depth: int = 4, seed: int = 0,
+                     spp_per_launch: int = 8, tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`render` with the depth mesh shading as the reference's TransBSDF ("Transparency editing"): where
+        `mask` [H,W] (bool) is set the surface is glass of index `ior` and transmission `spec_trans` over the picture `bg` [H,W,3].
+        The maps are used as given (`relight.render_trans` edits them inside the mask first).  Forward only: there is no backward
+        pass through it, and a tracer with inserted objects refuses it."""
+        if self.objects is not None:
+            raise ValueError("render_trans knows no inserted objects: build the PathTracer without `objects`")
+        H, W, dev = self.H, self.W, self.device
+        mk, bgt = torch.as_tensor(mask), torch.as_tensor(bg)
+        if tuple(mk.shape) != (H, W):
+            raise ValueError(f"mask must be [{H},{W}], got {tuple(mk.shape)}")
+        if tuple(bgt.shape) != (H, W, 3):
+            raise ValueError(f"bg must be [{H},{W},3], got {tuple(bgt.shape)}")
+        ed = trans_edit(ior, spec_trans, refract_distance)
+        mk = (mk != 0).to(dev, torch.uint8).contiguous()
+        bgt = bgt.to(dev, torch.float32).contiguous()
+        a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
+        out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(load().matpbr_path_render_trans(self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
+                                              env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]),
+                                              int(spp), int(max_depth), int(seed) & 0xFFFFFFFF, int(spp_per_launch), out.data_ptr(),
+                                              rays.data_ptr() if rays is not None else None, stream, mk.data_ptr(), bgt.data_ptr(),
+                                              ctypes.cast(ctypes.byref(ed), _P)), "matpbr_path_render_trans")
         return out
 
     @torch.no_grad()

@@ -28,8 +28,8 @@ from .pipeline import OUT_DIR, load_image, write_png
 
 
 def load_estimated_brdf(root_dir: str, device="cuda") -> Dict[str, torch.Tensor]:
-    """myutils/mi_plugin.py:701-739: best_results/{albedo,roughness,metallic,normal}.exr (+ envmap.hdr); roughness is rescaled
-    `r * 0.95 + 0.05` on reload (:716)."""
+    """myutils/mi_plugin.py:701-739: best_results/{albedo,roughness,metallic,normal}.exr (+ envmap.hdr, mask.png, bg.png); roughness
+    is rescaled `r * 0.95 + 0.05` on reload (:716)."""
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
     mat = {"albedo": t(read_exr(os.path.join(root_dir, "albedo.exr"))),
            "roughness": t(read_exr(os.path.join(root_dir, "roughness.exr"))[..., :1]) * 0.95 + 0.05,
@@ -44,6 +44,21 @@ def load_estimated_brdf(root_dir: str, device="cuda") -> Dict[str, torch.Tensor]
 
         m = np.asarray(Image.open(p))
         mat["mask"] = torch.from_numpy(np.ascontiguousarray((m[..., 0] if m.ndim == 3 else m) > 0)).to(device)
+    p = os.path.join(root_dir, "bg.png")                              # "load background for transparency editing" (:720-728)
+    if os.path.exists(p):
+        from PIL import Image
+
+        im = Image.open(p)
+        if im.mode not in ("RGB", "RGBA", "L"):
+            im = im.convert("RGB")
+        b = np.asarray(im).astype(np.float32) / 255.0                 # 8-bit values over 255, kept in the file's gamma space
+        b = np.repeat(b[..., None], 3, -1) if b.ndim == 2 else b[..., :3]
+        bg = t(b)
+        H, W = mat["albedo"].shape[0], mat["albedo"].shape[1]
+        if bg.shape[0] != H or bg.shape[1] != W:                      # (:723-726)
+            bg = torch.nn.functional.interpolate(bg[None].permute(0, 3, 1, 2), size=(H, W), mode="bilinear", align_corners=True)[0]
+            bg = bg.permute(1, 2, 0).contiguous()
+        mat["bg"] = bg
     return mat
 
 
@@ -266,6 +281,48 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
     base = os.path.join(out_dir, f"mi_oi_{save_name}_{env_id}")              # (:233-236)
+    write_exr(base + ".exr", img.cpu().numpy())
+    write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
+    return base + ".png"
+
+
+TRANS_ALBEDO, TRANS_ROUGHNESS, TRANS_METALLIC = 0.7, 0.3, 0.0   # the maps inside the mask (trans_edit.py:25-28)
+
+
+def render_trans(save_name: str, ior: float = 1.2, keep_albedo_color: bool = False, spec_trans: float = 0.4, env_path: Optional[str] = None,
+                 input_path: Optional[str] = None, save_path: Optional[str] = None, spp: int = 64, iters: int = 10, max_depth: int = 4,
+                 seed: int = 0, refract_distance: float = 100.0, device="cuda") -> str:
+    """trans_edit.py:16-60: the masked part of the scene as glass (TransBSDF; DESIGN.md section 1.4, "Transparency editing") ->
+    mi_trans_<ior>_<wA|woA>_<specTrans>_<name>_<env>.exr / .png.  Needs best_results/mask.png and best_results/bg.png.  Inside the
+    mask the albedo becomes 0.7 unless `keep_albedo_color`, roughness 0.3 and metallic 0.  The light is `env_path`, else
+    best_results/envmap.hdr.  `iters` renders with seeds seed + i are averaged."""
+    scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
+    mat_dir = os.path.join(scene_dir, "best_results")
+    for name in ("mask.png", "bg.png"):
+        if not os.path.exists(os.path.join(mat_dir, name)):
+            raise FileNotFoundError(f"transparency editing needs {os.path.join(mat_dir, name)}")
+    if iters < 1:
+        raise ValueError(f"iters must be at least 1, got {iters}")
+    env_path = find_envmap(save_name, env_path, input_path)
+    mat = load_estimated_brdf(mat_dir, device)
+    mask = mat["mask"]
+    if not keep_albedo_color:
+        mat["albedo"][mask] = TRANS_ALBEDO
+    mat["roughness"][mask] = TRANS_ROUGHNESS
+    mat["metallic"][mask] = TRANS_METALLIC
+    pt = _path_tracer(scene_dir, save_name, mat, device)
+    env = load_image(env_path)
+    tabs = pt.tables(env)
+    img = torch.zeros_like(mat["albedo"])
+    for i in range(iters):
+        img += pt.render_trans(mat["albedo"], mat["roughness"], mat["metallic"], env, mask, mat["bg"], ior, spec_trans, refract_distance, spp,
+                               max_depth, seed + i, tables=tabs)
+    img /= iters
+    env_id = os.path.basename(env_path)[:-4]
+    out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
+    os.makedirs(out_dir, exist_ok=True)
+    flag = "wA" if keep_albedo_color else "woA"
+    base = os.path.join(out_dir, f"mi_trans_{ior}_{flag}_{spec_trans}_{save_name}_{env_id}")   # (trans_edit.py:45-48)
     write_exr(base + ".exr", img.cpu().numpy())
     write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
     return base + ".png"
