@@ -2,7 +2,8 @@
  * matpbr_path.h -- C ABI of libmatpbr_path.so: a path-traced re-render of the depth mesh and its backward pass (MI355X, gfx950).
  *
  * The integrator is Mitsuba 3's `path` as the reference configures it for its final images (render_final.py:35-96,
- * inverse_img_w_mi.py:49-52: `max_depth` 4, MatDiffBSDF on the `.ply` depth mesh, equirectangular envmap emitter); its
+ * inverse_img_w_mi.py:49-52: `max_depth` 4, MatDiffBSDF on the `.ply` depth mesh, shading with the face normals or with a
+ * shading-normal map (MatDiffBSDF's use_mesh_normal=False: the *_normals entry points), equirectangular envmap emitter); its
  * definition and the ways it differs from Mitsuba are DESIGN.md section 1.4.  It is a separate library so that
  * libmatpbr.so's sources (and the digest the traffic profile is tied to) stay untouched.
  *
@@ -132,6 +133,24 @@ int matpbr_path_render_trans(const void* nodes, const void* tris, const float* a
                              int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                              const uint8_t* mask, const float* bg, const MatpbrPathTransEdit* edit);
 
+/* matpbr_path_render with a shading-normal map ("Shading normals").  nrm[H,W,3] (fp32, DEVICE, unit length,
+ * used as given) is read at the texel a vertex reads its material from and takes the place of MatDiffBSDF's `normal`: every cosine
+ * of the BSDF, both samplers' frames, the pdf.  The face normal keeps the back-face test and the spawn offset, and a direction on
+ * its far side carries nothing: an emitter sample there traces no shadow ray, a BSDF sample there ends the path.  With nrm == NULL
+ * this is matpbr_path_render, bit for bit, and launches its kernel.  There is no variant with inserted objects or with the
+ * transparency edit. */
+int matpbr_path_render_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                               const float* nrm);
+
+/* d (g . f) / d n of the BSDF value f (RGB, with its cosine) at N lanes on the CPU: n[N,3], wo[N,3], wi[N,3], a[N,3], r[N], m[N],
+ * upstream g[N,3] -> d_n[N,3] = gl wi + gv wo + gh h, h = normalize(wi + wo), each cosine's gradient passed where the raw cosine is
+ * positive, with respect to the three components of n as free variables.  The gates and the composition are the routine the
+ * backward kernel runs; gl, gv, gh restate the device's cosine gradients with plain divisions. */
+int matpbr_path_eval_normal_grad_host(const float* n, const float* wo, const float* wi, const float* a, const float* r, const float* m,
+                                      const float* g, long N, float* d_n);
+
 /* The masked branch of the edited BSDF on the CPU, with the routine the kernel runs: per lane the face normal n[N,3], wo[N,3] towards
  * the viewer, wi[N,3] towards the light (either side of the surface), the texel's a[N,3] r[N] m[N] and bg[N,3] at the refracted
  * texel -> f[N,3] (with its cosine) and pdf[N]. */
@@ -159,6 +178,22 @@ int matpbr_path_render_bwd(const void* nodes, const void* tris, const float* a, 
                            const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                            int max_depth, uint32_t seed, int spp_per_launch, const float* d_out, float* d_a, float* d_r, float* d_m,
                            float* d_env, void* workspace, size_t workspace_bytes, uint32_t* rays, void* stream);
+
+/* Workspace of matpbr_path_render_bwd_normals with a normal map: three more accumulators per pixel. */
+size_t matpbr_path_render_bwd_normals_workspace_bytes(int H, int W, int He, int We);
+
+/* The backward pass of matpbr_path_render_normals: matpbr_path_render_bwd's arguments, the map nrm[H,W,3] (DEVICE) and d_n[H,W,3]
+ * (DEVICE, nullable: not computed, not touched), to which d loss / d nrm is ADDED.  The sampling stays detached; at every vertex
+ * both BSDF values (the emitter term's and the sample factor's) send gl wi + gv wo + gh h to the texel the vertex reads, with
+ * the upstreams of matpbr_path_render_bwd and the gates of matpbr_path_eval_normal_grad_host.  The gradient is with respect to the
+ * three components as free variables: normalising is the caller's.  Same fixed-point sums, same bit-identity.  `workspace` holds
+ * matpbr_path_render_bwd_normals_workspace_bytes(H, W, He, We) bytes.  With nrm == NULL, d_n must be NULL, the workspace of
+ * matpbr_path_render_bwd suffices, and this is matpbr_path_render_bwd, bit for bit. */
+int matpbr_path_render_bwd_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                   float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                   int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, const float* d_out, float* d_a, float* d_r,
+                                   float* d_m, float* d_env, void* workspace, size_t workspace_bytes, uint32_t* rays, void* stream,
+                                   const float* nrm, float* d_n);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Command line of the inverse-rendering pipeline, same flags as the reference's inverse_img_w_mi.py (:771-801) plus
-`--size`, `--spp`, `--num_epochs`, `--pred_dir`, `--integrator` / `--max_depth` / `--seed`.  Runs on libmatpbr.so (MI355X); see materialist_amd/pipeline.py."""
+`--size`, `--spp`, `--num_epochs`, `--pred_dir`, `--integrator` / `--max_depth` / `--seed` / `--shading_normals`.  Runs on libmatpbr.so (MI355X); see materialist_amd/pipeline.py."""
 import argparse
 import os
 import sys
@@ -32,8 +32,13 @@ def parse_args(argv=None):
                          "render of the depth mesh with its backward pass (shadows and inter-reflection, as the reference's Mitsuba `path`)")
     ap.add_argument("--max_depth", type=int, default=4, help="--integrator path: Mitsuba's max_depth (1 emission, 2 direct + shadows, 4 the reference's)")
     ap.add_argument("--seed", type=int, default=0, help="--integrator path: seed of the sequence each render draws its seed from")
+    ap.add_argument("--shading_normals", choices=("face", "map"), default="face",
+                    help="--integrator path: face = shade with the mesh's face normals (default); map = 'n' in --opt_order is accepted and the "
+                         "path render shades with, and fits, the normal map")
     args = ap.parse_args(argv)
-    if args.integrator == "path" and "n" in "".join(args.opt_order):
+    if args.shading_normals == "map" and args.integrator != "path":
+        ap.error("--shading_normals map needs --integrator path")
+    if args.integrator == "path" and args.shading_normals == "face" and "n" in "".join(args.opt_order):
         ap.error(f"--integrator path shades with the mesh's face normals: it cannot optimise normals ('n' in --opt_order {' '.join(args.opt_order)})")
     if args.integrator == "path" and not 1 <= args.max_depth <= 16:
         ap.error("--max_depth must lie in 1..16")
@@ -47,7 +52,7 @@ def main(argv=None):
     res = inverse_image(args.img_inverse_path, args.save_name, args.opt_src, args.opt_order, args.use_mask, args.opt_env_from,
                         args.save_path, args.model_name, size=args.size, spp=args.spp, num_epochs=args.num_epochs, pred_dir=args.pred_dir,
                         matnet_weights=args.matnet_weights, geometry=args.geometry, integrator=args.integrator, max_depth=args.max_depth,
-                        seed=args.seed)
+                        seed=args.seed, shading_normals=args.shading_normals)
     print(f"done: PSNR {res['psnr']:.2f} dB, best loss_mse {res['best_loss']:.6f}, outputs in {res['output_dir']}")
 
 

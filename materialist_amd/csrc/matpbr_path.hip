@@ -215,6 +215,14 @@ __device__ __forceinline__ void path_lane(PLane& ln, const float wi[3], const fl
         ln.den = ggx_den_literal(ln.pc, ln.NoH);
     }
 }
+// path_lane's h and n . h before its clamp (the same operations): the normal's gradient reads them (shading normals, backward)
+__device__ __forceinline__ float half_vector(const float wi[3], const float wo[3], const float n[3], float h[3]) {
+    h[0] = wi[0] + wo[0]; h[1] = wi[1] + wo[1]; h[2] = wi[2] + wo[2];
+    const float il = rsq(dot3(h, h));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) h[c] *= il;
+    return dot3(n, h);
+}
 // eval_brdf(wi, wo) -> f (RGB, with the trailing cosine) and the mixture pdf
 __device__ __forceinline__ void path_eval(const float wi[3], const float wo[3], const float n[3], const float a[3], float r, float m, float f[3],
                                           float& pdf) {
@@ -453,6 +461,66 @@ __device__ __forceinline__ float trans_pdf(const PLane& ln, const BrdfState<floa
     return fmaf(0.125f * (st.D * ln.NoH), rcp(fmaxf(ln.VoH, 1e-4f)), (0.5f * kInvPi) * st.NoL);
 }
 
+// ---- shading normals ("Shading normals") -------------------------------------------------------------------
+// The map travels to the kernel in the table's place.  A vertex then has two normals: ng, the face normal, keeps everything geometric
+// (the back-face test, the spawn offset, which side a direction leaves on); ns = nrm[tp] takes the place of MatDiffBSDF's `normal`.
+struct ShadeNormals {
+    const float* nrm;   // [H,W,3], unit length, used as given
+};
+__device__ __forceinline__ int object_of(const ShadeNormals&, int, float[3]) { return 0; }
+
+// d f / d n for one BSDF value at a vertex, added to dn: gl wi + gv wo + gh h with each cosine's gradient passed where the raw cosine
+// is positive (eval_brdf_bwd_kernel's gates; dr.maximum passes the gradient where its argument is > 0)
+__host__ __device__ inline void normal_grad(float gl, float gv, float gh, float NoL_raw, float NoV_raw, float nh_raw, const float wi[3],
+                                            const float wo[3], const float h[3], float dn[3]) {
+    gl = NoL_raw > 0.0f ? gl : 0.0f;
+    gv = NoV_raw > 0.0f ? gv : 0.0f;
+    gh = nh_raw > 0.0f ? gh : 0.0f;
+    for (int c = 0; c < 3; ++c) dn[c] += fmaf(gl, wi[c], fmaf(gv, wo[c], gh * h[c]));
+}
+
+// The cosine gradients gl, gv, gh of brdf_core_grad<float, true> at (n, wo, wi) for the host entry point.  matpbr_device.hpp's
+// functions are device code (hardware reciprocals), so the CPU restates path_lane, brdf_core and the WANT_N branch with plain
+// divisions; the gates and the composition it feeds, normal_grad above, are the code the kernel runs.  cosines = n.wi, n.wo, n.h raw.
+inline void cosine_grads_host(const float n[3], const float wo[3], const float wi[3], const float a[3], float r, float m, const float g[3],
+                              float& gl, float& gv, float& gh, float cosines[3], float h[3]) {
+    const float kInvPiF = 0.31830988618379067154f;
+    for (int c = 0; c < 3; ++c) h[c] = wi[c] + wo[c];
+    const float il = 1.0f / sqrtf(dot3h(h, h));
+    for (int c = 0; c < 3; ++c) h[c] *= il;
+    const float nh_raw = dot3h(n, h);
+    cosines[0] = dot3h(n, wi); cosines[1] = dot3h(n, wo); cosines[2] = nh_raw;
+    const float NoL = fmaxf(cosines[0], 0.0f), NoV = fmaxf(cosines[1], 0.0f), NoH = fmaxf(nh_raw, 0.0f), VoH = fmaxf(dot3h(wo, h), 0.0f);
+    const float alpha2 = (r * r) * (r * r), am1 = alpha2 - 1.0f;
+    float den;
+    if (fabsf(dot3h(n, n) - 1.0f) < 1e-5f && nh_raw > 0.0f) {
+        float cr[3];
+        cross3(n, h, cr);
+        den = (alpha2 - dot3h(cr, cr) * am1) + 1e-6f;
+    } else {
+        den = (NoH * NoH * am1 + 1.0f) + 1e-6f;
+    }
+    const float iden = 1.0f / den, D = alpha2 * kInvPiF * (iden * iden);
+    const float k = (r + 1.0f) * (r + 1.0f) * 0.125f, omk = 1.0f - k, kpe = k + 1e-6f;
+    const float g1l = 1.0f / (NoL * omk + kpe), g1v = 1.0f / (NoV * omk + kpe), G = g1l * g1v;
+    const float FDm1 = 2.0f * r * VoH * VoH - 0.5f;
+    const float ol = 1.0f - NoL, ov = 1.0f - NoV, ol4 = (ol * ol) * (ol * ol), ov4 = (ov * ov) * (ov * ov);
+    const float Fi = FDm1 * (ol4 * ol) + 1.0f, Fo = FDm1 * (ov4 * ov) + 1.0f;
+    const float xh = 1.0f - VoH, x5 = (xh * xh) * (xh * xh) * xh;
+    float gd = 0.0f, gs = 0.0f;
+    for (int c = 0; c < 3; ++c) {
+        const float C0 = m * a[c] + (1.0f - m) * 0.04f;
+        gd += g[c] * ((a[c] * (1.0f - m)) * kInvPiF);
+        gs += g[c] * (x5 * (1.0f - C0) + C0);
+    }
+    const float dFi = -5.0f * FDm1 * ol4, dFo = -5.0f * ov4 * FDm1;
+    const float dG_dNoL = -omk * g1l * G, dG_dNoV = -g1v * omk * G;
+    const float gsq = gs * 0.25f * NoL;
+    gl = gd * Fo * (dFi * NoL + Fi) + gs * 0.25f * D * (dG_dNoL * NoL + G);
+    gv = gd * dFo * (Fi * NoL) + gsq * D * dG_dNoV;
+    gh = gsq * G * (-4.0f * am1 * D * NoH * iden);
+}
+
 struct PathArgs {
     const float4* nodes;
     const float4* tris;
@@ -471,12 +539,14 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 
 // samples [s0, s1) of every pixel added to out (first: start from 0; last: divide by spp).  OBJ: the BVH holds inserted objects
 // (Objects = ObjTable, passed by value); EDIT: transparency editing (Objects = TransEdit, by value in the table's place).  With
-// NoObjects every `if (OBJ ...)` and `if (EDIT ...)` below folds away and the walk is the depth mesh's alone, the code the kernel had
-// before there were objects; with ObjTable every `if (EDIT ...)` folds away.
+// NoObjects every `if (OBJ ...)`, `if (EDIT ...)` and `if (NRM ...)` below folds away and the walk is the depth mesh's alone, the code
+// the kernel had before there were objects; with ObjTable every `if (EDIT ...)` folds away.  NRM: shading normals (Objects =
+// ShadeNormals): `n` stays the face normal ng and `ns` is the map's.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
     constexpr bool OBJ = std::is_same<Objects, ObjTable>::value;
     constexpr bool EDIT = std::is_same<Objects, TransEdit>::value;
+    constexpr bool NRM = std::is_same<Objects, ShadeNormals>::value;
     __shared__ int s_stack[kStack * kBlock];
     const int tid = threadIdx.y * kTileX + threadIdx.x;
     const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
@@ -541,6 +611,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
             const long tp = OBJ && kind != 0 ? 0 : (long)ty * q.W + tx;   // an object reads no texel
             const float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+            float ns[3] = {n[0], n[1], n[2]};   // (NRM) the shading normal: every cosine, both samplers' frames, the pdf
+            if constexpr (NRM) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ns[c] = ot.nrm[3 * tp + c];
+            }
             bool masked = false;   // (EDIT) the vertex reads a masked texel: TransBSDF's glass over bg at the refracted texel
             float bgv[3] = {0.0f, 0.0f, 0.0f};
             if constexpr (EDIT) {
@@ -574,7 +649,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                         path_eval_st(wl, wo, n, av, rv, mv, ln, st, f, pdf_b);
                         pdf_b = trans_pdf(ln, st);
                     } else {
-                        path_eval(wl, wo, n, av, rv, mv, f, pdf_b);
+                        path_eval(wl, wo, NRM ? ns : n, av, rv, mv, f, pdf_b);
                     }
                     if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
                         float ts = FLT_MAX;
@@ -610,8 +685,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 for (int c = 0; c < 3; ++c) wgt[c] = f[c] > 0.0f ? f[c] * ip : 0.0f;
                 pdf_s = pt > 0.0f ? pt : 0.0f;
             } else {
-                path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, wgt, pdf_s);
+                path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, NRM ? ns : n, av, rv, mv, wi, wgt, pdf_s);
                 if (OBJ) prev_delta = false;
+                if (NRM && !(dot3(n, wi) > 0.0f)) break;   // sampled below the sheet: nothing is carried through it
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) thr[c] *= wgt[c];
@@ -659,8 +735,22 @@ __device__ __forceinline__ long long to_fix(float v, float inv_q) {
     return __float2ll_rn(fminf(fmaxf(v * inv_q, -kFixClamp), kFixClamp));
 }
 
+// the backward pass's shading normals: a trailing kernel argument that the plain instantiation does not have (an empty pack, so its
+// kernel arguments are what they were).  Without it the accumulators are a (3), r, m per pixel and every `if (NRM ...)` folds away;
+// with it three more follow, the normal's.
+struct BwdNormals {
+    const float* nrm;   // [H,W,3]
+    int want_n;
+};
+__device__ __forceinline__ bool want_n_of() { return false; }
+__device__ __forceinline__ bool want_n_of(const BwdNormals& nm) { return nm.want_n != 0; }
+__device__ __forceinline__ const float* nrm_of() { return nullptr; }
+__device__ __forceinline__ const float* nrm_of(const BwdNormals& nm) { return nm.nrm; }
+template <class... Normals> constexpr int kAccOf = sizeof...(Normals) ? 8 : 5;
+
 // one vertex's material gradient to its texel: the lane's own texel in registers, any other with integer atomics
-__device__ __forceinline__ void put_material(const BwdArgs& b, const BrdfGrad<float>& gv, long tp, long pix, float inv_q, long long own[5]) {
+template <int ACC>
+__device__ __forceinline__ void put_material(const BwdArgs& b, const BrdfGrad<float>& gv, long tp, long pix, float inv_q, long long* own) {
     const float v[5] = {gv.d_a[0], gv.d_a[1], gv.d_a[2], gv.d_r, gv.d_m};
     const int want[5] = {b.want_a, b.want_a, b.want_a, b.want_r, b.want_m};
 #pragma unroll
@@ -669,7 +759,17 @@ __device__ __forceinline__ void put_material(const BwdArgs& b, const BrdfGrad<fl
         const long long x = to_fix(v[k], inv_q);
         if (x == 0) continue;
         if (tp == pix) own[k] += x;
-        else atomicAdd(b.acc + 5 * tp + k, (unsigned long long)x);
+        else atomicAdd(b.acc + ACC * tp + k, (unsigned long long)x);
+    }
+}
+// one vertex's normal gradient, to accumulators 5..7 of its texel
+__device__ __forceinline__ void put_normal(const BwdArgs& b, const float dn[3], long tp, long pix, float inv_q, long long* own) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const long long x = to_fix(dn[c], inv_q);
+        if (x == 0) continue;
+        if (tp == pix) own[5 + c] += x;
+        else atomicAdd(b.acc + 8 * tp + 5 + c, (unsigned long long)x);
     }
 }
 __device__ __forceinline__ void put_env(unsigned long long* s_env, int tx, const float v[3], float inv_q) {
@@ -684,9 +784,12 @@ __device__ __forceinline__ void put_env(unsigned long long* s_env, int tx, const
 // added in fp64); GRAD = true replays it with rem = that radiance, takes the same fp32 terms off in fp64, and sends the gradients of
 // g . L to the sinks.  In fp32, rem = L - (terms so far) would be off by ~2^-24 L per term: at a black metal under a sun, where the
 // radiance still to come is a small part of L and is divided by a tiny f_s, that cancellation alone made d_a several % wrong.
-template <bool GRAD>
-__device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint32_t base, int i, int j, long pix, bool have_tab, LdsStack& stk,
-                                       double L[3], const float g[3], float inv_q, long long own[5], unsigned long long* s_env, uint32_t& n_rays) {
+template <bool GRAD, class... Normals>
+__device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, const Normals&... nm, uint32_t base, int i, int j, long pix, bool have_tab,
+                                       LdsStack& stk, double L[3], const float g[3], float inv_q, long long* own, unsigned long long* s_env,
+                                       uint32_t& n_rays) {
+    constexpr bool NRM = sizeof...(Normals) != 0;   // `n` stays the face normal ng, `ns` is the map's
+    constexpr int ACC = kAccOf<Normals...>;
     float thr[3] = {1.0f, 1.0f, 1.0f};
     double rem[3] = {L[0], L[1], L[2]};
     const float x = (float)j - 0.5f + rng_u(base, 0, 0), y = (float)i - 0.5f + rng_u(base, 0, 1);
@@ -697,6 +800,7 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
         for (int c = 0; c < 3; ++c) d[c] *= il;
     }
     const bool want_mat = b.want_a || b.want_r || b.want_m;
+    const bool want_n = want_n_of(nm...), want_brdf = NRM ? want_mat || want_n : want_mat;
     float prev_pdf = 0.0f;
     for (int depth = 0;; ++depth) {
         float t = FLT_MAX;
@@ -736,13 +840,19 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
         const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
         const long tp = (long)ty * q.W + tx;
         const float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+        float ns[3] = {n[0], n[1], n[2]};
+        if constexpr (NRM) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ns[c] = nrm_of(nm...)[3 * tp + c];
+        }
         const float eps = spawn_eps(p);
         float po[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
         BrdfGrad<float> gv;
         brdf_grad_zero(gv);
-        float gl, gh;   // (cosine gradients: not asked for)
+        float gl, gh;   // cosine gradients: read with NRM only
+        float dn[3] = {0.0f, 0.0f, 0.0f};
         if (have_tab) {
             float wl[3], pdf_e;
             const int te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
@@ -751,7 +861,7 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
                 float f[3], pdf_b;
                 PLane ln;
                 BrdfState<float> st;
-                path_eval_st(wl, wo, n, av, rv, mv, ln, st, f, pdf_b);
+                path_eval_st(wl, wo, NRM ? ns : n, av, rv, mv, ln, st, f, pdf_b);
                 if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
                     float ts = FLT_MAX;
                     ++n_rays;
@@ -766,7 +876,16 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
                                 ge[c] = g[c] * (thr[c] * (Le * w));
                                 ve[c] = g[c] * (thr[c] * (f[c] * w));
                             }
-                            if (want_mat) brdf_core_grad<float, false>(ln.pc, st, ge, gv, gl, gh);
+                            if constexpr (NRM) {
+                                if (want_brdf) {   // gv.dNoV gathers both BSDF values' d/d(n . wo): composed once, below
+                                    brdf_core_grad<float, true>(ln.pc, st, ge, gv, gl, gh);
+                                    float h[3];
+                                    const float nh_raw = half_vector(wl, wo, ns, h);
+                                    normal_grad(gl, 0.0f, gh, ln.NoL_raw, 0.0f, nh_raw, wl, wo, h, dn);
+                                }
+                            } else {
+                                if (want_mat) brdf_core_grad<float, false>(ln.pc, st, ge, gv, gl, gh);
+                            }
                             if (b.want_env) put_env(s_env, te, ve, inv_q);
                         } else {
 #pragma unroll
@@ -779,9 +898,10 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
         float wi[3], fs[3], ps;
         PLane ln;
         BrdfState<float> st;
-        path_sample_st(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, n, av, rv, mv, wi, ln, st, fs, ps);
-        const float ip = ps > 1e-6f ? 1.0f / (ps + 1e-6f) : 0.0f;
-        if (GRAD && want_mat) {
+        path_sample_st(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, NRM ? ns : n, av, rv, mv, wi, ln, st, fs, ps);
+        // (NRM) sampled below the sheet: the path ends here (thr = 0), after the emitter term's gradient has gone out
+        const float ip = ps > 1e-6f && !(NRM && !(dot3(n, wi) > 0.0f)) ? 1.0f / (ps + 1e-6f) : 0.0f;
+        if (GRAD && want_brdf) {
             if (ip > 0.0f) {   // d (f_s / (pdf_s + 1e-6)) / d theta carried by everything after this vertex: rem / f_s per channel
                 // rem is L minus at most 2 max_depth fp32 terms in fp64, off by <= 2 max_depth 2^-53 L: a rem below kRemFloor
                 // max_depth L is that rounding (the path gathers nothing more), and dividing it by a small f_s (a black metal) would
@@ -790,9 +910,22 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
                     gs[c] = fs[c] > 0.0f && rem[c] > kRemFloor * (double)q.max_depth * L[c] ? g[c] * ((float)rem[c] / fs[c]) : 0.0f;
-                brdf_core_grad<float, false>(ln.pc, st, gs, gv, gl, gh);
+                if constexpr (NRM) {
+                    brdf_core_grad<float, true>(ln.pc, st, gs, gv, gl, gh);
+                    float h[3];
+                    const float nh_raw = half_vector(wi, wo, ns, h);
+                    normal_grad(gl, 0.0f, gh, ln.NoL_raw, 0.0f, nh_raw, wi, wo, h, dn);
+                } else {
+                    brdf_core_grad<float, false>(ln.pc, st, gs, gv, gl, gh);
+                }
             }
-            put_material(b, gv, tp, pix, inv_q, own);
+            if (!NRM || want_mat) put_material<ACC>(b, gv, tp, pix, inv_q, own);
+            if constexpr (NRM) {
+                if (want_n) {
+                    normal_grad(0.0f, gv.dNoV, 0.0f, 0.0f, ln.pc.NoV_raw, 0.0f, wi, wo, wo, dn);
+                    put_normal(b, dn, tp, pix, inv_q, own);
+                }
+            }
         }
         (void)gl; (void)gh;
 #pragma unroll
@@ -805,7 +938,9 @@ __device__ __forceinline__ void replay(const PathArgs& q, const BwdArgs& b, uint
 }
 
 // samples [s0, s1) of every pixel: both passes per sample; the lane's own-texel sums and the workgroup's envmap row go out at the end
-__global__ __launch_bounds__(kBlock) void path_bwd_kernel(const PathArgs q, const BwdArgs b, int s0, int s1) {
+template <class... Normals>
+__global__ __launch_bounds__(kBlock) void path_bwd_kernel(const PathArgs q, const BwdArgs b, int s0, int s1, const Normals... nm) {
+    constexpr int ACC = kAccOf<Normals...>;
     __shared__ int s_stack[kStack * kBlock];
     extern __shared__ unsigned long long s_env[];   // [He*We*3] when d_env is asked for
     const int tid = threadIdx.y * kTileX + threadIdx.x;
@@ -819,18 +954,18 @@ __global__ __launch_bounds__(kBlock) void path_bwd_kernel(const PathArgs q, cons
         const bool have_tab = q.row_cdf[q.He] > 0.0f;
         const float inv_q = b.scale[0];
         const float g[3] = {b.d_out[3 * pix], b.d_out[3 * pix + 1], b.d_out[3 * pix + 2]};
-        long long own[5] = {0, 0, 0, 0, 0};
+        long long own[ACC] = {};
         const uint32_t pix_hash = pcg_hash(q.seed_hash + (uint32_t)pix);
         uint32_t n_rays = 0;
         for (int s = s0; s < s1; ++s) {
             const uint32_t base = pcg_hash(pix_hash + (uint32_t)s);
             double L[3] = {0.0, 0.0, 0.0};
-            replay<false>(q, b, base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
-            replay<true>(q, b, base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
+            replay<false, Normals...>(q, b, nm..., base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
+            replay<true, Normals...>(q, b, nm..., base, i, j, pix, have_tab, stk, L, g, inv_q, own, s_env, n_rays);
         }
 #pragma unroll
-        for (int k = 0; k < 5; ++k)
-            if (own[k] != 0) atomicAdd(b.acc + 5 * pix + k, (unsigned long long)own[k]);
+        for (int k = 0; k < ACC; ++k)
+            if (own[k] != 0) atomicAdd(b.acc + ACC * pix + k, (unsigned long long)own[k]);
         if (q.rays) q.rays[pix] += n_rays;
     }
     __syncthreads();
@@ -859,18 +994,28 @@ __global__ __launch_bounds__(1024) void path_bwd_scale_kernel(const float* __res
 }
 
 // fixed point -> fp32, ADDED to the caller's maps: d_x += sum * q / spp
+template <int ACC>
 __global__ __launch_bounds__(256) void path_bwd_maps_kernel(const unsigned long long* __restrict__ acc, const float* __restrict__ scale, long P,
                                                             int spp, float* d_a, float* d_r, float* d_m) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     const double s = (double)scale[1] / (double)spp;
-    const unsigned long long* e = acc + 5 * p;
+    const unsigned long long* e = acc + ACC * p;
     if (d_a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) d_a[3 * p + c] += (float)((double)(long long)e[c] * s);
     }
     if (d_r) d_r[p] += (float)((double)(long long)e[3] * s);
     if (d_m) d_m[p] += (float)((double)(long long)e[4] * s);
+}
+// accumulators 5..7 of a pixel -> d_n += sum * q / spp
+__global__ __launch_bounds__(256) void path_bwd_normal_kernel(const unsigned long long* __restrict__ acc, const float* __restrict__ scale, long P,
+                                                              int spp, float* d_n) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const double s = (double)scale[1] / (double)spp;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d_n[3 * p + c] += (float)((double)(long long)acc[8 * p + 5 + c] * s);
 }
 // the workgroups' envmap rows, added in row order, -> d_env += sum * q / spp
 __global__ __launch_bounds__(256) void path_bwd_env_kernel(const unsigned long long* __restrict__ rows, const float* __restrict__ scale, int n_env,
@@ -1202,11 +1347,12 @@ int matpbr_path_render(const void* nodes, const void* tris, const float* a, cons
                                       spp_per_launch, out, rays, stream, nullptr, 0);
 }
 
-// the three renders: `edit` (nullable) selects the transparency-editing instantiation, else n_objects > 0 the object one
+// the four renders: `edit` (nullable) selects the transparency-editing instantiation, else `nrm` the shading-normal one, else
+// n_objects > 0 the object one
 static int render_common(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
                          const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                          int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream, const ObjTable& ot,
-                         int n_objects, const TransEdit* edit) {
+                         int n_objects, const TransEdit* edit, const float* nrm = nullptr) {
     if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !out || H <= 0 || W <= 0 || He <= 0 || We <= 0 ||
         spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f))
         return MATPBR_PATH_ERR_INVALID_ARG;
@@ -1230,6 +1376,7 @@ static int render_common(const void* nodes, const void* tris, const float* a, co
         const int s1 = std::min(spp, s0 + spp_per_launch);
         const int first = s0 == 0 ? 1 : 0, last = s1 == spp ? 1 : 0;
         if (edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, *edit);
+        else if (nrm) hipLaunchKernelGGL(path_kernel<ShadeNormals>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ShadeNormals{nrm});
         else if (n_objects > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ot);
         else hipLaunchKernelGGL(path_kernel<NoObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, NoObjects{});
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
@@ -1262,6 +1409,26 @@ int matpbr_path_render_trans(const void* nodes, const void* tris, const float* a
                          rays, stream, ObjTable{}, 0, &te);
 }
 
+int matpbr_path_render_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                               const float* nrm) {
+    return render_common(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out,
+                         rays, stream, ObjTable{}, 0, nullptr, nrm);
+}
+
+int matpbr_path_eval_normal_grad_host(const float* n, const float* wo, const float* wi, const float* a, const float* r, const float* m,
+                                      const float* g, long N, float* d_n) {
+    if (!n || !wo || !wi || !a || !r || !m || !g || !d_n || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        float gl, gv, gh, cosines[3], h[3];
+        cosine_grads_host(n + 3 * k, wo + 3 * k, wi + 3 * k, a + 3 * k, r[k], m[k], g + 3 * k, gl, gv, gh, cosines, h);
+        d_n[3 * k] = d_n[3 * k + 1] = d_n[3 * k + 2] = 0.0f;
+        normal_grad(gl, gv, gh, cosines[0], cosines[1], cosines[2], wi + 3 * k, wo + 3 * k, h, d_n + 3 * k);
+    }
+    return MATPBR_PATH_OK;
+}
+
 int matpbr_path_trans_eval_host(const MatpbrPathTransEdit* edit, const float* n, const float* wo, const float* wi, const float* a,
                                 const float* r, const float* m, const float* bg, long N, float* f, float* pdf) {
     if (!trans_edit_valid(edit) || !n || !wo || !wi || !a || !r || !m || !bg || !f || !pdf || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
@@ -1284,22 +1451,35 @@ int matpbr_path_trans_lookup_host(const MatpbrPathTransEdit* edit, const float* 
     return MATPBR_PATH_OK;
 }
 
-size_t matpbr_path_render_bwd_workspace_bytes(int H, int W, int He, int We) {
+static size_t bwd_workspace_bytes(int H, int W, int He, int We, int n_acc) {
     if (H <= 0 || W <= 0 || He <= 0 || We <= 0) return 0;
     const size_t n_wg = (size_t)((W + kTileX - 1) / kTileX) * (size_t)((H + kTileY - 1) / kTileY);
-    return 256 + (size_t)H * W * 5 * 8 + n_wg * (size_t)He * We * 3 * 8;
+    return 256 + (size_t)H * W * n_acc * 8 + n_wg * (size_t)He * We * 3 * 8;
 }
+size_t matpbr_path_render_bwd_workspace_bytes(int H, int W, int He, int We) { return bwd_workspace_bytes(H, W, He, We, 5); }
+size_t matpbr_path_render_bwd_normals_workspace_bytes(int H, int W, int He, int We) { return bwd_workspace_bytes(H, W, He, We, 8); }
 
 int matpbr_path_render_bwd(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
                            const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                            int max_depth, uint32_t seed, int spp_per_launch, const float* d_out, float* d_a, float* d_r, float* d_m,
                            float* d_env, void* workspace, size_t workspace_bytes, uint32_t* rays, void* stream) {
-    if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !d_out || !workspace || H <= 0 || W <= 0 ||
+    return matpbr_path_render_bwd_normals(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
+                                          spp_per_launch, d_out, d_a, d_r, d_m, d_env, workspace, workspace_bytes, rays, stream, nullptr, nullptr);
+}
+
+// nrm == NULL: the plain backward kernel and its five accumulators per pixel; else the shading-normal one and eight
+int matpbr_path_render_bwd_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                   float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                   int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, const float* d_out, float* d_a, float* d_r,
+                                   float* d_m, float* d_env, void* workspace, size_t workspace_bytes, uint32_t* rays, void* stream,
+                                   const float* nrm, float* d_n) {
+    const int n_acc = nrm ? 8 : 5;
+    if ((!nrm && d_n) || !nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !d_out || !workspace || H <= 0 || W <= 0 ||
         He <= 0 || We <= 0 || spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH ||
         !(fov_x_deg > 0.0f && fov_x_deg < 180.0f) || (d_env && (long)He * We > kBwdMaxEnvTexels) ||
-        workspace_bytes < matpbr_path_render_bwd_workspace_bytes(H, W, He, We) || ((uintptr_t)workspace & 7))
+        workspace_bytes < bwd_workspace_bytes(H, W, He, We, n_acc) || ((uintptr_t)workspace & 7))
         return MATPBR_PATH_ERR_INVALID_ARG;
-    if (!d_a && !d_r && !d_m && !d_env) return MATPBR_PATH_OK;
+    if (!d_a && !d_r && !d_m && !d_env && !d_n) return MATPBR_PATH_OK;
     PathArgs q{};
     q.nodes = static_cast<const float4*>(nodes);
     q.tris = static_cast<const float4*>(tris);
@@ -1324,20 +1504,28 @@ int matpbr_path_render_bwd(const void* nodes, const void* tris, const float* a, 
     b.d_out = d_out;
     b.scale = reinterpret_cast<float*>(ws);
     b.acc = reinterpret_cast<unsigned long long*>(ws + 256);
-    b.env_rows = b.acc + 5 * P;
+    b.env_rows = b.acc + n_acc * P;
     b.want_a = d_a != nullptr; b.want_r = d_r != nullptr; b.want_m = d_m != nullptr; b.want_env = d_env != nullptr;
     const hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws + 256, 0, (size_t)P * 5 * 8 + (size_t)n_wg * n_env * 8, st) != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    if (hipMemsetAsync(ws + 256, 0, (size_t)P * n_acc * 8 + (size_t)n_wg * n_env * 8, st) != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
     hipLaunchKernelGGL(path_bwd_scale_kernel, dim3(1), dim3(1024), 0, st, d_out, 3 * P, reinterpret_cast<float*>(ws));
     if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
     for (int s0 = 0; s0 < spp; s0 += spp_per_launch) {
         const int s1 = std::min(spp, s0 + spp_per_launch);
-        hipLaunchKernelGGL(path_bwd_kernel, grid, dim3(kTileX, kTileY), (size_t)n_env * 8, st, q, b, s0, s1);
+        if (nrm) hipLaunchKernelGGL(path_bwd_kernel<BwdNormals>, grid, dim3(kTileX, kTileY), (size_t)n_env * 8, st, q, b, s0, s1,
+                                    BwdNormals{nrm, d_n != nullptr});
+        else hipLaunchKernelGGL(path_bwd_kernel<>, grid, dim3(kTileX, kTileY), (size_t)n_env * 8, st, q, b, s0, s1);
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
     }
     if (d_a || d_r || d_m) {
-        hipLaunchKernelGGL(path_bwd_maps_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)b.acc, b.scale, P, spp,
-                           d_a, d_r, d_m);
+        const dim3 mg((unsigned)((P + 255) / 256));
+        if (nrm) hipLaunchKernelGGL(path_bwd_maps_kernel<8>, mg, dim3(256), 0, st, (const unsigned long long*)b.acc, b.scale, P, spp, d_a, d_r, d_m);
+        else hipLaunchKernelGGL(path_bwd_maps_kernel<5>, mg, dim3(256), 0, st, (const unsigned long long*)b.acc, b.scale, P, spp, d_a, d_r, d_m);
+        if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    if (d_n) {
+        hipLaunchKernelGGL(path_bwd_normal_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)b.acc, b.scale, P,
+                           spp, d_n);
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
     }
     if (d_env) {

@@ -1204,7 +1204,7 @@ class PosMlpNormalPhase:
     also predicts the shading normal (`'n'` in --opt_order, predicted normals instead of geometric ones).  Maps from the net
     (clamps of :493-496, `normalize` of :497), the autograd render, the torch-composed loss with the L1 anchor on every live part
     (:522-537), AdamW + StepLR.  On the GPU (no `--use_mask`) the render, the loss statistics, SaveBest's decision and the gradients of the
-    maps run on the C ABI (`_step_device`: the launches of `NormalBrdfPhase`); autograd only carries those gradients back through the clamps,
+    maps run on the C ABI under the deterministic render (`_step_device`: the launches of `NormalBrdfPhase`); autograd only carries those gradients back through the clamps,
     the normalisation and the MLP (its layers are the HIP kernels of `posmlp._PosMlpHipFn`).  Otherwise: the operator face (`render_w_brdf`)
     and the torch-composed loss."""
 
@@ -1227,8 +1227,10 @@ class PosMlpNormalPhase:
         self._t, self.ops = 0, None          # (`ops` and the device buffers: set up by the first `_step_device`)
         # round 6: the network launch by launch on the C ABI (armhead.MlpEngine: forward, backward products, AdamW with SaveBest's weight snapshot --
         # no autograd graph, no framework optimiser); the head (tanh / residual / clamps / normalize) and its backward are element-wise passes here
+        # the launches of `_step_device` are the deterministic render's: under the path integrator the render is the operator face's
+        self.device_loss = self.DEVICE_LOSS and self.armn and mask is None and gt_image.is_cuda and scene.integrator != "path"
         self.engine = None
-        if self.ENGINE and self.DEVICE_LOSS and self.armn and mask is None and gt_image.is_cuda:
+        if self.ENGINE and self.device_loss:
             from .armhead import MlpEngine
 
             if MlpEngine.why_not(net, self.start.shape[0], gt_image.device) is None:
@@ -1386,7 +1388,7 @@ class PosMlpNormalPhase:
         return self.stats[0, o.STAT_MSE].clone()
 
     def step(self) -> torch.Tensor:
-        if self.DEVICE_LOSS and self.armn and self.mask is None and self.gt.is_cuda:
+        if self.device_loss:
             return self._step_device()
         maps, live = self.maps_from_net()
         pred = _render.render_w_brdf(self.scene, maps["albedo"], maps["roughness"], maps["metallic"], maps["normal"], self.spp)   # :515

@@ -303,6 +303,10 @@ class _Inversion:
         if not self.scene.use_mesh_normal and "normal" in self.saver.best:
             mat["normal"] = self.saver.best["normal"].detach().clone()
             params["shape.bsdf.n"] = mat["normal"]
+        elif self.scene.integrator == "path" and not self.scene.use_mesh_normal and "normal" in mat:
+            # no snapshot holds a normal map yet (no part has improved on the env phase's loss): the scene still has the part's last
+            # iterate, a node of a graph that is gone, and the next env phase renders through PathRenderFn, which differentiates its normals
+            params["shape.bsdf.n"] = mat["normal"] = mat["normal"].detach()
         self.save_results()                                                         # :465,590
         self.stage_digest(f"loop {loop_num} brdf {part}", mat["albedo"], mat["roughness"], mat["metallic"])
 

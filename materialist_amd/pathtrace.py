@@ -60,6 +60,12 @@ SIGNATURES = {
     "matpbr_path_render_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "matpbr_path_render_bwd": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P]),
+    "matpbr_path_render_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
+                                   [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P]),
+    "matpbr_path_eval_normal_grad_host": (ctypes.c_int, [_P] * 7 + [ctypes.c_long, _P]),
+    "matpbr_path_render_bwd_normals_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "matpbr_path_render_bwd_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
+                                       [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P, _P, _P]),
 }
 VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
@@ -262,6 +268,21 @@ def trans_lookup_host(p: np.ndarray, n: np.ndarray, wo: np.ndarray, H: int, W: i
     return tp, tq
 
 
+def eval_normal_grad_host(n: np.ndarray, wo: np.ndarray, wi: np.ndarray, a: np.ndarray, r: np.ndarray, m: np.ndarray, g: np.ndarray):
+    """d (g . f) / d n of the BSDF value on the CPU, composed and gated by the routine the backward kernel runs: n, wo, wi, a, g [N,3],
+    r, m [N] -> d_n [N,3] = gl wi + gv wo + gh h, with respect to n's components as free variables."""
+    v3 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
+    v1 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    nn, WO, WI, A, G, R, M = v3(n), v3(wo), v3(wi), v3(a), v3(g), v1(r), v1(m)
+    N = nn.shape[0]
+    if any(x.shape[0] != N for x in (WO, WI, A, G, R, M)):
+        raise ValueError("n, wo, wi, a, r, m and g must have the same rows")
+    d_n = np.empty((N, 3), np.float32)
+    check(load().matpbr_path_eval_normal_grad_host(_ptr(nn), _ptr(WO), _ptr(WI), _ptr(A), _ptr(R), _ptr(M), _ptr(G), N, _ptr(d_n)),
+          "matpbr_path_eval_normal_grad_host")
+    return d_n
+
+
 class PathTracer:
     """One mesh in the renderer's frame (camera at the origin looking down -z, `fov_x_deg` horizontal field of view, H x W pixels).
     The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
@@ -314,15 +335,26 @@ class PathTracer:
                 raise ValueError(f"envmap {tuple(env.shape)} does not match its tables {tuple(pdf.shape)}")
         return a, r, m, env, row, col, pdf
 
+    def _normal(self, normal, what: str) -> torch.Tensor:
+        """The shading-normal map [H,W,3] on the device, used as given; `what` names the caller in the refusals."""
+        if self.objects is not None:
+            raise ValueError(f"{what} knows no shading normals on a tracer with inserted objects: build the PathTracer without `objects`")
+        nrm = torch.as_tensor(normal)
+        if tuple(nrm.shape) != (self.H, self.W, 3):
+            raise ValueError(f"normal must be [{self.H},{self.W},3], got {tuple(nrm.shape)}")
+        return nrm.to(self.device, torch.float32).contiguous()
+
     @torch.no_grad()
     def render(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
                seed: int = 0, spp_per_launch: int = 8, out: Optional[torch.Tensor] = None, rays: Optional[torch.Tensor] = None,
-               tables: Optional[tuple] = None) -> torch.Tensor:
+               tables: Optional[tuple] = None, normal=None) -> torch.Tensor:
         """-> linear radiance [H,W,3] on the current torch stream.  albedo [H,W,3], roughness / metallic [H,W] or [H,W,1], envmap
         [He,We,3] (tensor or array, the `sh.py` equirectangular convention).  Every split into launches of `spp_per_launch` samples gives
         the same bits.  `rays` (optional int32 [H,W] on the device): the rays each pixel traced are added to it.  `tables`: what
-        `tables(envmap)` returned (default: built from `envmap` now)."""
+        `tables(envmap)` returned (default: built from `envmap` now).  `normal` [H,W,3] (unit length, used as given): the shading-normal
+        map ("Shading normals"); None shades with the face normals.  A tracer with objects refuses it."""
         H, W, dev = self.H, self.W, self.device
+        nrm = self._normal(normal, "render") if normal is not None else None
         a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
         if out is None:
             out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
@@ -332,7 +364,9 @@ class PathTracer:
                 env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]),
                 int(spp), int(max_depth), int(seed) & 0xFFFFFFFF, int(spp_per_launch), out.data_ptr(),
                 rays.data_ptr() if rays is not None else None, stream)
-        if self.objects is None:
+        if nrm is not None:
+            check(lib.matpbr_path_render_normals(*args, nrm.data_ptr()), "matpbr_path_render_normals")
+        elif self.objects is None:
             check(lib.matpbr_path_render(*args), "matpbr_path_render")
         else:
             check(lib.matpbr_path_render_objects(*args, ctypes.cast(self.objects, _P), len(self.objects)), "matpbr_path_render_objects")
@@ -341,11 +375,13 @@ class PathTracer:
     @torch.no_grad()
     def render_trans(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, mask, bg, ior: float = 1.2,
                      spec_trans: float = 0.4, refract_distance: float = 100.0, spp: int = 64, max_depth: int = 4, seed: int = 0,
-                     spp_per_launch: int = 8, tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     spp_per_launch: int = 8, tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None, normal=None) -> torch.Tensor:
         """`render` with the depth mesh shading as the reference's TransBSDF ("Transparency editing"): where
         `mask` [H,W] (bool) is set the surface is glass of index `ior` and transmission `spec_trans` over the picture `bg` [H,W,3].
         The maps are used as given (`relight.render_trans` edits them inside the mask first).  Forward only: there is no backward
-        pass through it, and a tracer with inserted objects refuses it."""
+        pass through it, a tracer with inserted objects refuses it, and it refuses a shading-normal map (`normal`)."""
+        if normal is not None:
+            raise ValueError("render_trans knows no shading normals: the transparency edit shades with the face normals")
         if self.objects is not None:
             raise ValueError("render_trans knows no inserted objects: build the PathTracer without `objects`")
         H, W, dev = self.H, self.W, self.device
@@ -370,18 +406,23 @@ class PathTracer:
     @torch.no_grad()
     def render_bwd(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, d_out: torch.Tensor, spp: int = 64,
                    max_depth: int = 4, seed: int = 0, spp_per_launch: int = 8, want=("a", "r", "m", "env"), grads: Optional[dict] = None,
-                   tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                   tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None, normal=None) -> Dict[str, torch.Tensor]:
         """The backward pass of `render` with the same arguments: d loss / d {"a" [H,W,3], "r" [H,W,1], "m" [H,W,1], "env" [He,We,3]}
         for d_out = d loss / d render [H,W,3], for the keys in `want`.  The derivative of the fixed-seed estimator with the sampling
         detached; bit-identical for every `spp_per_launch`.  `grads`: device buffers to ADD to (by key; the
-        missing ones start from zero).  `rays` (optional int32 [H,W]): the rays both replays traced are added to it."""
+        missing ones start from zero).  `rays` (optional int32 [H,W]): the rays both replays traced are added to it.  `normal`: the
+        shading-normal map of `render`; with it `want` may hold "n", d loss / d normal [H,W,3] with respect to the map's components as
+        free variables (normalising is the caller's)."""
         if self.objects is not None:
             raise ValueError("render_bwd knows no inserted objects: build the PathTracer without `objects` for gradients")
+        if "n" in want and normal is None:
+            raise ValueError("want 'n' needs the shading-normal map it is the gradient of: pass `normal`")
+        nrm = self._normal(normal, "render_bwd") if normal is not None else None
         H, W, dev = self.H, self.W, self.device
         a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
         He, We = int(env.shape[0]), int(env.shape[1])
         d_out = torch.as_tensor(d_out).to(dev, torch.float32).reshape(H, W, 3).contiguous()
-        shapes = {"a": (H, W, 3), "r": (H, W, 1), "m": (H, W, 1), "env": (He, We, 3)}
+        shapes = {"a": (H, W, 3), "r": (H, W, 1), "m": (H, W, 1), "env": (He, We, 3), "n": (H, W, 3)}
         grads = dict(grads or {})
         for k in want:
             if k not in shapes:
@@ -394,42 +435,50 @@ class PathTracer:
         if "env" in want and He * We > MAX_BWD_ENV_TEXELS:
             raise ValueError(f"the envmap gradient needs He * We <= {MAX_BWD_ENV_TEXELS}, got {He} x {We}")
         lib = load()
-        nbytes = int(lib.matpbr_path_render_bwd_workspace_bytes(H, W, He, We))
+        size = lib.matpbr_path_render_bwd_workspace_bytes if nrm is None else lib.matpbr_path_render_bwd_normals_workspace_bytes
+        nbytes = int(size(H, W, He, We))
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         ptr = lambda k: grads[k].data_ptr() if k in want else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        code = lib.matpbr_path_render_bwd(self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
-                                          env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), He, We, int(spp), int(max_depth),
-                                          int(seed) & 0xFFFFFFFF, int(spp_per_launch), d_out.data_ptr(), ptr("a"), ptr("r"), ptr("m"), ptr("env"),
-                                          self._ws.data_ptr(), nbytes, rays.data_ptr() if rays is not None else None, stream)
-        check(code, "matpbr_path_render_bwd")
+        args = (self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
+                env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), He, We, int(spp), int(max_depth),
+                int(seed) & 0xFFFFFFFF, int(spp_per_launch), d_out.data_ptr(), ptr("a"), ptr("r"), ptr("m"), ptr("env"),
+                self._ws.data_ptr(), nbytes, rays.data_ptr() if rays is not None else None, stream)
+        if nrm is None:
+            check(lib.matpbr_path_render_bwd(*args), "matpbr_path_render_bwd")
+        else:
+            check(lib.matpbr_path_render_bwd_normals(*args, nrm.data_ptr(), ptr("n")), "matpbr_path_render_bwd_normals")
         return {k: grads[k] for k in want}
 
 
 class PathRenderFn(torch.autograd.Function):
-    """out = PathTracer.render(a, r, m, env) (bit for bit), differentiable in a [H,W,3], r [H,W,1], m [H,W,1] and env [He,We,3] by
-    `render_bwd` with the forward's seed.  `ctx_in`: {"tracer", "spp", "max_depth", "seed", "spp_per_launch"} and the envmap-table cache
-    `PathTables`."""
+    """out = PathTracer.render(a, r, m, env[, normal=nrm]) (bit for bit), differentiable in a [H,W,3], r [H,W,1], m [H,W,1], env
+    [He,We,3] and the shading-normal map nrm [H,W,3] (None: face normals) by `render_bwd` with the forward's seed.  `ctx_in`:
+    {"tracer", "spp", "max_depth", "seed", "spp_per_launch"} and the envmap-table cache `PathTables`."""
 
     @staticmethod
-    def forward(ctx, a, r, m, env, ctx_in):
+    def forward(ctx, a, r, m, env, ctx_in, nrm=None):
         tracer = ctx_in["tracer"]
         tabs = ctx_in["tables"].get(tracer, env)
         kw = {k: ctx_in[k] for k in ("spp", "max_depth", "seed", "spp_per_launch")}
-        out = tracer.render(a.detach(), r.detach(), m.detach(), env.detach(), tables=tabs, **kw)
-        ctx.save_for_backward(a, r, m, env)
+        out = tracer.render(a.detach(), r.detach(), m.detach(), env.detach(), tables=tabs, normal=None if nrm is None else nrm.detach(), **kw)
+        ctx.save_for_backward(a, r, m, env, *(() if nrm is None else (nrm,)))
         ctx.tracer, ctx.tabs, ctx.kw = tracer, tabs, kw
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        a, r, m, env = ctx.saved_tensors
+        a, r, m, env, *rest = ctx.saved_tensors
+        nrm = rest[0] if rest else None
         need = ctx.needs_input_grad
-        want = [k for k, n in zip(("a", "r", "m", "env"), need[:4]) if n]
-        g = ctx.tracer.render_bwd(a.detach(), r.detach(), m.detach(), env.detach(), d_out, want=want, tables=ctx.tabs, **ctx.kw) if want else {}
+        need = need[:4] + (bool(nrm is not None and need[5]),)
+        want = [k for k, n in zip(("a", "r", "m", "env", "n"), need) if n]
+        g = ctx.tracer.render_bwd(a.detach(), r.detach(), m.detach(), env.detach(), d_out, want=want, tables=ctx.tabs,
+                                  normal=None if nrm is None else nrm.detach(), **ctx.kw) if want else {}
         return (g["a"].reshape(a.shape) if need[0] else None, g["r"].reshape(r.shape) if need[1] else None,
-                g["m"].reshape(m.shape) if need[2] else None, g["env"].reshape(env.shape) if need[3] else None, None)
+                g["m"].reshape(m.shape) if need[2] else None, g["env"].reshape(env.shape) if need[3] else None, None,
+                g["n"].reshape(nrm.shape) if need[4] else None)
 
 
 class PathTables:

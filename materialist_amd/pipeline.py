@@ -393,17 +393,23 @@ def inverse_image(img_inverse_path: str, save_name: str, opt_src: str = "arm", o
                   opt_env_from: int = 0, save_path: Optional[str] = None, model_name: str = "pos_mlp", size: int = 512, spp: int = 64,
                   num_epochs: int = 5000, pred_dir: Optional[str] = None, device: str = "cuda", sync_every: int = 10,
                   log=print, matnet_weights: Optional[str] = None, frame_interval: float = 0.2, matnet=None, geometry: str = "mesh",
-                  digests: Optional[list] = None, integrator: str = "sh", max_depth: int = 4, seed: int = 0) -> Dict[str, object]:
+                  digests: Optional[list] = None, integrator: str = "sh", max_depth: int = 4, seed: int = 0,
+                  shading_normals: str = "face") -> Dict[str, object]:
     """inverse_img_w_mi.py:623-770 (resolution-generic: `size`; `model_name` is honoured, F4).  `matnet`: an already loaded MaterialNet
     (run_batch.py loads the weights once on rank 0 and broadcasts them).  `integrator` "path": every part fits through the
-    path-traced render of the depth mesh (`max_depth`, renders seeded from `seed`; render.Scene.set_integrator) on the operator face."""
+    path-traced render of the depth mesh (`max_depth`, renders seeded from `seed`; render.Scene.set_integrator) on the operator face.  `shading_normals` "map"
+    (with "path" only): 'n' in `opt_order` is accepted and the path render shades with, and fits, the normal map."""
     from . import optimize, render
 
     if model_name not in ("none", "pos_mlp"):
         raise ValueError("model_name should be 'none' or 'pos_mlp'")
     if integrator not in ("sh", "path"):
         raise ValueError(f"--integrator: 'sh' or 'path', got {integrator!r}")
-    if integrator == "path" and "n" in "".join(opt_order):
+    if shading_normals not in ("face", "map"):
+        raise ValueError(f"--shading_normals: 'face' or 'map', got {shading_normals!r}")
+    if shading_normals == "map" and integrator != "path":
+        raise ValueError("--shading_normals map needs --integrator path")
+    if integrator == "path" and shading_normals == "face" and "n" in "".join(opt_order):
         raise ValueError(f"--integrator path shades with the mesh's face normals: it cannot optimise normals ('n' in --opt_order {list(opt_order)})")
     log(f"Inverse image {img_inverse_path}")
     output_dir = get_output_dir(save_name, save_path)
@@ -485,9 +491,9 @@ def inverse_image(img_inverse_path: str, save_name: str, opt_src: str = "arm", o
         rm = _mesh.reference_mesh(d_mesh, render.DEFAULT_FOV)                                    # :726-727, minAngle 6, gap closing included
         _mesh.write_ply(mesh_path, rm["vertices"], rm["triangles"])
     scene = render.load_estimated_mesh(t(depth), use_mesh_normal=use_mesh_normal, max_path=max_depth, device=device, mesh_mask=mesh_mask,
-                                       geometry=geometry, integrator=integrator, seed=seed)
+                                       geometry=geometry, integrator=integrator, seed=seed, shading_normals=shading_normals)
     if integrator == "path":
-        log(f"integrator path: max_depth {max_depth}, seed {seed}, BVH of {scene.path['tracer'].stats['n_tris']} triangles; every part runs on "
+        log(f"integrator path: max_depth {max_depth}, seed {seed}, shading normals {shading_normals!r}, BVH of {scene.path['tracer'].stats['n_tris']} triangles; every part runs on "
             "the operator face")
     if digests is not None:
         digests.append(("prep", _loss.tensors_digest(t(img), t(depth), scene.geo_normal)))       # the image as read, the depth as flipped, the mesher's normals

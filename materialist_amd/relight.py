@@ -197,24 +197,30 @@ def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], d
     return PathTracer(V, T, H, W, DEFAULT_FOV, device=device, objects=objects)
 
 
-def _check_integrator(integrator: str) -> None:
+def _check_integrator(integrator: str, shading_normals: str = "face") -> None:
     if integrator not in ("sh", "path"):
         raise ValueError(f"integrator must be 'sh' or 'path', got {integrator!r}")
+    if shading_normals not in ("face", "map"):
+        raise ValueError(f"shading_normals must be 'face' or 'map', got {shading_normals!r}")
+    if shading_normals == "map" and integrator != "path":
+        raise ValueError("shading_normals='map' needs integrator='path' (the 'sh' render takes its normals by the scene's name)")
 
 
 def render_real(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
                 spp: int = 64, device="cuda", edit: Optional[Dict[str, object]] = None, integrator: str = "sh", max_depth: int = 4,
-                seed: int = 0) -> str:
+                seed: int = 0, shading_normals: str = "face") -> str:
     """render_final.py:148-203,241-260: one re-render under `env_path` -> mi_<name>_<env>_<edit flag>.exr / .png.
-    integrator "sh": the deterministic render (SH25 light, direct, unshadowed); "path": the path tracer, `max_depth` / `seed`."""
-    _check_integrator(integrator)
+    integrator "sh": the deterministic render (SH25 light, direct, unshadowed); "path": the path tracer, `max_depth` / `seed`, shading
+    with the mesh's face normals or, with `shading_normals="map"`, with best_results/normal.exr whatever the scene is called."""
+    _check_integrator(integrator, shading_normals)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
     edit_flag = apply_edit(mat, edit)
     if integrator == "path":
         img = _path_tracer(scene_dir, save_name, mat, device).render(mat["albedo"], mat["roughness"], mat["metallic"],
-                                                                     load_image(env_path), spp, max_depth, seed)
+                                                                     load_image(env_path), spp, max_depth, seed,
+                                                                     normal=mat["normal"] if shading_normals == "map" else None)
     else:
         rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))
         img = rl.frames(envmap_to_light(load_image(env_path))[None])[0]
@@ -331,10 +337,10 @@ def render_trans(save_name: str, ior: float = 1.2, keep_albedo_color: bool = Fal
 def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int = 36, rotation_step: float = 10.0,
                           input_path: Optional[str] = None, save_path: Optional[str] = None, spp: int = 64, device="cuda",
                           write_frames: bool = True, edit: Optional[Dict[str, object]] = None, integrator: str = "sh",
-                          max_depth: int = 4, seed: int = 0) -> Dict[str, object]:
+                          max_depth: int = 4, seed: int = 0, shading_normals: str = "face") -> Dict[str, object]:
     """render_final.py:300-418: `frames` renders, the envmap rolled by int(angle/360*W) columns per frame.  integrator "sh": the
-    rolled light is the SH rotation of the projected envmap; "path": the path tracer renders the rolled texels themselves."""
-    _check_integrator(integrator)
+    rolled light is the SH rotation of the projected envmap; "path": the path tracer renders the rolled texels themselves (`shading_normals` as in `render_real`)."""
+    _check_integrator(integrator, shading_normals)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
     env = load_image(env_path)
@@ -345,8 +351,9 @@ def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int =
     apply_edit(mat, edit)
     if integrator == "path":
         pt = _path_tracer(scene_dir, save_name, mat, device)
+        nrm = mat["normal"] if shading_normals == "map" else None
         render_frames = lambda f0, f1: torch.stack([pt.render(mat["albedo"], mat["roughness"], mat["metallic"], np.roll(env, shifts[f], axis=1),
-                                                              spp, max_depth, seed) for f in range(f0, f1)])
+                                                              spp, max_depth, seed, normal=nrm) for f in range(f0, f1)])
     else:
         lights = [_sh.rotate_y_matrix(2 * np.pi * s / We) @ light0 for s in shifts]
         rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))

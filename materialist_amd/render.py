@@ -161,21 +161,27 @@ class Scene:
         self.integrator = "sh"                           # "sh": the deterministic render; "path": pathtrace.PathRenderFn (set_integrator)
         self.path: Optional[dict] = None
         self.last_seed: Optional[int] = None             # "path": the seed of the last render (its backward pass replays it)
+        self.shading_normals = "face"                    # "path": "face" = the mesh's face normals only; "map" = shape.bsdf.n may shade
 
     # -- integrator ----------------------------------------------------------------------------------
-    def set_integrator(self, kind: str, vertices=None, triangles=None, max_depth: int = 4, seed: int = 0, spp_per_launch: int = 8) -> None:
+    def set_integrator(self, kind: str, vertices=None, triangles=None, max_depth: int = 4, seed: int = 0, spp_per_launch: int = 8,
+                       shading_normals: str = "face") -> None:
         """"sh" (default): the deterministic render, direct light under the SH25 projection of the light.  "path": the path-traced render
         of the triangle mesh (vertices [V,3], triangles [T,3] in the renderer's frame: mesh.reference_mesh) with `max_depth`, differentiable
         in the maps and the envmap texels (pathtrace.PathRenderFn).  Each render draws a fresh seed from a sequence
-        seeded by `seed`, so a run is reproducible.  The path render shades with face normals and takes the light as texels."""
+        seeded by `seed`, so a run is reproducible.  The path render takes the light as texels.  `shading_normals`: "face" (default) shades with
+        the mesh's face normals and refuses a normal map; "map" accepts use_mesh_normal=False and shape.bsdf.n, which then shades as
+        MatDiffBSDF's `normal` does and receives a gradient ("Shading normals")."""
+        if shading_normals not in ("face", "map"):
+            raise ValueError(f"shading_normals: 'face' or 'map', got {shading_normals!r}")
         if kind == "sh":
-            self.integrator, self.path = "sh", None
+            self.integrator, self.path, self.shading_normals = "sh", None, "face"
             return
         if kind != "path":
             raise ValueError(f"integrator: 'sh' or 'path', got {kind!r}")
         if self.B != 1:
             raise ValueError("integrator 'path' renders one image per scene (batch 1)")
-        if not self.use_mesh_normal:
+        if not self.use_mesh_normal and shading_normals == "face":
             raise ValueError("integrator 'path' shades with the mesh's face normals: it needs use_mesh_normal=True (no 'n' in --opt_order)")
         if vertices is None or triangles is None:
             raise ValueError("integrator 'path' needs the scene's mesh (vertices, triangles)")
@@ -184,7 +190,7 @@ class Scene:
         tracer = pathtrace.PathTracer(vertices, triangles, self.H, self.W, self.fov, device=self.device)
         self.path = {"tracer": tracer, "max_depth": int(max_depth), "base_seed": int(seed), "rng": np.random.default_rng(int(seed)),
                      "spp_per_launch": int(spp_per_launch), "tables": pathtrace.PathTables()}
-        self.integrator = "path"
+        self.integrator, self.shading_normals = "path", shading_normals
 
     def next_seed(self) -> int:
         """The seed of the next "path" render: drawn from the sequence `set_integrator` seeded."""
@@ -193,7 +199,7 @@ class Scene:
     def _render_path(self, spp: int) -> torch.Tensor:
         from . import pathtrace
 
-        if not self.use_mesh_normal:
+        if not self.use_mesh_normal and self.shading_normals == "face":
             raise ValueError("integrator 'path' shades with the mesh's face normals: shape.bsdf.use_mesh_normal must stay True")
         env = self.emitter_data
         if env is self.light or env.ndim != 3 or env.shape[-1] != 3 or tuple(env.shape[-2:]) == (_sh.NSH, 3):
@@ -202,7 +208,8 @@ class Scene:
         args = dict(self.path, spp=int(spp), seed=self.last_seed)
         r = self.r.reshape(self.H, self.W, 1)
         m = self.m.reshape(self.H, self.W, 1)
-        return pathtrace.PathRenderFn.apply(self.a, r, m, env, args)
+        nrm = None if self.use_mesh_normal else self.shading_normal().reshape(self.H, self.W, 3)   # None: the plain kernel
+        return pathtrace.PathRenderFn.apply(self.a, r, m, env, args, nrm)
 
     # -- pixels without geometry ---------------------------------------------------------------------
     def set_mesh_mask(self, mask: Optional[torch.Tensor]) -> None:
@@ -238,9 +245,11 @@ class Scene:
 
     def _set(self, key, value):
         if self.integrator == "path":
-            if key == "shape.bsdf.n" and value is not None and value is not self.n:
+            if self.shading_normals == "map" and key in ("shape.bsdf.n", "shape.bsdf.use_mesh_normal"):
+                pass
+            elif key == "shape.bsdf.n" and value is not None and value is not self.n:
                 raise ValueError("integrator 'path' shades with the mesh's face normals: a normal map (shape.bsdf.n) cannot be used")
-            if key == "shape.bsdf.use_mesh_normal" and not value:
+            elif key == "shape.bsdf.use_mesh_normal" and not value:
                 raise ValueError("integrator 'path' shades with the mesh's face normals: use_mesh_normal=False cannot be used")
             if key == "emitter.data" and (value.ndim != 3 or value.shape[-1] != 3 or tuple(value.shape[-2:]) == (_sh.NSH, 3)):
                 raise ValueError(f"integrator 'path' needs emitter.data as envmap texels [He,We,3], got {tuple(value.shape)}")
@@ -347,15 +356,20 @@ def traverse(scene: Scene) -> SceneParameters:
 
 def load_estimated_mesh(depth: Optional[torch.Tensor], use_mesh_normal: bool, max_path: int = 4, height: int = 512, width: int = 512,
                         device="cuda", fov_x_deg: float = DEFAULT_FOV, batch: int = 1, mesh_mask: Optional[torch.Tensor] = None,
-                        geometry: str = "depth", integrator: str = "sh", seed: int = 0) -> Scene:
+                        geometry: str = "depth", integrator: str = "sh", seed: int = 0, shading_normals: str = "face") -> Scene:
     """Counterpart of load_estimated_mesh(mesh_path, use_mesh_normal, max_path) (inverse_img_w_mi.py:30-56).
     The reference loads a .ply triangulated from depth; the per-pixel build needs only the geometric normal
     of the heightfield, computed on the GPU from `depth` [H,W] (or [B,H,W]).  Under `integrator="sh"` `max_path` is accepted for
     signature compatibility: the deterministic render is direct lighting only.  `integrator="path"`: the
     path-traced render of the reference's mesh of `depth` (pixels of `mesh_mask` without triangles) with max_depth = `max_path`,
-    random sequence seeded by `seed` (Scene.set_integrator)."""
+    random sequence seeded by `seed`; `shading_normals="map"` lets it shade with `shape.bsdf.n` when `use_mesh_normal` is False
+    (Scene.set_integrator)."""
     if integrator not in ("sh", "path"):
         raise ValueError(f"integrator: 'sh' or 'path', got {integrator!r}")
+    if shading_normals not in ("face", "map"):
+        raise ValueError(f"shading_normals: 'face' or 'map', got {shading_normals!r}")
+    if shading_normals == "map" and integrator != "path":
+        raise ValueError("shading_normals='map' is the path integrator's switch: under 'sh' use_mesh_normal alone selects the normal map")
     if integrator == "path" and (depth is None or depth.ndim != 2):
         raise ValueError("integrator 'path' needs one [H,W] depth map to mesh")
     geo = None
@@ -392,7 +406,7 @@ def load_estimated_mesh(depth: Optional[torch.Tensor], use_mesh_normal: bool, ma
         if mesh_mask is not None:
             d_host[mesh_mask.cpu().numpy().astype(bool).reshape(d_host.shape)] = 0.0       # inverse_img_w_mi.py:723
         rm = _mesh.reference_mesh(d_host, fov_x_deg)
-        scene.set_integrator("path", rm["vertices"], rm["triangles"], max_depth=max_path, seed=seed)
+        scene.set_integrator("path", rm["vertices"], rm["triangles"], max_depth=max_path, seed=seed, shading_normals=shading_normals)
     return scene
 
 

@@ -28,9 +28,14 @@ def parse_args(argv=None):
                          "ignored by --mode oi, which always path traces")
     ap.add_argument("--max_depth", type=int, default=4, help="--integrator path: Mitsuba's max_depth (1 emission, 2 direct + shadows, 4 the reference's)")
     ap.add_argument("--seed", type=int, default=0, help="--integrator path and --mode oi: random seed")
+    ap.add_argument("--shading_normals", choices=("face", "map"), default="face",
+                    help="--integrator path: face = shade with the mesh's face normals (default); map = shade with best_results/normal.exr")
     ap.add_argument("--oi_iters", type=int, default=10, help="--mode oi: renders averaged (seeds seed, seed + 1, ...)")
     ap.add_argument("--oi_max_depth", type=int, default=16, help="--mode oi: Mitsuba's max_depth (a camera path through glass needs 5 to see light)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.shading_normals == "map" and (a.integrator != "path" or a.mode == "oi"):
+        ap.error("--shading_normals map needs --integrator path and --mode real or rolling (inserted objects know no normal map)")
+    return a
 
 
 def main(argv=None):
@@ -38,7 +43,7 @@ def main(argv=None):
     from materialist_amd import relight
 
     edit = {"albedo": a.edit_albedo, "roughness": a.edit_roughness, "metallic": a.edit_metallic}
-    it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed}
+    it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed, "shading_normals": a.shading_normals}
     if a.mode == "real":
         print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it))
     elif a.mode == "rolling":
