@@ -44,6 +44,10 @@ enum {
     MATPBR_PATH_BSDF_DIFFUSE = 2,    /* one-sided Lambertian: p = reflectance RGB in [0, 1] */
 };
 
+/* OR-ed into MatpbrPathObject.kind: the object shades with interpolated corner normals ("Smooth inserted
+ * objects").  Only matpbr_path_render_objects_normals takes it; to matpbr_path_render_objects it is an unknown kind. */
+#define MATPBR_PATH_OBJECT_SMOOTH 0x100
+
 /* One inserted mesh: triangles [first_tri, first_tri + n_tri) of the mesh handed to matpbr_path_bvh_build_objects (ids at or
  * above its n_scene_tri), outward winding. */
 typedef struct MatpbrPathObject {
@@ -121,6 +125,33 @@ int matpbr_path_render_objects(const void* nodes, const void* tris, const float*
  * pdf[N] (solid angle; for the dielectric the probability of the chosen event), flags[N] (bit 0: delta, bit 1: transmitted). */
 int matpbr_path_object_sample_host(const MatpbrPathObject* object, const float* n, const float* wo, const float* u, long N, float* wi,
                                    float* weight, float* pdf, int32_t* flags);
+
+/* matpbr_path_render_objects where an object whose kind carries MATPBR_PATH_OBJECT_SMOOTH shades with its vertex normals.  obj_nrm
+ * (DEVICE, fp32, [n_tri - n_scene_tri, 3, 3]): one normal per corner of every inserted triangle, in input order, indexed by
+ * id - n_scene_tri, outward, any length; the triangles of objects without the flag are never read.  At a hit on a smooth object
+ * u, v are Moller-Trumbore's (u the second input vertex's, v the third's), ns = normalize((1 - u - v) n0 + u n1 + v n2), and
+ * ns = ng, the face normal, where ns is not finite or of zero length, where ns . ng <= 0, or where (ns . wo)(ng . wo) <= 0.  The
+ * BSDF shades with ns, ng keeps the geometry (back-face test, spawn offset, side of an emitter sample, a diffuse sample below ng
+ * ends the path), and a dielectric event about ns that disagrees with ng about crossing the surface is redone about ng.  With
+ * obj_nrm == NULL or no flagged object this launches matpbr_path_render_objects' kernel and gives its bits.  Invalid arguments,
+ * besides matpbr_path_render_objects': a flagged object with obj_nrm == NULL, an object range that starts below n_scene_tri. */
+int matpbr_path_render_objects_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                       float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                       int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri);
+
+/* The shading normal of a smooth object on the CPU, with the routines the kernel runs (the barycentrics of the winning triangle
+ * and the interpolation with its first two fallbacks): per lane the triangle record tri[N,3,3] = (v0, e1, e2), the corner normals
+ * nrm[N,3,3] and the ray o[N,3], d[N,3] -> u[N], v[N], ns[N,3].  The face normal is normalize(e1 x e2), formed here with a plain
+ * division (the kernel's uses the device's reciprocal square root). */
+int matpbr_path_object_normal_host(const float* tri, const float* nrm, const float* o, const float* d, long N, float* u, float* v, float* ns);
+
+/* matpbr_path_object_sample_host at vertices with a face normal ng[N,3] and a shading normal ns[N,3] (unit length, as
+ * matpbr_path_object_normal_host returns it), with the routine the kernel runs at a smooth object: the third fallback (ns = ng where
+ * the two disagree about wo's side), the sample about ns, the dielectric's redo about ng where the event disagrees with the geometry,
+ * weight 0 for a diffuse sample below ng or a diffuse vertex seen from behind ng.  Same outputs, same flags. */
+int matpbr_path_object_sample_shading_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* u,
+                                           long N, float* wi, float* weight, float* pdf, int32_t* flags);
 
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;

@@ -371,6 +371,70 @@ __host__ __device__ inline void object_sample(int kind, const float p[3], const 
     pdf = ct * 0.31830988618379067154f;
 }
 
+// ---- smooth inserted objects ("Smooth inserted objects") --------------------------------------------------
+// An object whose kind carries MATPBR_PATH_OBJECT_SMOOTH shades with its corner normals interpolated at the hit point; the face
+// normal ng keeps everything geometric.  The table, the corner normals (one per corner of every inserted triangle, in input order,
+// indexed by id - n_scene_tri) and n_scene_tri travel to the kernel by value.  Interpolation, the fallbacks and the redo are
+// __host__ __device__ (plain divisions and sqrtf): the CPU entry points run what the kernel runs.
+struct SmoothObjects {
+    ObjTable t;
+    const float* nrm;   // [n_tri - n_scene_tri, 3, 3]
+    int32_t n_scene_tri;
+};
+// object_of for the smooth table: the kind still carries the flag bit
+__device__ __forceinline__ int object_of(const SmoothObjects& so, int id, float p[3]) { return object_of(so.t, id, p); }
+
+// Moller-Trumbore's u, v of the ray o + t d on (v0, e1, e2), tri_test's operations: u belongs to the second input vertex, v to the
+// third.  A ray in the triangle's plane (det 0) gives values that are not finite, which the interpolation below turns into flat.
+__host__ __device__ inline void tri_uv(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d[3], float& u,
+                                       float& v) {
+    float pv[3], qv[3];
+    cross3(d, e2, pv);
+    const float idet = 1.0f / dot3h(e1, pv);
+    const float tv[3] = {o[0] - v0[0], o[1] - v0[1], o[2] - v0[2]};
+    u = dot3h(tv, pv) * idet;
+    cross3(tv, e1, qv);
+    v = dot3h(d, qv) * idet;
+}
+// ns = normalize((1 - u - v) n0 + u n1 + v n2) for the corner normals cn = (n0, n1, n2); ns = ng where the sum is not finite or has
+// zero length, or where ns . ng <= 0
+__host__ __device__ inline void smooth_normal(const float cn[9], float u, float v, const float ng[3], float ns[3]) {
+    const float w = (1.0f - u) - v;
+    for (int c = 0; c < 3; ++c) ns[c] = w * cn[c] + u * cn[3 + c] + v * cn[6 + c];
+    const float l2 = dot3h(ns, ns);
+    bool ok = l2 > 0.0f && l2 <= FLT_MAX;
+    if (ok) {
+        const float il = 1.0f / sqrtf(l2);
+        for (int c = 0; c < 3; ++c) ns[c] *= il;
+        ok = dot3h(ns, ng) > 0.0f;
+    }
+    if (!ok)
+        for (int c = 0; c < 3; ++c) ns[c] = ng[c];
+}
+// the third fallback: ns = ng where the two normals disagree about the side the viewer is on
+__host__ __device__ inline void smooth_side(const float ng[3], const float wo[3], float ns[3]) {
+    if (!(dot3h(ns, wo) * dot3h(ng, wo) > 0.0f))
+        for (int c = 0; c < 3; ++c) ns[c] = ng[c];
+}
+// object_sample at a vertex with the face normal ng and the shading normal ns (the third fallback applied here too: it is
+// idempotent).  dielectric: the event about ns must agree with the geometry, a reflected wi on wo's side of ng and a transmitted
+// one on the other; if it does not, the event is redone about ng with the same dim 6, so that "transmitted" always means "crossed
+// the surface".  diffuse: sampled about ns; seen from behind ng, or sampled below ng, the path ends (weight 0).
+__host__ __device__ inline void object_sample_shading(int kind, const float p[3], const float ng[3], const float ns_in[3], const float wo[3],
+                                                      float u_lobe, float u0, float u1, float wi[3], float w[3], float& pdf, int& flags) {
+    float n[3] = {ns_in[0], ns_in[1], ns_in[2]};
+    smooth_side(ng, wo, n);
+    const float go = dot3h(ng, wo);
+    for (int pass = 0;; ++pass) {
+        object_sample(kind, p, n, wo, u_lobe, u0, u1, wi, w, pdf, flags);
+        if (kind != MATPBR_PATH_BSDF_DIELECTRIC || pass == 1) break;
+        const float side = dot3h(ng, wi) * go;
+        if ((flags & kFlagTransmitted) ? side < 0.0f : side > 0.0f) break;
+        for (int c = 0; c < 3; ++c) n[c] = ng[c];
+    }
+    if (kind != MATPBR_PATH_BSDF_DIELECTRIC && !(go > 0.0f && dot3h(ng, wi) > 0.0f)) w[0] = w[1] = w[2] = 0.0f;
+}
+
 // ---- transparency editing ("Transparency editing"): TransBSDF (myutils/mi_plugin.py:1477-1771) -----------
 // Where mask[tp] is set the depth mesh shades as a sheet of glass in front of the photograph `bg`, read at the texel a ray refracted
 // twice through the sheet lands on.  The edit travels to the kernel by value, in the place of the object table.  The masked-branch
@@ -541,10 +605,12 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 // (Objects = ObjTable, passed by value); EDIT: transparency editing (Objects = TransEdit, by value in the table's place).  With
 // NoObjects every `if (OBJ ...)`, `if (EDIT ...)` and `if (NRM ...)` below folds away and the walk is the depth mesh's alone, the code
 // the kernel had before there were objects; with ObjTable every `if (EDIT ...)` folds away.  NRM: shading normals (Objects =
-// ShadeNormals): `n` stays the face normal ng and `ns` is the map's.
+// ShadeNormals): `n` stays the face normal ng and `ns` is the map's.  SMOOTH: smooth inserted objects (Objects = SmoothObjects): OBJ
+// with `ns` the interpolated corner normal at the vertices of a flagged object; every `if (SMOOTH ...)` folds away in the other four.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool OBJ = std::is_same<Objects, ObjTable>::value;
+    constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value;
+    constexpr bool OBJ = std::is_same<Objects, ObjTable>::value || SMOOTH;
     constexpr bool EDIT = std::is_same<Objects, TransEdit>::value;
     constexpr bool NRM = std::is_same<Objects, ShadeNormals>::value;
     __shared__ int s_stack[kStack * kBlock];
@@ -599,6 +665,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             int kind = 0;          // (OBJ) 0: the depth mesh; else the inserted object's BSDF and its parameters
             float op[3] = {0.0f, 0.0f, 0.0f};
             if (OBJ) kind = object_of(ot, __float_as_int(q.tris[3 * k].w), op);
+            bool smooth = false;   // (SMOOTH) the object shades with its interpolated corner normals, `ns` below
+            if constexpr (SMOOTH) {
+                smooth = (kind & MATPBR_PATH_OBJECT_SMOOTH) != 0;
+                kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
+            }
             // a hit on the back of a triangle ends the path (glass shades from both sides)
             if (!(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !(dot3(n, wo) > 0.0f)) break;
             float p[3];
@@ -615,6 +686,19 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             if constexpr (NRM) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) ns[c] = ot.nrm[3 * tp + c];
+            }
+            if constexpr (SMOOTH) {
+                if (smooth) {   // u, v of the winning triangle once more; its nine corner normals, consumed at once
+                    const float4 A = q.tris[3 * k];
+                    const float v0[3] = {A.x, A.y, A.z};
+                    const float* cp = ot.nrm + 9 * (long)(__float_as_int(A.w) - ot.n_scene_tri);
+                    float cn[9], bu, bv;
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) cn[c] = cp[c];
+                    tri_uv(v0, e1, e2, o, d, bu, bv);
+                    smooth_normal(cn, bu, bv, n, ns);
+                    smooth_side(n, wo, ns);
+                }
             }
             bool masked = false;   // (EDIT) the vertex reads a masked texel: TransBSDF's glass over bg at the refracted texel
             float bgv[3] = {0.0f, 0.0f, 0.0f};
@@ -638,7 +722,8 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 if (pdf_e > 0.0f && dot3(n, wl) > 0.0f) {
                     float f[3], pdf_b;
                     if (OBJ && kind == MATPBR_PATH_BSDF_DIFFUSE) {   // f cos = rho / pi max(n . wi, 0), pdf = cos / pi
-                        pdf_b = dot3(n, wl) * kInvPi;
+                        if constexpr (SMOOTH) pdf_b = fmaxf(dot3(ns, wl), 0.0f) * kInvPi;   // ns = n on a flat object
+                        else pdf_b = dot3(n, wl) * kInvPi;
 #pragma unroll
                         for (int c = 0; c < 3; ++c) f[c] = op[c] * pdf_b;
                     } else if (EDIT && masked) {
@@ -666,7 +751,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             float wi[3], wgt[3], pdf_s;
             if (OBJ && kind != 0) {
                 int flags;
-                object_sample(kind, op, n, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
+                if (SMOOTH && smooth)
+                    object_sample_shading(kind, op, n, ns, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
+                else
+                    object_sample(kind, op, n, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
                 prev_delta = (flags & kFlagDelta) != 0;
                 const float side = dot3(n, wi) > 0.0f ? eps : -eps;   // spawn on the side the new ray leaves on
 #pragma unroll
@@ -1152,12 +1240,19 @@ bool object_valid(const MatpbrPathObject& ob) {
     }
     return false;
 }
-bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot) {
+// `n_smooth` (nullable): where given, a kind may carry MATPBR_PATH_OBJECT_SMOOTH, and the flagged objects are counted
+bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, int* n_smooth = nullptr) {
     if (n_objects < 0 || n_objects > MATPBR_PATH_MAX_OBJECTS || (n_objects > 0 && !objects)) return false;
     ot.n = n_objects;
     ot.min_id = INT32_MAX;
+    if (n_smooth) *n_smooth = 0;
     for (int k = 0; k < n_objects; ++k) {
-        if (!object_valid(objects[k])) return false;
+        MatpbrPathObject plain = objects[k];
+        if (n_smooth && (plain.kind & MATPBR_PATH_OBJECT_SMOOTH)) {
+            plain.kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
+            ++*n_smooth;
+        }
+        if (!object_valid(plain)) return false;
         for (int j = 0; j < k; ++j)   // ranges may not overlap
             if (objects[k].first_tri < objects[j].first_tri + objects[j].n_tri && objects[j].first_tri < objects[k].first_tri + objects[k].n_tri)
                 return false;
@@ -1180,7 +1275,7 @@ const char* matpbr_path_strerror(int code) {
     switch (code) {
         case MATPBR_PATH_OK: return "ok";
         case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, max_depth outside 1..16, "
-                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, a bad object table or a bad transparency edit)";
+                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, a bad object table, a smooth object without corner normals or a bad transparency edit)";
         case MATPBR_PATH_ERR_LAUNCH: return "HIP kernel launch failed";
         case MATPBR_PATH_ERR_CAPACITY: return "node buffer smaller than matpbr_path_bvh_size() asks for";
         default: return "unknown error";
@@ -1347,12 +1442,13 @@ int matpbr_path_render(const void* nodes, const void* tris, const float* a, cons
                                       spp_per_launch, out, rays, stream, nullptr, 0);
 }
 
-// the four renders: `edit` (nullable) selects the transparency-editing instantiation, else `nrm` the shading-normal one, else
-// n_objects > 0 the object one
+// the five renders: `edit` (nullable) selects the transparency-editing instantiation, else `nrm` the shading-normal one, else
+// `obj_nrm` the smooth-object one, else n_objects > 0 the object one
 static int render_common(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
                          const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                          int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream, const ObjTable& ot,
-                         int n_objects, const TransEdit* edit, const float* nrm = nullptr) {
+                         int n_objects, const TransEdit* edit, const float* nrm = nullptr, const float* obj_nrm = nullptr,
+                         int32_t n_scene_tri = 0) {
     if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !out || H <= 0 || W <= 0 || He <= 0 || We <= 0 ||
         spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f))
         return MATPBR_PATH_ERR_INVALID_ARG;
@@ -1377,6 +1473,7 @@ static int render_common(const void* nodes, const void* tris, const float* a, co
         const int first = s0 == 0 ? 1 : 0, last = s1 == spp ? 1 : 0;
         if (edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, *edit);
         else if (nrm) hipLaunchKernelGGL(path_kernel<ShadeNormals>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ShadeNormals{nrm});
+        else if (obj_nrm) hipLaunchKernelGGL(path_kernel<SmoothObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, SmoothObjects{ot, obj_nrm, n_scene_tri});
         else if (n_objects > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ot);
         else hipLaunchKernelGGL(path_kernel<NoObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, NoObjects{});
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
@@ -1397,6 +1494,46 @@ int matpbr_path_render_objects(const void* nodes, const void* tris, const float*
     if (!object_table(objects, n_objects, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
     return render_common(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out,
                          rays, stream, ot, n_objects, nullptr);
+}
+
+int matpbr_path_render_objects_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                       float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                       int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri) {
+    ObjTable ot{};
+    int n_smooth = 0;
+    if (!object_table(objects, n_objects, ot, &n_smooth) || n_scene_tri < 0 || n_scene_tri > INT32_MAX || (n_smooth > 0 && !obj_nrm))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int k = 0; k < n_objects; ++k)
+        if (objects[k].first_tri < n_scene_tri) return MATPBR_PATH_ERR_INVALID_ARG;
+    return render_common(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out,
+                         rays, stream, ot, n_objects, nullptr, nullptr, n_smooth > 0 ? obj_nrm : nullptr, (int32_t)n_scene_tri);
+}
+
+int matpbr_path_object_normal_host(const float* tri, const float* nrm, const float* o, const float* d, long N, float* u, float* v, float* ns) {
+    if (!tri || !nrm || !o || !d || !u || !v || !ns || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        const float *v0 = tri + 9 * k, *e1 = v0 + 3, *e2 = v0 + 6;
+        float ng[3];
+        cross3(e1, e2, ng);
+        const float il = 1.0f / sqrtf(dot3h(ng, ng));
+        for (int c = 0; c < 3; ++c) ng[c] *= il;
+        tri_uv(v0, e1, e2, o + 3 * k, d + 3 * k, u[k], v[k]);
+        smooth_normal(nrm + 9 * k, u[k], v[k], ng, ns + 3 * k);
+    }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_object_sample_shading_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* u,
+                                           long N, float* wi, float* weight, float* pdf, int32_t* flags) {
+    if (!object || !ng || !ns || !wo || !u || !wi || !weight || !pdf || !flags || N < 0 || !object_valid(*object)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        int fl = 0;
+        object_sample_shading(object->kind, object->p, ng + 3 * k, ns + 3 * k, wo + 3 * k, u[3 * k], u[3 * k + 1], u[3 * k + 2], wi + 3 * k,
+                              weight + 3 * k, pdf[k], fl);
+        flags[k] = fl;
+    }
+    return MATPBR_PATH_OK;
 }
 
 int matpbr_path_render_trans(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,

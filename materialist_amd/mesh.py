@@ -95,11 +95,13 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply_any(path: str) -> Tuple[np.ndarray, np.ndarray]:
+def read_ply_any(path: str, normals: bool = False):
     """A PLY somebody else wrote (an inserted object, `oi.ply`) -> (vertices [Nv,3] float64, triangles [Nt,3] int32).  ASCII or
-    binary little-endian; x, y, z of any scalar type, other vertex properties (normals, colours, uv) skipped; faces as one
+    binary little-endian; x, y, z of any scalar type, other vertex properties (colours, uv) skipped; faces as one
     `list uchar|uint8|int ... vertex_indices` of 3 or more vertices, fan-triangulated; elements after the faces are not read.
-    Vertex normals are ignored: inserted meshes shade flat.  Anything else is a ValueError naming the file."""
+    Vertex normals are returned on request: `normals=True` gives (vertices, triangles, N) with N [Nv,3] float64 the file's nx, ny, nz
+    as written, or None when the vertex element has none (smooth inserted objects).  Anything else is a
+    ValueError naming the file."""
     def bad(why):
         return ValueError(f"{path}: {why}")
 
@@ -126,7 +128,7 @@ def read_ply_any(path: str) -> Tuple[np.ndarray, np.ndarray]:
                 break
         if fmt not in ("ascii", "binary_little_endian"):
             raise bad(f"format {fmt!r} is not supported (ascii and binary_little_endian are)")
-        V = T = None
+        V = T = Nn = None
         for name, count, props in elements:
             for pr in props:
                 if any(t not in _PLY_TYPES for t in pr[1:]):
@@ -140,6 +142,8 @@ def read_ply_any(path: str) -> Tuple[np.ndarray, np.ndarray]:
                     if rows.shape[1] < len(props):
                         raise bad("a vertex line is shorter than its properties")
                     V = np.stack([rows[:, names.index(c)] for c in "xyz"], -1)
+                    if all(c in names for c in ("nx", "ny", "nz")):
+                        Nn = np.stack([rows[:, names.index(c)] for c in ("nx", "ny", "nz")], -1)
                 else:
                     dt = np.dtype([(n, "<" + _PLY_TYPES[t]) for n, t in props])
                     buf = fh.read(count * dt.itemsize)
@@ -147,6 +151,8 @@ def read_ply_any(path: str) -> Tuple[np.ndarray, np.ndarray]:
                         raise bad("the vertex data ends early")
                     rec = np.frombuffer(buf, dtype=dt)
                     V = np.stack([rec[c].astype(np.float64) for c in "xyz"], -1)
+                    if all(c in names for c in ("nx", "ny", "nz")):
+                        Nn = np.stack([rec[c].astype(np.float64) for c in ("nx", "ny", "nz")], -1)
             elif name == "face":
                 if len(props) != 1 or len(props[0]) != 3:
                     raise bad("the face element must be one list property")
@@ -174,7 +180,27 @@ def read_ply_any(path: str) -> Tuple[np.ndarray, np.ndarray]:
         raise bad("needs a vertex and a face element")
     if T.size and (T.min() < 0 or T.max() >= V.shape[0]):
         raise bad("a face index is outside the vertex array")
-    return V, T.astype(np.int32)
+    return (V, T.astype(np.int32), Nn) if normals else (V, T.astype(np.int32))
+
+
+def angle_weighted_normals(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:
+    """Per vertex, the sum of the adjacent face normals (unit, oriented by the winding) weighted by the triangle's angle at that
+    vertex, normalised; 0 where the sum has zero length or no triangle uses the vertex (the path render then shades flat there).
+    What a smooth inserted object gets when its file carries no normals."""
+    V, T = np.asarray(vertices, np.float64), np.asarray(triangles, np.int64)
+    P = V[T]
+    fn = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    fl = np.linalg.norm(fn, axis=-1, keepdims=True)
+    fn = np.where(fl > 0, fn / np.maximum(fl, 1e-300), 0.0)
+    acc = np.zeros_like(V)
+    for k in range(3):
+        a, b = P[:, (k + 1) % 3] - P[:, k], P[:, (k + 2) % 3] - P[:, k]
+        la, lb = np.linalg.norm(a, axis=-1), np.linalg.norm(b, axis=-1)
+        ok = (la > 0) & (lb > 0)
+        cos = np.clip((a * b).sum(-1) / np.where(ok, la * lb, 1.0), -1.0, 1.0)
+        np.add.at(acc, T[:, k], np.where(ok, np.arccos(cos), 0.0)[:, None] * fn)
+    ln = np.linalg.norm(acc, axis=-1, keepdims=True)
+    return np.where(ln > 0, acc / np.maximum(ln, 1e-300), 0.0)
 
 
 def vertex_normals(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:

@@ -27,6 +27,7 @@ TRI_BYTES = 48
 MAX_BVH_DEPTH = 40
 MAX_OBJECTS = 8
 BSDF_DIELECTRIC, BSDF_DIFFUSE = 1, 2
+OBJECT_SMOOTH = 0x100          # MATPBR_PATH_OBJECT_SMOOTH, OR-ed into PathObject.kind
 
 
 class PathObject(ctypes.Structure):
@@ -53,6 +54,10 @@ SIGNATURES = {
     "matpbr_path_render_objects": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                    [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int]),
     "matpbr_path_object_sample_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 4),
+    "matpbr_path_render_objects_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
+                                           [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_long]),
+    "matpbr_path_object_normal_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
+    "matpbr_path_object_sample_shading_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
     "matpbr_path_render_trans": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                  [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, _P, _P]),
     "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
@@ -69,6 +74,8 @@ SIGNATURES = {
 }
 VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
+# added at version 3 (smooth inserted objects): a version-3 library built before them loads, and `symbol` names what it lacks
+LATE_SYMBOLS = ("matpbr_path_render_objects_normals", "matpbr_path_object_normal_host", "matpbr_path_object_sample_shading_host")
 
 
 class PathError(RuntimeError):
@@ -84,12 +91,22 @@ def load() -> ctypes.CDLL:
         _build.build_path_library()
         lib = ctypes.CDLL(_build.PATH_LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if name in LATE_SYMBOLS and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.matpbr_path_version() != VERSION:
             raise PathError(f"libmatpbr_path.so is version {lib.matpbr_path_version()}, this binding needs {VERSION}")
         _lib = lib
         return lib
+
+
+def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
+    """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
+    lib = load() if lib is None else lib
+    if not hasattr(lib, name):
+        raise PathError(f"libmatpbr_path.so has no {name}: it was built before smooth inserted objects; rebuild it (build.build_path_library)")
+    return getattr(lib, name)
 
 
 def check(code: int, what: str) -> None:
@@ -179,14 +196,33 @@ def object_bsdf(bsdf: dict) -> tuple:
     raise ValueError(f"object bsdf type must be 'dielectric' or 'diffuse', got {kind!r}")
 
 
-def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict]):
+def _corner_normals(k: int, ob: dict, Vo: np.ndarray, To: np.ndarray) -> np.ndarray:
+    """Object k's "normals" [Nv,3], normalised in fp64 and expanded to one record per triangle corner [Nt,3,3]; ValueError when bad."""
+    No = np.asarray(ob["normals"], dtype=np.float64)
+    if No.shape != Vo.shape:
+        raise ValueError(f"object {k}: normals must be [Nv,3] = {Vo.shape}, one per vertex, got {No.shape}")
+    if not np.isfinite(No).all():
+        raise ValueError(f"object {k}: normals must be finite")
+    ln = np.linalg.norm(No, axis=-1)
+    used = np.zeros(Vo.shape[0], bool)
+    used[To.reshape(-1)] = True
+    if (used & ~(ln > 0)).any():
+        raise ValueError(f"object {k}: the normal of vertex {int(np.nonzero(used & ~(ln > 0))[0][0])}, which a triangle uses, has zero length")
+    return (No / np.where(ln > 0, ln, 1.0)[:, None])[To]
+
+
+def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False):
     """The depth mesh with the inserted meshes appended -> (V [Nv,3] float64, T [Nt,3] int32, [PathObject]).  Object k's triangles
-    follow the scene's in the order given; its ids are its range of T."""
+    follow the scene's in the order given; its ids are its range of T.  An object may carry "normals" [Nv,3] (per vertex, outward, any
+    length): it is smooth ("Smooth inserted objects"), its kind carries OBJECT_SMOOTH, and with `normals=True`
+    a fourth value follows, the corner normals [Nt - scene's Nt, 3, 3] float32 of every inserted triangle (unit length, normalised in
+    fp64; zero for the objects without normals, which the kernel never reads), or None when no object is smooth."""
     V = [np.asarray(vertices, dtype=np.float64).reshape(-1, 3)]
     T = [np.asarray(triangles, dtype=np.int32).reshape(-1, 3)]
     if len(objects) > MAX_OBJECTS:
         raise ValueError(f"at most {MAX_OBJECTS} inserted objects, got {len(objects)}")
     table: List[PathObject] = []
+    corner: List[np.ndarray] = []
     nv, nt = V[0].shape[0], T[0].shape[0]
     for k, ob in enumerate(objects):
         kind, p = object_bsdf(ob.get("bsdf"))
@@ -198,11 +234,19 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
             raise ValueError(f"object {k}: vertices must be finite")
         if not np.issubdtype(To.dtype, np.integer) or To.min() < 0 or To.max() >= Vo.shape[0]:
             raise ValueError(f"object {k}: triangle indices must be integers in [0, {Vo.shape[0]})")
+        if ob.get("normals") is not None:
+            corner.append(_corner_normals(k, ob, Vo, To))
+            kind |= OBJECT_SMOOTH
+        else:
+            corner.append(np.zeros((To.shape[0], 3, 3)))
         V.append(Vo)
         T.append((To.astype(np.int64) + nv).astype(np.int32))
         table.append(PathObject(kind, nt, To.shape[0], (ctypes.c_float * 3)(*p)))
         nv, nt = nv + Vo.shape[0], nt + To.shape[0]
-    return np.concatenate(V), np.concatenate(T), table
+    if not normals:
+        return np.concatenate(V), np.concatenate(T), table
+    smooth = any(t.kind & OBJECT_SMOOTH for t in table)
+    return np.concatenate(V), np.concatenate(T), table, (np.ascontiguousarray(np.concatenate(corner), dtype=np.float32) if smooth else None)
 
 
 def object_sample_host(bsdf: dict, n: np.ndarray, wo: np.ndarray, u: np.ndarray):
@@ -220,6 +264,42 @@ def object_sample_host(bsdf: dict, n: np.ndarray, wo: np.ndarray, u: np.ndarray)
     pdf, flags = np.empty(N, np.float32), np.empty(N, np.int32)
     check(load().matpbr_path_object_sample_host(ctypes.cast(ctypes.byref(ob), _P), _ptr(nn), _ptr(WO), _ptr(U), N, _ptr(wi), _ptr(w), _ptr(pdf),
                                                 _ptr(flags)), "matpbr_path_object_sample_host")
+    return wi, w, pdf, flags
+
+
+def object_normal_host(tri: np.ndarray, nrm: np.ndarray, o: np.ndarray, d: np.ndarray):
+    """The kernel's shading normal of a smooth object on the CPU: triangle records tri [N,3,3] = (v0, e1, e2), corner normals nrm
+    [N,3,3], rays o, d [N,3] -> (u [N], v [N], ns [N,3]); ns after the first two fallbacks (not finite or zero, ns . ng <= 0)."""
+    TR = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1, 3, 3)
+    NR = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3, 3)
+    O = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
+    D = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    N = TR.shape[0]
+    if any(x.shape[0] != N for x in (NR, O, D)):
+        raise ValueError("tri, nrm, o and d must have the same rows")
+    u, v, ns = np.empty(N, np.float32), np.empty(N, np.float32), np.empty((N, 3), np.float32)
+    check(symbol("matpbr_path_object_normal_host")(_ptr(TR), _ptr(NR), _ptr(O), _ptr(D), N, _ptr(u), _ptr(v), _ptr(ns)),
+          "matpbr_path_object_normal_host")
+    return u, v, ns
+
+
+def object_sample_shading_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: np.ndarray, u: np.ndarray):
+    """`object_sample_host` at vertices with a face normal ng [N,3] (or [3]) and a shading normal ns [N,3] (or [3]), as the kernel
+    samples a smooth object: the third fallback, the sample about ns, the dielectric's redo about ng, weight 0 below ng ->
+    (wi [N,3], weight [N,3], pdf [N], flags [N])."""
+    kind, p = object_bsdf(bsdf)
+    ob = PathObject(kind, 0, 0, (ctypes.c_float * 3)(*p))
+    WO = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
+    U = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 3)
+    N = WO.shape[0]
+    if U.shape[0] != N:
+        raise ValueError(f"wo and u must have the same rows, got {N} and {U.shape[0]}")
+    NG = np.ascontiguousarray(np.broadcast_to(np.asarray(ng, dtype=np.float32).reshape(-1, 3), (N, 3)))
+    NS = np.ascontiguousarray(np.broadcast_to(np.asarray(ns, dtype=np.float32).reshape(-1, 3), (N, 3)))
+    wi, w = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
+    pdf, flags = np.empty(N, np.float32), np.empty(N, np.int32)
+    check(symbol("matpbr_path_object_sample_shading_host")(ctypes.cast(ctypes.byref(ob), _P), _ptr(NG), _ptr(NS), _ptr(WO), _ptr(U), N, _ptr(wi),
+                                                           _ptr(w), _ptr(pdf), _ptr(flags)), "matpbr_path_object_sample_shading_host")
     return wi, w, pdf, flags
 
 
@@ -288,7 +368,8 @@ class PathTracer:
     The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
     `objects`: meshes inserted into the scene ("Inserted objects"), in the same frame, outward winding, a list
     of {"vertices" [Nv,3], "triangles" [Nt,3], "bsdf": {"type": "dielectric", "int_ior": 1.49, "ext_ior": 1.000277} or
-    {"type": "diffuse", "reflectance": (r, g, b)}}.  A tracer with objects renders forward only."""
+    {"type": "diffuse", "reflectance": (r, g, b)}} and optionally "normals" [Nv,3] (per vertex, outward): with them the object shades
+    smooth, with the normals interpolated at each hit; without them flat.  A tracer with objects renders forward only."""
 
     def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
                  objects: Optional[Sequence[dict]] = None):
@@ -296,9 +377,16 @@ class PathTracer:
         self.device = torch.device(device)
         n_scene = int(np.asarray(triangles).reshape(-1, 3).shape[0])
         self.objects = None
+        self.obj_nrm: Optional[torch.Tensor] = None   # corner normals of the inserted triangles, when some object is smooth
+        self.n_scene_tris = n_scene
+        n_smooth = 0
         if objects:
-            vertices, triangles, table = merge_objects(vertices, triangles, objects)
+            vertices, triangles, table, corner = merge_objects(vertices, triangles, objects, normals=True)
             self.objects = (PathObject * len(table))(*table)
+            n_smooth = sum(1 for t in table if t.kind & OBJECT_SMOOTH)
+            if corner is not None:
+                symbol("matpbr_path_render_objects_normals")
+                self.obj_nrm = torch.from_numpy(corner).to(self.device)
             bvh = build_bvh(vertices, triangles, n_scene)
         else:
             bvh = build_bvh(vertices, triangles)
@@ -306,6 +394,7 @@ class PathTracer:
         self.stats["n_tris"] = int(np.asarray(triangles).reshape(-1, 3).shape[0])
         self.stats["n_objects"] = len(self.objects) if self.objects is not None else 0
         self.stats["n_object_tris"] = self.stats["n_tris"] - n_scene
+        self.stats["n_smooth_objects"] = n_smooth
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -368,8 +457,12 @@ class PathTracer:
             check(lib.matpbr_path_render_normals(*args, nrm.data_ptr()), "matpbr_path_render_normals")
         elif self.objects is None:
             check(lib.matpbr_path_render(*args), "matpbr_path_render")
-        else:
+        elif self.obj_nrm is None:
             check(lib.matpbr_path_render_objects(*args, ctypes.cast(self.objects, _P), len(self.objects)), "matpbr_path_render_objects")
+        else:
+            check(symbol("matpbr_path_render_objects_normals", lib)(*args, ctypes.cast(self.objects, _P), len(self.objects),
+                                                                    self.obj_nrm.data_ptr(), self.n_scene_tris),
+                  "matpbr_path_render_objects_normals")
         return out
 
     @torch.no_grad()

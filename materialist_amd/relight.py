@@ -253,11 +253,13 @@ def find_envmap_oi(save_name: str, env_path: Optional[str], input_path: Optional
 
 
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
-              spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda") -> str:
+              spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat") -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
-    The meshes are in the renderer's frame, read by `mesh.read_ply_any`, and shade flat.  `n_iter` renders with seeds seed + i are
+    The meshes are in the renderer's frame, read by `mesh.read_ply_any`.  `object_normals`: "flat" (default) shades them with their
+    face normals; "vertex" shades each smooth, with its file's vertex normals where it has them, else with
+    `mesh.angle_weighted_normals` ("Smooth inserted objects").  `n_iter` renders with seeds seed + i are
     averaged.  There is no denoiser here: the reference renders spp 32 x 10 and denoises each with OptiX, so
     the samples do the denoiser's work (default spp 64 x 10)."""
     from . import mesh as _mesh
@@ -270,11 +272,15 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
         raise FileNotFoundError(f"object insertion needs {plys[0]} (glass) or {plys[1]} (diffuse); neither exists")
     if n_iter < 1:
         raise ValueError(f"n_iter must be at least 1, got {n_iter}")
+    if object_normals not in ("flat", "vertex"):
+        raise ValueError(f"object_normals must be 'flat' or 'vertex', got {object_normals!r}")
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
     for p, b in have:
-        V, T = _mesh.read_ply_any(p)
+        V, T, Nn = _mesh.read_ply_any(p, normals=True)
         objects.append({"vertices": V, "triangles": T, "bsdf": b})
+        if object_normals == "vertex":
+            objects[-1]["normals"] = Nn if Nn is not None else _mesh.angle_weighted_normals(V, T)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
     pt = _path_tracer(scene_dir, save_name, mat, device, objects)
     env = load_image(env_path)

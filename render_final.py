@@ -31,6 +31,8 @@ def parse_args(argv=None):
     ap.add_argument("--shading_normals", choices=("face", "map"), default="face",
                     help="--integrator path: face = shade with the mesh's face normals (default); map = shade with best_results/normal.exr")
     ap.add_argument("--oi_iters", type=int, default=10, help="--mode oi: renders averaged (seeds seed, seed + 1, ...)")
+    ap.add_argument("--oi_normals", choices=["flat", "vertex"], default="flat",
+                    help="--mode oi: flat = face normals; vertex = each .ply shades smooth with its vertex normals (angle-weighted ones if it has none)")
     ap.add_argument("--oi_max_depth", type=int, default=16, help="--mode oi: Mitsuba's max_depth (a camera path through glass needs 5 to see light)")
     a = ap.parse_args(argv)
     if a.shading_normals == "map" and (a.integrator != "path" or a.mode == "oi"):
@@ -51,7 +53,8 @@ def main(argv=None):
                                             **it)
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
-        print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed))
+        print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
+                                                 object_normals=a.oi_normals))
     else:
         raise ValueError("Invalid mode")
 

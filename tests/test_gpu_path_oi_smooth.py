@@ -1,0 +1,311 @@
+"""Smooth inserted objects on the GPU (libmatpbr_path.so's `matpbr_path_render_objects_normals`, DESIGN.md section 1.4, "Smooth
+inserted objects"): every path of a table with smooth and flat objects against the fp64 restatement, a glass furnace with a smooth
+sphere, bits across launch splits and against the flat kernel, the refusals, `render_final.py --oi_normals vertex`, and the cost of
+one indoor2 frame smooth against flat."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import path_fp64 as pf  # noqa: E402
+import path_oi_fp64 as po  # noqa: E402
+import path_oi_smooth_fp64 as ps  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+FOV = pf.FOV
+
+
+@pytest.fixture(scope="module")
+def pt():
+    from materialist_amd import build, pathtrace
+
+    build.build_path_library()
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return pathtrace
+
+
+def _report(what, value):
+    print(f"[path oi smooth] {what}: {value}")
+    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"test_gpu_path_oi_smooth\t{what}\t{value}\n")
+
+
+@pytest.fixture(scope="module")
+def scene(pt):
+    """The groove at 24 x 20 with `path_oi_smooth_fp64.table_scene` in front of it: a smooth glass and a smooth diffuse icosphere of
+    80 triangles each and a flat diffuse cube in one table."""
+    from materialist_amd import mesh
+
+    H, W = 20, 24
+    rm = mesh.reference_mesh(pf.groove_scene(H, W), FOV)
+    rng = np.random.default_rng(11)
+    a, r, m = pf.groove_maps(H, W, rng)
+    env = pf.groove_env(rng)
+    objects = ps.table_scene()
+    V, T, table = ps.merged(rm["vertices"], rm["triangles"], objects)
+    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=objects)
+    assert tracer.stats["n_objects"] == 3 and tracer.stats["n_smooth_objects"] == 2 and tracer.stats["n_object_tris"] == 172
+    return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "H": H, "W": W, "objects": objects, "V": V, "T": T, "table": table, "tracer": tracer}
+
+
+def _bits(x):
+    return x.cpu().numpy().view(np.uint32)
+
+
+def _parity(got, ref):
+    """test_gpu_path.py's criterion: per-pixel error relative to max(|ref|, mean |ref|) -> (share within 1e-3, the errors)."""
+    err = (np.abs(got - ref) / np.maximum(np.abs(ref), np.abs(ref).mean())).max(-1)
+    return float((err <= 1e-3).mean()), err
+
+
+def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64):
+    """At least 0.99 of the pixels within 1e-3 (the rest: paths whose fp32 and fp64 hit decisions differ; on the CPU the restatement
+    over the library's fp32 traversal and over the fp64 brute force disagree in no pixel of these six renders,
+    test_path_oi_smooth_host.py)."""
+    s = scene
+    H, W = s["H"], s["W"]
+    tab = pt.env_tables(s["env"])
+    seen = {k: 0 for k in ("smooth_transmitted", "smooth_diffuse", "blocked_by_object", "redo", "fallback")}
+    for max_depth in (6, 16):
+        for seed in (0, 1, 2):
+            got = s["tracer"].render(s["a"], s["r"], s["m"], s["env"], spp=1, max_depth=max_depth, seed=seed).cpu().numpy().astype(np.float64)
+            assert np.isfinite(got).all()
+            ref, rec = ps.replay_oi(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], s["env"], tab, H, W, max_depth, seed, s["table"])
+            frac, err = _parity(got, ref)
+            _report(f"per-path parity with smooth objects, max_depth {max_depth} seed {seed}: share of pixels within 1e-3",
+                    f"{frac:.4f} ({int((err > 1e-3).sum())} flipped paths, max err {err.max():.3e})")
+            assert frac >= 0.99, (max_depth, seed, frac, np.argwhere(err > 1e-3)[:10])
+            for k in ("smooth_transmitted", "smooth_diffuse", "blocked_by_object"):
+                assert rec[k].any(), (k, max_depth, seed)     # the scene does what it is for, in every one of the renders
+            for k in seen:
+                seen[k] += int(rec[k].sum())
+    _report("pixels with a smooth transmitted vertex / a smooth diffuse vertex / a blocked emitter sample / a redo about ng / a fallback "
+            "(6 renders)", " / ".join(str(seen[k]) for k in seen))
+    assert seen["redo"] >= 1 and seen["fallback"] >= 1
+
+
+def _footprints(objects, H, W, n=9):
+    """test_gpu_path_oi.py's: per pixel, from an n x n grid of rays over its footprint and the objects' projected vertices: (every
+    ray hits an object, no ray hits and no vertex projects into the footprint)."""
+    f = (W / 2.0) / np.tan(np.radians(FOV) / 2.0)
+    g = np.linspace(-0.5, 0.5, n)
+    y, x = np.meshgrid((np.arange(H)[:, None] + g[None]).reshape(-1), (np.arange(W)[:, None] + g[None]).reshape(-1), indexing="ij")
+    d = np.stack([(x - (W - 1) / 2) / f, -(y - (H - 1) / 2) / f, -np.ones_like(x)], -1).reshape(-1, 3)
+    P = np.concatenate([np.asarray(ob["vertices"], np.float64)[np.asarray(ob["triangles"])] for ob in objects])
+    hit = np.isfinite(pf.brute(P, np.zeros_like(d), d)[0]).reshape(H, n, W, n)
+    vert = np.zeros((H, W), bool)
+    for ob in objects:
+        v = np.asarray(ob["vertices"], np.float64)
+        px, py = v[:, 0] / -v[:, 2] * f + (W - 1) / 2, -v[:, 1] / -v[:, 2] * f + (H - 1) / 2
+        for a, b in zip(px, py):
+            vert[max(int(np.floor(b - 0.5)), 0):int(np.ceil(b + 0.5)) + 1, max(int(np.floor(a - 0.5)), 0):int(np.ceil(a + 0.5)) + 1] = True
+    return hit.all(axis=(1, 3)), ~hit.any(axis=(1, 3)) & ~vert
+
+
+def _erode(mask):
+    m = np.pad(mask, 1, constant_values=False)
+    return np.logical_and.reduce([m[1 + di:m.shape[0] - 1 + di, 1 + dj:m.shape[1] - 1 + dj] for di in (-1, 0, 1) for dj in (-1, 0, 1)])
+
+
+def test_glass_furnace_with_a_smooth_sphere(pt):
+    """A smooth glass icosphere (320 triangles) under a constant envmap c: every path that escapes carries c, because a transmitted
+    event always crosses the surface (the redo about ng), so the eta^2 factors cancel along every path; a truncated path carries 0."""
+    H = W = 32
+    c = np.float32(0.75)
+    env = np.full((4, 8, 3), c, np.float32)
+    Vs = np.array([[50.0, 50.0, -1.0], [50.001, 50.0, -1.0], [50.0, 50.001, -1.0]])
+    Vb, Tb, Nb = ps.icosphere((0.01, -0.02, -1.2), 0.2, 2)
+    glass = [{"vertices": Vb, "triangles": Tb, "bsdf": po.GLASS, "normals": Nb}]
+    tracer = pt.PathTracer(Vs, np.array([[0, 1, 2]], np.int32), H, W, FOV, objects=glass)
+    assert tracer.stats["n_smooth_objects"] == 1
+    maps = (np.full((H, W, 3), 0.5, np.float32), np.full((H, W, 1), 0.5, np.float32), np.zeros((H, W, 1), np.float32))
+    img = tracer.render(*maps, env, spp=64, max_depth=16, seed=0).cpu().numpy()
+    inside, outside = _footprints(glass, H, W)
+    core = _erode(inside)
+    assert core.sum() > 50 and outside.sum() > 400
+    assert np.all(img[outside] == c)
+    assert np.all(img <= c * (1 + 1e-5)), img.max()
+    assert np.all(img[core] > 0)
+    _report("glass furnace, smooth sphere: mean over the sphere's inner pixels / c, max / c", f"{img[core].mean() / c:.4f}, {img.max() / c:.7f}")
+
+
+def _unwelded(ob):
+    """The object with every triangle on vertices of its own, and per-vertex normals equal to the face normals."""
+    V, T = np.asarray(ob["vertices"], np.float64), np.asarray(ob["triangles"], np.int64)
+    P = V[T]
+    fn = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    return {"vertices": P.reshape(-1, 3), "triangles": np.arange(3 * T.shape[0], dtype=np.int32).reshape(-1, 3), "bsdf": ob["bsdf"],
+            "normals": np.repeat(fn, 3, 0)}
+
+
+def test_bits(pt, scene):
+    s = scene
+    args = (s["a"], s["r"], s["m"], s["env"])
+    H, W, rm = s["H"], s["W"], s["rm"]
+    x8 = s["tracer"].render(*args, spp=64, max_depth=16, seed=7, spp_per_launch=8)
+    for split in (1, 3, 64):
+        assert np.array_equal(_bits(x8), _bits(s["tracer"].render(*args, spp=64, max_depth=16, seed=7, spp_per_launch=split))), split
+    d2, d6, d16 = (s["tracer"].render(*args, spp=8, max_depth=k, seed=3).cpu().numpy() for k in (2, 6, 16))
+    assert np.all(d16 >= d6) and np.all(d6 >= d2), (np.argwhere(d16 < d6)[:5], np.argwhere(d6 < d2)[:5])
+    assert (d6 - d2).mean() > 1e-3 * d6.mean()
+    # objects without normals: the new entry point launches render_objects' kernel and gives its bits, with and without an array
+    bare = [{k: v for k, v in ob.items() if k != "normals"} for ob in s["objects"]]
+    flat = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=bare)
+    assert flat.stats["n_smooth_objects"] == 0 and flat.obj_nrm is None
+    ref = flat.render(*args, spp=8, max_depth=16, seed=5)
+    a, r, m, env, row, col, pdf = flat._inputs(*args, None)
+    dummy = torch.zeros(flat.stats["n_object_tris"], 3, 3, device=flat.device)
+    for nrm_ptr in (None, dummy.data_ptr()):
+        out = torch.empty(H, W, 3, device=flat.device)
+        code = pt.symbol("matpbr_path_render_objects_normals")(
+            flat.nodes.data_ptr(), flat.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, FOV, env.data_ptr(), row.data_ptr(),
+            col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]), 8, 16, 5, 8, out.data_ptr(), None,
+            torch.cuda.current_stream().cuda_stream, ctypes.cast(flat.objects, ctypes.c_void_p), len(flat.objects), nrm_ptr, flat.n_scene_tris)
+        assert code == 0
+        assert np.array_equal(_bits(out), _bits(ref))
+    assert not np.array_equal(_bits(s["tracer"].render(*args, spp=8, max_depth=16, seed=5)), _bits(ref))   # the normals do something
+    # normals equal to the face normals: the smooth kernel walks the flat render's paths (the host's normalisation may move an ulp)
+    faces = [_unwelded(ob) for ob in s["objects"]]
+    as_flat = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=[{k: v for k, v in ob.items() if k != "normals"} for ob in faces])
+    as_smooth = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=faces)
+    assert as_smooth.stats["n_smooth_objects"] == 3 and as_flat.stats["n_smooth_objects"] == 0
+    for seed in (0, 1):
+        g = as_smooth.render(*args, spp=1, max_depth=16, seed=seed).cpu().numpy().astype(np.float64)
+        f = as_flat.render(*args, spp=1, max_depth=16, seed=seed).cpu().numpy().astype(np.float64)
+        frac, err = _parity(g, f)
+        _report(f"face normals as vertex normals against the flat render, seed {seed}: share of pixels within 1e-3", f"{frac:.4f} (max err {err.max():.3e})")
+        assert frac >= 0.99
+
+
+def test_refusals(pt, scene):
+    s = scene
+    with pytest.raises(ValueError, match="objects"):
+        s["tracer"].render_bwd(s["a"], s["r"], s["m"], s["env"], np.ones((s["H"], s["W"], 3), np.float32), spp=1)
+    with pytest.raises(ValueError, match="objects"):
+        s["tracer"].render_trans(s["a"], s["r"], s["m"], s["env"], np.ones((s["H"], s["W"]), bool), np.ones((s["H"], s["W"], 3), np.float32), spp=1)
+    with pytest.raises(ValueError, match="objects"):
+        s["tracer"].render(s["a"], s["r"], s["m"], s["env"], spp=1, normal=np.tile(np.float32([0, 0, 1]), (s["H"], s["W"], 1)))
+
+
+def _synthetic_output(tmp, name="case", H=32, W=32):
+    """tests/test_gpu_path_oi.py's synthetic output directory, at 32 x 32."""
+    from materialist_amd import mesh
+    from materialist_amd.imageio_exr import write_exr
+    from materialist_amd.imageio_hdr import write_hdr
+
+    rng = np.random.default_rng(2)
+    scene = os.path.join(tmp, name)
+    br = os.path.join(scene, "best_results")
+    os.makedirs(br)
+    a, r, m = pf.groove_maps(H, W, rng)
+    write_exr(os.path.join(br, "albedo.exr"), a)
+    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
+    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
+    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
+    write_hdr(os.path.join(br, "envmap.hdr"), pf.groove_env(rng))
+    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)
+    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
+    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
+    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
+    return scene
+
+
+def test_render_final_cli_oi_normals(pt, tmp_path):
+    from materialist_amd import mesh, relight
+    from materialist_amd.imageio_exr import read_exr
+
+    tmp = str(tmp_path)
+    scene_dir = _synthetic_output(tmp)
+    Vg, Tg, Ng = ps.icosphere((-0.05, 0.03, -0.9), 0.09, 1)
+    Vg, Ng = Vg.astype(np.float32).astype(np.float64), (1.7 * Ng).astype(np.float32).astype(np.float64)   # the file's normals: any length
+    Vd, Td = po.cube((0.10, -0.04, -1.0), 0.14, (-0.3, 0.7, 0.2))
+    with open(os.path.join(scene_dir, "oi.ply"), "w") as f:                    # somebody else's file: ASCII, with normals
+        f.write(f"ply\nformat ascii 1.0\nelement vertex {Vg.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+                f"property float nx\nproperty float ny\nproperty float nz\nelement face {Tg.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n" +
+                "".join(" ".join(repr(x) for x in v + n) + "\n" for v, n in zip(Vg.tolist(), Ng.tolist())) +
+                "".join(f"3 {t[0]} {t[1]} {t[2]}\n" for t in Tg.tolist()))
+    mesh.write_ply(os.path.join(scene_dir, "oi2.ply"), Vd, Td)                   # no normals: angle-weighted ones under `vertex`
+    cli = [sys.executable, os.path.join(ROOT, "render_final.py"), "--save_name", "case", "--input_path", tmp, "--save_path", tmp,
+           "--mode", "oi", "--spp", "4", "--oi_iters", "2", "--oi_max_depth", "8"]
+    mat = relight.load_estimated_brdf(os.path.join(scene_dir, "best_results"))
+    env = relight.load_image(os.path.join(scene_dir, "best_results", "envmap.hdr"))
+    exr = os.path.join(tmp, "case", "mi_oi_case_envmap.exr")
+    images = {}
+    for flags, normals in ((["--oi_normals", "vertex"], (Ng, mesh.angle_weighted_normals(Vd, Td))), ([], (None, None))):
+        res = subprocess.run(cli + flags, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout + res.stderr
+        img = read_exr(exr)
+        objects = [{"vertices": Vg, "triangles": Tg, "bsdf": po.GLASS}, {"vertices": Vd, "triangles": Td, "bsdf": po.DIFFUSE_08}]
+        for ob, n in zip(objects, normals):
+            if n is not None:
+                ob["normals"] = n
+        tracer = relight._path_tracer(scene_dir, "case", mat, "cuda", objects)
+        assert tracer.stats["n_smooth_objects"] == (2 if flags else 0)
+        acc = torch.zeros_like(mat["albedo"])
+        for seed in (0, 1):                                                    # two renders averaged as render_oi averages them
+            acc += tracer.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp=4, max_depth=8, seed=seed)
+        acc /= 2
+        assert np.array_equal(acc.cpu().numpy().view(np.uint32), np.ascontiguousarray(img[..., :3], dtype=np.float32).view(np.uint32)), flags
+        images[bool(flags)] = acc.cpu().numpy()
+    assert not np.array_equal(images[True], images[False])
+
+
+def test_indoor2_frame_smooth_against_flat(pt, golden_dir):
+    """test_gpu_path_oi.py's frame (512 x 512 indoor2, a glass sphere of 1280 triangles and a diffuse cube, spp 32, max_depth 16),
+    flat and with the sphere smooth, in one process: times, rates and the ratio go to the report; the bound is that test's "finishes"."""
+    from materialist_amd import mesh
+
+    dev = torch.device("cuda:0")
+    z = np.load(os.path.join(golden_dir, "indoor2.npz"))
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+    a = t(z["ref_albedo_u8"].astype(np.float32) / 255.0)
+    r = t(z["ref_roughness_u8"].astype(np.float32)[..., None] / 255.0).clamp(0.07, 1.0)
+    m = t(z["ref_metallic_u8"].astype(np.float32)[..., None] / 255.0)
+    env = z["ref_envmap_f32"]
+    depth = z["depth_pred_f32"]
+    depth = 2 * depth.max() - depth
+    H, W = depth.shape
+    rm = mesh.reference_mesh(depth, FOV)
+    z0 = 0.6 * float(depth[depth > 0].min())
+    Vs, Ts, Ns = ps.icosphere((-0.10 * z0, 0.0, -z0), 0.09 * z0, 3)
+    Vc, Tc = po.cube((0.13 * z0, -0.05 * z0, -z0), 0.13 * z0, (0.3, 0.6, 0.2))
+    assert Ts.shape[0] == 1280
+    cube = {"vertices": Vc, "triangles": Tc, "bsdf": po.DIFFUSE_08}
+    result = {}
+    for name, sphere in (("flat", {"vertices": Vs, "triangles": Ts, "bsdf": po.GLASS}),
+                         ("smooth", {"vertices": Vs, "triangles": Ts, "bsdf": po.GLASS, "normals": Ns})):
+        tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=[sphere, cube])
+        assert tracer.stats["n_object_tris"] == 1292 and tracer.stats["n_smooth_objects"] == (name == "smooth")
+        tables = tracer.tables(env)
+        img = tracer.render(a, r, m, env, spp=32, max_depth=16, seed=1, tables=tables)      # warm-up
+        assert bool(torch.isfinite(img).all())
+        best = None
+        for _ in range(2):
+            rays = torch.zeros(H, W, dtype=torch.int32, device=dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            tracer.render(a, r, m, env, spp=32, max_depth=16, seed=1, rays=rays, tables=tables)
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1)
+            best = ms if best is None else min(best, ms)
+        n_rays = float(rays.to(torch.float64).sum())
+        result[name] = (best, n_rays)
+        _report(f"512x512 spp 32 max_depth 16 frame, glass sphere (1280 triangles) {name} and a diffuse cube: ms (best of 2), Mrays, Mrays/s",
+                f"{best:.1f}, {n_rays / 1e6:.1f}, {n_rays / 1e3 / best:.0f}")
+        assert best < 5000.0
+    _report("smooth / flat time ratio", f"{result['smooth'][0] / result['flat'][0]:.3f}")
