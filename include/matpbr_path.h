@@ -226,6 +226,55 @@ int matpbr_path_render_bwd_normals(const void* nodes, const void* tris, const fl
                                    float* d_m, float* d_env, void* workspace, size_t workspace_bytes, uint32_t* rays, void* stream,
                                    const float* nrm, float* d_n);
 
+/* ---- Denoiser ("Denoiser"): first-hit features and a variance-guided edge-avoiding a-trous filter ----------
+ * Forward only, deterministic (no atomics), opt-in.  All images fp32, contiguous, HWC.
+ *   A, B [H,W,3]   two renders of the same scene with independent seeds and the same sample count, finite
+ *   geom [H,W,8]   two float4 per pixel, (px, py, pz, rho) and (nx, ny, nz, id), of the camera ray through the pixel centre: p the
+ *                  first hit, rho = |p| 2 tan(fov_x / 2) / W the pixel's footprint there, n the unit normal matpbr_path_render* shades
+ *                  that camera vertex with, id (a float) -1 = no hit (p = n = 0, rho = 0), 0 = the depth mesh, 1 + k = object k
+ *   alb [H,W,3]    the albedo guide (the caller composes it)
+ *   cv [H,W,4]     (colour, variance of the colour's luminance): what the levels pass on
+ * prepare: c0 = (A + B) / 2; v0 = the 3 x 3 binomial average [1 2 1] x [1 2 1] of (lum(A) - lum(B))^2 / 4 over the taps inside the image
+ * with the pixel's id, normalised by the weights used; lum = 0.2126 R + 0.7152 G + 0.0722 B.
+ * level l: stride s = 2^l, taps q = p + s (i, j), i, j in -2..2, those outside the image skipped, h = (1/16, 1/4, 3/8, 1/4, 1/16); the
+ * centre weighs 9/64, every other tap w = h_i h_j [id_q == id_p] w_n w_x w_a w_c,
+ *   w_n = max(0, n_p . n_q)^sigma_n                                                        (1 where id_p == -1)
+ *   w_x = exp(-|n_p . (x_q - x_p)| / (sigma_x rho_p s sqrt(i^2 + j^2) + 1e-30))             (1 where id_p == -1)
+ *   w_a = exp(-|alb_p - alb_q|^2 / sigma_a^2)
+ *   w_c = exp(-|lum(c_p) - lum(c_q)| / (sigma_c sqrt(max(v_p, 0)) + 1e-3 lum(c_p) + 1e-30))
+ * and c' = sum w c_q / sum w, v' = sum w^2 v_q / (sum w)^2.  The output is the colour after `levels` levels. */
+typedef struct MatpbrPathDenoise {
+    int32_t levels;                              /* 1..8 (5) */
+    float sigma_n, sigma_x, sigma_a, sigma_c;    /* finite and > 0 (32, 1, 0.1, 4) */
+} MatpbrPathDenoise;
+
+/* geom of an H x W camera (matpbr_path_render's) over a BVH: one lane per pixel traces one closest-hit ray through the pixel centre.
+ * objects[n_objects] (HOST, copied before the call returns), obj_nrm (DEVICE, nullable unless an object is smooth) and n_scene_tri as
+ * matpbr_path_render_objects_normals takes them; with n_objects == 0 they may be null / 0.  nrm_map (DEVICE, nullable): the
+ * shading-normal map of matpbr_path_render_normals, read at the texel the hit point projects to.  geom: DEVICE, 16-byte aligned. */
+int matpbr_path_features(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                         const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom, void* stream);
+/* matpbr_path_features on the CPU with the routine the kernel runs (every pointer HOST). */
+int matpbr_path_features_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                              const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom);
+
+/* The steps on their own (DEVICE pointers, 16-byte aligned cv and geom; `prm` HOST, copied before the call returns).  `level` in
+ * 0..7; cv_out must not be cv_in.  Invalid argument: a null pointer, `levels` outside 1..8, a sigma that is not finite and > 0. */
+int matpbr_path_denoise_prepare(const float* A, const float* B, const float* geom, int H, int W, float* cv0, void* stream);
+int matpbr_path_denoise_level(const float* cv_in, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm, int level,
+                              float* cv_out, void* stream);
+/* The same steps on the CPU with the per-pixel routines the kernels run (every pointer HOST). */
+int matpbr_path_denoise_prepare_host(const float* A, const float* B, const float* geom, int H, int W, float* cv0);
+int matpbr_path_denoise_level_host(const float* cv_in, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm, int level,
+                                   float* cv_out);
+
+/* Workspace of matpbr_path_denoise: two [H,W,4] buffers, in bytes (0 for a non-positive size). */
+size_t matpbr_path_denoise_workspace_bytes(int H, int W);
+/* The chain: prepare, then `levels` levels ping-ponging in `workspace` (DEVICE, 16-byte aligned, used by the enqueued work until it has
+ * run); the last level writes its colour to out[H,W,3].  Equal to the separate calls bit for bit. */
+int matpbr_path_denoise(const float* A, const float* B, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1674,3 +1674,434 @@ int matpbr_path_render_bwd_normals(const void* nodes, const void* tris, const fl
 }
 
 }  // extern "C"
+
+// =================================================================================================================================
+// Denoiser ("Denoiser"): first-hit features and a variance-guided edge-avoiding a-trous filter
+// =================================================================================================================================
+// The spatial part of SVGF (Schied et al. 2017) over the a-trous wavelet of Dammertz et al. 2010, the variance from two half
+// buffers (Rousselle et al. 2012), the guides noise-free features of the camera ray through the pixel centre.  Forward only, no
+// atomics: the bits are the same from run to run.  The per-pixel bodies are __host__ __device__: the *_host entry points run what
+// the kernels run (the device takes its exponentials and reciprocals from the hardware's approximations, the CPU from libm).
+namespace {
+
+constexpr int kDnTileX = 32, kDnTileY = 8;   // the filter's workgroup: 256 lanes, a wave = two rows of 32 pixels (512 B of cv each)
+constexpr int kDnMaxLevels = 8;
+
+__host__ __device__ inline float dn_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }   // matpbr_path_env_tables' weights
+__host__ __device__ inline float dn_exp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __expf(x);
+#else
+    return expf(x);
+#endif
+}
+__host__ __device__ inline float dn_rcp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(x);
+#else
+    return 1.0f / x;
+#endif
+}
+// max(0, c)^sigma as exp2(sigma log2 c), 0 where c <= 0 (or is not a number)
+__host__ __device__ inline float dn_pow(float c, float sigma) {
+    if (!(c > 0.0f)) return 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_exp2f(sigma * __log2f(c));
+#else
+    return exp2f(sigma * log2f(c));
+#endif
+}
+
+// index of the object whose range holds triangle `id`, -1: the depth mesh (object_of's lookup, returning the index the id feature
+// needs; __host__ __device__ for the CPU entry point)
+__host__ __device__ inline int object_index(const ObjTable& ot, int id) {
+    int idx = -1;
+    if (id < ot.min_id) return idx;
+    for (int k = 0; k < MATPBR_PATH_MAX_OBJECTS; ++k) {
+        const MatpbrPathObject& ob = ot.o[k];
+        if (k < ot.n && id >= ob.first_tri && id - ob.first_tri < ob.n_tri) idx = k;
+    }
+    return idx;
+}
+
+// ---- the feature ray's traversal ---------------------------------------------------------------------------------------------------
+// The depth mesh's vertices lie on the rays through the pixel centres ("Camera"), so a feature ray meets the
+// mesh in a vertex, where rounding decides which of the triangles around it wins.  `trace` rounds differently on the device (fused
+// multiply-adds) and on the CPU (none), and the two would name different triangles there.  The feature ray therefore walks the BVH
+// with `trace`'s closest-hit statements restated under `fp contract(off)`: every product and sum is rounded on its own, divisions
+// and square roots are correctly rounded on both sides, and the device takes the decisions the CPU takes, which are `trace`'s own
+// on the CPU (matpbr_path_trace_host).  The render kernels keep `trace`.
+__host__ __device__ inline float dot3s(const float a[3], const float b[3]) {
+#pragma clang fp contract(off)
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+__host__ __device__ inline void cross3s(const float a[3], const float b[3], float c[3]) {
+#pragma clang fp contract(off)
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+__host__ __device__ inline bool box_hit_s(float lx, float ly, float lz, float hx, float hy, float hz, const float inv[3], const float oi[3],
+                                          float tmin, float tmax, float& tn) {
+#pragma clang fp contract(off)
+    const float ax = lx * inv[0] - oi[0], bx = hx * inv[0] - oi[0];
+    const float ay = ly * inv[1] - oi[1], by = hy * inv[1] - oi[1];
+    const float az = lz * inv[2] - oi[2], bz = hz * inv[2] - oi[2];
+    const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tmin));
+    const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tmax)) * 1.0000004f;
+    tn = t0;
+    return t0 <= t1;
+}
+__host__ __device__ inline void tri_test_s(const float4* tris, int k, const float o[3], const float d[3], float tmin, float& t, int& hit) {
+#pragma clang fp contract(off)
+    const float4 A = tris[3 * k], B = tris[3 * k + 1], C = tris[3 * k + 2];
+    const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+    float pv[3];
+    cross3s(d, e2, pv);
+    const float det = dot3s(e1, pv);
+    if (det == 0.0f) return;
+    const float idet = 1.0f / det;
+    const float tv[3] = {o[0] - A.x, o[1] - A.y, o[2] - A.z};
+    const float u = dot3s(tv, pv) * idet;
+    if (!(u >= 0.0f && u <= 1.0f)) return;
+    float qv[3];
+    cross3s(tv, e1, qv);
+    const float v = dot3s(d, qv) * idet;
+    if (!(v >= 0.0f && u + v <= 1.0f)) return;
+    const float tt = dot3s(e2, qv) * idet;
+    if (tt > tmin && tt < t) { t = tt; hit = k; }
+}
+template <class Stack>
+__host__ __device__ inline int trace_strict(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float o[3], const float d[3],
+                                            float tmin, float& t, Stack& stk) {
+#pragma clang fp contract(off)
+    float inv[3], oi[3];
+    for (int c = 0; c < 3; ++c) {
+        const float dc = fabsf(d[c]) < 1e-30f ? copysignf(1e-30f, d[c]) : d[c];
+        inv[c] = 1.0f / dc;
+        oi[c] = o[c] * inv[c];
+    }
+    int hit = -1, node = 0, sp = 0;
+    while (true) {
+        const float4* np = nodes + 4 * node;
+        const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3f = np[3];
+        const int4 q3 = *reinterpret_cast<const int4*>(&q3f);
+        float tn0, tn1;
+        bool h0 = box_hit_s(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, inv, oi, tmin, t, tn0);
+        bool h1 = box_hit_s(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, inv, oi, tmin, t, tn1);
+        if (h0 && q3.z >= 0) {
+            for (int k = q3.x, e = q3.x + q3.z; k < e; ++k) tri_test_s(tris, k, o, d, tmin, t, hit);
+            h0 = false;
+        }
+        if (h1 && q3.w >= 0) {
+            for (int k = q3.y, e = q3.y + q3.w; k < e; ++k) tri_test_s(tris, k, o, d, tmin, t, hit);
+            h1 = false;
+        }
+        if (h0 && h1) {
+            const bool first0 = tn0 <= tn1;
+            node = first0 ? q3.x : q3.y;
+            if (sp < kStack) stk[sp++] = first0 ? q3.y : q3.x;
+        } else if (h0) {
+            node = q3.x;
+        } else if (h1) {
+            node = q3.y;
+        } else {
+            if (sp == 0) break;
+            node = stk[--sp];
+        }
+    }
+    return hit;
+}
+
+struct FeatArgs {
+    const float4* nodes;
+    const float4* tris;
+    const float* obj_nrm;   // nullable: corner normals of the inserted triangles (smooth objects)
+    const float* nrm_map;   // nullable: the shading-normal map of the depth mesh
+    float4* geom;           // [H,W,2]
+    int H, W;
+    int32_t n_scene_tri;
+    float f_pix, cx, cy, f_ndc, aspect;
+    float rho_scale;        // 2 tan(fov_x / 2) / W: the footprint of a pixel at distance 1
+};
+
+// The features of the camera ray through the centre of pixel (i, j): g0 = (p, rho), g1 = (n, id).  n is the normal the forward
+// kernel shades that camera vertex with: the depth mesh's camera-side face normal or its map's texel, an object's face normal or,
+// where it is smooth, smooth_normal + smooth_side.
+template <class Stack>
+__host__ __device__ inline void features_pixel(const FeatArgs& q, const ObjTable& ot, int i, int j, Stack& stk, float4& g0, float4& g1) {
+    const float o[3] = {0.0f, 0.0f, 0.0f};
+    float d[3] = {((float)j - q.cx) / q.f_pix, -((float)i - q.cy) / q.f_pix, -1.0f};
+    {
+        const float il = 1.0f / sqrtf(dot3s(d, d));   // the same bits on the device and on the CPU: see trace_strict
+        for (int c = 0; c < 3; ++c) d[c] *= il;
+    }
+    float t = FLT_MAX;
+    const int k = trace_strict(q.nodes, q.tris, o, d, 0.0f, t, stk);
+    if (k < 0) {
+        g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        g1 = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        return;
+    }
+    const float4 A = q.tris[3 * k], B = q.tris[3 * k + 1], C = q.tris[3 * k + 2];
+    const float v0[3] = {A.x, A.y, A.z}, e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+    float n[3];
+    cross3(e1, e2, n);
+    {
+        const float il = 1.0f / sqrtf(dot3h(n, n));
+        for (int c = 0; c < 3; ++c) n[c] *= il;
+    }
+    int32_t id;
+    __builtin_memcpy(&id, &A.w, 4);
+    // the hit point on the winning triangle's plane, (n . v0) / (n . d) along the ray from the origin: without the cancellation of
+    // Moller-Trumbore's t, which the traversal only needs for ordering (n . d != 0: the triangle test refuses det == 0)
+    t = dot3h(n, v0) / dot3h(n, d);
+    const float p[3] = {t * d[0], t * d[1], t * d[2]};
+    const int obj = object_index(ot, id);
+    if (obj < 0) {
+        if (q.nrm_map) {
+            const long tp = screen_texel(p, q.f_ndc, q.aspect, q.H, q.W);
+            for (int c = 0; c < 3; ++c) n[c] = q.nrm_map[3 * tp + c];
+        }
+    } else if (ot.o[obj].kind & MATPBR_PATH_OBJECT_SMOOTH) {
+        const float* cp = q.obj_nrm + 9 * (long)(id - q.n_scene_tri);
+        const float wo[3] = {-d[0], -d[1], -d[2]};
+        float cn[9], bu, bv, ns[3];
+        for (int c = 0; c < 9; ++c) cn[c] = cp[c];
+        tri_uv(v0, e1, e2, o, d, bu, bv);
+        smooth_normal(cn, bu, bv, n, ns);
+        smooth_side(n, wo, ns);
+        for (int c = 0; c < 3; ++c) n[c] = ns[c];
+    }
+    g0 = make_float4(p[0], p[1], p[2], sqrtf(dot3h(p, p)) * q.rho_scale);
+    g1 = make_float4(n[0], n[1], n[2], (float)(obj + 1));
+}
+
+__global__ __launch_bounds__(kBlock) void features_kernel(const FeatArgs q, const ObjTable ot) {
+    __shared__ int s_stack[kStack * kBlock];
+    const int tid = threadIdx.y * kTileX + threadIdx.x;
+    const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
+    if (i >= q.H || j >= q.W) return;   // no barriers below: each lane's stack column is its own
+    LdsStack stk{s_stack + tid};
+    float4 g0, g1;
+    features_pixel(q, ot, i, j, stk, g0, g1);
+    float4* gp = q.geom + 2 * ((long)i * q.W + j);
+    gp[0] = g0;
+    gp[1] = g1;
+}
+
+// prepare: cv0 = ((A + B) / 2, v0), v0 the 3 x 3 binomial average of (lum(A) - lum(B))^2 / 4 over the taps inside the image that
+// carry the pixel's id, normalised by the weights used
+__host__ __device__ inline float4 dn_prepare_pixel(const float* __restrict__ A, const float* __restrict__ B, const float4* __restrict__ geom, int H,
+                                                   int W, int i, int j) {
+    const long p = (long)i * W + j;
+    const float idp = geom[2 * p + 1].w;
+    float sv = 0.0f, sw = 0.0f;
+    for (int di = -1; di <= 1; ++di) {
+        for (int dj = -1; dj <= 1; ++dj) {
+            const int qi = i + di, qj = j + dj;
+            const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
+            const long q = in ? (long)qi * W + qj : p;   // a tap outside reads the centre and weighs nothing
+            const float dl = dn_lum(A[3 * q], A[3 * q + 1], A[3 * q + 2]) - dn_lum(B[3 * q], B[3 * q + 1], B[3 * q + 2]);
+            const float w = in && geom[2 * q + 1].w == idp ? (float)((2 - (di < 0 ? -di : di)) * (2 - (dj < 0 ? -dj : dj))) : 0.0f;
+            sv += w * (dl * dl * 0.25f);
+            sw += w;
+        }
+    }
+    return make_float4(0.5f * (A[3 * p] + B[3 * p]), 0.5f * (A[3 * p + 1] + B[3 * p + 1]), 0.5f * (A[3 * p + 2] + B[3 * p + 2]), sv / sw);
+}
+
+// one a-trous level at stride s: the 5 x 5 taps p + s (di, dj), the centre with weight 9/64, every other tap with
+// h h [id_q == id_p] w_n w_x w_a w_c.  The centre's guides stay in registers; a tap outside the image reads
+// the centre's records and weighs nothing (no branch).  -> (sum w c / sum w, sum w^2 v / (sum w)^2)
+__host__ __device__ inline float4 dn_level_pixel(const float4* __restrict__ cv, const float4* __restrict__ geom, const float* __restrict__ alb, int H,
+                                                 int W, int i, int j, int s, const MatpbrPathDenoise& prm) {
+    const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    const long p = (long)i * W + j;
+    const float4 cp = cv[p], xp = geom[2 * p], np_ = geom[2 * p + 1];
+    const float ap[3] = {alb[3 * p], alb[3 * p + 1], alb[3 * p + 2]};
+    const float lp = dn_lum(cp.x, cp.y, cp.z);
+    const bool geo = np_.w != -1.0f;   // a pixel that hit nothing has no normal and no position to compare
+    const float inv_c = 1.0f / (prm.sigma_c * sqrtf(fmaxf(cp.w, 0.0f)) + 1e-3f * lp + 1e-30f);
+    const float inv_a = 1.0f / (prm.sigma_a * prm.sigma_a);
+    const float xs = prm.sigma_x * xp.w * (float)s;
+    const float w0 = h[2] * h[2];
+    float sw = w0, sc[3] = {w0 * cp.x, w0 * cp.y, w0 * cp.z}, sv = (w0 * w0) * cp.w;
+#pragma unroll
+    for (int di = -2; di <= 2; ++di) {
+#pragma unroll
+        for (int dj = -2; dj <= 2; ++dj) {
+            if (di == 0 && dj == 0) continue;
+            const int qi = i + s * di, qj = j + s * dj;
+            const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
+            const long q = in ? (long)qi * W + qj : p;
+            const float4 cq = cv[q], xq = geom[2 * q], nq = geom[2 * q + 1];
+            const float da[3] = {ap[0] - alb[3 * q], ap[1] - alb[3 * q + 1], ap[2] - alb[3 * q + 2]};
+            float e = (da[0] * da[0] + da[1] * da[1] + da[2] * da[2]) * inv_a + fabsf(lp - dn_lum(cq.x, cq.y, cq.z)) * inv_c;
+            float wn = 1.0f;
+            if (geo) {
+                wn = dn_pow(np_.x * nq.x + np_.y * nq.y + np_.z * nq.z, prm.sigma_n);
+                const float dist = fabsf(np_.x * (xq.x - xp.x) + np_.y * (xq.y - xp.y) + np_.z * (xq.z - xp.z));
+                e += dist * dn_rcp(xs * sqrtf((float)(di * di + dj * dj)) + 1e-30f);
+            }
+            const float w = in && nq.w == np_.w ? (h[di + 2] * h[dj + 2]) * wn * dn_exp(-e) : 0.0f;
+            sw += w;
+            sc[0] += w * cq.x; sc[1] += w * cq.y; sc[2] += w * cq.z;
+            sv += (w * w) * cq.w;
+        }
+    }
+    const float iw = 1.0f / sw;
+    return make_float4(sc[0] * iw, sc[1] * iw, sc[2] * iw, sv * (iw * iw));
+}
+
+__global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_prepare_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                                             const float4* __restrict__ geom, int H, int W, float4* __restrict__ cv0) {
+    const int j = blockIdx.x * kDnTileX + threadIdx.x, i = blockIdx.y * kDnTileY + threadIdx.y;
+    if (i >= H || j >= W) return;
+    cv0[(long)i * W + j] = dn_prepare_pixel(A, B, geom, H, W, i, j);
+}
+
+// `rgb`: 0 writes (c, v) to cv_out[H,W,4]; 1 writes c to rgb_out[H,W,3] (the last level of the chain).  One kernel for both, so the
+// chain's last level runs the instructions the separate call runs.
+__global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_level_kernel(const float4* __restrict__ cv, const float4* __restrict__ geom,
+                                                                           const float* __restrict__ alb, int H, int W, int s,
+                                                                           const MatpbrPathDenoise prm, float4* __restrict__ cv_out,
+                                                                           float* __restrict__ rgb_out, int rgb) {
+    const int j = blockIdx.x * kDnTileX + threadIdx.x, i = blockIdx.y * kDnTileY + threadIdx.y;
+    if (i >= H || j >= W) return;
+    const float4 r = dn_level_pixel(cv, geom, alb, H, W, i, j, s, prm);
+    const long p = (long)i * W + j;
+    if (rgb) {
+        rgb_out[3 * p] = r.x; rgb_out[3 * p + 1] = r.y; rgb_out[3 * p + 2] = r.z;
+    } else {
+        cv_out[p] = r;
+    }
+}
+
+bool denoise_params_valid(const MatpbrPathDenoise* prm) {
+    if (!prm || prm->levels < 1 || prm->levels > kDnMaxLevels) return false;
+    for (float s : {prm->sigma_n, prm->sigma_x, prm->sigma_a, prm->sigma_c})
+        if (!(s > 0.0f && std::isfinite(s))) return false;
+    return true;
+}
+bool denoise_size_valid(int H, int W) { return H > 0 && W > 0 && (long)H * W <= INT32_MAX / 8; }
+dim3 denoise_grid(int H, int W) { return dim3((unsigned)((W + kDnTileX - 1) / kDnTileX), (unsigned)((H + kDnTileY - 1) / kDnTileY)); }
+
+// the arguments both feature entry points share, checked and packed
+bool features_args(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                   const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom, FeatArgs& q, ObjTable& ot) {
+    int n_smooth = 0;
+    if (!nodes || !tris || !geom || !denoise_size_valid(H, W) || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f) || n_scene_tri < 0 ||
+        n_scene_tri > INT32_MAX || !object_table(objects, n_objects, ot, &n_smooth) || (n_smooth > 0 && !obj_nrm))
+        return false;
+    for (int k = 0; k < n_objects; ++k)
+        if (objects[k].first_tri < n_scene_tri) return false;
+    q.nodes = static_cast<const float4*>(nodes);
+    q.tris = static_cast<const float4*>(tris);
+    q.obj_nrm = obj_nrm;
+    q.nrm_map = nrm_map;
+    q.geom = reinterpret_cast<float4*>(geom);
+    q.H = H; q.W = W;
+    q.n_scene_tri = (int32_t)n_scene_tri;
+    const double th = std::tan(0.5 * (double)fov_x_deg * 3.14159265358979323846 / 180.0);   // render_common's camera
+    q.f_pix = (float)((0.5 * W) / th);
+    q.cx = 0.5f * (float)(W - 1);
+    q.cy = 0.5f * (float)(H - 1);
+    q.f_ndc = (float)(1.0 / th);
+    q.aspect = (float)W / (float)H;
+    q.rho_scale = (float)(2.0 * th / W);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int matpbr_path_features(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                         const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom, void* stream) {
+    FeatArgs q{};
+    ObjTable ot{};
+    if (!features_args(nodes, tris, H, W, fov_x_deg, objects, n_objects, obj_nrm, n_scene_tri, nrm_map, geom, q, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
+    const dim3 grid((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((H + kTileY - 1) / kTileY));
+    hipLaunchKernelGGL(features_kernel, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, ot);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_features_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                              const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom) {
+    FeatArgs q{};
+    ObjTable ot{};
+    if (!features_args(nodes, tris, H, W, fov_x_deg, objects, n_objects, obj_nrm, n_scene_tri, nrm_map, geom, q, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j) {
+            HostStack stk;
+            float4 g0, g1;
+            features_pixel(q, ot, i, j, stk, g0, g1);
+            q.geom[2 * ((long)i * W + j)] = g0;
+            q.geom[2 * ((long)i * W + j) + 1] = g1;
+        }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_denoise_prepare(const float* A, const float* B, const float* geom, int H, int W, float* cv0, void* stream) {
+    if (!A || !B || !geom || !cv0 || !denoise_size_valid(H, W)) return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(denoise_prepare_kernel, denoise_grid(H, W), dim3(kDnTileX, kDnTileY), 0, (hipStream_t)stream, A, B,
+                       reinterpret_cast<const float4*>(geom), H, W, reinterpret_cast<float4*>(cv0));
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_denoise_prepare_host(const float* A, const float* B, const float* geom, int H, int W, float* cv0) {
+    if (!A || !B || !geom || !cv0 || !denoise_size_valid(H, W)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j)
+            reinterpret_cast<float4*>(cv0)[(long)i * W + j] = dn_prepare_pixel(A, B, reinterpret_cast<const float4*>(geom), H, W, i, j);
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_denoise_level(const float* cv_in, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm, int level,
+                              float* cv_out, void* stream) {
+    if (!cv_in || !geom || !alb || !cv_out || cv_in == cv_out || !denoise_size_valid(H, W) || !denoise_params_valid(prm) || level < 0 ||
+        level >= kDnMaxLevels)
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(denoise_level_kernel, denoise_grid(H, W), dim3(kDnTileX, kDnTileY), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(cv_in), reinterpret_cast<const float4*>(geom), alb, H, W, 1 << level, *prm,
+                       reinterpret_cast<float4*>(cv_out), (float*)nullptr, 0);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_denoise_level_host(const float* cv_in, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm, int level,
+                                   float* cv_out) {
+    if (!cv_in || !geom || !alb || !cv_out || cv_in == cv_out || !denoise_size_valid(H, W) || !denoise_params_valid(prm) || level < 0 ||
+        level >= kDnMaxLevels)
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j)
+            reinterpret_cast<float4*>(cv_out)[(long)i * W + j] =
+                dn_level_pixel(reinterpret_cast<const float4*>(cv_in), reinterpret_cast<const float4*>(geom), alb, H, W, i, j, 1 << level, *prm);
+    return MATPBR_PATH_OK;
+}
+
+size_t matpbr_path_denoise_workspace_bytes(int H, int W) {
+    return denoise_size_valid(H, W) ? 2 * (size_t)H * (size_t)W * sizeof(float4) : 0;
+}
+
+int matpbr_path_denoise(const float* A, const float* B, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (!A || !B || !geom || !alb || !out || !workspace || !denoise_size_valid(H, W) || !denoise_params_valid(prm) ||
+        workspace_bytes < matpbr_path_denoise_workspace_bytes(H, W) || ((uintptr_t)workspace & 15))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    const MatpbrPathDenoise pr = *prm;
+    float4* ws[2] = {static_cast<float4*>(workspace), static_cast<float4*>(workspace) + (size_t)H * W};
+    const float4* g = reinterpret_cast<const float4*>(geom);
+    hipLaunchKernelGGL(denoise_prepare_kernel, denoise_grid(H, W), dim3(kDnTileX, kDnTileY), 0, (hipStream_t)stream, A, B, g, H, W, ws[0]);
+    if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    for (int l = 0; l < pr.levels; ++l) {
+        const int last = l + 1 == pr.levels ? 1 : 0;
+        hipLaunchKernelGGL(denoise_level_kernel, denoise_grid(H, W), dim3(kDnTileX, kDnTileY), 0, (hipStream_t)stream, (const float4*)ws[l & 1], g,
+                           alb, H, W, 1 << l, pr, ws[(l + 1) & 1], out, last);
+        if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    return MATPBR_PATH_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,9 @@ The deterministic render is direct light, unshadowed, unde
 Mitsuba's `path` integrator, `max_depth` 4, on the `.ply` mesh under the texel envmap (render_final.py:35-96, inverse_img_w_mi.py:
 49-52).  `PathTracer` is that render on the GPU: shadows, inter-reflection, the envmap's texels as the light.
 `PathTracer.render_bwd` is its backward pass (the fixed-seed estimator's derivative with the sampling detached) and `PathRenderFn`
-puts both behind autograd.  There is no fallback: a missing or failing library raises.
+puts both behind autograd.  `PathTracer.features` and `PathTracer.denoise` are the opt-in denoiser (DESIGN.md section 1.4,
+"Denoiser"): first-hit features and a variance-guided a-trous filter over two half renders, forward only.  There is no fallback: a
+missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -40,6 +42,12 @@ class PathTransEdit(ctypes.Structure):
     _fields_ = [("ior", ctypes.c_float), ("spec_trans", ctypes.c_float), ("refract_distance", ctypes.c_float), ("reserved", ctypes.c_float)]
 
 
+class PathDenoise(ctypes.Structure):
+    """MatpbrPathDenoise (include/matpbr_path.h): the levels and the four sigmas of the a-trous filter."""
+    _fields_ = [("levels", ctypes.c_int32), ("sigma_n", ctypes.c_float), ("sigma_x", ctypes.c_float), ("sigma_a", ctypes.c_float),
+                ("sigma_c", ctypes.c_float)]
+
+
 SIGNATURES = {
     "matpbr_path_version": (ctypes.c_int, []),
     "matpbr_path_strerror": (ctypes.c_char_p, [ctypes.c_int]),
@@ -71,11 +79,24 @@ SIGNATURES = {
     "matpbr_path_render_bwd_normals_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "matpbr_path_render_bwd_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                        [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P, _P, _P]),
+    "matpbr_path_features": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P]),
+    "matpbr_path_features_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P]),
+    "matpbr_path_denoise_prepare": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "matpbr_path_denoise_prepare_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P]),
+    "matpbr_path_denoise_level": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, _P]),
+    "matpbr_path_denoise_level_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
+    "matpbr_path_denoise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "matpbr_path_denoise": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_size_t, _P]),
 }
 VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
 # added at version 3 (smooth inserted objects): a version-3 library built before them loads, and `symbol` names what it lacks
-LATE_SYMBOLS = ("matpbr_path_render_objects_normals", "matpbr_path_object_normal_host", "matpbr_path_object_sample_shading_host")
+SMOOTH_SYMBOLS = ("matpbr_path_render_objects_normals", "matpbr_path_object_normal_host", "matpbr_path_object_sample_shading_host")
+# added at version 3 too (the denoiser)
+DENOISE_SYMBOLS = ("matpbr_path_features", "matpbr_path_features_host", "matpbr_path_denoise_prepare", "matpbr_path_denoise_prepare_host",
+                   "matpbr_path_denoise_level", "matpbr_path_denoise_level_host", "matpbr_path_denoise_workspace_bytes", "matpbr_path_denoise")
+LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS
+DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
 class PathError(RuntimeError):
@@ -105,7 +126,8 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        raise PathError(f"libmatpbr_path.so has no {name}: it was built before smooth inserted objects; rebuild it (build.build_path_library)")
+        what = "the denoiser" if name in DENOISE_SYMBOLS else "smooth inserted objects"
+        raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 
 
@@ -363,6 +385,139 @@ def eval_normal_grad_host(n: np.ndarray, wo: np.ndarray, wi: np.ndarray, a: np.n
     return d_n
 
 
+# ---- the denoiser ("Denoiser") ----------------------------------------------------------------------------------
+def denoise_params(levels: Optional[int] = None, sigma_n: Optional[float] = None, sigma_x: Optional[float] = None,
+                   sigma_a: Optional[float] = None, sigma_c: Optional[float] = None) -> PathDenoise:
+    """The filter's parameters (None: DENOISE_DEFAULTS), checked as the library checks them; ValueError when bad."""
+    given = {"levels": levels, "sigma_n": sigma_n, "sigma_x": sigma_x, "sigma_a": sigma_a, "sigma_c": sigma_c}
+    v = {k: DENOISE_DEFAULTS[k] if x is None else x for k, x in given.items()}
+    if int(v["levels"]) != v["levels"] or not 1 <= int(v["levels"]) <= 8:
+        raise ValueError(f"levels must be an integer in 1..8, got {v['levels']}")
+    for k in ("sigma_n", "sigma_x", "sigma_a", "sigma_c"):
+        if not (float(v[k]) > 0 and np.isfinite(float(v[k]))):
+            raise ValueError(f"{k} must be positive and finite, got {v[k]}")
+    return PathDenoise(int(v["levels"]), float(v["sigma_n"]), float(v["sigma_x"]), float(v["sigma_a"]), float(v["sigma_c"]))
+
+
+def _host_image(x, shape, what: str) -> np.ndarray:
+    """A fresh (so aligned) contiguous float32 copy of `x`, which must have `shape`."""
+    a = np.asarray(x)
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError(f"{what} must be {list(shape)}, got {list(a.shape)}")
+    return np.array(a, dtype=np.float32, order="C", copy=True)
+
+
+def _geom_shape(geom, what: str = "geom") -> tuple:
+    shp = tuple(geom.shape)
+    if len(shp) != 3 or shp[2] != 8 or shp[0] < 1 or shp[1] < 1:
+        raise ValueError(f"{what} must be [H,W,8], got {list(shp)}")
+    return shp[0], shp[1]
+
+
+def features_host(bvh: Dict[str, object], H: int, W: int, fov_x_deg: float = 35.0, objects: Optional[Sequence[PathObject]] = None,
+                  obj_nrm: Optional[np.ndarray] = None, n_scene_tri: int = 0, normal: Optional[np.ndarray] = None) -> np.ndarray:
+    """`PathTracer.features` on the CPU with the routine the kernel runs -> geom [H,W,8].  `bvh`: what `build_bvh` returned;
+    `objects`, `obj_nrm`, `n_scene_tri`: `merge_objects`' table, its corner normals and the depth mesh's triangle count; `normal`
+    [H,W,3]: the shading-normal map."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"H and W must be positive, got {H} x {W}")
+    table = (PathObject * len(objects))(*objects) if objects else None
+    cn = None if obj_nrm is None else np.array(obj_nrm, dtype=np.float32, order="C", copy=True)
+    nm = None if normal is None else _host_image(normal, (H, W, 3), "normal")
+    geom = np.empty((H, W, 8), np.float32)
+    check(symbol("matpbr_path_features_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), H, W, float(fov_x_deg),
+                                              ctypes.cast(table, _P) if table is not None else None, len(objects) if objects else 0,
+                                              _ptr(cn) if cn is not None else None, int(n_scene_tri), _ptr(nm) if nm is not None else None,
+                                              _ptr(geom)), "matpbr_path_features_host")
+    return geom
+
+
+def denoise_prepare_host(A: np.ndarray, B: np.ndarray, geom: np.ndarray) -> np.ndarray:
+    """The filter's first step on the CPU with the routine the kernel runs: A, B [H,W,3], geom [H,W,8] -> cv0 [H,W,4] = ((A + B) / 2,
+    the prefiltered variance of the mean's luminance)."""
+    H, W = _geom_shape(np.asarray(geom))
+    a, b, g = _host_image(A, (H, W, 3), "A"), _host_image(B, (H, W, 3), "B"), _host_image(geom, (H, W, 8), "geom")
+    cv = np.empty((H, W, 4), np.float32)
+    check(symbol("matpbr_path_denoise_prepare_host")(_ptr(a), _ptr(b), _ptr(g), H, W, _ptr(cv)), "matpbr_path_denoise_prepare_host")
+    return cv
+
+
+def denoise_level_host(cv: np.ndarray, geom: np.ndarray, alb: np.ndarray, level: int, **params) -> np.ndarray:
+    """One a-trous level (stride 2^level) on the CPU with the routine the kernel runs: cv [H,W,4], geom [H,W,8], alb [H,W,3] ->
+    cv [H,W,4].  `params`: levels, sigma_n, sigma_x, sigma_a, sigma_c (`denoise_params`)."""
+    prm = denoise_params(**params)
+    H, W = _geom_shape(np.asarray(geom))
+    if not 0 <= int(level) <= 7:
+        raise ValueError(f"level must lie in 0..7, got {level}")
+    c, g, al = _host_image(cv, (H, W, 4), "cv"), _host_image(geom, (H, W, 8), "geom"), _host_image(alb, (H, W, 3), "alb")
+    out = np.empty((H, W, 4), np.float32)
+    check(symbol("matpbr_path_denoise_level_host")(_ptr(c), _ptr(g), _ptr(al), H, W, ctypes.cast(ctypes.byref(prm), _P), int(level), _ptr(out)),
+          "matpbr_path_denoise_level_host")
+    return out
+
+
+def _device_image(x, shape, what: str, device=None) -> torch.Tensor:
+    t = torch.as_tensor(x)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be {list(shape)}, got {list(t.shape)}")
+    return t.to(device if device is not None else t.device, torch.float32).contiguous()
+
+
+def _device_of(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    return torch.device("cuda")
+
+
+@torch.no_grad()
+def denoise_prepare(A, B, geom) -> torch.Tensor:
+    """`denoise_prepare_host` on the device (the current torch stream) -> cv0 [H,W,4]."""
+    H, W = _geom_shape(torch.as_tensor(geom))
+    dev = _device_of(geom, A, B)
+    a, b, g = _device_image(A, (H, W, 3), "A", dev), _device_image(B, (H, W, 3), "B", dev), _device_image(geom, (H, W, 8), "geom", dev)
+    cv = torch.empty(H, W, 4, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_denoise_prepare")(a.data_ptr(), b.data_ptr(), g.data_ptr(), H, W, cv.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream), "matpbr_path_denoise_prepare")
+    return cv
+
+
+@torch.no_grad()
+def denoise_level(cv, geom, alb, level: int, **params) -> torch.Tensor:
+    """`denoise_level_host` on the device (the current torch stream) -> cv [H,W,4]."""
+    prm = denoise_params(**params)
+    H, W = _geom_shape(torch.as_tensor(geom))
+    if not 0 <= int(level) <= 7:
+        raise ValueError(f"level must lie in 0..7, got {level}")
+    dev = _device_of(geom, cv, alb)
+    c, g, al = _device_image(cv, (H, W, 4), "cv", dev), _device_image(geom, (H, W, 8), "geom", dev), _device_image(alb, (H, W, 3), "alb", dev)
+    out = torch.empty(H, W, 4, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_denoise_level")(c.data_ptr(), g.data_ptr(), al.data_ptr(), H, W, ctypes.cast(ctypes.byref(prm), _P), int(level),
+                                              out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "matpbr_path_denoise_level")
+    return out
+
+
+@torch.no_grad()
+def denoise(A, B, alb, geom, workspace: Optional[torch.Tensor] = None, **params) -> torch.Tensor:
+    """The whole filter on the device (the current torch stream): two half renders A, B [H,W,3], the albedo guide alb [H,W,3] and the
+    features geom [H,W,8] -> the denoised mean [H,W,3].  Equal to `denoise_prepare` and `levels` calls of `denoise_level`, bit for
+    bit.  `workspace`: a uint8 device tensor of at least matpbr_path_denoise_workspace_bytes (default: allocated here)."""
+    prm = denoise_params(**params)
+    H, W = _geom_shape(torch.as_tensor(geom))
+    dev = _device_of(geom, A, B, alb)
+    a, b = _device_image(A, (H, W, 3), "A", dev), _device_image(B, (H, W, 3), "B", dev)
+    al, g = _device_image(alb, (H, W, 3), "alb", dev), _device_image(geom, (H, W, 8), "geom", dev)
+    nbytes = int(symbol("matpbr_path_denoise_workspace_bytes")(H, W))
+    if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_denoise")(a.data_ptr(), b.data_ptr(), g.data_ptr(), al.data_ptr(), H, W, ctypes.cast(ctypes.byref(prm), _P),
+                                        out.data_ptr(), workspace.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
+          "matpbr_path_denoise")
+    return out
+
+
 class PathTracer:
     """One mesh in the renderer's frame (camera at the origin looking down -z, `fov_x_deg` horizontal field of view, H x W pixels).
     The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
@@ -399,6 +554,7 @@ class PathTracer:
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
         self._ws: Optional[torch.Tensor] = None      # render_bwd's workspace, kept between calls
+        self._dn_ws: Optional[torch.Tensor] = None   # denoise's
 
     def _tables(self, env: torch.Tensor):
         tab = env_tables(env.cpu().numpy())          # host, fp64 -> fp32: microseconds for the 16 x 32 maps of the pipeline
@@ -464,6 +620,34 @@ class PathTracer:
                                                                     self.obj_nrm.data_ptr(), self.n_scene_tris),
                   "matpbr_path_render_objects_normals")
         return out
+
+    @torch.no_grad()
+    def features(self, normal=None) -> torch.Tensor:
+        """geom [H,W,8] on the device: per pixel (p, rho) and (n, id) of the camera ray through the pixel centre, the denoiser's guides
+        ("Denoiser").  n is the normal `render` shades that camera vertex with: `normal` [H,W,3] is the
+        shading-normal map of `render` (a tracer with objects refuses it); id -1 = no hit, 0 = the depth mesh, 1 + k = object k."""
+        nrm = self._normal(normal, "features") if normal is not None else None
+        geom = torch.empty(self.H, self.W, 8, device=self.device, dtype=torch.float32)
+        check(symbol("matpbr_path_features")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov,
+                                             ctypes.cast(self.objects, _P) if self.objects is not None else None,
+                                             len(self.objects) if self.objects is not None else 0,
+                                             self.obj_nrm.data_ptr() if self.obj_nrm is not None else None, self.n_scene_tris,
+                                             nrm.data_ptr() if nrm is not None else None, geom.data_ptr(),
+                                             torch.cuda.current_stream(self.device).cuda_stream), "matpbr_path_features")
+        return geom
+
+    @torch.no_grad()
+    def denoise(self, A, B, alb, geom, **params) -> torch.Tensor:
+        """The a-trous filter over two half renders A, B [H,W,3] of this tracer (independent seeds, the same sample count), guided by
+        the albedo alb [H,W,3] and `features()` -> the denoised mean [H,W,3].  `params`: levels, sigma_n, sigma_x, sigma_a, sigma_c
+        (default DENOISE_DEFAULTS).  Forward only."""
+        if tuple(torch.as_tensor(geom).shape) != (self.H, self.W, 8):
+            raise ValueError(f"geom must be [{self.H},{self.W},8], got {list(torch.as_tensor(geom).shape)}")
+        nbytes = int(symbol("matpbr_path_denoise_workspace_bytes")(self.H, self.W))
+        if self._dn_ws is None or self._dn_ws.numel() < nbytes:
+            self._dn_ws = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        to = lambda x: x.to(self.device) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x)).to(self.device)
+        return denoise(to(A), to(B), to(alb), to(geom), workspace=self._dn_ws, **params)
 
     @torch.no_grad()
     def render_trans(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, mask, bg, ior: float = 1.2,

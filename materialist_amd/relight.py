@@ -9,7 +9,9 @@ Material editing inside `best_results/mask.png` (`edit=` of `render_w_mi`, :143-
 transfer is computed.  Object insertion (`--mode oi`, :100-141,207-237,263-288) is `render_oi`: it always path traces.
 `integrator="path"` renders instead with the path tracer (materialist_amd/pathtrace.py), the integrator the
 reference's final images come from: the `.ply` mesh, shadows, inter-reflection, the envmap's texels as the light; rolling frames
-roll the envmap's texel columns.
+roll the envmap's texel columns.  `denoise="atrous"` passes a path-traced image through the project's denoiser (DESIGN.md section 1.4,
+"Denoiser"): every render of `spp` samples becomes two of `spp / 2` with independent seeds, and one variance-guided a-trous filter
+runs over their sums, guided by the first-hit features and the albedo.  The default, "off", leaves every output as it was.
 """
 from __future__ import annotations
 
@@ -206,18 +208,67 @@ def _check_integrator(integrator: str, shading_normals: str = "face") -> None:
         raise ValueError("shading_normals='map' needs integrator='path' (the 'sh' render takes its normals by the scene's name)")
 
 
+def _check_denoise(denoise: str, integrator: str, spp: int) -> bool:
+    """True when the a-trous denoiser is asked for and can run; ValueError when it cannot."""
+    if denoise not in ("off", "atrous"):
+        raise ValueError(f"denoise must be 'off' or 'atrous', got {denoise!r}")
+    if denoise == "off":
+        return False
+    if integrator != "path":
+        raise ValueError("denoise='atrous' needs integrator='path': the 'sh' render is deterministic quadrature and has no noise to filter")
+    if spp < 2 or spp % 2:
+        raise ValueError(f"denoise='atrous' splits every render into two halves of spp / 2 samples: spp must be even, got {spp}")
+    return True
+
+
+def albedo_guide(geom: torch.Tensor, albedo: torch.Tensor, bsdfs=()) -> torch.Tensor:
+    """The denoiser's albedo guide [H,W,3] from the features' ids: the albedo map as rendered where the camera ray hits the depth mesh
+    (id 0), a diffuse object's reflectance, 1 on glass, 0 where it hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
+    ids = geom[..., 7]
+    guide = albedo.to(geom.device, torch.float32).reshape(geom.shape[0], geom.shape[1], 3).clone()
+    guide[ids < 0] = 0.0
+    for k, b in enumerate(bsdfs):
+        value = b["reflectance"] if b["type"] == "diffuse" else (1.0, 1.0, 1.0)
+        guide[ids == 1 + k] = torch.tensor([float(x) for x in np.broadcast_to(np.asarray(value, np.float64), (3,))], device=geom.device)
+    return guide
+
+
+def _denoised(pt, render_half, iters: int, seed: int, geom: torch.Tensor, guide: torch.Tensor) -> torch.Tensor:
+    """`iters` pairs of half renders, `render_half(seed)` with seeds seed + 2 i (summed into A) and seed + 2 i + 1 (into B), then one
+    filter over the two means."""
+    A = torch.zeros_like(guide)
+    B = torch.zeros_like(guide)
+    for i in range(iters):
+        A += render_half(seed + 2 * i)
+        B += render_half(seed + 2 * i + 1)
+    if iters > 1:
+        A /= iters
+        B /= iters
+    return pt.denoise(A, B, guide, geom)
+
+
 def render_real(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
                 spp: int = 64, device="cuda", edit: Optional[Dict[str, object]] = None, integrator: str = "sh", max_depth: int = 4,
-                seed: int = 0, shading_normals: str = "face") -> str:
+                seed: int = 0, shading_normals: str = "face", denoise: str = "off") -> str:
     """render_final.py:148-203,241-260: one re-render under `env_path` -> mi_<name>_<env>_<edit flag>.exr / .png.
     integrator "sh": the deterministic render (SH25 light, direct, unshadowed); "path": the path tracer, `max_depth` / `seed`, shading
-    with the mesh's face normals or, with `shading_normals="map"`, with best_results/normal.exr whatever the scene is called."""
+    with the mesh's face normals or, with `shading_normals="map"`, with best_results/normal.exr whatever the scene is called.
+    `denoise="atrous"` (path only, even `spp`): two renders of spp / 2, seeds `seed` and `seed + 1`, through the a-trous filter."""
     _check_integrator(integrator, shading_normals)
+    atrous = _check_denoise(denoise, integrator, spp)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
     edit_flag = apply_edit(mat, edit)
-    if integrator == "path":
+    if atrous:
+        pt = _path_tracer(scene_dir, save_name, mat, device)
+        nrm = mat["normal"] if shading_normals == "map" else None
+        env = load_image(env_path)
+        tabs = pt.tables(env)
+        geom = pt.features(normal=nrm)
+        half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs, normal=nrm)
+        img = _denoised(pt, half, 1, seed, geom, albedo_guide(geom, mat["albedo"]))
+    elif integrator == "path":
         img = _path_tracer(scene_dir, save_name, mat, device).render(mat["albedo"], mat["roughness"], mat["metallic"],
                                                                      load_image(env_path), spp, max_depth, seed,
                                                                      normal=mat["normal"] if shading_normals == "map" else None)
@@ -253,15 +304,18 @@ def find_envmap_oi(save_name: str, env_path: Optional[str], input_path: Optional
 
 
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
-              spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat") -> str:
+              spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
+              denoise: str = "off") -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
     The meshes are in the renderer's frame, read by `mesh.read_ply_any`.  `object_normals`: "flat" (default) shades them with their
     face normals; "vertex" shades each smooth, with its file's vertex normals where it has them, else with
     `mesh.angle_weighted_normals` ("Smooth inserted objects").  `n_iter` renders with seeds seed + i are
-    averaged.  There is no denoiser here: the reference renders spp 32 x 10 and denoises each with OptiX, so
-    the samples do the denoiser's work (default spp 64 x 10)."""
+    averaged.  The reference renders spp 32 x 10 and denoises each with OptiX, which stays out: by default the
+    samples do the denoiser's work (spp 64 x 10).  `denoise="atrous"` (even `spp`) runs the project's own filter instead: each of
+    the `n_iter` renders becomes two of spp / 2, seeds seed + 2 i and seed + 2 i + 1, summed into two half buffers, and one a-trous
+    pass runs over them ("Denoiser"); behind glass only its colour term guides."""
     from . import mesh as _mesh
 
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
@@ -274,6 +328,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
         raise ValueError(f"n_iter must be at least 1, got {n_iter}")
     if object_normals not in ("flat", "vertex"):
         raise ValueError(f"object_normals must be 'flat' or 'vertex', got {object_normals!r}")
+    atrous = _check_denoise(denoise, "path", spp)
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
     for p, b in have:
@@ -285,10 +340,15 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     pt = _path_tracer(scene_dir, save_name, mat, device, objects)
     env = load_image(env_path)
     tabs = pt.tables(env)
-    img = torch.zeros_like(mat["albedo"])
-    for i in range(n_iter):
-        img += pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp, max_depth, seed + i, tables=tabs)
-    img /= n_iter
+    if atrous:
+        geom = pt.features()
+        half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs)
+        img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], [b for _, b in have]))
+    else:
+        img = torch.zeros_like(mat["albedo"])
+        for i in range(n_iter):
+            img += pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp, max_depth, seed + i, tables=tabs)
+        img /= n_iter
     env_id = os.path.basename(env_path)[:-4]
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
@@ -303,11 +363,13 @@ TRANS_ALBEDO, TRANS_ROUGHNESS, TRANS_METALLIC = 0.7, 0.3, 0.0   # the maps insid
 
 def render_trans(save_name: str, ior: float = 1.2, keep_albedo_color: bool = False, spec_trans: float = 0.4, env_path: Optional[str] = None,
                  input_path: Optional[str] = None, save_path: Optional[str] = None, spp: int = 64, iters: int = 10, max_depth: int = 4,
-                 seed: int = 0, refract_distance: float = 100.0, device="cuda") -> str:
+                 seed: int = 0, refract_distance: float = 100.0, device="cuda", denoise: str = "off") -> str:
     """trans_edit.py:16-60: the masked part of the scene as glass (TransBSDF; DESIGN.md section 1.4, "Transparency editing") ->
     mi_trans_<ior>_<wA|woA>_<specTrans>_<name>_<env>.exr / .png.  Needs best_results/mask.png and best_results/bg.png.  Inside the
     mask the albedo becomes 0.7 unless `keep_albedo_color`, roughness 0.3 and metallic 0.  The light is `env_path`, else
-    best_results/envmap.hdr.  `iters` renders with seeds seed + i are averaged."""
+    best_results/envmap.hdr.  `iters` renders with seeds seed + i are averaged.  `denoise="atrous"` (even `spp`): each of them becomes
+    two of spp / 2, seeds seed + 2 i and seed + 2 i + 1, and one a-trous pass runs over the two sums; the masked pixels are an id of
+    their own, so nothing filters across the mask's edge, and inside it the guide is the edited albedo."""
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     mat_dir = os.path.join(scene_dir, "best_results")
     for name in ("mask.png", "bg.png"):
@@ -315,6 +377,7 @@ def render_trans(save_name: str, ior: float = 1.2, keep_albedo_color: bool = Fal
             raise FileNotFoundError(f"transparency editing needs {os.path.join(mat_dir, name)}")
     if iters < 1:
         raise ValueError(f"iters must be at least 1, got {iters}")
+    atrous = _check_denoise(denoise, "path", spp)
     env_path = find_envmap(save_name, env_path, input_path)
     mat = load_estimated_brdf(mat_dir, device)
     mask = mat["mask"]
@@ -325,11 +388,20 @@ def render_trans(save_name: str, ior: float = 1.2, keep_albedo_color: bool = Fal
     pt = _path_tracer(scene_dir, save_name, mat, device)
     env = load_image(env_path)
     tabs = pt.tables(env)
-    img = torch.zeros_like(mat["albedo"])
-    for i in range(iters):
-        img += pt.render_trans(mat["albedo"], mat["roughness"], mat["metallic"], env, mask, mat["bg"], ior, spec_trans, refract_distance, spp,
-                               max_depth, seed + i, tables=tabs)
-    img /= iters
+    if atrous:
+        geom = pt.features()
+        guide = albedo_guide(geom, mat["albedo"])                   # the maps are edited above: inside the mask, the edited albedo
+        geom = geom.clone()
+        geom[..., 7][mask] = 1.0                                    # the glass is an id of its own
+        half = lambda sd: pt.render_trans(mat["albedo"], mat["roughness"], mat["metallic"], env, mask, mat["bg"], ior, spec_trans,
+                                          refract_distance, spp // 2, max_depth, sd, tables=tabs)
+        img = _denoised(pt, half, iters, seed, geom, guide)
+    else:
+        img = torch.zeros_like(mat["albedo"])
+        for i in range(iters):
+            img += pt.render_trans(mat["albedo"], mat["roughness"], mat["metallic"], env, mask, mat["bg"], ior, spec_trans, refract_distance, spp,
+                                   max_depth, seed + i, tables=tabs)
+        img /= iters
     env_id = os.path.basename(env_path)[:-4]
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
@@ -343,10 +415,13 @@ def render_trans(save_name: str, ior: float = 1.2, keep_albedo_color: bool = Fal
 def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int = 36, rotation_step: float = 10.0,
                           input_path: Optional[str] = None, save_path: Optional[str] = None, spp: int = 64, device="cuda",
                           write_frames: bool = True, edit: Optional[Dict[str, object]] = None, integrator: str = "sh",
-                          max_depth: int = 4, seed: int = 0, shading_normals: str = "face") -> Dict[str, object]:
+                          max_depth: int = 4, seed: int = 0, shading_normals: str = "face", denoise: str = "off") -> Dict[str, object]:
     """render_final.py:300-418: `frames` renders, the envmap rolled by int(angle/360*W) columns per frame.  integrator "sh": the
-    rolled light is the SH rotation of the projected envmap; "path": the path tracer renders the rolled texels themselves (`shading_normals` as in `render_real`)."""
+    rolled light is the SH rotation of the projected envmap; "path": the path tracer renders the rolled texels themselves (`shading_normals` as in `render_real`).
+    `denoise="atrous"` (path only, even `spp`): every frame is two renders of spp / 2, seeds `seed` and `seed + 1`, through the a-trous
+    filter; the features are computed once for all frames."""
     _check_integrator(integrator, shading_normals)
+    atrous = _check_denoise(denoise, integrator, spp)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
     env = load_image(env_path)
@@ -358,8 +433,20 @@ def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int =
     if integrator == "path":
         pt = _path_tracer(scene_dir, save_name, mat, device)
         nrm = mat["normal"] if shading_normals == "map" else None
-        render_frames = lambda f0, f1: torch.stack([pt.render(mat["albedo"], mat["roughness"], mat["metallic"], np.roll(env, shifts[f], axis=1),
-                                                              spp, max_depth, seed, normal=nrm) for f in range(f0, f1)])
+        if atrous:
+            geom = pt.features(normal=nrm)                           # the camera and the mesh do not move: one set for all frames
+            guide = albedo_guide(geom, mat["albedo"])
+
+            def render_frame(f):
+                rolled = np.roll(env, shifts[f], axis=1)
+                tabs = pt.tables(rolled)
+                half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], rolled, spp // 2, max_depth, sd, tables=tabs,
+                                            normal=nrm)
+                return _denoised(pt, half, 1, seed, geom, guide)
+        else:
+            render_frame = lambda f: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], np.roll(env, shifts[f], axis=1), spp, max_depth,
+                                               seed, normal=nrm)
+        render_frames = lambda f0, f1: torch.stack([render_frame(f) for f in range(f0, f1)])
     else:
         lights = [_sh.rotate_y_matrix(2 * np.pi * s / We) @ light0 for s in shifts]
         rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))

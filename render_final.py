@@ -30,6 +30,9 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="--integrator path and --mode oi: random seed")
     ap.add_argument("--shading_normals", choices=("face", "map"), default="face",
                     help="--integrator path: face = shade with the mesh's face normals (default); map = shade with best_results/normal.exr")
+    ap.add_argument("--denoise", choices=("off", "atrous"), default="off",
+                    help="--integrator path and --mode oi: atrous = split every render into two halves of spp/2 with independent seeds and pass "
+                         "their mean through the variance-guided a-trous filter (needs an even --spp); off = the plain average")
     ap.add_argument("--oi_iters", type=int, default=10, help="--mode oi: renders averaged (seeds seed, seed + 1, ...)")
     ap.add_argument("--oi_normals", choices=["flat", "vertex"], default="flat",
                     help="--mode oi: flat = face normals; vertex = each .ply shades smooth with its vertex normals (angle-weighted ones if it has none)")
@@ -37,6 +40,11 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.shading_normals == "map" and (a.integrator != "path" or a.mode == "oi"):
         ap.error("--shading_normals map needs --integrator path and --mode real or rolling (inserted objects know no normal map)")
+    if a.denoise == "atrous":
+        if a.mode != "oi" and a.integrator != "path":
+            ap.error("--denoise atrous needs --integrator path (or --mode oi): the sh render is deterministic and has no noise to filter")
+        if a.spp < 2 or a.spp % 2:
+            ap.error("--denoise atrous splits every render into two halves of spp/2 samples: --spp must be even")
     return a
 
 
@@ -45,7 +53,7 @@ def main(argv=None):
     from materialist_amd import relight
 
     edit = {"albedo": a.edit_albedo, "roughness": a.edit_roughness, "metallic": a.edit_metallic}
-    it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed, "shading_normals": a.shading_normals}
+    it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed, "shading_normals": a.shading_normals, "denoise": a.denoise}
     if a.mode == "real":
         print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it))
     elif a.mode == "rolling":
@@ -54,7 +62,7 @@ def main(argv=None):
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
         print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
-                                                 object_normals=a.oi_normals))
+                                                 object_normals=a.oi_normals, denoise=a.denoise))
     else:
         raise ValueError("Invalid mode")
 

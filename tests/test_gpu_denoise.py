@@ -1,0 +1,326 @@
+"""The denoiser on the GPU ("Denoiser"): the feature kernel against the CPU routine, the prepare and level
+kernels against fp64 at every pixel, the chain (bit-identity with the separate steps and from run to run, and against the fp64
+chain), small real renders inside their per-id convex hull, quality and cost on one indoor2 frame, and the command lines."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import denoise_fp64 as dn  # noqa: E402
+import path_fp64 as pf  # noqa: E402
+import path_oi_fp64 as po  # noqa: E402
+import path_oi_smooth_fp64 as ps  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+FOV = pf.FOV
+# the device chain against the fp64 chain at L = 5 on 40 x 72, worst pixel relative to max|c_in|: measured 3.66e-07 (MI355X; the CPU
+# routine: 4.43e-07); the bound is four times that (the project's ceiling for such a bound is 1e-3)
+CHAIN_MEASURED = 3.66e-7
+CHAIN_BOUND = min(4 * CHAIN_MEASURED, 1e-3)
+
+
+@pytest.fixture(scope="module")
+def pt():
+    from materialist_amd import build, pathtrace
+
+    build.build_path_library()
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return pathtrace
+
+
+def _report(what, value):
+    print(f"[denoise] {what}: {value}")
+    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"test_gpu_denoise\t{what}\t{value}\n")
+
+
+def _bits(x):
+    return x.cpu().numpy().view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def fields():
+    """The CPU test's random inputs and their fp64 results, computed once: {(H, W): (inputs, prepare64, [level64 0..4])}."""
+    out = {}
+    for H, W in dn.SHAPES:
+        x = dn.random_inputs(H, W)
+        out[(H, W)] = (x, dn.prepare(x["A"], x["B"], x["geom"]), [dn.level(x["cv"], x["geom"], x["alb"], l) for l in range(5)])
+    return out
+
+
+# ---- 1: the feature kernel ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", [(36, 20), (17, 9)])
+def test_features_match_the_cpu_routine(pt, H, W):
+    """id exact, p within 1e-5 (1 + |p|), n within 1e-5, rho within 1e-6 relative, in every pixel (17 x 9: partial workgroups).
+
+    The depth mesh's vertices lie on the rays through the pixel centres ("Camera"), so every centre ray that
+    meets the mesh meets it in a vertex, where rounding decides which of the up to six triangles around it wins, or that none does.
+    The feature ray therefore walks the BVH without fused multiply-adds (`trace_strict`), so that the device takes the decisions the
+    CPU takes; with `trace` itself 35 of 720 ids and 76 face normals differed at 36 x 20.  Measured (MI355X): no id and no triangle
+    differs at 36 x 20, 17 x 9, 24 x 24 and 64 x 64; worst p 1.9e-7, n 1.5e-6, rho 3.1e-7."""
+    from materialist_amd import mesh
+
+    rm = mesh.reference_mesh(pf.groove_scene(H, W), FOV)
+    for name, V, T, n_scene, table, corner, nmap in dn.feature_scenes(pt, H, W):
+        ref = pt.features_host(pt.build_bvh(V, T, n_scene if table else None), H, W, FOV, table, corner, n_scene, nmap)
+        tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=ps.table_scene() if table else None)
+        got = tracer.features(normal=nmap).cpu().numpy()
+        dn.check_features(got, ref.astype(np.float64), f"device against host, {name} {H}x{W}", _report)
+
+
+# ---- 2: prepare and every level against fp64 -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", dn.SHAPES)
+def test_prepare_and_every_level_match_fp64(pt, fields, H, W):
+    """The CPU test's inputs, shapes and bounds, every pixel: |c - c64| <= 1e-4 max|c_in|, |v - v64| <= 1e-4 max v_in.  Measured worst
+    case over the four shapes (MI355X): prepare 5.4e-8 / 3.0e-7, levels 1.1e-6 (colour) and 9.0e-7 (variance)."""
+    x, prep64, levels64 = fields[(H, W)]
+    got = pt.denoise_prepare(torch.from_numpy(x["A"]).cuda(), torch.from_numpy(x["B"]).cuda(), torch.from_numpy(x["geom"]).cuda())
+    got = got.cpu().numpy().astype(np.float64)
+    c_in = max(float(np.abs(x["A"]).max()), float(np.abs(x["B"]).max()))
+    v_in = float(((dn.lum(x["A"]) - dn.lum(x["B"])) ** 2 / 4).max())
+    ec, ev = float(np.abs(got[..., :3] - prep64[..., :3]).max()) / c_in, float(np.abs(got[..., 3] - prep64[..., 3]).max()) / v_in
+    _report(f"device prepare {H}x{W}: worst colour / variance error relative to the largest input", (ec, ev))
+    assert ec <= 1e-4 and ev <= 1e-4
+    c_in, v_in = float(np.abs(x["cv"][..., :3]).max()), float(x["cv"][..., 3].max())
+    cv, geom, alb = (torch.from_numpy(x[k]).cuda() for k in ("cv", "geom", "alb"))
+    for l in range(5):
+        got = pt.denoise_level(cv, geom, alb, l).cpu().numpy().astype(np.float64)
+        ec = float(np.abs(got[..., :3] - levels64[l][..., :3]).max()) / c_in
+        ev = float(np.abs(got[..., 3] - levels64[l][..., 3]).max()) / v_in
+        _report(f"device level {l} {H}x{W}: worst colour / variance error relative to the largest input", (ec, ev))
+        assert ec <= 1e-4 and ev <= 1e-4, (l, ec, ev)
+
+
+# ---- 3: the composed call ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", [(17, 9), (40, 72)])
+def test_the_chain_equals_its_steps_bit_for_bit(pt, fields, H, W):
+    x = fields[(H, W)][0]
+    A, B, geom, alb = (torch.from_numpy(x[k]).cuda() for k in ("A", "B", "geom", "alb"))
+    for levels in (1, 2, 5):
+        one = pt.denoise(A, B, alb, geom, levels=levels)
+        cv = pt.denoise_prepare(A, B, geom)
+        for l in range(levels):
+            cv = pt.denoise_level(cv, geom, alb, l, levels=levels)
+        assert np.array_equal(_bits(one), _bits(cv[..., :3].contiguous())), levels
+        assert np.array_equal(_bits(one), _bits(pt.denoise(A, B, alb, geom, levels=levels))), levels      # and from run to run
+
+
+def test_the_chain_matches_the_fp64_chain(pt, fields):
+    """L = 5 on 40 x 72, the worst pixel relative to max|c_in|: measured CHAIN_MEASURED, asserted at four times that."""
+    x = fields[(40, 72)][0]
+    A, B, geom, alb = (torch.from_numpy(x[k]).cuda() for k in ("A", "B", "geom", "alb"))
+    got = pt.denoise(A, B, alb, geom, levels=5).cpu().numpy().astype(np.float64)
+    ref = dn.chain(x["A"], x["B"], x["geom"], x["alb"], levels=5)
+    worst = float(np.abs(got - ref).max()) / max(float(np.abs(x["A"]).max()), float(np.abs(x["B"]).max()))
+    _report("device chain against the fp64 chain, L = 5, 40x72: worst pixel relative to max|c_in|", worst)
+    assert worst <= CHAIN_BOUND
+
+
+# ---- 4: real renders, small ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene", ["groove", "table"])
+def test_small_renders_stay_inside_their_convex_hull(pt, scene):
+    """Halves at spp 4: the output is finite, non-negative and, per channel, within the [min, max] of (A + B) / 2 over the pixels of
+    its own id its footprint reaches (1e-6 relative for rounding)."""
+    from materialist_amd import mesh
+    from materialist_amd.relight import albedo_guide
+
+    H, W = (24, 24) if scene == "groove" else (36, 20)
+    rm = mesh.reference_mesh(pf.groove_scene(H, W), FOV)
+    rng = np.random.default_rng(11)
+    a, r, m = pf.groove_maps(H, W, rng)
+    env = pf.groove_env(rng)
+    objects = ps.table_scene() if scene == "table" else None
+    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=objects)
+    kw = dict(spp=4, max_depth=6 if scene == "table" else 4, tables=tracer.tables(env))
+    A, B = tracer.render(a, r, m, env, seed=0, **kw), tracer.render(a, r, m, env, seed=1, **kw)
+    geom = tracer.features()
+    guide = albedo_guide(geom, torch.from_numpy(a).cuda(), [ob["bsdf"] for ob in objects or ()])
+    out = tracer.denoise(A, B, guide, geom).cpu().numpy().astype(np.float64)
+    assert np.isfinite(out).all() and (out >= 0).all()
+    ids = geom[..., 7].cpu().numpy()
+    if scene == "table":
+        assert set(np.unique(ids)) >= {0.0, 1.0, 2.0, 3.0}
+        g = guide.cpu().numpy()
+        assert np.all(g[ids == 1] == 1.0) and np.allclose(g[ids == 2], 0.8) and np.all(g[ids == -1] == 0.0) and np.array_equal(g[ids == 0], a[ids == 0])
+    mean = (A.cpu().numpy().astype(np.float64) + B.cpu().numpy().astype(np.float64)) / 2
+    worst = dn.convex_hull_violation(out, mean, ids)
+    _report(f"{scene} {H}x{W}, halves at spp 4: worst excess over the per-id convex hull, relative to the largest input", worst)
+    assert worst <= 1e-6
+    assert float(np.abs(out - mean).max()) > 0.02 * float(mean.max())       # it filtered
+
+
+# ---- 5: quality and cost at real size ------------------------------------------------------------------------------------------------------------
+def test_indoor2_denoised_against_plain_at_the_same_sample_count(pt, golden_dir):
+    """One 512 x 512 frame of tests/golden/indoor2.npz (test_gpu_path_trans.py's set-up without the mask), max_depth 4.  Against a
+    converged render (spp 2048, seed 100), in the gamma-2.2 PSNR of test_gpu_path.py: the denoised image (halves of spp 8, seeds 2 and 3)
+    must beat the plain render of spp 16 (seed 1).  Recorded: both PSNRs, plain spp 64's, features + denoise in ms (hip events, best of
+    two after a warm-up) and the spp-16 render's ms.  Guard: features + denoise cost less than the spp-16 render itself (about 2 ms of
+    cache traffic against about 20 ms: it catches spills or a runaway, and is no target).
+    Measured (MI355X): 32.04 dB denoised, 26.62 dB plain spp 16, 32.59 dB plain spp 64; features + guide + denoise 0.46 ms (features
+    alone 0.27 ms) against 20.3 ms for the spp-16 render."""
+    from materialist_amd import mesh
+    from materialist_amd.relight import albedo_guide
+
+    dev = torch.device("cuda:0")
+    z = np.load(os.path.join(golden_dir, "indoor2.npz"))
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+    a = t(z["ref_albedo_u8"].astype(np.float32) / 255.0)
+    r = t(z["ref_roughness_u8"].astype(np.float32)[..., None] / 255.0).clamp(0.07, 1.0)
+    m = t(z["ref_metallic_u8"].astype(np.float32)[..., None] / 255.0)
+    env = z["ref_envmap_f32"]
+    depth = z["depth_pred_f32"]
+    depth = 2 * depth.max() - depth                                                  # inverse_img_w_mi.py:722
+    H, W = depth.shape
+    rm = mesh.reference_mesh(depth, FOV)
+    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV)
+    tabs = tracer.tables(env)
+    render = lambda spp, seed: tracer.render(a, r, m, env, spp=spp, max_depth=4, seed=seed, tables=tabs)
+    converged = render(2048, 100).cpu().numpy().astype(np.float64)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), res
+
+    A, B = render(8, 2), render(8, 3)
+
+    def filt():
+        geom = tracer.features()
+        return tracer.denoise(A, B, albedo_guide(geom, a), geom)
+
+    filt()                                                                           # warm-up (the spp-16 render is warm already)
+    (ms_f, den), (ms_f2, _) = timed(filt), timed(filt)
+    (ms_r, plain), (ms_r2, _) = timed(lambda: render(16, 1)), timed(lambda: render(16, 1))
+    ms_f, ms_r = min(ms_f, ms_f2), min(ms_r, ms_r2)
+    geom = tracer.features()
+    ms_feat = min(timed(tracer.features)[0], timed(tracer.features)[0])
+    g = lambda x: np.clip(x, 0, 1) ** (1 / 2.2)
+    psnr = lambda x: float(-10 * np.log10(np.mean((g(x.cpu().numpy().astype(np.float64)) - g(converged)) ** 2)))
+    assert bool(torch.isfinite(den).all()) and float((geom[..., 7] >= 0).float().mean()) > 0.9
+    p_den, p_plain, p_64 = psnr(den), psnr(plain), psnr(render(64, 1))
+    _report("indoor2 512x512 max_depth 4, gamma-2.2 PSNR against spp 2048: denoised (2 x spp 8), plain spp 16, plain spp 64",
+            f"{p_den:.2f}, {p_plain:.2f}, {p_64:.2f}")
+    _report("indoor2 512x512: features + guide + denoise ms, features alone ms, the spp-16 render's ms (best of 2)",
+            f"{ms_f:.3f}, {ms_feat:.3f}, {ms_r:.2f}")
+    assert p_den > p_plain
+    assert ms_f < ms_r
+
+
+# ---- 6: command lines ------------------------------------------------------------------------------------------------------------------------------
+def _synthetic_output(tmp, name="case", H=32, W=32):
+    """tests/test_gpu_path_trans.py's synthetic output directory: the 32 x 32 scene, best_results/mask.png and an RGBA bg.png."""
+    from PIL import Image
+
+    from materialist_amd import mesh
+    from materialist_amd.imageio_exr import write_exr
+    from materialist_amd.imageio_hdr import write_hdr
+
+    rng = np.random.default_rng(2)
+    scene = os.path.join(tmp, name)
+    br = os.path.join(scene, "best_results")
+    os.makedirs(br)
+    a, r, m = pf.groove_maps(H, W, rng)
+    write_exr(os.path.join(br, "albedo.exr"), a)
+    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
+    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
+    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
+    write_hdr(os.path.join(br, "envmap.hdr"), pf.groove_env(rng))
+    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)         # depthPred.exr: the pipeline flips it to 2 max - d
+    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
+    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
+    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
+    mask = (i - 15) ** 2 + (j - 14) ** 2 < 81
+    Image.fromarray(np.repeat((mask * 255).astype(np.uint8)[..., None], 3, -1), "RGB").save(os.path.join(br, "mask.png"))
+    Image.fromarray(rng.integers(0, 256, (H, W, 4), dtype=np.uint8), "RGBA").save(os.path.join(br, "bg.png"))
+    return scene
+
+
+def _run(script, *args):
+    return subprocess.run([sys.executable, os.path.join(ROOT, script), *args], capture_output=True, text=True, timeout=600)
+
+
+def test_render_final_cli_denoise(pt, tmp_path):
+    """--mode real --integrator path --denoise atrous equals the direct PathTracer calls bit for bit; --denoise off gives
+    `relight.render_real`'s bits as before; the sh integrator and an odd --spp are refused with a message."""
+    from materialist_amd import relight
+    from materialist_amd.imageio_exr import read_exr
+
+    tmp = str(tmp_path)
+    scene_dir = _synthetic_output(tmp)
+    common = ["--save_name", "case", "--input_path", tmp, "--save_path", tmp, "--mode", "real"]
+    exr = os.path.join(tmp, "case", "mi_case_envmap_.exr")
+    res = _run("render_final.py", *common, "--integrator", "path", "--spp", "8", "--seed", "5", "--denoise", "atrous")
+    assert res.returncode == 0, res.stdout + res.stderr
+    img = np.ascontiguousarray(read_exr(exr)[..., :3], dtype=np.float32)
+    mat = relight.load_estimated_brdf(os.path.join(scene_dir, "best_results"))
+    tracer = relight._path_tracer(scene_dir, "case", mat, "cuda")
+    env = relight.load_image(os.path.join(scene_dir, "best_results", "envmap.hdr"))
+    A, B = (tracer.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp=4, max_depth=4, seed=s) for s in (5, 6))
+    geom = tracer.features()
+    direct = tracer.denoise(A, B, relight.albedo_guide(geom, mat["albedo"]), geom)
+    assert np.array_equal(_bits(direct), img.view(np.uint32))
+    plain = tracer.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp=8, max_depth=4, seed=5)
+    assert not np.array_equal(_bits(plain), img.view(np.uint32))
+    # off: the bits of before, through the command line and through relight.render_real
+    res = _run("render_final.py", *common, "--integrator", "path", "--spp", "8", "--seed", "5", "--denoise", "off")
+    assert res.returncode == 0, res.stdout + res.stderr
+    off = np.ascontiguousarray(read_exr(exr)[..., :3], dtype=np.float32)
+    assert np.array_equal(_bits(plain), off.view(np.uint32))
+    relight.render_real("case", None, tmp, tmp, 8, integrator="path", seed=5)
+    assert np.array_equal(np.ascontiguousarray(read_exr(exr)[..., :3], dtype=np.float32).view(np.uint32), off.view(np.uint32))
+    # refusals, by the command line and by the function
+    res = _run("render_final.py", *common, "--integrator", "sh", "--denoise", "atrous")
+    assert res.returncode != 0 and "--integrator path" in res.stderr, res.stderr
+    res = _run("render_final.py", *common, "--integrator", "path", "--spp", "7", "--denoise", "atrous")
+    assert res.returncode != 0 and "even" in res.stderr, res.stderr
+    with pytest.raises(ValueError, match="integrator='path'"):
+        relight.render_real("case", None, tmp, tmp, 8, integrator="sh", denoise="atrous")
+    with pytest.raises(ValueError, match="even"):
+        relight.render_real("case", None, tmp, tmp, 7, integrator="path", denoise="atrous")
+    with pytest.raises(ValueError, match="even"):
+        relight.render_rolling_envmap("case", None, 2, input_path=tmp, save_path=tmp, spp=7, integrator="path", denoise="atrous")
+    with pytest.raises(ValueError, match="'off' or 'atrous'"):
+        relight.render_real("case", None, tmp, tmp, 8, integrator="path", denoise="optix")
+
+
+def test_oi_and_trans_edit_cli_denoise(pt, tmp_path):
+    """--mode oi --denoise atrous and trans_edit.py --denoise atrous run and write finite images under the usual names; the rolling
+    mode, in process, filters every frame."""
+    from materialist_amd import mesh, relight
+    from materialist_amd.imageio_exr import read_exr
+
+    tmp = str(tmp_path)
+    scene_dir = _synthetic_output(tmp)
+    Vg, Tg, _ = ps.icosphere((-0.05, 0.03, -0.9), 0.09, 1)
+    Vd, Td = po.cube((0.10, -0.04, -1.0), 0.14, (-0.3, 0.7, 0.2))
+    mesh.write_ply(os.path.join(scene_dir, "oi.ply"), Vg, Tg)
+    mesh.write_ply(os.path.join(scene_dir, "oi2.ply"), Vd, Td)
+    common = ["--save_name", "case", "--input_path", tmp, "--save_path", tmp]
+    res = _run("render_final.py", *common, "--mode", "oi", "--spp", "4", "--oi_iters", "2", "--oi_max_depth", "8", "--denoise", "atrous")
+    assert res.returncode == 0, res.stdout + res.stderr
+    oi = read_exr(os.path.join(tmp, "case", "mi_oi_case_envmap.exr"))[..., :3]
+    assert oi.shape == (32, 32, 3) and np.isfinite(oi).all() and os.path.exists(os.path.join(tmp, "case", "mi_oi_case_envmap.png"))
+    res = _run("trans_edit.py", *common, "--spp", "4", "--iters", "2", "--denoise", "atrous")
+    assert res.returncode == 0, res.stdout + res.stderr
+    tr = read_exr(os.path.join(tmp, "case", "mi_trans_1.2_woA_0.4_case_envmap.exr"))[..., :3]
+    assert tr.shape == (32, 32, 3) and np.isfinite(tr).all() and os.path.exists(os.path.join(tmp, "case", "mi_trans_1.2_woA_0.4_case_envmap.png"))
+    res = _run("trans_edit.py", *common, "--spp", "5", "--denoise", "atrous")
+    assert res.returncode != 0 and "even" in res.stderr, res.stderr
+    out = relight.render_rolling_envmap("case", None, 2, 90.0, tmp, tmp, spp=4, integrator="path", denoise="atrous")
+    assert len(out["frames"]) == 2 and all(os.path.exists(p) for p in out["frames"])

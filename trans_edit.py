@@ -23,6 +23,9 @@ def parse_args(argv=None):
     ap.add_argument("--max_depth", type=int, default=4, help="Mitsuba's max_depth")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--refract_distance", type=float, default=100.0, help="thickness scale of the glass in the background lookup")
+    ap.add_argument("--denoise", choices=("off", "atrous"), default="off",
+                    help="atrous = split every render into two halves of spp/2 and pass their mean through the variance-guided a-trous filter "
+                         "(needs an even --spp); off = the plain average")
     a = ap.parse_args(argv)
     if not (a.ior > 0 and math.isfinite(a.ior)):
         ap.error("--ior must be positive")
@@ -32,6 +35,8 @@ def parse_args(argv=None):
         ap.error("--refract_distance must be non-negative")
     if a.spp < 1 or a.iters < 1:
         ap.error("--spp and --iters must be at least 1")
+    if a.denoise == "atrous" and a.spp % 2:
+        ap.error("--denoise atrous splits every render into two halves of spp/2 samples: --spp must be even")
     if not 1 <= a.max_depth <= 16:
         ap.error("--max_depth must lie in 1..16")
     return a
@@ -42,7 +47,7 @@ def main(argv=None):
     from materialist_amd import relight
 
     print("Wrote file to", relight.render_trans(a.save_name, a.ior, a.keep_albedo_color, a.specTrans, a.env_path, a.input_path, a.save_path,
-                                                a.spp, a.iters, a.max_depth, a.seed, a.refract_distance))
+                                                a.spp, a.iters, a.max_depth, a.seed, a.refract_distance, denoise=a.denoise))
 
 
 if __name__ == "__main__":
