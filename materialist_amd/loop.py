@@ -332,7 +332,10 @@ class FusedBrdfPhase:
         # parts that leave the roughness alone: the specular sums of every pixel are constants of the part (kept from its first render)
         # lazy (default): every part renders from the per-pixel models -- in a part that leaves the roughness alone no pixel ever leaves its
         # model's interval, so its iteration is the same two launches with no re-sampling at all
-        self.s1cache = None if ("r" in optimize_part or self.lazy) else torch.empty((3,) + tuple(self.jac.shape[1:]), dtype=torch.float32, device=self.jac.device)
+        # (d out / d r depends on albedo and metallic: the planes the first render keeps give the later steps' roughness gradient as of the FIRST
+        # step's a, m -- off by lr / a per step.  A caller that reads `g` gets every step's own planes: the samples are walked every time,
+        # the render is the same bit for bit.  Pixels without geometry need the kept planes, which carry their constant models.)
+        self.s1cache = None if ("r" in optimize_part or self.lazy or (keep_grads and scene.bg_mask is None)) else torch.empty((3,) + tuple(self.jac.shape[1:]), dtype=torch.float32, device=self.jac.device)
         ph.s1cache = P(self.s1cache) if self.s1cache is not None else None
         self.lazy_state = ops.lazy_state(self._p["albedo"]) if self.lazy else None
         ph.lazy_state = P(self.lazy_state) if self.lazy else None
