@@ -42,6 +42,8 @@ enum {
 enum {
     MATPBR_PATH_BSDF_DIELECTRIC = 1, /* smooth glass, a delta BSDF: p[0] = int_ior, p[1] = ext_ior (p[2] unused) */
     MATPBR_PATH_BSDF_DIFFUSE = 2,    /* one-sided Lambertian: p = reflectance RGB in [0, 1] */
+    MATPBR_PATH_BSDF_PBR = 3,        /* MatDiffBSDF on constants, one-sided: a MatpbrPathObjectPbr record beside the table; p[] is ignored.
+                                        Only matpbr_path_render_objects_pbr (and the feature entry points) take it. */
 };
 
 /* OR-ed into MatpbrPathObject.kind: the object shades with interpolated corner normals ("Smooth inserted
@@ -56,6 +58,16 @@ typedef struct MatpbrPathObject {
     int32_t n_tri;
     float p[3];
 } MatpbrPathObject;
+
+/* The material of an object of kind MATPBR_PATH_BSDF_PBR ("PBR inserted objects"): the depth mesh's BSDF
+ * on constants.  MatpbrPathObject is frozen, so the record travels beside the table, one per object (read for kind 3 only).  Valid:
+ * a[c] in [0, 1], r in [0.07, 1] (the floor the project's roughness maps are clamped to), m in [0, 1], all finite. */
+typedef struct MatpbrPathObjectPbr {
+    float a[3];
+    float r;
+    float m;
+    float reserved[3];
+} MatpbrPathObjectPbr;
 
 /* Transparency editing ("Transparency editing"): the reference's TransBSDF where the mask is set. */
 typedef struct MatpbrPathTransEdit {
@@ -152,6 +164,27 @@ int matpbr_path_object_normal_host(const float* tri, const float* nrm, const flo
  * weight 0 for a diffuse sample below ng or a diffuse vertex seen from behind ng.  Same outputs, same flags. */
 int matpbr_path_object_sample_shading_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* u,
                                            long N, float* wi, float* weight, float* pdf, int32_t* flags);
+
+/* matpbr_path_render_objects_normals where an object may be of kind MATPBR_PATH_BSDF_PBR (with or without
+ * MATPBR_PATH_OBJECT_SMOOTH).  pbr[n_objects] (HOST memory, copied before the call returns): record k is object k's material and is
+ * read only where object k is of kind 3.  A vertex on such an object is the depth mesh's vertex of matpbr_path_render_normals on the
+ * record's constants: one-sided about the outward face normal ng, no texel read, ns = ng or, where smooth, the interpolated normal
+ * with its three fallbacks; the emitter sample needs ng . wl > 0 and takes f and its pdf from the BSDF about ns; the BSDF sample is
+ * MatDiffBSDF's about ns (lobe by dim 6 > 0.5, weight f / (pdf + 1e-6) where pdf > 1e-6), not a delta event, a sample with
+ * ng . wi <= 0 ends the path, and the next ray starts on ng's side.  With no object of kind 3 this calls
+ * matpbr_path_render_objects_normals and gives its bits (pbr may be NULL then).  Invalid arguments, besides that entry point's: an
+ * object of kind 3 with pbr == NULL or with a record outside the ranges above. */
+int matpbr_path_render_objects_pbr(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                   float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                   int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                   const MatpbrPathObjectPbr* pbr);
+
+/* The table lookup of matpbr_path_render_objects_pbr on the CPU, with the routine the kernel runs: triangle ids[N] -> kind[N] (0: the
+ * id lies in no range; the smooth flag is kept), a[N,3], r[N], m[N] (the record of an object of kind 3; 0 for every other id).  The
+ * table and the records are checked as the render checks them (pbr may be NULL when no object is of kind 3). */
+int matpbr_path_object_lookup_host(const MatpbrPathObject* objects, int n_objects, const MatpbrPathObjectPbr* pbr, const int32_t* ids, long N,
+                                   int32_t* kind, float* a, float* r, float* m);
 
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;
@@ -250,7 +283,8 @@ typedef struct MatpbrPathDenoise {
 
 /* geom of an H x W camera (matpbr_path_render's) over a BVH: one lane per pixel traces one closest-hit ray through the pixel centre.
  * objects[n_objects] (HOST, copied before the call returns), obj_nrm (DEVICE, nullable unless an object is smooth) and n_scene_tri as
- * matpbr_path_render_objects_normals takes them; with n_objects == 0 they may be null / 0.  nrm_map (DEVICE, nullable): the
+ * matpbr_path_render_objects_normals takes them (an object may also be of kind MATPBR_PATH_BSDF_PBR: the features need its kind and
+ * its smooth flag only, and take no records); with n_objects == 0 they may be null / 0.  nrm_map (DEVICE, nullable): the
  * shading-normal map of matpbr_path_render_normals, read at the texel the hit point projects to.  geom: DEVICE, 16-byte aligned. */
 int matpbr_path_features(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
                          const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom, void* stream);

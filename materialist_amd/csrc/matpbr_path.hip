@@ -384,6 +384,33 @@ struct SmoothObjects {
 // object_of for the smooth table: the kind still carries the flag bit
 __device__ __forceinline__ int object_of(const SmoothObjects& so, int id, float p[3]) { return object_of(so.t, id, p); }
 
+// ---- PBR inserted objects ("PBR inserted objects") --------------------------------------------------------
+// An object of kind MATPBR_PATH_BSDF_PBR shades as the depth mesh does, MatDiffBSDF, on the constants of its record instead of a
+// texel's.  MatpbrPathObject is frozen, so the eight records travel to the kernel by value beside the smooth table.
+struct PbrObjects : SmoothObjects {
+    MatpbrPathObjectPbr pbr[MATPBR_PATH_MAX_OBJECTS];
+};
+// object_of for that table: kind (with its flag bit) and p as above; a, r, m written where the object is of kind 3 and left alone
+// elsewhere.  The same unrolled selects over wave-uniform reads.  __host__ __device__: matpbr_path_object_lookup_host runs it.
+__host__ __device__ inline int object_lookup(const ObjTable& ot, const MatpbrPathObjectPbr* pbr, int id, float p[3], float a[3], float& r, float& m) {
+    int kind = 0;
+    if (id < ot.min_id) return kind;
+#pragma unroll
+    for (int k = 0; k < MATPBR_PATH_MAX_OBJECTS; ++k) {
+        const MatpbrPathObject& ob = ot.o[k];
+        if (k < ot.n && id >= ob.first_tri && id - ob.first_tri < ob.n_tri) {
+            kind = ob.kind;
+            p[0] = ob.p[0]; p[1] = ob.p[1]; p[2] = ob.p[2];
+            if ((ob.kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR) {
+                a[0] = pbr[k].a[0]; a[1] = pbr[k].a[1]; a[2] = pbr[k].a[2];
+                r = pbr[k].r;
+                m = pbr[k].m;
+            }
+        }
+    }
+    return kind;
+}
+
 // Moller-Trumbore's u, v of the ray o + t d on (v0, e1, e2), tri_test's operations: u belongs to the second input vertex, v to the
 // third.  A ray in the triangle's plane (det 0) gives values that are not finite, which the interpolation below turns into flat.
 __host__ __device__ inline void tri_uv(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d[3], float& u,
@@ -607,9 +634,12 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 // the kernel had before there were objects; with ObjTable every `if (EDIT ...)` folds away.  NRM: shading normals (Objects =
 // ShadeNormals): `n` stays the face normal ng and `ns` is the map's.  SMOOTH: smooth inserted objects (Objects = SmoothObjects): OBJ
 // with `ns` the interpolated corner normal at the vertices of a flagged object; every `if (SMOOTH ...)` folds away in the other four.
+// PBR: SMOOTH with objects of kind 3 (Objects = PbrObjects), whose vertices run the depth mesh's branch about `ns` on the constants of
+// their record; every `if (PBR ...)` folds away in the other five.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value;
+    constexpr bool PBR = std::is_same<Objects, PbrObjects>::value;
+    constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value || PBR;
     constexpr bool OBJ = std::is_same<Objects, ObjTable>::value || SMOOTH;
     constexpr bool EDIT = std::is_same<Objects, TransEdit>::value;
     constexpr bool NRM = std::is_same<Objects, ShadeNormals>::value;
@@ -664,7 +694,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             const float wo[3] = {-d[0], -d[1], -d[2]};
             int kind = 0;          // (OBJ) 0: the depth mesh; else the inserted object's BSDF and its parameters
             float op[3] = {0.0f, 0.0f, 0.0f};
-            if (OBJ) kind = object_of(ot, __float_as_int(q.tris[3 * k].w), op);
+            float oa[3] = {0.0f, 0.0f, 0.0f}, o_r = 0.0f, o_m = 0.0f;   // (PBR) the record of an object of kind 3
+            if constexpr (PBR) kind = object_lookup(ot.t, ot.pbr, __float_as_int(q.tris[3 * k].w), op, oa, o_r, o_m);
+            else if (OBJ) kind = object_of(ot, __float_as_int(q.tris[3 * k].w), op);
             bool smooth = false;   // (SMOOTH) the object shades with its interpolated corner normals, `ns` below
             if constexpr (SMOOTH) {
                 smooth = (kind & MATPBR_PATH_OBJECT_SMOOTH) != 0;
@@ -681,7 +713,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             const float sx = (ndc0 + 1.0f) * 0.5f * (float)q.W, sy = (ndc1 + 1.0f) * 0.5f * (float)q.H;
             const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
             const long tp = OBJ && kind != 0 ? 0 : (long)ty * q.W + tx;   // an object reads no texel
-            const float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+            float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+            const bool pbr = PBR && kind == MATPBR_PATH_BSDF_PBR;   // (PBR) the depth mesh's branch on the object's constants
+            if constexpr (PBR) {
+                if (pbr) { av[0] = oa[0]; av[1] = oa[1]; av[2] = oa[2]; rv = o_r; mv = o_m; }
+            }
             float ns[3] = {n[0], n[1], n[2]};   // (NRM) the shading normal: every cosine, both samplers' frames, the pdf
             if constexpr (NRM) {
 #pragma unroll
@@ -734,7 +770,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                         path_eval_st(wl, wo, n, av, rv, mv, ln, st, f, pdf_b);
                         pdf_b = trans_pdf(ln, st);
                     } else {
-                        path_eval(wl, wo, NRM ? ns : n, av, rv, mv, f, pdf_b);
+                        path_eval(wl, wo, NRM || PBR ? ns : n, av, rv, mv, f, pdf_b);   // (PBR) ns = n on the depth mesh
                     }
                     if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
                         float ts = FLT_MAX;
@@ -749,7 +785,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             }
             // BSDF sample: the next ray
             float wi[3], wgt[3], pdf_s;
-            if (OBJ && kind != 0) {
+            if (OBJ && kind != 0 && !pbr) {
                 int flags;
                 if (SMOOTH && smooth)
                     object_sample_shading(kind, op, n, ns, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
@@ -773,9 +809,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 for (int c = 0; c < 3; ++c) wgt[c] = f[c] > 0.0f ? f[c] * ip : 0.0f;
                 pdf_s = pt > 0.0f ? pt : 0.0f;
             } else {
-                path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, NRM ? ns : n, av, rv, mv, wi, wgt, pdf_s);
+                path_sample(rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wo, NRM || PBR ? ns : n, av, rv, mv, wi, wgt, pdf_s);
                 if (OBJ) prev_delta = false;
                 if (NRM && !(dot3(n, wi) > 0.0f)) break;   // sampled below the sheet: nothing is carried through it
+                if (PBR && pbr && !(dot3(n, wi) > 0.0f)) break;   // a reflection that leaves below the object's face carries nothing
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) thr[c] *= wgt[c];
@@ -1240,17 +1277,33 @@ bool object_valid(const MatpbrPathObject& ob) {
     }
     return false;
 }
-// `n_smooth` (nullable): where given, a kind may carry MATPBR_PATH_OBJECT_SMOOTH, and the flagged objects are counted
-bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, int* n_smooth = nullptr) {
+// the record of an object of kind MATPBR_PATH_BSDF_PBR: a in [0, 1], r in [0.07, 1], m in [0, 1] (a NaN fails every comparison)
+bool pbr_valid(const MatpbrPathObjectPbr& pr) {
+    for (int c = 0; c < 3; ++c)
+        if (!(pr.a[c] >= 0.0f && pr.a[c] <= 1.0f)) return false;
+    return pr.r >= 0.07f && pr.r <= 1.0f && pr.m >= 0.0f && pr.m <= 1.0f;
+}
+// `n_smooth` (nullable): where given, a kind may carry MATPBR_PATH_OBJECT_SMOOTH, and the flagged objects are counted.  `n_pbr`
+// (nullable): where given, a kind may be MATPBR_PATH_BSDF_PBR (its p[] is ignored), and those objects are counted; their records
+// are checked where `pbr` is given.
+bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, int* n_smooth = nullptr, int* n_pbr = nullptr,
+                  const MatpbrPathObjectPbr* pbr = nullptr) {
     if (n_objects < 0 || n_objects > MATPBR_PATH_MAX_OBJECTS || (n_objects > 0 && !objects)) return false;
     ot.n = n_objects;
     ot.min_id = INT32_MAX;
     if (n_smooth) *n_smooth = 0;
+    if (n_pbr) *n_pbr = 0;
     for (int k = 0; k < n_objects; ++k) {
         MatpbrPathObject plain = objects[k];
         if (n_smooth && (plain.kind & MATPBR_PATH_OBJECT_SMOOTH)) {
             plain.kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
             ++*n_smooth;
+        }
+        if (n_pbr && plain.kind == MATPBR_PATH_BSDF_PBR) {   // checked as a diffuse object of reflectance 0: the range alone
+            if (pbr && !pbr_valid(pbr[k])) return false;
+            plain.kind = MATPBR_PATH_BSDF_DIFFUSE;
+            plain.p[0] = plain.p[1] = plain.p[2] = 0.0f;
+            ++*n_pbr;
         }
         if (!object_valid(plain)) return false;
         for (int j = 0; j < k; ++j)   // ranges may not overlap
@@ -1442,13 +1495,14 @@ int matpbr_path_render(const void* nodes, const void* tris, const float* a, cons
                                       spp_per_launch, out, rays, stream, nullptr, 0);
 }
 
-// the five renders: `edit` (nullable) selects the transparency-editing instantiation, else `nrm` the shading-normal one, else
-// `obj_nrm` the smooth-object one, else n_objects > 0 the object one
+// the six renders: `edit` (nullable) selects the transparency-editing instantiation, else `nrm` the shading-normal one, else
+// `pbr` the PBR-object one (obj_nrm may be null then: no object is smooth), else `obj_nrm` the smooth-object one, else n_objects > 0
+// the object one
 static int render_common(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W, float fov_x_deg,
                          const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He, int We, int spp,
                          int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream, const ObjTable& ot,
                          int n_objects, const TransEdit* edit, const float* nrm = nullptr, const float* obj_nrm = nullptr,
-                         int32_t n_scene_tri = 0) {
+                         int32_t n_scene_tri = 0, const MatpbrPathObjectPbr* pbr = nullptr) {
     if (!nodes || !tris || !a || !r || !m || !env || !row_cdf || !col_cdf || !env_pdf || !out || H <= 0 || W <= 0 || He <= 0 || We <= 0 ||
         spp <= 0 || spp_per_launch <= 0 || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f))
         return MATPBR_PATH_ERR_INVALID_ARG;
@@ -1468,11 +1522,19 @@ static int render_common(const void* nodes, const void* tris, const float* a, co
     q.aspect = (float)W / (float)H;
     q.seed_hash = pcg_hash(seed);
     const dim3 grid((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((H + kTileY - 1) / kTileY));
+    PbrObjects pbo{};
+    if (pbr) {
+        pbo.t = ot;
+        pbo.nrm = obj_nrm;
+        pbo.n_scene_tri = n_scene_tri;
+        for (int k = 0; k < n_objects; ++k) pbo.pbr[k] = pbr[k];
+    }
     for (int s0 = 0; s0 < spp; s0 += spp_per_launch) {
         const int s1 = std::min(spp, s0 + spp_per_launch);
         const int first = s0 == 0 ? 1 : 0, last = s1 == spp ? 1 : 0;
         if (edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, *edit);
         else if (nrm) hipLaunchKernelGGL(path_kernel<ShadeNormals>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ShadeNormals{nrm});
+        else if (pbr) hipLaunchKernelGGL(path_kernel<PbrObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, pbo);
         else if (obj_nrm) hipLaunchKernelGGL(path_kernel<SmoothObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, SmoothObjects{ot, obj_nrm, n_scene_tri});
         else if (n_objects > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, ot);
         else hipLaunchKernelGGL(path_kernel<NoObjects>, grid, dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, s0, s1, first, last, NoObjects{});
@@ -1532,6 +1594,43 @@ int matpbr_path_object_sample_shading_host(const MatpbrPathObject* object, const
         object_sample_shading(object->kind, object->p, ng + 3 * k, ns + 3 * k, wo + 3 * k, u[3 * k], u[3 * k + 1], u[3 * k + 2], wi + 3 * k,
                               weight + 3 * k, pdf[k], fl);
         flags[k] = fl;
+    }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_render_objects_pbr(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                   float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                   int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                   const MatpbrPathObjectPbr* pbr) {
+    bool any_pbr = false;
+    for (int k = 0; objects && k >= 0 && k < n_objects && k < MATPBR_PATH_MAX_OBJECTS; ++k)
+        any_pbr = any_pbr || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR;
+    if (!any_pbr)
+        return matpbr_path_render_objects_normals(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
+                                                  spp_per_launch, out, rays, stream, objects, n_objects, obj_nrm, n_scene_tri);
+    ObjTable ot{};
+    int n_smooth = 0, n_pbr = 0;
+    if (!pbr || !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr) || n_scene_tri < 0 || n_scene_tri > INT32_MAX ||
+        (n_smooth > 0 && !obj_nrm))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int k = 0; k < n_objects; ++k)
+        if (objects[k].first_tri < n_scene_tri) return MATPBR_PATH_ERR_INVALID_ARG;
+    return render_common(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out,
+                         rays, stream, ot, n_objects, nullptr, nullptr, n_smooth > 0 ? obj_nrm : nullptr, (int32_t)n_scene_tri, pbr);
+}
+
+int matpbr_path_object_lookup_host(const MatpbrPathObject* objects, int n_objects, const MatpbrPathObjectPbr* pbr, const int32_t* ids, long N,
+                                   int32_t* kind, float* a, float* r, float* m) {
+    ObjTable ot{};
+    int n_smooth = 0, n_pbr = 0;
+    if (!ids || !kind || !a || !r || !m || N < 0 || !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr) || (n_pbr > 0 && !pbr))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        float p[3] = {0.0f, 0.0f, 0.0f};
+        a[3 * k] = a[3 * k + 1] = a[3 * k + 2] = 0.0f;
+        r[k] = m[k] = 0.0f;
+        kind[k] = object_lookup(ot, pbr, ids[k], p, a + 3 * k, r[k], m[k]);
     }
     return MATPBR_PATH_OK;
 }
@@ -1990,9 +2089,9 @@ dim3 denoise_grid(int H, int W) { return dim3((unsigned)((W + kDnTileX - 1) / kD
 // the arguments both feature entry points share, checked and packed
 bool features_args(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
                    const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom, FeatArgs& q, ObjTable& ot) {
-    int n_smooth = 0;
+    int n_smooth = 0, n_pbr = 0;   // an object of kind 3 is valid here: the features read its kind and its flag, never its record
     if (!nodes || !tris || !geom || !denoise_size_valid(H, W) || !(fov_x_deg > 0.0f && fov_x_deg < 180.0f) || n_scene_tri < 0 ||
-        n_scene_tri > INT32_MAX || !object_table(objects, n_objects, ot, &n_smooth) || (n_smooth > 0 && !obj_nrm))
+        n_scene_tri > INT32_MAX || !object_table(objects, n_objects, ot, &n_smooth, &n_pbr) || (n_smooth > 0 && !obj_nrm))
         return false;
     for (int k = 0; k < n_objects; ++k)
         if (objects[k].first_tri < n_scene_tri) return false;

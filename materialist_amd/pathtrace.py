@@ -29,12 +29,20 @@ TRI_BYTES = 48
 MAX_BVH_DEPTH = 40
 MAX_OBJECTS = 8
 BSDF_DIELECTRIC, BSDF_DIFFUSE = 1, 2
+BSDF_PBR = 3                   # MATPBR_PATH_BSDF_PBR: MatDiffBSDF on the constants of a PathObjectPbr record
+PBR_MIN_ROUGHNESS = 0.07       # the floor the project's roughness maps are clamped to (matpbr_shade.hpp, armhead.py)
+PBR_DEFAULTS = {"albedo": 0.8, "roughness": 0.5, "metallic": 0.0}
 OBJECT_SMOOTH = 0x100          # MATPBR_PATH_OBJECT_SMOOTH, OR-ed into PathObject.kind
 
 
 class PathObject(ctypes.Structure):
     """MatpbrPathObject (include/matpbr_path.h): the BSDF of one range of triangle ids."""
     _fields_ = [("kind", ctypes.c_int32), ("first_tri", ctypes.c_int32), ("n_tri", ctypes.c_int32), ("p", ctypes.c_float * 3)]
+
+
+class PathObjectPbr(ctypes.Structure):
+    """MatpbrPathObjectPbr (include/matpbr_path.h): albedo, roughness and metallic of one object of kind BSDF_PBR."""
+    _fields_ = [("a", ctypes.c_float * 3), ("r", ctypes.c_float), ("m", ctypes.c_float), ("reserved", ctypes.c_float * 3)]
 
 
 class PathTransEdit(ctypes.Structure):
@@ -65,6 +73,9 @@ SIGNATURES = {
     "matpbr_path_render_objects_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                            [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_long]),
     "matpbr_path_object_normal_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
+    "matpbr_path_render_objects_pbr": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
+                                       [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_long, _P]),
+    "matpbr_path_object_lookup_host": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_long, _P, _P, _P, _P]),
     "matpbr_path_object_sample_shading_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
     "matpbr_path_render_trans": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
                                  [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, _P, _P]),
@@ -95,7 +106,9 @@ SMOOTH_SYMBOLS = ("matpbr_path_render_objects_normals", "matpbr_path_object_norm
 # added at version 3 too (the denoiser)
 DENOISE_SYMBOLS = ("matpbr_path_features", "matpbr_path_features_host", "matpbr_path_denoise_prepare", "matpbr_path_denoise_prepare_host",
                    "matpbr_path_denoise_level", "matpbr_path_denoise_level_host", "matpbr_path_denoise_workspace_bytes", "matpbr_path_denoise")
-LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS
+# added at version 3 as well (PBR inserted objects)
+PBR_SYMBOLS = ("matpbr_path_render_objects_pbr", "matpbr_path_object_lookup_host")
+LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -126,7 +139,7 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        what = "the denoiser" if name in DENOISE_SYMBOLS else "smooth inserted objects"
+        what = "the denoiser" if name in DENOISE_SYMBOLS else "PBR inserted objects" if name in PBR_SYMBOLS else "smooth inserted objects"
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 
@@ -203,7 +216,9 @@ def env_sample_host(tables: Dict[str, object], u: np.ndarray):
 
 
 def object_bsdf(bsdf: dict) -> tuple:
-    """{"type": "dielectric", "int_ior", "ext_ior"} | {"type": "diffuse", "reflectance"} -> (kind, (p0, p1, p2)); ValueError when bad."""
+    """{"type": "dielectric", "int_ior", "ext_ior"} | {"type": "diffuse", "reflectance"} -> (kind, (p0, p1, p2));
+    {"type": "pbr", "albedo": scalar or 3 values (0.8), "roughness" (0.5), "metallic" (0)} -> (BSDF_PBR, (a0, a1, a2, r, m)).
+    ValueError when bad."""
     kind = bsdf.get("type") if isinstance(bsdf, dict) else None
     if kind == "dielectric":
         p = (float(bsdf.get("int_ior", 1.49)), float(bsdf.get("ext_ior", 1.000277)), 0.0)
@@ -215,7 +230,21 @@ def object_bsdf(bsdf: dict) -> tuple:
         if not ((rho >= 0) & (rho <= 1)).all():
             raise ValueError(f"diffuse: reflectance must lie in [0, 1], got {rho.tolist()}")
         return BSDF_DIFFUSE, tuple(float(x) for x in rho)
-    raise ValueError(f"object bsdf type must be 'dielectric' or 'diffuse', got {kind!r}")
+    if kind == "pbr":
+        alb = np.asarray(bsdf.get("albedo", PBR_DEFAULTS["albedo"]), dtype=np.float64)
+        if alb.shape not in ((), (1,), (3,)):
+            raise ValueError(f"pbr: albedo must be a scalar or 3 values, got shape {alb.shape}")
+        alb = np.broadcast_to(alb, (3,))
+        if not ((alb >= 0) & (alb <= 1)).all():
+            raise ValueError(f"pbr: albedo must lie in [0, 1], got {alb.tolist()}")
+        rough, metal = float(bsdf.get("roughness", PBR_DEFAULTS["roughness"])), float(bsdf.get("metallic", PBR_DEFAULTS["metallic"]))
+        # the bounds as the library sees them: the record is fp32 (0.07 is not a float; its nearest one lies above it)
+        if not np.float32(PBR_MIN_ROUGHNESS) <= np.float32(rough) <= 1:
+            raise ValueError(f"pbr: roughness must lie in [{PBR_MIN_ROUGHNESS}, 1], got {rough}")
+        if not 0 <= metal <= 1:
+            raise ValueError(f"pbr: metallic must lie in [0, 1], got {metal}")
+        return BSDF_PBR, (*(float(x) for x in alb), rough, metal)
+    raise ValueError(f"object bsdf type must be 'dielectric', 'diffuse' or 'pbr', got {kind!r}")
 
 
 def _corner_normals(k: int, ob: dict, Vo: np.ndarray, To: np.ndarray) -> np.ndarray:
@@ -233,21 +262,27 @@ def _corner_normals(k: int, ob: dict, Vo: np.ndarray, To: np.ndarray) -> np.ndar
     return (No / np.where(ln > 0, ln, 1.0)[:, None])[To]
 
 
-def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False):
+def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False, pbr: bool = False):
     """The depth mesh with the inserted meshes appended -> (V [Nv,3] float64, T [Nt,3] int32, [PathObject]).  Object k's triangles
     follow the scene's in the order given; its ids are its range of T.  An object may carry "normals" [Nv,3] (per vertex, outward, any
     length): it is smooth ("Smooth inserted objects"), its kind carries OBJECT_SMOOTH, and with `normals=True`
     a fourth value follows, the corner normals [Nt - scene's Nt, 3, 3] float32 of every inserted triangle (unit length, normalised in
-    fp64; zero for the objects without normals, which the kernel never reads), or None when no object is smooth."""
+    fp64; zero for the objects without normals, which the kernel never reads), or None when no object is smooth.  With `pbr=True`
+    one more value follows, the [n_objects] PathObjectPbr records (zero for the objects of another kind, which the kernel never
+    reads); a table entry of kind BSDF_PBR has p = 0."""
     V = [np.asarray(vertices, dtype=np.float64).reshape(-1, 3)]
     T = [np.asarray(triangles, dtype=np.int32).reshape(-1, 3)]
     if len(objects) > MAX_OBJECTS:
         raise ValueError(f"at most {MAX_OBJECTS} inserted objects, got {len(objects)}")
     table: List[PathObject] = []
     corner: List[np.ndarray] = []
+    records: List[PathObjectPbr] = []
     nv, nt = V[0].shape[0], T[0].shape[0]
     for k, ob in enumerate(objects):
         kind, p = object_bsdf(ob.get("bsdf"))
+        records.append(PathObjectPbr((ctypes.c_float * 3)(*p[:3]), p[3], p[4]) if kind == BSDF_PBR else PathObjectPbr())
+        if kind == BSDF_PBR:
+            p = (0.0, 0.0, 0.0)
         Vo = np.asarray(ob["vertices"], dtype=np.float64)
         To = np.asarray(ob["triangles"])
         if Vo.ndim != 2 or Vo.shape[1] != 3 or To.ndim != 2 or To.shape[1] != 3 or To.shape[0] == 0:
@@ -265,16 +300,42 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
         T.append((To.astype(np.int64) + nv).astype(np.int32))
         table.append(PathObject(kind, nt, To.shape[0], (ctypes.c_float * 3)(*p)))
         nv, nt = nv + Vo.shape[0], nt + To.shape[0]
-    if not normals:
-        return np.concatenate(V), np.concatenate(T), table
-    smooth = any(t.kind & OBJECT_SMOOTH for t in table)
-    return np.concatenate(V), np.concatenate(T), table, (np.ascontiguousarray(np.concatenate(corner), dtype=np.float32) if smooth else None)
+    out = (np.concatenate(V), np.concatenate(T), table)
+    if normals:
+        smooth = any(t.kind & OBJECT_SMOOTH for t in table)
+        out += (np.ascontiguousarray(np.concatenate(corner), dtype=np.float32) if smooth else None,)
+    return out + ((records,) if pbr else ())
+
+
+def object_lookup_host(table: Sequence[PathObject], records: Optional[Sequence[PathObjectPbr]], ids: np.ndarray):
+    """The kernel's table lookup on the CPU: `merge_objects`' table and PBR records, triangle ids [N] -> (kind [N] int32, 0 where the
+    id lies in no range, the smooth flag kept; a [N,3], r [N], m [N]: a PBR object's record, 0 for every other id)."""
+    I = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    tab = (PathObject * len(table))(*table) if len(table) else None
+    rec = (PathObjectPbr * len(records))(*records) if records is not None and len(records) else None
+    if rec is not None and len(records) != len(table):
+        raise ValueError(f"one record per object: {len(table)} objects, {len(records)} records")
+    kind = np.empty(I.size, np.int32)
+    a, r, m = np.empty((I.size, 3), np.float32), np.empty(I.size, np.float32), np.empty(I.size, np.float32)
+    check(symbol("matpbr_path_object_lookup_host")(ctypes.cast(tab, _P) if tab is not None else None, len(table),
+                                                   ctypes.cast(rec, _P) if rec is not None else None, _ptr(I), I.size, _ptr(kind), _ptr(a), _ptr(r),
+                                                   _ptr(m)), "matpbr_path_object_lookup_host")
+    return kind, a, r, m
+
+
+def _sampled_bsdf(bsdf: dict) -> tuple:
+    """`object_bsdf` for the object samplers' host twins, which know the dielectric and the diffuse BSDF (a PBR object is sampled by the
+    depth mesh's device routines, which have no host twin)."""
+    kind, p = object_bsdf(bsdf)
+    if kind == BSDF_PBR:
+        raise ValueError("the object samplers on the CPU know 'dielectric' and 'diffuse'; a 'pbr' object samples with MatDiffBSDF's device code")
+    return kind, p
 
 
 def object_sample_host(bsdf: dict, n: np.ndarray, wo: np.ndarray, u: np.ndarray):
     """The kernel's BSDF sampler of an inserted object on the CPU: outward face normal n [3], wo [N,3], u [N,3] (dims 6, 7, 8) ->
     (wi [N,3], weight [N,3], pdf [N], flags [N]: bit 0 delta, bit 1 transmitted)."""
-    kind, p = object_bsdf(bsdf)
+    kind, p = _sampled_bsdf(bsdf)
     ob = PathObject(kind, 0, 0, (ctypes.c_float * 3)(*p))
     nn = np.ascontiguousarray(n, dtype=np.float32).reshape(3)
     WO = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
@@ -309,7 +370,7 @@ def object_sample_shading_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: n
     """`object_sample_host` at vertices with a face normal ng [N,3] (or [3]) and a shading normal ns [N,3] (or [3]), as the kernel
     samples a smooth object: the third fallback, the sample about ns, the dielectric's redo about ng, weight 0 below ng ->
     (wi [N,3], weight [N,3], pdf [N], flags [N])."""
-    kind, p = object_bsdf(bsdf)
+    kind, p = _sampled_bsdf(bsdf)
     ob = PathObject(kind, 0, 0, (ctypes.c_float * 3)(*p))
     WO = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
     U = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 3)
@@ -523,8 +584,10 @@ class PathTracer:
     The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
     `objects`: meshes inserted into the scene ("Inserted objects"), in the same frame, outward winding, a list
     of {"vertices" [Nv,3], "triangles" [Nt,3], "bsdf": {"type": "dielectric", "int_ior": 1.49, "ext_ior": 1.000277} or
-    {"type": "diffuse", "reflectance": (r, g, b)}} and optionally "normals" [Nv,3] (per vertex, outward): with them the object shades
-    smooth, with the normals interpolated at each hit; without them flat.  A tracer with objects renders forward only."""
+    {"type": "diffuse", "reflectance": (r, g, b)} or {"type": "pbr", "albedo": (r, g, b), "roughness": r, "metallic": m} (the depth
+    mesh's own BSDF on constants; DESIGN.md section 1.4, "PBR inserted objects")} and optionally "normals" [Nv,3] (per vertex,
+    outward): with them the object shades smooth, with the normals interpolated at each hit; without them flat.  A tracer with
+    objects renders forward only."""
 
     def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
                  objects: Optional[Sequence[dict]] = None):
@@ -534,11 +597,16 @@ class PathTracer:
         self.objects = None
         self.obj_nrm: Optional[torch.Tensor] = None   # corner normals of the inserted triangles, when some object is smooth
         self.n_scene_tris = n_scene
-        n_smooth = 0
+        self.pbr = None                               # the PathObjectPbr records, when some object is of kind BSDF_PBR
+        n_smooth = n_pbr = 0
         if objects:
-            vertices, triangles, table, corner = merge_objects(vertices, triangles, objects, normals=True)
+            vertices, triangles, table, corner, records = merge_objects(vertices, triangles, objects, normals=True, pbr=True)
             self.objects = (PathObject * len(table))(*table)
             n_smooth = sum(1 for t in table if t.kind & OBJECT_SMOOTH)
+            n_pbr = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_PBR)
+            if n_pbr:
+                symbol("matpbr_path_render_objects_pbr")
+                self.pbr = (PathObjectPbr * len(records))(*records)
             if corner is not None:
                 symbol("matpbr_path_render_objects_normals")
                 self.obj_nrm = torch.from_numpy(corner).to(self.device)
@@ -550,6 +618,7 @@ class PathTracer:
         self.stats["n_objects"] = len(self.objects) if self.objects is not None else 0
         self.stats["n_object_tris"] = self.stats["n_tris"] - n_scene
         self.stats["n_smooth_objects"] = n_smooth
+        self.stats["n_pbr_objects"] = n_pbr
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -613,6 +682,11 @@ class PathTracer:
             check(lib.matpbr_path_render_normals(*args, nrm.data_ptr()), "matpbr_path_render_normals")
         elif self.objects is None:
             check(lib.matpbr_path_render(*args), "matpbr_path_render")
+        elif self.pbr is not None:
+            check(symbol("matpbr_path_render_objects_pbr", lib)(*args, ctypes.cast(self.objects, _P), len(self.objects),
+                                                                self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,
+                                                                self.n_scene_tris, ctypes.cast(self.pbr, _P)),
+                  "matpbr_path_render_objects_pbr")
         elif self.obj_nrm is None:
             check(lib.matpbr_path_render_objects(*args, ctypes.cast(self.objects, _P), len(self.objects)), "matpbr_path_render_objects")
         else:

@@ -221,14 +221,17 @@ def _check_denoise(denoise: str, integrator: str, spp: int) -> bool:
     return True
 
 
+_PBR_ALBEDO = 0.8   # pathtrace.PBR_DEFAULTS["albedo"]: what `object_bsdf` gives a "pbr" dict without one
+
+
 def albedo_guide(geom: torch.Tensor, albedo: torch.Tensor, bsdfs=()) -> torch.Tensor:
     """The denoiser's albedo guide [H,W,3] from the features' ids: the albedo map as rendered where the camera ray hits the depth mesh
-    (id 0), a diffuse object's reflectance, 1 on glass, 0 where it hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
+    (id 0), a diffuse object's reflectance, a PBR object's albedo, 1 on glass, 0 where it hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
     ids = geom[..., 7]
     guide = albedo.to(geom.device, torch.float32).reshape(geom.shape[0], geom.shape[1], 3).clone()
     guide[ids < 0] = 0.0
     for k, b in enumerate(bsdfs):
-        value = b["reflectance"] if b["type"] == "diffuse" else (1.0, 1.0, 1.0)
+        value = b["reflectance"] if b["type"] == "diffuse" else b.get("albedo", _PBR_ALBEDO) if b["type"] == "pbr" else (1.0, 1.0, 1.0)
         guide[ids == 1 + k] = torch.tensor([float(x) for x in np.broadcast_to(np.asarray(value, np.float64), (3,))], device=geom.device)
     return guide
 
@@ -303,9 +306,61 @@ def find_envmap_oi(save_name: str, env_path: Optional[str], input_path: Optional
     raise ValueError("No envmap found")
 
 
+OI_SCENE_MAX_OBJECTS = 8                              # pathtrace.MAX_OBJECTS
+
+
+def load_oi_scene(path: str) -> List[dict]:
+    """An object list file for `render_oi(objects_file=...)`: JSON that holds only settings,
+    {"objects": [{"ply": "chrome_ball.ply", "bsdf": {"type": "pbr", "albedo": [0.95, 0.93, 0.88], "roughness": 0.1, "metallic": 1.0},
+    "normals": "vertex"}, ...]}, at most 8 objects.  "ply" is relative to the file; "bsdf" is any of PathTracer's three types
+    (dielectric, diffuse, pbr); "normals" is "flat" (default) or "vertex" (the file's normals if it has them, else
+    `mesh.angle_weighted_normals`) -> [{"ply": absolute path, "bsdf", "normals"}], nothing read yet but the list.  ValueError naming
+    the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
+    import json
+
+    from .pathtrace import object_bsdf
+
+    try:
+        with open(path) as f:
+            doc = json.load(f)
+    except (OSError, ValueError) as e:
+        raise ValueError(f"{path}: cannot read the object list: {e}") from None
+    if not isinstance(doc, dict) or not isinstance(doc.get("objects"), list):
+        raise ValueError(f'{path}: the object list must be {{"objects": [...]}}')
+    extra = sorted(set(doc) - {"objects"})
+    if extra:
+        raise ValueError(f"{path}: unknown key {extra[0]!r} (known: 'objects')")
+    if not doc["objects"]:
+        raise ValueError(f"{path}: the object list is empty")
+    if len(doc["objects"]) > OI_SCENE_MAX_OBJECTS:
+        raise ValueError(f"{path}: at most {OI_SCENE_MAX_OBJECTS} objects, got {len(doc['objects'])}")
+    out = []
+    for k, ob in enumerate(doc["objects"]):
+        where = f"{path}: objects[{k}]"
+        if not isinstance(ob, dict):
+            raise ValueError(f"{where} must be an object with 'ply' and 'bsdf'")
+        extra = sorted(set(ob) - {"ply", "bsdf", "normals"})
+        if extra:
+            raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals')")
+        if not isinstance(ob.get("ply"), str) or not ob["ply"]:
+            raise ValueError(f"{where}: 'ply' must name a mesh file")
+        ply = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob["ply"]))
+        if not os.path.isfile(ply):
+            raise ValueError(f"{where}: no such ply: {ply}")
+        try:
+            object_bsdf(ob.get("bsdf"))
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"{where}: bad bsdf: {e}") from None
+        normals = ob.get("normals", "flat")
+        if normals not in ("flat", "vertex"):
+            raise ValueError(f"{where}: 'normals' must be 'flat' or 'vertex', got {normals!r}")
+        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals})
+    return out
+
+
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
-              denoise: str = "off") -> str:
+              denoise: str = "off", objects_file: Optional[str] = None) -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -315,15 +370,20 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     averaged.  The reference renders spp 32 x 10 and denoises each with OptiX, which stays out: by default the
     samples do the denoiser's work (spp 64 x 10).  `denoise="atrous"` (even `spp`) runs the project's own filter instead: each of
     the `n_iter` renders becomes two of spp / 2, seeds seed + 2 i and seed + 2 i + 1, summed into two half buffers, and one a-trous
-    pass runs over them ("Denoiser"); behind glass only its colour term guides."""
+    pass runs over them ("Denoiser"); behind glass only its colour term guides.  `objects_file`: an object
+    list (`load_oi_scene`) whose meshes are inserted instead, each with its own BSDF (dielectric, diffuse or pbr) and its own
+    normals; with it oi.ply and oi2.ply are not looked for and `object_normals` is ignored.  The output names are the same."""
     from . import mesh as _mesh
 
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
-    plys = [os.path.join(scene_dir, "oi.ply"), os.path.join(scene_dir, "oi2.ply")]
-    bsdfs = [{"type": "dielectric", "int_ior": OI_INT_IOR, "ext_ior": OI_EXT_IOR}, {"type": "diffuse", "reflectance": (OI_REFLECTANCE,) * 3}]
-    have = [(p, b) for p, b in zip(plys, bsdfs) if os.path.exists(p)]
-    if not have:
-        raise FileNotFoundError(f"object insertion needs {plys[0]} (glass) or {plys[1]} (diffuse); neither exists")
+    if objects_file is not None:
+        have = [(e["ply"], e["bsdf"], e["normals"]) for e in load_oi_scene(objects_file)]
+    else:
+        plys = [os.path.join(scene_dir, "oi.ply"), os.path.join(scene_dir, "oi2.ply")]
+        bsdfs = [{"type": "dielectric", "int_ior": OI_INT_IOR, "ext_ior": OI_EXT_IOR}, {"type": "diffuse", "reflectance": (OI_REFLECTANCE,) * 3}]
+        have = [(p, b, object_normals) for p, b in zip(plys, bsdfs) if os.path.exists(p)]
+        if not have:
+            raise FileNotFoundError(f"object insertion needs {plys[0]} (glass) or {plys[1]} (diffuse); neither exists")
     if n_iter < 1:
         raise ValueError(f"n_iter must be at least 1, got {n_iter}")
     if object_normals not in ("flat", "vertex"):
@@ -331,10 +391,10 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     atrous = _check_denoise(denoise, "path", spp)
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
-    for p, b in have:
+    for p, b, normals in have:
         V, T, Nn = _mesh.read_ply_any(p, normals=True)
         objects.append({"vertices": V, "triangles": T, "bsdf": b})
-        if object_normals == "vertex":
+        if normals == "vertex":
             objects[-1]["normals"] = Nn if Nn is not None else _mesh.angle_weighted_normals(V, T)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
     pt = _path_tracer(scene_dir, save_name, mat, device, objects)
@@ -343,7 +403,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     if atrous:
         geom = pt.features()
         half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs)
-        img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], [b for _, b in have]))
+        img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], [b for _, b, _ in have]))
     else:
         img = torch.zeros_like(mat["albedo"])
         for i in range(n_iter):

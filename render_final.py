@@ -12,7 +12,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter, description="re-render an optimised scene under new lighting")
     ap.add_argument("--env_path", required=False, default=None, type=str)
     ap.add_argument("--save_name", required=True, type=str)
-    ap.add_argument("--mode", required=True, type=str, help="real, rolling, or oi (object insertion: <scene>/oi.ply as glass and <scene>/oi2.ply as a diffuse object, path traced)")
+    ap.add_argument("--mode", required=True, type=str, help="real, rolling, or oi (object insertion: <scene>/oi.ply as glass and <scene>/oi2.ply as a diffuse object, or the objects of --oi_scene, path traced)")
     ap.add_argument("--input_path", required=False, default=None, type=str)
     ap.add_argument("--save_path", required=False, default=None, type=str)
     ap.add_argument("--frames", type=int, default=36)
@@ -36,6 +36,10 @@ def parse_args(argv=None):
     ap.add_argument("--oi_iters", type=int, default=10, help="--mode oi: renders averaged (seeds seed, seed + 1, ...)")
     ap.add_argument("--oi_normals", choices=["flat", "vertex"], default="flat",
                     help="--mode oi: flat = face normals; vertex = each .ply shades smooth with its vertex normals (angle-weighted ones if it has none)")
+    ap.add_argument("--oi_scene", type=str, default=None, metavar="FILE.json",
+                    help='--mode oi: an object list, {"objects": [{"ply": path relative to the file, "bsdf": {"type": "pbr", "albedo": [r, g, b], '
+                         '"roughness": r, "metallic": m} (or a "dielectric" or "diffuse" one), "normals": "flat" or "vertex"}, ...]}, at most 8 '
+                         "objects; with it <scene>/oi.ply and <scene>/oi2.ply are not looked for and --oi_normals is ignored")
     ap.add_argument("--oi_max_depth", type=int, default=16, help="--mode oi: Mitsuba's max_depth (a camera path through glass needs 5 to see light)")
     a = ap.parse_args(argv)
     if a.shading_normals == "map" and (a.integrator != "path" or a.mode == "oi"):
@@ -62,7 +66,7 @@ def main(argv=None):
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
         print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
-                                                 object_normals=a.oi_normals, denoise=a.denoise))
+                                                 object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene))
     else:
         raise ValueError("Invalid mode")
 
