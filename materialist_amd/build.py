@@ -78,7 +78,8 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 # digest profiles/pmc_traffic.json is tied to -- stay untouched.  It includes matpbr_device.hpp for the BRDF arithmetic.
 PATH_LIB_PATH = os.path.join(_HERE, "libmatpbr_path.so")
 PATH_SOURCES = ["matpbr_path.hip"]
-PATH_HEADERS = [os.path.join("..", "..", "include", "matpbr_path.h"), "matpbr_device.hpp"]
+PATH_HEADERS = [os.path.join("..", "..", "include", "matpbr_path.h"), "matpbr_device.hpp", "path_bvh.hpp", "path_shading.hpp", "path_objects.hpp",
+                "path_denoise.hpp"]
 
 
 def path_is_stale() -> bool:

@@ -56,6 +56,11 @@ class PathDenoise(ctypes.Structure):
                 ("sigma_c", ctypes.c_float)]
 
 
+# the 18 common arguments of a render or a backward pass (`PathTracer._frame`); a render then takes out, rays, stream, a backward pass
+# d_out, d_a, d_r, d_m, d_env, workspace, workspace_bytes, rays, stream; an entry point's own arguments follow
+_FRAME = [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 + [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int]
+_RENDER = _FRAME + [_P] * 3
+_RENDER_BWD = _FRAME + [_P] * 6 + [ctypes.c_size_t, _P, _P]
 SIGNATURES = {
     "matpbr_path_version": (ctypes.c_int, []),
     "matpbr_path_strerror": (ctypes.c_char_p, [ctypes.c_int]),
@@ -65,31 +70,23 @@ SIGNATURES = {
     "matpbr_path_trace_host": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_long, ctypes.c_float, ctypes.c_float, _P, _P]),
     "matpbr_path_env_tables": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "matpbr_path_env_sample_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P]),
-    "matpbr_path_render": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                           [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P]),
-    "matpbr_path_render_objects": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                                   [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int]),
+    "matpbr_path_render": (ctypes.c_int, _RENDER),
+    "matpbr_path_render_objects": (ctypes.c_int, _RENDER + [_P, ctypes.c_int]),
     "matpbr_path_object_sample_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 4),
-    "matpbr_path_render_objects_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                                           [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_long]),
+    "matpbr_path_render_objects_normals": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long]),
     "matpbr_path_object_normal_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
-    "matpbr_path_render_objects_pbr": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                                       [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_long, _P]),
+    "matpbr_path_render_objects_pbr": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P]),
     "matpbr_path_object_lookup_host": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_long, _P, _P, _P, _P]),
     "matpbr_path_object_sample_shading_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
-    "matpbr_path_render_trans": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                                 [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P, _P, _P]),
+    "matpbr_path_render_trans": (ctypes.c_int, _RENDER + [_P, _P, _P]),
     "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
     "matpbr_path_trans_lookup_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
     "matpbr_path_render_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
-    "matpbr_path_render_bwd": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                               [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P]),
-    "matpbr_path_render_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                                   [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, _P, _P, _P, _P]),
+    "matpbr_path_render_bwd": (ctypes.c_int, _RENDER_BWD),
+    "matpbr_path_render_normals": (ctypes.c_int, _RENDER + [_P]),
     "matpbr_path_eval_normal_grad_host": (ctypes.c_int, [_P] * 7 + [ctypes.c_long, _P]),
     "matpbr_path_render_bwd_normals_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
-    "matpbr_path_render_bwd_normals": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 +
-                                       [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int] + [_P] * 6 + [ctypes.c_size_t, _P, _P, _P, _P]),
+    "matpbr_path_render_bwd_normals": (ctypes.c_int, _RENDER_BWD + [_P, _P]),
     "matpbr_path_features": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_features_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P]),
     "matpbr_path_denoise_prepare": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
@@ -154,6 +151,32 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _rows(x, cols: int) -> np.ndarray:
+    """`x` as contiguous float32 rows: [N, cols], or [N] for cols = 1."""
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    return a.reshape(-1) if cols == 1 else a.reshape(-1, cols)
+
+
+def _same_rows(refusal: str, first: np.ndarray, *rest: np.ndarray) -> int:
+    """The row count the arrays share; ValueError(refusal) when they do not."""
+    if any(x.shape[0] != first.shape[0] for x in rest):
+        raise ValueError(refusal)
+    return first.shape[0]
+
+
+def _table_ptrs(table, records=None) -> tuple:
+    """(the PathObject table, its PathObjectPbr records) as the C ABI takes them: a pointer, or None for a missing or empty one.
+    ValueError unless there is one record per object."""
+    def ptr(kind, xs):
+        if xs is None or not len(xs):
+            return None
+        return ctypes.cast(xs if isinstance(xs, ctypes.Array) else (kind * len(xs))(*xs), _P)
+
+    if records is not None and len(records) and len(records) != len(table):
+        raise ValueError(f"one record per object: {len(table)} objects, {len(records)} records")
+    return ptr(PathObject, table), ptr(PathObjectPbr, records)
+
+
 def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional[int] = None) -> Dict[str, object]:
     """Host BVH of a triangle mesh: {"nodes" uint8 [n_nodes*64], "tris" uint8 [T*48], "n_nodes", "depth", "n_leaves", "build_s"}.
     `n_scene_tri`: triangles from this index on belong to inserted meshes and keep their winding (`matpbr_path_bvh_build_objects`);
@@ -181,8 +204,7 @@ def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional
 
 def trace_host(bvh: Dict[str, object], origins: np.ndarray, dirs: np.ndarray, tmin: float = 0.0, tmax: float = 3.0e38):
     """Closest hit on the CPU with the kernel's routine -> (t [N] float32, tmax where missed; triangle index [N] int32, -1 = miss)."""
-    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
-    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    o, d = _rows(origins, 3), _rows(dirs, 3)
     t = np.empty(o.shape[0], np.float32)
     k = np.empty(o.shape[0], np.int32)
     check(load().matpbr_path_trace_host(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), _ptr(o), _ptr(d), o.shape[0], tmin, tmax, _ptr(t), _ptr(k)),
@@ -205,7 +227,7 @@ def env_tables(env: np.ndarray) -> Dict[str, object]:
 
 def env_sample_host(tables: Dict[str, object], u: np.ndarray):
     """The render's emitter sampler on the CPU: u [N,4] -> (dir [N,3], pdf [N], texel [N] = row*We + col)."""
-    U = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 4)
+    U = _rows(u, 4)
     He, We = tables["pdf"].shape
     d = np.empty((U.shape[0], 3), np.float32)
     p = np.empty(U.shape[0], np.float32)
@@ -311,15 +333,11 @@ def object_lookup_host(table: Sequence[PathObject], records: Optional[Sequence[P
     """The kernel's table lookup on the CPU: `merge_objects`' table and PBR records, triangle ids [N] -> (kind [N] int32, 0 where the
     id lies in no range, the smooth flag kept; a [N,3], r [N], m [N]: a PBR object's record, 0 for every other id)."""
     I = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
-    tab = (PathObject * len(table))(*table) if len(table) else None
-    rec = (PathObjectPbr * len(records))(*records) if records is not None and len(records) else None
-    if rec is not None and len(records) != len(table):
-        raise ValueError(f"one record per object: {len(table)} objects, {len(records)} records")
+    tab, rec = _table_ptrs(table, records)
     kind = np.empty(I.size, np.int32)
     a, r, m = np.empty((I.size, 3), np.float32), np.empty(I.size, np.float32), np.empty(I.size, np.float32)
-    check(symbol("matpbr_path_object_lookup_host")(ctypes.cast(tab, _P) if tab is not None else None, len(table),
-                                                   ctypes.cast(rec, _P) if rec is not None else None, _ptr(I), I.size, _ptr(kind), _ptr(a), _ptr(r),
-                                                   _ptr(m)), "matpbr_path_object_lookup_host")
+    check(symbol("matpbr_path_object_lookup_host")(tab, len(table), rec, _ptr(I), I.size, _ptr(kind), _ptr(a), _ptr(r), _ptr(m)),
+          "matpbr_path_object_lookup_host")
     return kind, a, r, m
 
 
@@ -338,11 +356,8 @@ def object_sample_host(bsdf: dict, n: np.ndarray, wo: np.ndarray, u: np.ndarray)
     kind, p = _sampled_bsdf(bsdf)
     ob = PathObject(kind, 0, 0, (ctypes.c_float * 3)(*p))
     nn = np.ascontiguousarray(n, dtype=np.float32).reshape(3)
-    WO = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
-    U = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 3)
-    if U.shape[0] != WO.shape[0]:
-        raise ValueError(f"wo and u must have the same rows, got {WO.shape[0]} and {U.shape[0]}")
-    N = WO.shape[0]
+    WO, U = _rows(wo, 3), _rows(u, 3)
+    N = _same_rows(f"wo and u must have the same rows, got {WO.shape[0]} and {U.shape[0]}", WO, U)
     wi, w = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
     pdf, flags = np.empty(N, np.float32), np.empty(N, np.int32)
     check(load().matpbr_path_object_sample_host(ctypes.cast(ctypes.byref(ob), _P), _ptr(nn), _ptr(WO), _ptr(U), N, _ptr(wi), _ptr(w), _ptr(pdf),
@@ -355,11 +370,8 @@ def object_normal_host(tri: np.ndarray, nrm: np.ndarray, o: np.ndarray, d: np.nd
     [N,3,3], rays o, d [N,3] -> (u [N], v [N], ns [N,3]); ns after the first two fallbacks (not finite or zero, ns . ng <= 0)."""
     TR = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1, 3, 3)
     NR = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3, 3)
-    O = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
-    D = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
-    N = TR.shape[0]
-    if any(x.shape[0] != N for x in (NR, O, D)):
-        raise ValueError("tri, nrm, o and d must have the same rows")
+    O, D = _rows(o, 3), _rows(d, 3)
+    N = _same_rows("tri, nrm, o and d must have the same rows", TR, NR, O, D)
     u, v, ns = np.empty(N, np.float32), np.empty(N, np.float32), np.empty((N, 3), np.float32)
     check(symbol("matpbr_path_object_normal_host")(_ptr(TR), _ptr(NR), _ptr(O), _ptr(D), N, _ptr(u), _ptr(v), _ptr(ns)),
           "matpbr_path_object_normal_host")
@@ -372,11 +384,8 @@ def object_sample_shading_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: n
     (wi [N,3], weight [N,3], pdf [N], flags [N])."""
     kind, p = _sampled_bsdf(bsdf)
     ob = PathObject(kind, 0, 0, (ctypes.c_float * 3)(*p))
-    WO = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
-    U = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 3)
-    N = WO.shape[0]
-    if U.shape[0] != N:
-        raise ValueError(f"wo and u must have the same rows, got {N} and {U.shape[0]}")
+    WO, U = _rows(wo, 3), _rows(u, 3)
+    N = _same_rows(f"wo and u must have the same rows, got {WO.shape[0]} and {U.shape[0]}", WO, U)
     NG = np.ascontiguousarray(np.broadcast_to(np.asarray(ng, dtype=np.float32).reshape(-1, 3), (N, 3)))
     NS = np.ascontiguousarray(np.broadcast_to(np.asarray(ns, dtype=np.float32).reshape(-1, 3), (N, 3)))
     wi, w = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
@@ -403,12 +412,8 @@ def trans_eval_host(n: np.ndarray, wo: np.ndarray, wi: np.ndarray, a: np.ndarray
     """The kernel's masked-branch BSDF (TransBSDF.eval_brdf where the mask is set) on the CPU: n, wo, wi, a, bg [N,3], r, m [N] ->
     (f [N,3] with its cosine, pdf [N])."""
     ed = trans_edit(ior, spec_trans)
-    v3 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
-    v1 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
-    nn, WO, WI, A, BG, R, M = v3(n), v3(wo), v3(wi), v3(a), v3(bg), v1(r), v1(m)
-    N = nn.shape[0]
-    if any(x.shape[0] != N for x in (WO, WI, A, BG, R, M)):
-        raise ValueError("n, wo, wi, a, r, m and bg must have the same rows")
+    nn, WO, WI, A, BG, R, M = _rows(n, 3), _rows(wo, 3), _rows(wi, 3), _rows(a, 3), _rows(bg, 3), _rows(r, 1), _rows(m, 1)
+    N = _same_rows("n, wo, wi, a, r, m and bg must have the same rows", nn, WO, WI, A, BG, R, M)
     f, pdf = np.empty((N, 3), np.float32), np.empty(N, np.float32)
     check(load().matpbr_path_trans_eval_host(ctypes.cast(ctypes.byref(ed), _P), _ptr(nn), _ptr(WO), _ptr(WI), _ptr(A), _ptr(R), _ptr(M), _ptr(BG),
                                              N, _ptr(f), _ptr(pdf)), "matpbr_path_trans_eval_host")
@@ -420,11 +425,8 @@ def trans_lookup_host(p: np.ndarray, n: np.ndarray, wo: np.ndarray, H: int, W: i
     """The kernel's texel lookups of a transparency edit on the CPU: hit points p, face normals n, wo [N,3] -> (texel [N] of the
     point itself, texel [N] the background is read at; row * W + col)."""
     ed = trans_edit(ior, 0.0, refract_distance)
-    v3 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
-    P, nn, WO = v3(p), v3(n), v3(wo)
-    N = P.shape[0]
-    if nn.shape[0] != N or WO.shape[0] != N:
-        raise ValueError("p, n and wo must have the same rows")
+    P, nn, WO = _rows(p, 3), _rows(n, 3), _rows(wo, 3)
+    N = _same_rows("p, n and wo must have the same rows", P, nn, WO)
     tp, tq = np.empty(N, np.int32), np.empty(N, np.int32)
     check(load().matpbr_path_trans_lookup_host(ctypes.cast(ctypes.byref(ed), _P), _ptr(P), _ptr(nn), _ptr(WO), N, int(H), int(W), float(fov_x_deg),
                                                _ptr(tp), _ptr(tq)), "matpbr_path_trans_lookup_host")
@@ -434,12 +436,8 @@ def trans_lookup_host(p: np.ndarray, n: np.ndarray, wo: np.ndarray, H: int, W: i
 def eval_normal_grad_host(n: np.ndarray, wo: np.ndarray, wi: np.ndarray, a: np.ndarray, r: np.ndarray, m: np.ndarray, g: np.ndarray):
     """d (g . f) / d n of the BSDF value on the CPU, composed and gated by the routine the backward kernel runs: n, wo, wi, a, g [N,3],
     r, m [N] -> d_n [N,3] = gl wi + gv wo + gh h, with respect to n's components as free variables."""
-    v3 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
-    v1 = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
-    nn, WO, WI, A, G, R, M = v3(n), v3(wo), v3(wi), v3(a), v3(g), v1(r), v1(m)
-    N = nn.shape[0]
-    if any(x.shape[0] != N for x in (WO, WI, A, G, R, M)):
-        raise ValueError("n, wo, wi, a, r, m and g must have the same rows")
+    nn, WO, WI, A, G, R, M = _rows(n, 3), _rows(wo, 3), _rows(wi, 3), _rows(a, 3), _rows(g, 3), _rows(r, 1), _rows(m, 1)
+    N = _same_rows("n, wo, wi, a, r, m and g must have the same rows", nn, WO, WI, A, G, R, M)
     d_n = np.empty((N, 3), np.float32)
     check(load().matpbr_path_eval_normal_grad_host(_ptr(nn), _ptr(WO), _ptr(WI), _ptr(A), _ptr(R), _ptr(M), _ptr(G), N, _ptr(d_n)),
           "matpbr_path_eval_normal_grad_host")
@@ -483,12 +481,11 @@ def features_host(bvh: Dict[str, object], H: int, W: int, fov_x_deg: float = 35.
     H, W = int(H), int(W)
     if H < 1 or W < 1:
         raise ValueError(f"H and W must be positive, got {H} x {W}")
-    table = (PathObject * len(objects))(*objects) if objects else None
+    table, _ = _table_ptrs(objects)
     cn = None if obj_nrm is None else np.array(obj_nrm, dtype=np.float32, order="C", copy=True)
     nm = None if normal is None else _host_image(normal, (H, W, 3), "normal")
     geom = np.empty((H, W, 8), np.float32)
-    check(symbol("matpbr_path_features_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), H, W, float(fov_x_deg),
-                                              ctypes.cast(table, _P) if table is not None else None, len(objects) if objects else 0,
+    check(symbol("matpbr_path_features_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), H, W, float(fov_x_deg), table, len(objects) if objects else 0,
                                               _ptr(cn) if cn is not None else None, int(n_scene_tri), _ptr(nm) if nm is not None else None,
                                               _ptr(geom)), "matpbr_path_features_host")
     return geom
@@ -649,6 +646,12 @@ class PathTracer:
                 raise ValueError(f"envmap {tuple(env.shape)} does not match its tables {tuple(pdf.shape)}")
         return a, r, m, env, row, col, pdf
 
+    def _frame(self, a, r, m, env, row, col, pdf, spp, max_depth, seed, spp_per_launch) -> tuple:
+        """The 18 common arguments of a render or a backward pass (SIGNATURES' _FRAME) over what `_inputs` returned."""
+        return (self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), self.H, self.W, self.fov,
+                env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]),
+                int(spp), int(max_depth), int(seed) & 0xFFFFFFFF, int(spp_per_launch))
+
     def _normal(self, normal, what: str) -> torch.Tensor:
         """The shading-normal map [H,W,3] on the device, used as given; `what` names the caller in the refusals."""
         if self.objects is not None:
@@ -669,29 +672,25 @@ class PathTracer:
         map ("Shading normals"); None shades with the face normals.  A tracer with objects refuses it."""
         H, W, dev = self.H, self.W, self.device
         nrm = self._normal(normal, "render") if normal is not None else None
-        a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
+        inputs = self._inputs(albedo, roughness, metallic, envmap, tables)
         if out is None:
             out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         lib = load()
-        args = (self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
-                env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]),
-                int(spp), int(max_depth), int(seed) & 0xFFFFFFFF, int(spp_per_launch), out.data_ptr(),
-                rays.data_ptr() if rays is not None else None, stream)
+        args = (*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), out.data_ptr(), rays.data_ptr() if rays is not None else None,
+                torch.cuda.current_stream(dev).cuda_stream)
+        table, records = _table_ptrs(self.objects, self.pbr)
         if nrm is not None:
             check(lib.matpbr_path_render_normals(*args, nrm.data_ptr()), "matpbr_path_render_normals")
         elif self.objects is None:
             check(lib.matpbr_path_render(*args), "matpbr_path_render")
         elif self.pbr is not None:
-            check(symbol("matpbr_path_render_objects_pbr", lib)(*args, ctypes.cast(self.objects, _P), len(self.objects),
+            check(symbol("matpbr_path_render_objects_pbr", lib)(*args, table, len(self.objects),
                                                                 self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,
-                                                                self.n_scene_tris, ctypes.cast(self.pbr, _P)),
-                  "matpbr_path_render_objects_pbr")
+                                                                self.n_scene_tris, records), "matpbr_path_render_objects_pbr")
         elif self.obj_nrm is None:
-            check(lib.matpbr_path_render_objects(*args, ctypes.cast(self.objects, _P), len(self.objects)), "matpbr_path_render_objects")
+            check(lib.matpbr_path_render_objects(*args, table, len(self.objects)), "matpbr_path_render_objects")
         else:
-            check(symbol("matpbr_path_render_objects_normals", lib)(*args, ctypes.cast(self.objects, _P), len(self.objects),
-                                                                    self.obj_nrm.data_ptr(), self.n_scene_tris),
+            check(symbol("matpbr_path_render_objects_normals", lib)(*args, table, len(self.objects), self.obj_nrm.data_ptr(), self.n_scene_tris),
                   "matpbr_path_render_objects_normals")
         return out
 
@@ -702,8 +701,7 @@ class PathTracer:
         shading-normal map of `render` (a tracer with objects refuses it); id -1 = no hit, 0 = the depth mesh, 1 + k = object k."""
         nrm = self._normal(normal, "features") if normal is not None else None
         geom = torch.empty(self.H, self.W, 8, device=self.device, dtype=torch.float32)
-        check(symbol("matpbr_path_features")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov,
-                                             ctypes.cast(self.objects, _P) if self.objects is not None else None,
+        check(symbol("matpbr_path_features")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov, _table_ptrs(self.objects)[0],
                                              len(self.objects) if self.objects is not None else 0,
                                              self.obj_nrm.data_ptr() if self.obj_nrm is not None else None, self.n_scene_tris,
                                              nrm.data_ptr() if nrm is not None else None, geom.data_ptr(),
@@ -744,14 +742,11 @@ class PathTracer:
         ed = trans_edit(ior, spec_trans, refract_distance)
         mk = (mk != 0).to(dev, torch.uint8).contiguous()
         bgt = bgt.to(dev, torch.float32).contiguous()
-        a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
+        inputs = self._inputs(albedo, roughness, metallic, envmap, tables)
         out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        check(load().matpbr_path_render_trans(self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
-                                              env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]),
-                                              int(spp), int(max_depth), int(seed) & 0xFFFFFFFF, int(spp_per_launch), out.data_ptr(),
-                                              rays.data_ptr() if rays is not None else None, stream, mk.data_ptr(), bgt.data_ptr(),
-                                              ctypes.cast(ctypes.byref(ed), _P)), "matpbr_path_render_trans")
+        check(load().matpbr_path_render_trans(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), out.data_ptr(),
+                                              rays.data_ptr() if rays is not None else None, torch.cuda.current_stream(dev).cuda_stream,
+                                              mk.data_ptr(), bgt.data_ptr(), ctypes.cast(ctypes.byref(ed), _P)), "matpbr_path_render_trans")
         return out
 
     @torch.no_grad()
@@ -770,8 +765,8 @@ class PathTracer:
             raise ValueError("want 'n' needs the shading-normal map it is the gradient of: pass `normal`")
         nrm = self._normal(normal, "render_bwd") if normal is not None else None
         H, W, dev = self.H, self.W, self.device
-        a, r, m, env, row, col, pdf = self._inputs(albedo, roughness, metallic, envmap, tables)
-        He, We = int(env.shape[0]), int(env.shape[1])
+        inputs = self._inputs(albedo, roughness, metallic, envmap, tables)
+        He, We = int(inputs[3].shape[0]), int(inputs[3].shape[1])
         d_out = torch.as_tensor(d_out).to(dev, torch.float32).reshape(H, W, 3).contiguous()
         shapes = {"a": (H, W, 3), "r": (H, W, 1), "m": (H, W, 1), "env": (He, We, 3), "n": (H, W, 3)}
         grads = dict(grads or {})
@@ -791,11 +786,8 @@ class PathTracer:
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         ptr = lambda k: grads[k].data_ptr() if k in want else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        args = (self.nodes.data_ptr(), self.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, self.fov,
-                env.data_ptr(), row.data_ptr(), col.data_ptr(), pdf.data_ptr(), He, We, int(spp), int(max_depth),
-                int(seed) & 0xFFFFFFFF, int(spp_per_launch), d_out.data_ptr(), ptr("a"), ptr("r"), ptr("m"), ptr("env"),
-                self._ws.data_ptr(), nbytes, rays.data_ptr() if rays is not None else None, stream)
+        args = (*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), d_out.data_ptr(), ptr("a"), ptr("r"), ptr("m"), ptr("env"),
+                self._ws.data_ptr(), nbytes, rays.data_ptr() if rays is not None else None, torch.cuda.current_stream(dev).cuda_stream)
         if nrm is None:
             check(lib.matpbr_path_render_bwd(*args), "matpbr_path_render_bwd")
         else:

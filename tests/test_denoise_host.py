@@ -18,24 +18,17 @@ import denoise_fp64 as dn  # noqa: E402
 import path_fp64 as pf  # noqa: E402
 import path_normal_fp64 as pn  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
+import path_testlib as tl  # noqa: E402
 
 FOV = pf.FOV
 
 
 @pytest.fixture(scope="module")
 def path_lib():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    return pathtrace
+    return tl.load()
 
 
-def _report(what, value):
-    print(f"[denoise] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_denoise_host\t{what}\t{value}\n")
+_report = tl.reporter("denoise", "test_denoise_host")
 
 
 # ---- 1: single steps against fp64 ------------------------------------------------------------------------------------------------------

@@ -18,6 +18,8 @@ import denoise_fp64 as dn  # noqa: E402
 import path_fp64 as pf  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
+import path_testlib as tl  # noqa: E402
+from path_testlib import bits as _bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -30,24 +32,10 @@ CHAIN_BOUND = min(4 * CHAIN_MEASURED, 1e-3)
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[denoise] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_denoise\t{what}\t{value}\n")
-
-
-def _bits(x):
-    return x.cpu().numpy().view(np.uint32)
+_report = tl.reporter("denoise", "test_gpu_denoise")
 
 
 @pytest.fixture(scope="module")
@@ -222,35 +210,6 @@ def test_indoor2_denoised_against_plain_at_the_same_sample_count(pt, golden_dir)
 
 
 # ---- 6: command lines ------------------------------------------------------------------------------------------------------------------------------
-def _synthetic_output(tmp, name="case", H=32, W=32):
-    """tests/test_gpu_path_trans.py's synthetic output directory: the 32 x 32 scene, best_results/mask.png and an RGBA bg.png."""
-    from PIL import Image
-
-    from materialist_amd import mesh
-    from materialist_amd.imageio_exr import write_exr
-    from materialist_amd.imageio_hdr import write_hdr
-
-    rng = np.random.default_rng(2)
-    scene = os.path.join(tmp, name)
-    br = os.path.join(scene, "best_results")
-    os.makedirs(br)
-    a, r, m = pf.groove_maps(H, W, rng)
-    write_exr(os.path.join(br, "albedo.exr"), a)
-    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
-    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
-    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
-    write_hdr(os.path.join(br, "envmap.hdr"), pf.groove_env(rng))
-    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)         # depthPred.exr: the pipeline flips it to 2 max - d
-    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
-    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
-    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
-    mask = (i - 15) ** 2 + (j - 14) ** 2 < 81
-    Image.fromarray(np.repeat((mask * 255).astype(np.uint8)[..., None], 3, -1), "RGB").save(os.path.join(br, "mask.png"))
-    Image.fromarray(rng.integers(0, 256, (H, W, 4), dtype=np.uint8), "RGBA").save(os.path.join(br, "bg.png"))
-    return scene
-
-
 def _run(script, *args):
     return subprocess.run([sys.executable, os.path.join(ROOT, script), *args], capture_output=True, text=True, timeout=600)
 
@@ -262,7 +221,7 @@ def test_render_final_cli_denoise(pt, tmp_path):
     from materialist_amd.imageio_exr import read_exr
 
     tmp = str(tmp_path)
-    scene_dir = _synthetic_output(tmp)
+    scene_dir = tl.synthetic_output(tmp, edit=True)[0]
     common = ["--save_name", "case", "--input_path", tmp, "--save_path", tmp, "--mode", "real"]
     exr = os.path.join(tmp, "case", "mi_case_envmap_.exr")
     res = _run("render_final.py", *common, "--integrator", "path", "--spp", "8", "--seed", "5", "--denoise", "atrous")
@@ -306,7 +265,7 @@ def test_oi_and_trans_edit_cli_denoise(pt, tmp_path):
     from materialist_amd.imageio_exr import read_exr
 
     tmp = str(tmp_path)
-    scene_dir = _synthetic_output(tmp)
+    scene_dir = tl.synthetic_output(tmp, edit=True)[0]
     Vg, Tg, _ = ps.icosphere((-0.05, 0.03, -0.9), 0.09, 1)
     Vd, Td = po.cube((0.10, -0.04, -1.0), 0.14, (-0.3, 0.7, 0.2))
     mesh.write_ply(os.path.join(scene_dir, "oi.ply"), Vg, Tg)

@@ -14,6 +14,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import path_testlib as tl  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
 import path_fp64 as pf  # noqa: E402  (the fp64 restatement of the integrator)
 
 pytestmark = pytest.mark.gpu
@@ -24,20 +27,10 @@ groove_scene, _maps, _env = pf.groove_scene, pf.groove_maps, pf.groove_env
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[path] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_path\t{what}\t{value}\n")
+_report = tl.reporter("path", "test_gpu_path")
 
 
 @pytest.fixture(scope="module")
@@ -199,34 +192,11 @@ def test_against_mitsuba_on_the_references_final_maps(pt, golden_dir):
     assert ms < 5000.0
 
 
-def _synthetic_output(tmp, name="case", H=64, W=64):
-    from materialist_amd import mesh
-    from materialist_amd.imageio_exr import write_exr
-    from materialist_amd.imageio_hdr import write_hdr
-
-    rng = np.random.default_rng(2)
-    scene = os.path.join(tmp, name)
-    br = os.path.join(scene, "best_results")
-    os.makedirs(br)
-    a, r, m = _maps(H, W, rng)
-    write_exr(os.path.join(br, "albedo.exr"), a)
-    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
-    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
-    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
-    write_hdr(os.path.join(br, "envmap.hdr"), _env(rng))
-    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)         # depthPred.exr: the pipeline flips it to 2 max - d
-    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
-    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
-    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
-    return scene
-
-
 def test_render_final_cli_with_the_path_integrator(pt, tmp_path):
     from materialist_amd.imageio_exr import read_exr
 
     tmp = str(tmp_path)
-    _synthetic_output(tmp)
+    tl.synthetic_output(tmp, H=64, W=64)
     cli = [sys.executable, os.path.join(ROOT, "render_final.py"), "--save_name", "case", "--input_path", tmp, "--save_path", tmp,
            "--spp", "8", "--integrator", "path"]
     res = subprocess.run(cli + ["--mode", "real"], capture_output=True, text=True, timeout=600)

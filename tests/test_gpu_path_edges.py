@@ -15,6 +15,7 @@ if ROOT not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
+import path_testlib as tl  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,20 +24,10 @@ KEYS = ("a", "r", "m", "env")
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[path edges] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_path_edges\t{what}\t{value}\n")
+_report = tl.reporter("path edges", "test_gpu_path_edges")
 
 
 # ---- configurations ----------------------------------------------------------------------------------------------------------
@@ -149,7 +140,8 @@ def cases(pt, oracle64):
 
 
 def _parity(got, ref):
-    """Share of elements (pixels / texels: the worst channel) within 1e-3 relative to max(|ref|, mean|ref|), and the error per element."""
+    """path_testlib.parity for any leading shape: the errors come back flat, one per element (an image's pixels or a gradient's
+    texels; the worst channel).  -> (share of elements within 1e-3 relative to max(|ref|, mean|ref|), the error per element)."""
     scale = np.abs(ref).mean()
     err = (np.abs(got - ref) / np.maximum(np.abs(ref), scale)).reshape(-1, got.shape[-1]).max(-1)
     return float((err <= 1e-3).mean()), err

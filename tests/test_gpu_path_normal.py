@@ -17,6 +17,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_normal_fp64 as pnf  # noqa: E402
+import path_testlib as tl  # noqa: E402
+from path_testlib import bits as _bits, parity as _parity  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -26,20 +28,10 @@ KEYS = ("a", "r", "m", "env", "n")
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[path normal] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_path_normal\t{what}\t{value}\n")
+_report = tl.reporter("path normal", "test_gpu_path_normal")
 
 
 def _scene(pt, H=24, W=24):
@@ -66,16 +58,6 @@ def _replays(s, oracle64):
 def replays(scene, oracle64):
     """The restatement's renders and records of the shared cases, computed once (the backward parity reads the max_depth 4 records)."""
     return _replays(scene, oracle64)
-
-
-def _bits(x):
-    return x.cpu().numpy().view(np.uint32)
-
-
-def _parity(got, ref):
-    """test_gpu_path.py's criterion: per-pixel error relative to max(|ref|, mean |ref|) -> (share of pixels within 1e-3, errors)."""
-    err = (np.abs(got - ref) / np.maximum(np.abs(ref), np.abs(ref).mean())).max(-1)
-    return float((err <= 1e-3).mean()), err
 
 
 def _forward_parity(s, reps, where):

@@ -16,6 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
+import path_testlib as tl  # noqa: E402
+from path_testlib import bits as _bits, footprints as _footprints, erode as _erode  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -24,41 +26,18 @@ FOV = pf.FOV
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[path oi] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_path_oi\t{what}\t{value}\n")
+_report = tl.reporter("path oi", "test_gpu_path_oi")
 
 
 @pytest.fixture(scope="module")
 def scene(pt):
     """The groove at 24 x 20 with the glass and the diffuse cube in front of it."""
-    from materialist_amd import mesh
-
-    H, W = 20, 24
-    rm = mesh.reference_mesh(pf.groove_scene(H, W), FOV)
-    rng = np.random.default_rng(11)
-    a, r, m = pf.groove_maps(H, W, rng)
-    env = pf.groove_env(rng)
-    objects = po.two_cubes()
-    V, T, table = po.merged(rm["vertices"], rm["triangles"], objects)
-    return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "H": H, "W": W, "objects": objects, "V": V, "T": T, "table": table,
-            "plain": pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV),
-            "tracer": pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=objects)}
-
-
-def _bits(x):
-    return x.cpu().numpy().view(np.uint32)
+    s = tl.groove_with_objects(pt, po.two_cubes(), po.merged)
+    s["plain"] = pt.PathTracer(s["rm"]["vertices"], s["rm"]["triangles"], s["H"], s["W"], FOV)
+    return s
 
 
 def test_no_objects_same_bits(pt, scene):
@@ -96,29 +75,6 @@ def test_every_path_matches_an_fp64_restatement(pt, scene, oracle64):
                 assert rec[k].any(), (k, max_depth, seed)     # the scene does what it is for, in every one of the renders
     _report("pixels with a transmitted vertex / a diffuse-object vertex / an emitter sample an object blocks (6 renders)",
             f"{seen['transmitted']} / {seen['diffuse_object']} / {seen['blocked_by_object']}")
-
-
-def _footprints(objects, H, W, n=9):
-    """Per pixel, from an n x n grid of rays over its footprint [j - 1/2, j + 1/2] x [i - 1/2, i + 1/2] (corners included) and the
-    objects' projected vertices: (every ray hits an object, no ray hits and no vertex projects into the footprint)."""
-    f = (W / 2.0) / np.tan(np.radians(FOV) / 2.0)
-    g = np.linspace(-0.5, 0.5, n)
-    y, x = np.meshgrid((np.arange(H)[:, None] + g[None]).reshape(-1), (np.arange(W)[:, None] + g[None]).reshape(-1), indexing="ij")
-    d = np.stack([(x - (W - 1) / 2) / f, -(y - (H - 1) / 2) / f, -np.ones_like(x)], -1).reshape(-1, 3)
-    P = np.concatenate([np.asarray(ob["vertices"], np.float64)[np.asarray(ob["triangles"])] for ob in objects])
-    hit = np.isfinite(pf.brute(P, np.zeros_like(d), d)[0]).reshape(H, n, W, n)
-    vert = np.zeros((H, W), bool)
-    for ob in objects:
-        v = np.asarray(ob["vertices"], np.float64)
-        px, py = v[:, 0] / -v[:, 2] * f + (W - 1) / 2, -v[:, 1] / -v[:, 2] * f + (H - 1) / 2
-        for a, b in zip(px, py):
-            vert[max(int(np.floor(b - 0.5)), 0):int(np.ceil(b + 0.5)) + 1, max(int(np.floor(a - 0.5)), 0):int(np.ceil(a + 0.5)) + 1] = True
-    return hit.all(axis=(1, 3)), ~hit.any(axis=(1, 3)) & ~vert
-
-
-def _erode(mask):
-    m = np.pad(mask, 1, constant_values=False)
-    return np.logical_and.reduce([m[1 + di:m.shape[0] - 1 + di, 1 + dj:m.shape[1] - 1 + dj] for di in (-1, 0, 1) for dj in (-1, 0, 1)])
 
 
 def test_glass_furnace(pt):
@@ -211,30 +167,6 @@ def test_refusals(pt, scene):
             pt.PathTracer(s["rm"]["vertices"], s["rm"]["triangles"], s["H"], s["W"], FOV, objects=[dict(s["objects"][0], bsdf=bsdf)])
 
 
-def _synthetic_output(tmp, name="case", H=32, W=32):
-    """tests/test_gpu_path.py's synthetic output directory, at 32 x 32."""
-    from materialist_amd import mesh
-    from materialist_amd.imageio_exr import write_exr
-    from materialist_amd.imageio_hdr import write_hdr
-
-    rng = np.random.default_rng(2)
-    scene = os.path.join(tmp, name)
-    br = os.path.join(scene, "best_results")
-    os.makedirs(br)
-    a, r, m = pf.groove_maps(H, W, rng)
-    write_exr(os.path.join(br, "albedo.exr"), a)
-    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
-    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
-    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
-    write_hdr(os.path.join(br, "envmap.hdr"), pf.groove_env(rng))
-    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)         # depthPred.exr: the pipeline flips it to 2 max - d
-    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
-    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
-    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
-    return scene
-
-
 def test_render_final_cli_inserts_objects(pt, tmp_path):
     from materialist_amd import mesh, relight
     from materialist_amd.imageio_exr import read_exr
@@ -242,7 +174,7 @@ def test_render_final_cli_inserts_objects(pt, tmp_path):
 
     tmp = str(tmp_path)
     H = W = 32
-    scene_dir = _synthetic_output(tmp)
+    scene_dir = tl.synthetic_output(tmp)
     Vg, Tg = po.cube((-0.05, 0.03, -0.9), 0.16, (0.4, 0.5, 0.3))
     Vd, Td = po.cube((0.10, -0.04, -1.0), 0.14, (-0.3, 0.7, 0.2))
     Vg = Vg.astype(np.float32).astype(np.float64)

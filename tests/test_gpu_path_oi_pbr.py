@@ -22,6 +22,8 @@ import path_fp64 as pf  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
+import path_testlib as tl  # noqa: E402
+from path_testlib import bits as _bits, parity as _parity, raw_args as _raw_args, footprints as _footprints  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -30,49 +32,21 @@ FOV = pf.FOV
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[path oi pbr] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_path_oi_pbr\t{what}\t{value}\n")
+_report = tl.reporter("path oi pbr", "test_gpu_path_oi_pbr")
 
 
 @pytest.fixture(scope="module")
 def scene(pt):
     """The groove at 24 x 20 (a partial tile) with `path_oi_pbr_fp64.table_scene` in front of it: a smooth metal icosphere, a flat PBR
     cube, a smooth glass icosphere and a flat diffuse cube in one table."""
-    from materialist_amd import mesh
-
-    H, W = 20, 24
-    rm = mesh.reference_mesh(pf.groove_scene(H, W), FOV)
-    rng = np.random.default_rng(11)
-    a, r, m = pf.groove_maps(H, W, rng)
-    env = pf.groove_env(rng)
-    objects = pp.table_scene()
-    V, T, table = pp.merged(rm["vertices"], rm["triangles"], objects)
-    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=objects)
+    s = tl.groove_with_objects(pt, pp.table_scene(), pp.merged)
+    tracer = s["tracer"]
     assert tracer.stats["n_objects"] == 4 and tracer.stats["n_pbr_objects"] == 2 and tracer.stats["n_smooth_objects"] == 2
     assert tracer.stats["n_object_tris"] == 184 and tracer.pbr is not None
-    return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "H": H, "W": W, "objects": objects, "V": V, "T": T, "table": table, "tracer": tracer}
-
-
-def _bits(x):
-    return x.cpu().numpy().view(np.uint32)
-
-
-def _parity(got, ref):
-    """test_gpu_path_oi_smooth.py's criterion: per-pixel error relative to max(|ref|, mean |ref|) -> (share within 1e-3, the errors)."""
-    err = (np.abs(got - ref) / np.maximum(np.abs(ref), np.abs(ref).mean())).max(-1)
-    return float((err <= 1e-3).mean()), err
+    return s
 
 
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------------------
@@ -137,14 +111,6 @@ def test_a_quad_as_depth_mesh_and_as_a_pbr_object(pt):
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------------------
-def _raw_args(tracer, maps, spp, max_depth, seed, spp_per_launch, out):
-    a, r, m, env, row, col, pdf = tracer._inputs(*maps, None)
-    keep = (a, r, m, env, row, col, pdf)
-    return keep, (tracer.nodes.data_ptr(), tracer.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), tracer.H, tracer.W, FOV, env.data_ptr(),
-                  row.data_ptr(), col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]), spp, max_depth, seed, spp_per_launch,
-                  out.data_ptr(), None, torch.cuda.current_stream().cuda_stream)
-
-
 def test_bits(pt, scene):
     s = scene
     maps = (s["a"], s["r"], s["m"], s["env"])
@@ -214,24 +180,6 @@ def test_face_normals_as_vertex_normals_give_the_flat_bits(pt):
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------------------
-def _footprints(objects, H, W, n=9):
-    """test_gpu_path_oi.py's: per pixel, from an n x n grid of rays over its footprint and the objects' projected vertices: (every
-    ray hits an object, no ray hits and no vertex projects into the footprint)."""
-    f = (W / 2.0) / np.tan(np.radians(FOV) / 2.0)
-    g = np.linspace(-0.5, 0.5, n)
-    y, x = np.meshgrid((np.arange(H)[:, None] + g[None]).reshape(-1), (np.arange(W)[:, None] + g[None]).reshape(-1), indexing="ij")
-    d = np.stack([(x - (W - 1) / 2) / f, -(y - (H - 1) / 2) / f, -np.ones_like(x)], -1).reshape(-1, 3)
-    P = np.concatenate([np.asarray(ob["vertices"], np.float64)[np.asarray(ob["triangles"])] for ob in objects])
-    hit = np.isfinite(pf.brute(P, np.zeros_like(d), d)[0]).reshape(H, n, W, n)
-    vert = np.zeros((H, W), bool)
-    for ob in objects:
-        v = np.asarray(ob["vertices"], np.float64)
-        px, py = v[:, 0] / -v[:, 2] * f + (W - 1) / 2, -v[:, 1] / -v[:, 2] * f + (H - 1) / 2
-        for a, b in zip(px, py):
-            vert[max(int(np.floor(b - 0.5)), 0):int(np.ceil(b + 0.5)) + 1, max(int(np.floor(a - 0.5)), 0):int(np.ceil(a + 0.5)) + 1] = True
-    return hit.all(axis=(1, 3)), ~hit.any(axis=(1, 3)) & ~vert
-
-
 def test_a_black_dielectric_ball_in_a_furnace(pt):
     """A smooth PBR icosphere (80 triangles) with a = 0, m = 0, r = 1 under a constant envmap c: every pixel inside its footprint is
     finite, not above c (1 + 1e-5) and darker than the same pixel with a = 1; the pixels outside it are c."""
@@ -281,30 +229,6 @@ def test_refusals(pt, scene):
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------------------
-def _synthetic_output(tmp, name="case", H=32, W=32):
-    """tests/test_gpu_path_oi.py's synthetic output directory, at 32 x 32."""
-    from materialist_amd import mesh
-    from materialist_amd.imageio_exr import write_exr
-    from materialist_amd.imageio_hdr import write_hdr
-
-    rng = np.random.default_rng(2)
-    scene = os.path.join(tmp, name)
-    br = os.path.join(scene, "best_results")
-    os.makedirs(br)
-    a, r, m = pf.groove_maps(H, W, rng)
-    write_exr(os.path.join(br, "albedo.exr"), a)
-    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
-    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
-    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
-    write_hdr(os.path.join(br, "envmap.hdr"), pf.groove_env(rng))
-    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)
-    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
-    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
-    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
-    return scene
-
-
 def test_render_final_cli_oi_scene(pt, tmp_path):
     """`render_final.py --mode oi --oi_scene scene.json` with one PBR and one glass object writes mi_oi_<name>_<env>.exr/.png, the
     bits of the direct PathTracer calls, finite and not constant; with `--denoise atrous` the image stays inside the per-id convex
@@ -313,7 +237,7 @@ def test_render_final_cli_oi_scene(pt, tmp_path):
     from materialist_amd.imageio_exr import read_exr
 
     tmp = str(tmp_path)
-    scene_dir = _synthetic_output(tmp)
+    scene_dir = tl.synthetic_output(tmp)
     Vb, Tb, _ = ps.icosphere((0.08, -0.03, -0.95), 0.1, 1)
     Vb = Vb.astype(np.float32).astype(np.float64)
     Vg, Tg = po.cube((-0.09, 0.03, -0.9), 0.1, (0.4, 0.5, 0.3))

@@ -19,6 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import path_fp64 as pf  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
+import path_testlib as tl  # noqa: E402
+from path_testlib import bits as _bits, parity as _parity, footprints as _footprints, erode as _erode  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,48 +29,20 @@ FOV = pf.FOV
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[path oi smooth] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_path_oi_smooth\t{what}\t{value}\n")
+_report = tl.reporter("path oi smooth", "test_gpu_path_oi_smooth")
 
 
 @pytest.fixture(scope="module")
 def scene(pt):
     """The groove at 24 x 20 with `path_oi_smooth_fp64.table_scene` in front of it: a smooth glass and a smooth diffuse icosphere of
     80 triangles each and a flat diffuse cube in one table."""
-    from materialist_amd import mesh
-
-    H, W = 20, 24
-    rm = mesh.reference_mesh(pf.groove_scene(H, W), FOV)
-    rng = np.random.default_rng(11)
-    a, r, m = pf.groove_maps(H, W, rng)
-    env = pf.groove_env(rng)
-    objects = ps.table_scene()
-    V, T, table = ps.merged(rm["vertices"], rm["triangles"], objects)
-    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=objects)
+    s = tl.groove_with_objects(pt, ps.table_scene(), ps.merged)
+    tracer = s["tracer"]
     assert tracer.stats["n_objects"] == 3 and tracer.stats["n_smooth_objects"] == 2 and tracer.stats["n_object_tris"] == 172
-    return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "H": H, "W": W, "objects": objects, "V": V, "T": T, "table": table, "tracer": tracer}
-
-
-def _bits(x):
-    return x.cpu().numpy().view(np.uint32)
-
-
-def _parity(got, ref):
-    """test_gpu_path.py's criterion: per-pixel error relative to max(|ref|, mean |ref|) -> (share within 1e-3, the errors)."""
-    err = (np.abs(got - ref) / np.maximum(np.abs(ref), np.abs(ref).mean())).max(-1)
-    return float((err <= 1e-3).mean()), err
+    return s
 
 
 def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64):
@@ -95,29 +69,6 @@ def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64):
     _report("pixels with a smooth transmitted vertex / a smooth diffuse vertex / a blocked emitter sample / a redo about ng / a fallback "
             "(6 renders)", " / ".join(str(seen[k]) for k in seen))
     assert seen["redo"] >= 1 and seen["fallback"] >= 1
-
-
-def _footprints(objects, H, W, n=9):
-    """test_gpu_path_oi.py's: per pixel, from an n x n grid of rays over its footprint and the objects' projected vertices: (every
-    ray hits an object, no ray hits and no vertex projects into the footprint)."""
-    f = (W / 2.0) / np.tan(np.radians(FOV) / 2.0)
-    g = np.linspace(-0.5, 0.5, n)
-    y, x = np.meshgrid((np.arange(H)[:, None] + g[None]).reshape(-1), (np.arange(W)[:, None] + g[None]).reshape(-1), indexing="ij")
-    d = np.stack([(x - (W - 1) / 2) / f, -(y - (H - 1) / 2) / f, -np.ones_like(x)], -1).reshape(-1, 3)
-    P = np.concatenate([np.asarray(ob["vertices"], np.float64)[np.asarray(ob["triangles"])] for ob in objects])
-    hit = np.isfinite(pf.brute(P, np.zeros_like(d), d)[0]).reshape(H, n, W, n)
-    vert = np.zeros((H, W), bool)
-    for ob in objects:
-        v = np.asarray(ob["vertices"], np.float64)
-        px, py = v[:, 0] / -v[:, 2] * f + (W - 1) / 2, -v[:, 1] / -v[:, 2] * f + (H - 1) / 2
-        for a, b in zip(px, py):
-            vert[max(int(np.floor(b - 0.5)), 0):int(np.ceil(b + 0.5)) + 1, max(int(np.floor(a - 0.5)), 0):int(np.ceil(a + 0.5)) + 1] = True
-    return hit.all(axis=(1, 3)), ~hit.any(axis=(1, 3)) & ~vert
-
-
-def _erode(mask):
-    m = np.pad(mask, 1, constant_values=False)
-    return np.logical_and.reduce([m[1 + di:m.shape[0] - 1 + di, 1 + dj:m.shape[1] - 1 + dj] for di in (-1, 0, 1) for dj in (-1, 0, 1)])
 
 
 def test_glass_furnace_with_a_smooth_sphere(pt):
@@ -166,14 +117,12 @@ def test_bits(pt, scene):
     flat = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=bare)
     assert flat.stats["n_smooth_objects"] == 0 and flat.obj_nrm is None
     ref = flat.render(*args, spp=8, max_depth=16, seed=5)
-    a, r, m, env, row, col, pdf = flat._inputs(*args, None)
     dummy = torch.zeros(flat.stats["n_object_tris"], 3, 3, device=flat.device)
     for nrm_ptr in (None, dummy.data_ptr()):
         out = torch.empty(H, W, 3, device=flat.device)
-        code = pt.symbol("matpbr_path_render_objects_normals")(
-            flat.nodes.data_ptr(), flat.tris.data_ptr(), a.data_ptr(), r.data_ptr(), m.data_ptr(), H, W, FOV, env.data_ptr(), row.data_ptr(),
-            col.data_ptr(), pdf.data_ptr(), int(env.shape[0]), int(env.shape[1]), 8, 16, 5, 8, out.data_ptr(), None,
-            torch.cuda.current_stream().cuda_stream, ctypes.cast(flat.objects, ctypes.c_void_p), len(flat.objects), nrm_ptr, flat.n_scene_tris)
+        keep, head = tl.raw_args(flat, args, 8, 16, 5, 8, out)
+        code = pt.symbol("matpbr_path_render_objects_normals")(*head, ctypes.cast(flat.objects, ctypes.c_void_p), len(flat.objects), nrm_ptr,
+                                                               flat.n_scene_tris)
         assert code == 0
         assert np.array_equal(_bits(out), _bits(ref))
     assert not np.array_equal(_bits(s["tracer"].render(*args, spp=8, max_depth=16, seed=5)), _bits(ref))   # the normals do something
@@ -200,36 +149,12 @@ def test_refusals(pt, scene):
         s["tracer"].render(s["a"], s["r"], s["m"], s["env"], spp=1, normal=np.tile(np.float32([0, 0, 1]), (s["H"], s["W"], 1)))
 
 
-def _synthetic_output(tmp, name="case", H=32, W=32):
-    """tests/test_gpu_path_oi.py's synthetic output directory, at 32 x 32."""
-    from materialist_amd import mesh
-    from materialist_amd.imageio_exr import write_exr
-    from materialist_amd.imageio_hdr import write_hdr
-
-    rng = np.random.default_rng(2)
-    scene = os.path.join(tmp, name)
-    br = os.path.join(scene, "best_results")
-    os.makedirs(br)
-    a, r, m = pf.groove_maps(H, W, rng)
-    write_exr(os.path.join(br, "albedo.exr"), a)
-    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
-    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
-    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
-    write_hdr(os.path.join(br, "envmap.hdr"), pf.groove_env(rng))
-    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)
-    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
-    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
-    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
-    return scene
-
-
 def test_render_final_cli_oi_normals(pt, tmp_path):
     from materialist_amd import mesh, relight
     from materialist_amd.imageio_exr import read_exr
 
     tmp = str(tmp_path)
-    scene_dir = _synthetic_output(tmp)
+    scene_dir = tl.synthetic_output(tmp)
     Vg, Tg, Ng = ps.icosphere((-0.05, 0.03, -0.9), 0.09, 1)
     Vg, Ng = Vg.astype(np.float32).astype(np.float64), (1.7 * Ng).astype(np.float32).astype(np.float64)   # the file's normals: any length
     Vd, Td = po.cube((0.10, -0.04, -1.0), 0.14, (-0.3, 0.7, 0.2))

@@ -16,6 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_trans_fp64 as ptf  # noqa: E402
+import path_testlib as tl  # noqa: E402
+from path_testlib import bits as _bits, parity as _parity  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +26,10 @@ FOV = pf.FOV
 
 @pytest.fixture(scope="module")
 def pt():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return pathtrace
+    return tl.load(gpu=True)
 
 
-def _report(what, value):
-    print(f"[path trans] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_gpu_path_trans\t{what}\t{value}\n")
+_report = tl.reporter("path trans", "test_gpu_path_trans")
 
 
 @pytest.fixture(scope="module")
@@ -47,16 +39,6 @@ def scene(pt):
     s["tracer"] = pt.PathTracer(s["rm"]["vertices"], s["rm"]["triangles"], s["H"], s["W"], FOV)
     s["maps"] = (s["a"], s["r"], s["m"], s["env"])
     return s
-
-
-def _bits(x):
-    return x.cpu().numpy().view(np.uint32)
-
-
-def _parity(got, ref):
-    """test_gpu_path.py's criterion: per-pixel error relative to max(|ref|, mean |ref|) -> (share of pixels within 1e-3, errors)."""
-    err = (np.abs(got - ref) / np.maximum(np.abs(ref), np.abs(ref).mean())).max(-1)
-    return float((err <= 1e-3).mean()), err
 
 
 @pytest.fixture(scope="module")
@@ -192,41 +174,12 @@ def test_refusals(pt, scene):
     assert not img.requires_grad and img.grad_fn is None
 
 
-def _synthetic_output(tmp, name="case", H=32, W=32):
-    """tests/test_gpu_path_oi.py's synthetic output directory at 32 x 32, plus best_results/mask.png and an RGBA best_results/bg.png."""
-    from PIL import Image
-
-    from materialist_amd import mesh
-    from materialist_amd.imageio_exr import write_exr
-    from materialist_amd.imageio_hdr import write_hdr
-
-    rng = np.random.default_rng(2)
-    scene = os.path.join(tmp, name)
-    br = os.path.join(scene, "best_results")
-    os.makedirs(br)
-    a, r, m = pf.groove_maps(H, W, rng)
-    write_exr(os.path.join(br, "albedo.exr"), a)
-    write_exr(os.path.join(br, "roughness.exr"), np.repeat(r, 3, -1))
-    write_exr(os.path.join(br, "metallic.exr"), np.repeat(m, 3, -1))
-    write_exr(os.path.join(br, "normal.exr"), np.tile(np.array([0, 0, 1], np.float32), (H, W, 1)))
-    write_hdr(os.path.join(br, "envmap.hdr"), pf.groove_env(rng))
-    i, j = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    pred = (1.0 + 0.3 * (j > W // 2) + 0.002 * i).astype(np.float32)         # depthPred.exr: the pipeline flips it to 2 max - d
-    write_exr(os.path.join(scene, "depthPred.exr"), np.repeat(pred[..., None], 3, -1))
-    rm = mesh.reference_mesh(2 * pred.max() - pred, FOV)
-    mesh.write_ply(os.path.join(scene, f"{name}.ply"), rm["vertices"], rm["triangles"])
-    mask = (i - 15) ** 2 + (j - 14) ** 2 < 81
-    Image.fromarray(np.repeat((mask * 255).astype(np.uint8)[..., None], 3, -1), "RGB").save(os.path.join(br, "mask.png"))
-    Image.fromarray(rng.integers(0, 256, (H, W, 4), dtype=np.uint8), "RGBA").save(os.path.join(br, "bg.png"))
-    return scene, mask
-
-
 def test_trans_edit_cli(pt, tmp_path):
     from materialist_amd import relight
     from materialist_amd.imageio_exr import read_exr
 
     tmp = str(tmp_path)
-    scene_dir, mask = _synthetic_output(tmp)
+    scene_dir, mask = tl.synthetic_output(tmp, edit=True)
     common = ["--save_name", "case", "--input_path", tmp, "--save_path", tmp]
     cli = [sys.executable, os.path.join(ROOT, "trans_edit.py"), *common, "--spp", "4", "--iters", "2"]
     res = subprocess.run(cli, capture_output=True, text=True, timeout=600)

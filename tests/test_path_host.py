@@ -11,14 +11,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import path_testlib as tl  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def path_lib():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    return pathtrace
+    return tl.load()
 
 
 def step_depth(H=40, W=48):

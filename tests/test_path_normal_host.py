@@ -17,22 +17,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_normal_fp64 as pnf  # noqa: E402
+import path_testlib as tl  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def path_lib():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    return pathtrace
+    return tl.load()
 
 
-def _report(what, value):
-    print(f"[path normal] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_path_normal_host\t{what}\t{value}\n")
+_report = tl.reporter("path normal", "test_path_normal_host")
 
 
 def _unit(v):

@@ -20,24 +20,17 @@ import path_fp64 as pf  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
+import path_testlib as tl  # noqa: E402
 
 FOV = pf.FOV
 
 
 @pytest.fixture(scope="module")
 def path_lib():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    return pathtrace
+    return tl.load()
 
 
-def _report(what, value):
-    print(f"[path oi pbr] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_path_oi_pbr_host\t{what}\t{value}\n")
+_report = tl.reporter("path oi pbr", "test_path_oi_pbr_host")
 
 
 # ---- 1: the symbols ----------------------------------------------------------------------------------------------------------------------

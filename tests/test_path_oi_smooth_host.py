@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import path_fp64 as pf  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
+import path_testlib as tl  # noqa: E402
 
 ETA = 1.49 / 1.000277
 U_TRANSMIT = 0.99999994          # dim 6 just below 1: transmits wherever anything is transmitted
@@ -24,18 +25,10 @@ U_TRANSMIT = 0.99999994          # dim 6 just below 1: transmits wherever anythi
 
 @pytest.fixture(scope="module")
 def path_lib():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    return pathtrace
+    return tl.load()
 
 
-def _report(what, value):
-    print(f"[path oi smooth] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_path_oi_smooth_host\t{what}\t{value}\n")
+_report = tl.reporter("path oi smooth", "test_path_oi_smooth_host")
 
 
 def _unit(x):

@@ -15,22 +15,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_trans_fp64 as ptf  # noqa: E402
+import path_testlib as tl  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def path_lib():
-    from materialist_amd import build, pathtrace
-
-    build.build_path_library()
-    return pathtrace
+    return tl.load()
 
 
-def _report(what, value):
-    print(f"[path trans] {what}: {value}")
-    path = os.environ.get("MATPBR_TOLERANCE_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(f"test_path_trans_host\t{what}\t{value}\n")
+_report = tl.reporter("path trans", "test_path_trans_host")
 
 
 def _unit(v):
