@@ -206,6 +206,13 @@ int matpbr_mlp_layer_bwd_weight_blk(const float* g, int ldg, const void* g_tile_
  * 0 mlp_wgrad_bx<3>, register-staged.  Both walk the same rows and form the same products in the same order: partial sums and d_w are the same
  * bits (tests/test_gpu_wgrad_stagger.py).  Process-wide; returns the previous setting.  (-DMATPBR_WG_HX=0 builds with 0 as the default.) */
 int matpbr_mlp_set_wgrad_kernel(int kernel);
+/* The cache plan of the f16 backward pass (matpbr_mlp_out_layer_bwd_tmax, matpbr_mlp_layer_bwd_input_blk, matpbr_mlp_first_layer_bwd_blk,
+ * matpbr_mlp_layer_bwd_weight_blk).  mode 1 (default): rows of the [M, 256] matrices that cannot stay in the Infinity Cache until their next
+ * use -- by the launches' row orders and the bytes moved in between -- are stored and loaded with the streaming (non-temporal) policy, the
+ * weight gradient's partial sums likewise; the rows next to a turnaround between two launches keep the default policy.  mode 0: the default
+ * policy everywhere.  resident_bytes: the cache budget the plan assumes; <= 0 selects the built-in default.  A launch whose whole footprint
+ * fits the budget is not changed.  Values never depend on the plan (tests/test_gpu_cache_plan.py).  Process-wide; returns the previous mode. */
+int matpbr_mlp_set_cache_plan(int mode, long resident_bytes);
 /* up to 8 splits in one launch (host arrays of n_jobs entries; transposed[j] = the flags of matpbr_mlp_split_weights_fmt for job j:
  * 0 / 1 as before, + MATPBR_WSPLIT_F16X2 for the f16 form): the weights of every layer change together, once per optimiser step */
 int matpbr_mlp_split_weights_multi(const float* const* w, const int* ldw, const int* N, const int* K, const int* transposed,

@@ -91,6 +91,40 @@ __device__ __forceinline__ void store4_upto(float* dst, float4 v, int valid, boo
   }
 }
 
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+// 16-byte / 4-byte accesses with the default (NT = false) or the streaming policy: one copy of the arithmetic around them, two instruction forms.
+// The streaming store stands between two compiler barriers (no instructions): `if (nt) st<true>(p, v); else st<false>(p, v);` is otherwise
+// folded into ONE plain store -- the optimiser merges the two arms and drops the policy, which it does not take for a difference
+template <bool NT>
+__device__ __forceinline__ void st_f4(float* dst, const float4& v) {
+  if constexpr (NT) {
+    asm volatile("" ::: "memory");
+    __builtin_nontemporal_store(f32x4v{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4v*>(dst));
+    asm volatile("" ::: "memory");
+  } else {
+    *reinterpret_cast<float4*>(dst) = v;
+  }
+}
+template <bool NT>
+__device__ __forceinline__ void st_f1(float* dst, float v) {
+  if constexpr (NT) {
+    asm volatile("" ::: "memory");
+    __builtin_nontemporal_store(v, dst);
+    asm volatile("" ::: "memory");
+  } else {
+    *dst = v;
+  }
+}
+template <bool NT>
+__device__ __forceinline__ float4 ld_f4(const float* src) {
+  if constexpr (NT) {
+    const f32x4v v = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(src));
+    return make_float4(v.x, v.y, v.z, v.w);
+  } else {
+    return *reinterpret_cast<const float4*>(src);
+  }
+}
+
 struct NtArgs {
   const float* A;      // [M, lda]   rows = points
   const float* B;      // [N, ldb]   rows = output features, k contiguous
@@ -109,6 +143,9 @@ struct NtArgs {
   float* w0_part;      // mlp_nt_bx<.., W0>: [4 gridDim.x][16][256] partial first-layer weight gradients (the layout of the skinny kernels)
   const unsigned* a_tmax;   // mlp_nt_gx<EPI_MULC, 3>: [M / 128] max |A| of every 128-row tile (f32 bit patterns): the tile's block exponent
   unsigned* o_tmax;         // nullable: the same of the rows written (atomic max into a zeroed array: the next product's a_tmax)
+  // the cache plan (plan_tiles_kept; mlp_nt_gx<EPI_MULC, 3> only).  The defaults are the plain policy everywhere
+  int nt_store_below = 0;            // tiles below this one: out0 by streaming stores (their reader comes from the last rows and is too far away)
+  int nt_load_from = 0x7fffffff;     // tiles from this one on: cmul by streaming loads (last use, and no longer cached from the weight gradient before)
 };
 
 // LDS image of a k-tile: [row][k] with a pitch of 36 floats: 16-byte writes and 16-byte reads are both conflict-free (8 lanes x
@@ -1180,7 +1217,6 @@ constexpr int kBxThreads = 512;
 // itself: each 32 x 32 block of G' sits in the wave's LDS slice for the transposition, the wave's 32 rows of x0 beside it, and sixteen
 // v_mfma_f32_16x16x4f32 per block fold them into 8 x 4 accumulator registers per wave.  Saves the 268 MB store, the 268 MB read of the
 // skinny weight-gradient pass and its launch.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 // GL: both operands of the main loop arrive by LDS-DMA (global_load_lds_dwordx4: no register round trip, no ds_write, full 128-byte
 // lines of the rows, the rows read once per workgroup instead of once per column half).  Weights: two 48 KB buffers, one super-step
 // ahead; rows: a ring of three 16 KB buffers [128 rows][8 x 16 B] (chunk c of row r at slot c ^ (r >> 1 & 7): the fragment reads of
@@ -1526,6 +1562,7 @@ __global__ __launch_bounds__(kGxThreads, 2) void mlp_nt_gx(const NtArgs p, const
   // slice (piece, g) = wave w's four DMA pieces, kept at the 6144-byte slice pitch of the bf16 form (the epilogue's scratch needs 4608)
   constexpr bool F16 = NPROD == 3;
   constexpr bool BLK = F16 && EPI == EPI_MULC;                            // the rows are loss gradients: one exponent per 128-row tile (block_scale)
+  constexpr bool PLAN = BLK && !HEAD;                                     // the cache plan reaches this form only (p.nt_store_below, p.nt_load_from)
   static_assert(!F16 || EPI != EPI_BIAS, "the two-piece f16 form: sine layers forward (sines in, unit scale) and input gradients (block-scaled rows)");
   constexpr int kSlicePitch = F16 ? 384 : 256;                            // uint4 between (piece, g) slices in LDS
   constexpr size_t kStepBytes = F16 ? 16384 : (size_t)kGxW;               // one half step of the global image
@@ -1682,10 +1719,18 @@ __global__ __launch_bounds__(kGxThreads, 2) void mlp_nt_gx(const NtArgs p, const
     // 128 of the main product a second set does not fit 256 registers, and the rows are cache hits behind the weight gradient that just read them
     constexpr int kCvSets = W0 ? 1 : 2;
     float4 cvb[kCvSets][4];
+    // the tile's cache policy (uniform): streaming loads of the cos operand, streaming stores of out0.  The arithmetic between them is ONE
+    // copy: a second copy of the epilogue per policy does not fit the registers beside the accumulators (it spilled)
+    const bool nt_c = PLAN && tile >= p.nt_load_from, nt_o = PLAN && !W0 && tile < p.nt_store_below;
     auto cv_load = [&](int b, float4 (&dst)[4]) {
       const float* src = p.cmul + (size_t)(row0 + wm * 64 + (b >> 2) * 32 + t_row) * p.ldo + wn * 128 + (b & 3) * 32 + t_col;
+      if (PLAN && nt_c) {
 #pragma unroll
-      for (int ps = 0; ps < 4; ++ps) dst[ps] = *reinterpret_cast<const float4*>(src + (size_t)(8 * ps) * p.ldo);
+        for (int ps = 0; ps < 4; ++ps) dst[ps] = ld_f4<true>(src + (size_t)(8 * ps) * p.ldo);
+      } else {
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) dst[ps] = ld_f4<false>(src + (size_t)(8 * ps) * p.ldo);
+      }
     };
     if (EPI == EPI_MULC) cv_load(0, cvb[0]);
     float hacc[4][5];
@@ -1734,7 +1779,8 @@ __global__ __launch_bounds__(kGxThreads, 2) void mlp_nt_gx(const NtArgs p, const
             if (col + 3 >= p.N) v.w = tl[col + 3];
         }
         if (W0) *reinterpret_cast<float4*>(scr + (t_row + 8 * ps) * kLd + t_col) = v;   // G' back into the block, for the product below
-        else *reinterpret_cast<float4*>(p.out0 + o0 + (size_t)(8 * ps) * p.ldo) = v;
+        else if (PLAN && nt_o) st_f4<true>(p.out0 + o0 + (size_t)(8 * ps) * p.ldo, v);
+        else st_f4<false>(p.out0 + o0 + (size_t)(8 * ps) * p.ldo, v);
         vrow[ps] = v;
       }
       if (W0) {     // dW0[16 ct + i][j] += sum over the block's 32 rows of G'[row][16 ct + i] x0[row][j]  (A: lane = (i, k), B: lane = (j, k))
@@ -1843,7 +1889,8 @@ __device__ __forceinline__ int wg_perm(int i) { return (i & 16) + 2 * (i & 7) + 
 // every step; with opposite orders one of them splits and stores while the other one multiplies.
 template <int NPROD, bool EARLY>
 __device__ __forceinline__ void wgrad_bx_body(const float* __restrict__ G, int ldg, const float* __restrict__ X, int ldx,
-                                              float* __restrict__ partial, long M, long rows_per_slab, uint4* sW, const unsigned* __restrict__ g_tmax) {
+                                              float* __restrict__ partial, long M, long rows_per_slab, uint4* sW, const unsigned* __restrict__ g_tmax,
+                                              int stream_partial) {
   // NPROD == 3: two f16 pieces per operand.  X (sines, the x0 tail) as it is; G under ONE exponent per slab, from the largest of the
   // tile maxima of the slab's rows (block_scale); the partial sums are scaled back when they are stored
   constexpr bool F16 = NPROD == 3;
@@ -1988,27 +2035,32 @@ __device__ __forceinline__ void wgrad_bx_body(const float* __restrict__ G, int l
     if constexpr (kWgDepth > 3) if (st0 + 2 < steps) step(std::integral_constant<int, 2>{}, st0 + 2);
   }
   float* out = partial + (long)blockIdx.x * 256 * 256;
+  auto store_partial = [&](auto nt) {                        // (as mlp_wgrad_hx: the f16 form's partial sums may stream past the cache)
 #pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
+    for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-    for (int ki = 0; ki < 4; ++ki)
+      for (int ki = 0; ki < 4; ++ki)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = nq * 64 + ni * 32 + wg_perm((r & 3) + 8 * (r >> 2) + 4 * lh);
-        const int k = kq * 128 + ki * 32 + wg_perm(li);
-        out[n * 256 + k] = F16 ? acc[ni][ki][r] * g_unscale : acc[ni][ki][r];
-      }
+        for (int r = 0; r < 16; ++r) {
+          const int n = nq * 64 + ni * 32 + wg_perm((r & 3) + 8 * (r >> 2) + 4 * lh);
+          const int k = kq * 128 + ki * 32 + wg_perm(li);
+          st_f1<decltype(nt)::value>(out + n * 256 + k, F16 ? acc[ni][ki][r] * g_unscale : acc[ni][ki][r]);
+        }
+  };
+  if (F16 && stream_partial) store_partial(std::true_type{});
+  else store_partial(std::false_type{});
 }
 
 template <int NPROD>
 __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_bx(const float* __restrict__ G, int ldg, const float* __restrict__ X, int ldx,
-                                                              float* __restrict__ partial, long M, long rows_per_slab, const unsigned* __restrict__ g_tmax) {
+                                                              float* __restrict__ partial, long M, long rows_per_slab, const unsigned* __restrict__ g_tmax,
+                                                              int stream_partial) {
   extern __shared__ __align__(16) unsigned char wg_smem[];
   uint4* sW = reinterpret_cast<uint4*>(wg_smem);
   if (threadIdx.x >> 8)
-    wgrad_bx_body<NPROD, true>(G, ldg, X, ldx, partial, M, rows_per_slab, sW, g_tmax);
+    wgrad_bx_body<NPROD, true>(G, ldg, X, ldx, partial, M, rows_per_slab, sW, g_tmax, stream_partial);
   else
-    wgrad_bx_body<NPROD, false>(G, ldg, X, ldx, partial, M, rows_per_slab, sW, g_tmax);
+    wgrad_bx_body<NPROD, false>(G, ldg, X, ldx, partial, M, rows_per_slab, sW, g_tmax, stream_partial);
 }
 
 // mlp_wgrad_hx: the two-piece f16 weight gradient with its rows brought in by LDS-DMA and cut ONCE (see EXPERIMENTS.md, "where the weight
@@ -2038,7 +2090,8 @@ constexpr int kHxPieces = 2 * 2 * 2 * 256;                 // uint4 of a piece b
 constexpr size_t kHxSmem = 3 * kHxRaw + 2 * kHxPieces * sizeof(uint4);   // 160 KB
 static_assert(kHxSmem <= 160 * 1024, "mlp_wgrad_hx: the LDS of a CU");
 __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_hx(const float* __restrict__ G, int ldg, const float* __restrict__ X, int ldx,
-                                                              float* __restrict__ partial, long M, long rows_per_slab, const unsigned* __restrict__ g_tmax) {
+                                                              float* __restrict__ partial, long M, long rows_per_slab, const unsigned* __restrict__ g_tmax,
+                                                              int stream_partial) {
   extern __shared__ __align__(16) unsigned char hx_smem[];
   uint4* sP = reinterpret_cast<uint4*>(hx_smem + 3 * kHxRaw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2171,17 +2224,22 @@ __global__ __launch_bounds__(kWgThreads, 1) void mlp_wgrad_hx(const float* __res
 #undef MATPBR_HX_BARRIER
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     // the look-ahead pieces: nothing may land after the workgroup has ended
   }
+  // the partial sums: read next by the fold, six launches on -- streamed past the cache when the plan says so (uniform over the launch)
   float* out = partial + (long)blockIdx.x * 256 * 256;
+  auto store_partial = [&](auto nt) {
 #pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
+    for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-    for (int ki = 0; ki < 4; ++ki)
+      for (int ki = 0; ki < 4; ++ki)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = nq * 64 + ni * 32 + wg_perm((r & 3) + 8 * (r >> 2) + 4 * lh);
-        const int k = kq * 128 + ki * 32 + wg_perm(li);
-        out[n * 256 + k] = acc[ni][ki][r] * g_unscale;
-      }
+        for (int r = 0; r < 16; ++r) {
+          const int n = nq * 64 + ni * 32 + wg_perm((r & 3) + 8 * (r >> 2) + 4 * lh);
+          const int k = kq * 128 + ki * 32 + wg_perm(li);
+          st_f1<decltype(nt)::value>(out + n * 256 + k, acc[ni][ki][r] * g_unscale);
+        }
+  };
+  if (stream_partial) store_partial(std::true_type{});
+  else store_partial(std::false_type{});
 }
 
 constexpr size_t kBxSmem = 2 * kBxStage * sizeof(uint4) + 8 * 32 * kLd * sizeof(float);   // 96 KB of weights + 36 KB of epilogue scratch
@@ -2192,6 +2250,34 @@ constexpr size_t kBxSmemHead = kBxSmem + (5 * 256 + 128 * 2 * 8) * sizeof(float)
 std::atomic<int> g_nt_gl{2};
 std::atomic<int> g_nt_w0_gx{0};   // measurement: mode 3 of matpbr_mlp_set_lds_dma                  // LDS-DMA main loop where the shape allows (matpbr_mlp_set_lds_dma: A/B switch)
 std::atomic<int> g_wg_hx{MATPBR_WG_HX};   // the f16 weight gradient on mlp_wgrad_hx (1) or on mlp_wgrad_bx<3> (0): matpbr_mlp_set_wgrad_kernel
+// The cache plan (matpbr_mlp_set_cache_plan): which rows of the image-sized [M, 256] matrices of the f16 backward pass may occupy the
+// Infinity Cache.  The launches walk the rows in alternating directions (output layer up, weight gradient down, input gradient up, ...), so
+// row tile number d from the turnaround between two launches is touched again after
+//     reuse distance(d) = fixed + d * bytes_per_tile
+// bytes of other traffic: `bytes_per_tile` is what the two launches together load and store per 128-row tile (128 KB per matrix each of them
+// reads or writes), `fixed` what is written at the turnaround itself (the weight gradient's partial sums).  A line survives only while that
+// distance fits the cache: the d < (resident - fixed) / bytes_per_tile tiles next to the turnaround keep the default policy, every other
+// tile is certain to be evicted before its next use and goes by streaming (non-temporal) stores and loads, which leave the cache to the
+// tiles that can hit.  A launch whose whole footprint fits keeps all its tiles: small M, the envmap MLP, the host-enqueue shapes.
+#ifndef MATPBR_CACHE_PLAN
+#define MATPBR_CACHE_PLAN 1                   // (measurement builds: the default mode)
+#endif
+#ifndef MATPBR_CACHE_STEPS                    // the streams the plan covers: 2 input-gradient stores, 4 weight-gradient partial sums, 8 loads at their
+#define MATPBR_CACHE_STEPS 14                 // last use (measurement builds: tools/ab.sh; EXPERIMENTS.md, "a cache plan", has each one's A/B)
+#endif
+#ifndef MATPBR_CACHE_RESIDENT_MIB
+#define MATPBR_CACHE_RESIDENT_MIB 192         // (measurement builds: the default budget; EXPERIMENTS.md, "cache plan")
+#endif
+std::atomic<int> g_cache_plan{MATPBR_CACHE_PLAN};
+std::atomic<long> g_cache_resident{0};        // <= 0: MATPBR_CACHE_RESIDENT_MIB
+constexpr long kTileBytes = (long)kBM * 256 * sizeof(float);               // a 128-row tile of one [M, 256] matrix
+inline long plan_tiles_kept(int step, long tiles, int matrices, long fixed_bytes) {   // step: the bit of MATPBR_CACHE_STEPS that asks
+  if (g_cache_plan.load(std::memory_order_relaxed) == 0 || !(MATPBR_CACHE_STEPS & step)) return tiles;
+  long resident = g_cache_resident.load(std::memory_order_relaxed);
+  if (resident <= 0) resident = (long)MATPBR_CACHE_RESIDENT_MIB << 20;
+  const long kept = resident > fixed_bytes ? (resident - fixed_bytes) / (matrices * kTileBytes) : 0;
+  return kept < tiles ? kept : tiles;
+}
 inline bool gl_ok(const NtArgs& p) {
   return g_nt_gl.load(std::memory_order_relaxed) != 0 && p.K > 32 && (long)kBM * p.lda * 4 < (1l << 31);   // (a ragged K: the rows hold 32-column granules, lda >= 32 ceil(K / 32))
 }
@@ -2567,6 +2653,7 @@ struct SkinnyDgrad {          // the input-gradient half of mlp_skinny_tn_kernel
   int ldg;
   float* gsum_part;           // [slabs][256]
   unsigned* tmax;             // nullable [M / 128]: atomic max of |G| per 128-row tile (zeroed by the caller): the block exponents of the f16 products
+  int stream_b;               // the cache plan (plan_tiles_kept): B, never read again in the iteration, arrives by streaming loads
 };
 template <int J, bool DGRAD = false, int JV = kOutJ>      // JV (DGRAD): the valid columns of S -- 5 ('arm'), 8 ('armn': round 6)
 __global__ __launch_bounds__(256) void mlp_skinny_tn_kernel(const float* __restrict__ S, int lds, const float* __restrict__ B, int ldb,
@@ -2599,12 +2686,21 @@ __global__ __launch_bounds__(256) void mlp_skinny_tn_kernel(const float* __restr
     }
     tmx = 0.f;
   };
+  const bool nt_b = DGRAD && dg.stream_b;   // (uniform over the launch; the policy is chosen at the access: a copy of the loop per policy costs 28 registers)
   for (long m0 = m_begin + rs; m0 < m_end; m0 += 4 * U) {
     float4 b[U];
+    if (nt_b) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long m = m0 + 4 * u;
-      b[u] = m < m_end ? *reinterpret_cast<const float4*>(B + m * ldb + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int u = 0; u < U; ++u) {
+        const long m = m0 + 4 * u;
+        b[u] = m < m_end ? ld_f4<true>(B + m * ldb + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long m = m0 + 4 * u;
+        b[u] = m < m_end ? ld_f4<false>(B + m * ldb + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -2776,6 +2872,11 @@ inline void reduce_or_defer(const MatpbrReduceJob& q, MatpbrReduceJob* defer, hi
 extern "C" {
 
 int matpbr_mlp_set_wgrad_kernel(int kernel) { return g_wg_hx.exchange(kernel != 0 ? 1 : 0, std::memory_order_relaxed); }
+
+int matpbr_mlp_set_cache_plan(int mode, long resident_bytes) {
+  g_cache_resident.store(resident_bytes > 0 ? resident_bytes : 0, std::memory_order_relaxed);
+  return g_cache_plan.exchange(mode != 0 ? 1 : 0, std::memory_order_relaxed);
+}
 
 int matpbr_mlp_set_lds_dma(int mode) {
   g_nt_w0_gx.store(mode == 3 ? 1 : 0, std::memory_order_relaxed);
@@ -2985,6 +3086,15 @@ static int mlp_layer_bwd_input_bx_impl(const float* g, int ldg, const void* wtsp
   NtArgs p{g, nullptr, nullptr, c_prev, g_prev, nullptr, d_bias_prev ? (float*)workspace : nullptr, (int)M, n_prev, n_red, ldg, 0, ldo};
   p.cmul_sin = sgn;
   p.a_tmax = g_tile_max; p.o_tmax = out_tile_max;
+  if (nprod == 3) {
+    // G' is read next by the weight gradient of the layer below, last rows first: behind a tile's store lie this launch's three matrices and
+    // that one's two, per tile above it.  cmul was read by this layer's weight gradient, first rows last (its two matrices, its
+    // partial sums, then this launch's three)
+    const long tiles = M / kBM;
+    p.nt_store_below = (int)(tiles - plan_tiles_kept(2, tiles, 5, 0));
+    const long kept = plan_tiles_kept(8, tiles, 5, (long)matpbr_mlp_bwd_weight_workspace_bytes(M));
+    if (kept < tiles) p.nt_load_from = (int)kept;
+  }
   const int groups = launch_nt_bx<EPI_MULC>(p, (const uint4*)wtsplit, nprod, (hipStream_t)stream);
   if (groups < 0) return MATPBR_ERR_LAUNCH;
   if (defer) defer->kind = MATPBR_REDUCE_NONE;
@@ -3012,6 +3122,10 @@ static int mlp_first_layer_bwd_impl(const float* g, int ldg, const void* wtsplit
   p.x0 = x0; p.ldx0 = ldx0; p.w0_part = (float*)workspace2;
   p.a_tmax = g_tile_max;
   const int tiles = (int)(M / kBM);
+  if (nprod == 3) {                                        // as mlp_layer_bwd_input_bx_impl, without the store: two matrices each
+    const long kept = plan_tiles_kept(8, tiles, 4, (long)matpbr_mlp_bwd_weight_workspace_bytes(M));
+    if (kept < tiles) p.nt_load_from = (int)kept;
+  }
   unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
   int slabs = (int)grid * 4;
   bool ok;
@@ -3116,18 +3230,21 @@ static int mlp_layer_bwd_weight_bx_impl(const float* g, int ldg, const float* x,
   int slabs = wgrad_slabs(M);
   long rows = ((M + slabs - 1) / slabs + 15) / 16 * 16;
   slabs = (int)((M + rows - 1) / rows);
+  // the partial sums are read by the fold at the end of the pass; written through the cache they evict the rows the input gradient is about to re-read
+  const long tiles_w = (M + kBM - 1) / kBM;
+  const int stream_partial = nprod == 3 && plan_tiles_kept(4, tiles_w, 2, (long)slabs * 256 * 256 * sizeof(float)) < tiles_w;
   if (nprod == 3 && g_wg_hx.load(std::memory_order_relaxed) != 0 && (long)ldg * 4 >= 1024 && (long)ldx * 4 >= 1024 && (long)3 * ldg * 4 + 1024 < (1l << 31) && (long)3 * ldx * 4 + 1024 < (1l << 31)) {
     if (!lds_opt_in<&mlp_wgrad_hx>(kHxSmem)) return MATPBR_ERR_LAUNCH;
-    hipLaunchKernelGGL(mlp_wgrad_hx, dim3(slabs), dim3(kWgThreads), kHxSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, g_tile_max);
+    hipLaunchKernelGGL(mlp_wgrad_hx, dim3(slabs), dim3(kWgThreads), kHxSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, g_tile_max, stream_partial);
   } else if (nprod == 3) {
     if (!lds_opt_in<&mlp_wgrad_bx<3>>(kWgSmem)) return MATPBR_ERR_LAUNCH;
-    hipLaunchKernelGGL(mlp_wgrad_bx<3>, dim3(slabs), dim3(kWgThreads), kWgSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, g_tile_max);
+    hipLaunchKernelGGL(mlp_wgrad_bx<3>, dim3(slabs), dim3(kWgThreads), kWgSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, g_tile_max, stream_partial);
   } else if (nprod == 6) {
     if (!lds_opt_in<&mlp_wgrad_bx<6>>(kWgSmem)) return MATPBR_ERR_LAUNCH;
-    hipLaunchKernelGGL(mlp_wgrad_bx<6>, dim3(slabs), dim3(kWgThreads), kWgSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, (const unsigned*)nullptr);
+    hipLaunchKernelGGL(mlp_wgrad_bx<6>, dim3(slabs), dim3(kWgThreads), kWgSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, (const unsigned*)nullptr, 0);
   } else {
     if (!lds_opt_in<&mlp_wgrad_bx<9>>(kWgSmem)) return MATPBR_ERR_LAUNCH;
-    hipLaunchKernelGGL(mlp_wgrad_bx<9>, dim3(slabs), dim3(kWgThreads), kWgSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, (const unsigned*)nullptr);
+    hipLaunchKernelGGL(mlp_wgrad_bx<9>, dim3(slabs), dim3(kWgThreads), kWgSmem, (hipStream_t)stream, g, ldg, x, ldx, (float*)workspace, M, rows, (const unsigned*)nullptr, 0);
   }
   MatpbrReduceJob q{};
   q.kind = MATPBR_REDUCE_WGRAD; q.groups = slabs; q.src = (const float*)workspace; q.dst = d_w; q.n0 = N; q.n1 = K; q.n2 = ldw;
@@ -3207,7 +3324,9 @@ static int mlp_out_layer_bwd_impl(const float* d_x, int ldd, const float* s_prev
   float* partial = (float*)workspace;
   float* bpart = partial + (size_t)kSkinnySlabs * 8 * 256;
   float* gsum_part = bpart + (size_t)kSkinnySlabs * 8;
-  SkinnyDgrad dg{w_out, ldw, J, c_prev, g_prev, ldg, gsum_part, g_tile_max};
+  // B is not read again in the iteration: streamed unless the launch and the weight gradient behind it (two matrices each) fit the cache
+  const long tiles = (M + kBM - 1) / kBM;
+  SkinnyDgrad dg{w_out, ldw, J, c_prev, g_prev, ldg, gsum_part, g_tile_max, plan_tiles_kept(8, tiles, 4, 0) < tiles};
   if (J <= kOutJ) hipLaunchKernelGGL((mlp_skinny_tn_kernel<8, true>), dim3(slabs), dim3(256), 0, (hipStream_t)stream, d_x, ldd, s_prev, lds, partial, bpart, M, rows, dg);
   else hipLaunchKernelGGL((mlp_skinny_tn_kernel<8, true, 8>), dim3(slabs), dim3(256), 0, (hipStream_t)stream, d_x, ldd, s_prev, lds, partial, bpart, M, rows, dg);
   MatpbrReduceJob q{};

@@ -931,6 +931,13 @@ def mlp_set_wgrad_kernel(kernel: int) -> int:
     return int(_lib.load().matpbr_mlp_set_wgrad_kernel(int(kernel)))
 
 
+def mlp_set_cache_plan(mode: int, resident_bytes: int = 0) -> int:
+    """The cache plan of the f16 backward pass (include/matpbr_mlp.h `matpbr_mlp_set_cache_plan`): 1 (default) streams what cannot stay in the
+    Infinity Cache until its next use, 0 the default policy everywhere -- the same bits.  resident_bytes <= 0: the built-in budget.  Process-wide;
+    returns the previous mode."""
+    return int(_lib.load().matpbr_mlp_set_cache_plan(int(mode), int(resident_bytes)))
+
+
 def mlp_reduce_jobs(jobs, n: int, like: torch.Tensor) -> None:
     """Every deferred fold of an iteration's backward pass in one launch (include/matpbr.h `matpbr_mlp_reduce_jobs`); jobs: a `_lib.ReduceJob` array."""
     with torch.cuda.device(like.device):
