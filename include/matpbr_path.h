@@ -44,6 +44,9 @@ enum {
     MATPBR_PATH_BSDF_DIFFUSE = 2,    /* one-sided Lambertian: p = reflectance RGB in [0, 1] */
     MATPBR_PATH_BSDF_PBR = 3,        /* MatDiffBSDF on constants, one-sided: a MatpbrPathObjectPbr record beside the table; p[] is ignored.
                                         Only matpbr_path_render_objects_pbr (and the feature entry points) take it. */
+    MATPBR_PATH_BSDF_AREA = 4,       /* an area light, one-sided, no BSDF: p = radiance RGB, finite and >= 0 (0 is valid).  Never with
+                                        MATPBR_PATH_OBJECT_SMOOTH.  Only matpbr_path_render_objects_lights, matpbr_path_light_tables (and
+                                        the feature entry points) take it; to every other entry point it is an unknown kind. */
 };
 
 /* OR-ed into MatpbrPathObject.kind: the object shades with interpolated corner normals ("Smooth inserted
@@ -186,6 +189,64 @@ int matpbr_path_render_objects_pbr(const void* nodes, const void* tris, const fl
 int matpbr_path_object_lookup_host(const MatpbrPathObject* objects, int n_objects, const MatpbrPathObjectPbr* pbr, const int32_t* ids, long N,
                                    int32_t* kind, float* a, float* r, float* m);
 
+/* ---- Emissive inserted objects ("Emissive inserted objects") -------------------------------------------------
+ * The emitters of a scene are the envmap, where it has tables (row_cdf[He] > 0), then the objects of kind MATPBR_PATH_BSDF_AREA in
+ * table order, each as one emitter; n_e is their count.  The header below travels to the kernel by value; the lights' triangle
+ * records and cumulative areas are buffers. */
+typedef struct MatpbrPathLights {
+    int32_t n_lights;                         /* the objects of kind 4 */
+    int32_t object[MATPBR_PATH_MAX_OBJECTS];  /* light l is objects[object[l]]: ascending */
+    int32_t first[MATPBR_PATH_MAX_OBJECTS];   /* its records: [first[l], first[l] + n_tri[l]) of light_tris / light_cdf; first[0] = 0, contiguous */
+    int32_t n_tri[MATPBR_PATH_MAX_OBJECTS];
+    float area[MATPBR_PATH_MAX_OBJECTS];      /* its area: summed in fp64, > 0 */
+} MatpbrPathLights;
+
+/* The light tables of a merged mesh (host; vert / tri / objects as matpbr_path_bvh_build_objects and the renders take them): the
+ * header, *n_light_tri = the records every light's triangles need, and, where light_tris != NULL, light_tris[n_light_tri, 3, 4]
+ * (fp32: (v0, 0) (e1, 0) (e2, 0) of each light triangle in input order, rounded as the BVH rounds them) and light_cdf[n_light_tri]
+ * (per light: the cumulative area / the light's area, built in fp64, stored fp32, upper bounds, the last exactly 1).  `capacity`:
+ * the records both buffers hold (MATPBR_PATH_ERR_CAPACITY when too few).  With light_tris == NULL only the header and the count are
+ * written: call once for the sizes, once more for the tables.  Invalid arguments: a bad table (a negative or non-finite radiance,
+ * kind 4 with the smooth flag, ...), a light's range outside the mesh, a light of total area 0.  A table without lights gives
+ * n_lights = 0 and *n_light_tri = 0. */
+int matpbr_path_light_tables(const double* vert, long n_vert, const int32_t* tri, long n_tri, const MatpbrPathObject* objects, int n_objects,
+                             const MatpbrPathObjectPbr* pbr, MatpbrPathLights* lights, float* light_tris, float* light_cdf, long capacity,
+                             long* n_light_tri);
+
+/* matpbr_path_render_objects_pbr where an object may be of kind MATPBR_PATH_BSDF_AREA, forward only.  `lights` (HOST, copied before
+ * the call returns), light_tris and light_cdf (DEVICE, 16-byte aligned, as matpbr_path_light_tables made them).  At every non-delta
+ * vertex ONE emitter is sampled (dims 2-5): idx = min(int(u2 n_e), n_e - 1), u2' = u2 n_e - idx (kept below 1); the envmap by
+ * (u2', u3, u4, u5) with pdf_e / n_e; light l by the first triangle whose cumulative area exceeds u2', the point
+ * y = v0 + (1 - s) e1 + s u4 e2 with s = sqrt(1 - u3), wl = normalize(y - po), dist = |y - po|, pdf = dist^2 / (A cos_l n_e); it needs
+ * cos_l = n_l . (-wl) > 0, ng . wl > 0, dist > 0; the shadow ray is any-hit up to dist (1 - 1e-3); the sample adds
+ * thr f p mis(pdf, pdf_b) / pdf.  A traced ray that lands on a light's front (ng . wo > 0) adds thr p w, w = 1 at depth 0 or after a
+ * delta vertex, else mis(prev_pdf, t^2 / (A (ng . wo) n_e)), BEFORE the max_depth test, and ends; on its back it ends with nothing
+ * added.  An escaped ray's weight takes env_pdf / n_e.  Without an object of kind 4 this calls matpbr_path_render_objects_pbr and
+ * gives its bits (the three light arguments may be NULL then).  Invalid arguments, besides that entry point's: a negative or
+ * non-finite radiance, kind 4 with the smooth flag, null tables with a kind-4 object, a header that is not the table's (the lights
+ * are the kind-4 objects in order, records contiguous from 0, n_tri the object's), an area that is not finite and > 0. */
+int matpbr_path_render_objects_lights(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                      float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                      int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                      const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                      const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                      const float* light_cdf);
+
+/* The emitter sample of matpbr_path_render_objects_lights on the CPU, with the routines the kernel runs (every pointer HOST;
+ * n_light_tri: the records the two buffers hold, checked against the header).  have_env: whether the envmap is emitter 0.  From
+ * po[N,3] with u[N,4] = dims 2-5 -> emitter[N] (the index among the n_e emitters), u_re[N] = u2', and for a light: record[N] (the
+ * triangle's index in light_tris; -1 for the envmap), y[N,3], wl[N,3], dist[N], pdf[N] (0 where cos_l <= 0 or dist = 0; the test
+ * against the vertex's normal is the caller's).  For the envmap y, wl, dist, pdf are 0 (matpbr_path_env_sample_host samples it). */
+int matpbr_path_light_sample_host(const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf, long n_light_tri, int have_env,
+                                  const float* po, const float* u, long N, int32_t* emitter, float* u_re, int32_t* record, float* y, float* wl,
+                                  float* dist, float* pdf);
+
+/* The hit side's pdf on the CPU, with the routine the kernel runs: a ray o[N,3], d[N,3] (unit length) that lands on record[N] of
+ * light[N] -> t[N] (Moller-Trumbore's t on the record's plane, the traversal's operations) and pdf[N] = t^2 / (A (n_l . -d) n_e), 0
+ * where t <= 0 or the ray meets the back. */
+int matpbr_path_light_pdf_host(const MatpbrPathLights* lights, const void* light_tris, long n_light_tri, int have_env, const int32_t* light,
+                               const int32_t* record, const float* o, const float* d, long N, float* t, float* pdf);
+
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;
  * `edit` is HOST memory, copied before the call returns.  Where the texel a vertex reads is masked, the BSDF is the glass of
@@ -283,8 +344,8 @@ typedef struct MatpbrPathDenoise {
 
 /* geom of an H x W camera (matpbr_path_render's) over a BVH: one lane per pixel traces one closest-hit ray through the pixel centre.
  * objects[n_objects] (HOST, copied before the call returns), obj_nrm (DEVICE, nullable unless an object is smooth) and n_scene_tri as
- * matpbr_path_render_objects_normals takes them (an object may also be of kind MATPBR_PATH_BSDF_PBR: the features need its kind and
- * its smooth flag only, and take no records); with n_objects == 0 they may be null / 0.  nrm_map (DEVICE, nullable): the
+ * matpbr_path_render_objects_normals takes them (an object may also be of kind MATPBR_PATH_BSDF_PBR or MATPBR_PATH_BSDF_AREA: the
+ * features need its kind and its smooth flag only, and take no records or light tables; a light has id 1 + k and its face normal); with n_objects == 0 they may be null / 0.  nrm_map (DEVICE, nullable): the
  * shading-normal map of matpbr_path_render_normals, read at the texel the hit point projects to.  geom: DEVICE, 16-byte aligned. */
 int matpbr_path_features(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
                          const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom, void* stream);

@@ -9,10 +9,12 @@
 // The BRDF arithmetic is matpbr_device.hpp's (pixel_const, brdf_core, ggx_den_stable, frame, to_world), unchanged.
 // One translation unit: this file holds PathArgs, the forward kernel, the backward kernels and the C ABI; path_bvh.hpp the BVH, its
 // traversals and the host builder; path_shading.hpp the RNG, the envmap sampler and the BSDF wrappers; path_objects.hpp the tables the
-// kernels take by value, their lookups, samplers and checks; path_denoise.hpp the denoiser.
+// kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
+// path_denoise.hpp the denoiser.
 #include <type_traits>
 
 #include "path_denoise.hpp"
+#include "path_lights.hpp"
 
 namespace {
 
@@ -39,10 +41,13 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 // ShadeNormals): `n` stays the face normal ng and `ns` is the map's.  SMOOTH: smooth inserted objects (Objects = SmoothObjects): OBJ
 // with `ns` the interpolated corner normal at the vertices of a flagged object; every `if (SMOOTH ...)` folds away in the other four.
 // PBR: SMOOTH with objects of kind 3 (Objects = PbrObjects), whose vertices run the depth mesh's branch about `ns` on the constants of
-// their record; every `if (PBR ...)` folds away in the other five.
+// their record; every `if (PBR ...)` folds away in the other five.  LIGHT: PBR with objects of kind 4 (Objects = LightObjects), area
+// lights: one emitter of n_e (the envmap, the lights) is sampled per vertex, and a ray that lands on a light adds its emission and
+// ends; every `if (LIGHT ...)` folds away in the other six.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool PBR = std::is_same<Objects, PbrObjects>::value;
+    constexpr bool LIGHT = std::is_same<Objects, LightObjects>::value;
+    constexpr bool PBR = std::is_same<Objects, PbrObjects>::value || LIGHT;
     constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value || PBR;
     constexpr bool OBJ = std::is_same<Objects, ObjTable>::value || SMOOTH;
     constexpr bool EDIT = std::is_same<Objects, TransEdit>::value;
@@ -54,6 +59,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     LdsStack stk{s_stack + tid};
     const long pix = (long)i * q.W + j;
     const bool have_tab = q.row_cdf[q.He] > 0.0f;   // an envmap of zero luminance has no emitter sampling
+    int n_e = 1;   // (LIGHT) the emitters: the envmap where it has tables, then the lights
+    if constexpr (LIGHT) n_e = (have_tab ? 1 : 0) + ot.lt.n;
+    const float n_ef = (float)n_e;
     float acc[3] = {0.0f, 0.0f, 0.0f};
     if (!first) {
 #pragma unroll
@@ -80,10 +88,36 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             const int k = trace<false>(q.nodes, q.tris, o, d, 0.0f, t, stk);
             if (k < 0) {   // escaped: the envmap, MIS-weighted against emitter sampling after a BSDF sample
                 const int tx = env_texel(d, q.He, q.We);
-                const float w = depth == 0 || (OBJ && prev_delta) ? 1.0f : mis_weight(prev_pdf, have_tab ? q.env_pdf[tx] : 0.0f);
+                const float w = depth == 0 || (OBJ && prev_delta)
+                                    ? 1.0f
+                                    : mis_weight(prev_pdf, have_tab ? (LIGHT ? q.env_pdf[tx] / n_ef : q.env_pdf[tx]) : 0.0f);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) L[c] += thr[c] * (q.env[3 * tx + c] * w);
                 break;
+            }
+            int kind = 0;          // (OBJ) 0: the depth mesh; else the inserted object's BSDF and its parameters
+            float op[3] = {0.0f, 0.0f, 0.0f};
+            float oa[3] = {0.0f, 0.0f, 0.0f}, o_r = 0.0f, o_m = 0.0f;   // (PBR) the record of an object of kind 3
+            if constexpr (LIGHT) {   // the table lookup moves ahead of the max_depth test: a light's emission is added as the envmap's escape term is
+                const LightLookup f = light_lookup(ot, __float_as_int(q.tris[3 * k].w));
+                kind = f.kind;
+                op[0] = f.p0; op[1] = f.p1; op[2] = f.p2;
+                oa[0] = f.a0; oa[1] = f.a1; oa[2] = f.a2;
+                o_r = f.r; o_m = f.m;
+                const float area = f.area;
+                if (kind == MATPBR_PATH_BSDF_AREA) {
+                    const float4 B = q.tris[3 * k + 1], C = q.tris[3 * k + 2];
+                    const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+                    float n[3];
+                    cross3(e1, e2, n);
+                    const float cos_o = -dot3(n, d) * rsq(dot3(n, n));
+                    if (cos_o > 0.0f) {   // one-sided: the back ends the path with nothing added
+                        const float w = depth == 0 || prev_delta ? 1.0f : mis_weight(prev_pdf, light_hit_pdf(t, area, cos_o, n_ef));
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) L[c] += thr[c] * (op[c] * w);
+                    }
+                    break;
+                }
             }
             if (depth + 1 >= q.max_depth) break;   // Mitsuba's active_next: the surfaces emit nothing
             const float4 B = q.tris[3 * k + 1], C = q.tris[3 * k + 2];
@@ -96,10 +130,8 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 for (int c = 0; c < 3; ++c) n[c] *= il;
             }
             const float wo[3] = {-d[0], -d[1], -d[2]};
-            int kind = 0;          // (OBJ) 0: the depth mesh; else the inserted object's BSDF and its parameters
-            float op[3] = {0.0f, 0.0f, 0.0f};
-            float oa[3] = {0.0f, 0.0f, 0.0f}, o_r = 0.0f, o_m = 0.0f;   // (PBR) the record of an object of kind 3
-            if constexpr (PBR) kind = object_lookup(ot.t, ot.pbr, __float_as_int(q.tris[3 * k].w), op, oa, o_r, o_m);
+            if constexpr (LIGHT) {
+            } else if constexpr (PBR) kind = object_lookup(ot.t, ot.pbr, __float_as_int(q.tris[3 * k].w), op, oa, o_r, o_m);
             else if (OBJ) kind = object_of(ot, __float_as_int(q.tris[3 * k].w), op);
             bool smooth = false;   // (SMOOTH) the object shades with its interpolated corner normals, `ns` below
             if constexpr (SMOOTH) {
@@ -155,10 +187,30 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
 #pragma unroll
             for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
             // emitter sample with a shadow ray (none at a delta vertex)
-            if (have_tab && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC)) {
+            if ((LIGHT || have_tab) && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC)) {
                 float wl[3], pdf_e;
-                const int te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
-                                          rng_u(base, depth, 4), rng_u(base, depth, 5), wl, pdf_e);
+                int te = 0;
+                float Le[3] = {0.0f, 0.0f, 0.0f}, ts_max = FLT_MAX;   // (LIGHT) the chosen emitter's radiance, the shadow ray's reach
+                if constexpr (LIGHT) {   // one emitter of n_e by sample reuse of dim 2; pdf_e carries the 1 / n_e
+                    float u_re;
+                    const int idx = emitter_choose(rng_u(base, depth, 2), n_e, u_re);
+                    if (have_tab && idx == 0) {
+                        te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, u_re, rng_u(base, depth, 3), rng_u(base, depth, 4),
+                                        rng_u(base, depth, 5), wl, pdf_e);
+                        pdf_e = pdf_e / n_ef;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) Le[c] = q.env[3 * te + c];
+                    } else {   // dim 5 is unused for a light
+                        const int l = idx - (have_tab ? 1 : 0);
+                        float y[3], dist;
+                        light_sample(ot.lt, l, u_re, rng_u(base, depth, 3), rng_u(base, depth, 4), po, n_ef, y, wl, dist, pdf_e);
+                        light_radiance(ot.lt, l, Le);
+                        ts_max = dist * (1.0f - kShadowEps);
+                    }
+                } else {
+                    te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
+                                    rng_u(base, depth, 4), rng_u(base, depth, 5), wl, pdf_e);
+                }
                 if (pdf_e > 0.0f && dot3(n, wl) > 0.0f) {
                     float f[3], pdf_b;
                     if (OBJ && kind == MATPBR_PATH_BSDF_DIFFUSE) {   // f cos = rho / pi max(n . wi, 0), pdf = cos / pi
@@ -177,12 +229,12 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                         path_eval(wl, wo, NRM || PBR ? ns : n, av, rv, mv, f, pdf_b);   // (PBR) ns = n on the depth mesh
                     }
                     if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
-                        float ts = FLT_MAX;
+                        float ts = LIGHT ? ts_max : FLT_MAX;
                         ++n_rays;
                         if (trace<true>(q.nodes, q.tris, po, wl, 0.0f, ts, stk) < 0) {
                             const float w = mis_weight(pdf_e, pdf_b) / pdf_e;
 #pragma unroll
-                            for (int c = 0; c < 3; ++c) L[c] += thr[c] * (f[c] * (q.env[3 * te + c] * w));
+                            for (int c = 0; c < 3; ++c) L[c] += thr[c] * (f[c] * ((LIGHT ? Le[c] : q.env[3 * te + c]) * w));
                         }
                     }
                 }
@@ -609,6 +661,7 @@ struct Extras {
     const float* obj_nrm = nullptr;   // set where some object is smooth
     int32_t n_scene_tri = 0;
     const MatpbrPathObjectPbr* pbr = nullptr;
+    const LightTable* lights = nullptr;   // set where some object is a light (pbr may be null then: no object is of kind 3)
     const TransEdit* edit = nullptr;
     const float* nrm = nullptr;
 };
@@ -621,10 +674,11 @@ struct ObjectArgs {
     long n_scene_tri;
     const MatpbrPathObjectPbr* pbr;   // nullable: no record is checked
 };
-// ... checked into the table, the corner normals, n_scene_tri and the records of `x`.  `with_pbr`: a kind may be MATPBR_PATH_BSDF_PBR
-bool object_extras(const ObjectArgs& g, bool with_pbr, Extras& x) {
+// ... checked into the table, the corner normals, n_scene_tri and the records of `x`.  `with_pbr`: a kind may be MATPBR_PATH_BSDF_PBR;
+// `n_light` (nullable): where given, a kind may be MATPBR_PATH_BSDF_AREA, counted there
+bool object_extras(const ObjectArgs& g, bool with_pbr, Extras& x, int* n_light = nullptr) {
     int n_smooth = 0, n_pbr = 0;
-    if (!object_table(g.objects, g.n_objects, x.ot, &n_smooth, with_pbr ? &n_pbr : nullptr, g.pbr) || g.n_scene_tri < 0 ||
+    if (!object_table(g.objects, g.n_objects, x.ot, &n_smooth, with_pbr ? &n_pbr : nullptr, g.pbr, n_light) || g.n_scene_tri < 0 ||
         g.n_scene_tri > INT32_MAX || (n_smooth > 0 && !g.obj_nrm))
         return false;
     for (int k = 0; k < g.n_objects; ++k)
@@ -647,11 +701,20 @@ int render_common(const Frame& f, const Extras& x) {
         pbo.n_scene_tri = x.n_scene_tri;
         for (int k = 0; k < x.ot.n; ++k) pbo.pbr[k] = x.pbr[k];
     }
+    LightObjects lo{};
+    if (x.lights) {
+        lo.t = x.ot;
+        lo.nrm = x.obj_nrm;
+        lo.n_scene_tri = x.n_scene_tri;
+        for (int k = 0; x.pbr && k < x.ot.n; ++k) lo.pbr[k] = x.pbr[k];
+        lo.lt = *x.lights;
+    }
     for (int s0 = 0; s0 < f.spp; s0 += f.spp_per_launch) {
         const int s1 = std::min(f.spp, s0 + f.spp_per_launch);
         const int first = s0 == 0 ? 1 : 0, last = s1 == f.spp ? 1 : 0;
         if (x.edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, block, 0, st, q, s0, s1, first, last, *x.edit);
         else if (x.nrm) hipLaunchKernelGGL(path_kernel<ShadeNormals>, grid, block, 0, st, q, s0, s1, first, last, ShadeNormals{x.nrm});
+        else if (x.lights) hipLaunchKernelGGL(path_kernel<LightObjects>, grid, block, 0, st, q, s0, s1, first, last, lo);
         else if (x.pbr) hipLaunchKernelGGL(path_kernel<PbrObjects>, grid, block, 0, st, q, s0, s1, first, last, pbo);
         else if (x.obj_nrm) hipLaunchKernelGGL(path_kernel<SmoothObjects>, grid, block, 0, st, q, s0, s1, first, last, SmoothObjects{x.ot, x.obj_nrm, x.n_scene_tri});
         else if (x.ot.n > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, block, 0, st, q, s0, s1, first, last, x.ot);
@@ -663,8 +726,9 @@ int render_common(const Frame& f, const Extras& x) {
 
 // the arguments both feature entry points share, checked and packed: `q` arrives with the caller's pointers and sizes
 bool features_args(const ObjectArgs& g, float fov_x_deg, FeatArgs& q, Extras& x) {
-    // an object of kind 3 is valid here: the features read its kind and its flag, never its record
-    if (!q.nodes || !q.tris || !q.geom || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) || !object_extras(g, true, x)) return false;
+    // an object of kind 3 or 4 is valid here: the features read its kind and its flag, never its record or its light tables
+    int n_light = 0;
+    if (!q.nodes || !q.tris || !q.geom || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) || !object_extras(g, true, x, &n_light)) return false;
     q.n_scene_tri = x.n_scene_tri;
     const Camera c = camera(q.H, q.W, fov_x_deg);   // the render's
     q.f_pix = c.f_pix; q.cx = c.cx; q.cy = c.cy;
@@ -908,6 +972,100 @@ int matpbr_path_render_objects_pbr(const void* nodes, const void* tris, const fl
     Extras x;
     if (!pbr || !object_extras({objects, n_objects, obj_nrm, n_scene_tri, pbr}, true, x)) return MATPBR_PATH_ERR_INVALID_ARG;
     return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+}
+
+int matpbr_path_light_tables(const double* vert, long n_vert, const int32_t* tri, long n_tri, const MatpbrPathObject* objects, int n_objects,
+                             const MatpbrPathObjectPbr* pbr, MatpbrPathLights* lights, float* light_tris, float* light_cdf, long capacity,
+                             long* n_light_tri) {
+    ObjTable ot{};
+    int n_smooth = 0, n_pbr = 0, n_light = 0;
+    if (!vert || !tri || !lights || !n_light_tri || n_vert <= 0 || n_tri < 0 || n_tri > INT32_MAX / 3 || (light_tris && (!light_cdf || capacity < 0)) ||
+        !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr, &n_light))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    return light_tables_build(vert, n_vert, tri, n_tri, ot, lights, light_tris, light_cdf, capacity, n_light_tri);
+}
+
+int matpbr_path_render_objects_lights(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                      float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                      int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                      const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                      const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                      const float* light_cdf) {
+    bool any_light = false, any_pbr = false;
+    for (int k = 0; objects && k >= 0 && k < n_objects && k < MATPBR_PATH_MAX_OBJECTS; ++k) {
+        any_light = any_light || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_AREA;
+        any_pbr = any_pbr || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR;
+    }
+    if (!any_light)
+        return matpbr_path_render_objects_pbr(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
+                                              spp_per_launch, out, rays, stream, objects, n_objects, obj_nrm, n_scene_tri, pbr);
+    Extras x;
+    LightTable lt;
+    int n_light = 0;
+    if ((any_pbr && !pbr) || !object_extras({objects, n_objects, obj_nrm, n_scene_tri, pbr}, true, x, &n_light) ||
+        !light_table(lights, x.ot, light_tris, light_cdf, lt))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    x.lights = &lt;
+    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+}
+
+// the header of the two CPU entry points, checked against itself (no object table there): records contiguous from 0 within n_light_tri
+static bool light_header(const MatpbrPathLights* h, const void* tri, const float* cdf, long n_light_tri, LightTable& lt) {
+    if (!h || !tri || ((uintptr_t)tri & 15) || h->n_lights < 1 || h->n_lights > kMaxLights) return false;
+    lt = LightTable{};
+    lt.tri = static_cast<const float4*>(tri);
+    lt.cdf = cdf;
+    lt.n = h->n_lights;
+    long first = 0;
+    for (int l = 0; l < h->n_lights; ++l) {
+        if (h->first[l] != first || h->n_tri[l] < 1 || !(h->area[l] > 0.0f) || !std::isfinite(h->area[l])) return false;
+        lt.first[l] = h->first[l];
+        lt.n_tri[l] = h->n_tri[l];
+        lt.area[l] = h->area[l];
+        first += h->n_tri[l];
+    }
+    return first == n_light_tri;
+}
+
+int matpbr_path_light_sample_host(const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf, long n_light_tri, int have_env,
+                                  const float* po, const float* u, long N, int32_t* emitter, float* u_re, int32_t* record, float* y, float* wl,
+                                  float* dist, float* pdf) {
+    LightTable lt;
+    if (!light_cdf || !po || !u || !emitter || !u_re || !record || !y || !wl || !dist || !pdf || N < 0 || (have_env != 0 && have_env != 1) ||
+        !light_header(lights, light_tris, light_cdf, n_light_tri, lt))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    const int n_e = have_env + lt.n;
+    for (long k = 0; k < N; ++k) {
+        emitter[k] = emitter_choose(u[4 * k], n_e, u_re[k]);
+        record[k] = -1;
+        y[3 * k] = y[3 * k + 1] = y[3 * k + 2] = wl[3 * k] = wl[3 * k + 1] = wl[3 * k + 2] = 0.0f;
+        dist[k] = pdf[k] = 0.0f;
+        if (have_env && emitter[k] == 0) continue;
+        record[k] = light_sample(lt, emitter[k] - have_env, u_re[k], u[4 * k + 1], u[4 * k + 2], po + 3 * k, (float)n_e, y + 3 * k, wl + 3 * k,
+                                 dist[k], pdf[k]);
+    }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_light_pdf_host(const MatpbrPathLights* lights, const void* light_tris, long n_light_tri, int have_env, const int32_t* light,
+                               const int32_t* record, const float* o, const float* d, long N, float* t, float* pdf) {
+    LightTable lt;
+    if (!light || !record || !o || !d || !t || !pdf || N < 0 || (have_env != 0 && have_env != 1) ||
+        !light_header(lights, light_tris, nullptr, n_light_tri, lt))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    const float n_e = (float)(have_env + lt.n);
+    for (long k = 0; k < N; ++k) {
+        const int l = light[k], rec = record[k];
+        if (l < 0 || l >= lt.n || rec < lt.first[l] || rec - lt.first[l] >= lt.n_tri[l]) return MATPBR_PATH_ERR_INVALID_ARG;
+        t[k] = tri_t(lt.tri, rec, o + 3 * k, d + 3 * k);
+        const float4 B = lt.tri[3 * rec + 1], C = lt.tri[3 * rec + 2];
+        const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+        float n[3];
+        cross3(e1, e2, n);
+        const float cos_o = -dot3h(n, d + 3 * k) / sqrtf(dot3h(n, n));
+        pdf[k] = t[k] > 0.0f && t[k] < FLT_MAX && cos_o > 0.0f ? light_hit_pdf(t[k], lt.area[l], cos_o, n_e) : 0.0f;
+    }
+    return MATPBR_PATH_OK;
 }
 
 int matpbr_path_object_lookup_host(const MatpbrPathObject* objects, int n_objects, const MatpbrPathObjectPbr* pbr, const int32_t* ids, long N,

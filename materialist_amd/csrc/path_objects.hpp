@@ -305,16 +305,25 @@ bool pbr_valid(const MatpbrPathObjectPbr& pr) {
 }
 // `n_smooth` (nullable): where given, a kind may carry MATPBR_PATH_OBJECT_SMOOTH, and the flagged objects are counted.  `n_pbr`
 // (nullable): where given, a kind may be MATPBR_PATH_BSDF_PBR (its p[] is ignored), and those objects are counted; their records
-// are checked where `pbr` is given.
+// are checked where `pbr` is given.  `n_light` (nullable): where given, a kind may be MATPBR_PATH_BSDF_AREA (without the smooth flag; p =
+// radiance, finite and >= 0), and those objects are counted.
 bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, int* n_smooth = nullptr, int* n_pbr = nullptr,
-                  const MatpbrPathObjectPbr* pbr = nullptr) {
+                  const MatpbrPathObjectPbr* pbr = nullptr, int* n_light = nullptr) {
     if (n_objects < 0 || n_objects > MATPBR_PATH_MAX_OBJECTS || (n_objects > 0 && !objects)) return false;
     ot.n = n_objects;
     ot.min_id = INT32_MAX;
     if (n_smooth) *n_smooth = 0;
     if (n_pbr) *n_pbr = 0;
+    if (n_light) *n_light = 0;
     for (int k = 0; k < n_objects; ++k) {
         MatpbrPathObject plain = objects[k];
+        if (n_light && plain.kind == MATPBR_PATH_BSDF_AREA) {   // checked as a diffuse object of reflectance 0: the range alone
+            for (int c = 0; c < 3; ++c)
+                if (!(plain.p[c] >= 0.0f) || !std::isfinite(plain.p[c])) return false;
+            plain.kind = MATPBR_PATH_BSDF_DIFFUSE;
+            plain.p[0] = plain.p[1] = plain.p[2] = 0.0f;
+            ++*n_light;
+        }
         if (n_smooth && (plain.kind & MATPBR_PATH_OBJECT_SMOOTH)) {
             plain.kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
             ++*n_smooth;

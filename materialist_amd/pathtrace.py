@@ -32,6 +32,7 @@ BSDF_DIELECTRIC, BSDF_DIFFUSE = 1, 2
 BSDF_PBR = 3                   # MATPBR_PATH_BSDF_PBR: MatDiffBSDF on the constants of a PathObjectPbr record
 PBR_MIN_ROUGHNESS = 0.07       # the floor the project's roughness maps are clamped to (matpbr_shade.hpp, armhead.py)
 PBR_DEFAULTS = {"albedo": 0.8, "roughness": 0.5, "metallic": 0.0}
+BSDF_AREA = 4                  # MATPBR_PATH_BSDF_AREA: an area light, p = radiance ("Emissive inserted objects")
 OBJECT_SMOOTH = 0x100          # MATPBR_PATH_OBJECT_SMOOTH, OR-ed into PathObject.kind
 
 
@@ -43,6 +44,12 @@ class PathObject(ctypes.Structure):
 class PathObjectPbr(ctypes.Structure):
     """MatpbrPathObjectPbr (include/matpbr_path.h): albedo, roughness and metallic of one object of kind BSDF_PBR."""
     _fields_ = [("a", ctypes.c_float * 3), ("r", ctypes.c_float), ("m", ctypes.c_float), ("reserved", ctypes.c_float * 3)]
+
+
+class PathLights(ctypes.Structure):
+    """MatpbrPathLights (include/matpbr_path.h): the per-light header of a table with objects of kind BSDF_AREA."""
+    _fields_ = [("n_lights", ctypes.c_int32), ("object", ctypes.c_int32 * MAX_OBJECTS), ("first", ctypes.c_int32 * MAX_OBJECTS),
+                ("n_tri", ctypes.c_int32 * MAX_OBJECTS), ("area", ctypes.c_float * MAX_OBJECTS)]
 
 
 class PathTransEdit(ctypes.Structure):
@@ -77,6 +84,10 @@ SIGNATURES = {
     "matpbr_path_object_normal_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
     "matpbr_path_render_objects_pbr": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P]),
     "matpbr_path_object_lookup_host": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_long, _P, _P, _P, _P]),
+    "matpbr_path_light_tables": (ctypes.c_int, [_P, ctypes.c_long, _P, ctypes.c_long, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_long, _P]),
+    "matpbr_path_render_objects_lights": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P]),
+    "matpbr_path_light_sample_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_long, ctypes.c_int, _P, _P, ctypes.c_long] + [_P] * 7),
+    "matpbr_path_light_pdf_host": (ctypes.c_int, [_P, _P, ctypes.c_long, ctypes.c_int, _P, _P, _P, _P, ctypes.c_long, _P, _P]),
     "matpbr_path_object_sample_shading_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
     "matpbr_path_render_trans": (ctypes.c_int, _RENDER + [_P, _P, _P]),
     "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
@@ -105,7 +116,9 @@ DENOISE_SYMBOLS = ("matpbr_path_features", "matpbr_path_features_host", "matpbr_
                    "matpbr_path_denoise_level", "matpbr_path_denoise_level_host", "matpbr_path_denoise_workspace_bytes", "matpbr_path_denoise")
 # added at version 3 as well (PBR inserted objects)
 PBR_SYMBOLS = ("matpbr_path_render_objects_pbr", "matpbr_path_object_lookup_host")
-LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS
+# and (emissive inserted objects)
+LIGHT_SYMBOLS = ("matpbr_path_light_tables", "matpbr_path_render_objects_lights", "matpbr_path_light_sample_host", "matpbr_path_light_pdf_host")
+LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -136,7 +149,8 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        what = "the denoiser" if name in DENOISE_SYMBOLS else "PBR inserted objects" if name in PBR_SYMBOLS else "smooth inserted objects"
+        what = ("the denoiser" if name in DENOISE_SYMBOLS else "PBR inserted objects" if name in PBR_SYMBOLS else
+                "emissive inserted objects" if name in LIGHT_SYMBOLS else "smooth inserted objects")
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 
@@ -239,7 +253,8 @@ def env_sample_host(tables: Dict[str, object], u: np.ndarray):
 
 def object_bsdf(bsdf: dict) -> tuple:
     """{"type": "dielectric", "int_ior", "ext_ior"} | {"type": "diffuse", "reflectance"} -> (kind, (p0, p1, p2));
-    {"type": "pbr", "albedo": scalar or 3 values (0.8), "roughness" (0.5), "metallic" (0)} -> (BSDF_PBR, (a0, a1, a2, r, m)).
+    {"type": "pbr", "albedo": scalar or 3 values (0.8), "roughness" (0.5), "metallic" (0)} -> (BSDF_PBR, (a0, a1, a2, r, m));
+    {"type": "area", "radiance": scalar or 3 values, finite and >= 0 (1)} -> (BSDF_AREA, (r, g, b)): an area light.
     ValueError when bad."""
     kind = bsdf.get("type") if isinstance(bsdf, dict) else None
     if kind == "dielectric":
@@ -266,7 +281,18 @@ def object_bsdf(bsdf: dict) -> tuple:
         if not 0 <= metal <= 1:
             raise ValueError(f"pbr: metallic must lie in [0, 1], got {metal}")
         return BSDF_PBR, (*(float(x) for x in alb), rough, metal)
-    raise ValueError(f"object bsdf type must be 'dielectric', 'diffuse' or 'pbr', got {kind!r}")
+    if kind == "area":
+        try:
+            rad = np.asarray(bsdf.get("radiance", 1.0), dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"area: radiance must be a number or 3 numbers, got {bsdf.get('radiance')!r}") from None
+        if rad.shape not in ((), (1,), (3,)):
+            raise ValueError(f"area: radiance must be a scalar or 3 values, got shape {rad.shape}")
+        rad = np.broadcast_to(rad, (3,))
+        if not (np.isfinite(rad).all() and (rad >= 0).all() and np.isfinite(rad.astype(np.float32)).all()):
+            raise ValueError(f"area: radiance must be finite and >= 0, got {rad.tolist()}")
+        return BSDF_AREA, tuple(float(x) for x in rad)
+    raise ValueError(f"object bsdf type must be 'dielectric', 'diffuse', 'pbr' or 'area', got {kind!r}")
 
 
 def _corner_normals(k: int, ob: dict, Vo: np.ndarray, To: np.ndarray) -> np.ndarray:
@@ -284,14 +310,75 @@ def _corner_normals(k: int, ob: dict, Vo: np.ndarray, To: np.ndarray) -> np.ndar
     return (No / np.where(ln > 0, ln, 1.0)[:, None])[To]
 
 
-def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False, pbr: bool = False):
+def light_tables(V: np.ndarray, T: np.ndarray, table: Sequence[PathObject], records: Optional[Sequence[PathObjectPbr]] = None) -> Optional[dict]:
+    """The light tables of a merged mesh (`merge_objects`' V, T, table and PBR records), built by the library on the host ->
+    {"header": PathLights, "tris" float32 [n_light_tri, 3, 4] = (v0, 0) (e1, 0) (e2, 0) of every light triangle in input order,
+    "cdf" float32 [n_light_tri]: per light the cumulative area / its area, the last entry exactly 1}; None when no object is of kind
+    BSDF_AREA.  PathError where the library refuses the table (a light of total area 0 among the reasons)."""
+    if not any(t.kind & ~OBJECT_SMOOTH == BSDF_AREA for t in table):
+        return None
+    Vv = np.ascontiguousarray(V, dtype=np.float64).reshape(-1, 3)
+    Tt = np.ascontiguousarray(T, dtype=np.int32).reshape(-1, 3)
+    tab, rec = _table_ptrs(table, records)
+    fn = symbol("matpbr_path_light_tables")
+    head, n = PathLights(), ctypes.c_long(0)
+    hp, np_ = ctypes.cast(ctypes.byref(head), _P), ctypes.cast(ctypes.byref(n), _P)
+    check(fn(_ptr(Vv), Vv.shape[0], _ptr(Tt), Tt.shape[0], tab, len(table), rec, hp, None, None, 0, np_), "matpbr_path_light_tables")
+    tris, cdf = np.zeros((n.value, 3, 4), np.float32), np.zeros(n.value, np.float32)
+    check(fn(_ptr(Vv), Vv.shape[0], _ptr(Tt), Tt.shape[0], tab, len(table), rec, hp, _ptr(tris), _ptr(cdf), n.value, np_), "matpbr_path_light_tables")
+    return {"header": head, "tris": tris, "cdf": cdf}
+
+
+def _light_args(lights: dict) -> tuple:
+    """A 16-byte aligned copy of the records and the pointers of the two CPU entry points' first arguments."""
+    n = lights["cdf"].shape[0]
+    raw = np.zeros(n * 12 + 4, np.float32)
+    off = (-raw.ctypes.data % 16) // 4
+    tris = raw[off:off + n * 12]
+    tris[:] = np.asarray(lights["tris"], np.float32).reshape(-1)
+    return tris, ctypes.cast(ctypes.byref(lights["header"]), _P), n
+
+
+def light_sample_host(lights: dict, have_env: bool, po: np.ndarray, u: np.ndarray):
+    """The kernel's emitter choice and light sampler on the CPU: `light_tables`' dict, whether the envmap is emitter 0, spawn points po
+    [N,3] and u [N,4] = dims 2-5 -> {"emitter" [N] (the index among the n_e emitters), "u_re" [N], "record" [N] (the light triangle;
+    -1 for the envmap), "y" [N,3], "wl" [N,3], "dist" [N], "pdf" [N] (0 where the light faces away or dist = 0)}."""
+    P, U = _rows(po, 3), _rows(u, 4)
+    N = _same_rows("po and u must have the same rows", P, U)
+    tris, hp, n = _light_args(lights)
+    cdf = np.ascontiguousarray(lights["cdf"], dtype=np.float32)
+    o = {"emitter": np.empty(N, np.int32), "u_re": np.empty(N, np.float32), "record": np.empty(N, np.int32), "y": np.empty((N, 3), np.float32),
+         "wl": np.empty((N, 3), np.float32), "dist": np.empty(N, np.float32), "pdf": np.empty(N, np.float32)}
+    check(symbol("matpbr_path_light_sample_host")(hp, _ptr(tris), _ptr(cdf), n, int(bool(have_env)), _ptr(P), _ptr(U), N,
+                                                  *(_ptr(o[k]) for k in ("emitter", "u_re", "record", "y", "wl", "dist", "pdf"))),
+          "matpbr_path_light_sample_host")
+    return o
+
+
+def light_pdf_host(lights: dict, have_env: bool, light: np.ndarray, record: np.ndarray, o: np.ndarray, d: np.ndarray):
+    """The hit side's pdf on the CPU with the kernel's routine: rays o, d [N,3] (unit length) that land on light triangle record [N] of
+    light [N] -> (t [N], pdf [N] = t^2 / (A (n_l . -d) n_e), 0 on the back)."""
+    O, D = _rows(o, 3), _rows(d, 3)
+    Lg, Rc = np.ascontiguousarray(light, dtype=np.int32).reshape(-1), np.ascontiguousarray(record, dtype=np.int32).reshape(-1)
+    N = _same_rows("light, record, o and d must have the same rows", O, D, Lg, Rc)
+    tris, hp, n = _light_args(lights)
+    t, pdf = np.empty(N, np.float32), np.empty(N, np.float32)
+    check(symbol("matpbr_path_light_pdf_host")(hp, _ptr(tris), n, int(bool(have_env)), _ptr(Lg), _ptr(Rc), _ptr(O), _ptr(D), N, _ptr(t), _ptr(pdf)),
+          "matpbr_path_light_pdf_host")
+    return t, pdf
+
+
+def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False, pbr: bool = False,
+                  lights: bool = False):
     """The depth mesh with the inserted meshes appended -> (V [Nv,3] float64, T [Nt,3] int32, [PathObject]).  Object k's triangles
     follow the scene's in the order given; its ids are its range of T.  An object may carry "normals" [Nv,3] (per vertex, outward, any
     length): it is smooth ("Smooth inserted objects"), its kind carries OBJECT_SMOOTH, and with `normals=True`
     a fourth value follows, the corner normals [Nt - scene's Nt, 3, 3] float32 of every inserted triangle (unit length, normalised in
     fp64; zero for the objects without normals, which the kernel never reads), or None when no object is smooth.  With `pbr=True`
     one more value follows, the [n_objects] PathObjectPbr records (zero for the objects of another kind, which the kernel never
-    reads); a table entry of kind BSDF_PBR has p = 0."""
+    reads); a table entry of kind BSDF_PBR has p = 0.  With `lights=True` one more value follows, `light_tables` of the merged mesh
+    (None when no object is an area light).  An area light ({"type": "area"}) has kind BSDF_AREA and p = its radiance; with "normals"
+    it is refused."""
     V = [np.asarray(vertices, dtype=np.float64).reshape(-1, 3)]
     T = [np.asarray(triangles, dtype=np.int32).reshape(-1, 3)]
     if len(objects) > MAX_OBJECTS:
@@ -313,6 +400,8 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
             raise ValueError(f"object {k}: vertices must be finite")
         if not np.issubdtype(To.dtype, np.integer) or To.min() < 0 or To.max() >= Vo.shape[0]:
             raise ValueError(f"object {k}: triangle indices must be integers in [0, {Vo.shape[0]})")
+        if ob.get("normals") is not None and kind == BSDF_AREA:
+            raise ValueError(f"object {k}: an area light has no shading normals: it emits from its faces (drop 'normals')")
         if ob.get("normals") is not None:
             corner.append(_corner_normals(k, ob, Vo, To))
             kind |= OBJECT_SMOOTH
@@ -326,7 +415,8 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
     if normals:
         smooth = any(t.kind & OBJECT_SMOOTH for t in table)
         out += (np.ascontiguousarray(np.concatenate(corner), dtype=np.float32) if smooth else None,)
-    return out + ((records,) if pbr else ())
+    out += (records,) if pbr else ()
+    return out + ((light_tables(out[0], out[1], table, records),) if lights else ())
 
 
 def object_lookup_host(table: Sequence[PathObject], records: Optional[Sequence[PathObjectPbr]], ids: np.ndarray):
@@ -583,7 +673,10 @@ class PathTracer:
     of {"vertices" [Nv,3], "triangles" [Nt,3], "bsdf": {"type": "dielectric", "int_ior": 1.49, "ext_ior": 1.000277} or
     {"type": "diffuse", "reflectance": (r, g, b)} or {"type": "pbr", "albedo": (r, g, b), "roughness": r, "metallic": m} (the depth
     mesh's own BSDF on constants; DESIGN.md section 1.4, "PBR inserted objects")} and optionally "normals" [Nv,3] (per vertex,
-    outward): with them the object shades smooth, with the normals interpolated at each hit; without them flat.  A tracer with
+    outward): with them the object shades smooth, with the normals interpolated at each hit; without them flat.  An object with
+    {"type": "area", "radiance": (r, g, b)} is an area light ("Emissive inserted objects"): it emits its
+    radiance from its outward faces, reflects nothing, takes no "normals", and is sampled as an emitter beside the envmap at every
+    vertex (`stats["n_lights"]` counts them; an envmap of zero luminance leaves the lights as the only emitters).  A tracer with
     objects renders forward only."""
 
     def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
@@ -595,14 +688,20 @@ class PathTracer:
         self.obj_nrm: Optional[torch.Tensor] = None   # corner normals of the inserted triangles, when some object is smooth
         self.n_scene_tris = n_scene
         self.pbr = None                               # the PathObjectPbr records, when some object is of kind BSDF_PBR
-        n_smooth = n_pbr = 0
+        self.lights = None                            # (PathLights, tris, cdf on the device), when some object is of kind BSDF_AREA
+        n_smooth = n_pbr = n_lights = 0
         if objects:
-            vertices, triangles, table, corner, records = merge_objects(vertices, triangles, objects, normals=True, pbr=True)
+            vertices, triangles, table, corner, records, lt = merge_objects(vertices, triangles, objects, normals=True, pbr=True, lights=True)
+            if lt is not None:
+                symbol("matpbr_path_render_objects_lights")
+                n_lights = int(lt["header"].n_lights)
+                self.lights = (lt["header"], torch.from_numpy(lt["tris"]).to(self.device), torch.from_numpy(lt["cdf"]).to(self.device))
             self.objects = (PathObject * len(table))(*table)
             n_smooth = sum(1 for t in table if t.kind & OBJECT_SMOOTH)
             n_pbr = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_PBR)
             if n_pbr:
                 symbol("matpbr_path_render_objects_pbr")
+            if n_pbr or lt is not None:               # the light entry point takes the records beside the table as well
                 self.pbr = (PathObjectPbr * len(records))(*records)
             if corner is not None:
                 symbol("matpbr_path_render_objects_normals")
@@ -616,6 +715,7 @@ class PathTracer:
         self.stats["n_object_tris"] = self.stats["n_tris"] - n_scene
         self.stats["n_smooth_objects"] = n_smooth
         self.stats["n_pbr_objects"] = n_pbr
+        self.stats["n_lights"] = n_lights
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -683,6 +783,12 @@ class PathTracer:
             check(lib.matpbr_path_render_normals(*args, nrm.data_ptr()), "matpbr_path_render_normals")
         elif self.objects is None:
             check(lib.matpbr_path_render(*args), "matpbr_path_render")
+        elif self.lights is not None:
+            head, ltris, lcdf = self.lights
+            check(symbol("matpbr_path_render_objects_lights", lib)(*args, table, len(self.objects),
+                                                                   self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,
+                                                                   self.n_scene_tris, records, ctypes.cast(ctypes.byref(head), _P),
+                                                                   ltris.data_ptr(), lcdf.data_ptr()), "matpbr_path_render_objects_lights")
         elif self.pbr is not None:
             check(symbol("matpbr_path_render_objects_pbr", lib)(*args, table, len(self.objects),
                                                                 self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,

@@ -221,12 +221,26 @@ def _check_denoise(denoise: str, integrator: str, spp: int) -> bool:
     return True
 
 
+def _scaled_env(env: np.ndarray, env_scale: float, integrator: str = "path") -> np.ndarray:
+    """The envmap times `env_scale`, before its sampling tables are built (1: the array itself, so the same bits; 0: an envmap of
+    zero luminance, which has no tables: with an area light, the night shot).  The 'sh' render does not take it."""
+    s = float(env_scale)
+    if not (np.isfinite(s) and s >= 0):
+        raise ValueError(f"env_scale must be finite and >= 0, got {env_scale}")
+    if s == 1.0:
+        return env
+    if integrator != "path":
+        raise ValueError("env_scale needs integrator='path' (or render_oi): the 'sh' render projects the envmap as it is")
+    return np.asarray(env, dtype=np.float32) * np.float32(s)
+
+
 _PBR_ALBEDO = 0.8   # pathtrace.PBR_DEFAULTS["albedo"]: what `object_bsdf` gives a "pbr" dict without one
 
 
 def albedo_guide(geom: torch.Tensor, albedo: torch.Tensor, bsdfs=()) -> torch.Tensor:
     """The denoiser's albedo guide [H,W,3] from the features' ids: the albedo map as rendered where the camera ray hits the depth mesh
-    (id 0), a diffuse object's reflectance, a PBR object's albedo, 1 on glass, 0 where it hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
+    (id 0), a diffuse object's reflectance, a PBR object's albedo, 1 on glass and on an area light (the fall-through: a light's
+    pixels are its radiance, which the colour term guides alone), 0 where it hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
     ids = geom[..., 7]
     guide = albedo.to(geom.device, torch.float32).reshape(geom.shape[0], geom.shape[1], 3).clone()
     guide[ids < 0] = 0.0
@@ -252,12 +266,14 @@ def _denoised(pt, render_half, iters: int, seed: int, geom: torch.Tensor, guide:
 
 def render_real(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
                 spp: int = 64, device="cuda", edit: Optional[Dict[str, object]] = None, integrator: str = "sh", max_depth: int = 4,
-                seed: int = 0, shading_normals: str = "face", denoise: str = "off") -> str:
+                seed: int = 0, shading_normals: str = "face", denoise: str = "off", env_scale: float = 1.0) -> str:
     """render_final.py:148-203,241-260: one re-render under `env_path` -> mi_<name>_<env>_<edit flag>.exr / .png.
     integrator "sh": the deterministic render (SH25 light, direct, unshadowed); "path": the path tracer, `max_depth` / `seed`, shading
     with the mesh's face normals or, with `shading_normals="map"`, with best_results/normal.exr whatever the scene is called.
-    `denoise="atrous"` (path only, even `spp`): two renders of spp / 2, seeds `seed` and `seed + 1`, through the a-trous filter."""
+    `denoise="atrous"` (path only, even `spp`): two renders of spp / 2, seeds `seed` and `seed + 1`, through the a-trous filter.
+    `env_scale` (path only): the envmap is multiplied by it before its tables are built; 1 gives the same bits as without it."""
     _check_integrator(integrator, shading_normals)
+    _scaled_env(np.zeros(0, np.float32), env_scale, integrator)
     atrous = _check_denoise(denoise, integrator, spp)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
@@ -266,14 +282,14 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
     if atrous:
         pt = _path_tracer(scene_dir, save_name, mat, device)
         nrm = mat["normal"] if shading_normals == "map" else None
-        env = load_image(env_path)
+        env = _scaled_env(load_image(env_path), env_scale)
         tabs = pt.tables(env)
         geom = pt.features(normal=nrm)
         half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs, normal=nrm)
         img = _denoised(pt, half, 1, seed, geom, albedo_guide(geom, mat["albedo"]))
     elif integrator == "path":
         img = _path_tracer(scene_dir, save_name, mat, device).render(mat["albedo"], mat["roughness"], mat["metallic"],
-                                                                     load_image(env_path), spp, max_depth, seed,
+                                                                     _scaled_env(load_image(env_path), env_scale), spp, max_depth, seed,
                                                                      normal=mat["normal"] if shading_normals == "map" else None)
     else:
         rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))
@@ -312,8 +328,8 @@ OI_SCENE_MAX_OBJECTS = 8                              # pathtrace.MAX_OBJECTS
 def load_oi_scene(path: str) -> List[dict]:
     """An object list file for `render_oi(objects_file=...)`: JSON that holds only settings,
     {"objects": [{"ply": "chrome_ball.ply", "bsdf": {"type": "pbr", "albedo": [0.95, 0.93, 0.88], "roughness": 0.1, "metallic": 1.0},
-    "normals": "vertex"}, ...]}, at most 8 objects.  "ply" is relative to the file; "bsdf" is any of PathTracer's three types
-    (dielectric, diffuse, pbr); "normals" is "flat" (default) or "vertex" (the file's normals if it has them, else
+    "normals": "vertex"}, ...]}, at most 8 objects.  "ply" is relative to the file; "bsdf" is any of PathTracer's four types
+    (dielectric, diffuse, pbr, area: {"type": "area", "radiance": [r, g, b]} is a lamp, which takes "normals": "flat" only); "normals" is "flat" (default) or "vertex" (the file's normals if it has them, else
     `mesh.angle_weighted_normals`) -> [{"ply": absolute path, "bsdf", "normals"}], nothing read yet but the list.  ValueError naming
     the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
     import json
@@ -354,13 +370,15 @@ def load_oi_scene(path: str) -> List[dict]:
         normals = ob.get("normals", "flat")
         if normals not in ("flat", "vertex"):
             raise ValueError(f"{where}: 'normals' must be 'flat' or 'vertex', got {normals!r}")
+        if normals == "vertex" and ob["bsdf"].get("type") == "area":
+            raise ValueError(f"{where}: 'normals' must be 'flat' for an area light: it emits from its faces")
         out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals})
     return out
 
 
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
-              denoise: str = "off", objects_file: Optional[str] = None) -> str:
+              denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0) -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -371,8 +389,10 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     samples do the denoiser's work (spp 64 x 10).  `denoise="atrous"` (even `spp`) runs the project's own filter instead: each of
     the `n_iter` renders becomes two of spp / 2, seeds seed + 2 i and seed + 2 i + 1, summed into two half buffers, and one a-trous
     pass runs over them ("Denoiser"); behind glass only its colour term guides.  `objects_file`: an object
-    list (`load_oi_scene`) whose meshes are inserted instead, each with its own BSDF (dielectric, diffuse or pbr) and its own
-    normals; with it oi.ply and oi2.ply are not looked for and `object_normals` is ignored.  The output names are the same."""
+    list (`load_oi_scene`) whose meshes are inserted instead, each with its own BSDF (dielectric, diffuse, pbr or area: a lamp) and
+    its own normals; with it oi.ply and oi2.ply are not looked for and `object_normals` is ignored.  The output names are the same.
+    `env_scale`: the envmap is multiplied by it before its tables are built (1: the same bits as without it; 0 with an area light in
+    the list: the night shot, lit by the lamp alone)."""
     from . import mesh as _mesh
 
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
@@ -389,6 +409,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     if object_normals not in ("flat", "vertex"):
         raise ValueError(f"object_normals must be 'flat' or 'vertex', got {object_normals!r}")
     atrous = _check_denoise(denoise, "path", spp)
+    _scaled_env(np.zeros(0, np.float32), env_scale)
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
     for p, b, normals in have:
@@ -398,7 +419,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
             objects[-1]["normals"] = Nn if Nn is not None else _mesh.angle_weighted_normals(V, T)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
     pt = _path_tracer(scene_dir, save_name, mat, device, objects)
-    env = load_image(env_path)
+    env = _scaled_env(load_image(env_path), env_scale)
     tabs = pt.tables(env)
     if atrous:
         geom = pt.features()
@@ -475,16 +496,18 @@ def render_trans(save_name: str, ior: float = 1.2, keep_albedo_color: bool = Fal
 def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int = 36, rotation_step: float = 10.0,
                           input_path: Optional[str] = None, save_path: Optional[str] = None, spp: int = 64, device="cuda",
                           write_frames: bool = True, edit: Optional[Dict[str, object]] = None, integrator: str = "sh",
-                          max_depth: int = 4, seed: int = 0, shading_normals: str = "face", denoise: str = "off") -> Dict[str, object]:
+                          max_depth: int = 4, seed: int = 0, shading_normals: str = "face", denoise: str = "off",
+                          env_scale: float = 1.0) -> Dict[str, object]:
     """render_final.py:300-418: `frames` renders, the envmap rolled by int(angle/360*W) columns per frame.  integrator "sh": the
     rolled light is the SH rotation of the projected envmap; "path": the path tracer renders the rolled texels themselves (`shading_normals` as in `render_real`).
     `denoise="atrous"` (path only, even `spp`): every frame is two renders of spp / 2, seeds `seed` and `seed + 1`, through the a-trous
-    filter; the features are computed once for all frames."""
+    filter; the features are computed once for all frames.  `env_scale` (path only): the envmap is multiplied by it first."""
     _check_integrator(integrator, shading_normals)
+    _scaled_env(np.zeros(0, np.float32), env_scale, integrator)
     atrous = _check_denoise(denoise, integrator, spp)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     env_path = find_envmap(save_name, env_path, input_path)
-    env = load_image(env_path)
+    env = _scaled_env(load_image(env_path), env_scale, integrator)
     We = env.shape[1]
     light0 = envmap_to_light(env)
     shifts = [int((f * rotation_step / 360.0) * We) for f in range(frames)]   # rotate_envmap (:290-298)

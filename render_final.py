@@ -38,12 +38,19 @@ def parse_args(argv=None):
                     help="--mode oi: flat = face normals; vertex = each .ply shades smooth with its vertex normals (angle-weighted ones if it has none)")
     ap.add_argument("--oi_scene", type=str, default=None, metavar="FILE.json",
                     help='--mode oi: an object list, {"objects": [{"ply": path relative to the file, "bsdf": {"type": "pbr", "albedo": [r, g, b], '
-                         '"roughness": r, "metallic": m} (or a "dielectric" or "diffuse" one), "normals": "flat" or "vertex"}, ...]}, at most 8 '
+                         '"roughness": r, "metallic": m} (or a "dielectric" or "diffuse" one, or {"type": "area", "radiance": [r, g, b]}, a lamp), "normals": "flat" or "vertex"}, ...]}, at most 8 '
                          "objects; with it <scene>/oi.ply and <scene>/oi2.ply are not looked for and --oi_normals is ignored")
+    ap.add_argument("--env_scale", type=float, default=1.0, metavar="S",
+                    help="--integrator path and --mode oi: multiply the envmap by S before its sampling tables are built (1 = the same bits as "
+                         "without it; 0 with an area light in --oi_scene = the night shot, lit by the lamp alone)")
     ap.add_argument("--oi_max_depth", type=int, default=16, help="--mode oi: Mitsuba's max_depth (a camera path through glass needs 5 to see light)")
     a = ap.parse_args(argv)
     if a.shading_normals == "map" and (a.integrator != "path" or a.mode == "oi"):
         ap.error("--shading_normals map needs --integrator path and --mode real or rolling (inserted objects know no normal map)")
+    if not (a.env_scale >= 0 and a.env_scale < float("inf")):
+        ap.error("--env_scale must be finite and >= 0")
+    if a.env_scale != 1.0 and a.mode != "oi" and a.integrator != "path":
+        ap.error("--env_scale needs --integrator path (or --mode oi): the sh render projects the envmap as it is")
     if a.denoise == "atrous":
         if a.mode != "oi" and a.integrator != "path":
             ap.error("--denoise atrous needs --integrator path (or --mode oi): the sh render is deterministic and has no noise to filter")
@@ -57,7 +64,8 @@ def main(argv=None):
     from materialist_amd import relight
 
     edit = {"albedo": a.edit_albedo, "roughness": a.edit_roughness, "metallic": a.edit_metallic}
-    it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed, "shading_normals": a.shading_normals, "denoise": a.denoise}
+    it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed, "shading_normals": a.shading_normals, "denoise": a.denoise,
+          "env_scale": a.env_scale}
     if a.mode == "real":
         print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it))
     elif a.mode == "rolling":
@@ -66,7 +74,8 @@ def main(argv=None):
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
         print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
-                                                 object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene))
+                                                 object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene,
+                                                 env_scale=a.env_scale))
     else:
         raise ValueError("Invalid mode")
 

@@ -1,0 +1,283 @@
+"""Emissive inserted objects on the GPU (libmatpbr_path.so's `matpbr_path_render_objects_lights`, DESIGN.md section 1.4, "Emissive
+inserted objects"): every path of a table with two lights and every other object kind against the fp64 restatement, the two closed
+forms of tests/test_path_light_host.py on the device, bits (launch splits, a table without lights, the routes `render` took before, a
+black light), the refusals, the features of a light, and `render_final.py --mode oi --oi_scene lamp.json` with and without the
+denoiser and with `--env_scale 0`."""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import path_fp64 as pf  # noqa: E402
+import path_light_fp64 as pl  # noqa: E402
+import path_oi_fp64 as po  # noqa: E402
+import path_oi_pbr_fp64 as pp  # noqa: E402
+import path_testlib as tl  # noqa: E402
+from path_testlib import bits as _bits, parity as _parity, raw_args as _raw_args  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+FOV = pf.FOV
+SEEDS = list(range(100, 164))      # the closed forms' 64 fixed seeds (tests/test_path_light_host.py)
+
+
+@pytest.fixture(scope="module")
+def pt():
+    return tl.load(gpu=True)
+
+
+_report = tl.reporter("path lights", "test_gpu_path_lights")
+
+
+@pytest.fixture(scope="module")
+def scene(pt):
+    """The groove at 24 x 20 (a partial tile) with `path_light_fp64.table_scene` in front of it: the unequal-sided emitter box, an
+    emitter quad, a smooth glass icosphere, a flat PBR cube and a diffuse cube in one table."""
+    s = tl.groove_with_objects(pt, pl.table_scene(), pl.merged)
+    st = s["tracer"].stats
+    assert st["n_objects"] == 5 and st["n_lights"] == 2 and st["n_pbr_objects"] == 1 and st["n_smooth_objects"] == 1
+    assert s["tracer"].lights is not None
+    return s
+
+
+# ---- 1 ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("env_on", [True, False])
+def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64, env_on):
+    """At least 0.99 of the pixels within 1e-3 at spp 1 (`path_testlib.parity`; on the CPU the restatement over the library's fp32
+    traversal and over the fp64 brute force disagrees in no pixel of these renders, test_path_light_host.py), with the envmap on
+    (n_e = 3) and zero (n_e = 2).  Every render holds every kind of light path (a light behind glass needs max_depth 3)."""
+    s = scene
+    H, W = s["H"], s["W"]
+    env = s["env"] if env_on else np.zeros_like(s["env"])
+    tab = pt.env_tables(env)
+    seen = {k: 0 for k in pl.RECORD_KEYS}
+    for max_depth in (2, 6, 16):
+        for seed in (0, 1, 2):
+            got = s["tracer"].render(s["a"], s["r"], s["m"], env, spp=1, max_depth=max_depth, seed=seed).cpu().numpy().astype(np.float64)
+            assert np.isfinite(got).all()
+            ref, rec = pl.replay_lights(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], env, tab, H, W, max_depth, seed, s["table"])
+            assert rec["n_e"] == 2 + env_on
+            frac, err = _parity(got, ref)
+            _report(f"per-path parity with lights, envmap {'on' if env_on else 'zero'}, max_depth {max_depth} seed {seed}: share of pixels within 1e-3",
+                    f"{frac:.4f} ({int((err > 1e-3).sum())} flipped paths, max err {err.max():.3e})")
+            assert frac >= 0.99, (max_depth, seed, frac, np.argwhere(err > 1e-3)[:10])
+            for k in pl.RECORD_KEYS:
+                assert rec[k].any() or (k == "light_through_glass" and max_depth == 2), (k, max_depth, seed)
+                seen[k] += int(rec[k].sum())
+    _report(f"envmap {'on' if env_on else 'zero'}: pixels with " + " / ".join(pl.RECORD_KEYS) + " (9 renders)", " / ".join(str(seen[k]) for k in pl.RECORD_KEYS))
+
+
+# ---- 2 ---------------------------------------------------------------------------------------------------------------------------------
+def _closed_form(pt, objects, env, max_depth, expected, covered, label, H=10, W=12):
+    Vs, Ts = pp.FAR_TRIANGLE
+    tracer = pt.PathTracer(Vs, Ts, H, W, FOV, objects=objects)
+    maps = (np.zeros((H, W, 3), np.float32), np.ones((H, W, 1), np.float32), np.zeros((H, W, 1), np.float32))
+    tabs = tracer.tables(env)
+    vals = np.stack([tracer.render(*maps, env, spp=16, max_depth=max_depth, seed=sd, spp_per_launch=16, tables=tabs).cpu().numpy() for sd in SEEDS])
+    assert np.isfinite(vals).all()
+    ok, worst = pl.within_five_sigma(vals.astype(np.float64), expected, covered)
+    _report(f"{label}, on the device: worst |mean - expected| / (5 se + 1e-3 expected) over {int(covered.sum())} pixels", f"{worst:.3f}")
+    assert covered.sum() >= 12 and ok, (label, worst)
+
+
+def test_lamberts_polygon_formula(pt):
+    """Host test 3 (a) on the device: the same scene, the same 64 seeds x spp 16 at 12 x 10, the same bound."""
+    expected, covered = pl.lambert_expected(10, 12)
+    _closed_form(pt, pl.lambert_scene(), np.zeros((4, 8, 3), np.float32), 2, expected, covered, "Lambert's polygon formula")
+
+
+@pytest.mark.parametrize("inner,max_depth", [("diffuse", 2), ("glass", 16)])
+@pytest.mark.parametrize("env_value", [0.0, 5.0])
+def test_the_furnace_box(pt, inner, max_depth, env_value):
+    """Host test 3 (b) on the device: rho L on the diffuse object at max_depth 2, L through the glass sphere at max_depth 16, with a
+    zero envmap and with a bright one that the box hides."""
+    objects = pl.furnace_scene(inner)
+    inside, _ = tl.footprints(objects[1:], 10, 12)
+    value = (np.asarray(pl.FURNACE_RHO) if inner == "diffuse" else np.ones(3)) * pl.f32(pl.FURNACE_L)
+    expected = np.broadcast_to(value, (10, 12, 3)).copy()
+    _closed_form(pt, objects, np.full((4, 8, 3), env_value, np.float32), max_depth, expected, inside, f"furnace, {inner}, envmap {env_value}")
+
+
+# ---- 3 ---------------------------------------------------------------------------------------------------------------------------------
+def _light_tail(pt, tracer):
+    head, ltris, lcdf = tracer.lights if tracer.lights is not None else (None, None, None)
+    table, records = pt._table_ptrs(tracer.objects, tracer.pbr)
+    return (table, len(tracer.objects), tracer.obj_nrm.data_ptr() if tracer.obj_nrm is not None else None, tracer.n_scene_tris, records,
+            ctypes.cast(ctypes.byref(head), ctypes.c_void_p) if head is not None else None, ltris.data_ptr() if ltris is not None else None,
+            lcdf.data_ptr() if lcdf is not None else None)
+
+
+def test_bits(pt, scene, oracle64):
+    s = scene
+    maps = (s["a"], s["r"], s["m"], s["env"])
+    H, W, rm = s["H"], s["W"], s["rm"]
+    # every split of a frame into launches gives the same bits
+    whole = s["tracer"].render(*maps, spp=6, max_depth=16, seed=7, spp_per_launch=6)
+    for split in (1, 3, 4):
+        assert np.array_equal(_bits(whole), _bits(s["tracer"].render(*maps, spp=6, max_depth=16, seed=7, spp_per_launch=split))), split
+    # a table without lights through the new entry point: matpbr_path_render_objects_pbr's bits, with and without light arguments
+    old = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=pp.table_scene())
+    assert old.stats["n_lights"] == 0 and old.lights is None and old.pbr is not None
+    ref = torch.empty(H, W, 3, device=old.device)
+    keep, args = _raw_args(old, maps, 6, 16, 5, 4, ref)
+    tail = _light_tail(pt, old)
+    assert pt.symbol("matpbr_path_render_objects_pbr")(*args, *tail[:5]) == 0
+    head, ltris, lcdf = s["tracer"].lights
+    for extra in (tail[5:], (ctypes.cast(ctypes.byref(head), ctypes.c_void_p), ltris.data_ptr(), lcdf.data_ptr())):
+        out = torch.empty(H, W, 3, device=old.device)
+        _, args2 = _raw_args(old, maps, 6, 16, 5, 4, out)
+        assert pt.symbol("matpbr_path_render_objects_lights")(*args2, *tail[:5], *extra) == 0
+        assert np.array_equal(_bits(out), _bits(ref))
+    # PathTracer.render without lights takes the routes it took: PBR objects, flat objects, no objects
+    assert np.array_equal(_bits(old.render(*maps, spp=6, max_depth=16, seed=5, spp_per_launch=4)), _bits(ref))
+    flat = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=po.two_cubes())
+    assert flat.pbr is None and flat.lights is None and flat.stats["n_lights"] == 0
+    ref = torch.empty(H, W, 3, device=flat.device)
+    keep, args = _raw_args(flat, maps, 6, 16, 5, 4, ref)
+    assert pt.load().matpbr_path_render_objects(*args, ctypes.cast(flat.objects, ctypes.c_void_p), len(flat.objects)) == 0
+    assert np.array_equal(_bits(flat.render(*maps, spp=6, max_depth=16, seed=5, spp_per_launch=4)), _bits(ref))
+    bare = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV)
+    assert bare.lights is None and bare.stats["n_lights"] == 0
+    ref = torch.empty(H, W, 3, device=bare.device)
+    keep, args = _raw_args(bare, maps, 6, 4, 5, 4, ref)
+    assert pt.load().matpbr_path_render(*args) == 0
+    assert np.array_equal(_bits(bare.render(*maps, spp=6, max_depth=4, seed=5, spp_per_launch=4)), _bits(ref))
+    # the light entry point through PathTracer.render is the raw call
+    out = torch.empty(H, W, 3, device=old.device)
+    _, args3 = _raw_args(s["tracer"], maps, 6, 16, 5, 4, out)
+    assert pt.symbol("matpbr_path_render_objects_lights")(*args3, *_light_tail(pt, s["tracer"])) == 0
+    assert np.array_equal(_bits(s["tracer"].render(*maps, spp=6, max_depth=16, seed=5, spp_per_launch=4)), _bits(out))
+    # a light of radiance 0 beside an envmap is not the render without it (n_e changed); it is finite and the restatement's
+    Vd, Td = po.cube(*pl.DIFFUSE_CUBE)
+    Vq, Tq = pl.quad(pl.LIGHT_QUAD)
+    cube = {"vertices": Vd, "triangles": Td, "bsdf": po.DIFFUSE_08}
+    black = [cube, {"vertices": Vq, "triangles": Tq, "bsdf": {"type": "area", "radiance": 0.0}}]
+    occluder = [cube, {"vertices": Vq, "triangles": Tq, "bsdf": {"type": "diffuse", "reflectance": 0.0}}]
+    with_black = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=black)
+    without = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, FOV, objects=occluder)
+    assert with_black.stats["n_lights"] == 1 and without.stats["n_lights"] == 0
+    got = with_black.render(*maps, spp=1, max_depth=6, seed=3)
+    assert bool(torch.isfinite(got).all()) and not np.array_equal(_bits(got), _bits(without.render(*maps, spp=1, max_depth=6, seed=3)))
+    V, T, table = pl.merged(rm["vertices"], rm["triangles"], black)
+    ref64, rec = pl.replay_lights(oracle64, V, T, *maps, pt.env_tables(s["env"]), H, W, 6, 3, table)
+    frac, err = _parity(got.cpu().numpy().astype(np.float64), ref64)
+    _report("a light of radiance 0 beside the envmap, spp 1 max_depth 6: share of pixels within 1e-3", f"{frac:.4f}")
+    assert rec["n_e"] == 2 and frac >= 0.99
+
+
+# ---- 4 ---------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_and_features(pt, scene):
+    s = scene
+    H, W = s["H"], s["W"]
+    with pytest.raises(ValueError, match="objects"):
+        s["tracer"].render_bwd(s["a"], s["r"], s["m"], s["env"], np.ones((H, W, 3), np.float32), spp=1)
+    with pytest.raises(ValueError, match="objects"):
+        s["tracer"].render_trans(s["a"], s["r"], s["m"], s["env"], np.ones((H, W), bool), np.ones((H, W, 3), np.float32), spp=1)
+    with pytest.raises(ValueError, match="objects"):
+        s["tracer"].render(s["a"], s["r"], s["m"], s["env"], spp=1, normal=np.tile(np.float32([0, 0, 1]), (H, W, 1)))
+    Vq, Tq = pl.quad(pl.LIGHT_QUAD)
+    for rad in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="radiance"):
+            pt.PathTracer(s["rm"]["vertices"], s["rm"]["triangles"], H, W, FOV, objects=[{"vertices": Vq, "triangles": Tq, "bsdf": {"type": "area", "radiance": rad}}])
+    with pytest.raises(ValueError, match="normals"):
+        pt.PathTracer(s["rm"]["vertices"], s["rm"]["triangles"], H, W, FOV,
+                      objects=[{"vertices": Vq, "triangles": Tq, "bsdf": pl.QUAD_LIGHT, "normals": np.tile([0.0, 0.0, 1.0], (4, 1))}])
+    with pytest.raises(pt.PathError, match="matpbr_path_light_tables"):                      # a light of total area 0
+        pt.PathTracer(s["rm"]["vertices"], s["rm"]["triangles"], H, W, FOV,
+                      objects=[{"vertices": Vq, "triangles": np.array([[0, 0, 1]], np.int32), "bsdf": pl.QUAD_LIGHT}])
+    # a header spoiled behind the binding's back: the library refuses it
+    Vs, Ts = pp.FAR_TRIANGLE
+    tracer = pt.PathTracer(Vs, Ts, 8, 8, FOV, objects=[{"vertices": Vq, "triangles": Tq, "bsdf": pl.QUAD_LIGHT}])
+    maps = (np.full((8, 8, 3), 0.5, np.float32), np.full((8, 8, 1), 0.5, np.float32), np.zeros((8, 8, 1), np.float32))
+    tracer.lights[0].area[0] = 0.0
+    with pytest.raises(pt.PathError, match="matpbr_path_render_objects_lights"):
+        tracer.render(*maps, np.ones((4, 8, 3), np.float32), spp=1)
+    # features: a light has id 1 + k and its face normal; the device agrees with the CPU routine
+    geom = s["tracer"].features().cpu().numpy()
+    Vm, Tm, tb, corner, _ = pt.merge_objects(s["rm"]["vertices"], s["rm"]["triangles"], s["objects"], normals=True, pbr=True)
+    n_scene = s["rm"]["triangles"].shape[0]
+    host = pt.features_host(pt.build_bvh(Vm, Tm, n_scene), H, W, FOV, tb, corner, n_scene)
+    ids = host[..., 7]
+    assert np.array_equal(geom[..., 7], ids) and set(np.unique(ids)) >= {0.0, 1.0, 2.0}
+    assert np.abs(geom[..., 4:7] - host[..., 4:7]).max() <= 1e-5
+    P = Vm[Tm]
+    fn = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    fn /= np.linalg.norm(fn, axis=-1, keepdims=True)
+    for k in (0, 1):                                                                         # the two lights: some face normal of theirs
+        sl = slice(tb[k].first_tri, tb[k].first_tri + tb[k].n_tri)
+        px = host[ids == 1 + k][:, 4:7]
+        assert px.shape[0] > 0 and (np.abs(px[:, None] - fn[sl][None]).max(-1).min(-1) <= 1e-5).all()
+
+
+# ---- 5 ---------------------------------------------------------------------------------------------------------------------------------
+def test_render_final_cli_lamp(pt, tmp_path):
+    """`render_final.py --mode oi --oi_scene lamp.json` with a lamp and a diffuse block writes mi_oi_<name>_<env>.exr/.png, the bits of
+    the direct PathTracer calls; with `--denoise atrous` the image is finite; with `--env_scale 0` (the night shot: the no-tables
+    branch, the lamp the only emitter) the lamp's pixels are its radiance and the mesh is lit by it alone."""
+    from materialist_amd import mesh, relight
+    from materialist_amd.imageio_exr import read_exr
+
+    tmp = str(tmp_path)
+    scene_dir = tl.synthetic_output(tmp)
+    Vl, Tl = pl.quad([[-0.06, 0.10, -0.95], [0.06, 0.10, -0.95], [0.06, 0.06, -0.85], [-0.06, 0.06, -0.85]])   # faces down and back, at the mesh
+    Vl = Vl.astype(np.float32).astype(np.float64)
+    Vg, Tg = po.cube((-0.09, -0.03, -0.9), 0.1, (0.4, 0.5, 0.3))
+    os.makedirs(os.path.join(tmp, "lists"))
+    mesh.write_ply(os.path.join(tmp, "lists", "lamp.ply"), Vl, Tl)
+    mesh.write_ply(os.path.join(tmp, "lists", "block.ply"), Vg, Tg)
+    lamp = {"type": "area", "radiance": [30.0, 28.0, 22.0]}
+    listing = os.path.join(tmp, "lists", "lamp.json")
+    with open(listing, "w") as f:
+        json.dump({"objects": [{"ply": "lamp.ply", "bsdf": lamp}, {"ply": "block.ply", "bsdf": po.DIFFUSE_08}]}, f)
+    cli = [sys.executable, os.path.join(ROOT, "render_final.py"), "--save_name", "case", "--input_path", tmp, "--save_path", tmp,
+           "--mode", "oi", "--spp", "4", "--oi_iters", "2", "--oi_max_depth", "8", "--oi_scene", listing]
+    mat = relight.load_estimated_brdf(os.path.join(scene_dir, "best_results"))
+    env = relight.load_image(os.path.join(scene_dir, "best_results", "envmap.hdr"))
+    objects = []
+    for name, bsdf in (("lamp.ply", lamp), ("block.ply", po.DIFFUSE_08)):
+        V, T = mesh.read_ply_any(os.path.join(tmp, "lists", name))
+        objects.append({"vertices": V, "triangles": T, "bsdf": bsdf})
+    tracer = relight._path_tracer(scene_dir, "case", mat, "cuda", objects)
+    assert tracer.stats["n_lights"] == 1 and tracer.stats["n_objects"] == 2
+    exr, png = (os.path.join(tmp, "case", "mi_oi_case_envmap" + ext) for ext in (".exr", ".png"))
+    maps = (mat["albedo"], mat["roughness"], mat["metallic"])
+
+    def run(extra):
+        for path in (exr, png):
+            if os.path.exists(path):
+                os.remove(path)
+        res = subprocess.run(cli + extra, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout + res.stderr
+        assert os.path.exists(png)
+        img = np.ascontiguousarray(read_exr(exr)[..., :3], dtype=np.float32)
+        assert np.isfinite(img).all() and (img >= 0).all() and float(img.std()) > 0
+        return img
+
+    def direct(envmap):
+        acc = torch.zeros_like(mat["albedo"])
+        for seed in (0, 1):
+            acc += tracer.render(*maps, envmap, spp=4, max_depth=8, seed=seed)
+        return (acc / 2).cpu().numpy()
+
+    assert np.array_equal(run([]).view(np.uint32), direct(env).view(np.uint32))
+    assert np.array_equal(run(["--env_scale", "1"]).view(np.uint32), direct(env).view(np.uint32))
+    run(["--denoise", "atrous"])
+    night = run(["--env_scale", "0"])
+    assert np.array_equal(night.view(np.uint32), direct(np.zeros_like(env)).view(np.uint32))
+    ids = tracer.features()[..., 7].cpu().numpy()
+    lit = tl.erode(ids == 1)
+    if lit.any():                                                                            # the lamp's front, seen whole: its radiance
+        assert np.all(np.isin(night[lit], np.float32([30.0, 28.0, 22.0, 0.0])))
+    assert night[ids == 0].max() > 0                                                         # the mesh is lit by the lamp alone
+    guide = relight.albedo_guide(tracer.features(), mat["albedo"], [lamp, po.DIFFUSE_08]).cpu().numpy()
+    assert np.all(guide[ids == 1] == 1.0) and np.all(guide[ids == 2] == np.float32(0.8))
