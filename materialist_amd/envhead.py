@@ -22,11 +22,10 @@ import torch
 from . import _lib, ops
 from . import loss as _loss
 from . import render as _render
+from .armhead import FlatOpt, _al4
 
-_al4 = lambda n: (n + 3) // 4 * 4
 
-
-class EnvMlpPhase:
+class EnvMlpPhase(FlatOpt):
     def __init__(self, scene: _render.Scene, gt_image: torch.Tensor, net: torch.nn.Module, start_envmap: torch.Tensor, spp: int = 64,
                  lr: float = 1e-3, patience: int = 0, min_delta: float = 0.0, best_mse: Optional[torch.Tensor] = None,
                  history_len: int = 5000, use_graph: bool = True, env_size=(16, 32)):
@@ -50,20 +49,8 @@ class EnvMlpPhase:
             raise ValueError("the envmap MLP runs on the small-tile kernels: at most 1024 texels")
         self.M, self.d0, self.L = M, d0, net.n_layers
         lins = [(getattr(net, f"lin{l}").linear if l < self.L - 1 else getattr(net, f"lin{l}")) for l in range(self.L)]
-        from .armhead import flat_state
-
-        st = flat_state(net, dev)   # validates that the module's parameters still alias the flat buffer on this device, rebuilds otherwise
-        self.flat, self.views = st["flat"], st["views"]
-        self.gflat = torch.zeros_like(self.flat)
-        self.adam_m, self.adam_v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)    # a fresh Adam per phase (:225-229)
-        self.hyper = torch.tensor([float(lr), 0.0], dtype=torch.float32, device=dev)
-        gviews, off = [], 0
-        for wp, bp in self.views:
-            gw = self.gflat[off:off + wp.numel()].view_as(wp)
-            off += wp.numel()
-            gb = self.gflat[off:off + _al4(bp.numel())]
-            off += _al4(bp.numel())
-            gviews.append((gw, gb))
+        FlatOpt.__init__(self, net, dev, lr, snapshot=False)    # a fresh Adam per phase (:225-229); SaveBest keeps the envmap, not the weights
+        gviews = self.gviews
         # ---- activations ---------------------------------------------------------------------------------------------------------
         E = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
         self.x0p = E(M, _al4(d0))
@@ -160,9 +147,6 @@ class EnvMlpPhase:
     FUSED_TAIL = True       # False: matpbr_env_phase_step + matpbr_select_improved + matpbr_env_project_bwd (the same bits: tests/test_gpu_parity.py)
 
     # ------------------------------------------------------------------------------------------------------------------------------
-    def set_lr(self, lr: float) -> None:
-        self.hyper[0:1].fill_(float(lr))
-
     def _body(self) -> None:
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
         for i, (fn, args) in enumerate(self._calls):
@@ -327,7 +311,9 @@ class EnvTexelPhase:
         _lib.check(fn(*args, stream), "matpbr_env_texel_phase_step")
         self._first = False
 
-    set_lr = EnvMlpPhase.set_lr
+    def set_lr(self, lr: float) -> None:
+        self.hyper[0:1].fill_(float(lr))
+
     step = EnvMlpPhase.step
     step_many, UNROLL_MAX = EnvMlpPhase.step_many, EnvMlpPhase.UNROLL_MAX
     poll = EnvMlpPhase.poll

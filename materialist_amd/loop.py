@@ -1228,8 +1228,8 @@ class PosMlpNormalPhase:
             self.orig["normal"] = self.start[:, 5:8].reshape(H, W, 3)
         self.saver = saver if saver is not None else DeviceSaveBest()
         self._t, self.ops = 0, None          # (`ops` and the device buffers: set up by the first `_step_device`)
-        # round 6: the network launch by launch on the C ABI (armhead.MlpEngine: forward, backward products, AdamW with SaveBest's weight snapshot --
-        # no autograd graph, no framework optimiser); the head (tanh / residual / clamps / normalize) and its backward are element-wise passes here
+        # round 6: the network launch by launch on the C ABI (armhead.MlpEngine without a head: forward, backward products, AdamW with SaveBest's
+        # weight snapshot and StepLR -- no autograd graph, no framework optimiser); the head (tanh / residual / clamps / normalize) and its backward are element-wise passes here
         # the launches of `_step_device` are the deterministic render's: under the path integrator the render is the operator face's
         self.device_loss = self.DEVICE_LOSS and self.armn and mask is None and gt_image.is_cuda and scene.integrator != "path"
         self.engine = None
@@ -1239,10 +1239,7 @@ class PosMlpNormalPhase:
             if MlpEngine.why_not(net, self.start.shape[0], gt_image.device) is None:
                 self.engine = MlpEngine(net, self.start, lr=lr)
         if self.engine is not None:
-            import types
-
-            self.opt, self.sched = types.SimpleNamespace(param_groups=[{"lr": float(lr)}]), None      # what the callers read back
-            self._sched_epoch, self._bw = 0, None
+            self.opt, self.sched, self._bw = self.engine.opt, None, None      # (`opt.param_groups[0]["lr"]`: what the callers read back)
         else:
             self.opt = _make_adamw(net.parameters(), lr)
             self.sched = torch.optim.lr_scheduler.StepLR(self.opt, step_size=100, gamma=0.8)
@@ -1370,13 +1367,8 @@ class PosMlpNormalPhase:
         if self.engine is not None:
             self._engine_backward(grads, live)                                           # :544
             self.saver.best_loss = self.stats[0, o.STAT_BEST].clone()
-            self.engine.adamw_step(self.stats)                                           # AdamW + SaveBest's copy of the weights (:546-547) in one launch
-            lr_now = self.opt.param_groups[0]["lr"]
-            if lr_now > 1.5e-4:                                                          # StepLR(100, 0.8), stepped while lr > 1.5e-4 (:553-554)
-                self._sched_epoch += 1
-                if self._sched_epoch % 100 == 0:
-                    self.engine.set_lr(lr_now * 0.8)
-                    self.opt.param_groups[0]["lr"] = lr_now * 0.8
+            self.engine.adamw_step(self.stats, self.engine.weight_decay)                 # AdamW + SaveBest's copy of the weights (:546-547) in one launch
+            self.engine.step_lr()                                                        # :553-554
             self._t += 1
             return self.stats[0, o.STAT_MSE].clone()
         torch.autograd.backward([maps[k] for k in live], [grads[k].reshape(maps[k].shape) for k in live])      # :544
