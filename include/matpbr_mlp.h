@@ -164,8 +164,14 @@ int matpbr_mlp_chain_fwd(const float* x0, int ldx0, const void* images, float* c
  * consecutive pixels) has ONE power-of-two exponent that brings its largest |g| to [2^13, 2^14), taken from `g_tile_max` -- [M / 128] f32
  * bit patterns of the tiles' largest |g|, which the kernel that PRODUCED g filled by atomic max into an array the caller zeroed (bit patterns
  * of magnitudes order as values: the result does not depend on the order of the adds).  Within a tile, elements down to 2^-16 of the largest
- * keep the 2^-24 relative accuracy of two pieces, smaller ones are carried to an absolute 2^-39 of it; against fp64 the products' error is
- * that of the three-bf16-piece form and of the exact-f32 kernels (tests/test_gpu_parity.py::test_block_scaled_f16_backward_products).
+ * keep the 2^-23 relative accuracy of two round-to-nearest f16 pieces (one f32 ulp: the second piece drops at most one bit), smaller ones are
+ * carried to an absolute 2^-38 of it (2^-25, half the spacing of f16 subnormals, under a largest of at least 2^13); the low x low product
+ * that is not formed is at most 2^-22 of |g| |w|.  Tiny tiles: the exponent is limited so that the scale stays finite -- a tile whose largest
+ * |g| is below 2^-113 (1e-34), subnormal tiles included, is scaled by 2^126 and its elements are carried to an absolute 2^-151, i.e. exactly;
+ * its results are finite and round as f32 subnormals do (2^-149).  A maximum that is not finite propagates as it is.  Against fp64 the
+ * products' error is that of the three-bf16-piece form and of the exact-f32 kernels
+ * (tests/test_gpu_parity.py::test_block_scaled_f16_backward_products); tests/posmlp_bwd_fp64.py derives a bound per output element from the
+ * constants above and tests/test_gpu_posmlp_bwd_fp64.py holds each kernel to it on its own.
  * The weight operand is an MATPBR_WSPLIT_F16X2 image (of the transposed forward weight for the input gradient).
  *   matpbr_mlp_out_layer_bwd_tmax    matpbr_mlp_out_layer_bwd that also fills g_tile_max for the g_prev it writes
  *   matpbr_mlp_layer_bwd_input_blk   matpbr_mlp_layer_bwd_input_bx_sgn (sign-carrying sines below) on these pieces; out_tile_max (nullable):

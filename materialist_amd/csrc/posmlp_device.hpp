@@ -73,14 +73,20 @@ __device__ __forceinline__ void arm_head_store(const ArmHead& h, long m, const f
 // Gradients on two f16 pieces (round 5).  A loss gradient has no natural size, so a 128-row tile of G travels as 2^-e (p1 + p2) with ONE
 // exponent e per tile -- the tile's largest |g| is brought to [2^13, 2^14) (f16 overflows at 2^16) -- taken from `tile_max`, which the
 // kernel that produced G filled (an atomic max over bit patterns: order-free).  Elements within 2^-16 of their tile's largest keep the
-// 2^-24 relative accuracy of two pieces; smaller ones are carried to an absolute 2^-39 of it.  Rows of one tile are 128 consecutive pixels.
+// 2^-23 relative accuracy of two pieces (one f32 ulp); smaller ones are carried to an absolute 2^-38 of it (half the spacing of f16
+// subnormals, 2^-25, under a largest of 2^13).  Rows of one tile are 128 consecutive pixels.
+// The exponent stops at -112: a tile whose largest is below 2^-113 (1e-34; subnormal tiles included) is scaled by 2^126, the largest finite
+// scale whose inverse is a normal float -- its elements are then carried to an absolute 2^-151, below the spacing of f32 subnormals.
+// (tests/posmlp_bwd_fp64.py derives these constants; tests/test_gpu_posmlp_bwd_fp64.py holds every kernel to them.)
 __device__ __forceinline__ void block_scale(unsigned max_bits, float& scale, float& unscale) {
-  const float mx = __uint_as_float(max_bits);
-  int e = 0;
-  if (mx > 0.f && mx < 3.0e38f) (void)__builtin_frexpf(mx, &e);        // mx = m 2^e, m in [0.5, 1)
-  else e = 14;                                                       // no gradient at all (or not finite: it propagates as it is)
-  scale = __builtin_ldexpf(1.0f, 14 - e);
-  unscale = __builtin_ldexpf(1.0f, e - 14);
+  // On the bit pattern, in integer arithmetic (the word is uniform: scalar instructions in the tile's prologue, nothing in the vector stream).
+  // A normal float with exponent field E is m 2^(E - 126), m in [0.5, 1) -- frexp's e = E - 126 -- so 2^(14 - e) has the field 267 - E and
+  // 2^(e - 14) the field E - 13.  The limit: E >= 14, i.e. a maximum below 2^-113 (E = 0, a subnormal, included) counts as 2^-113.
+  unsigned E = max_bits >> 23;
+  E = E < 14u ? 14u : E;
+  if (max_bits == 0u || max_bits >= 0x7f61b1e6u) E = 140u;           // no gradient at all, or not below 3.0e38f (not finite: it propagates as it is): e = 14
+  scale = __uint_as_float((267u - E) << 23);
+  unscale = __uint_as_float((E - 13u) << 23);
 }
 __device__ __forceinline__ float wave_max_lane63(float v) {
 #define MATPBR_DPP_MAX(ctrl, rowmask) v = __builtin_fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rowmask, 0xf, true)))

@@ -2481,8 +2481,8 @@ def test_deferred_folds_of_the_backward_pass_are_the_same_bits():
 @pytest.mark.parametrize("n_prev,n_red", [(256, 256), (241, 256), (256, 241)])
 def test_block_scaled_f16_backward_products(n_prev, n_red):
     """f2 (round 5): the backward products of the 256-wide layers on two f16 pieces with one exponent per 128-row tile
-    (`matpbr_mlp_layer_bwd_input_blk`, `matpbr_mlp_layer_bwd_weight_blk`, `matpbr_mlp_out_layer_bwd_tmax`; the autograd backward of
-    mymodels/mlps.py:102-103).  Gradients of the size a mean loss over 512 x 512 pixels produces (1e-6), tiles whose magnitudes differ by
+    (`matpbr_mlp_layer_bwd_input_blk`, `matpbr_mlp_layer_bwd_weight_blk`; the autograd backward of mymodels/mlps.py:102-103 -- the output layer's
+    `matpbr_mlp_out_layer_bwd_tmax` and the first layer's form are held to fp64, each on its own, in tests/test_gpu_posmlp_bwd_fp64.py).  Gradients of the size a mean loss over 512 x 512 pixels produces (1e-6), tiles whose magnitudes differ by
     1e4 (each tile has its own exponent), a few elements far below their tile's largest: against fp64 the error is that of the three-bf16-piece
     form and within 1.5 x the exact-f32 kernels' (the f32 accumulation dominates), ROW by row inside a tile as well; the tile maxima the
     kernels write are the maxima; the bias gradient is the column sum; a zero tile stays zero."""
