@@ -47,6 +47,11 @@ enum {
     MATPBR_PATH_BSDF_AREA = 4,       /* an area light, one-sided, no BSDF: p = radiance RGB, finite and >= 0 (0 is valid).  Never with
                                         MATPBR_PATH_OBJECT_SMOOTH.  Only matpbr_path_render_objects_lights, matpbr_path_light_tables (and
                                         the feature entry points) take it; to every other entry point it is an unknown kind. */
+    MATPBR_PATH_BSDF_ROUGH_DIELECTRIC = 5, /* rough glass (Walter et al. 2007, GGX, visible normals), two-sided, never delta:
+                                        p[0] = int_ior, p[1] = ext_ior, p[2] = alpha (the GGX width) in [0.02, 1]; the indices finite and
+                                        > 0 with |int_ior / ext_ior - 1| >= 0.01.  MATPBR_PATH_OBJECT_SMOOTH may be OR-ed in.  Only
+                                        matpbr_path_render_objects_rough, matpbr_path_light_tables, matpbr_path_object_lookup_host (and
+                                        the feature entry points) take it; to every other entry point it is an unknown kind. */
 };
 
 /* OR-ed into MatpbrPathObject.kind: the object shades with interpolated corner normals ("Smooth inserted
@@ -246,6 +251,36 @@ int matpbr_path_light_sample_host(const MatpbrPathLights* lights, const void* li
  * where t <= 0 or the ray meets the back. */
 int matpbr_path_light_pdf_host(const MatpbrPathLights* lights, const void* light_tris, long n_light_tri, int have_env, const int32_t* light,
                                const int32_t* record, const float* o, const float* d, long N, float* t, float* pdf);
+
+/* ---- Rough dielectric objects ("Rough dielectric objects") ------------------------------------------------------
+ * matpbr_path_render_objects_lights where an object may be of kind MATPBR_PATH_BSDF_ROUGH_DIELECTRIC, forward only.  At a vertex on
+ * such an object n is the outward normal the BSDF shades with (the face normal ng, or, where smooth, the interpolated one after its
+ * three fallbacks), N = sign(n . wo) n, eta_it = int_ior / ext_ior entering and its inverse leaving.  The half vector h comes from
+ * the visible normals of wo (dims 7, 8); dim 6 <= F(wo . h) reflects about h, else refracts about h with the radiance factor
+ * eta_ti^2; the weight is G1(wi) (x eta_ti^2), the pdf the solid-angle density, and the vertex is never delta.  A direction w with
+ * (ng . w)(n . w) <= 0 carries nothing.  The vertex shades from both sides (no back-face exit); its emitter sample (chosen as
+ * matpbr_path_render_objects_lights chooses, sampled from the point spawn_eps off the face on ng's side) is taken on either side of
+ * the face, its shadow ray starting spawn_eps off the face on the sample's side.  With a kind-5 object the table may hold no light:
+ * the three light arguments may be NULL then, and the envmap, where it has tables, is the only emitter.  Without a kind-5 object
+ * this calls matpbr_path_render_objects_lights and gives its bits.  Invalid arguments, besides that entry point's: the bounds of
+ * kind 5 above. */
+int matpbr_path_render_objects_rough(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                     float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                     int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                     const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                     const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                     const float* light_cdf);
+
+/* The BSDF sampler of a kind-5 object on the CPU, with the routine the kernel runs: face normals ng[N,3], shading normals ns[N,3]
+ * (unit length; ns = ng on a flat object), wo[N,3], u[N,3] = dims 6, 7, 8 -> wi[N,3], weight[N,3] (0 = the path ends), pdf[N] (solid
+ * angle), flags[N] (bit 1: transmitted; bit 0, delta, is never set). */
+int matpbr_path_rough_sample_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* u, long N,
+                                  float* wi, float* weight, float* pdf, int32_t* flags);
+
+/* The BSDF evaluation of a kind-5 object on the CPU, with the routine the kernel runs at an emitter sample: directions wl[N,3] ->
+ * f[N,3] (with its cosine, the radiance factor included) and pdf[N], the density matpbr_path_rough_sample_host gives wl. */
+int matpbr_path_rough_eval_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* wl, long N,
+                                float* f, float* pdf);
 
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;

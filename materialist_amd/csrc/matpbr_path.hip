@@ -43,10 +43,13 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 // PBR: SMOOTH with objects of kind 3 (Objects = PbrObjects), whose vertices run the depth mesh's branch about `ns` on the constants of
 // their record; every `if (PBR ...)` folds away in the other five.  LIGHT: PBR with objects of kind 4 (Objects = LightObjects), area
 // lights: one emitter of n_e (the envmap, the lights) is sampled per vertex, and a ray that lands on a light adds its emission and
-// ends; every `if (LIGHT ...)` folds away in the other six.
+// ends; every `if (LIGHT ...)` folds away in the other six.  ROUGH: LIGHT with objects of kind 5 (Objects = RoughObjects), rough
+// dielectrics: a non-delta vertex that shades from both sides, whose emitter sample may arrive on either side of the face and whose
+// light table may be empty; every `if (ROUGH ...)` folds away in the other seven.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool LIGHT = std::is_same<Objects, LightObjects>::value;
+    constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value;
+    constexpr bool LIGHT = std::is_same<Objects, LightObjects>::value || ROUGH;
     constexpr bool PBR = std::is_same<Objects, PbrObjects>::value || LIGHT;
     constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value || PBR;
     constexpr bool OBJ = std::is_same<Objects, ObjTable>::value || SMOOTH;
@@ -139,7 +142,8 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
             }
             // a hit on the back of a triangle ends the path (glass shades from both sides)
-            if (!(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !(dot3(n, wo) > 0.0f)) break;
+            const bool rough = ROUGH && kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC;   // (ROUGH) shades from both sides, like glass
+            if (!(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !rough && !(dot3(n, wo) > 0.0f)) break;
             float p[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) p[c] = fmaf(t, d[c], o[c]);
@@ -187,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
 #pragma unroll
             for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
             // emitter sample with a shadow ray (none at a delta vertex)
-            if ((LIGHT || have_tab) && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC)) {
+            if (((ROUGH ? n_e > 0 : LIGHT) || have_tab) && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC)) {
                 float wl[3], pdf_e;
                 int te = 0;
                 float Le[3] = {0.0f, 0.0f, 0.0f}, ts_max = FLT_MAX;   // (LIGHT) the chosen emitter's radiance, the shadow ray's reach
@@ -211,9 +215,19 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                     te = env_sample(q.row_cdf, q.col_cdf, q.env_pdf, q.He, q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
                                     rng_u(base, depth, 4), rng_u(base, depth, 5), wl, pdf_e);
                 }
-                if (pdf_e > 0.0f && dot3(n, wl) > 0.0f) {
+                if (pdf_e > 0.0f && (rough || dot3(n, wl) > 0.0f)) {   // (ROUGH) a rough dielectric takes the sample on either side of its face
                     float f[3], pdf_b;
-                    if (OBJ && kind == MATPBR_PATH_BSDF_DIFFUSE) {   // f cos = rho / pi max(n . wi, 0), pdf = cos / pi
+                    if constexpr (ROUGH) {
+                        if (rough) {   // the shadow ray starts on wl's side of the face
+                            const float side = dot3(n, wl) > 0.0f ? eps : -eps;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) po[c] = fmaf(side, n[c], p[c]);
+                        }
+                    }
+                    if (rough) {
+                        rough_eval(op, n, ns, wo, wl, f[0], pdf_b);
+                        f[1] = f[2] = f[0];
+                    } else if (OBJ && kind == MATPBR_PATH_BSDF_DIFFUSE) {   // f cos = rho / pi max(n . wi, 0), pdf = cos / pi
                         if constexpr (SMOOTH) pdf_b = fmaxf(dot3(ns, wl), 0.0f) * kInvPi;   // ns = n on a flat object
                         else pdf_b = dot3(n, wl) * kInvPi;
 #pragma unroll
@@ -243,7 +257,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             float wi[3], wgt[3], pdf_s;
             if (OBJ && kind != 0 && !pbr) {
                 int flags;
-                if (SMOOTH && smooth)
+                if (rough)
+                    rough_sample(op, n, ns, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
+                else if (SMOOTH && smooth)
                     object_sample_shading(kind, op, n, ns, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
                 else
                     object_sample(kind, op, n, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
@@ -654,7 +670,7 @@ bool frame_args(const Frame& f, PathArgs& q) {
     return true;
 }
 
-// what the six renders select their kernel on: `edit` the transparency-editing instantiation, else `nrm` the shading-normal one, else `pbr`
+// what the renders select their kernel on: `rough` the rough-dielectric instantiation, else `edit` the transparency-editing instantiation, else `nrm` the shading-normal one, else `pbr`
 // the PBR-object one (obj_nrm may be null then: no object is smooth), else `obj_nrm` the smooth-object one, else ot.n > 0 the object one
 struct Extras {
     ObjTable ot{};
@@ -662,6 +678,7 @@ struct Extras {
     int32_t n_scene_tri = 0;
     const MatpbrPathObjectPbr* pbr = nullptr;
     const LightTable* lights = nullptr;   // set where some object is a light (pbr may be null then: no object is of kind 3)
+    bool rough = false;                   // some object is a rough dielectric: `lights` is set (its table may be empty)
     const TransEdit* edit = nullptr;
     const float* nrm = nullptr;
 };
@@ -675,10 +692,11 @@ struct ObjectArgs {
     const MatpbrPathObjectPbr* pbr;   // nullable: no record is checked
 };
 // ... checked into the table, the corner normals, n_scene_tri and the records of `x`.  `with_pbr`: a kind may be MATPBR_PATH_BSDF_PBR;
-// `n_light` (nullable): where given, a kind may be MATPBR_PATH_BSDF_AREA, counted there
-bool object_extras(const ObjectArgs& g, bool with_pbr, Extras& x, int* n_light = nullptr) {
+// `n_light` (nullable): where given, a kind may be MATPBR_PATH_BSDF_AREA, counted there; `n_rough` likewise for
+// MATPBR_PATH_BSDF_ROUGH_DIELECTRIC
+bool object_extras(const ObjectArgs& g, bool with_pbr, Extras& x, int* n_light = nullptr, int* n_rough = nullptr) {
     int n_smooth = 0, n_pbr = 0;
-    if (!object_table(g.objects, g.n_objects, x.ot, &n_smooth, with_pbr ? &n_pbr : nullptr, g.pbr, n_light) || g.n_scene_tri < 0 ||
+    if (!object_table(g.objects, g.n_objects, x.ot, &n_smooth, with_pbr ? &n_pbr : nullptr, g.pbr, n_light, n_rough) || g.n_scene_tri < 0 ||
         g.n_scene_tri > INT32_MAX || (n_smooth > 0 && !g.obj_nrm))
         return false;
     for (int k = 0; k < g.n_objects; ++k)
@@ -709,10 +727,13 @@ int render_common(const Frame& f, const Extras& x) {
         for (int k = 0; x.pbr && k < x.ot.n; ++k) lo.pbr[k] = x.pbr[k];
         lo.lt = *x.lights;
     }
+    RoughObjects ro{};
+    if (x.rough) static_cast<LightObjects&>(ro) = lo;
     for (int s0 = 0; s0 < f.spp; s0 += f.spp_per_launch) {
         const int s1 = std::min(f.spp, s0 + f.spp_per_launch);
         const int first = s0 == 0 ? 1 : 0, last = s1 == f.spp ? 1 : 0;
-        if (x.edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, block, 0, st, q, s0, s1, first, last, *x.edit);
+        if (x.rough) hipLaunchKernelGGL(path_kernel<RoughObjects>, grid, block, 0, st, q, s0, s1, first, last, ro);
+        else if (x.edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, block, 0, st, q, s0, s1, first, last, *x.edit);
         else if (x.nrm) hipLaunchKernelGGL(path_kernel<ShadeNormals>, grid, block, 0, st, q, s0, s1, first, last, ShadeNormals{x.nrm});
         else if (x.lights) hipLaunchKernelGGL(path_kernel<LightObjects>, grid, block, 0, st, q, s0, s1, first, last, lo);
         else if (x.pbr) hipLaunchKernelGGL(path_kernel<PbrObjects>, grid, block, 0, st, q, s0, s1, first, last, pbo);
@@ -726,9 +747,9 @@ int render_common(const Frame& f, const Extras& x) {
 
 // the arguments both feature entry points share, checked and packed: `q` arrives with the caller's pointers and sizes
 bool features_args(const ObjectArgs& g, float fov_x_deg, FeatArgs& q, Extras& x) {
-    // an object of kind 3 or 4 is valid here: the features read its kind and its flag, never its record or its light tables
-    int n_light = 0;
-    if (!q.nodes || !q.tris || !q.geom || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) || !object_extras(g, true, x, &n_light)) return false;
+    // an object of kind 3, 4 or 5 is valid here: the features read its kind and its flag, never its record or its light tables
+    int n_light = 0, n_rough = 0;
+    if (!q.nodes || !q.tris || !q.geom || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) || !object_extras(g, true, x, &n_light, &n_rough)) return false;
     q.n_scene_tri = x.n_scene_tri;
     const Camera c = camera(q.H, q.W, fov_x_deg);   // the render's
     q.f_pix = c.f_pix; q.cx = c.cx; q.cy = c.cy;
@@ -978,9 +999,9 @@ int matpbr_path_light_tables(const double* vert, long n_vert, const int32_t* tri
                              const MatpbrPathObjectPbr* pbr, MatpbrPathLights* lights, float* light_tris, float* light_cdf, long capacity,
                              long* n_light_tri) {
     ObjTable ot{};
-    int n_smooth = 0, n_pbr = 0, n_light = 0;
+    int n_smooth = 0, n_pbr = 0, n_light = 0, n_rough = 0;
     if (!vert || !tri || !lights || !n_light_tri || n_vert <= 0 || n_tri < 0 || n_tri > INT32_MAX / 3 || (light_tris && (!light_cdf || capacity < 0)) ||
-        !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr, &n_light))
+        !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr, &n_light, &n_rough))
         return MATPBR_PATH_ERR_INVALID_ARG;
     return light_tables_build(vert, n_vert, tri, n_tri, ot, lights, light_tris, light_cdf, capacity, n_light_tri);
 }
@@ -1068,11 +1089,64 @@ int matpbr_path_light_pdf_host(const MatpbrPathLights* lights, const void* light
     return MATPBR_PATH_OK;
 }
 
+int matpbr_path_render_objects_rough(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                     float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                     int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                     const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                     const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                     const float* light_cdf) {
+    bool any_rough = false, any_light = false, any_pbr = false;
+    for (int k = 0; objects && k >= 0 && k < n_objects && k < MATPBR_PATH_MAX_OBJECTS; ++k) {
+        any_rough = any_rough || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC;
+        any_light = any_light || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_AREA;
+        any_pbr = any_pbr || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR;
+    }
+    if (!any_rough)
+        return matpbr_path_render_objects_lights(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
+                                                 spp_per_launch, out, rays, stream, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris,
+                                                 light_cdf);
+    Extras x;
+    LightTable lt{};   // without a light: no record is read (n = 0)
+    int n_light = 0, n_rough = 0;
+    if ((any_pbr && !pbr) || !object_extras({objects, n_objects, obj_nrm, n_scene_tri, pbr}, true, x, &n_light, &n_rough) ||
+        (any_light && !light_table(lights, x.ot, light_tris, light_cdf, lt)))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    x.lights = &lt;
+    x.rough = true;
+    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+}
+
+// the object of the two CPU entry points below: kind 5, with or without the smooth flag (the caller passes both normals either way)
+static bool rough_object(const MatpbrPathObject* ob) {
+    return ob && (ob->kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC && rough_valid(ob->p);
+}
+
+int matpbr_path_rough_sample_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* u, long N,
+                                  float* wi, float* weight, float* pdf, int32_t* flags) {
+    if (!rough_object(object) || !ng || !ns || !wo || !u || !wi || !weight || !pdf || !flags || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        int fl = 0;
+        rough_sample(object->p, ng + 3 * k, ns + 3 * k, wo + 3 * k, u[3 * k], u[3 * k + 1], u[3 * k + 2], wi + 3 * k, weight + 3 * k, pdf[k], fl);
+        flags[k] = fl;
+    }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_rough_eval_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* wl, long N,
+                                float* f, float* pdf) {
+    if (!rough_object(object) || !ng || !ns || !wo || !wl || !f || !pdf || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        rough_eval(object->p, ng + 3 * k, ns + 3 * k, wo + 3 * k, wl + 3 * k, f[3 * k], pdf[k]);
+        f[3 * k + 1] = f[3 * k + 2] = f[3 * k];
+    }
+    return MATPBR_PATH_OK;
+}
+
 int matpbr_path_object_lookup_host(const MatpbrPathObject* objects, int n_objects, const MatpbrPathObjectPbr* pbr, const int32_t* ids, long N,
                                    int32_t* kind, float* a, float* r, float* m) {
     ObjTable ot{};
-    int n_smooth = 0, n_pbr = 0;
-    if (!ids || !kind || !a || !r || !m || N < 0 || !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr) || (n_pbr > 0 && !pbr))
+    int n_smooth = 0, n_pbr = 0, n_rough = 0;
+    if (!ids || !kind || !a || !r || !m || N < 0 || !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr, nullptr, &n_rough) || (n_pbr > 0 && !pbr))
         return MATPBR_PATH_ERR_INVALID_ARG;
     for (long k = 0; k < N; ++k) {
         float p[3] = {0.0f, 0.0f, 0.0f};

@@ -24,6 +24,8 @@ struct LightTable {
 struct LightObjects : PbrObjects {
     LightTable lt;
 };
+// the table of a scene with a rough dielectric object (kind 5): the light table may be empty then (lt.n = 0)
+struct RoughObjects : LightObjects {};
 
 // emitter `idx` of n_e by sample reuse: idx = min(int(u n_e), n_e - 1), u' = u n_e - idx kept below 1
 __host__ __device__ inline int emitter_choose(float u, int n_e, float& u_re) {

@@ -1,5 +1,5 @@
 // path_objects.hpp -- the tables that travel to libmatpbr_path.so's kernels by value (matpbr_path.hip includes it) and everything that
-// operates on them: inserted objects (flat, smooth, PBR), the transparency edit, the shading-normal map; their lookups, samplers and
+// operates on them: inserted objects (flat, smooth, PBR, rough dielectric), the transparency edit, the shading-normal map; their lookups, samplers and
 // the checks of what the caller passes.
 #pragma once
 #include "path_shading.hpp"
@@ -207,6 +207,136 @@ __host__ __device__ inline void object_sample_shading(int kind, const float p[3]
     if (kind != MATPBR_PATH_BSDF_DIELECTRIC && !(go > 0.0f && dot3h(ng, wi) > 0.0f)) w[0] = w[1] = w[2] = 0.0f;
 }
 
+// ---- rough dielectric objects ("Rough dielectric objects"): Walter et al. 2007 with GGX, visible normals ---
+// p = (int_ior, ext_ior, alpha).  The surface shades from both sides: n is the outward normal the BSDF shades with (the face normal,
+// or the interpolated one after its three fallbacks), N = sign(n . wo) n the same normal on the viewer's side, eta_it = eta entering,
+// 1 / eta leaving.  A direction w with (ng . w)(n . w) <= 0 carries nothing, in the sample and in the evaluation alike.  Plain
+// divisions and sqrtf: the CPU entry points run what the kernel runs.
+__host__ __device__ inline void rough_side(const float p[3], const float ng[3], const float ns_in[3], const float wo[3], float n[3], float N[3],
+                                           float& eta_it, float& cos_o) {
+    for (int c = 0; c < 3; ++c) n[c] = ns_in[c];
+    smooth_side(ng, wo, n);
+    const float no = dot3h(n, wo), eta = p[0] / p[1];
+    const float s = no > 0.0f ? 1.0f : -1.0f;
+    for (int c = 0; c < 3; ++c) N[c] = s * n[c];
+    eta_it = no > 0.0f ? eta : 1.0f / eta;
+    cos_o = fabsf(no);
+}
+// GGX about N at the half vector h (h . N > 0), 1 - NoH^2 from N x h (ggx_den_stable's form: the literal one loses its digits on the peak)
+__host__ __device__ inline float rough_d(float alpha, const float N[3], const float h[3]) {
+    float cr[3];
+    cross3(N, h, cr);
+    const float a2 = alpha * alpha, den = a2 + dot3h(cr, cr) * (1.0f - a2);
+    return a2 * 0.31830988618379067154f / (den * den);
+}
+// Smith's G1 of the separable form: vn = v . N, vh = v . h; 0 where the two disagree about v's side
+__host__ __device__ inline float rough_g1(float alpha, float vn, float vh) {
+    if (!(vn * vh > 0.0f)) return 0.0f;
+    const float c2 = vn * vn, t2 = fmaxf(1.0f - c2, 0.0f) / c2;
+    return 2.0f / (1.0f + sqrtf(1.0f + (alpha * alpha) * t2));
+}
+// 1 - F of fresnel_dielectric(ci, eta_it, ct) in the form that does not cancel near total internal reflection:
+// 1 - a_s^2 = 4 eta ci ct / (ci + eta ct)^2 and 1 - a_p^2 = 4 eta ci ct / (ct + eta ci)^2
+__host__ __device__ inline float rough_transmittance(float ci, float eta_it, float ct) {
+    const float a = ci + eta_it * ct, b = ct + eta_it * ci;
+    return ct > 0.0f ? 2.0f * eta_it * ci * ct * (1.0f / (a * a) + 1.0f / (b * b)) : 0.0f;
+}
+// BSDF sample at a rough dielectric vertex; u_lobe, u0, u1 = dims 6, 7, 8.  h from the visible normals of wo (Heitz 2018), then
+// u_lobe <= F reflects about h (weight G1(wi)), else refracts by Snell about h (weight G1(wi) eta_ti^2, kFlagTransmitted).  pdf is
+// the solid-angle density of wi; the vertex is never delta.  weight 0: the path ends.
+__host__ __device__ inline void rough_sample(const float p[3], const float ng[3], const float ns_in[3], const float wo[3], float u_lobe, float u0,
+                                             float u1, float wi[3], float w[3], float& pdf, int& flags) {
+    float n[3], N[3], eta_it, cos_o;
+    rough_side(p, ng, ns_in, wo, n, N, eta_it, cos_o);
+    const float alpha = p[2], eta_ti = 1.0f / eta_it;
+    wi[0] = wi[1] = wi[2] = 0.0f;
+    w[0] = w[1] = w[2] = 0.0f;
+    pdf = 0.0f;
+    flags = 0;
+    if (!(cos_o > 0.0f)) return;
+    // the frame of Duff et al. 2017 about N, wo in it
+    const float sg = copysignf(1.0f, N[2]), a = -1.0f / (sg + N[2]), b = N[0] * N[1] * a;
+    const float S[3] = {1.0f + sg * N[0] * N[0] * a, sg * b, -sg * N[0]}, T[3] = {b, sg + N[1] * N[1] * a, -N[1]};
+    // the visible normals: the hemisphere configuration, a disk sample warped onto its projected area, back to the ellipsoid
+    float V[3] = {alpha * dot3h(S, wo), alpha * dot3h(T, wo), cos_o};
+    {
+        const float il = 1.0f / sqrtf(dot3h(V, V));
+        for (int c = 0; c < 3; ++c) V[c] *= il;
+    }
+    const float lensq = V[0] * V[0] + V[1] * V[1];
+    const float il1 = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
+    const float T1[3] = {lensq > 0.0f ? -V[1] * il1 : 1.0f, lensq > 0.0f ? V[0] * il1 : 0.0f, 0.0f};
+    const float T2[3] = {-V[2] * T1[1], V[2] * T1[0], V[0] * T1[1] - V[1] * T1[0]};
+    const float r = sqrtf(fmaxf(u0, 0.0f)), ph = 6.28318530717958647692f * u1;
+    const float t1 = r * cosf(ph), sm = 0.5f * (1.0f + V[2]);
+    const float t2 = (1.0f - sm) * sqrtf(fmaxf(1.0f - t1 * t1, 0.0f)) + sm * (r * sinf(ph));
+    const float t3 = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
+    float m[3] = {alpha * (t1 * T1[0] + t2 * T2[0] + t3 * V[0]), alpha * (t1 * T1[1] + t2 * T2[1] + t3 * V[1]), fmaxf(t2 * T2[2] + t3 * V[2], 0.0f)};
+    const float ml2 = dot3h(m, m);
+    if (!(ml2 > 0.0f)) return;
+    const float ilm = 1.0f / sqrtf(ml2);
+    float h[3];
+    for (int c = 0; c < 3; ++c) h[c] = (m[0] * S[c] + m[1] * T[c] + m[2] * N[c]) * ilm;
+    const float woh = dot3h(wo, h);
+    if (!(woh > 0.0f)) return;
+    float ct;
+    const float F = fresnel_dielectric(woh, eta_it, ct);
+    const float Dv = rough_g1(alpha, cos_o, woh) * woh * rough_d(alpha, N, h) / cos_o;
+    float win, wih;
+    if (u_lobe <= F) {
+        for (int c = 0; c < 3; ++c) wi[c] = 2.0f * woh * h[c] - wo[c];
+        win = dot3h(wi, N);
+        wih = dot3h(wi, h);
+        pdf = F * Dv / (4.0f * woh);
+        w[0] = win > 0.0f ? rough_g1(alpha, win, wih) : 0.0f;
+    } else {
+        const float k = eta_ti * woh - ct;
+        for (int c = 0; c < 3; ++c) wi[c] = k * h[c] - eta_ti * wo[c];
+        win = dot3h(wi, N);
+        wih = dot3h(wi, h);
+        const float q = woh + eta_it * wih;
+        pdf = rough_transmittance(woh, eta_it, ct) * Dv * (eta_it * eta_it) * fabsf(wih) / (q * q);
+        w[0] = win < 0.0f ? rough_g1(alpha, win, wih) * (eta_ti * eta_ti) : 0.0f;
+        flags = kFlagTransmitted;
+    }
+    if (!(dot3h(ng, wi) * dot3h(n, wi) > 0.0f) || !(pdf > 0.0f)) w[0] = 0.0f;   // the two normals disagree about wi's side
+    w[1] = w[2] = w[0];
+}
+// The BSDF's value for the direction wl (with its cosine) and the density rough_sample gives wl: f / pdf is its weight.
+__host__ __device__ inline void rough_eval(const float p[3], const float ng[3], const float ns_in[3], const float wo[3], const float wl[3], float& f,
+                                           float& pdf) {
+    float n[3], N[3], eta_it, cos_o;
+    rough_side(p, ng, ns_in, wo, n, N, eta_it, cos_o);
+    const float alpha = p[2];
+    f = 0.0f;
+    pdf = 0.0f;
+    const float cos_l = dot3h(wl, N);
+    if (!(cos_o > 0.0f) || !(dot3h(ng, wl) * dot3h(n, wl) > 0.0f)) return;
+    const bool reflect = cos_l > 0.0f;
+    const float kl = reflect ? 1.0f : eta_it;
+    float h[3] = {wo[0] + kl * wl[0], wo[1] + kl * wl[1], wo[2] + kl * wl[2]};
+    const float l2 = dot3h(h, h);
+    if (!(l2 > 0.0f)) return;
+    const float il = (dot3h(h, N) > 0.0f ? 1.0f : -1.0f) / sqrtf(l2);
+    for (int c = 0; c < 3; ++c) h[c] *= il;
+    const float woh = dot3h(wo, h), wlh = dot3h(wl, h);
+    if (!(woh > 0.0f) || (!reflect && !(wlh < 0.0f))) return;   // a refraction leaves on the far side of the microfacet
+    float ct;
+    const float F = fresnel_dielectric(woh, eta_it, ct);
+    const float D = rough_d(alpha, N, h), G1o = rough_g1(alpha, cos_o, woh), G1l = rough_g1(alpha, cos_l, wlh);
+    const float Dv = G1o * woh * D / cos_o;
+    if (reflect) {
+        f = F * D * (G1o * G1l) / (4.0f * cos_o);
+        pdf = F * Dv / (4.0f * woh);
+    } else {
+        const float q = woh + eta_it * wlh;
+        const float Tr = rough_transmittance(woh, eta_it, ct);
+        f = Tr * D * (G1o * G1l) * (woh * fabsf(wlh)) / (cos_o * (q * q));
+        pdf = Tr * Dv * (eta_it * eta_it) * fabsf(wlh) / (q * q);
+    }
+    if (!(pdf > 0.0f)) { f = 0.0f; pdf = 0.0f; }
+}
+
 // the texel a point projects to ("Material at a hit": floor, clamped to the image; a NaN coordinate clamps to 0)
 __host__ __device__ inline long screen_texel(const float p[3], float f_ndc, float aspect, int H, int W) {
     const float ndc0 = f_ndc * (-p[0]) / p[2], ndc1 = (f_ndc * aspect) * p[1] / p[2];
@@ -303,18 +433,27 @@ bool pbr_valid(const MatpbrPathObjectPbr& pr) {
         if (!(pr.a[c] >= 0.0f && pr.a[c] <= 1.0f)) return false;
     return pr.r >= 0.07f && pr.r <= 1.0f && pr.m >= 0.0f && pr.m <= 1.0f;
 }
+// a rough dielectric's p: both indices finite and > 0, their ratio and its inverse finite fp32 numbers at least 0.01 away from 1,
+// alpha in [0.02, 1]
+bool rough_valid(const float p[3]) {
+    if (!(p[0] > 0.0f && p[1] > 0.0f && std::isfinite(p[0]) && std::isfinite(p[1]))) return false;
+    const float eta = p[0] / p[1];
+    return eta > 0.0f && std::isfinite(eta) && std::isfinite(1.0f / eta) && fabsf(eta - 1.0f) >= 0.01f && p[2] >= 0.02f && p[2] <= 1.0f;
+}
 // `n_smooth` (nullable): where given, a kind may carry MATPBR_PATH_OBJECT_SMOOTH, and the flagged objects are counted.  `n_pbr`
 // (nullable): where given, a kind may be MATPBR_PATH_BSDF_PBR (its p[] is ignored), and those objects are counted; their records
 // are checked where `pbr` is given.  `n_light` (nullable): where given, a kind may be MATPBR_PATH_BSDF_AREA (without the smooth flag; p =
-// radiance, finite and >= 0), and those objects are counted.
+// radiance, finite and >= 0), and those objects are counted.  `n_rough` (nullable): where given, a kind may be
+// MATPBR_PATH_BSDF_ROUGH_DIELECTRIC (rough_valid), and those objects are counted.
 bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, int* n_smooth = nullptr, int* n_pbr = nullptr,
-                  const MatpbrPathObjectPbr* pbr = nullptr, int* n_light = nullptr) {
+                  const MatpbrPathObjectPbr* pbr = nullptr, int* n_light = nullptr, int* n_rough = nullptr) {
     if (n_objects < 0 || n_objects > MATPBR_PATH_MAX_OBJECTS || (n_objects > 0 && !objects)) return false;
     ot.n = n_objects;
     ot.min_id = INT32_MAX;
     if (n_smooth) *n_smooth = 0;
     if (n_pbr) *n_pbr = 0;
     if (n_light) *n_light = 0;
+    if (n_rough) *n_rough = 0;
     for (int k = 0; k < n_objects; ++k) {
         MatpbrPathObject plain = objects[k];
         if (n_light && plain.kind == MATPBR_PATH_BSDF_AREA) {   // checked as a diffuse object of reflectance 0: the range alone
@@ -327,6 +466,12 @@ bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, 
         if (n_smooth && (plain.kind & MATPBR_PATH_OBJECT_SMOOTH)) {
             plain.kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
             ++*n_smooth;
+        }
+        if (n_rough && plain.kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC) {   // checked as a diffuse object of reflectance 0: the range alone
+            if (!rough_valid(plain.p)) return false;
+            plain.kind = MATPBR_PATH_BSDF_DIFFUSE;
+            plain.p[0] = plain.p[1] = plain.p[2] = 0.0f;
+            ++*n_rough;
         }
         if (n_pbr && plain.kind == MATPBR_PATH_BSDF_PBR) {   // checked as a diffuse object of reflectance 0: the range alone
             if (pbr && !pbr_valid(pbr[k])) return false;

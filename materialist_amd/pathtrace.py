@@ -33,6 +33,9 @@ BSDF_PBR = 3                   # MATPBR_PATH_BSDF_PBR: MatDiffBSDF on the consta
 PBR_MIN_ROUGHNESS = 0.07       # the floor the project's roughness maps are clamped to (matpbr_shade.hpp, armhead.py)
 PBR_DEFAULTS = {"albedo": 0.8, "roughness": 0.5, "metallic": 0.0}
 BSDF_AREA = 4                  # MATPBR_PATH_BSDF_AREA: an area light, p = radiance ("Emissive inserted objects")
+BSDF_ROUGH_DIELECTRIC = 5      # MATPBR_PATH_BSDF_ROUGH_DIELECTRIC: rough glass, p = (int_ior, ext_ior, alpha) ("Rough dielectric objects")
+ROUGH_MIN_ALPHA = 0.02         # the GGX width's floor: the peak of D is 1 / (pi alpha^2)
+ROUGH_MIN_CONTRAST = 0.01      # |int_ior / ext_ior - 1| at least this: at a ratio of 1 the refraction Jacobian has no finite value
 OBJECT_SMOOTH = 0x100          # MATPBR_PATH_OBJECT_SMOOTH, OR-ed into PathObject.kind
 
 
@@ -88,6 +91,9 @@ SIGNATURES = {
     "matpbr_path_render_objects_lights": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P]),
     "matpbr_path_light_sample_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_long, ctypes.c_int, _P, _P, ctypes.c_long] + [_P] * 7),
     "matpbr_path_light_pdf_host": (ctypes.c_int, [_P, _P, ctypes.c_long, ctypes.c_int, _P, _P, _P, _P, ctypes.c_long, _P, _P]),
+    "matpbr_path_render_objects_rough": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P]),
+    "matpbr_path_rough_sample_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
+    "matpbr_path_rough_eval_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 2),
     "matpbr_path_object_sample_shading_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
     "matpbr_path_render_trans": (ctypes.c_int, _RENDER + [_P, _P, _P]),
     "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
@@ -118,7 +124,9 @@ DENOISE_SYMBOLS = ("matpbr_path_features", "matpbr_path_features_host", "matpbr_
 PBR_SYMBOLS = ("matpbr_path_render_objects_pbr", "matpbr_path_object_lookup_host")
 # and (emissive inserted objects)
 LIGHT_SYMBOLS = ("matpbr_path_light_tables", "matpbr_path_render_objects_lights", "matpbr_path_light_sample_host", "matpbr_path_light_pdf_host")
-LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS
+# and (rough dielectric inserted objects)
+ROUGH_SYMBOLS = ("matpbr_path_render_objects_rough", "matpbr_path_rough_sample_host", "matpbr_path_rough_eval_host")
+LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -150,7 +158,8 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
         what = ("the denoiser" if name in DENOISE_SYMBOLS else "PBR inserted objects" if name in PBR_SYMBOLS else
-                "emissive inserted objects" if name in LIGHT_SYMBOLS else "smooth inserted objects")
+                "emissive inserted objects" if name in LIGHT_SYMBOLS else "rough dielectric inserted objects" if name in ROUGH_SYMBOLS else
+                "smooth inserted objects")
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 
@@ -255,8 +264,26 @@ def object_bsdf(bsdf: dict) -> tuple:
     """{"type": "dielectric", "int_ior", "ext_ior"} | {"type": "diffuse", "reflectance"} -> (kind, (p0, p1, p2));
     {"type": "pbr", "albedo": scalar or 3 values (0.8), "roughness" (0.5), "metallic" (0)} -> (BSDF_PBR, (a0, a1, a2, r, m));
     {"type": "area", "radiance": scalar or 3 values, finite and >= 0 (1)} -> (BSDF_AREA, (r, g, b)): an area light.
+    {"type": "roughdielectric", "int_ior" (1.49), "ext_ior" (1.000277), "alpha" (0.1): the GGX width in [0.02, 1]} ->
+    (BSDF_ROUGH_DIELECTRIC, (int_ior, ext_ior, alpha)): rough glass; the indices' ratio stays at least 0.01 away from 1.
     ValueError when bad."""
     kind = bsdf.get("type") if isinstance(bsdf, dict) else None
+    if kind == "roughdielectric":
+        try:
+            p = (float(bsdf.get("int_ior", 1.49)), float(bsdf.get("ext_ior", 1.000277)), float(bsdf.get("alpha", 0.1)))
+        except (TypeError, ValueError):
+            raise ValueError(f"roughdielectric: int_ior, ext_ior and alpha must be numbers, got {bsdf!r}") from None
+        q = np.asarray(p, np.float32)                    # the bounds as the library sees them: the table is fp32
+        if not (q[0] > 0 and q[1] > 0 and np.isfinite(q[:2]).all()):
+            raise ValueError(f"roughdielectric: int_ior and ext_ior must be positive and finite, got {p[0]}, {p[1]}")
+        with np.errstate(over="ignore", under="ignore", divide="ignore"):
+            eta = q[0] / q[1]
+            inv = np.float32(1) / eta
+        if not (eta > 0 and np.isfinite(eta) and np.isfinite(inv) and abs(eta - np.float32(1)) >= np.float32(ROUGH_MIN_CONTRAST)):
+            raise ValueError(f"roughdielectric: int_ior / ext_ior must differ from 1 by at least {ROUGH_MIN_CONTRAST}, got {p[0]} / {p[1]}")
+        if not np.float32(ROUGH_MIN_ALPHA) <= q[2] <= 1:
+            raise ValueError(f"roughdielectric: alpha must lie in [{ROUGH_MIN_ALPHA}, 1], got {p[2]}")
+        return BSDF_ROUGH_DIELECTRIC, p
     if kind == "dielectric":
         p = (float(bsdf.get("int_ior", 1.49)), float(bsdf.get("ext_ior", 1.000277)), 0.0)
         if not (p[0] > 0 and p[1] > 0 and np.isfinite(p[:2]).all()):
@@ -292,7 +319,7 @@ def object_bsdf(bsdf: dict) -> tuple:
         if not (np.isfinite(rad).all() and (rad >= 0).all() and np.isfinite(rad.astype(np.float32)).all()):
             raise ValueError(f"area: radiance must be finite and >= 0, got {rad.tolist()}")
         return BSDF_AREA, tuple(float(x) for x in rad)
-    raise ValueError(f"object bsdf type must be 'dielectric', 'diffuse', 'pbr' or 'area', got {kind!r}")
+    raise ValueError(f"object bsdf type must be 'dielectric', 'diffuse', 'pbr', 'area' or 'roughdielectric', got {kind!r}")
 
 
 def _corner_normals(k: int, ob: dict, Vo: np.ndarray, To: np.ndarray) -> np.ndarray:
@@ -437,6 +464,8 @@ def _sampled_bsdf(bsdf: dict) -> tuple:
     kind, p = object_bsdf(bsdf)
     if kind == BSDF_PBR:
         raise ValueError("the object samplers on the CPU know 'dielectric' and 'diffuse'; a 'pbr' object samples with MatDiffBSDF's device code")
+    if kind == BSDF_ROUGH_DIELECTRIC:
+        raise ValueError("the object samplers on the CPU know 'dielectric' and 'diffuse'; a 'roughdielectric' object samples with rough_sample_host")
     return kind, p
 
 
@@ -483,6 +512,44 @@ def object_sample_shading_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: n
     check(symbol("matpbr_path_object_sample_shading_host")(ctypes.cast(ctypes.byref(ob), _P), _ptr(NG), _ptr(NS), _ptr(WO), _ptr(U), N, _ptr(wi),
                                                            _ptr(w), _ptr(pdf), _ptr(flags)), "matpbr_path_object_sample_shading_host")
     return wi, w, pdf, flags
+
+
+def _rough_object(bsdf: dict) -> PathObject:
+    kind, p = object_bsdf(bsdf)
+    if kind != BSDF_ROUGH_DIELECTRIC:
+        raise ValueError(f"rough_sample_host and rough_eval_host take a 'roughdielectric' bsdf, got {bsdf.get('type')!r}")
+    return PathObject(kind, 0, 0, (ctypes.c_float * 3)(*p))
+
+
+def _normal_rows(x, N: int) -> np.ndarray:
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float32).reshape(-1, 3), (N, 3)))
+
+
+def rough_sample_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: np.ndarray, u: np.ndarray):
+    """The kernel's sampler of a rough dielectric object on the CPU: face normal ng [N,3] (or [3]), shading normal ns [N,3] (or [3];
+    ng on a flat object), wo [N,3], u [N,3] (dims 6, 7, 8) -> (wi [N,3], weight [N,3], pdf [N], flags [N]: bit 1 transmitted)."""
+    ob = _rough_object(bsdf)
+    WO, U = _rows(wo, 3), _rows(u, 3)
+    N = _same_rows(f"wo and u must have the same rows, got {WO.shape[0]} and {U.shape[0]}", WO, U)
+    NG, NS = _normal_rows(ng, N), _normal_rows(ns, N)
+    wi, w = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
+    pdf, flags = np.empty(N, np.float32), np.empty(N, np.int32)
+    check(symbol("matpbr_path_rough_sample_host")(ctypes.cast(ctypes.byref(ob), _P), _ptr(NG), _ptr(NS), _ptr(WO), _ptr(U), N, _ptr(wi), _ptr(w),
+                                                  _ptr(pdf), _ptr(flags)), "matpbr_path_rough_sample_host")
+    return wi, w, pdf, flags
+
+
+def rough_eval_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: np.ndarray, wl: np.ndarray):
+    """The kernel's evaluation of a rough dielectric object on the CPU, as an emitter sample takes it: directions wl [N,3] ->
+    (f [N,3], with its cosine; pdf [N], the density `rough_sample_host` gives wl)."""
+    ob = _rough_object(bsdf)
+    WO, WL = _rows(wo, 3), _rows(wl, 3)
+    N = _same_rows(f"wo and wl must have the same rows, got {WO.shape[0]} and {WL.shape[0]}", WO, WL)
+    NG, NS = _normal_rows(ng, N), _normal_rows(ns, N)
+    f, pdf = np.empty((N, 3), np.float32), np.empty(N, np.float32)
+    check(symbol("matpbr_path_rough_eval_host")(ctypes.cast(ctypes.byref(ob), _P), _ptr(NG), _ptr(NS), _ptr(WO), _ptr(WL), N, _ptr(f), _ptr(pdf)),
+          "matpbr_path_rough_eval_host")
+    return f, pdf
 
 
 def trans_edit(ior: float = 1.2, spec_trans: float = 0.4, refract_distance: float = 100.0) -> PathTransEdit:
@@ -676,8 +743,10 @@ class PathTracer:
     outward): with them the object shades smooth, with the normals interpolated at each hit; without them flat.  An object with
     {"type": "area", "radiance": (r, g, b)} is an area light ("Emissive inserted objects"): it emits its
     radiance from its outward faces, reflects nothing, takes no "normals", and is sampled as an emitter beside the envmap at every
-    vertex (`stats["n_lights"]` counts them; an envmap of zero luminance leaves the lights as the only emitters).  A tracer with
-    objects renders forward only."""
+    vertex (`stats["n_lights"]` counts them; an envmap of zero luminance leaves the lights as the only emitters).  An object with
+    {"type": "roughdielectric", "int_ior": 1.49, "ext_ior": 1.000277, "alpha": 0.1} is rough (frosted) glass (DESIGN.md section 1.4,
+    "Rough dielectric objects"; `stats["n_rough_objects"]` counts them): it shades from both sides, takes "normals", and, unlike
+    clear glass, takes an emitter sample at every vertex.  A tracer with objects renders forward only."""
 
     def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
                  objects: Optional[Sequence[dict]] = None):
@@ -689,7 +758,8 @@ class PathTracer:
         self.n_scene_tris = n_scene
         self.pbr = None                               # the PathObjectPbr records, when some object is of kind BSDF_PBR
         self.lights = None                            # (PathLights, tris, cdf on the device), when some object is of kind BSDF_AREA
-        n_smooth = n_pbr = n_lights = 0
+        self.rough = False                            # some object is of kind BSDF_ROUGH_DIELECTRIC: `render` takes the rough entry point
+        n_smooth = n_pbr = n_lights = n_rough = 0
         if objects:
             vertices, triangles, table, corner, records, lt = merge_objects(vertices, triangles, objects, normals=True, pbr=True, lights=True)
             if lt is not None:
@@ -699,9 +769,13 @@ class PathTracer:
             self.objects = (PathObject * len(table))(*table)
             n_smooth = sum(1 for t in table if t.kind & OBJECT_SMOOTH)
             n_pbr = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_PBR)
+            n_rough = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_ROUGH_DIELECTRIC)
+            if n_rough:
+                symbol("matpbr_path_render_objects_rough")
+                self.rough = True
             if n_pbr:
                 symbol("matpbr_path_render_objects_pbr")
-            if n_pbr or lt is not None:               # the light entry point takes the records beside the table as well
+            if n_pbr or lt is not None or n_rough:    # the light and rough entry points take the records beside the table as well
                 self.pbr = (PathObjectPbr * len(records))(*records)
             if corner is not None:
                 symbol("matpbr_path_render_objects_normals")
@@ -716,6 +790,7 @@ class PathTracer:
         self.stats["n_smooth_objects"] = n_smooth
         self.stats["n_pbr_objects"] = n_pbr
         self.stats["n_lights"] = n_lights
+        self.stats["n_rough_objects"] = n_rough
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -783,6 +858,14 @@ class PathTracer:
             check(lib.matpbr_path_render_normals(*args, nrm.data_ptr()), "matpbr_path_render_normals")
         elif self.objects is None:
             check(lib.matpbr_path_render(*args), "matpbr_path_render")
+        elif self.rough:
+            head, ltris, lcdf = self.lights if self.lights is not None else (None, None, None)
+            check(symbol("matpbr_path_render_objects_rough", lib)(*args, table, len(self.objects),
+                                                                  self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,
+                                                                  self.n_scene_tris, records,
+                                                                  ctypes.cast(ctypes.byref(head), _P) if head is not None else None,
+                                                                  ltris.data_ptr() if ltris is not None else None,
+                                                                  lcdf.data_ptr() if lcdf is not None else None), "matpbr_path_render_objects_rough")
         elif self.lights is not None:
             head, ltris, lcdf = self.lights
             check(symbol("matpbr_path_render_objects_lights", lib)(*args, table, len(self.objects),

@@ -239,8 +239,9 @@ _PBR_ALBEDO = 0.8   # pathtrace.PBR_DEFAULTS["albedo"]: what `object_bsdf` gives
 
 def albedo_guide(geom: torch.Tensor, albedo: torch.Tensor, bsdfs=()) -> torch.Tensor:
     """The denoiser's albedo guide [H,W,3] from the features' ids: the albedo map as rendered where the camera ray hits the depth mesh
-    (id 0), a diffuse object's reflectance, a PBR object's albedo, 1 on glass and on an area light (the fall-through: a light's
-    pixels are its radiance, which the colour term guides alone), 0 where it hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
+    (id 0), a diffuse object's reflectance, a PBR object's albedo, 1 on glass, on rough glass ("roughdielectric": colourless, like
+    glass) and on an area light (the fall-through: a light's pixels are its radiance, which the colour term guides alone), 0 where it
+    hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
     ids = geom[..., 7]
     guide = albedo.to(geom.device, torch.float32).reshape(geom.shape[0], geom.shape[1], 3).clone()
     guide[ids < 0] = 0.0
@@ -328,8 +329,9 @@ OI_SCENE_MAX_OBJECTS = 8                              # pathtrace.MAX_OBJECTS
 def load_oi_scene(path: str) -> List[dict]:
     """An object list file for `render_oi(objects_file=...)`: JSON that holds only settings,
     {"objects": [{"ply": "chrome_ball.ply", "bsdf": {"type": "pbr", "albedo": [0.95, 0.93, 0.88], "roughness": 0.1, "metallic": 1.0},
-    "normals": "vertex"}, ...]}, at most 8 objects.  "ply" is relative to the file; "bsdf" is any of PathTracer's four types
-    (dielectric, diffuse, pbr, area: {"type": "area", "radiance": [r, g, b]} is a lamp, which takes "normals": "flat" only); "normals" is "flat" (default) or "vertex" (the file's normals if it has them, else
+    "normals": "vertex"}, ...]}, at most 8 objects.  "ply" is relative to the file; "bsdf" is any of PathTracer's five types
+    (dielectric, diffuse, pbr, roughdielectric: {"type": "roughdielectric", "int_ior", "ext_ior", "alpha"} is frosted glass, area:
+    {"type": "area", "radiance": [r, g, b]} is a lamp, which takes "normals": "flat" only); "normals" is "flat" (default) or "vertex" (the file's normals if it has them, else
     `mesh.angle_weighted_normals`) -> [{"ply": absolute path, "bsdf", "normals"}], nothing read yet but the list.  ValueError naming
     the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
     import json
@@ -389,7 +391,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     samples do the denoiser's work (spp 64 x 10).  `denoise="atrous"` (even `spp`) runs the project's own filter instead: each of
     the `n_iter` renders becomes two of spp / 2, seeds seed + 2 i and seed + 2 i + 1, summed into two half buffers, and one a-trous
     pass runs over them ("Denoiser"); behind glass only its colour term guides.  `objects_file`: an object
-    list (`load_oi_scene`) whose meshes are inserted instead, each with its own BSDF (dielectric, diffuse, pbr or area: a lamp) and
+    list (`load_oi_scene`) whose meshes are inserted instead, each with its own BSDF (dielectric, diffuse, pbr, roughdielectric: frosted glass, or area: a lamp) and
     its own normals; with it oi.ply and oi2.ply are not looked for and `object_normals` is ignored.  The output names are the same.
     `env_scale`: the envmap is multiplied by it before its tables are built (1: the same bits as without it; 0 with an area light in
     the list: the night shot, lit by the lamp alone)."""

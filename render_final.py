@@ -38,7 +38,7 @@ def parse_args(argv=None):
                     help="--mode oi: flat = face normals; vertex = each .ply shades smooth with its vertex normals (angle-weighted ones if it has none)")
     ap.add_argument("--oi_scene", type=str, default=None, metavar="FILE.json",
                     help='--mode oi: an object list, {"objects": [{"ply": path relative to the file, "bsdf": {"type": "pbr", "albedo": [r, g, b], '
-                         '"roughness": r, "metallic": m} (or a "dielectric" or "diffuse" one, or {"type": "area", "radiance": [r, g, b]}, a lamp), "normals": "flat" or "vertex"}, ...]}, at most 8 '
+                         '"roughness": r, "metallic": m} (or a "dielectric" or "diffuse" one, or {"type": "roughdielectric", "int_ior": n, "ext_ior": n, "alpha": a}, frosted glass, or {"type": "area", "radiance": [r, g, b]}, a lamp), "normals": "flat" or "vertex"}, ...]}, at most 8 '
                          "objects; with it <scene>/oi.ply and <scene>/oi2.ply are not looked for and --oi_normals is ignored")
     ap.add_argument("--env_scale", type=float, default=1.0, metavar="S",
                     help="--integrator path and --mode oi: multiply the envmap by S before its sampling tables are built (1 = the same bits as "

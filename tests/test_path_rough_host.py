@@ -1,0 +1,502 @@
+"""Host side of rough dielectric inserted objects ("Rough dielectric objects"): the exported symbols, the sampler
+and the evaluation the kernel runs (on the CPU) against the fp64 restatement `path_rough_fp64`, their mutual consistency, the
+restatement's closed forms (reciprocity, the pdf's integral, the sampled directions' histogram), two scenes in expectation, the
+restatement over the library's fp32 traversal, the tables, the refusals and the routing.  No GPU needed."""
+import ctypes
+import functools
+import json
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import path_fp64 as pf  # noqa: E402
+import path_light_fp64 as pl  # noqa: E402
+import path_oi_fp64 as po  # noqa: E402
+import path_oi_pbr_fp64 as pp  # noqa: E402
+import path_oi_smooth_fp64 as ps  # noqa: E402
+import path_rough_fp64 as pr  # noqa: E402
+import path_testlib as tl  # noqa: E402
+
+FOV = pf.FOV
+SEEDS = list(range(100, 164))      # the 64 fixed seeds of the scenes in expectation
+ALPHAS = (0.02, 0.05, 0.2, 0.6, 1.0)
+IORS = ((1.49, 1.000277), (1.33, 1.0), (1.0, 1.49))
+LEFT_OUT_CAP = 1e-3                # the project's cap for element-wise comparisons
+# The lanes of tests 1 and 2 are chosen, from the fp64 restatement alone, where the BSDF is well conditioned: cos_t^2 (a difference, 0 at
+# total internal reflection), (wo . h)^2 and (wl . N)^2 (tan^2 divides by it) all at least WELL.  Below it a rounding of 2^-24 in a cosine
+# is a relative error of 1e-4 and more in a value that itself tends to 0, whatever the arithmetic; like |ng . wo| >= 0.05, this is a
+# condition on the inputs, and about 3 % of random lanes fall under it.
+WELL = 1e-3
+
+
+@pytest.fixture(scope="module")
+def path_lib():
+    return tl.load()
+
+
+_report = tl.reporter("path rough", "test_path_rough_host")
+
+
+def _bsdf(alpha, ior):
+    return {"type": "roughdielectric", "int_ior": ior[0], "ext_ior": ior[1], "alpha": alpha}
+
+
+def _unit(x):
+    return x / np.linalg.norm(x, axis=-1, keepdims=True)
+
+
+def _lanes(rng, N, smooth):
+    """N vertices with |ng . wo| >= 0.05 on both sides of the face, ns = ng or a normal 0.25 off it; all fp32 values."""
+    wo = _unit(rng.normal(size=(N, 3)))
+    ng = _unit(rng.normal(size=(N, 3)))
+    while True:
+        bad = np.abs((ng * wo).sum(-1)) < 0.06
+        if not bad.any():
+            break
+        ng[bad] = _unit(rng.normal(size=(int(bad.sum()), 3)))
+    ns = _unit(ng + 0.25 * rng.normal(size=(N, 3))) if smooth else ng
+    f = lambda x: x.astype(np.float32).astype(np.float64)
+    ng, ns, wo = _unit(f(ng)), _unit(f(ns)), _unit(f(wo))
+    return f(ng), f(ns), f(wo), f(rng.random((N, 3)))
+
+
+def _rel(a, b):
+    return np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
+
+
+@functools.lru_cache(maxsize=None)
+def _comparison():
+    """Tests 1 and 2 share one pass over 5 alphas x 3 index pairs x flat / smooth, 2048 lanes each (61440 in all): per quantity the worst
+    error of the float32 transcription and of the library against fp64 on the kept lanes, the share left out, and the library's own
+    sampler-against-evaluation differences."""
+    from materialist_amd import pathtrace as path_lib
+
+    rng = np.random.default_rng(5)
+    worst32 = {k: 0.0 for k in ("sample", "eval")}
+    worst_lib = dict(worst32)
+    n_all = n_out32 = n_out_lib = 0
+    self_pdf = self_w = 0.0
+    exact_zero = True
+    n_killed = n_trans = n_refl = n_inside = 0
+    for alpha in ALPHAS:
+        for ior in IORS:
+            for smooth in (False, True):
+                b = _bsdf(alpha, ior)
+                p = pr.rough_params(b)
+                ng, ns, wo, u = _lanes(rng, 2048, smooth)
+                s64, s32 = pr.rough_sample(p, ng, ns, wo, u), pr.rough_sample(p, ng, ns, wo, u, np.float32)
+                wi, w, pdf, fl = path_lib.rough_sample_host(b, ng, ns, wo, u)
+                assert np.array_equal(w[:, 0], w[:, 1]) and np.array_equal(w[:, 0], w[:, 2]) and not (fl & 1).any()
+                # a lane is left out where a discrete decision differs between fp32 and fp64: the lobe (u6 against F), a side test
+                same32 = (np.sign(s64["decisions"]) == np.sign(s32["decisions"])).all(-1) & ((s64["weight"] > 0) == (s32["weight"] > 0))
+                same_lib = (((fl & 2) != 0) == s64["transmitted"]) | ~s64["alive"]
+                same_lib &= (w[:, 0] > 0) == (s64["weight"] > 0)
+                # the lanes: those whose fp64 sample is well conditioned (WELL: away from grazing exit and from total internal reflection)
+                well = pr.rough_eval(p, ng, ns, wo, s64["wi"])["cond"] >= WELL
+                n_all += int(well.sum())
+                n_out32 += int((~same32 & well).sum())
+                n_out_lib += int((~same_lib & well).sum())
+                k = same32 & same_lib & (s64["weight"] > 0) & well
+                worst32["sample"] = max(worst32["sample"], _rel(s32["pdf"][k], s64["pdf"][k]).max(), _rel(s32["weight"][k], s64["weight"][k]).max(),
+                                        np.abs(s32["wi"][k] - s64["wi"][k]).max())
+                worst_lib["sample"] = max(worst_lib["sample"], _rel(pdf[k], s64["pdf"][k]).max(), _rel(w[k, 0], s64["weight"][k]).max(),
+                                          np.abs(wi[k] - s64["wi"][k]).max())
+                n_trans += int(s64["transmitted"][k].sum())
+                n_refl += int((~s64["transmitted"][k]).sum())
+                n_inside += int(((ng * wo).sum(-1) < 0)[k].sum())
+                # the evaluation: at the sampled directions (the library's own, as fp32 holds them) and at directions of their own
+                for wl in (wi.astype(np.float64), _unit(rng.normal(size=wo.shape)).astype(np.float32).astype(np.float64)):
+                    e64, e32 = pr.rough_eval(p, ng, ns, wo, wl), pr.rough_eval(p, ng, ns, wo, wl, np.float32)
+                    f, pe = path_lib.rough_eval_host(b, ng, ns, wo, wl)
+                    assert np.array_equal(f[:, 0], f[:, 1]) and np.array_equal(f[:, 0], f[:, 2])
+                    same32e = (np.sign(e64["decisions"]) == np.sign(e32["decisions"])).all(-1) & ((e64["f"] > 0) == (e32["f"] > 0))
+                    same_libe = (f[:, 0] > 0) == (e64["f"] > 0)
+                    well = (e64["cond"] >= WELL) | ~(e64["f"] > 0)
+                    n_all += int(well.sum())
+                    n_out32 += int((~same32e & well).sum())
+                    n_out_lib += int((~same_libe & well).sum())
+                    k2 = same32e & same_libe & (e64["f"] > 0) & well
+                    worst32["eval"] = max(worst32["eval"], _rel(e32["f"][k2], e64["f"][k2]).max(), _rel(e32["pdf"][k2], e64["pdf"][k2]).max())
+                    worst_lib["eval"] = max(worst_lib["eval"], _rel(f[k2, 0], e64["f"][k2]).max(), _rel(pe[k2], e64["pdf"][k2]).max())
+                # test 2: the library's evaluation at its own sampled direction
+                f, pe = path_lib.rough_eval_host(b, ng, ns, wo, wi)
+                ok = (w[:, 0] > 0) & (f[:, 0] > 0) & k
+                self_pdf = max(self_pdf, _rel(pe[ok], pdf[ok]).max())
+                self_w = max(self_w, _rel(f[ok, 0] / pe[ok], w[ok, 0]).max())
+                n_out_lib += int(((w[:, 0] > 0) & ~(f[:, 0] > 0) & k).sum())
+                # killed by the side rule (ng and the shading normal disagree about wi): the evaluation is 0 exactly there
+                gi = (ng.astype(np.float32) * wi).sum(-1)
+                nn = np.where(((ns * wo).sum(-1) * (ng * wo).sum(-1) > 0)[:, None], ns, ng)
+                ni = (nn.astype(np.float32) * wi).sum(-1)
+                clear = s64["killed"] & (gi.astype(np.float64) * ni < -1e-6)
+                n_killed += int(clear.sum())
+                exact_zero &= bool((f[clear, 0] == 0).all() and (pe[clear] == 0).all() and (w[clear, 0] == 0).all())
+    return {"worst32": worst32, "worst_lib": worst_lib, "out32": n_out32 / n_all, "out_lib": n_out_lib / n_all, "self_pdf": self_pdf,
+            "self_w": self_w, "exact_zero": exact_zero, "n_killed": n_killed, "n_trans": n_trans, "n_refl": n_refl, "n_inside": n_inside, "n": n_all}
+
+
+def _bound(worst32):
+    """The issue's rule: 1e-5 (the smooth sampler's bound) if the float32 transcription holds it, else 4 x the transcription's own worst
+    error (the library uses fmaf and another operation order)."""
+    return 1e-5 if 4 * worst32 <= 1e-5 else 4 * worst32
+
+
+# ---- 0: the symbols ----------------------------------------------------------------------------------------------------------------------
+def test_symbols(path_lib):
+    with open(os.path.join(ROOT, "include", "matpbr_path.h")) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    declared = set(re.findall(r"\b(matpbr_path_\w+)\s*\(", text))
+    new = {"matpbr_path_render_objects_rough", "matpbr_path_rough_sample_host", "matpbr_path_rough_eval_host"}
+    assert new <= declared and set(path_lib.ROUGH_SYMBOLS) == new and new <= set(path_lib.LATE_SYMBOLS)
+    lib = path_lib.load()
+    for name in new:
+        fn = path_lib.symbol(name, lib)
+        assert fn.argtypes == path_lib.SIGNATURES[name][1] and fn.restype == path_lib.SIGNATURES[name][0], name
+    assert lib.matpbr_path_version() == 3 == path_lib.VERSION
+    assert "MATPBR_PATH_BSDF_ROUGH_DIELECTRIC = 5" in text and path_lib.BSDF_ROUGH_DIELECTRIC == 5
+    assert path_lib.SIGNATURES["matpbr_path_render_objects_rough"] == path_lib.SIGNATURES["matpbr_path_render_objects_lights"]
+
+    class Old:
+        pass
+
+    for name in new:
+        with pytest.raises(path_lib.PathError, match=name):
+            path_lib.symbol(name, Old())
+
+
+# ---- 1: the host sampler and evaluation against the restatement -----------------------------------------------------------------------------
+def test_host_sampler_and_evaluation_against_the_restatement(path_lib):
+    """61440 vertices (alpha 0.02 ... 1, three index pairs, both sides, flat and smooth, |ng . wo| >= 0.05, the well-conditioned ones
+    kept: WELL) and twice as many evaluated directions.  The tolerance is not fixed in advance: the worst relative error of the numpy-float32 transcription of the
+    restatement against fp64 on the kept lanes, times 4 (1e-5 where the transcription holds 1e-5).  fp32 does not hold 1e-5 here even on
+    well-conditioned lanes: near the rim of the visible-normal sampler's disk sqrt(1 - t1^2 - t2^2) is the root of a difference, the
+    half vector moves by more than a rounding, and at alpha 0.02 D follows it steeply.  Measured: see the report lines."""
+    c = _comparison()
+    assert c["n"] >= 3 * 8192 and c["n_trans"] > 1000 and c["n_refl"] > 1000 and c["n_inside"] > 1000
+    _report("share of lanes left out (a discrete decision differs from fp64): float32 transcription / library", f"{c['out32']:.2e} / {c['out_lib']:.2e}")
+    assert c["out32"] <= LEFT_OUT_CAP and c["out_lib"] <= LEFT_OUT_CAP
+    for what in ("sample", "eval"):
+        bound = _bound(c["worst32"][what])
+        _report(f"{what}: worst relative error against fp64, float32 transcription / library (bound {bound:.2e})",
+                f"{c['worst32'][what]:.2e} / {c['worst_lib'][what]:.2e}")
+        assert c["worst_lib"][what] <= bound, what
+
+
+# ---- 2: internal consistency -------------------------------------------------------------------------------------------------------------------
+def test_evaluation_at_the_sampled_direction_is_the_sampler(path_lib):
+    """`rough_eval_host(wo, wi_sampled)`: the sampler's pdf, f / pdf its weight (test 1's bound for the evaluation: both sides are fp32
+    and the sampled wi is rounded to fp32 between them), and f = 0 exactly where the side rule dropped the sample."""
+    c = _comparison()
+    bound = max(_bound(c["worst32"]["eval"]), _bound(c["worst32"]["sample"]))
+    _report(f"evaluation at the sampled direction: worst relative difference of the pdf / of f / pdf against the weight (bound {bound:.2e})",
+            f"{c['self_pdf']:.2e} / {c['self_w']:.2e}")
+    assert c["self_pdf"] <= bound and c["self_w"] <= bound
+    assert c["n_killed"] > 100 and c["exact_zero"]
+
+
+# ---- 3: closed forms on the restatement -------------------------------------------------------------------------------------------------------
+def test_reciprocity():
+    """Without its cosine f(wo = a, wl = b) / eta_a^2 = f(wo = b, wl = a) / eta_b^2 (eta_x the index on x's side): what radiance
+    transport leaves of reciprocity.  Flat faces, reflection and transmission, to 1e-12 on the well-conditioned lanes."""
+    rng = np.random.default_rng(9)
+    N = 4096
+    ng = _unit(rng.normal(size=(N, 3)))
+    a, b = _unit(rng.normal(size=(N, 3))), _unit(rng.normal(size=(N, 3)))
+    for alpha in (0.05, 0.2, 1.0):
+        for ior in IORS:
+            p = pr.rough_params(_bsdf(alpha, ior))
+            side = lambda w: np.where((ng * w).sum(-1) > 0, p[1], p[0])      # outside: ext_ior
+            eab, eba = pr.rough_eval(p, ng, ng, a, b, cosine=False), pr.rough_eval(p, ng, ng, b, a, cosine=False)
+            fab, fba = eab["f"] / side(a) ** 2, eba["f"] / side(b) ** 2
+            # cos_t^2 = 1 - eta_ti^2 (1 - ci^2) is a difference: within 1e-3 of total internal reflection (or of grazing incidence, where
+            # tan^2 divides by a cosine^2 that small) fp64's 2^-53 is amplified a thousandfold and more, past 1e-12; those lanes are
+            # ill-conditioned in any arithmetic and stay out
+            both = ((fab > 0) | (fba > 0)) & (eab["cond"] >= 1e-3) & (eba["cond"] >= 1e-3)
+            trans = (ng * a).sum(-1) * (ng * b).sum(-1) < 0
+            assert (both & trans).sum() > 200 and (both & ~trans).sum() > 200
+            assert _rel(fab[both], fba[both]).max() <= 1e-12, (alpha, ior)
+
+
+def _sphere_grid(n_t, n_p):
+    """Midpoints of an n_t x n_p grid in (cos theta, phi) about +z -> (directions [n_t n_p, 3], the cell's solid angle)."""
+    ct = 1 - 2 * (np.arange(n_t) + 0.5) / n_t
+    ph = 2 * np.pi * (np.arange(n_p) + 0.5) / n_p
+    st = np.sqrt(1 - ct * ct)
+    w = np.stack([st[:, None] * np.cos(ph)[None], st[:, None] * np.sin(ph)[None], np.broadcast_to(ct[:, None], (n_t, n_p))], -1)
+    return w.reshape(-1, 3), 4 * np.pi / (n_t * n_p)
+
+
+@pytest.mark.parametrize("alpha,ior,cos_o", [(0.2, IORS[0], 0.8), (0.2, IORS[0], -0.6), (0.6, IORS[1], 0.3), (0.6, IORS[2], 0.7)])
+def test_pdf_integrates_and_samples_follow_it(alpha, ior, cos_o):
+    """The pdf integrates to at most 1 over the sphere, and to the share of samples the sampler accepts (midpoint rule, 768 x 1536
+    cells, against the share over a 256 x 256 grid of dims 7, 8 with dim 6 integrated); 2^16 stratified u fall into 8 x 16 bins of (cos theta, phi) within binomial 5 sigma of the pdf's integral over each bin
+    (plus 2e-3 of it for the quadrature), as the light sampler's test does."""
+    p = pr.rough_params(_bsdf(alpha, ior))
+    n_t, n_p = 768, 1536
+    W, dw = _sphere_grid(n_t, n_p)
+    ng = np.tile([0.0, 0.0, 1.0], (W.shape[0], 1))
+    wo1 = np.array([math.sqrt(1 - cos_o * cos_o), 0.0, cos_o])
+    cell = (pr.rough_eval(p, ng, ng, np.tile(wo1, (W.shape[0], 1)), W)["pdf"] * dw).reshape(n_t, n_p)
+    total = cell.sum()
+    g = (np.arange(256) + 0.5) / 256
+    u7, u8 = (x.reshape(-1) for x in np.meshgrid(g, g, indexing="ij"))
+    n = u7.size
+    assert n == 1 << 16
+    # dims 7, 8 on a 256 x 256 grid; dim 6 equidistributed (a Kronecker sequence) over a fixed shuffle of the lanes, so that the lobe
+    # choice is not quantised against F
+    u6 = np.mod((np.random.default_rng(3).permutation(n) + 0.5) * 0.6180339887498949, 1.0)
+    sample = lambda u_lobe: pr.rough_sample(p, ng[:n], ng[:n], np.tile(wo1, (n, 1)), np.stack([u_lobe, u7, u8], -1))
+    s, s_r, s_t = sample(u6), sample(np.zeros(n)), sample(np.full(n, 2.0))
+    ok = s["weight"] > 0
+    # the accepted share with dim 6 integrated out: F where the reflection is valid, 1 - F where the refraction is
+    share = float((s_r["F"] * (s_r["weight"] > 0) + (1 - s_r["F"]) * (s_t["weight"] > 0)).mean())
+    _report(f"alpha {alpha} eta {ior[0] / ior[1]:.3f} cos_o {cos_o}: integral of the pdf / accepted share", f"{total:.5f} / {share:.5f}")
+    assert total <= 1 + 1e-3
+    assert abs(total - share) <= 2e-3                                   # two midpoint rules, 768 x 1536 and 256 x 256
+    wi = s["wi"][ok]
+    bt = np.clip(((1 - wi[:, 2]) / 2 * 8).astype(int), 0, 7)
+    bp = np.clip((np.mod(np.arctan2(wi[:, 1], wi[:, 0]), 2 * np.pi) / (2 * np.pi) * 16).astype(int), 0, 15)
+    count = np.zeros((8, 16))
+    np.add.at(count, (bt, bp), 1)
+    prob = cell.reshape(8, n_t // 8, 16, n_p // 16).sum(axis=(1, 3))
+    slack = 5 * np.sqrt(n * prob * (1 - prob)) + 2e-3 * n * prob + 1.0
+    assert (np.abs(count - n * prob) <= slack).all(), np.argwhere(np.abs(count - n * prob) > slack)
+
+
+# ---- 4: in expectation ---------------------------------------------------------------------------------------------------------------------
+def _means(path_lib, objects, env, **kw):
+    Vs, Ts = pp.FAR_TRIANGLE
+    V, T, table = pr.merged(Vs, Ts, objects)
+    return pr.replay_mean(10, 12, 16, SEEDS, 16, V, T, env, path_lib.env_tables(env), table, **kw)
+
+
+def test_rough_sphere_in_a_constant_envmap(path_lib):
+    """A closed rough-glass sphere in a constant envmap c, nothing behind it: the pixels that miss are c exactly; the covered ones are
+    at most c (a single-scattering microfacet model loses energy, it never gains): mean <= c + 5 standard errors + 1e-3 c."""
+    objects = pr.furnace_scene(False)
+    inside, outside = tl.footprints(objects, 10, 12)
+    vals = _means(path_lib, objects, np.full((4, 8, 3), pr.FURNACE_C, np.float32))
+    c = float(np.float32(pr.FURNACE_C))
+    assert inside.sum() >= 12 and outside.sum() >= 12 and np.isfinite(vals).all()
+    assert np.abs(vals[:, outside] - c).max() <= 1e-12
+    mean, se = vals.mean(0), vals.std(0, ddof=1) / math.sqrt(vals.shape[0])
+    excess = ((mean - c) / (5 * se + 1e-3 * c))[inside]
+    _report(f"rough sphere in a constant envmap: worst (mean - c) / (5 se + 1e-3 c) over {int(inside.sum())} pixels; the least mean / c",
+            f"{excess.max():.3f}; {mean[inside].min() / c:.4f}")
+    assert excess.max() <= 1.0 and mean[inside].min() > 0.5 * c
+
+
+def test_lamp_inside_the_rough_sphere_two_sided_mis(path_lib):
+    """The sphere around a small lamp, zero envmap: finite, non-negative, non-zero, and the mean with the emitter sample switched off
+    (every MIS weight 1) agrees within 5 standard errors of the difference + 1e-3: the two-sided MIS bookkeeping sums to one."""
+    objects = pr.furnace_scene(True)
+    inside, _ = tl.footprints(objects[:1], 10, 12)
+    env = np.zeros((4, 8, 3), np.float32)
+    both = _means(path_lib, objects, env)
+    alone = _means(path_lib, objects, env, emitter_sample=False)
+    assert np.isfinite(both).all() and (both >= 0).all() and both[:, inside].max() > 0 and inside.sum() >= 12
+    se = np.sqrt(both.var(0, ddof=1) / both.shape[0] + alone.var(0, ddof=1) / alone.shape[0])
+    excess = (np.abs(both.mean(0) - alone.mean(0)) / (5 * se + 1e-3 * np.abs(alone.mean(0)) + 1e-300))[inside]
+    _report(f"lamp inside the rough sphere: worst |mean with - mean without emitter samples| / (5 se + 1e-3) over {int(inside.sum())} pixels",
+            f"{excess.max():.3f}")
+    assert excess.max() <= 1.0 and alone.mean(0)[inside].min() > 0
+
+
+# ---- 5: traversal, tables, refusals -----------------------------------------------------------------------------------------------------------
+def _groove(path_lib, H, W, objects):
+    from materialist_amd import mesh
+
+    rm = mesh.reference_mesh(pf.groove_scene(H, W), FOV)
+    rng = np.random.default_rng(11)
+    a, r, m = pf.groove_maps(H, W, rng)
+    return rm, a, r, m, pf.groove_env(rng)
+
+
+@pytest.mark.parametrize("env_on", [True, False])
+def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
+    """The GPU criterion's ground: over the library's fp32 traversal and over the fp64 brute force the restatement disagrees in NO pixel
+    of the GPU test's renders (the groove at 24 x 20 with `path_rough_fp64.table_scene`; max_depth 2, 6, 16; seeds 0-2; the envmap on
+    and zero), and across the renders every kind of rough-glass path occurs."""
+    H, W = 20, 24
+    objects = pr.table_scene()
+    rm, a, r, m, env = _groove(path_lib, H, W, objects)
+    if not env_on:
+        env = np.zeros_like(env)
+    V, T, table = pr.merged(rm["vertices"], rm["triangles"], objects)
+    Vm, Tm, tb, corner, records, lt = path_lib.merge_objects(rm["vertices"], rm["triangles"], objects, normals=True, pbr=True, lights=True)
+    n_scene = rm["triangles"].shape[0]
+    assert [t.kind for t in tb] == [0x105, 5, 4, 2, 0x101] and lt["header"].n_lights == 1
+    assert tuple(tb[1].p) == tuple(np.float32([1.49, 1.000277, 0.05]))
+    bvh = path_lib.build_bvh(Vm, Tm, n_scene)
+
+    def closest(o, d):
+        t, k = path_lib.trace_host(bvh, o, d)
+        return np.where(k < 0, np.inf, t.astype(np.float64)), k.astype(np.int64)
+
+    tab = path_lib.env_tables(env)
+    seen = {k: 0 for k in pr.RECORD_KEYS}
+    for max_depth in (2, 6, 16):
+        for seed in (0, 1, 2):
+            args = (oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, table)
+            L64, rec = pr.replay_rough(*args)
+            L32, _ = pr.replay_rough(*args, closest=closest)
+            assert rec["n_e"] == 1 + env_on
+            err = (np.abs(L32 - L64) / np.maximum(np.abs(L64), np.abs(L64).mean())).max(-1)
+            assert int((err > 1e-3).sum()) == 0, (max_depth, seed, np.argwhere(err > 1e-3)[:10])
+            for k in pr.RECORD_KEYS:
+                seen[k] += int(rec[k].sum())
+    _report(f"envmap {'on' if env_on else 'zero'}: pixels with " + " / ".join(pr.RECORD_KEYS) + " (9 renders)", " / ".join(str(seen[k]) for k in pr.RECORD_KEYS))
+    assert all(seen[k] > 0 for k in pr.RECORD_KEYS), seen
+
+
+def test_restatement_without_rough_objects_is_the_lights_restatement(oracle64, path_lib):
+    H, W = 10, 12
+    rm, a, r, m, env = _groove(path_lib, H, W, None)
+    V, T, table = pl.merged(rm["vertices"], rm["triangles"], pl.table_scene())
+    args = (oracle64, V, T, a, r, m, env, path_lib.env_tables(env), H, W, 6, 1, table)
+    ref, rec0 = pl.replay_lights(*args)
+    got, rec1 = pr.replay_rough(*args)
+    assert np.array_equal(ref, got) and rec1["n_e"] == 3
+    assert all(np.array_equal(rec0[k], rec1[k]) for k in rec0 if isinstance(rec0[k], np.ndarray))
+    assert not any(rec1[k].any() for k in pr.RECORD_KEYS)
+
+
+def test_tables_and_refusals(path_lib):
+    lib = path_lib.load()
+    Vs, Ts = pp.FAR_TRIANGLE
+    Vc, Tc = po.cube((0.0, 0.0, -1.0), 0.2, (0.0, 0.0, 0.0))
+    Vq, Tq = pl.quad(pl.LIGHT_QUAD)
+    objects = [{"vertices": Vc, "triangles": Tc, "bsdf": pr.FROSTED_02}, {"vertices": Vq, "triangles": Tq, "bsdf": pl.QUAD_LIGHT}]
+    # the light tables and the lookup take a table with kind 5
+    V, T, table, records, lt = path_lib.merge_objects(Vs, Ts, objects, pbr=True, lights=True)
+    assert [t.kind for t in table] == [5, 4] and lt["header"].n_lights == 1 and lt["header"].object[0] == 1
+    _, _, table2, records2 = path_lib.merge_objects(Vs, Ts, [objects[0], {"vertices": Vq, "triangles": Tq, "bsdf": pp.PLASTIC}], pbr=True)
+    kind, a_, r_, m_ = path_lib.object_lookup_host(table2, records2, np.array([0, 1, 12, 13, 14, 15], np.int32))   # (it knows no kind 4)
+    assert kind.tolist() == [0, 5, 5, 3, 3, 0] and not a_[:3].any() and a_[3:5].all()
+    # the features: id 1 + k and the normal the render shades the camera vertex with (flat: the face normal)
+    Vm, Tm, tb, corner, _ = path_lib.merge_objects(Vs, Ts, objects[:1], normals=True, pbr=True)
+    geom = path_lib.features_host(path_lib.build_bvh(Vm, Tm, 1), 5, 6, FOV, tb, corner, 1)
+    hit = geom[..., 7] == 1.0
+    assert hit.any() and np.abs(geom[hit][:, 4:7] - [0.0, 0.0, 1.0]).max() <= 1e-6
+    # every bound of the kind, at the binding and at the C ABI
+    nan, inf = float("nan"), float("inf")
+    good = (1.49, 1.000277, 0.1)
+    bad = [(0.0, 1.0, 0.1), (-1.5, 1.0, 0.1), (1.5, 0.0, 0.1), (nan, 1.0, 0.1), (1.5, inf, 0.1), (inf, 1.0, 0.1), (1.005, 1.0, 0.1), (1.0, 1.0, 0.1),
+           (1.0, 1.009, 0.1), (1.5, 1.0, 0.019), (1.5, 1.0, 0.0), (1.5, 1.0, 1.001), (1.5, 1.0, nan), (1.5, 1.0, -0.1), (1e-30, 1e30, 0.5),
+           (1e30, 1e-30, 0.5)]                                       # the last two: a ratio that underflows to 0 or overflows in fp32
+    assert path_lib.object_bsdf(dict(pr.FROSTED_02)) == (5, (1.49, 1.000277, 0.2))
+    assert path_lib.object_bsdf({"type": "roughdielectric"}) == (5, good)
+    for p in ((1.5, 1.0, 0.02), (1.5, 1.0, 1.0), (1.0, 1.02, 0.5), (1.02, 1.0, 0.5)):
+        assert path_lib.object_bsdf({"type": "roughdielectric", "int_ior": p[0], "ext_ior": p[1], "alpha": p[2]})[0] == 5, p
+    for p in bad:
+        with pytest.raises(ValueError, match="roughdielectric"):
+            path_lib.object_bsdf({"type": "roughdielectric", "int_ior": p[0], "ext_ior": p[1], "alpha": p[2]})
+    with pytest.raises(ValueError, match="'roughdielectric'"):
+        path_lib.object_bsdf({"type": "frosted"})
+    P_ = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    tab = lambda t: ctypes.cast(t, ctypes.c_void_p)
+    obj = lambda k, p=good, n=12: (path_lib.PathObject * 1)(path_lib.PathObject(k, 1, n, (ctypes.c_float * 3)(*p)))
+    one = np.zeros(12, np.float32)
+    one[2] = 1.0
+    io = np.zeros(3, np.int32)
+
+    def sample(ob):
+        return lib.matpbr_path_rough_sample_host(tab(ob), P_(one), P_(one), P_(one), P_(one[3:]), 1, P_(one[6:]), P_(one[9:]), P_(one[3:]), P_(io))
+
+    def evaluate(ob):
+        return lib.matpbr_path_rough_eval_host(tab(ob), P_(one), P_(one), P_(one), P_(one), 1, P_(one[6:]), P_(one[3:]))
+
+    frame = [P_(one)] * 5 + [4, 4, 35.0] + [P_(one)] * 4 + [2, 4, 1, 4, 0, 1, P_(one), None, None]
+    render = lib.matpbr_path_render_objects_rough
+    assert sample(obj(5)) == 0 and sample(obj(0x105)) == 0 and evaluate(obj(5)) == 0
+    for p in bad:
+        assert sample(obj(5, p)) == -1 and evaluate(obj(5, p)) == -1, p
+        assert render(*frame, tab(obj(5, p)), 1, None, 1, None, None, None, None) == -1, p
+    for k in (1, 2, 3, 4):
+        assert sample(obj(k)) == -1 and evaluate(obj(k)) == -1
+    assert sample(None) == -1 and evaluate(None) == -1
+    assert lib.matpbr_path_rough_sample_host(tab(obj(5)), None, P_(one), P_(one), P_(one), 1, P_(one), P_(one), P_(one), P_(io)) == -1
+    assert lib.matpbr_path_rough_eval_host(tab(obj(5)), P_(one), P_(one), P_(one), None, 1, P_(one), P_(one)) == -1
+    # null tables: a smooth rough object without corner normals; a light beside the rough object without light tables
+    assert render(*frame, tab(obj(0x105)), 1, None, 1, None, None, None, None) == -1
+    two = (path_lib.PathObject * 2)(path_lib.PathObject(5, 1, 12, (ctypes.c_float * 3)(*good)), path_lib.PathObject(4, 13, 2, (ctypes.c_float * 3)(1, 1, 1)))
+    assert render(*frame, tab(two), 2, None, 1, None, None, None, None) == -1
+    assert render(*frame, None, 1, None, 1, None, None, None, None) == -1
+    bad_depth = list(frame)
+    bad_depth[15] = 17
+    assert render(*bad_depth, tab(obj(5)), 1, None, 1, None, None, None, None) == -1      # a valid table: still refused before any launch
+    # every older entry point refuses kind 5 as an unknown kind
+    assert lib.matpbr_path_render_objects(*frame, tab(obj(5)), 1) == -1
+    assert lib.matpbr_path_render_objects_normals(*frame, tab(obj(5)), 1, P_(one), 1) == -1
+    assert lib.matpbr_path_render_objects_pbr(*frame, tab(obj(5)), 1, None, 1, None) == -1
+    assert lib.matpbr_path_render_objects_lights(*frame, tab(obj(5)), 1, None, 1, None, None, None, None) == -1
+    assert lib.matpbr_path_object_sample_host(tab(obj(5)), P_(one), P_(one), P_(one), 1, P_(one), P_(one), P_(one), P_(io)) == -1
+    assert lib.matpbr_path_object_sample_shading_host(tab(obj(5)), P_(one), P_(one), P_(one), P_(one), 1, P_(one), P_(one), P_(one), P_(io)) == -1
+    with pytest.raises(ValueError, match="rough_sample_host"):
+        path_lib.object_sample_host(pr.FROSTED_02, [0, 0, 1], [[0, 0, 1]], [[0.5, 0.5, 0.5]])
+    with pytest.raises(ValueError, match="roughdielectric"):
+        path_lib.rough_sample_host(po.GLASS, [0, 0, 1], [0, 0, 1], [[0, 0, 1]], [[0.5, 0.5, 0.5]])
+
+
+class _Host:
+    """torch.from_numpy's result for a tracer built without a device: keeps the array, `.to()` returns itself."""
+
+    def __init__(self, x):
+        self.x = x
+
+    def to(self, *a, **k):
+        return self
+
+
+def test_routing_scene_file_and_guide(path_lib, monkeypatch, tmp_path):
+    """`PathTracer` asks for the rough entry point only with a rough object and counts it; `render_bwd` refuses; the object list file
+    takes the type with either kind of normals; the albedo guide is 1 on rough glass."""
+    import torch
+
+    from materialist_amd import mesh, relight
+
+    asked = []
+    real = path_lib.symbol
+    monkeypatch.setattr(path_lib, "symbol", lambda name, lib=None: (asked.append(name), real(name, lib))[1])
+    monkeypatch.setattr(path_lib.torch, "from_numpy", lambda x: _Host(x))
+    Vs, Ts = pp.FAR_TRIANGLE
+    for objects in (pl.table_scene(), pp.table_scene(), po.two_cubes(), None):
+        del asked[:]
+        tracer = path_lib.PathTracer(Vs, Ts, 4, 4, FOV, device="cpu", objects=objects)
+        assert "matpbr_path_render_objects_rough" not in asked and not tracer.rough and tracer.stats["n_rough_objects"] == 0
+    del asked[:]
+    tracer = path_lib.PathTracer(Vs, Ts, 4, 4, FOV, device="cpu", objects=pr.table_scene())
+    assert "matpbr_path_render_objects_rough" in asked and tracer.rough
+    assert tracer.stats["n_rough_objects"] == 2 and tracer.stats["n_lights"] == 1 and tracer.stats["n_smooth_objects"] == 2 and tracer.pbr is not None
+    with pytest.raises(ValueError, match="objects"):
+        tracer.render_bwd(None, None, None, None, None)
+    alone = path_lib.PathTracer(Vs, Ts, 4, 4, FOV, device="cpu", objects=pr.furnace_scene(False))
+    assert alone.rough and alone.lights is None and alone.stats["n_rough_objects"] == 1 and alone.pbr is not None
+    # the object list file
+    Vi, Ti, _ = ps.icosphere((0.0, 0.0, -1.0), 0.1, 0)
+    os.makedirs(tmp_path / "lists")
+    mesh.write_ply(str(tmp_path / "lists" / "globe.ply"), Vi, Ti)
+    path = str(tmp_path / "lists" / "globe.json")
+    frosted = {"type": "roughdielectric", "int_ior": 1.49, "ext_ior": 1.000277, "alpha": 0.1}
+    for normals in ("flat", "vertex"):
+        with open(path, "w") as f:
+            json.dump({"objects": [{"ply": "globe.ply", "bsdf": frosted, "normals": normals}]}, f)
+        got = relight.load_oi_scene(path)
+        assert got[0]["bsdf"] == frosted and got[0]["normals"] == normals
+    with open(path, "w") as f:
+        json.dump({"objects": [{"ply": "globe.ply", "bsdf": dict(frosted, alpha=0.001)}]}, f)
+    with pytest.raises(ValueError, match=r"objects\[0\].*bad bsdf.*alpha must lie in"):
+        relight.load_oi_scene(path)
+    geom = torch.zeros(1, 2, 8)
+    geom[..., 7] = torch.tensor([[1.0, 0.0]])
+    guide = relight.albedo_guide(geom, torch.full((1, 2, 3), 0.25), [frosted]).numpy()
+    assert np.all(guide[0, 0] == 1.0) and np.all(guide[0, 1] == 0.25)
