@@ -179,9 +179,10 @@ int matpbr_path_object_sample_shading_host(const MatpbrPathObject* object, const
  * record's constants: one-sided about the outward face normal ng, no texel read, ns = ng or, where smooth, the interpolated normal
  * with its three fallbacks; the emitter sample needs ng . wl > 0 and takes f and its pdf from the BSDF about ns; the BSDF sample is
  * MatDiffBSDF's about ns (lobe by dim 6 > 0.5, weight f / (pdf + 1e-6) where pdf > 1e-6), not a delta event, a sample with
- * ng . wi <= 0 ends the path, and the next ray starts on ng's side.  With no object of kind 3 this calls
- * matpbr_path_render_objects_normals and gives its bits (pbr may be NULL then).  Invalid arguments, besides that entry point's: an
- * object of kind 3 with pbr == NULL or with a record outside the ranges above. */
+ * ng . wi <= 0 ends the path, and the next ray starts on ng's side.  This is level 3 of the table in DESIGN.md section 1.4, "The
+ * object entries": with no object of kind 3 it launches matpbr_path_render_objects_normals' kernel and gives its bits (pbr may be NULL
+ * then).  Invalid arguments, besides that entry point's: an object of kind 3 with pbr == NULL or with a record outside the ranges
+ * above. */
 int matpbr_path_render_objects_pbr(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
                                    float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
                                    int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
@@ -226,8 +227,9 @@ int matpbr_path_light_tables(const double* vert, long n_vert, const int32_t* tri
  * cos_l = n_l . (-wl) > 0, ng . wl > 0, dist > 0; the shadow ray is any-hit up to dist (1 - 1e-3); the sample adds
  * thr f p mis(pdf, pdf_b) / pdf.  A traced ray that lands on a light's front (ng . wo > 0) adds thr p w, w = 1 at depth 0 or after a
  * delta vertex, else mis(prev_pdf, t^2 / (A (ng . wo) n_e)), BEFORE the max_depth test, and ends; on its back it ends with nothing
- * added.  An escaped ray's weight takes env_pdf / n_e.  Without an object of kind 4 this calls matpbr_path_render_objects_pbr and
- * gives its bits (the three light arguments may be NULL then).  Invalid arguments, besides that entry point's: a negative or
+ * added.  An escaped ray's weight takes env_pdf / n_e.  This is level 4 of the table in DESIGN.md section 1.4, "The object entries":
+ * without an object of kind 4 it launches matpbr_path_render_objects_pbr's kernel and gives its bits (the three light arguments may
+ * be NULL then).  Invalid arguments, besides that entry point's: a negative or
  * non-finite radiance, kind 4 with the smooth flag, null tables with a kind-4 object, a header that is not the table's (the lights
  * are the kind-4 objects in order, records contiguous from 0, n_tri the object's), an area that is not finite and > 0. */
 int matpbr_path_render_objects_lights(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -261,9 +263,9 @@ int matpbr_path_light_pdf_host(const MatpbrPathLights* lights, const void* light
  * (ng . w)(n . w) <= 0 carries nothing.  The vertex shades from both sides (no back-face exit); its emitter sample (chosen as
  * matpbr_path_render_objects_lights chooses, sampled from the point spawn_eps off the face on ng's side) is taken on either side of
  * the face, its shadow ray starting spawn_eps off the face on the sample's side.  With a kind-5 object the table may hold no light:
- * the three light arguments may be NULL then, and the envmap, where it has tables, is the only emitter.  Without a kind-5 object
- * this calls matpbr_path_render_objects_lights and gives its bits.  Invalid arguments, besides that entry point's: the bounds of
- * kind 5 above. */
+ * the three light arguments may be NULL then, and the envmap, where it has tables, is the only emitter.  This is level 5 of the table
+ * in DESIGN.md section 1.4, "The object entries": without a kind-5 object it launches matpbr_path_render_objects_lights' kernel and
+ * gives its bits.  Invalid arguments, besides that entry point's: the bounds of kind 5 above. */
 int matpbr_path_render_objects_rough(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
                                      float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
                                      int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,

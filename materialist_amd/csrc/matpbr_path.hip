@@ -670,93 +670,102 @@ bool frame_args(const Frame& f, PathArgs& q) {
     return true;
 }
 
-// what the renders select their kernel on: `rough` the rough-dielectric instantiation, else `edit` the transparency-editing instantiation, else `nrm` the shading-normal one, else `pbr`
-// the PBR-object one (obj_nrm may be null then: no object is smooth), else `obj_nrm` the smooth-object one, else ot.n > 0 the object one
-struct Extras {
+// the path_kernel instantiation a render launches; it also says which members of `Scene` the launch reads
+enum class Kernel { NoObjects, ObjTable, SmoothObjects, PbrObjects, LightObjects, RoughObjects, TransEdit, ShadeNormals };
+// what a render hands its kernel besides the frame, checked
+struct Scene {
+    Kernel kernel = Kernel::NoObjects;
     ObjTable ot{};
-    const float* obj_nrm = nullptr;   // set where some object is smooth
+    const float* obj_nrm = nullptr;             // set where some object is smooth
     int32_t n_scene_tri = 0;
-    const MatpbrPathObjectPbr* pbr = nullptr;
-    const LightTable* lights = nullptr;   // set where some object is a light (pbr may be null then: no object is of kind 3)
-    bool rough = false;                   // some object is a rough dielectric: `lights` is set (its table may be empty)
-    const TransEdit* edit = nullptr;
+    const MatpbrPathObjectPbr* pbr = nullptr;   // set where some object is of kind 3
+    LightTable lt{};                            // empty (n = 0) where no object is a light
+    TransEdit edit{};
     const float* nrm = nullptr;
 };
 
-// the object arguments of the entry points that know smooth objects, as the C ABI receives them ...
-struct ObjectArgs {
-    const MatpbrPathObject* objects;
-    int n_objects;
-    const float* obj_nrm;
-    long n_scene_tri;
-    const MatpbrPathObjectPbr* pbr;   // nullable: no record is checked
-};
-// ... checked into the table, the corner normals, n_scene_tri and the records of `x`.  `with_pbr`: a kind may be MATPBR_PATH_BSDF_PBR;
-// `n_light` (nullable): where given, a kind may be MATPBR_PATH_BSDF_AREA, counted there; `n_rough` likewise for
-// MATPBR_PATH_BSDF_ROUGH_DIELECTRIC
-bool object_extras(const ObjectArgs& g, bool with_pbr, Extras& x, int* n_light = nullptr, int* n_rough = nullptr) {
-    int n_smooth = 0, n_pbr = 0;
-    if (!object_table(g.objects, g.n_objects, x.ot, &n_smooth, with_pbr ? &n_pbr : nullptr, g.pbr, n_light, n_rough) || g.n_scene_tri < 0 ||
-        g.n_scene_tri > INT32_MAX || (n_smooth > 0 && !g.obj_nrm))
-        return false;
-    for (int k = 0; k < g.n_objects; ++k)
-        if (g.objects[k].first_tri < g.n_scene_tri) return false;
-    x.obj_nrm = n_smooth > 0 ? g.obj_nrm : nullptr;
-    x.n_scene_tri = (int32_t)g.n_scene_tri;
-    x.pbr = g.pbr;
-    return true;
-}
-
-int render_common(const Frame& f, const Extras& x) {
-    PathArgs q{};
-    if (!f.out || !frame_args(f, q)) return MATPBR_PATH_ERR_INVALID_ARG;
+template <class Table>
+int launch_frame(const Frame& f, const PathArgs& q, const Table& table) {
     const dim3 grid = tile_grid(f.H, f.W), block(kTileX, kTileY);
-    const hipStream_t st = (hipStream_t)f.stream;
-    PbrObjects pbo{};
-    if (x.pbr) {
-        pbo.t = x.ot;
-        pbo.nrm = x.obj_nrm;
-        pbo.n_scene_tri = x.n_scene_tri;
-        for (int k = 0; k < x.ot.n; ++k) pbo.pbr[k] = x.pbr[k];
-    }
-    LightObjects lo{};
-    if (x.lights) {
-        lo.t = x.ot;
-        lo.nrm = x.obj_nrm;
-        lo.n_scene_tri = x.n_scene_tri;
-        for (int k = 0; x.pbr && k < x.ot.n; ++k) lo.pbr[k] = x.pbr[k];
-        lo.lt = *x.lights;
-    }
-    RoughObjects ro{};
-    if (x.rough) static_cast<LightObjects&>(ro) = lo;
     for (int s0 = 0; s0 < f.spp; s0 += f.spp_per_launch) {
         const int s1 = std::min(f.spp, s0 + f.spp_per_launch);
         const int first = s0 == 0 ? 1 : 0, last = s1 == f.spp ? 1 : 0;
-        if (x.rough) hipLaunchKernelGGL(path_kernel<RoughObjects>, grid, block, 0, st, q, s0, s1, first, last, ro);
-        else if (x.edit) hipLaunchKernelGGL(path_kernel<TransEdit>, grid, block, 0, st, q, s0, s1, first, last, *x.edit);
-        else if (x.nrm) hipLaunchKernelGGL(path_kernel<ShadeNormals>, grid, block, 0, st, q, s0, s1, first, last, ShadeNormals{x.nrm});
-        else if (x.lights) hipLaunchKernelGGL(path_kernel<LightObjects>, grid, block, 0, st, q, s0, s1, first, last, lo);
-        else if (x.pbr) hipLaunchKernelGGL(path_kernel<PbrObjects>, grid, block, 0, st, q, s0, s1, first, last, pbo);
-        else if (x.obj_nrm) hipLaunchKernelGGL(path_kernel<SmoothObjects>, grid, block, 0, st, q, s0, s1, first, last, SmoothObjects{x.ot, x.obj_nrm, x.n_scene_tri});
-        else if (x.ot.n > 0) hipLaunchKernelGGL(path_kernel<ObjTable>, grid, block, 0, st, q, s0, s1, first, last, x.ot);
-        else hipLaunchKernelGGL(path_kernel<NoObjects>, grid, block, 0, st, q, s0, s1, first, last, NoObjects{});
+        hipLaunchKernelGGL(path_kernel<Table>, grid, block, 0, (hipStream_t)f.stream, q, s0, s1, first, last, table);
         if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
     }
     return MATPBR_PATH_OK;
 }
 
+int render_common(const Frame& f, const Scene& s) {
+    PathArgs q{};
+    if (!f.out || !frame_args(f, q)) return MATPBR_PATH_ERR_INVALID_ARG;
+    switch (s.kernel) {
+        case Kernel::NoObjects: return launch_frame(f, q, NoObjects{});
+        case Kernel::ObjTable: return launch_frame(f, q, s.ot);
+        case Kernel::SmoothObjects: return launch_frame(f, q, SmoothObjects{s.ot, s.obj_nrm, s.n_scene_tri});
+        case Kernel::TransEdit: return launch_frame(f, q, s.edit);
+        case Kernel::ShadeNormals: return launch_frame(f, q, ShadeNormals{s.nrm});
+        default: break;
+    }
+    RoughObjects ro{};   // the three kernels whose tables extend one another
+    ro.t = s.ot;
+    ro.nrm = s.obj_nrm;
+    ro.n_scene_tri = s.n_scene_tri;
+    for (int k = 0; s.pbr && k < s.ot.n; ++k) ro.pbr[k] = s.pbr[k];
+    if (s.kernel == Kernel::PbrObjects) return launch_frame<PbrObjects>(f, q, ro);
+    ro.lt = s.lt;
+    return s.kernel == Kernel::LightObjects ? launch_frame<LightObjects>(f, q, ro) : launch_frame(f, q, ro);
+}
+
+// The table of an entry point that knows n_scene_tri, with the rules those entries share: n_scene_tri an int32 >= 0, no range starts
+// below it, and corner normals are given where an object is smooth.
+bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept, const float* obj_nrm, long n_scene_tri,
+                 const MatpbrPathObjectPbr* pbr, ObjTable& ot, ObjCounts& n) {
+    if (!object_table(objects, n_objects, accept, pbr, ot, &n) || n_scene_tri < 0 || n_scene_tri > INT32_MAX || (n.smooth > 0 && !obj_nrm)) return false;
+    for (int k = 0; k < n_objects; ++k)
+        if (objects[k].first_tri < n_scene_tri) return false;
+    return true;
+}
+
+// The five object entries are the five levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
+// admits kinds 1 and 2, level 2 the smooth flag on them, level 3 kind 3, level 4 kind 4, level 5 kind 5.  An entry passes null / 0 for
+// the arguments it does not have; level 1's n_scene_tri = 0 lies below every range.  An argument is consulted only where the table needs
+// it: obj_nrm where an object is smooth, pbr where one is of kind 3, the light header and buffers where one is of kind 4.  The counts
+// alone choose the kernel.
+int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                   const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf) {
+    const unsigned accept = (level >= 2 ? kAcceptSmooth : 0u) | (level >= 3 ? kAcceptPbr : 0u) | (level >= 4 ? kAcceptLight : 0u) |
+                            (level >= 5 ? kAcceptRough : 0u);
+    Scene s;
+    ObjCounts n;
+    if (!scene_table(objects, n_objects, accept, obj_nrm, n_scene_tri, pbr, s.ot, n) || (n.pbr > 0 && !pbr) ||
+        (n.light > 0 && !light_table(lights, &s.ot, light_tris, light_cdf, s.lt)))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    s.kernel = n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
+               n.smooth > 0 ? Kernel::SmoothObjects : n_objects > 0 ? Kernel::ObjTable : Kernel::NoObjects;
+    s.obj_nrm = n.smooth > 0 ? obj_nrm : nullptr;
+    s.n_scene_tri = (int32_t)n_scene_tri;
+    s.pbr = n.pbr > 0 ? pbr : nullptr;
+    return render_common(f, s);
+}
+
 // the arguments both feature entry points share, checked and packed: `q` arrives with the caller's pointers and sizes
-bool features_args(const ObjectArgs& g, float fov_x_deg, FeatArgs& q, Extras& x) {
+bool features_args(const MatpbrPathObject* objects, int n_objects, long n_scene_tri, float fov_x_deg, FeatArgs& q, ObjTable& ot) {
     // an object of kind 3, 4 or 5 is valid here: the features read its kind and its flag, never its record or its light tables
-    int n_light = 0, n_rough = 0;
-    if (!q.nodes || !q.tris || !q.geom || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) || !object_extras(g, true, x, &n_light, &n_rough)) return false;
-    q.n_scene_tri = x.n_scene_tri;
+    ObjCounts n;
+    if (!q.nodes || !q.tris || !q.geom || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) ||
+        !scene_table(objects, n_objects, kAcceptAll, q.obj_nrm, n_scene_tri, nullptr, ot, n))
+        return false;
+    q.n_scene_tri = (int32_t)n_scene_tri;
     const Camera c = camera(q.H, q.W, fov_x_deg);   // the render's
     q.f_pix = c.f_pix; q.cx = c.cx; q.cy = c.cy;
     q.f_ndc = c.f_ndc; q.aspect = c.aspect;
     q.rho_scale = (float)(2.0 * c.th / q.W);
     return true;
 }
+
+// the Frame of a render entry point, from the names every one of them gives its first 21 parameters
+#define RENDER_FRAME Frame{nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}
 
 }  // namespace
 
@@ -939,18 +948,14 @@ int matpbr_path_render_objects(const void* nodes, const void* tris, const float*
                                float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
                                int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                                const MatpbrPathObject* objects, int n_objects) {
-    Extras x;
-    if (!object_table(objects, n_objects, x.ot)) return MATPBR_PATH_ERR_INVALID_ARG;
-    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+    return render_objects(RENDER_FRAME, 1, objects, n_objects, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int matpbr_path_render_objects_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
                                        float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
                                        int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                                        const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri) {
-    Extras x;
-    if (!object_extras({objects, n_objects, obj_nrm, n_scene_tri, nullptr}, false, x)) return MATPBR_PATH_ERR_INVALID_ARG;
-    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+    return render_objects(RENDER_FRAME, 2, objects, n_objects, obj_nrm, n_scene_tri, nullptr, nullptr, nullptr, nullptr);
 }
 
 int matpbr_path_object_normal_host(const float* tri, const float* nrm, const float* o, const float* d, long N, float* u, float* v, float* ns) {
@@ -984,24 +989,15 @@ int matpbr_path_render_objects_pbr(const void* nodes, const void* tris, const fl
                                    int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                                    const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                    const MatpbrPathObjectPbr* pbr) {
-    bool any_pbr = false;
-    for (int k = 0; objects && k >= 0 && k < n_objects && k < MATPBR_PATH_MAX_OBJECTS; ++k)
-        any_pbr = any_pbr || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR;
-    if (!any_pbr)
-        return matpbr_path_render_objects_normals(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
-                                                  spp_per_launch, out, rays, stream, objects, n_objects, obj_nrm, n_scene_tri);
-    Extras x;
-    if (!pbr || !object_extras({objects, n_objects, obj_nrm, n_scene_tri, pbr}, true, x)) return MATPBR_PATH_ERR_INVALID_ARG;
-    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+    return render_objects(RENDER_FRAME, 3, objects, n_objects, obj_nrm, n_scene_tri, pbr, nullptr, nullptr, nullptr);
 }
 
 int matpbr_path_light_tables(const double* vert, long n_vert, const int32_t* tri, long n_tri, const MatpbrPathObject* objects, int n_objects,
                              const MatpbrPathObjectPbr* pbr, MatpbrPathLights* lights, float* light_tris, float* light_cdf, long capacity,
                              long* n_light_tri) {
     ObjTable ot{};
-    int n_smooth = 0, n_pbr = 0, n_light = 0, n_rough = 0;
     if (!vert || !tri || !lights || !n_light_tri || n_vert <= 0 || n_tri < 0 || n_tri > INT32_MAX / 3 || (light_tris && (!light_cdf || capacity < 0)) ||
-        !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr, &n_light, &n_rough))
+        !object_table(objects, n_objects, kAcceptAll, pbr, ot))
         return MATPBR_PATH_ERR_INVALID_ARG;
     return light_tables_build(vert, n_vert, tri, n_tri, ot, lights, light_tris, light_cdf, capacity, n_light_tri);
 }
@@ -1012,48 +1008,16 @@ int matpbr_path_render_objects_lights(const void* nodes, const void* tris, const
                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                       const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
                                       const float* light_cdf) {
-    bool any_light = false, any_pbr = false;
-    for (int k = 0; objects && k >= 0 && k < n_objects && k < MATPBR_PATH_MAX_OBJECTS; ++k) {
-        any_light = any_light || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_AREA;
-        any_pbr = any_pbr || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR;
-    }
-    if (!any_light)
-        return matpbr_path_render_objects_pbr(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
-                                              spp_per_launch, out, rays, stream, objects, n_objects, obj_nrm, n_scene_tri, pbr);
-    Extras x;
-    LightTable lt;
-    int n_light = 0;
-    if ((any_pbr && !pbr) || !object_extras({objects, n_objects, obj_nrm, n_scene_tri, pbr}, true, x, &n_light) ||
-        !light_table(lights, x.ot, light_tris, light_cdf, lt))
-        return MATPBR_PATH_ERR_INVALID_ARG;
-    x.lights = &lt;
-    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
-}
-
-// the header of the two CPU entry points, checked against itself (no object table there): records contiguous from 0 within n_light_tri
-static bool light_header(const MatpbrPathLights* h, const void* tri, const float* cdf, long n_light_tri, LightTable& lt) {
-    if (!h || !tri || ((uintptr_t)tri & 15) || h->n_lights < 1 || h->n_lights > kMaxLights) return false;
-    lt = LightTable{};
-    lt.tri = static_cast<const float4*>(tri);
-    lt.cdf = cdf;
-    lt.n = h->n_lights;
-    long first = 0;
-    for (int l = 0; l < h->n_lights; ++l) {
-        if (h->first[l] != first || h->n_tri[l] < 1 || !(h->area[l] > 0.0f) || !std::isfinite(h->area[l])) return false;
-        lt.first[l] = h->first[l];
-        lt.n_tri[l] = h->n_tri[l];
-        lt.area[l] = h->area[l];
-        first += h->n_tri[l];
-    }
-    return first == n_light_tri;
+    return render_objects(RENDER_FRAME, 4, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf);
 }
 
 int matpbr_path_light_sample_host(const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf, long n_light_tri, int have_env,
                                   const float* po, const float* u, long N, int32_t* emitter, float* u_re, int32_t* record, float* y, float* wl,
                                   float* dist, float* pdf) {
     LightTable lt;
+    long n_rec = 0;
     if (!light_cdf || !po || !u || !emitter || !u_re || !record || !y || !wl || !dist || !pdf || N < 0 || (have_env != 0 && have_env != 1) ||
-        !light_header(lights, light_tris, light_cdf, n_light_tri, lt))
+        !light_table(lights, nullptr, light_tris, light_cdf, lt, &n_rec) || n_rec != n_light_tri)
         return MATPBR_PATH_ERR_INVALID_ARG;
     const int n_e = have_env + lt.n;
     for (long k = 0; k < N; ++k) {
@@ -1071,8 +1035,9 @@ int matpbr_path_light_sample_host(const MatpbrPathLights* lights, const void* li
 int matpbr_path_light_pdf_host(const MatpbrPathLights* lights, const void* light_tris, long n_light_tri, int have_env, const int32_t* light,
                                const int32_t* record, const float* o, const float* d, long N, float* t, float* pdf) {
     LightTable lt;
+    long n_rec = 0;
     if (!light || !record || !o || !d || !t || !pdf || N < 0 || (have_env != 0 && have_env != 1) ||
-        !light_header(lights, light_tris, nullptr, n_light_tri, lt))
+        !light_table(lights, nullptr, light_tris, nullptr, lt, &n_rec) || n_rec != n_light_tri)
         return MATPBR_PATH_ERR_INVALID_ARG;
     const float n_e = (float)(have_env + lt.n);
     for (long k = 0; k < N; ++k) {
@@ -1095,25 +1060,7 @@ int matpbr_path_render_objects_rough(const void* nodes, const void* tris, const 
                                      const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                      const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
                                      const float* light_cdf) {
-    bool any_rough = false, any_light = false, any_pbr = false;
-    for (int k = 0; objects && k >= 0 && k < n_objects && k < MATPBR_PATH_MAX_OBJECTS; ++k) {
-        any_rough = any_rough || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC;
-        any_light = any_light || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_AREA;
-        any_pbr = any_pbr || (objects[k].kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR;
-    }
-    if (!any_rough)
-        return matpbr_path_render_objects_lights(nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed,
-                                                 spp_per_launch, out, rays, stream, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris,
-                                                 light_cdf);
-    Extras x;
-    LightTable lt{};   // without a light: no record is read (n = 0)
-    int n_light = 0, n_rough = 0;
-    if ((any_pbr && !pbr) || !object_extras({objects, n_objects, obj_nrm, n_scene_tri, pbr}, true, x, &n_light, &n_rough) ||
-        (any_light && !light_table(lights, x.ot, light_tris, light_cdf, lt)))
-        return MATPBR_PATH_ERR_INVALID_ARG;
-    x.lights = &lt;
-    x.rough = true;
-    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+    return render_objects(RENDER_FRAME, 5, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf);
 }
 
 // the object of the two CPU entry points below: kind 5, with or without the smooth flag (the caller passes both normals either way)
@@ -1145,8 +1092,8 @@ int matpbr_path_rough_eval_host(const MatpbrPathObject* object, const float* ng,
 int matpbr_path_object_lookup_host(const MatpbrPathObject* objects, int n_objects, const MatpbrPathObjectPbr* pbr, const int32_t* ids, long N,
                                    int32_t* kind, float* a, float* r, float* m) {
     ObjTable ot{};
-    int n_smooth = 0, n_pbr = 0, n_rough = 0;
-    if (!ids || !kind || !a || !r || !m || N < 0 || !object_table(objects, n_objects, ot, &n_smooth, &n_pbr, pbr, nullptr, &n_rough) || (n_pbr > 0 && !pbr))
+    ObjCounts n;
+    if (!ids || !kind || !a || !r || !m || N < 0 || !object_table(objects, n_objects, kAcceptAll & ~kAcceptLight, pbr, ot, &n) || (n.pbr > 0 && !pbr))
         return MATPBR_PATH_ERR_INVALID_ARG;
     for (long k = 0; k < N; ++k) {
         float p[3] = {0.0f, 0.0f, 0.0f};
@@ -1162,19 +1109,20 @@ int matpbr_path_render_trans(const void* nodes, const void* tris, const float* a
                              int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                              const uint8_t* mask, const float* bg, const MatpbrPathTransEdit* edit) {
     if (!mask || !bg || !trans_edit_valid(edit)) return MATPBR_PATH_ERR_INVALID_ARG;
-    const TransEdit te{mask, bg, edit->ior, edit->spec_trans, edit->refract_distance};
-    Extras x;
-    x.edit = &te;
-    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+    Scene s;
+    s.kernel = Kernel::TransEdit;
+    s.edit = TransEdit{mask, bg, edit->ior, edit->spec_trans, edit->refract_distance};
+    return render_common(RENDER_FRAME, s);
 }
 
 int matpbr_path_render_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
                                float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
                                int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                                const float* nrm) {
-    Extras x;
-    x.nrm = nrm;
-    return render_common({nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}, x);
+    Scene s;
+    s.kernel = nrm ? Kernel::ShadeNormals : Kernel::NoObjects;
+    s.nrm = nrm;
+    return render_common(RENDER_FRAME, s);
 }
 
 int matpbr_path_eval_normal_grad_host(const float* n, const float* wo, const float* wi, const float* a, const float* r, const float* m,
@@ -1285,22 +1233,22 @@ int matpbr_path_render_bwd_normals(const void* nodes, const void* tris, const fl
 int matpbr_path_features(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
                          const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom, void* stream) {
     FeatArgs q{static_cast<const float4*>(nodes), static_cast<const float4*>(tris), obj_nrm, nrm_map, reinterpret_cast<float4*>(geom), H, W};
-    Extras x;
-    if (!features_args({objects, n_objects, obj_nrm, n_scene_tri, nullptr}, fov_x_deg, q, x)) return MATPBR_PATH_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(features_kernel, tile_grid(H, W), dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, x.ot);
+    ObjTable ot{};
+    if (!features_args(objects, n_objects, n_scene_tri, fov_x_deg, q, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(features_kernel, tile_grid(H, W), dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, ot);
     return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
 }
 
 int matpbr_path_features_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
                               const float* obj_nrm, long n_scene_tri, const float* nrm_map, float* geom) {
     FeatArgs q{static_cast<const float4*>(nodes), static_cast<const float4*>(tris), obj_nrm, nrm_map, reinterpret_cast<float4*>(geom), H, W};
-    Extras x;
-    if (!features_args({objects, n_objects, obj_nrm, n_scene_tri, nullptr}, fov_x_deg, q, x)) return MATPBR_PATH_ERR_INVALID_ARG;
+    ObjTable ot{};
+    if (!features_args(objects, n_objects, n_scene_tri, fov_x_deg, q, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
     for (int i = 0; i < H; ++i)
         for (int j = 0; j < W; ++j) {
             HostStack stk;
             float4 g0, g1;
-            features_pixel(q, x.ot, i, j, stk, g0, g1);
+            features_pixel(q, ot, i, j, stk, g0, g1);
             q.geom[2 * ((long)i * W + j)] = g0;
             q.geom[2 * ((long)i * W + j) + 1] = g1;
         }

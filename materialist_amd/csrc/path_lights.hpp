@@ -123,28 +123,30 @@ __host__ __device__ inline float tri_t(const float4* tris, int k, const float o[
     return dot3h(e2, qv) * (1.0f / det);
 }
 
-// the caller's header against the (checked) table: the lights are the kind-4 objects in table order, their records follow each other
-// from 0, every area is finite and positive.  -> the kernel's table (tri / cdf are the caller's device or host buffers)
-bool light_table(const MatpbrPathLights* h, const ObjTable& ot, const void* tri, const float* cdf, LightTable& lt, long* n_light_tri = nullptr) {
-    if (!h || !tri || !cdf || ((uintptr_t)tri & 15) || h->n_lights < 1 || h->n_lights > kMaxLights) return false;
+// The caller's header -> the kernel's table (tri / cdf are the caller's device or host buffers): the records of the lights follow each
+// other from 0, every area is finite and positive.  With `ot`, the (checked) table: the lights are its kind-4 objects in table order,
+// n_tri the object's, cdf is needed, and the radiances and the objects' areas are filled in.  Without (the CPU entry points, which have
+// no table): the header is checked against itself alone.  *n_light_tri: the records it counts.
+bool light_table(const MatpbrPathLights* h, const ObjTable* ot, const void* tri, const float* cdf, LightTable& lt, long* n_light_tri = nullptr) {
+    if (!h || !tri || (ot && !cdf) || ((uintptr_t)tri & 15) || h->n_lights < 1 || h->n_lights > kMaxLights) return false;
     lt = LightTable{};
     lt.tri = static_cast<const float4*>(tri);
     lt.cdf = cdf;
     lt.n = h->n_lights;
     int l = 0;
     long first = 0;
-    for (int k = 0; k < ot.n; ++k) {
-        if (ot.o[k].kind != MATPBR_PATH_BSDF_AREA) continue;
-        if (l >= h->n_lights || h->object[l] != k || h->first[l] != first || h->n_tri[l] != ot.o[k].n_tri || h->n_tri[l] < 1 ||
-            !(h->area[l] > 0.0f) || !std::isfinite(h->area[l]))
-            return false;
+    for (int k = 0; k < (ot ? ot->n : h->n_lights); ++k) {
+        if (ot && ot->o[k].kind != MATPBR_PATH_BSDF_AREA) continue;
+        if (l >= h->n_lights || h->first[l] != first || h->n_tri[l] < 1 || !(h->area[l] > 0.0f) || !std::isfinite(h->area[l])) return false;
         lt.first[l] = h->first[l];
         lt.n_tri[l] = h->n_tri[l];
         lt.area[l] = h->area[l];
-        lt.obj_area[k] = h->area[l];
-        for (int c = 0; c < 3; ++c) lt.rad[l][c] = ot.o[k].p[c];
         first += h->n_tri[l];
-        if (first > INT32_MAX) return false;
+        if (ot) {
+            if (h->object[l] != k || h->n_tri[l] != ot->o[k].n_tri || first > INT32_MAX) return false;
+            lt.obj_area[k] = h->area[l];
+            for (int c = 0; c < 3; ++c) lt.rad[l][c] = ot->o[k].p[c];
+        }
         ++l;
     }
     if (n_light_tri) *n_light_tri = first;

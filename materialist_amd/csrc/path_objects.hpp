@@ -440,44 +440,47 @@ bool rough_valid(const float p[3]) {
     const float eta = p[0] / p[1];
     return eta > 0.0f && std::isfinite(eta) && std::isfinite(1.0f / eta) && fabsf(eta - 1.0f) >= 0.01f && p[2] >= 0.02f && p[2] <= 1.0f;
 }
-// `n_smooth` (nullable): where given, a kind may carry MATPBR_PATH_OBJECT_SMOOTH, and the flagged objects are counted.  `n_pbr`
-// (nullable): where given, a kind may be MATPBR_PATH_BSDF_PBR (its p[] is ignored), and those objects are counted; their records
-// are checked where `pbr` is given.  `n_light` (nullable): where given, a kind may be MATPBR_PATH_BSDF_AREA (without the smooth flag; p =
-// radiance, finite and >= 0), and those objects are counted.  `n_rough` (nullable): where given, a kind may be
-// MATPBR_PATH_BSDF_ROUGH_DIELECTRIC (rough_valid), and those objects are counted.
-bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, int* n_smooth = nullptr, int* n_pbr = nullptr,
-                  const MatpbrPathObjectPbr* pbr = nullptr, int* n_light = nullptr, int* n_rough = nullptr) {
+// What a table may hold besides the plain kinds 1 and 2, as object_table's accept mask: kAcceptSmooth a kind that carries
+// MATPBR_PATH_OBJECT_SMOOTH; kAcceptPbr kind MATPBR_PATH_BSDF_PBR (its p[] is ignored; its record is checked where `pbr` is given);
+// kAcceptLight kind MATPBR_PATH_BSDF_AREA (never with the smooth flag; p = radiance, finite and >= 0); kAcceptRough kind
+// MATPBR_PATH_BSDF_ROUGH_DIELECTRIC (rough_valid).  A kind outside the mask is an unknown kind.
+enum : unsigned { kAcceptSmooth = 1u, kAcceptPbr = 2u, kAcceptLight = 4u, kAcceptRough = 8u, kAcceptAll = 15u };
+// how many objects of a checked table are smooth, of kind 3, of kind 4, of kind 5
+struct ObjCounts {
+    int smooth = 0, pbr = 0, light = 0, rough = 0;
+};
+bool object_table(const MatpbrPathObject* objects, int n_objects, unsigned accept, const MatpbrPathObjectPbr* pbr, ObjTable& ot,
+                  ObjCounts* counts = nullptr) {
     if (n_objects < 0 || n_objects > MATPBR_PATH_MAX_OBJECTS || (n_objects > 0 && !objects)) return false;
     ot.n = n_objects;
     ot.min_id = INT32_MAX;
-    if (n_smooth) *n_smooth = 0;
-    if (n_pbr) *n_pbr = 0;
-    if (n_light) *n_light = 0;
-    if (n_rough) *n_rough = 0;
+    ObjCounts c;
     for (int k = 0; k < n_objects; ++k) {
         MatpbrPathObject plain = objects[k];
-        if (n_light && plain.kind == MATPBR_PATH_BSDF_AREA) {   // checked as a diffuse object of reflectance 0: the range alone
-            for (int c = 0; c < 3; ++c)
-                if (!(plain.p[c] >= 0.0f) || !std::isfinite(plain.p[c])) return false;
-            plain.kind = MATPBR_PATH_BSDF_DIFFUSE;
-            plain.p[0] = plain.p[1] = plain.p[2] = 0.0f;
-            ++*n_light;
+        bool range_alone = false;   // kinds 3, 4, 5 are checked as a diffuse object of reflectance 0: the range alone
+        if ((accept & kAcceptLight) && plain.kind == MATPBR_PATH_BSDF_AREA) {
+            for (int j = 0; j < 3; ++j)
+                if (!(plain.p[j] >= 0.0f) || !std::isfinite(plain.p[j])) return false;
+            range_alone = true;
+            ++c.light;
         }
-        if (n_smooth && (plain.kind & MATPBR_PATH_OBJECT_SMOOTH)) {
+        if ((accept & kAcceptSmooth) && (plain.kind & MATPBR_PATH_OBJECT_SMOOTH)) {
             plain.kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
-            ++*n_smooth;
+            ++c.smooth;
         }
-        if (n_rough && plain.kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC) {   // checked as a diffuse object of reflectance 0: the range alone
+        if ((accept & kAcceptRough) && plain.kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC) {
             if (!rough_valid(plain.p)) return false;
-            plain.kind = MATPBR_PATH_BSDF_DIFFUSE;
-            plain.p[0] = plain.p[1] = plain.p[2] = 0.0f;
-            ++*n_rough;
+            range_alone = true;
+            ++c.rough;
         }
-        if (n_pbr && plain.kind == MATPBR_PATH_BSDF_PBR) {   // checked as a diffuse object of reflectance 0: the range alone
+        if ((accept & kAcceptPbr) && plain.kind == MATPBR_PATH_BSDF_PBR) {
             if (pbr && !pbr_valid(pbr[k])) return false;
+            range_alone = true;
+            ++c.pbr;
+        }
+        if (range_alone) {
             plain.kind = MATPBR_PATH_BSDF_DIFFUSE;
             plain.p[0] = plain.p[1] = plain.p[2] = 0.0f;
-            ++*n_pbr;
         }
         if (!object_valid(plain)) return false;
         for (int j = 0; j < k; ++j)   // ranges may not overlap
@@ -486,6 +489,7 @@ bool object_table(const MatpbrPathObject* objects, int n_objects, ObjTable& ot, 
         ot.o[k] = objects[k];
         ot.min_id = std::min(ot.min_id, objects[k].first_tri);
     }
+    if (counts) *counts = c;
     return true;
 }
 bool trans_edit_valid(const MatpbrPathTransEdit* e) {

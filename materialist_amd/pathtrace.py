@@ -127,6 +127,13 @@ LIGHT_SYMBOLS = ("matpbr_path_light_tables", "matpbr_path_render_objects_lights"
 # and (rough dielectric inserted objects)
 ROUGH_SYMBOLS = ("matpbr_path_render_objects_rough", "matpbr_path_rough_sample_host", "matpbr_path_rough_eval_host")
 LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS
+# the feature each of them came with, as `symbol` names it
+_FEATURE = {name: what for names, what in ((SMOOTH_SYMBOLS, "smooth inserted objects"), (DENOISE_SYMBOLS, "the denoiser"),
+                                           (PBR_SYMBOLS, "PBR inserted objects"), (LIGHT_SYMBOLS, "emissive inserted objects"),
+                                           (ROUGH_SYMBOLS, "rough dielectric inserted objects")) for name in names}
+# the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
+OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
+                  "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8}
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -157,9 +164,7 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        what = ("the denoiser" if name in DENOISE_SYMBOLS else "PBR inserted objects" if name in PBR_SYMBOLS else
-                "emissive inserted objects" if name in LIGHT_SYMBOLS else "rough dielectric inserted objects" if name in ROUGH_SYMBOLS else
-                "smooth inserted objects")
+        what = _FEATURE.get(name, "smooth inserted objects")
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 
@@ -762,23 +767,20 @@ class PathTracer:
         n_smooth = n_pbr = n_lights = n_rough = 0
         if objects:
             vertices, triangles, table, corner, records, lt = merge_objects(vertices, triangles, objects, normals=True, pbr=True, lights=True)
-            if lt is not None:
-                symbol("matpbr_path_render_objects_lights")
-                n_lights = int(lt["header"].n_lights)
-                self.lights = (lt["header"], torch.from_numpy(lt["tris"]).to(self.device), torch.from_numpy(lt["cdf"]).to(self.device))
             self.objects = (PathObject * len(table))(*table)
             n_smooth = sum(1 for t in table if t.kind & OBJECT_SMOOTH)
             n_pbr = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_PBR)
             n_rough = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_ROUGH_DIELECTRIC)
-            if n_rough:
-                symbol("matpbr_path_render_objects_rough")
-                self.rough = True
-            if n_pbr:
-                symbol("matpbr_path_render_objects_pbr")
+            for have, level in ((lt is not None, "lights"), (n_rough, "rough"), (n_pbr, "pbr"), (corner is not None, "normals")):
+                if have:                              # a library built before the feature: PathError now, not at the first render
+                    symbol("matpbr_path_render_objects_" + level)
+            if lt is not None:
+                n_lights = int(lt["header"].n_lights)
+                self.lights = (lt["header"], torch.from_numpy(lt["tris"]).to(self.device), torch.from_numpy(lt["cdf"]).to(self.device))
+            self.rough = n_rough > 0
             if n_pbr or lt is not None or n_rough:    # the light and rough entry points take the records beside the table as well
                 self.pbr = (PathObjectPbr * len(records))(*records)
             if corner is not None:
-                symbol("matpbr_path_render_objects_normals")
                 self.obj_nrm = torch.from_numpy(corner).to(self.device)
             bvh = build_bvh(vertices, triangles, n_scene)
         else:
@@ -836,6 +838,16 @@ class PathTracer:
             raise ValueError(f"normal must be [{self.H},{self.W},3], got {tuple(nrm.shape)}")
         return nrm.to(self.device, torch.float32).contiguous()
 
+    def object_args(self) -> tuple:
+        """(table, n_objects, obj_nrm, n_scene_tri, records, lights header, light_tris, light_cdf): the object arguments of a forward
+        entry point after `stream`, as the C ABI takes them, None where the tracer has none.  An entry takes the first
+        OBJECT_ENTRIES[its name] of them."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        table, records = _table_ptrs(self.objects, self.pbr)
+        head, ltris, lcdf = self.lights if self.lights is not None else (None, None, None)
+        return (table, len(self.objects) if self.objects is not None else 0, ptr(self.obj_nrm), self.n_scene_tris, records,
+                ctypes.cast(ctypes.byref(head), _P) if head is not None else None, ptr(ltris), ptr(lcdf))
+
     @torch.no_grad()
     def render(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
                seed: int = 0, spp_per_launch: int = 8, out: Optional[torch.Tensor] = None, rays: Optional[torch.Tensor] = None,
@@ -853,34 +865,15 @@ class PathTracer:
         lib = load()
         args = (*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), out.data_ptr(), rays.data_ptr() if rays is not None else None,
                 torch.cuda.current_stream(dev).cuda_stream)
-        table, records = _table_ptrs(self.objects, self.pbr)
         if nrm is not None:
-            check(lib.matpbr_path_render_normals(*args, nrm.data_ptr()), "matpbr_path_render_normals")
+            entry, own = "matpbr_path_render_normals", (nrm.data_ptr(),)
         elif self.objects is None:
-            check(lib.matpbr_path_render(*args), "matpbr_path_render")
-        elif self.rough:
-            head, ltris, lcdf = self.lights if self.lights is not None else (None, None, None)
-            check(symbol("matpbr_path_render_objects_rough", lib)(*args, table, len(self.objects),
-                                                                  self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,
-                                                                  self.n_scene_tris, records,
-                                                                  ctypes.cast(ctypes.byref(head), _P) if head is not None else None,
-                                                                  ltris.data_ptr() if ltris is not None else None,
-                                                                  lcdf.data_ptr() if lcdf is not None else None), "matpbr_path_render_objects_rough")
-        elif self.lights is not None:
-            head, ltris, lcdf = self.lights
-            check(symbol("matpbr_path_render_objects_lights", lib)(*args, table, len(self.objects),
-                                                                   self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,
-                                                                   self.n_scene_tris, records, ctypes.cast(ctypes.byref(head), _P),
-                                                                   ltris.data_ptr(), lcdf.data_ptr()), "matpbr_path_render_objects_lights")
-        elif self.pbr is not None:
-            check(symbol("matpbr_path_render_objects_pbr", lib)(*args, table, len(self.objects),
-                                                                self.obj_nrm.data_ptr() if self.obj_nrm is not None else None,
-                                                                self.n_scene_tris, records), "matpbr_path_render_objects_pbr")
-        elif self.obj_nrm is None:
-            check(lib.matpbr_path_render_objects(*args, table, len(self.objects)), "matpbr_path_render_objects")
+            entry, own = "matpbr_path_render", ()
         else:
-            check(symbol("matpbr_path_render_objects_normals", lib)(*args, table, len(self.objects), self.obj_nrm.data_ptr(), self.n_scene_tris),
-                  "matpbr_path_render_objects_normals")
+            entry = "matpbr_path_render_objects" + ("_rough" if self.rough else "_lights" if self.lights is not None else
+                                                    "_pbr" if self.pbr is not None else "_normals" if self.obj_nrm is not None else "")
+            own = self.object_args()[:OBJECT_ENTRIES[entry]]
+        check(symbol(entry, lib)(*args, *own), entry)
         return out
 
     @torch.no_grad()

@@ -78,6 +78,14 @@ def raw_args(tracer, maps, spp, max_depth, seed, spp_per_launch, out):
     return keep, (*tracer._frame(*keep, spp, max_depth, seed, spp_per_launch), out.data_ptr(), None, torch.cuda.current_stream().cuda_stream)
 
 
+def object_tail(tracer, entry="matpbr_path_render_objects_rough"):
+    """The object arguments of the forward entry point `entry` after `stream`, for calls past `PathTracer.render`: the prefix of
+    `PathTracer.object_args()` it takes (all eight by default)."""
+    from materialist_amd import pathtrace
+
+    return tracer.object_args()[:pathtrace.OBJECT_ENTRIES[entry]]
+
+
 def groove_with_objects(pt, objects, merged):
     """The groove at 24 x 20 (a partial tile) with `objects` in front of it; `merged`: the restatement's table builder.  -> the maps,
     the envmap, the mesh `rm`, the merged V, T, table and the tracer."""

@@ -109,14 +109,6 @@ def test_the_furnace_box(pt, inner, max_depth, env_value):
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------------------
-def _light_tail(pt, tracer):
-    head, ltris, lcdf = tracer.lights if tracer.lights is not None else (None, None, None)
-    table, records = pt._table_ptrs(tracer.objects, tracer.pbr)
-    return (table, len(tracer.objects), tracer.obj_nrm.data_ptr() if tracer.obj_nrm is not None else None, tracer.n_scene_tris, records,
-            ctypes.cast(ctypes.byref(head), ctypes.c_void_p) if head is not None else None, ltris.data_ptr() if ltris is not None else None,
-            lcdf.data_ptr() if lcdf is not None else None)
-
-
 def test_bits(pt, scene, oracle64):
     s = scene
     maps = (s["a"], s["r"], s["m"], s["env"])
@@ -130,7 +122,7 @@ def test_bits(pt, scene, oracle64):
     assert old.stats["n_lights"] == 0 and old.lights is None and old.pbr is not None
     ref = torch.empty(H, W, 3, device=old.device)
     keep, args = _raw_args(old, maps, 6, 16, 5, 4, ref)
-    tail = _light_tail(pt, old)
+    tail = tl.object_tail(old)
     assert pt.symbol("matpbr_path_render_objects_pbr")(*args, *tail[:5]) == 0
     head, ltris, lcdf = s["tracer"].lights
     for extra in (tail[5:], (ctypes.cast(ctypes.byref(head), ctypes.c_void_p), ltris.data_ptr(), lcdf.data_ptr())):
@@ -155,7 +147,7 @@ def test_bits(pt, scene, oracle64):
     # the light entry point through PathTracer.render is the raw call
     out = torch.empty(H, W, 3, device=old.device)
     _, args3 = _raw_args(s["tracer"], maps, 6, 16, 5, 4, out)
-    assert pt.symbol("matpbr_path_render_objects_lights")(*args3, *_light_tail(pt, s["tracer"])) == 0
+    assert pt.symbol("matpbr_path_render_objects_lights")(*args3, *tl.object_tail(s["tracer"])) == 0
     assert np.array_equal(_bits(s["tracer"].render(*maps, spp=6, max_depth=16, seed=5, spp_per_launch=4)), _bits(out))
     # a light of radiance 0 beside an envmap is not the render without it (n_e changed); it is finite and the restatement's
     Vd, Td = po.cube(*pl.DIFFUSE_CUBE)

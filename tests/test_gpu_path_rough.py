@@ -3,7 +3,6 @@ dielectric objects"): every path of a table with two rough-glass objects, a ligh
 against the fp64 restatement, bits (launch splits, a table without rough objects, the routes `render` took before), the two scenes of
 tests/test_path_rough_host.py in expectation on the device, the features of a rough object, and `render_final.py --mode oi
 --oi_scene globe.json` with and without the denoiser."""
-import ctypes
 import json
 import math
 import os
@@ -81,14 +80,6 @@ def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64, env_on):
 
 
 # ---- 7 ---------------------------------------------------------------------------------------------------------------------------------
-def _tail(pt, tracer):
-    head, ltris, lcdf = tracer.lights if tracer.lights is not None else (None, None, None)
-    table, records = pt._table_ptrs(tracer.objects, tracer.pbr)
-    return (table, len(tracer.objects), tracer.obj_nrm.data_ptr() if tracer.obj_nrm is not None else None, tracer.n_scene_tris, records,
-            ctypes.cast(ctypes.byref(head), ctypes.c_void_p) if head is not None else None, ltris.data_ptr() if ltris is not None else None,
-            lcdf.data_ptr() if lcdf is not None else None)
-
-
 def test_bits(pt, scene):
     s = scene
     maps = (s["a"], s["r"], s["m"], s["env"])
@@ -101,7 +92,7 @@ def test_bits(pt, scene):
     # PathTracer.render with rough glass is the raw call
     out = torch.empty(H, W, 3, device=s["tracer"].device)
     keep, args = _raw_args(s["tracer"], maps, 6, 16, 5, 4, out)
-    assert rough(*args, *_tail(pt, s["tracer"])) == 0
+    assert rough(*args, *tl.object_tail(s["tracer"])) == 0
     assert np.array_equal(_bits(s["tracer"].render(*maps, spp=6, max_depth=16, seed=5, spp_per_launch=4)), _bits(out))
 
     def routed(objects, entry, n_tail, direct=None):
@@ -110,7 +101,7 @@ def test_bits(pt, scene):
         assert not tracer.rough and tracer.stats["n_rough_objects"] == 0
         ref = torch.empty(H, W, 3, device=tracer.device)
         keep, args = _raw_args(tracer, maps, 6, 16, 5, 4, ref)
-        tail = _tail(pt, tracer) if objects else ()
+        tail = tl.object_tail(tracer) if objects else ()
         assert (direct or pt.symbol(entry))(*args, *tail[:n_tail]) == 0
         assert np.array_equal(_bits(tracer.render(*maps, spp=6, max_depth=16, seed=5, spp_per_launch=4)), _bits(ref)), entry
         if objects:
@@ -127,7 +118,7 @@ def test_bits(pt, scene):
     # the older light entry point refuses the table with rough glass
     out = torch.empty(H, W, 3, device=s["tracer"].device)
     _, args3 = _raw_args(s["tracer"], maps, 1, 2, 0, 1, out)
-    assert lights(*args3, *_tail(pt, s["tracer"])) == -1
+    assert lights(*args3, *tl.object_tail(s["tracer"])) == -1
 
 
 # ---- 8 ---------------------------------------------------------------------------------------------------------------------------------
