@@ -58,6 +58,11 @@ enum {
  * objects").  Only matpbr_path_render_objects_normals takes it; to matpbr_path_render_objects it is an unknown kind. */
 #define MATPBR_PATH_OBJECT_SMOOTH 0x100
 
+/* OR-ed into MatpbrPathObject.kind beside MATPBR_PATH_OBJECT_SMOOTH: the object's reflectance (kind 2) or albedo (kind 3) is multiplied
+ * by a colour interpolated from its corners ("Vertex-coloured inserted objects").  Valid on kinds 2 and 3 only.
+ * Only matpbr_path_render_objects_colors and matpbr_path_feature_colors take it; to every other entry point it is an unknown kind. */
+#define MATPBR_PATH_OBJECT_COLORED 0x200
+
 /* One inserted mesh: triangles [first_tri, first_tri + n_tri) of the mesh handed to matpbr_path_bvh_build_objects (ids at or
  * above its n_scene_tri), outward winding. */
 typedef struct MatpbrPathObject {
@@ -283,6 +288,40 @@ int matpbr_path_rough_sample_host(const MatpbrPathObject* object, const float* n
  * f[N,3] (with its cosine, the radiance factor included) and pdf[N], the density matpbr_path_rough_sample_host gives wl. */
 int matpbr_path_rough_eval_host(const MatpbrPathObject* object, const float* ng, const float* ns, const float* wo, const float* wl, long N,
                                 float* f, float* pdf);
+
+/* ---- Vertex-coloured inserted objects ("Vertex-coloured inserted objects") --------------------------------------
+ * matpbr_path_render_objects_rough where an object of kind 2 or 3 may carry MATPBR_PATH_OBJECT_COLORED (with or without
+ * MATPBR_PATH_OBJECT_SMOOTH), forward only.  obj_col (DEVICE, fp32, [n_tri - n_scene_tri, 3, 3]): one linear RGB triple per corner of
+ * every inserted triangle, in input order, indexed by id - n_scene_tri (obj_nrm's layout), finite and in [0, 1] (the caller's
+ * responsibility: the library cannot check a device buffer); the triangles of objects without the flag are never read.  At a hit on a
+ * flagged object u, v are Moller-Trumbore's (the ones the smooth normal uses), c = clamp(c0 + u (c1 - c0) + v (c2 - c0), 0, 1) per
+ * channel, and the vertex shades with reflectance p * c (kind 2) or albedo a * c (kind 3; roughness and metallic stay the record's).
+ * Neither sampler depends on the colour: the object walks the paths of its uncoloured twin.  This is level 6 of the table in DESIGN.md
+ * section 1.4, "The object entries": without a flagged object it launches matpbr_path_render_objects_rough's kernel choice and gives
+ * its bits (obj_col may be NULL then).  Invalid arguments, besides that entry point's: a flagged object with obj_col == NULL, the flag
+ * on kind 1, 4 or 5. */
+int matpbr_path_render_objects_colors(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                      float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                      int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                      const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                      const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                      const float* light_cdf, const float* obj_col);
+
+/* The colour of a flagged object at a hit on the CPU, with the routines the kernel runs (the barycentrics of the winning triangle and
+ * the interpolation): per lane the triangle record tri[N,3,3] = (v0, e1, e2), the corner colours col[N,3,3] and the ray o[N,3], d[N,3]
+ * -> u[N], v[N], c[N,3].  Three equal corners give exactly their colour; every c lies in [0, 1]. */
+int matpbr_path_object_color_host(const float* tri, const float* col, const float* o, const float* d, long N, float* u, float* v, float* c);
+
+/* The colour guide of the denoiser: one ray per pixel through its centre, matpbr_path_features' ray and traversal.  out[H,W,3] (DEVICE)
+ * = the interpolated colour c where the first hit lies on a flagged object, (1, 1, 1) everywhere else (no hit included).  objects
+ * (HOST, copied before the call returns; any kind the render entries take), n_scene_tri and obj_col (DEVICE; nullable without a
+ * flagged object) as matpbr_path_render_objects_colors takes them.  The barycentrics are formed without contraction, so that the CPU
+ * twin gives the same bits. */
+int matpbr_path_feature_colors(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                               long n_scene_tri, const float* obj_col, float* out, void* stream);
+/* matpbr_path_feature_colors on the CPU with the routine the kernel runs (every pointer HOST). */
+int matpbr_path_feature_colors_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects,
+                                    int n_objects, long n_scene_tri, const float* obj_col, float* out);
 
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;

@@ -45,10 +45,13 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 // lights: one emitter of n_e (the envmap, the lights) is sampled per vertex, and a ray that lands on a light adds its emission and
 // ends; every `if (LIGHT ...)` folds away in the other six.  ROUGH: LIGHT with objects of kind 5 (Objects = RoughObjects), rough
 // dielectrics: a non-delta vertex that shades from both sides, whose emitter sample may arrive on either side of the face and whose
-// light table may be empty; every `if (ROUGH ...)` folds away in the other seven.
+// light table may be empty; every `if (ROUGH ...)` folds away in the other seven.  COLOR: ROUGH with vertex-coloured objects (Objects =
+// ColorObjects): at a vertex of a flagged object of kind 2 or 3 the reflectance or the albedo is multiplied by the colour interpolated
+// from the triangle's corners; every `if (COLOR ...)` folds away in the other eight.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value;
+    constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value;
+    constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
     constexpr bool LIGHT = std::is_same<Objects, LightObjects>::value || ROUGH;
     constexpr bool PBR = std::is_same<Objects, PbrObjects>::value || LIGHT;
     constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value || PBR;
@@ -101,8 +104,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             int kind = 0;          // (OBJ) 0: the depth mesh; else the inserted object's BSDF and its parameters
             float op[3] = {0.0f, 0.0f, 0.0f};
             float oa[3] = {0.0f, 0.0f, 0.0f}, o_r = 0.0f, o_m = 0.0f;   // (PBR) the record of an object of kind 3
+            bool colored = false;         // (COLOR) the object's reflectance or albedo is multiplied by its interpolated corner colours
+            float bu = 0.0f, bv = 0.0f;   // (COLOR) u, v of the winning triangle, formed once for the colour and the smooth normal
             if constexpr (LIGHT) {   // the table lookup moves ahead of the max_depth test: a light's emission is added as the envmap's escape term is
-                const LightLookup f = light_lookup(ot, __float_as_int(q.tris[3 * k].w));
+                const LightLookup f = light_lookup<COLOR ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED : MATPBR_PATH_OBJECT_SMOOTH>(
+                    ot, __float_as_int(q.tris[3 * k].w));
                 kind = f.kind;
                 op[0] = f.p0; op[1] = f.p1; op[2] = f.p2;
                 oa[0] = f.a0; oa[1] = f.a1; oa[2] = f.a2;
@@ -141,6 +147,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 smooth = (kind & MATPBR_PATH_OBJECT_SMOOTH) != 0;
                 kind &= ~MATPBR_PATH_OBJECT_SMOOTH;
             }
+            if constexpr (COLOR) {
+                colored = (kind & MATPBR_PATH_OBJECT_COLORED) != 0;
+                kind &= ~MATPBR_PATH_OBJECT_COLORED;
+            }
             // a hit on the back of a triangle ends the path (glass shades from both sides)
             const bool rough = ROUGH && kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC;   // (ROUGH) shades from both sides, like glass
             if (!(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !rough && !(dot3(n, wo) > 0.0f)) break;
@@ -158,6 +168,25 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             if constexpr (PBR) {
                 if (pbr) { av[0] = oa[0]; av[1] = oa[1]; av[2] = oa[2]; rv = o_r; mv = o_m; }
             }
+            if constexpr (COLOR) {
+                if (smooth || colored) {
+                    const float4 A = q.tris[3 * k];
+                    const float v0[3] = {A.x, A.y, A.z};
+                    tri_uv(v0, e1, e2, o, d, bu, bv);
+                }
+                if (colored) {   // its nine corner colours, consumed at once
+                    const float* cp = ot.col + 9 * (long)(__float_as_int(q.tris[3 * k].w) - ot.n_scene_tri);
+                    float cc[9], cv[3];
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) cc[c] = cp[c];
+                    object_color(cc, bu, bv, cv);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        av[c] *= cv[c];
+                        op[c] *= cv[c];
+                    }
+                }
+            }
             float ns[3] = {n[0], n[1], n[2]};   // (NRM) the shading normal: every cosine, both samplers' frames, the pdf
             if constexpr (NRM) {
 #pragma unroll
@@ -168,11 +197,12 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                     const float4 A = q.tris[3 * k];
                     const float v0[3] = {A.x, A.y, A.z};
                     const float* cp = ot.nrm + 9 * (long)(__float_as_int(A.w) - ot.n_scene_tri);
-                    float cn[9], bu, bv;
+                    float cn[9], su, sv;
 #pragma unroll
                     for (int c = 0; c < 9; ++c) cn[c] = cp[c];
-                    tri_uv(v0, e1, e2, o, d, bu, bv);
-                    smooth_normal(cn, bu, bv, n, ns);
+                    if constexpr (COLOR) { su = bu; sv = bv; }
+                    else tri_uv(v0, e1, e2, o, d, su, sv);
+                    smooth_normal(cn, su, sv, n, ns);
                     smooth_side(n, wo, ns);
                 }
             }
@@ -671,7 +701,7 @@ bool frame_args(const Frame& f, PathArgs& q) {
 }
 
 // the path_kernel instantiation a render launches; it also says which members of `Scene` the launch reads
-enum class Kernel { NoObjects, ObjTable, SmoothObjects, PbrObjects, LightObjects, RoughObjects, TransEdit, ShadeNormals };
+enum class Kernel { NoObjects, ObjTable, SmoothObjects, PbrObjects, LightObjects, RoughObjects, ColorObjects, TransEdit, ShadeNormals };
 // what a render hands its kernel besides the frame, checked
 struct Scene {
     Kernel kernel = Kernel::NoObjects;
@@ -680,6 +710,7 @@ struct Scene {
     int32_t n_scene_tri = 0;
     const MatpbrPathObjectPbr* pbr = nullptr;   // set where some object is of kind 3
     LightTable lt{};                            // empty (n = 0) where no object is a light
+    const float* obj_col = nullptr;             // set where some object is coloured
     TransEdit edit{};
     const float* nrm = nullptr;
 };
@@ -707,14 +738,16 @@ int render_common(const Frame& f, const Scene& s) {
         case Kernel::ShadeNormals: return launch_frame(f, q, ShadeNormals{s.nrm});
         default: break;
     }
-    RoughObjects ro{};   // the three kernels whose tables extend one another
+    ColorObjects ro{};   // the four kernels whose tables extend one another
     ro.t = s.ot;
     ro.nrm = s.obj_nrm;
     ro.n_scene_tri = s.n_scene_tri;
     for (int k = 0; s.pbr && k < s.ot.n; ++k) ro.pbr[k] = s.pbr[k];
     if (s.kernel == Kernel::PbrObjects) return launch_frame<PbrObjects>(f, q, ro);
     ro.lt = s.lt;
-    return s.kernel == Kernel::LightObjects ? launch_frame<LightObjects>(f, q, ro) : launch_frame(f, q, ro);
+    ro.col = s.obj_col;
+    return s.kernel == Kernel::LightObjects ? launch_frame<LightObjects>(f, q, ro) :
+           s.kernel == Kernel::RoughObjects ? launch_frame<RoughObjects>(f, q, ro) : launch_frame(f, q, ro);
 }
 
 // The table of an entry point that knows n_scene_tri, with the rules those entries share: n_scene_tri an int32 >= 0, no range starts
@@ -727,25 +760,28 @@ bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept
     return true;
 }
 
-// The five object entries are the five levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
-// admits kinds 1 and 2, level 2 the smooth flag on them, level 3 kind 3, level 4 kind 4, level 5 kind 5.  An entry passes null / 0 for
+// The six object entries are the six levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
+// admits kinds 1 and 2, level 2 the smooth flag on them, level 3 kind 3, level 4 kind 4, level 5 kind 5, level 6 the colour flag on
+// kinds 2 and 3 (obj_col is consulted where an object carries it).  An entry passes null / 0 for
 // the arguments it does not have; level 1's n_scene_tri = 0 lies below every range.  An argument is consulted only where the table needs
 // it: obj_nrm where an object is smooth, pbr where one is of kind 3, the light header and buffers where one is of kind 4.  The counts
 // alone choose the kernel.
 int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
-                   const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf) {
+                   const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
+                   const float* obj_col = nullptr) {
     const unsigned accept = (level >= 2 ? kAcceptSmooth : 0u) | (level >= 3 ? kAcceptPbr : 0u) | (level >= 4 ? kAcceptLight : 0u) |
-                            (level >= 5 ? kAcceptRough : 0u);
+                            (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u);
     Scene s;
     ObjCounts n;
-    if (!scene_table(objects, n_objects, accept, obj_nrm, n_scene_tri, pbr, s.ot, n) || (n.pbr > 0 && !pbr) ||
+    if (!scene_table(objects, n_objects, accept, obj_nrm, n_scene_tri, pbr, s.ot, n) || (n.pbr > 0 && !pbr) || (n.color > 0 && !obj_col) ||
         (n.light > 0 && !light_table(lights, &s.ot, light_tris, light_cdf, s.lt)))
         return MATPBR_PATH_ERR_INVALID_ARG;
-    s.kernel = n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
+    s.kernel = n.color > 0 ? Kernel::ColorObjects : n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
                n.smooth > 0 ? Kernel::SmoothObjects : n_objects > 0 ? Kernel::ObjTable : Kernel::NoObjects;
     s.obj_nrm = n.smooth > 0 ? obj_nrm : nullptr;
     s.n_scene_tri = (int32_t)n_scene_tri;
     s.pbr = n.pbr > 0 ? pbr : nullptr;
+    s.obj_col = n.color > 0 ? obj_col : nullptr;
     return render_common(f, s);
 }
 
@@ -764,6 +800,21 @@ bool features_args(const MatpbrPathObject* objects, int n_objects, long n_scene_
     return true;
 }
 
+// the arguments both colour-guide entry points share, checked and packed: the table may hold every kind and both flags
+bool feature_colors_args(const MatpbrPathObject* objects, int n_objects, long n_scene_tri, float fov_x_deg, FeatColorArgs& q, ObjTable& ot) {
+    ObjCounts n;
+    if (!q.nodes || !q.tris || !q.out || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) ||
+        !object_table(objects, n_objects, kAcceptAll | kAcceptColor, nullptr, ot, &n) || n_scene_tri < 0 || n_scene_tri > INT32_MAX ||
+        (n.color > 0 && !q.obj_col))
+        return false;
+    for (int k = 0; k < n_objects; ++k)
+        if (objects[k].first_tri < n_scene_tri) return false;
+    q.n_scene_tri = (int32_t)n_scene_tri;
+    const Camera c = camera(q.H, q.W, fov_x_deg);   // the render's
+    q.f_pix = c.f_pix; q.cx = c.cx; q.cy = c.cy;
+    return true;
+}
+
 // the Frame of a render entry point, from the names every one of them gives its first 21 parameters
 #define RENDER_FRAME Frame{nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}
 
@@ -777,7 +828,7 @@ const char* matpbr_path_strerror(int code) {
     switch (code) {
         case MATPBR_PATH_OK: return "ok";
         case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, max_depth outside 1..16, "
-                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, a bad object table, a smooth object without corner normals or a bad transparency edit)";
+                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, a bad object table, a smooth object without corner normals, a coloured object without corner colours or a bad transparency edit)";
         case MATPBR_PATH_ERR_LAUNCH: return "HIP kernel launch failed";
         case MATPBR_PATH_ERR_CAPACITY: return "node buffer smaller than matpbr_path_bvh_size() asks for";
         default: return "unknown error";
@@ -1063,6 +1114,25 @@ int matpbr_path_render_objects_rough(const void* nodes, const void* tris, const 
     return render_objects(RENDER_FRAME, 5, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf);
 }
 
+int matpbr_path_render_objects_colors(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                      float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                      int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                      const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                      const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                      const float* light_cdf, const float* obj_col) {
+    return render_objects(RENDER_FRAME, 6, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col);
+}
+
+int matpbr_path_object_color_host(const float* tri, const float* col, const float* o, const float* d, long N, float* u, float* v, float* c) {
+    if (!tri || !col || !o || !d || !u || !v || !c || N < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        const float *v0 = tri + 9 * k, *e1 = v0 + 3, *e2 = v0 + 6;
+        tri_uv(v0, e1, e2, o + 3 * k, d + 3 * k, u[k], v[k]);
+        object_color(col + 9 * k, u[k], v[k], c + 3 * k);
+    }
+    return MATPBR_PATH_OK;
+}
+
 // the object of the two CPU entry points below: kind 5, with or without the smooth flag (the caller passes both normals either way)
 static bool rough_object(const MatpbrPathObject* ob) {
     return ob && (ob->kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC && rough_valid(ob->p);
@@ -1251,6 +1321,28 @@ int matpbr_path_features_host(const void* nodes, const void* tris, int H, int W,
             features_pixel(q, ot, i, j, stk, g0, g1);
             q.geom[2 * ((long)i * W + j)] = g0;
             q.geom[2 * ((long)i * W + j) + 1] = g1;
+        }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_feature_colors(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                               long n_scene_tri, const float* obj_col, float* out, void* stream) {
+    FeatColorArgs q{static_cast<const float4*>(nodes), static_cast<const float4*>(tris), obj_col, out, H, W};
+    ObjTable ot{};
+    if (!feature_colors_args(objects, n_objects, n_scene_tri, fov_x_deg, q, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(feature_colors_kernel, tile_grid(H, W), dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, ot);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_feature_colors_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects,
+                                    int n_objects, long n_scene_tri, const float* obj_col, float* out) {
+    FeatColorArgs q{static_cast<const float4*>(nodes), static_cast<const float4*>(tris), obj_col, out, H, W};
+    ObjTable ot{};
+    if (!feature_colors_args(objects, n_objects, n_scene_tri, fov_x_deg, q, ot)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j) {
+            HostStack stk;
+            feature_colors_pixel(q, ot, i, j, stk, out + 3 * ((long)i * W + j));
         }
     return MATPBR_PATH_OK;
 }

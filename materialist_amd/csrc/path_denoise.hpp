@@ -113,6 +113,54 @@ __global__ __launch_bounds__(kBlock) void features_kernel(const FeatArgs q, cons
     gp[1] = g1;
 }
 
+// ---- the colour guide ("Vertex-coloured inserted objects") -------------------------------------------------
+struct FeatColorArgs {
+    const float4* nodes;
+    const float4* tris;
+    const float* obj_col;   // nullable: corner colours of the inserted triangles (coloured objects)
+    float* out;             // [H,W,3]
+    int H, W;
+    int32_t n_scene_tri;
+    float f_pix, cx, cy;
+};
+// features_pixel's ray and traversal: c = the interpolated colour where the first hit lies on a coloured object, (1, 1, 1) elsewhere
+template <class Stack>
+__host__ __device__ inline void feature_colors_pixel(const FeatColorArgs& q, const ObjTable& ot, int i, int j, Stack& stk, float c[3]) {
+    const float o[3] = {0.0f, 0.0f, 0.0f};
+    float d[3] = {((float)j - q.cx) / q.f_pix, -((float)i - q.cy) / q.f_pix, -1.0f};
+    {
+        const float il = 1.0f / sqrtf(dot3s(d, d));
+        for (int k = 0; k < 3; ++k) d[k] *= il;
+    }
+    c[0] = c[1] = c[2] = 1.0f;
+    float t = FLT_MAX;
+    const int k = trace_strict(q.nodes, q.tris, o, d, 0.0f, t, stk);
+    if (k < 0) return;
+    const float4 A = q.tris[3 * k], B = q.tris[3 * k + 1], C = q.tris[3 * k + 2];
+    int32_t id;
+    __builtin_memcpy(&id, &A.w, 4);
+    const int obj = object_index(ot, id);
+    if (obj < 0 || !(ot.o[obj].kind & MATPBR_PATH_OBJECT_COLORED)) return;
+    const float v0[3] = {A.x, A.y, A.z}, e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+    const float* cp = q.obj_col + 9 * (long)(id - q.n_scene_tri);
+    float cc[9], bu, bv;
+    for (int n = 0; n < 9; ++n) cc[n] = cp[n];
+    tri_uv_strict(v0, e1, e2, o, d, bu, bv);
+    object_color(cc, bu, bv, c);
+}
+
+__global__ __launch_bounds__(kBlock) void feature_colors_kernel(const FeatColorArgs q, const ObjTable ot) {
+    __shared__ int s_stack[kStack * kBlock];
+    const int tid = threadIdx.y * kTileX + threadIdx.x;
+    const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
+    if (i >= q.H || j >= q.W) return;   // no barriers below: each lane's stack column is its own
+    LdsStack stk{s_stack + tid};
+    float c[3];
+    feature_colors_pixel(q, ot, i, j, stk, c);
+    float* op = q.out + 3 * ((long)i * q.W + j);
+    op[0] = c[0]; op[1] = c[1]; op[2] = c[2];
+}
+
 // prepare: cv0 = ((A + B) / 2, v0), v0 the 3 x 3 binomial average of (lum(A) - lum(B))^2 / 4 over the taps inside the image that
 // carry the pixel's id, normalised by the weights used
 __host__ __device__ inline float4 dn_prepare_pixel(const float* __restrict__ A, const float* __restrict__ B, const float4* __restrict__ geom, int H,

@@ -26,6 +26,10 @@ struct LightObjects : PbrObjects {
 };
 // the table of a scene with a rough dielectric object (kind 5): the light table may be empty then (lt.n = 0)
 struct RoughObjects : LightObjects {};
+// the table of a scene with a vertex-coloured object ("Vertex-coloured inserted objects"): the superset table
+struct ColorObjects : RoughObjects {
+    const float* col;   // [n_tri - n_scene_tri, 3, 3]: one linear RGB triple per corner of every inserted triangle
+};
 
 // emitter `idx` of n_e by sample reuse: idx = min(int(u n_e), n_e - 1), u' = u n_e - idx kept below 1
 __host__ __device__ inline int emitter_choose(float u, int n_e, float& u_re) {
@@ -89,12 +93,14 @@ struct LightLookup {
     int kind;
     float p0, p1, p2, a0, a1, a2, r, m, area;
 };
+// FLAGS: the bits a kind may carry beside its BSDF (the colour table's kinds carry MATPBR_PATH_OBJECT_COLORED as well)
+template <int FLAGS = MATPBR_PATH_OBJECT_SMOOTH>
 __host__ __device__ inline LightLookup light_lookup(const LightObjects& lo, int id) {
     LightLookup f{0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     object_match(lo.t, id, [&](int k, const MatpbrPathObject& ob) {
         f.kind = ob.kind;
         f.p0 = ob.p[0]; f.p1 = ob.p[1]; f.p2 = ob.p[2];
-        if ((ob.kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_PBR) {
+        if ((ob.kind & ~FLAGS) == MATPBR_PATH_BSDF_PBR) {
             f.a0 = lo.pbr[k].a[0]; f.a1 = lo.pbr[k].a[1]; f.a2 = lo.pbr[k].a[2];
             f.r = lo.pbr[k].r;
             f.m = lo.pbr[k].m;

@@ -188,6 +188,25 @@ __host__ __device__ inline void smooth_side(const float ng[3], const float wo[3]
     if (!(dot3h(ns, wo) * dot3h(ng, wo) > 0.0f))
         for (int c = 0; c < 3; ++c) ns[c] = ng[c];
 }
+// ---- vertex-coloured inserted objects ("Vertex-coloured inserted objects") -------------------------------------
+// c = clamp(c0 + u (c1 - c0) + v (c2 - c0), 0, 1) per channel for the corner colours cc = (c0, c1, c2) and tri_uv's u, v.  Differences
+// and explicit fmaf, so that three equal corners give exactly their colour and the CPU and the device give the same bits for the same
+// u, v; the clamp takes the rounding of u, v at an edge (and a u, v that is not a number, which gives 0).
+__host__ __device__ inline void object_color(const float cc[9], float u, float v, float c[3]) {
+    for (int k = 0; k < 3; ++k) c[k] = fminf(fmaxf(fmaf(v, cc[6 + k] - cc[k], fmaf(u, cc[3 + k] - cc[k], cc[k])), 0.0f), 1.0f);
+}
+// tri_uv without contraction (tri_test_strict's operations): the colour guide's, the same bits on the device and on the CPU
+__host__ __device__ inline void tri_uv_strict(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d[3], float& u,
+                                              float& v) {
+#pragma clang fp contract(off)
+    float pv[3], qv[3];
+    cross3s(d, e2, pv);
+    const float idet = 1.0f / dot3s(e1, pv);
+    const float tv[3] = {o[0] - v0[0], o[1] - v0[1], o[2] - v0[2]};
+    u = dot3s(tv, pv) * idet;
+    cross3s(tv, e1, qv);
+    v = dot3s(d, qv) * idet;
+}
 // object_sample at a vertex with the face normal ng and the shading normal ns (the third fallback applied here too: it is
 // idempotent).  dielectric: the event about ns must agree with the geometry, a reflected wi on wo's side of ng and a transmitted
 // one on the other; if it does not, the event is redone about ng with the same dim 6, so that "transmitted" always means "crossed
@@ -443,11 +462,12 @@ bool rough_valid(const float p[3]) {
 // What a table may hold besides the plain kinds 1 and 2, as object_table's accept mask: kAcceptSmooth a kind that carries
 // MATPBR_PATH_OBJECT_SMOOTH; kAcceptPbr kind MATPBR_PATH_BSDF_PBR (its p[] is ignored; its record is checked where `pbr` is given);
 // kAcceptLight kind MATPBR_PATH_BSDF_AREA (never with the smooth flag; p = radiance, finite and >= 0); kAcceptRough kind
-// MATPBR_PATH_BSDF_ROUGH_DIELECTRIC (rough_valid).  A kind outside the mask is an unknown kind.
-enum : unsigned { kAcceptSmooth = 1u, kAcceptPbr = 2u, kAcceptLight = 4u, kAcceptRough = 8u, kAcceptAll = 15u };
-// how many objects of a checked table are smooth, of kind 3, of kind 4, of kind 5
+// MATPBR_PATH_BSDF_ROUGH_DIELECTRIC (rough_valid); kAcceptColor a kind 2 or 3 that carries MATPBR_PATH_OBJECT_COLORED (on another kind
+// the flag is refused).  A kind outside the mask is an unknown kind.  kAcceptAll is what the entries before the colour flag admit.
+enum : unsigned { kAcceptSmooth = 1u, kAcceptPbr = 2u, kAcceptLight = 4u, kAcceptRough = 8u, kAcceptAll = 15u, kAcceptColor = 16u };
+// how many objects of a checked table are smooth, of kind 3, of kind 4, of kind 5, coloured
 struct ObjCounts {
-    int smooth = 0, pbr = 0, light = 0, rough = 0;
+    int smooth = 0, pbr = 0, light = 0, rough = 0, color = 0;
 };
 bool object_table(const MatpbrPathObject* objects, int n_objects, unsigned accept, const MatpbrPathObjectPbr* pbr, ObjTable& ot,
                   ObjCounts* counts = nullptr) {
@@ -458,6 +478,12 @@ bool object_table(const MatpbrPathObject* objects, int n_objects, unsigned accep
     for (int k = 0; k < n_objects; ++k) {
         MatpbrPathObject plain = objects[k];
         bool range_alone = false;   // kinds 3, 4, 5 are checked as a diffuse object of reflectance 0: the range alone
+        if ((accept & kAcceptColor) && (plain.kind & MATPBR_PATH_OBJECT_COLORED)) {
+            const int base = plain.kind & ~(MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_SMOOTH);
+            if (base != MATPBR_PATH_BSDF_DIFFUSE && base != MATPBR_PATH_BSDF_PBR) return false;
+            plain.kind &= ~MATPBR_PATH_OBJECT_COLORED;
+            ++c.color;
+        }
         if ((accept & kAcceptLight) && plain.kind == MATPBR_PATH_BSDF_AREA) {
             for (int j = 0; j < 3; ++j)
                 if (!(plain.p[j] >= 0.0f) || !std::isfinite(plain.p[j])) return false;

@@ -95,13 +95,15 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply_any(path: str, normals: bool = False):
+def read_ply_any(path: str, normals: bool = False, colors: bool = False):
     """A PLY somebody else wrote (an inserted object, `oi.ply`) -> (vertices [Nv,3] float64, triangles [Nt,3] int32).  ASCII or
-    binary little-endian; x, y, z of any scalar type, other vertex properties (colours, uv) skipped; faces as one
+    binary little-endian; x, y, z of any scalar type, other vertex properties (uv, ...) skipped; faces as one
     `list uchar|uint8|int ... vertex_indices` of 3 or more vertices, fan-triangulated; elements after the faces are not read.
     Vertex normals are returned on request: `normals=True` gives (vertices, triangles, N) with N [Nv,3] float64 the file's nx, ny, nz
-    as written, or None when the vertex element has none (smooth inserted objects).  Anything else is a
-    ValueError naming the file."""
+    as written, or None when the vertex element has none (smooth inserted objects).  Vertex colours likewise:
+    with `colors=True` one more value follows, C [Nv,3] float64 from the properties `red green blue` (or `r g b`), an integer type
+    divided by its type's maximum, a float type as written, or None when the vertex element has none (vertex-coloured inserted
+    objects).  Anything else is a ValueError naming the file."""
     def bad(why):
         return ValueError(f"{path}: {why}")
 
@@ -128,7 +130,7 @@ def read_ply_any(path: str, normals: bool = False):
                 break
         if fmt not in ("ascii", "binary_little_endian"):
             raise bad(f"format {fmt!r} is not supported (ascii and binary_little_endian are)")
-        V = T = Nn = None
+        V = T = Nn = Cc = None
         for name, count, props in elements:
             for pr in props:
                 if any(t not in _PLY_TYPES for t in pr[1:]):
@@ -137,6 +139,11 @@ def read_ply_any(path: str, normals: bool = False):
                 if any(len(pr) != 2 for pr in props) or any(c not in [pr[0] for pr in props] for c in "xyz"):
                     raise bad("the vertex element needs scalar properties x, y and z")
                 names = [pr[0] for pr in props]
+                rgb = next((c for c in (("red", "green", "blue"), ("r", "g", "b")) if all(x in names for x in c)), None)
+
+                def scale(c):   # an integer colour's divisor: its type's maximum
+                    dt = np.dtype(_PLY_TYPES[props[names.index(c)][1]])
+                    return float(np.iinfo(dt).max) if dt.kind in "iu" else 1.0
                 if fmt == "ascii":
                     rows = np.array([fh.readline().split() for _ in range(count)], dtype=np.float64).reshape(count, -1)
                     if rows.shape[1] < len(props):
@@ -144,6 +151,8 @@ def read_ply_any(path: str, normals: bool = False):
                     V = np.stack([rows[:, names.index(c)] for c in "xyz"], -1)
                     if all(c in names for c in ("nx", "ny", "nz")):
                         Nn = np.stack([rows[:, names.index(c)] for c in ("nx", "ny", "nz")], -1)
+                    if rgb is not None:
+                        Cc = np.stack([rows[:, names.index(c)] / scale(c) for c in rgb], -1)
                 else:
                     dt = np.dtype([(n, "<" + _PLY_TYPES[t]) for n, t in props])
                     buf = fh.read(count * dt.itemsize)
@@ -153,6 +162,8 @@ def read_ply_any(path: str, normals: bool = False):
                     V = np.stack([rec[c].astype(np.float64) for c in "xyz"], -1)
                     if all(c in names for c in ("nx", "ny", "nz")):
                         Nn = np.stack([rec[c].astype(np.float64) for c in ("nx", "ny", "nz")], -1)
+                    if rgb is not None:
+                        Cc = np.stack([rec[c].astype(np.float64) / scale(c) for c in rgb], -1)
             elif name == "face":
                 if len(props) != 1 or len(props[0]) != 3:
                     raise bad("the face element must be one list property")
@@ -180,7 +191,7 @@ def read_ply_any(path: str, normals: bool = False):
         raise bad("needs a vertex and a face element")
     if T.size and (T.min() < 0 or T.max() >= V.shape[0]):
         raise bad("a face index is outside the vertex array")
-    return (V, T.astype(np.int32), Nn) if normals else (V, T.astype(np.int32))
+    return (V, T.astype(np.int32)) + ((Nn,) if normals else ()) + ((Cc,) if colors else ())
 
 
 def angle_weighted_normals(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:

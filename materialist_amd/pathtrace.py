@@ -37,6 +37,7 @@ BSDF_ROUGH_DIELECTRIC = 5      # MATPBR_PATH_BSDF_ROUGH_DIELECTRIC: rough glass,
 ROUGH_MIN_ALPHA = 0.02         # the GGX width's floor: the peak of D is 1 / (pi alpha^2)
 ROUGH_MIN_CONTRAST = 0.01      # |int_ior / ext_ior - 1| at least this: at a ratio of 1 the refraction Jacobian has no finite value
 OBJECT_SMOOTH = 0x100          # MATPBR_PATH_OBJECT_SMOOTH, OR-ed into PathObject.kind
+OBJECT_COLORED = 0x200         # MATPBR_PATH_OBJECT_COLORED, OR-ed into the kind of a diffuse or pbr object ("Vertex-coloured inserted objects")
 
 
 class PathObject(ctypes.Structure):
@@ -95,6 +96,10 @@ SIGNATURES = {
     "matpbr_path_rough_sample_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
     "matpbr_path_rough_eval_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 2),
     "matpbr_path_object_sample_shading_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
+    "matpbr_path_render_objects_colors": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P]),
+    "matpbr_path_object_color_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
+    "matpbr_path_feature_colors": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P]),
+    "matpbr_path_feature_colors_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P]),
     "matpbr_path_render_trans": (ctypes.c_int, _RENDER + [_P, _P, _P]),
     "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
     "matpbr_path_trans_lookup_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
@@ -126,14 +131,17 @@ PBR_SYMBOLS = ("matpbr_path_render_objects_pbr", "matpbr_path_object_lookup_host
 LIGHT_SYMBOLS = ("matpbr_path_light_tables", "matpbr_path_render_objects_lights", "matpbr_path_light_sample_host", "matpbr_path_light_pdf_host")
 # and (rough dielectric inserted objects)
 ROUGH_SYMBOLS = ("matpbr_path_render_objects_rough", "matpbr_path_rough_sample_host", "matpbr_path_rough_eval_host")
-LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS
+# and (vertex-coloured inserted objects)
+COLOR_SYMBOLS = ("matpbr_path_render_objects_colors", "matpbr_path_object_color_host", "matpbr_path_feature_colors", "matpbr_path_feature_colors_host")
+LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS
 # the feature each of them came with, as `symbol` names it
 _FEATURE = {name: what for names, what in ((SMOOTH_SYMBOLS, "smooth inserted objects"), (DENOISE_SYMBOLS, "the denoiser"),
                                            (PBR_SYMBOLS, "PBR inserted objects"), (LIGHT_SYMBOLS, "emissive inserted objects"),
-                                           (ROUGH_SYMBOLS, "rough dielectric inserted objects")) for name in names}
+                                           (ROUGH_SYMBOLS, "rough dielectric inserted objects"),
+                                           (COLOR_SYMBOLS, "vertex-coloured inserted objects")) for name in names}
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
-                  "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8}
+                  "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9}
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -203,6 +211,14 @@ def _table_ptrs(table, records=None) -> tuple:
     if records is not None and len(records) and len(records) != len(table):
         raise ValueError(f"one record per object: {len(table)} objects, {len(records)} records")
     return ptr(PathObject, table), ptr(PathObjectPbr, records)
+
+
+def _uncolored(table):
+    """`table` as the entry points from before the colour flag take it (the features, the light tables: they need the kind and the smooth
+    flag only): the same table where no object carries OBJECT_COLORED, else copies without it."""
+    if table is None or not any(t.kind & OBJECT_COLORED for t in table):
+        return table
+    return [PathObject(t.kind & ~OBJECT_COLORED, t.first_tri, t.n_tri, t.p) for t in table]
 
 
 def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional[int] = None) -> Dict[str, object]:
@@ -349,6 +365,7 @@ def light_tables(V: np.ndarray, T: np.ndarray, table: Sequence[PathObject], reco
     BSDF_AREA.  PathError where the library refuses the table (a light of total area 0 among the reasons)."""
     if not any(t.kind & ~OBJECT_SMOOTH == BSDF_AREA for t in table):
         return None
+    table = _uncolored(table)
     Vv = np.ascontiguousarray(V, dtype=np.float64).reshape(-1, 3)
     Tt = np.ascontiguousarray(T, dtype=np.int32).reshape(-1, 3)
     tab, rec = _table_ptrs(table, records)
@@ -400,8 +417,22 @@ def light_pdf_host(lights: dict, have_env: bool, light: np.ndarray, record: np.n
     return t, pdf
 
 
+def _corner_colors(k: int, ob: dict, kind: int, Vo: np.ndarray, To: np.ndarray) -> np.ndarray:
+    """Object k's "colors" [Nv,3] (linear RGB, finite, in [0, 1]) expanded to one record per triangle corner [Nt,3,3]; ValueError when bad."""
+    if kind not in (BSDF_DIFFUSE, BSDF_PBR):
+        raise ValueError(f"object {k}: vertex colours tint a 'diffuse' or a 'pbr' object; a {ob['bsdf'].get('type')!r} object takes none (drop 'colors')")
+    Co = np.asarray(ob["colors"], dtype=np.float64)
+    if Co.shape != Vo.shape:
+        raise ValueError(f"object {k}: colors must be [Nv,3] = {Vo.shape}, one per vertex, got {Co.shape}")
+    bad = ~(np.isfinite(Co) & (Co >= 0) & (Co <= 1)).all(-1)
+    if bad.any():
+        v = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"object {k}: the colour of vertex {v} must be finite and lie in [0, 1], got {Co[v].tolist()}")
+    return Co[To]
+
+
 def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False, pbr: bool = False,
-                  lights: bool = False):
+                  lights: bool = False, colors: bool = False):
     """The depth mesh with the inserted meshes appended -> (V [Nv,3] float64, T [Nt,3] int32, [PathObject]).  Object k's triangles
     follow the scene's in the order given; its ids are its range of T.  An object may carry "normals" [Nv,3] (per vertex, outward, any
     length): it is smooth ("Smooth inserted objects"), its kind carries OBJECT_SMOOTH, and with `normals=True`
@@ -410,13 +441,17 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
     one more value follows, the [n_objects] PathObjectPbr records (zero for the objects of another kind, which the kernel never
     reads); a table entry of kind BSDF_PBR has p = 0.  With `lights=True` one more value follows, `light_tables` of the merged mesh
     (None when no object is an area light).  An area light ({"type": "area"}) has kind BSDF_AREA and p = its radiance; with "normals"
-    it is refused."""
+    it is refused.  A diffuse or pbr object may carry "colors" [Nv,3] (per vertex, linear RGB, finite, in [0, 1]; DESIGN.md section 1.4,
+    "Vertex-coloured inserted objects"): its kind carries OBJECT_COLORED, and with `colors=True` one more value follows, last, the
+    corner colours [Nt - scene's Nt, 3, 3] float32 of every inserted triangle (zero for the objects without colours, which the kernel
+    never reads), or None when no object has "colors".  On a dielectric, area or roughdielectric object "colors" is refused."""
     V = [np.asarray(vertices, dtype=np.float64).reshape(-1, 3)]
     T = [np.asarray(triangles, dtype=np.int32).reshape(-1, 3)]
     if len(objects) > MAX_OBJECTS:
         raise ValueError(f"at most {MAX_OBJECTS} inserted objects, got {len(objects)}")
     table: List[PathObject] = []
     corner: List[np.ndarray] = []
+    tint: List[np.ndarray] = []
     records: List[PathObjectPbr] = []
     nv, nt = V[0].shape[0], T[0].shape[0]
     for k, ob in enumerate(objects):
@@ -439,6 +474,11 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
             kind |= OBJECT_SMOOTH
         else:
             corner.append(np.zeros((To.shape[0], 3, 3)))
+        if ob.get("colors") is not None:
+            tint.append(_corner_colors(k, ob, kind & ~OBJECT_SMOOTH, Vo, To))
+            kind |= OBJECT_COLORED
+        else:
+            tint.append(np.zeros((To.shape[0], 3, 3)))
         V.append(Vo)
         T.append((To.astype(np.int64) + nv).astype(np.int32))
         table.append(PathObject(kind, nt, To.shape[0], (ctypes.c_float * 3)(*p)))
@@ -448,7 +488,10 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
         smooth = any(t.kind & OBJECT_SMOOTH for t in table)
         out += (np.ascontiguousarray(np.concatenate(corner), dtype=np.float32) if smooth else None,)
     out += (records,) if pbr else ()
-    return out + ((light_tables(out[0], out[1], table, records),) if lights else ())
+    out += (light_tables(out[0], out[1], table, records),) if lights else ()
+    if colors:
+        out += (np.ascontiguousarray(np.concatenate(tint), dtype=np.float32) if any(t.kind & OBJECT_COLORED for t in table) else None,)
+    return out
 
 
 def object_lookup_host(table: Sequence[PathObject], records: Optional[Sequence[PathObjectPbr]], ids: np.ndarray):
@@ -500,6 +543,19 @@ def object_normal_host(tri: np.ndarray, nrm: np.ndarray, o: np.ndarray, d: np.nd
     check(symbol("matpbr_path_object_normal_host")(_ptr(TR), _ptr(NR), _ptr(O), _ptr(D), N, _ptr(u), _ptr(v), _ptr(ns)),
           "matpbr_path_object_normal_host")
     return u, v, ns
+
+
+def object_color_host(tri: np.ndarray, col: np.ndarray, o: np.ndarray, d: np.ndarray):
+    """The kernel's colour of a vertex-coloured object on the CPU: triangle records tri [N,3,3] = (v0, e1, e2), corner colours col
+    [N,3,3], rays o, d [N,3] -> (u [N], v [N], c [N,3] = clamp(c0 + u (c1 - c0) + v (c2 - c0), 0, 1))."""
+    TR = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1, 3, 3)
+    CL = np.ascontiguousarray(col, dtype=np.float32).reshape(-1, 3, 3)
+    O, D = _rows(o, 3), _rows(d, 3)
+    N = _same_rows("tri, col, o and d must have the same rows", TR, CL, O, D)
+    u, v, c = np.empty(N, np.float32), np.empty(N, np.float32), np.empty((N, 3), np.float32)
+    check(symbol("matpbr_path_object_color_host")(_ptr(TR), _ptr(CL), _ptr(O), _ptr(D), N, _ptr(u), _ptr(v), _ptr(c)),
+          "matpbr_path_object_color_host")
+    return u, v, c
 
 
 def object_sample_shading_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: np.ndarray, u: np.ndarray):
@@ -643,7 +699,7 @@ def features_host(bvh: Dict[str, object], H: int, W: int, fov_x_deg: float = 35.
     H, W = int(H), int(W)
     if H < 1 or W < 1:
         raise ValueError(f"H and W must be positive, got {H} x {W}")
-    table, _ = _table_ptrs(objects)
+    table, _ = _table_ptrs(_uncolored(objects))
     cn = None if obj_nrm is None else np.array(obj_nrm, dtype=np.float32, order="C", copy=True)
     nm = None if normal is None else _host_image(normal, (H, W, 3), "normal")
     geom = np.empty((H, W, 8), np.float32)
@@ -651,6 +707,23 @@ def features_host(bvh: Dict[str, object], H: int, W: int, fov_x_deg: float = 35.
                                               _ptr(cn) if cn is not None else None, int(n_scene_tri), _ptr(nm) if nm is not None else None,
                                               _ptr(geom)), "matpbr_path_features_host")
     return geom
+
+
+def feature_colors_host(bvh: Dict[str, object], H: int, W: int, fov_x_deg: float = 35.0, objects: Optional[Sequence[PathObject]] = None,
+                        obj_col: Optional[np.ndarray] = None, n_scene_tri: int = 0) -> np.ndarray:
+    """`PathTracer.feature_colors` on the CPU with the routine the kernel runs -> [H,W,3]: the interpolated colour where the camera
+    ray through the pixel centre first hits a vertex-coloured object, (1, 1, 1) elsewhere.  `objects`, `obj_col`, `n_scene_tri`:
+    `merge_objects`' table, its corner colours and the depth mesh's triangle count."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"H and W must be positive, got {H} x {W}")
+    table, _ = _table_ptrs(objects)
+    cc = None if obj_col is None else np.array(obj_col, dtype=np.float32, order="C", copy=True)
+    out = np.empty((H, W, 3), np.float32)
+    check(symbol("matpbr_path_feature_colors_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), H, W, float(fov_x_deg), table,
+                                                    len(objects) if objects else 0, int(n_scene_tri), _ptr(cc) if cc is not None else None,
+                                                    _ptr(out)), "matpbr_path_feature_colors_host")
+    return out
 
 
 def denoise_prepare_host(A: np.ndarray, B: np.ndarray, geom: np.ndarray) -> np.ndarray:
@@ -751,7 +824,9 @@ class PathTracer:
     vertex (`stats["n_lights"]` counts them; an envmap of zero luminance leaves the lights as the only emitters).  An object with
     {"type": "roughdielectric", "int_ior": 1.49, "ext_ior": 1.000277, "alpha": 0.1} is rough (frosted) glass (DESIGN.md section 1.4,
     "Rough dielectric objects"; `stats["n_rough_objects"]` counts them): it shades from both sides, takes "normals", and, unlike
-    clear glass, takes an emitter sample at every vertex.  A tracer with objects renders forward only."""
+    clear glass, takes an emitter sample at every vertex.  A diffuse or pbr object may carry "colors" [Nv,3] (per vertex, linear RGB in
+    [0, 1]; DESIGN.md section 1.4, "Vertex-coloured inserted objects"; `stats["n_colored_objects"]` counts them): its reflectance or
+    albedo is multiplied by the colour interpolated at each hit.  A tracer with objects renders forward only."""
 
     def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
                  objects: Optional[Sequence[dict]] = None):
@@ -764,21 +839,28 @@ class PathTracer:
         self.pbr = None                               # the PathObjectPbr records, when some object is of kind BSDF_PBR
         self.lights = None                            # (PathLights, tris, cdf on the device), when some object is of kind BSDF_AREA
         self.rough = False                            # some object is of kind BSDF_ROUGH_DIELECTRIC: `render` takes the rough entry point
-        n_smooth = n_pbr = n_lights = n_rough = 0
+        self.obj_col: Optional[torch.Tensor] = None   # corner colours of the inserted triangles, when some object is coloured
+        n_smooth = n_pbr = n_lights = n_rough = n_colored = 0
         if objects:
-            vertices, triangles, table, corner, records, lt = merge_objects(vertices, triangles, objects, normals=True, pbr=True, lights=True)
+            vertices, triangles, table, corner, records, lt, tint = merge_objects(vertices, triangles, objects, normals=True, pbr=True,
+                                                                                  lights=True, colors=True)
             self.objects = (PathObject * len(table))(*table)
             n_smooth = sum(1 for t in table if t.kind & OBJECT_SMOOTH)
-            n_pbr = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_PBR)
+            n_pbr = sum(1 for t in table if t.kind & ~(OBJECT_SMOOTH | OBJECT_COLORED) == BSDF_PBR)
             n_rough = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_ROUGH_DIELECTRIC)
-            for have, level in ((lt is not None, "lights"), (n_rough, "rough"), (n_pbr, "pbr"), (corner is not None, "normals")):
+            n_colored = sum(1 for t in table if t.kind & OBJECT_COLORED)
+            for have, level in ((lt is not None, "lights"), (n_rough, "rough"), (n_pbr, "pbr"), (corner is not None, "normals"),
+                                (tint is not None, "colors")):
                 if have:                              # a library built before the feature: PathError now, not at the first render
                     symbol("matpbr_path_render_objects_" + level)
+            if tint is not None:
+                symbol("matpbr_path_feature_colors")
+                self.obj_col = torch.from_numpy(tint).to(self.device)
             if lt is not None:
                 n_lights = int(lt["header"].n_lights)
                 self.lights = (lt["header"], torch.from_numpy(lt["tris"]).to(self.device), torch.from_numpy(lt["cdf"]).to(self.device))
             self.rough = n_rough > 0
-            if n_pbr or lt is not None or n_rough:    # the light and rough entry points take the records beside the table as well
+            if n_pbr or lt is not None or n_rough or n_colored:   # the light, rough and colour entry points take the records beside the table as well
                 self.pbr = (PathObjectPbr * len(records))(*records)
             if corner is not None:
                 self.obj_nrm = torch.from_numpy(corner).to(self.device)
@@ -793,6 +875,7 @@ class PathTracer:
         self.stats["n_pbr_objects"] = n_pbr
         self.stats["n_lights"] = n_lights
         self.stats["n_rough_objects"] = n_rough
+        self.stats["n_colored_objects"] = n_colored
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -839,14 +922,14 @@ class PathTracer:
         return nrm.to(self.device, torch.float32).contiguous()
 
     def object_args(self) -> tuple:
-        """(table, n_objects, obj_nrm, n_scene_tri, records, lights header, light_tris, light_cdf): the object arguments of a forward
+        """(table, n_objects, obj_nrm, n_scene_tri, records, lights header, light_tris, light_cdf, obj_col): the object arguments of a forward
         entry point after `stream`, as the C ABI takes them, None where the tracer has none.  An entry takes the first
         OBJECT_ENTRIES[its name] of them."""
         ptr = lambda t: t.data_ptr() if t is not None else None
         table, records = _table_ptrs(self.objects, self.pbr)
         head, ltris, lcdf = self.lights if self.lights is not None else (None, None, None)
         return (table, len(self.objects) if self.objects is not None else 0, ptr(self.obj_nrm), self.n_scene_tris, records,
-                ctypes.cast(ctypes.byref(head), _P) if head is not None else None, ptr(ltris), ptr(lcdf))
+                ctypes.cast(ctypes.byref(head), _P) if head is not None else None, ptr(ltris), ptr(lcdf), ptr(self.obj_col))
 
     @torch.no_grad()
     def render(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
@@ -870,7 +953,7 @@ class PathTracer:
         elif self.objects is None:
             entry, own = "matpbr_path_render", ()
         else:
-            entry = "matpbr_path_render_objects" + ("_rough" if self.rough else "_lights" if self.lights is not None else
+            entry = "matpbr_path_render_objects" + ("_colors" if self.obj_col is not None else "_rough" if self.rough else "_lights" if self.lights is not None else
                                                     "_pbr" if self.pbr is not None else "_normals" if self.obj_nrm is not None else "")
             own = self.object_args()[:OBJECT_ENTRIES[entry]]
         check(symbol(entry, lib)(*args, *own), entry)
@@ -883,12 +966,23 @@ class PathTracer:
         shading-normal map of `render` (a tracer with objects refuses it); id -1 = no hit, 0 = the depth mesh, 1 + k = object k."""
         nrm = self._normal(normal, "features") if normal is not None else None
         geom = torch.empty(self.H, self.W, 8, device=self.device, dtype=torch.float32)
-        check(symbol("matpbr_path_features")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov, _table_ptrs(self.objects)[0],
+        check(symbol("matpbr_path_features")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov, _table_ptrs(_uncolored(self.objects))[0],
                                              len(self.objects) if self.objects is not None else 0,
                                              self.obj_nrm.data_ptr() if self.obj_nrm is not None else None, self.n_scene_tris,
                                              nrm.data_ptr() if nrm is not None else None, geom.data_ptr(),
                                              torch.cuda.current_stream(self.device).cuda_stream), "matpbr_path_features")
         return geom
+
+    @torch.no_grad()
+    def feature_colors(self) -> torch.Tensor:
+        """[H,W,3] on the device: the interpolated colour where the camera ray through the pixel centre (`features`' ray) first hits a
+        vertex-coloured object, (1, 1, 1) elsewhere: what `relight.albedo_guide` multiplies a coloured object's constant by."""
+        out = torch.empty(self.H, self.W, 3, device=self.device, dtype=torch.float32)
+        check(symbol("matpbr_path_feature_colors")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov, _table_ptrs(self.objects)[0],
+                                                   len(self.objects) if self.objects is not None else 0, self.n_scene_tris,
+                                                   self.obj_col.data_ptr() if self.obj_col is not None else None, out.data_ptr(),
+                                                   torch.cuda.current_stream(self.device).cuda_stream), "matpbr_path_feature_colors")
+        return out
 
     @torch.no_grad()
     def denoise(self, A, B, alb, geom, **params) -> torch.Tensor:

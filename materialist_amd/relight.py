@@ -237,17 +237,21 @@ def _scaled_env(env: np.ndarray, env_scale: float, integrator: str = "path") -> 
 _PBR_ALBEDO = 0.8   # pathtrace.PBR_DEFAULTS["albedo"]: what `object_bsdf` gives a "pbr" dict without one
 
 
-def albedo_guide(geom: torch.Tensor, albedo: torch.Tensor, bsdfs=()) -> torch.Tensor:
+def albedo_guide(geom: torch.Tensor, albedo: torch.Tensor, bsdfs=(), colors: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The denoiser's albedo guide [H,W,3] from the features' ids: the albedo map as rendered where the camera ray hits the depth mesh
     (id 0), a diffuse object's reflectance, a PBR object's albedo, 1 on glass, on rough glass ("roughdielectric": colourless, like
     glass) and on an area light (the fall-through: a light's pixels are its radiance, which the colour term guides alone), 0 where it
-    hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order."""
+    hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order.  `colors` [H,W,3]: `PathTracer.feature_colors()` of a tracer with
+    vertex-coloured objects; a diffuse or pbr object's constant is multiplied by it, so that the guide follows a colour edge inside
+    the object (it is 1 off the coloured objects)."""
     ids = geom[..., 7]
     guide = albedo.to(geom.device, torch.float32).reshape(geom.shape[0], geom.shape[1], 3).clone()
     guide[ids < 0] = 0.0
     for k, b in enumerate(bsdfs):
         value = b["reflectance"] if b["type"] == "diffuse" else b.get("albedo", _PBR_ALBEDO) if b["type"] == "pbr" else (1.0, 1.0, 1.0)
         guide[ids == 1 + k] = torch.tensor([float(x) for x in np.broadcast_to(np.asarray(value, np.float64), (3,))], device=geom.device)
+        if colors is not None and b["type"] in ("diffuse", "pbr"):
+            guide[ids == 1 + k] *= colors.to(geom.device, torch.float32)[ids == 1 + k]
     return guide
 
 
@@ -329,10 +333,13 @@ OI_SCENE_MAX_OBJECTS = 8                              # pathtrace.MAX_OBJECTS
 def load_oi_scene(path: str) -> List[dict]:
     """An object list file for `render_oi(objects_file=...)`: JSON that holds only settings,
     {"objects": [{"ply": "chrome_ball.ply", "bsdf": {"type": "pbr", "albedo": [0.95, 0.93, 0.88], "roughness": 0.1, "metallic": 1.0},
-    "normals": "vertex"}, ...]}, at most 8 objects.  "ply" is relative to the file; "bsdf" is any of PathTracer's five types
+    "normals": "vertex", "colors": "vertex"}, ...]}, at most 8 objects.  "ply" is relative to the file; "bsdf" is any of PathTracer's five types
     (dielectric, diffuse, pbr, roughdielectric: {"type": "roughdielectric", "int_ior", "ext_ior", "alpha"} is frosted glass, area:
     {"type": "area", "radiance": [r, g, b]} is a lamp, which takes "normals": "flat" only); "normals" is "flat" (default) or "vertex" (the file's normals if it has them, else
-    `mesh.angle_weighted_normals`) -> [{"ply": absolute path, "bsdf", "normals"}], nothing read yet but the list.  ValueError naming
+    `mesh.angle_weighted_normals`); "colors" (a diffuse or pbr object only) is "none" (default), "vertex" (the file's `red green blue`,
+    display values, decoded to linear as `loss.srgb_to_linear` decodes) or "vertex_linear" (the file's values as written, what Mitsuba's
+    `mesh_attribute` does; DESIGN.md section 1.4, "Vertex-coloured inserted objects")
+    -> [{"ply": absolute path, "bsdf", "normals", "colors"}], nothing read yet but the list.  ValueError naming
     the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
     import json
 
@@ -357,9 +364,9 @@ def load_oi_scene(path: str) -> List[dict]:
         where = f"{path}: objects[{k}]"
         if not isinstance(ob, dict):
             raise ValueError(f"{where} must be an object with 'ply' and 'bsdf'")
-        extra = sorted(set(ob) - {"ply", "bsdf", "normals"})
+        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors"})
         if extra:
-            raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals')")
+            raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals', 'colors')")
         if not isinstance(ob.get("ply"), str) or not ob["ply"]:
             raise ValueError(f"{where}: 'ply' must name a mesh file")
         ply = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob["ply"]))
@@ -374,13 +381,29 @@ def load_oi_scene(path: str) -> List[dict]:
             raise ValueError(f"{where}: 'normals' must be 'flat' or 'vertex', got {normals!r}")
         if normals == "vertex" and ob["bsdf"].get("type") == "area":
             raise ValueError(f"{where}: 'normals' must be 'flat' for an area light: it emits from its faces")
-        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals})
+        colors = ob.get("colors", "none")
+        if colors not in OI_COLORS:
+            raise ValueError(f"{where}: 'colors' must be 'none', 'vertex' or 'vertex_linear', got {colors!r}")
+        if colors != "none" and ob["bsdf"].get("type") not in ("diffuse", "pbr"):
+            raise ValueError(f"{where}: 'colors' must be 'none' for a {ob['bsdf'].get('type')!r} object: vertex colours tint a 'diffuse' or a 'pbr' one")
+        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals, "colors": colors})
     return out
+
+
+OI_COLORS = ("none", "vertex", "vertex_linear")
+
+
+def _object_colors(path: str, C: Optional[np.ndarray], colors: str) -> np.ndarray:
+    """The vertex colours `mesh.read_ply_any` found in `path`, as linear RGB: "vertex" decodes them as display values, "vertex_linear"
+    takes them as written.  ValueError naming the file when it has none."""
+    if C is None:
+        raise ValueError(f"{path}: colors={colors!r} needs vertex colours ('red green blue' or 'r g b' properties), the file has none")
+    return np.clip(C, 0.0, 1.0) ** 2.2 if colors == "vertex" else C
 
 
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
-              denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0) -> str:
+              denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none") -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -394,29 +417,38 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     list (`load_oi_scene`) whose meshes are inserted instead, each with its own BSDF (dielectric, diffuse, pbr, roughdielectric: frosted glass, or area: a lamp) and
     its own normals; with it oi.ply and oi2.ply are not looked for and `object_normals` is ignored.  The output names are the same.
     `env_scale`: the envmap is multiplied by it before its tables are built (1: the same bits as without it; 0 with an area light in
-    the list: the night shot, lit by the lamp alone)."""
+    the list: the night shot, lit by the lamp alone).  `object_colors`: "none" (default), "vertex" or "vertex_linear" (`load_oi_scene`'s
+    "colors") tints oi2.ply, the diffuse object, with its file's vertex colours; with `objects_file` it is ignored and each entry's
+    "colors" holds.  A file without colours is a ValueError naming it."""
     from . import mesh as _mesh
 
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     if objects_file is not None:
-        have = [(e["ply"], e["bsdf"], e["normals"]) for e in load_oi_scene(objects_file)]
+        have = [(e["ply"], e["bsdf"], e["normals"], e["colors"]) for e in load_oi_scene(objects_file)]
     else:
         plys = [os.path.join(scene_dir, "oi.ply"), os.path.join(scene_dir, "oi2.ply")]
         bsdfs = [{"type": "dielectric", "int_ior": OI_INT_IOR, "ext_ior": OI_EXT_IOR}, {"type": "diffuse", "reflectance": (OI_REFLECTANCE,) * 3}]
-        have = [(p, b, object_normals) for p, b in zip(plys, bsdfs) if os.path.exists(p)]
+        have = [(p, b, object_normals, c) for p, b, c in zip(plys, bsdfs, ("none", object_colors)) if os.path.exists(p)]
         if not have:
             raise FileNotFoundError(f"object insertion needs {plys[0]} (glass) or {plys[1]} (diffuse); neither exists")
     if n_iter < 1:
         raise ValueError(f"n_iter must be at least 1, got {n_iter}")
     if object_normals not in ("flat", "vertex"):
         raise ValueError(f"object_normals must be 'flat' or 'vertex', got {object_normals!r}")
+    if object_colors not in OI_COLORS:
+        raise ValueError(f"object_colors must be 'none', 'vertex' or 'vertex_linear', got {object_colors!r}")
     atrous = _check_denoise(denoise, "path", spp)
     _scaled_env(np.zeros(0, np.float32), env_scale)
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
-    for p, b, normals in have:
-        V, T, Nn = _mesh.read_ply_any(p, normals=True)
+    for p, b, normals, colors in have:
+        if colors == "none":
+            V, T, Nn = _mesh.read_ply_any(p, normals=True)
+        else:
+            V, T, Nn, Cc = _mesh.read_ply_any(p, normals=True, colors=True)
         objects.append({"vertices": V, "triangles": T, "bsdf": b})
+        if colors != "none":
+            objects[-1]["colors"] = _object_colors(p, Cc, colors)
         if normals == "vertex":
             objects[-1]["normals"] = Nn if Nn is not None else _mesh.angle_weighted_normals(V, T)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
@@ -426,7 +458,8 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     if atrous:
         geom = pt.features()
         half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs)
-        img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], [b for _, b, _ in have]))
+        tint = pt.feature_colors() if pt.stats["n_colored_objects"] else None
+        img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], [h[1] for h in have], tint))
     else:
         img = torch.zeros_like(mat["albedo"])
         for i in range(n_iter):
