@@ -63,6 +63,12 @@ enum {
  * Only matpbr_path_render_objects_colors and matpbr_path_feature_colors take it; to every other entry point it is an unknown kind. */
 #define MATPBR_PATH_OBJECT_COLORED 0x200
 
+/* OR-ed into MatpbrPathObject.kind beside the two flags above: the object's reflectance (kind 2) or albedo (kind 3) is multiplied by a
+ * base-colour image, and a kind-3 object's roughness and metallic by an orm image, both looked up at the texture coordinate interpolated
+ * from its corners ("Textured inserted objects").  Valid on kinds 2 and 3 only.  Only
+ * matpbr_path_render_objects_textures and matpbr_path_feature_tints take it; to every other entry point it is an unknown kind. */
+#define MATPBR_PATH_OBJECT_TEXTURED 0x400
+
 /* One inserted mesh: triangles [first_tri, first_tri + n_tri) of the mesh handed to matpbr_path_bvh_build_objects (ids at or
  * above its n_scene_tri), outward winding. */
 typedef struct MatpbrPathObject {
@@ -81,6 +87,15 @@ typedef struct MatpbrPathObjectPbr {
     float m;
     float reserved[3];
 } MatpbrPathObjectPbr;
+
+/* The images of an object that carries MATPBR_PATH_OBJECT_TEXTURED, one record per object beside the table (read for flagged objects
+ * only): image x is texels [x_first, x_first + x_w x_h) of the texel buffer, row-major, row 0 the top row; x_w == 0: no such image.
+ * Valid: at least one image; orm on kind 3 only; w, h in [1, 8192]; first >= 0; first + w h <= n_texels; reserved == 0. */
+typedef struct MatpbrPathObjectTex {
+    int32_t base_first, base_w, base_h; /* base colour: linear r, g, b */
+    int32_t orm_first, orm_w, orm_h;    /* glTF's occlusion (ignored), roughness, metallic */
+    int32_t reserved[2];
+} MatpbrPathObjectTex;
 
 /* Transparency editing ("Transparency editing"): the reference's TransBSDF where the mask is set. */
 typedef struct MatpbrPathTransEdit {
@@ -322,6 +337,46 @@ int matpbr_path_feature_colors(const void* nodes, const void* tris, int H, int W
 /* matpbr_path_feature_colors on the CPU with the routine the kernel runs (every pointer HOST). */
 int matpbr_path_feature_colors_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects,
                                     int n_objects, long n_scene_tri, const float* obj_col, float* out);
+
+/* ---- Textured inserted objects ("Textured inserted objects") ----------------------------------------------------
+ * matpbr_path_render_objects_colors where an object of kind 2 or 3 may carry MATPBR_PATH_OBJECT_TEXTURED (with or without the smooth
+ * and the colour flag), forward only.  obj_uv (DEVICE, fp32, [n_tri - n_scene_tri, 3, 2]): the texture coordinate (s, t) of every corner
+ * of every inserted triangle, in obj_nrm's layout (finite: the caller's responsibility); the triangles of objects without the flag are
+ * never read.  texels (DEVICE, 16-byte aligned, n_texels float4 = linear r, g, b, 0 in [0, 1]): all images one after another.  tex (HOST,
+ * one record per object, copied before the call returns).  At a hit on a flagged object (s, t) = st0 + u (st1 - st0) + v (st2 - st0)
+ * with the smooth normal's u, v; an image is read with bilinear filtering and repeat wrapping, t = 0 its bottom row, texel centres at
+ * half-integers; a coordinate that is not finite reads (0, 0, 0).  The vertex shades with reflectance p * c_vertex * c_base (kind 2) or
+ * albedo a * c_vertex * c_base, roughness clamp(r * orm.g, 0.07, 1) and metallic clamp(m * orm.b, 0, 1) (kind 3); a factor the object
+ * does not carry is 1.  This is level 7 of the table in DESIGN.md section 1.4, "The object entries": without a flagged object it
+ * launches matpbr_path_render_objects_colors' kernel choice and gives its bits (obj_uv, tex, texels may be NULL and n_texels 0 then).
+ * Invalid arguments, besides that entry point's: a flagged object with obj_uv, tex or texels NULL or texels misaligned, a record that
+ * is not valid (MatpbrPathObjectTex), the flag on kind 1, 4 or 5. */
+int matpbr_path_render_objects_textures(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                        float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                        int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                        const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                        const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                        const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                        const void* texels, long n_texels);
+
+/* The texture lookups of a flagged object at a hit on the CPU, with the routines the kernel runs: per lane the triangle record
+ * tri[N,3,3] = (v0, e1, e2), the corner coordinates uv[N,3,2] and the ray o[N,3], d[N,3]; one record `tex` (checked as a kind-3
+ * object's) over the HOST buffer texels[n_texels] -> u[N], v[N], st[N,2], base[N,3], orm[N,3].  An image the record does not have gives
+ * (1, 1, 1).  Four equal texels give exactly their value; every value lies in [0, 1]. */
+int matpbr_path_object_texture_host(const float* tri, const float* uv, const float* o, const float* d, long N, const MatpbrPathObjectTex* tex,
+                                    const void* texels, long n_texels, float* u, float* v, float* st, float* base, float* orm);
+
+/* The tint guide of the denoiser: matpbr_path_feature_colors' ray, traversal and uncontracted barycentrics.  out[H,W,3] (DEVICE) =
+ * c_vertex * c_base where the first hit lies on a coloured or textured object (a factor the object does not carry is 1), (1, 1, 1)
+ * everywhere else.  obj_col, obj_uv, tex, texels, n_texels as matpbr_path_render_objects_textures takes them (the buffers DEVICE, tex
+ * HOST; nullable where no object needs them).  The CPU twin gives the same bits. */
+int matpbr_path_feature_tints(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                              long n_scene_tri, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex, const void* texels,
+                              long n_texels, float* out, void* stream);
+/* matpbr_path_feature_tints on the CPU with the routine the kernel runs (every pointer HOST). */
+int matpbr_path_feature_tints_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects,
+                                   int n_objects, long n_scene_tri, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                   const void* texels, long n_texels, float* out);
 
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;

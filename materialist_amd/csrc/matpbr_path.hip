@@ -10,11 +10,10 @@
 // One translation unit: this file holds PathArgs, the forward kernel, the backward kernels and the C ABI; path_bvh.hpp the BVH, its
 // traversals and the host builder; path_shading.hpp the RNG, the envmap sampler and the BSDF wrappers; path_objects.hpp the tables the
 // kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
-// path_denoise.hpp the denoiser.
+// path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser.
 #include <type_traits>
 
 #include "path_denoise.hpp"
-#include "path_lights.hpp"
 
 namespace {
 
@@ -47,10 +46,14 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 // dielectrics: a non-delta vertex that shades from both sides, whose emitter sample may arrive on either side of the face and whose
 // light table may be empty; every `if (ROUGH ...)` folds away in the other seven.  COLOR: ROUGH with vertex-coloured objects (Objects =
 // ColorObjects): at a vertex of a flagged object of kind 2 or 3 the reflectance or the albedo is multiplied by the colour interpolated
-// from the triangle's corners; every `if (COLOR ...)` folds away in the other eight.
+// from the triangle's corners; every `if (COLOR ...)` folds away in the other eight.  TEX: COLOR with UV-textured objects (Objects =
+// TexObjects): at a vertex of a flagged object the reflectance or the albedo is multiplied by a base-colour image, a PBR object's
+// roughness and metallic by an orm image, at the coordinate interpolated from the triangle's corners; every `if (TEX ...)` folds away in
+// the other nine.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value;
+    constexpr bool TEX = std::is_same<Objects, TexObjects>::value;
+    constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
     constexpr bool LIGHT = std::is_same<Objects, LightObjects>::value || ROUGH;
     constexpr bool PBR = std::is_same<Objects, PbrObjects>::value || LIGHT;
@@ -105,9 +108,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             float op[3] = {0.0f, 0.0f, 0.0f};
             float oa[3] = {0.0f, 0.0f, 0.0f}, o_r = 0.0f, o_m = 0.0f;   // (PBR) the record of an object of kind 3
             bool colored = false;         // (COLOR) the object's reflectance or albedo is multiplied by its interpolated corner colours
-            float bu = 0.0f, bv = 0.0f;   // (COLOR) u, v of the winning triangle, formed once for the colour and the smooth normal
+            bool textured = false;        // (TEX) the object's images are read at its interpolated corner coordinates
+            float bu = 0.0f, bv = 0.0f;   // (COLOR) u, v of the winning triangle, formed once for the texture, the colour and the smooth normal
             if constexpr (LIGHT) {   // the table lookup moves ahead of the max_depth test: a light's emission is added as the envmap's escape term is
-                const LightLookup f = light_lookup<COLOR ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED : MATPBR_PATH_OBJECT_SMOOTH>(
+                const LightLookup f = light_lookup<TEX     ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_TEXTURED :
+                                                   COLOR ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED : MATPBR_PATH_OBJECT_SMOOTH>(
                     ot, __float_as_int(q.tris[3 * k].w));
                 kind = f.kind;
                 op[0] = f.p0; op[1] = f.p1; op[2] = f.p2;
@@ -151,6 +156,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 colored = (kind & MATPBR_PATH_OBJECT_COLORED) != 0;
                 kind &= ~MATPBR_PATH_OBJECT_COLORED;
             }
+            if constexpr (TEX) {
+                textured = (kind & MATPBR_PATH_OBJECT_TEXTURED) != 0;
+                kind &= ~MATPBR_PATH_OBJECT_TEXTURED;
+            }
             // a hit on the back of a triangle ends the path (glass shades from both sides)
             const bool rough = ROUGH && kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC;   // (ROUGH) shades from both sides, like glass
             if (!(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !rough && !(dot3(n, wo) > 0.0f)) break;
@@ -169,7 +178,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 if (pbr) { av[0] = oa[0]; av[1] = oa[1]; av[2] = oa[2]; rv = o_r; mv = o_m; }
             }
             if constexpr (COLOR) {
-                if (smooth || colored) {
+                if (smooth || colored || (TEX && textured)) {
                     const float4 A = q.tris[3 * k];
                     const float v0[3] = {A.x, A.y, A.z};
                     tri_uv(v0, e1, e2, o, d, bu, bv);
@@ -184,6 +193,29 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                     for (int c = 0; c < 3; ++c) {
                         av[c] *= cv[c];
                         op[c] *= cv[c];
+                    }
+                }
+            }
+            if constexpr (TEX) {
+                if (textured) {   // its six corner coordinates, consumed at once; the orm fetch follows the base fetch
+                    const int id = __float_as_int(q.tris[3 * k].w);
+                    const MatpbrPathObjectTex tr = tex_lookup(ot.t, ot.tex, id);
+                    const float* up = ot.uv + 6 * (long)(id - ot.n_scene_tri);
+                    float cs[6], ts, tt, cb[3];
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) cs[c] = up[c];
+                    object_st(cs, bu, bv, ts, tt);
+                    if (tr.base_w > 0) {
+                        texture_fetch(ot.texels + (long)tr.base_first, tr.base_w, tr.base_h, ts, tt, cb);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            av[c] *= cb[c];
+                            op[c] *= cb[c];
+                        }
+                    }
+                    if (tr.orm_w > 0) {   // kind 3 only: the record check refuses it elsewhere
+                        texture_fetch(ot.texels + (long)tr.orm_first, tr.orm_w, tr.orm_h, ts, tt, cb);
+                        orm_apply(cb, rv, mv);
                     }
                 }
             }
@@ -701,7 +733,7 @@ bool frame_args(const Frame& f, PathArgs& q) {
 }
 
 // the path_kernel instantiation a render launches; it also says which members of `Scene` the launch reads
-enum class Kernel { NoObjects, ObjTable, SmoothObjects, PbrObjects, LightObjects, RoughObjects, ColorObjects, TransEdit, ShadeNormals };
+enum class Kernel { NoObjects, ObjTable, SmoothObjects, PbrObjects, LightObjects, RoughObjects, ColorObjects, TexObjects, TransEdit, ShadeNormals };
 // what a render hands its kernel besides the frame, checked
 struct Scene {
     Kernel kernel = Kernel::NoObjects;
@@ -711,6 +743,9 @@ struct Scene {
     const MatpbrPathObjectPbr* pbr = nullptr;   // set where some object is of kind 3
     LightTable lt{};                            // empty (n = 0) where no object is a light
     const float* obj_col = nullptr;             // set where some object is coloured
+    const float* obj_uv = nullptr;              // set where some object is textured, with its records and the texels
+    const MatpbrPathObjectTex* tex = nullptr;
+    const float4* texels = nullptr;
     TransEdit edit{};
     const float* nrm = nullptr;
 };
@@ -738,7 +773,7 @@ int render_common(const Frame& f, const Scene& s) {
         case Kernel::ShadeNormals: return launch_frame(f, q, ShadeNormals{s.nrm});
         default: break;
     }
-    ColorObjects ro{};   // the four kernels whose tables extend one another
+    TexObjects ro{};   // the five kernels whose tables extend one another
     ro.t = s.ot;
     ro.nrm = s.obj_nrm;
     ro.n_scene_tri = s.n_scene_tri;
@@ -746,8 +781,28 @@ int render_common(const Frame& f, const Scene& s) {
     if (s.kernel == Kernel::PbrObjects) return launch_frame<PbrObjects>(f, q, ro);
     ro.lt = s.lt;
     ro.col = s.obj_col;
+    if (s.kernel == Kernel::TexObjects) {   // a record is copied where its object carries the flag: the others stay zero
+        ro.uv = s.obj_uv;
+        ro.texels = s.texels;
+        for (int k = 0; k < s.ot.n; ++k)
+            if (s.ot.o[k].kind & MATPBR_PATH_OBJECT_TEXTURED) ro.tex[k] = s.tex[k];
+        return launch_frame(f, q, ro);
+    }
     return s.kernel == Kernel::LightObjects ? launch_frame<LightObjects>(f, q, ro) :
-           s.kernel == Kernel::RoughObjects ? launch_frame<RoughObjects>(f, q, ro) : launch_frame(f, q, ro);
+           s.kernel == Kernel::RoughObjects ? launch_frame<RoughObjects>(f, q, ro) : launch_frame<ColorObjects>(f, q, ro);
+}
+
+// what a table with a textured object needs besides the flag's place (object_table): the three buffers, texels aligned for float4
+// loads, and a valid record for every flagged object
+bool textures_valid(const MatpbrPathObject* objects, int n_objects, const float* obj_uv, const MatpbrPathObjectTex* tex, const void* texels,
+                    long n_texels) {
+    if (!obj_uv || !tex || !texels || ((uintptr_t)texels & 15) || n_texels < 1) return false;
+    for (int k = 0; k < n_objects; ++k) {
+        if (!(objects[k].kind & MATPBR_PATH_OBJECT_TEXTURED)) continue;
+        const int base = objects[k].kind & ~(MATPBR_PATH_OBJECT_TEXTURED | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_SMOOTH);
+        if (!tex_valid(tex[k], base == MATPBR_PATH_BSDF_PBR, n_texels)) return false;
+    }
+    return true;
 }
 
 // The table of an entry point that knows n_scene_tri, with the rules those entries share: n_scene_tri an int32 >= 0, no range starts
@@ -760,28 +815,36 @@ bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept
     return true;
 }
 
-// The six object entries are the six levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
+// The seven object entries are the seven levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
 // admits kinds 1 and 2, level 2 the smooth flag on them, level 3 kind 3, level 4 kind 4, level 5 kind 5, level 6 the colour flag on
-// kinds 2 and 3 (obj_col is consulted where an object carries it).  An entry passes null / 0 for
+// kinds 2 and 3 (obj_col is consulted where an object carries it), level 7 the texture flag on them (obj_uv, tex and texels are consulted
+// where an object carries it, and its record is checked against n_texels).  An entry passes null / 0 for
 // the arguments it does not have; level 1's n_scene_tri = 0 lies below every range.  An argument is consulted only where the table needs
 // it: obj_nrm where an object is smooth, pbr where one is of kind 3, the light header and buffers where one is of kind 4.  The counts
 // alone choose the kernel.
 int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                    const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
-                   const float* obj_col = nullptr) {
+                   const float* obj_col = nullptr, const float* obj_uv = nullptr, const MatpbrPathObjectTex* tex = nullptr,
+                   const void* texels = nullptr, long n_texels = 0) {
     const unsigned accept = (level >= 2 ? kAcceptSmooth : 0u) | (level >= 3 ? kAcceptPbr : 0u) | (level >= 4 ? kAcceptLight : 0u) |
-                            (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u);
+                            (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u) | (level >= 7 ? kAcceptTexture : 0u);
     Scene s;
     ObjCounts n;
     if (!scene_table(objects, n_objects, accept, obj_nrm, n_scene_tri, pbr, s.ot, n) || (n.pbr > 0 && !pbr) || (n.color > 0 && !obj_col) ||
-        (n.light > 0 && !light_table(lights, &s.ot, light_tris, light_cdf, s.lt)))
+        (n.light > 0 && !light_table(lights, &s.ot, light_tris, light_cdf, s.lt)) ||
+        (n.tex > 0 && !textures_valid(objects, n_objects, obj_uv, tex, texels, n_texels)))
         return MATPBR_PATH_ERR_INVALID_ARG;
-    s.kernel = n.color > 0 ? Kernel::ColorObjects : n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
+    s.kernel = n.tex > 0 ? Kernel::TexObjects : n.color > 0 ? Kernel::ColorObjects : n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
                n.smooth > 0 ? Kernel::SmoothObjects : n_objects > 0 ? Kernel::ObjTable : Kernel::NoObjects;
     s.obj_nrm = n.smooth > 0 ? obj_nrm : nullptr;
     s.n_scene_tri = (int32_t)n_scene_tri;
     s.pbr = n.pbr > 0 ? pbr : nullptr;
     s.obj_col = n.color > 0 ? obj_col : nullptr;
+    if (n.tex > 0) {
+        s.obj_uv = obj_uv;
+        s.tex = tex;
+        s.texels = static_cast<const float4*>(texels);
+    }
     return render_common(f, s);
 }
 
@@ -801,10 +864,12 @@ bool features_args(const MatpbrPathObject* objects, int n_objects, long n_scene_
 }
 
 // the arguments both colour-guide entry points share, checked and packed: the table may hold every kind and both flags
-bool feature_colors_args(const MatpbrPathObject* objects, int n_objects, long n_scene_tri, float fov_x_deg, FeatColorArgs& q, ObjTable& ot) {
+// (`accept`: the tint guide's table may hold the texture flag as well; it returns the number of textured objects in *n_tex)
+bool feature_colors_args(const MatpbrPathObject* objects, int n_objects, long n_scene_tri, float fov_x_deg, FeatColorArgs& q, ObjTable& ot,
+                         unsigned accept = kAcceptAll | kAcceptColor, int* n_tex = nullptr) {
     ObjCounts n;
     if (!q.nodes || !q.tris || !q.out || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) ||
-        !object_table(objects, n_objects, kAcceptAll | kAcceptColor, nullptr, ot, &n) || n_scene_tri < 0 || n_scene_tri > INT32_MAX ||
+        !object_table(objects, n_objects, accept, nullptr, ot, &n) || n_scene_tri < 0 || n_scene_tri > INT32_MAX ||
         (n.color > 0 && !q.obj_col))
         return false;
     for (int k = 0; k < n_objects; ++k)
@@ -812,6 +877,23 @@ bool feature_colors_args(const MatpbrPathObject* objects, int n_objects, long n_
     q.n_scene_tri = (int32_t)n_scene_tri;
     const Camera c = camera(q.H, q.W, fov_x_deg);   // the render's
     q.f_pix = c.f_pix; q.cx = c.cx; q.cy = c.cy;
+    if (n_tex) *n_tex = n.tex;
+    return true;
+}
+// the tint guide's arguments: the colour guide's, and the textures checked and packed where an object carries the flag
+bool feature_tints_args(const MatpbrPathObject* objects, int n_objects, long n_scene_tri, float fov_x_deg, const float* obj_uv,
+                        const MatpbrPathObjectTex* tex, const void* texels, long n_texels, FeatColorArgs& q, ObjTable& ot, FeatTextures& tx) {
+    int n_tex = 0;
+    if (!feature_colors_args(objects, n_objects, n_scene_tri, fov_x_deg, q, ot, kAcceptAll | kAcceptColor | kAcceptTexture, &n_tex) ||
+        (n_tex > 0 && !textures_valid(objects, n_objects, obj_uv, tex, texels, n_texels)))
+        return false;
+    tx = FeatTextures{};
+    if (n_tex > 0) {
+        tx.uv = obj_uv;
+        tx.texels = static_cast<const float4*>(texels);
+        for (int k = 0; k < n_objects; ++k)
+            if (objects[k].kind & MATPBR_PATH_OBJECT_TEXTURED) tx.tex[k] = tex[k];
+    }
     return true;
 }
 
@@ -828,7 +910,7 @@ const char* matpbr_path_strerror(int code) {
     switch (code) {
         case MATPBR_PATH_OK: return "ok";
         case MATPBR_PATH_ERR_INVALID_ARG: return "invalid argument (null pointer, non-positive size, index out of range, max_depth outside 1..16, "
-                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, a bad object table, a smooth object without corner normals, a coloured object without corner colours or a bad transparency edit)";
+                                                  "a workspace too small, an envmap of more than 1024 texels with d_env, a bad object table, a smooth object without corner normals, a coloured object without corner colours, a textured object without coordinates, texels or a valid record, or a bad transparency edit)";
         case MATPBR_PATH_ERR_LAUNCH: return "HIP kernel launch failed";
         case MATPBR_PATH_ERR_CAPACITY: return "node buffer smaller than matpbr_path_bvh_size() asks for";
         default: return "unknown error";
@@ -1133,6 +1215,31 @@ int matpbr_path_object_color_host(const float* tri, const float* col, const floa
     return MATPBR_PATH_OK;
 }
 
+int matpbr_path_render_objects_textures(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                        float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                        int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                        const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                        const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                        const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                        const void* texels, long n_texels) {
+    return render_objects(RENDER_FRAME, 7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels,
+                          n_texels);
+}
+
+int matpbr_path_object_texture_host(const float* tri, const float* uv, const float* o, const float* d, long N, const MatpbrPathObjectTex* tex,
+                                    const void* texels, long n_texels, float* u, float* v, float* st, float* base, float* orm) {
+    if (!tri || !uv || !o || !d || !tex || !texels || ((uintptr_t)texels & 15) || !u || !v || !st || !base || !orm || N < 0 ||
+        !tex_valid(*tex, true, n_texels))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) {
+        const float *v0 = tri + 9 * k, *e1 = v0 + 3, *e2 = v0 + 6;
+        tri_uv(v0, e1, e2, o + 3 * k, d + 3 * k, u[k], v[k]);
+        object_st(uv + 6 * k, u[k], v[k], st[2 * k], st[2 * k + 1]);
+        texture_fetch_record(*tex, static_cast<const float4*>(texels), st[2 * k], st[2 * k + 1], base + 3 * k, orm + 3 * k);
+    }
+    return MATPBR_PATH_OK;
+}
+
 // the object of the two CPU entry points below: kind 5, with or without the smooth flag (the caller passes both normals either way)
 static bool rough_object(const MatpbrPathObject* ob) {
     return ob && (ob->kind & ~MATPBR_PATH_OBJECT_SMOOTH) == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC && rough_valid(ob->p);
@@ -1343,6 +1450,32 @@ int matpbr_path_feature_colors_host(const void* nodes, const void* tris, int H, 
         for (int j = 0; j < W; ++j) {
             HostStack stk;
             feature_colors_pixel(q, ot, i, j, stk, out + 3 * ((long)i * W + j));
+        }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_feature_tints(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects, int n_objects,
+                              long n_scene_tri, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex, const void* texels,
+                              long n_texels, float* out, void* stream) {
+    FeatColorArgs q{static_cast<const float4*>(nodes), static_cast<const float4*>(tris), obj_col, out, H, W};
+    ObjTable ot{};
+    FeatTextures tx;
+    if (!feature_tints_args(objects, n_objects, n_scene_tri, fov_x_deg, obj_uv, tex, texels, n_texels, q, ot, tx)) return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(feature_tints_kernel, tile_grid(H, W), dim3(kTileX, kTileY), 0, (hipStream_t)stream, q, ot, tx);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_feature_tints_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, const MatpbrPathObject* objects,
+                                   int n_objects, long n_scene_tri, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                   const void* texels, long n_texels, float* out) {
+    FeatColorArgs q{static_cast<const float4*>(nodes), static_cast<const float4*>(tris), obj_col, out, H, W};
+    ObjTable ot{};
+    FeatTextures tx;
+    if (!feature_tints_args(objects, n_objects, n_scene_tri, fov_x_deg, obj_uv, tex, texels, n_texels, q, ot, tx)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j) {
+            HostStack stk;
+            feature_colors_pixel(q, ot, i, j, stk, out + 3 * ((long)i * W + j), tx);
         }
     return MATPBR_PATH_OK;
 }

@@ -5,7 +5,7 @@
 // atomics: the bits are the same from run to run.  The per-pixel bodies are __host__ __device__: the *_host entry points run what
 // the kernels run (the device takes its exponentials and reciprocals from the hardware's approximations, the CPU from libm).
 #pragma once
-#include "path_objects.hpp"
+#include "path_textures.hpp"
 
 namespace {
 constexpr int kDnTileX = 32, kDnTileY = 8;   // the filter's workgroup: 256 lanes, a wave = two rows of 32 pixels (512 B of cv each)
@@ -123,9 +123,30 @@ struct FeatColorArgs {
     int32_t n_scene_tri;
     float f_pix, cx, cy;
 };
-// features_pixel's ray and traversal: c = the interpolated colour where the first hit lies on a coloured object, (1, 1, 1) elsewhere
-template <class Stack>
-__host__ __device__ inline void feature_colors_pixel(const FeatColorArgs& q, const ObjTable& ot, int i, int j, Stack& stk, float c[3]) {
+// the tint guide's textures ("Textured inserted objects"): a trailing argument that the colour guide does not have
+struct FeatTextures {
+    const float* uv;        // nullable: corner coordinates of the inserted triangles (textured objects)
+    const float4* texels;
+    MatpbrPathObjectTex tex[MATPBR_PATH_MAX_OBJECTS];
+};
+// c *= the base-colour fetch of the textured object that holds triangle `id` (slot = id - n_scene_tri) at the hit u, v
+__host__ __device__ inline void feature_texture(const FeatTextures& tx, const ObjTable& ot, int id, int slot, float u, float v, float c[3]) {
+    const MatpbrPathObjectTex r = tex_lookup(ot, tx.tex, id);
+    const float* up = tx.uv + 6 * (long)slot;
+    float cs[6], s, t, base[3];
+    for (int n = 0; n < 6; ++n) cs[n] = up[n];
+    object_st(cs, u, v, s, t);
+    base[0] = base[1] = base[2] = 1.0f;
+    if (r.base_w > 0) texture_fetch(tx.texels + (long)r.base_first, r.base_w, r.base_h, s, t, base);
+    for (int n = 0; n < 3; ++n) c[n] *= base[n];
+}
+// features_pixel's ray and traversal: c = the interpolated colour where the first hit lies on a coloured object, (1, 1, 1) elsewhere.
+// With FeatTextures the colour is multiplied by the base-colour fetch where the object is textured; without, every `if (TEX ...)` folds
+// away.
+template <class Stack, class... Tex>
+__host__ __device__ inline void feature_colors_pixel(const FeatColorArgs& q, const ObjTable& ot, int i, int j, Stack& stk, float c[3],
+                                                     const Tex&... tx) {
+    constexpr bool TEX = sizeof...(Tex) != 0;
     const float o[3] = {0.0f, 0.0f, 0.0f};
     float d[3] = {((float)j - q.cx) / q.f_pix, -((float)i - q.cy) / q.f_pix, -1.0f};
     {
@@ -140,13 +161,19 @@ __host__ __device__ inline void feature_colors_pixel(const FeatColorArgs& q, con
     int32_t id;
     __builtin_memcpy(&id, &A.w, 4);
     const int obj = object_index(ot, id);
-    if (obj < 0 || !(ot.o[obj].kind & MATPBR_PATH_OBJECT_COLORED)) return;
+    if (obj < 0 || !(ot.o[obj].kind & (TEX ? MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_TEXTURED : MATPBR_PATH_OBJECT_COLORED))) return;
     const float v0[3] = {A.x, A.y, A.z}, e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
-    const float* cp = q.obj_col + 9 * (long)(id - q.n_scene_tri);
-    float cc[9], bu, bv;
-    for (int n = 0; n < 9; ++n) cc[n] = cp[n];
+    float bu, bv;
     tri_uv_strict(v0, e1, e2, o, d, bu, bv);
-    object_color(cc, bu, bv, c);
+    if (!TEX || (ot.o[obj].kind & MATPBR_PATH_OBJECT_COLORED)) {
+        const float* cp = q.obj_col + 9 * (long)(id - q.n_scene_tri);
+        float cc[9];
+        for (int n = 0; n < 9; ++n) cc[n] = cp[n];
+        object_color(cc, bu, bv, c);
+    }
+    if constexpr (TEX) {
+        if (ot.o[obj].kind & MATPBR_PATH_OBJECT_TEXTURED) feature_texture(tx..., ot, id, id - q.n_scene_tri, bu, bv, c);
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void feature_colors_kernel(const FeatColorArgs q, const ObjTable ot) {
@@ -157,6 +184,19 @@ __global__ __launch_bounds__(kBlock) void feature_colors_kernel(const FeatColorA
     LdsStack stk{s_stack + tid};
     float c[3];
     feature_colors_pixel(q, ot, i, j, stk, c);
+    float* op = q.out + 3 * ((long)i * q.W + j);
+    op[0] = c[0]; op[1] = c[1]; op[2] = c[2];
+}
+
+// the tint guide: feature_colors_kernel with the textures
+__global__ __launch_bounds__(kBlock) void feature_tints_kernel(const FeatColorArgs q, const ObjTable ot, const FeatTextures tx) {
+    __shared__ int s_stack[kStack * kBlock];
+    const int tid = threadIdx.y * kTileX + threadIdx.x;
+    const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
+    if (i >= q.H || j >= q.W) return;   // no barriers below: each lane's stack column is its own
+    LdsStack stk{s_stack + tid};
+    float c[3];
+    feature_colors_pixel(q, ot, i, j, stk, c, tx);
     float* op = q.out + 3 * ((long)i * q.W + j);
     op[0] = c[0]; op[1] = c[1]; op[2] = c[2];
 }

@@ -95,7 +95,7 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply_any(path: str, normals: bool = False, colors: bool = False):
+def read_ply_any(path: str, normals: bool = False, colors: bool = False, uv: bool = False):
     """A PLY somebody else wrote (an inserted object, `oi.ply`) -> (vertices [Nv,3] float64, triangles [Nt,3] int32).  ASCII or
     binary little-endian; x, y, z of any scalar type, other vertex properties (uv, ...) skipped; faces as one
     `list uchar|uint8|int ... vertex_indices` of 3 or more vertices, fan-triangulated; elements after the faces are not read.
@@ -103,7 +103,10 @@ def read_ply_any(path: str, normals: bool = False, colors: bool = False):
     as written, or None when the vertex element has none (smooth inserted objects).  Vertex colours likewise:
     with `colors=True` one more value follows, C [Nv,3] float64 from the properties `red green blue` (or `r g b`), an integer type
     divided by its type's maximum, a float type as written, or None when the vertex element has none (vertex-coloured inserted
-    objects).  Anything else is a ValueError naming the file."""
+    objects).  Texture coordinates likewise: with `uv=True` one more value follows, last, UV [Nv,2] float64 from
+    the per-vertex properties `s t`, `u v` or `texture_u texture_v` (the first pair the file has, of any scalar type, as written), or
+    None when the vertex element has none (textured inserted objects; a `texcoord` list on the faces is not
+    read).  Anything else is a ValueError naming the file."""
     def bad(why):
         return ValueError(f"{path}: {why}")
 
@@ -130,7 +133,7 @@ def read_ply_any(path: str, normals: bool = False, colors: bool = False):
                 break
         if fmt not in ("ascii", "binary_little_endian"):
             raise bad(f"format {fmt!r} is not supported (ascii and binary_little_endian are)")
-        V = T = Nn = Cc = None
+        V = T = Nn = Cc = Uv = None
         for name, count, props in elements:
             for pr in props:
                 if any(t not in _PLY_TYPES for t in pr[1:]):
@@ -140,6 +143,7 @@ def read_ply_any(path: str, normals: bool = False, colors: bool = False):
                     raise bad("the vertex element needs scalar properties x, y and z")
                 names = [pr[0] for pr in props]
                 rgb = next((c for c in (("red", "green", "blue"), ("r", "g", "b")) if all(x in names for x in c)), None)
+                st = next((c for c in (("s", "t"), ("u", "v"), ("texture_u", "texture_v")) if all(x in names for x in c)), None)
 
                 def scale(c):   # an integer colour's divisor: its type's maximum
                     dt = np.dtype(_PLY_TYPES[props[names.index(c)][1]])
@@ -153,6 +157,8 @@ def read_ply_any(path: str, normals: bool = False, colors: bool = False):
                         Nn = np.stack([rows[:, names.index(c)] for c in ("nx", "ny", "nz")], -1)
                     if rgb is not None:
                         Cc = np.stack([rows[:, names.index(c)] / scale(c) for c in rgb], -1)
+                    if st is not None:
+                        Uv = np.stack([rows[:, names.index(c)] for c in st], -1)
                 else:
                     dt = np.dtype([(n, "<" + _PLY_TYPES[t]) for n, t in props])
                     buf = fh.read(count * dt.itemsize)
@@ -164,6 +170,8 @@ def read_ply_any(path: str, normals: bool = False, colors: bool = False):
                         Nn = np.stack([rec[c].astype(np.float64) for c in ("nx", "ny", "nz")], -1)
                     if rgb is not None:
                         Cc = np.stack([rec[c].astype(np.float64) / scale(c) for c in rgb], -1)
+                    if st is not None:
+                        Uv = np.stack([rec[c].astype(np.float64) for c in st], -1)
             elif name == "face":
                 if len(props) != 1 or len(props[0]) != 3:
                     raise bad("the face element must be one list property")
@@ -191,7 +199,7 @@ def read_ply_any(path: str, normals: bool = False, colors: bool = False):
         raise bad("needs a vertex and a face element")
     if T.size and (T.min() < 0 or T.max() >= V.shape[0]):
         raise bad("a face index is outside the vertex array")
-    return (V, T.astype(np.int32)) + ((Nn,) if normals else ()) + ((Cc,) if colors else ())
+    return (V, T.astype(np.int32)) + ((Nn,) if normals else ()) + ((Cc,) if colors else ()) + ((Uv,) if uv else ())
 
 
 def angle_weighted_normals(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:

@@ -38,6 +38,10 @@ ROUGH_MIN_ALPHA = 0.02         # the GGX width's floor: the peak of D is 1 / (pi
 ROUGH_MIN_CONTRAST = 0.01      # |int_ior / ext_ior - 1| at least this: at a ratio of 1 the refraction Jacobian has no finite value
 OBJECT_SMOOTH = 0x100          # MATPBR_PATH_OBJECT_SMOOTH, OR-ed into PathObject.kind
 OBJECT_COLORED = 0x200         # MATPBR_PATH_OBJECT_COLORED, OR-ed into the kind of a diffuse or pbr object ("Vertex-coloured inserted objects")
+OBJECT_TEXTURED = 0x400        # MATPBR_PATH_OBJECT_TEXTURED, OR-ed into the kind of a diffuse or pbr object ("Textured inserted objects")
+OBJECT_FLAGS = OBJECT_SMOOTH | OBJECT_COLORED | OBJECT_TEXTURED
+TEXTURE_MAX_SIDE = 8192        # w, h of an image
+TEXTURE_MAX_UV = 64.0          # |s|, |t| of a corner: a coordinate's fractional part keeps 17 bits or more
 
 
 class PathObject(ctypes.Structure):
@@ -48,6 +52,13 @@ class PathObject(ctypes.Structure):
 class PathObjectPbr(ctypes.Structure):
     """MatpbrPathObjectPbr (include/matpbr_path.h): albedo, roughness and metallic of one object of kind BSDF_PBR."""
     _fields_ = [("a", ctypes.c_float * 3), ("r", ctypes.c_float), ("m", ctypes.c_float), ("reserved", ctypes.c_float * 3)]
+
+
+class PathObjectTex(ctypes.Structure):
+    """MatpbrPathObjectTex (include/matpbr_path.h): where the base-colour and the orm image of one textured object lie among the texels
+    (w = 0: no such image)."""
+    _fields_ = [("base_first", ctypes.c_int32), ("base_w", ctypes.c_int32), ("base_h", ctypes.c_int32), ("orm_first", ctypes.c_int32),
+                ("orm_w", ctypes.c_int32), ("orm_h", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
 class PathLights(ctypes.Structure):
@@ -100,6 +111,12 @@ SIGNATURES = {
     "matpbr_path_object_color_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
     "matpbr_path_feature_colors": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_feature_colors_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P]),
+    "matpbr_path_render_objects_textures": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long]),
+    "matpbr_path_object_texture_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long, _P, _P, ctypes.c_long] + [_P] * 5),
+    "matpbr_path_feature_tints": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P, _P,
+                                                 ctypes.c_long, _P, _P]),
+    "matpbr_path_feature_tints_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P, _P,
+                                                      ctypes.c_long, _P]),
     "matpbr_path_render_trans": (ctypes.c_int, _RENDER + [_P, _P, _P]),
     "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
     "matpbr_path_trans_lookup_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
@@ -133,15 +150,19 @@ LIGHT_SYMBOLS = ("matpbr_path_light_tables", "matpbr_path_render_objects_lights"
 ROUGH_SYMBOLS = ("matpbr_path_render_objects_rough", "matpbr_path_rough_sample_host", "matpbr_path_rough_eval_host")
 # and (vertex-coloured inserted objects)
 COLOR_SYMBOLS = ("matpbr_path_render_objects_colors", "matpbr_path_object_color_host", "matpbr_path_feature_colors", "matpbr_path_feature_colors_host")
-LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS
+# and (textured inserted objects)
+TEXTURE_SYMBOLS = ("matpbr_path_render_objects_textures", "matpbr_path_object_texture_host", "matpbr_path_feature_tints", "matpbr_path_feature_tints_host")
+LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS + TEXTURE_SYMBOLS
 # the feature each of them came with, as `symbol` names it
 _FEATURE = {name: what for names, what in ((SMOOTH_SYMBOLS, "smooth inserted objects"), (DENOISE_SYMBOLS, "the denoiser"),
                                            (PBR_SYMBOLS, "PBR inserted objects"), (LIGHT_SYMBOLS, "emissive inserted objects"),
                                            (ROUGH_SYMBOLS, "rough dielectric inserted objects"),
-                                           (COLOR_SYMBOLS, "vertex-coloured inserted objects")) for name in names}
+                                           (COLOR_SYMBOLS, "vertex-coloured inserted objects"),
+                                           (TEXTURE_SYMBOLS, "textured inserted objects")) for name in names}
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
-                  "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9}
+                  "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
+                  "matpbr_path_render_objects_textures": 13}
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -213,12 +234,24 @@ def _table_ptrs(table, records=None) -> tuple:
     return ptr(PathObject, table), ptr(PathObjectPbr, records)
 
 
-def _uncolored(table):
+def _uncolored(table, flags: int = OBJECT_COLORED | OBJECT_TEXTURED):
     """`table` as the entry points from before the colour flag take it (the features, the light tables: they need the kind and the smooth
-    flag only): the same table where no object carries OBJECT_COLORED, else copies without it."""
-    if table is None or not any(t.kind & OBJECT_COLORED for t in table):
+    flag only): the same table where no object carries OBJECT_COLORED or OBJECT_TEXTURED, else copies without them.  `flags`: the
+    flags to hide (the colour guide takes the colour flag and not the texture flag)."""
+    if table is None or not any(t.kind & flags for t in table):
         return table
-    return [PathObject(t.kind & ~OBJECT_COLORED, t.first_tri, t.n_tri, t.p) for t in table]
+    return [PathObject(t.kind & ~flags, t.first_tri, t.n_tri, t.p) for t in table]
+
+
+def _tex_ptrs(table, tex, texels):
+    """(the PathObjectTex records, the texel buffer's address, its length) as the C ABI takes them; None, None, 0 without textures.
+    `texels`: a float32 [n,4] numpy array or torch tensor.  ValueError unless there is one record per object."""
+    if tex is None or not len(tex):
+        return None, None, 0
+    if len(tex) != len(table):
+        raise ValueError(f"one record per object: {len(table)} objects, {len(tex)} texture records")
+    rec = ctypes.cast(tex if isinstance(tex, ctypes.Array) else (PathObjectTex * len(tex))(*tex), _P)
+    return rec, (texels.data_ptr() if hasattr(texels, "data_ptr") else _ptr(texels)), int(texels.shape[0])
 
 
 def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional[int] = None) -> Dict[str, object]:
@@ -431,8 +464,63 @@ def _corner_colors(k: int, ob: dict, kind: int, Vo: np.ndarray, To: np.ndarray) 
     return Co[To]
 
 
+def _corner_uv(k: int, ob: dict, Vo: np.ndarray, To: np.ndarray) -> np.ndarray:
+    """Object k's "uv" [Nv,2] (finite, |.| <= TEXTURE_MAX_UV) expanded to one record per triangle corner [Nt,3,2]; ValueError when bad."""
+    Uo = np.asarray(ob["uv"], dtype=np.float64)
+    if Uo.shape != (Vo.shape[0], 2):
+        raise ValueError(f"object {k}: uv must be [Nv,2] = {(Vo.shape[0], 2)}, one (s, t) per vertex, got {Uo.shape}")
+    bad = ~(np.isfinite(Uo) & (np.abs(Uo) <= TEXTURE_MAX_UV)).all(-1)
+    if bad.any():
+        v = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"object {k}: the texture coordinate of vertex {v} must be finite with |s|, |t| <= {TEXTURE_MAX_UV:g}, got {Uo[v].tolist()}")
+    return Uo[To]
+
+
+def _texture_image(k: int, key: str, img) -> np.ndarray:
+    """Object k's image ob[key] [h,w,3] (linear, finite, in [0, 1]) as texels [h w, 4] float32 = (r, g, b, 0), row 0 the top row;
+    ValueError naming the texel when bad."""
+    A = np.asarray(img, dtype=np.float64)
+    if A.ndim != 3 or A.shape[2] != 3 or not (1 <= A.shape[0] <= TEXTURE_MAX_SIDE and 1 <= A.shape[1] <= TEXTURE_MAX_SIDE):
+        raise ValueError(f"object {k}: {key} must be [h,w,3] with h, w in [1, {TEXTURE_MAX_SIDE}], got {A.shape}")
+    bad = ~(np.isfinite(A) & (A >= 0) & (A <= 1)).all(-1)
+    if bad.any():
+        i, j = (int(x[0]) for x in np.nonzero(bad))
+        raise ValueError(f"object {k}: {key}: texel (row {i}, column {j}) must be finite and lie in [0, 1], got {A[i, j].tolist()}")
+    out = np.zeros((A.shape[0] * A.shape[1], 4), np.float32)
+    out[:, :3] = A.reshape(-1, 3)
+    return out
+
+
+def _object_textures(k: int, ob: dict, kind: int, first: int):
+    """Object k's images -> (its PathObjectTex with the images placed from texel `first` on, [texel arrays]); ValueError where the
+    object may carry none, or carries "uv" and images the wrong way round."""
+    have = [key for key in ("texture", "orm_texture") if ob.get(key) is not None]
+    if not have and ob.get("uv") is None:
+        return PathObjectTex(), []
+    if kind not in (BSDF_DIFFUSE, BSDF_PBR):
+        raise ValueError(f"object {k}: an image textures a 'diffuse' or a 'pbr' object; a {ob['bsdf'].get('type')!r} object takes none "
+                         f"(drop 'uv', 'texture' and 'orm_texture')")
+    if not have:
+        raise ValueError(f"object {k}: 'uv' without an image: give 'texture' (or 'orm_texture' on a pbr object), or drop 'uv'")
+    if ob.get("uv") is None:
+        raise ValueError(f"object {k}: {have[0]!r} without 'uv': an image needs one (s, t) per vertex")
+    if "orm_texture" in have and kind != BSDF_PBR:
+        raise ValueError(f"object {k}: 'orm_texture' holds roughness and metallic, which a 'diffuse' object does not have (a 'pbr' one does)")
+    rec, texels = PathObjectTex(), []
+    for key, name in (("texture", "base"), ("orm_texture", "orm")):
+        if key in have:
+            tx = _texture_image(k, key, ob[key])
+            h, w = np.asarray(ob[key]).shape[:2]
+            setattr(rec, name + "_first", first)
+            setattr(rec, name + "_w", w)
+            setattr(rec, name + "_h", h)
+            texels.append(tx)
+            first += tx.shape[0]
+    return rec, texels
+
+
 def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False, pbr: bool = False,
-                  lights: bool = False, colors: bool = False):
+                  lights: bool = False, colors: bool = False, textures: bool = False):
     """The depth mesh with the inserted meshes appended -> (V [Nv,3] float64, T [Nt,3] int32, [PathObject]).  Object k's triangles
     follow the scene's in the order given; its ids are its range of T.  An object may carry "normals" [Nv,3] (per vertex, outward, any
     length): it is smooth ("Smooth inserted objects"), its kind carries OBJECT_SMOOTH, and with `normals=True`
@@ -444,7 +532,12 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
     it is refused.  A diffuse or pbr object may carry "colors" [Nv,3] (per vertex, linear RGB, finite, in [0, 1]; DESIGN.md section 1.4,
     "Vertex-coloured inserted objects"): its kind carries OBJECT_COLORED, and with `colors=True` one more value follows, last, the
     corner colours [Nt - scene's Nt, 3, 3] float32 of every inserted triangle (zero for the objects without colours, which the kernel
-    never reads), or None when no object has "colors".  On a dielectric, area or roughdielectric object "colors" is refused."""
+    never reads), or None when no object has "colors".  On a dielectric, area or roughdielectric object "colors" is refused.  A diffuse
+    or pbr object may carry "uv" [Nv,2] (per vertex, finite, |.| <= 64) with "texture" [h,w,3] (base colour: linear, finite, in [0, 1],
+    row 0 the top row) and, on a pbr object, "orm_texture" [h,w,3] (glTF's occlusion, roughness, metallic; DESIGN.md section 1.4,
+    "Textured inserted objects"): its kind carries OBJECT_TEXTURED, and with `textures=True` one more value follows, last,
+    (obj_uv [Nt - scene's Nt, 3, 2] float32, [PathObjectTex] one per object, texels [n, 4] float32), or None when no object is textured.
+    "uv" without an image, an image without "uv", an image on another kind and "orm_texture" on a diffuse object are refused."""
     V = [np.asarray(vertices, dtype=np.float64).reshape(-1, 3)]
     T = [np.asarray(triangles, dtype=np.int32).reshape(-1, 3)]
     if len(objects) > MAX_OBJECTS:
@@ -452,6 +545,9 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
     table: List[PathObject] = []
     corner: List[np.ndarray] = []
     tint: List[np.ndarray] = []
+    st: List[np.ndarray] = []
+    tex: List[PathObjectTex] = []
+    texels: List[np.ndarray] = []
     records: List[PathObjectPbr] = []
     nv, nt = V[0].shape[0], T[0].shape[0]
     for k, ob in enumerate(objects):
@@ -479,6 +575,14 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
             kind |= OBJECT_COLORED
         else:
             tint.append(np.zeros((To.shape[0], 3, 3)))
+        rec, images = _object_textures(k, ob, kind & ~OBJECT_FLAGS, sum(x.shape[0] for x in texels))
+        tex.append(rec)
+        texels += images
+        if images:
+            st.append(_corner_uv(k, ob, Vo, To))
+            kind |= OBJECT_TEXTURED
+        else:
+            st.append(np.zeros((To.shape[0], 3, 2)))
         V.append(Vo)
         T.append((To.astype(np.int64) + nv).astype(np.int32))
         table.append(PathObject(kind, nt, To.shape[0], (ctypes.c_float * 3)(*p)))
@@ -491,6 +595,8 @@ def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence
     out += (light_tables(out[0], out[1], table, records),) if lights else ()
     if colors:
         out += (np.ascontiguousarray(np.concatenate(tint), dtype=np.float32) if any(t.kind & OBJECT_COLORED for t in table) else None,)
+    if textures:
+        out += ((np.ascontiguousarray(np.concatenate(st), dtype=np.float32), tex, np.ascontiguousarray(np.concatenate(texels))) if texels else None,)
     return out
 
 
@@ -556,6 +662,33 @@ def object_color_host(tri: np.ndarray, col: np.ndarray, o: np.ndarray, d: np.nda
     check(symbol("matpbr_path_object_color_host")(_ptr(TR), _ptr(CL), _ptr(O), _ptr(D), N, _ptr(u), _ptr(v), _ptr(c)),
           "matpbr_path_object_color_host")
     return u, v, c
+
+
+def object_texture_host(tri: np.ndarray, uv: np.ndarray, o: np.ndarray, d: np.ndarray, tex: PathObjectTex, texels: np.ndarray):
+    """The kernel's texture lookups of a textured object on the CPU: triangle records tri [N,3,3] = (v0, e1, e2), corner coordinates
+    uv [N,3,2], rays o, d [N,3], one record over texels [n,4] -> (u [N], v [N], st [N,2], base [N,3], orm [N,3]); (1, 1, 1) for an
+    image the record does not have."""
+    TR = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1, 3, 3)
+    UV = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 3, 2)
+    O, D = _rows(o, 3), _rows(d, 3)
+    N = _same_rows("tri, uv, o and d must have the same rows", TR, UV, O, D)
+    TX = _aligned_texels(texels)
+    u, v, st = np.empty(N, np.float32), np.empty(N, np.float32), np.empty((N, 2), np.float32)
+    base, orm = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
+    check(symbol("matpbr_path_object_texture_host")(_ptr(TR), _ptr(UV), _ptr(O), _ptr(D), N, ctypes.cast(ctypes.byref(tex), _P), _ptr(TX),
+                                                    TX.shape[0], _ptr(u), _ptr(v), _ptr(st), _ptr(base), _ptr(orm)),
+          "matpbr_path_object_texture_host")
+    return u, v, st, base, orm
+
+
+def _aligned_texels(texels) -> np.ndarray:
+    """`texels` as float32 [n,4] in memory whose address is a multiple of 16, as the library's float4 loads need it."""
+    a = np.asarray(texels, dtype=np.float32).reshape(-1, 4)
+    buf = np.empty(a.size + 4, np.float32)
+    off = (-buf.ctypes.data % 16) // 4
+    out = buf[off:off + a.size].reshape(-1, 4)
+    out[...] = a
+    return out
 
 
 def object_sample_shading_host(bsdf: dict, ng: np.ndarray, ns: np.ndarray, wo: np.ndarray, u: np.ndarray):
@@ -726,6 +859,31 @@ def feature_colors_host(bvh: Dict[str, object], H: int, W: int, fov_x_deg: float
     return out
 
 
+def feature_tints_host(bvh: Dict[str, object], H: int, W: int, fov_x_deg: float = 35.0, objects: Optional[Sequence[PathObject]] = None,
+                       obj_col: Optional[np.ndarray] = None, textures=None, n_scene_tri: int = 0) -> np.ndarray:
+    """`PathTracer.feature_tints` on the CPU with the routine the kernel runs -> [H,W,3]: the interpolated colour times the base-colour
+    fetch where the camera ray through the pixel centre first hits a coloured or textured object, (1, 1, 1) elsewhere.  `objects`,
+    `obj_col`, `textures`, `n_scene_tri`: `merge_objects`' table, its corner colours, its (obj_uv, records, texels) and the depth
+    mesh's triangle count."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"H and W must be positive, got {H} x {W}")
+    table, _ = _table_ptrs(objects)
+    cc = None if obj_col is None else np.array(obj_col, dtype=np.float32, order="C", copy=True)
+    uv = rec = tx = None
+    n_texels = 0
+    if textures is not None:
+        uv = np.array(textures[0], dtype=np.float32, order="C", copy=True)
+        tx_arr = _aligned_texels(textures[2])
+        rec, tx, n_texels = _tex_ptrs(objects, textures[1], tx_arr)
+    out = np.empty((H, W, 3), np.float32)
+    check(symbol("matpbr_path_feature_tints_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), H, W, float(fov_x_deg), table,
+                                                   len(objects) if objects else 0, int(n_scene_tri), _ptr(cc) if cc is not None else None,
+                                                   _ptr(uv) if uv is not None else None, rec, tx, n_texels, _ptr(out)),
+          "matpbr_path_feature_tints_host")
+    return out
+
+
 def denoise_prepare_host(A: np.ndarray, B: np.ndarray, geom: np.ndarray) -> np.ndarray:
     """The filter's first step on the CPU with the routine the kernel runs: A, B [H,W,3], geom [H,W,8] -> cv0 [H,W,4] = ((A + B) / 2,
     the prefiltered variance of the mean's luminance)."""
@@ -826,7 +984,11 @@ class PathTracer:
     "Rough dielectric objects"; `stats["n_rough_objects"]` counts them): it shades from both sides, takes "normals", and, unlike
     clear glass, takes an emitter sample at every vertex.  A diffuse or pbr object may carry "colors" [Nv,3] (per vertex, linear RGB in
     [0, 1]; DESIGN.md section 1.4, "Vertex-coloured inserted objects"; `stats["n_colored_objects"]` counts them): its reflectance or
-    albedo is multiplied by the colour interpolated at each hit.  A tracer with objects renders forward only."""
+    albedo is multiplied by the colour interpolated at each hit.  A diffuse or pbr object may carry "uv" [Nv,2] with "texture" [h,w,3]
+    (base colour, linear, in [0, 1], row 0 the top row) and, a pbr one, "orm_texture" [h,w,3] ("Textured inserted
+    objects"; `stats["n_textured_objects"]` counts them): the reflectance or the albedo is multiplied by the base colour, the roughness
+    and the metallic by the orm image's g and b, each read with bilinear filtering and repeat wrapping at the coordinate interpolated
+    at the hit.  A tracer with objects renders forward only."""
 
     def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
                  objects: Optional[Sequence[dict]] = None):
@@ -840,27 +1002,33 @@ class PathTracer:
         self.lights = None                            # (PathLights, tris, cdf on the device), when some object is of kind BSDF_AREA
         self.rough = False                            # some object is of kind BSDF_ROUGH_DIELECTRIC: `render` takes the rough entry point
         self.obj_col: Optional[torch.Tensor] = None   # corner colours of the inserted triangles, when some object is coloured
-        n_smooth = n_pbr = n_lights = n_rough = n_colored = 0
+        self.textures = None                          # (obj_uv, PathObjectTex records, texels on the device), when some object is textured
+        n_smooth = n_pbr = n_lights = n_rough = n_colored = n_textured = 0
         if objects:
-            vertices, triangles, table, corner, records, lt, tint = merge_objects(vertices, triangles, objects, normals=True, pbr=True,
-                                                                                  lights=True, colors=True)
+            vertices, triangles, table, corner, records, lt, tint, tex = merge_objects(vertices, triangles, objects, normals=True, pbr=True,
+                                                                                       lights=True, colors=True, textures=True)
             self.objects = (PathObject * len(table))(*table)
             n_smooth = sum(1 for t in table if t.kind & OBJECT_SMOOTH)
-            n_pbr = sum(1 for t in table if t.kind & ~(OBJECT_SMOOTH | OBJECT_COLORED) == BSDF_PBR)
+            n_pbr = sum(1 for t in table if t.kind & ~OBJECT_FLAGS == BSDF_PBR)
             n_rough = sum(1 for t in table if t.kind & ~OBJECT_SMOOTH == BSDF_ROUGH_DIELECTRIC)
             n_colored = sum(1 for t in table if t.kind & OBJECT_COLORED)
+            n_textured = sum(1 for t in table if t.kind & OBJECT_TEXTURED)
             for have, level in ((lt is not None, "lights"), (n_rough, "rough"), (n_pbr, "pbr"), (corner is not None, "normals"),
-                                (tint is not None, "colors")):
+                                (tint is not None, "colors"), (tex is not None, "textures")):
                 if have:                              # a library built before the feature: PathError now, not at the first render
                     symbol("matpbr_path_render_objects_" + level)
             if tint is not None:
                 symbol("matpbr_path_feature_colors")
                 self.obj_col = torch.from_numpy(tint).to(self.device)
+            if tex is not None:
+                symbol("matpbr_path_feature_tints")
+                self.textures = (torch.from_numpy(tex[0]).to(self.device), (PathObjectTex * len(tex[1]))(*tex[1]),
+                                 torch.from_numpy(tex[2]).to(self.device))
             if lt is not None:
                 n_lights = int(lt["header"].n_lights)
                 self.lights = (lt["header"], torch.from_numpy(lt["tris"]).to(self.device), torch.from_numpy(lt["cdf"]).to(self.device))
             self.rough = n_rough > 0
-            if n_pbr or lt is not None or n_rough or n_colored:   # the light, rough and colour entry points take the records beside the table as well
+            if n_pbr or lt is not None or n_rough or n_colored or n_textured:   # the entry points from the lights' on take the records beside the table as well
                 self.pbr = (PathObjectPbr * len(records))(*records)
             if corner is not None:
                 self.obj_nrm = torch.from_numpy(corner).to(self.device)
@@ -876,6 +1044,7 @@ class PathTracer:
         self.stats["n_lights"] = n_lights
         self.stats["n_rough_objects"] = n_rough
         self.stats["n_colored_objects"] = n_colored
+        self.stats["n_textured_objects"] = n_textured
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -922,14 +1091,23 @@ class PathTracer:
         return nrm.to(self.device, torch.float32).contiguous()
 
     def object_args(self) -> tuple:
-        """(table, n_objects, obj_nrm, n_scene_tri, records, lights header, light_tris, light_cdf, obj_col): the object arguments of a forward
-        entry point after `stream`, as the C ABI takes them, None where the tracer has none.  An entry takes the first
-        OBJECT_ENTRIES[its name] of them."""
+        """(table, n_objects, obj_nrm, n_scene_tri, records, lights header, light_tris, light_cdf, obj_col, obj_uv, texture records, texels,
+        n_texels): the object arguments of a forward entry point after `stream`, as the C ABI takes them, None where the tracer has
+        none.  An entry takes the first OBJECT_ENTRIES[its name] of them.  The last four are there on a tracer with a textured object
+        only, the one whose `render` takes the entry that reads them: a tracer without one returns the nine values it always has."""
         ptr = lambda t: t.data_ptr() if t is not None else None
         table, records = _table_ptrs(self.objects, self.pbr)
         head, ltris, lcdf = self.lights if self.lights is not None else (None, None, None)
         return (table, len(self.objects) if self.objects is not None else 0, ptr(self.obj_nrm), self.n_scene_tris, records,
-                ctypes.cast(ctypes.byref(head), _P) if head is not None else None, ptr(ltris), ptr(lcdf), ptr(self.obj_col))
+                ctypes.cast(ctypes.byref(head), _P) if head is not None else None, ptr(ltris), ptr(lcdf), ptr(self.obj_col),
+                *(self._texture_args() if self.textures is not None else ()))
+
+    def _texture_args(self) -> tuple:
+        """(obj_uv, texture records, texels, n_texels) as the C ABI takes them; (None, None, None, 0) without a textured object."""
+        if self.textures is None:
+            return None, None, None, 0
+        uv, rec, texels = self.textures
+        return (uv.data_ptr(), *_tex_ptrs(self.objects, rec, texels))
 
     @torch.no_grad()
     def render(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
@@ -953,7 +1131,7 @@ class PathTracer:
         elif self.objects is None:
             entry, own = "matpbr_path_render", ()
         else:
-            entry = "matpbr_path_render_objects" + ("_colors" if self.obj_col is not None else "_rough" if self.rough else "_lights" if self.lights is not None else
+            entry = "matpbr_path_render_objects" + ("_textures" if self.textures is not None else "_colors" if self.obj_col is not None else "_rough" if self.rough else "_lights" if self.lights is not None else
                                                     "_pbr" if self.pbr is not None else "_normals" if self.obj_nrm is not None else "")
             own = self.object_args()[:OBJECT_ENTRIES[entry]]
         check(symbol(entry, lib)(*args, *own), entry)
@@ -978,10 +1156,23 @@ class PathTracer:
         """[H,W,3] on the device: the interpolated colour where the camera ray through the pixel centre (`features`' ray) first hits a
         vertex-coloured object, (1, 1, 1) elsewhere: what `relight.albedo_guide` multiplies a coloured object's constant by."""
         out = torch.empty(self.H, self.W, 3, device=self.device, dtype=torch.float32)
-        check(symbol("matpbr_path_feature_colors")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov, _table_ptrs(self.objects)[0],
+        check(symbol("matpbr_path_feature_colors")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov,
+                                                   _table_ptrs(_uncolored(self.objects, OBJECT_TEXTURED))[0],
                                                    len(self.objects) if self.objects is not None else 0, self.n_scene_tris,
                                                    self.obj_col.data_ptr() if self.obj_col is not None else None, out.data_ptr(),
                                                    torch.cuda.current_stream(self.device).cuda_stream), "matpbr_path_feature_colors")
+        return out
+
+    @torch.no_grad()
+    def feature_tints(self) -> torch.Tensor:
+        """[H,W,3] on the device: the interpolated colour times the base-colour fetch where the camera ray through the pixel centre
+        (`features`' ray) first hits a coloured or textured object, (1, 1, 1) elsewhere: `feature_colors` with the textures, what
+        `relight.albedo_guide` multiplies a textured object's constant by."""
+        out = torch.empty(self.H, self.W, 3, device=self.device, dtype=torch.float32)
+        check(symbol("matpbr_path_feature_tints")(self.nodes.data_ptr(), self.tris.data_ptr(), self.H, self.W, self.fov, _table_ptrs(self.objects)[0],
+                                                  len(self.objects) if self.objects is not None else 0, self.n_scene_tris,
+                                                  self.obj_col.data_ptr() if self.obj_col is not None else None, *self._texture_args(),
+                                                  out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), "matpbr_path_feature_tints")
         return out
 
     @torch.no_grad()

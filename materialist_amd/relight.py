@@ -242,8 +242,8 @@ def albedo_guide(geom: torch.Tensor, albedo: torch.Tensor, bsdfs=(), colors: Opt
     (id 0), a diffuse object's reflectance, a PBR object's albedo, 1 on glass, on rough glass ("roughdielectric": colourless, like
     glass) and on an area light (the fall-through: a light's pixels are its radiance, which the colour term guides alone), 0 where it
     hits nothing.  `bsdfs`: the inserted objects' BSDFs, in order.  `colors` [H,W,3]: `PathTracer.feature_colors()` of a tracer with
-    vertex-coloured objects; a diffuse or pbr object's constant is multiplied by it, so that the guide follows a colour edge inside
-    the object (it is 1 off the coloured objects)."""
+    vertex-coloured objects, or `PathTracer.feature_tints()` of one with textured objects; a diffuse or pbr object's constant is
+    multiplied by it, so that the guide follows a colour edge inside the object (it is 1 off the coloured and textured objects)."""
     ids = geom[..., 7]
     guide = albedo.to(geom.device, torch.float32).reshape(geom.shape[0], geom.shape[1], 3).clone()
     guide[ids < 0] = 0.0
@@ -338,8 +338,11 @@ def load_oi_scene(path: str) -> List[dict]:
     {"type": "area", "radiance": [r, g, b]} is a lamp, which takes "normals": "flat" only); "normals" is "flat" (default) or "vertex" (the file's normals if it has them, else
     `mesh.angle_weighted_normals`); "colors" (a diffuse or pbr object only) is "none" (default), "vertex" (the file's `red green blue`,
     display values, decoded to linear as `loss.srgb_to_linear` decodes) or "vertex_linear" (the file's values as written, what Mitsuba's
-    `mesh_attribute` does; DESIGN.md section 1.4, "Vertex-coloured inserted objects")
-    -> [{"ply": absolute path, "bsdf", "normals", "colors"}], nothing read yet but the list.  ValueError naming
+    `mesh_attribute` does; DESIGN.md section 1.4, "Vertex-coloured inserted objects"); "texture": "wood.png" (a diffuse or pbr object
+    only) and "orm_texture": "wood_orm.png" (a pbr object only) name images relative to the file, read over the ply's per-vertex texture
+    coordinates ("Textured inserted objects")
+    -> [{"ply": absolute path, "bsdf", "normals", "colors", "texture": absolute path or None, "orm_texture"}], nothing read yet but the
+    list.  ValueError naming
     the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
     import json
 
@@ -364,9 +367,9 @@ def load_oi_scene(path: str) -> List[dict]:
         where = f"{path}: objects[{k}]"
         if not isinstance(ob, dict):
             raise ValueError(f"{where} must be an object with 'ply' and 'bsdf'")
-        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors"})
+        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors", "texture", "orm_texture"})
         if extra:
-            raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals', 'colors')")
+            raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals', 'colors', 'texture', 'orm_texture')")
         if not isinstance(ob.get("ply"), str) or not ob["ply"]:
             raise ValueError(f"{where}: 'ply' must name a mesh file")
         ply = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob["ply"]))
@@ -386,7 +389,19 @@ def load_oi_scene(path: str) -> List[dict]:
             raise ValueError(f"{where}: 'colors' must be 'none', 'vertex' or 'vertex_linear', got {colors!r}")
         if colors != "none" and ob["bsdf"].get("type") not in ("diffuse", "pbr"):
             raise ValueError(f"{where}: 'colors' must be 'none' for a {ob['bsdf'].get('type')!r} object: vertex colours tint a 'diffuse' or a 'pbr' one")
-        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals, "colors": colors})
+        images = {}
+        for key, kinds in (("texture", ("diffuse", "pbr")), ("orm_texture", ("pbr",))):
+            images[key] = None
+            if ob.get(key) is None:
+                continue
+            if not isinstance(ob[key], str) or not ob[key]:
+                raise ValueError(f"{where}: {key!r} must name an image file")
+            if ob["bsdf"].get("type") not in kinds:
+                raise ValueError(f"{where}: {key!r} belongs to a {' or a '.join(repr(x) for x in kinds)} object, not to a {ob['bsdf'].get('type')!r} one")
+            images[key] = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob[key]))
+            if not os.path.isfile(images[key]):
+                raise ValueError(f"{where}: no such {key}: {images[key]}")
+        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals, "colors": colors, **images})
     return out
 
 
@@ -401,9 +416,40 @@ def _object_colors(path: str, C: Optional[np.ndarray], colors: str) -> np.ndarra
     return np.clip(C, 0.0, 1.0) ** 2.2 if colors == "vertex" else C
 
 
+def _object_image(path: str, decode: bool) -> np.ndarray:
+    """An inserted object's image as linear values [h,w,3] float64 in [0, 1], row 0 the top row.  An integer image (a PNG) is divided
+    by its type's maximum and, with `decode` (a base colour: display values), decoded with the project's 2.2 power; an orm image is
+    never decoded.  `.exr` / `.hdr` are taken as written and must lie in [0, 1].  ValueError naming the file."""
+    try:
+        img = np.asarray(load_image(path))
+    except Exception as e:
+        raise ValueError(f"{path}: cannot read the image: {e}") from None
+    if img.ndim == 2:
+        img = np.repeat(img[..., None], 3, -1)
+    if img.ndim != 3 or img.shape[2] < 3:
+        raise ValueError(f"{path}: an image of three channels is needed, got an array of shape {img.shape}")
+    img = img[..., :3]
+    if img.dtype.kind in "iu":
+        out = img.astype(np.float64) / float(np.iinfo(img.dtype).max)
+        return out ** 2.2 if decode else out
+    out = img.astype(np.float64)
+    if not (np.isfinite(out).all() and out.min() >= 0.0 and out.max() <= 1.0):
+        raise ValueError(f"{path}: a floating-point texture is taken as written and must be finite and lie in [0, 1]")
+    return out
+
+
+def _object_uv(path: str, Uv: Optional[np.ndarray]) -> np.ndarray:
+    """The per-vertex texture coordinates `mesh.read_ply_any` found in `path`; ValueError naming the file when it has none."""
+    if Uv is None:
+        raise ValueError(f"{path}: a texture needs per-vertex texture coordinates ('s t', 'u v' or 'texture_u texture_v' properties), "
+                         f"the file has none")
+    return Uv
+
+
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
-              denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none") -> str:
+              denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
+              object_texture: Optional[str] = None) -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -419,16 +465,20 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     `env_scale`: the envmap is multiplied by it before its tables are built (1: the same bits as without it; 0 with an area light in
     the list: the night shot, lit by the lamp alone).  `object_colors`: "none" (default), "vertex" or "vertex_linear" (`load_oi_scene`'s
     "colors") tints oi2.ply, the diffuse object, with its file's vertex colours; with `objects_file` it is ignored and each entry's
-    "colors" holds.  A file without colours is a ValueError naming it."""
+    "colors" holds.  A file without colours is a ValueError naming it.  `object_texture`: an image (a PNG of display values, or an
+    .exr / .hdr of linear ones in [0, 1]) that textures oi2.ply over its file's per-vertex texture coordinates (DESIGN.md section 1.4,
+    "Textured inserted objects"); with `objects_file` it is ignored and each entry's "texture" and "orm_texture" hold.  A file without
+    coordinates is a ValueError naming it."""
     from . import mesh as _mesh
 
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     if objects_file is not None:
-        have = [(e["ply"], e["bsdf"], e["normals"], e["colors"]) for e in load_oi_scene(objects_file)]
+        have = [(e["ply"], e["bsdf"], e["normals"], e["colors"], e["texture"], e["orm_texture"]) for e in load_oi_scene(objects_file)]
     else:
         plys = [os.path.join(scene_dir, "oi.ply"), os.path.join(scene_dir, "oi2.ply")]
         bsdfs = [{"type": "dielectric", "int_ior": OI_INT_IOR, "ext_ior": OI_EXT_IOR}, {"type": "diffuse", "reflectance": (OI_REFLECTANCE,) * 3}]
-        have = [(p, b, object_normals, c) for p, b, c in zip(plys, bsdfs, ("none", object_colors)) if os.path.exists(p)]
+        have = [(p, b, object_normals, c, t, None) for p, b, c, t in zip(plys, bsdfs, ("none", object_colors), (None, object_texture))
+                if os.path.exists(p)]
         if not have:
             raise FileNotFoundError(f"object insertion needs {plys[0]} (glass) or {plys[1]} (diffuse); neither exists")
     if n_iter < 1:
@@ -441,12 +491,15 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     _scaled_env(np.zeros(0, np.float32), env_scale)
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
-    for p, b, normals, colors in have:
-        if colors == "none":
-            V, T, Nn = _mesh.read_ply_any(p, normals=True)
-        else:
-            V, T, Nn, Cc = _mesh.read_ply_any(p, normals=True, colors=True)
+    for p, b, normals, colors, texture, orm_texture in have:
+        V, T, Nn, Cc, Uv = _mesh.read_ply_any(p, normals=True, colors=True, uv=True)
         objects.append({"vertices": V, "triangles": T, "bsdf": b})
+        if texture is not None or orm_texture is not None:
+            objects[-1]["uv"] = _object_uv(p, Uv)
+        if texture is not None:
+            objects[-1]["texture"] = _object_image(texture, decode=True)
+        if orm_texture is not None:
+            objects[-1]["orm_texture"] = _object_image(orm_texture, decode=False)
         if colors != "none":
             objects[-1]["colors"] = _object_colors(p, Cc, colors)
         if normals == "vertex":
@@ -458,7 +511,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     if atrous:
         geom = pt.features()
         half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs)
-        tint = pt.feature_colors() if pt.stats["n_colored_objects"] else None
+        tint = pt.feature_tints() if pt.stats["n_textured_objects"] else pt.feature_colors() if pt.stats["n_colored_objects"] else None
         img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], [h[1] for h in have], tint))
     else:
         img = torch.zeros_like(mat["albedo"])

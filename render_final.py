@@ -39,6 +39,10 @@ def parse_args(argv=None):
     ap.add_argument("--oi_colors", choices=["none", "vertex", "vertex_linear"], default="none",
                     help="--mode oi without --oi_scene: tint oi2.ply, the diffuse object, with its file's vertex colours (red green blue): vertex = "
                          "decoded from display values to linear; vertex_linear = as written (an --oi_scene entry says \"colors\" itself)")
+    ap.add_argument("--oi_texture", type=str, default=None, metavar="PATH",
+                    help="--mode oi without --oi_scene: texture oi2.ply, the diffuse object, with this image over its file's per-vertex texture "
+                         "coordinates (s t, u v or texture_u texture_v): a PNG holds display values, an .exr or .hdr linear ones in [0, 1] (an "
+                         "--oi_scene entry says \"texture\" and, a pbr one, \"orm_texture\" itself)")
     ap.add_argument("--oi_scene", type=str, default=None, metavar="FILE.json",
                     help='--mode oi: an object list, {"objects": [{"ply": path relative to the file, "bsdf": {"type": "pbr", "albedo": [r, g, b], '
                          '"roughness": r, "metallic": m} (or a "dielectric" or "diffuse" one, or {"type": "roughdielectric", "int_ior": n, "ext_ior": n, "alpha": a}, frosted glass, or {"type": "area", "radiance": [r, g, b]}, a lamp), "normals": "flat" or "vertex"}, ...]}, at most 8 '
@@ -78,7 +82,7 @@ def main(argv=None):
     elif a.mode == "oi":
         print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
                                                  object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene,
-                                                 env_scale=a.env_scale, object_colors=a.oi_colors))
+                                                 env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture))
     else:
         raise ValueError("Invalid mode")
 
