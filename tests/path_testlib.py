@@ -101,6 +101,14 @@ def groove_with_objects(pt, objects, merged):
     return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "H": H, "W": W, "objects": objects, "V": V, "T": T, "table": table, "tracer": tracer}
 
 
+def recorded_walk(entry):
+    """What the walk that `path_objects_fp64.replay_objects` replaced returned for `entry` ("smooth", "pbr", "lights", "texture") on
+    its own table scene over the groove at 12 x 10, max_depth 6, seed 1, recorded before the copies were folded into one
+    (tests/golden/gen_path_replay_chain.py) -> {"L": the render, key: each array of its record}."""
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "path_replay_chain.npz")) as z:
+        return {k.split(".", 1)[1]: z[k] for k in z.files if k.startswith(entry + ".")}
+
+
 def synthetic_output(tmp, name="case", H=32, W=32, edit=False):
     """An output directory of the pipeline as the command lines read it, H x W: best_results/ (the groove's maps, a flat normal map,
     the envmap), depthPred.exr and the mesh <name>.ply -> its path.  `edit`: plus best_results/mask.png (a disc) and an RGBA

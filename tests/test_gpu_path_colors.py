@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import path_color_fp64 as pc  # noqa: E402
 import path_fp64 as pf  # noqa: E402
 import path_light_fp64 as pl  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_rough_fp64 as pr  # noqa: E402
@@ -43,7 +44,7 @@ _report = tl.reporter("path color", "test_gpu_path_colors")
 @pytest.fixture(scope="module")
 def scene(pt):
     """The groove at 24 x 20 (a partial tile) with `path_color_fp64.table_scene` in front of it."""
-    s = tl.groove_with_objects(pt, pc.table_scene(), pc.merged)
+    s = tl.groove_with_objects(pt, pc.table_scene(), pob.merged)
     st = s["tracer"].stats
     assert st["n_objects"] == 4 and st["n_colored_objects"] == 2 and st["n_pbr_objects"] == 1 and st["n_smooth_objects"] == 2
     assert s["tracer"].obj_col is not None and not s["tracer"].rough and s["tracer"].lights is None
@@ -64,7 +65,7 @@ def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64, env_on):
         for seed in (0, 1, 2):
             got = s["tracer"].render(s["a"], s["r"], s["m"], env, spp=1, max_depth=max_depth, seed=seed).cpu().numpy().astype(np.float64)
             assert np.isfinite(got).all()
-            ref, rec = pc.replay_color(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], env, tab, H, W, max_depth, seed, s["table"])
+            ref, rec = pob.replay_objects(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], env, tab, H, W, max_depth, seed, s["table"])
             assert rec["colored_camera"][:, 0].any() and rec["colored_camera"][:, 1].any() and rec["colored_indirect"].any()
             if not env_on:                                          # this table holds no light: without the envmap there is no emitter and
                 assert not ref.any() and not got.any()              # parity's denominator is 0; the render is black, exactly

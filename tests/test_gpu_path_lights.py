@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_light_fp64 as pl  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_testlib as tl  # noqa: E402
@@ -43,7 +44,7 @@ _report = tl.reporter("path lights", "test_gpu_path_lights")
 def scene(pt):
     """The groove at 24 x 20 (a partial tile) with `path_light_fp64.table_scene` in front of it: the unequal-sided emitter box, an
     emitter quad, a smooth glass icosphere, a flat PBR cube and a diffuse cube in one table."""
-    s = tl.groove_with_objects(pt, pl.table_scene(), pl.merged)
+    s = tl.groove_with_objects(pt, pl.table_scene(), pob.merged)
     st = s["tracer"].stats
     assert st["n_objects"] == 5 and st["n_lights"] == 2 and st["n_pbr_objects"] == 1 and st["n_smooth_objects"] == 1
     assert s["tracer"].lights is not None
@@ -65,7 +66,7 @@ def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64, env_on):
         for seed in (0, 1, 2):
             got = s["tracer"].render(s["a"], s["r"], s["m"], env, spp=1, max_depth=max_depth, seed=seed).cpu().numpy().astype(np.float64)
             assert np.isfinite(got).all()
-            ref, rec = pl.replay_lights(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], env, tab, H, W, max_depth, seed, s["table"])
+            ref, rec = pob.replay_objects(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], env, tab, H, W, max_depth, seed, s["table"])
             assert rec["n_e"] == 2 + env_on
             frac, err = _parity(got, ref)
             _report(f"per-path parity with lights, envmap {'on' if env_on else 'zero'}, max_depth {max_depth} seed {seed}: share of pixels within 1e-3",
@@ -160,8 +161,8 @@ def test_bits(pt, scene, oracle64):
     assert with_black.stats["n_lights"] == 1 and without.stats["n_lights"] == 0
     got = with_black.render(*maps, spp=1, max_depth=6, seed=3)
     assert bool(torch.isfinite(got).all()) and not np.array_equal(_bits(got), _bits(without.render(*maps, spp=1, max_depth=6, seed=3)))
-    V, T, table = pl.merged(rm["vertices"], rm["triangles"], black)
-    ref64, rec = pl.replay_lights(oracle64, V, T, *maps, pt.env_tables(s["env"]), H, W, 6, 3, table)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], black)
+    ref64, rec = pob.replay_objects(oracle64, V, T, *maps, pt.env_tables(s["env"]), H, W, 6, 3, table)
     frac, err = _parity(got.cpu().numpy().astype(np.float64), ref64)
     _report("a light of radiance 0 beside the envmap, spp 1 max_depth 6: share of pixels within 1e-3", f"{frac:.4f}")
     assert rec["n_e"] == 2 and frac >= 0.99

@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import denoise_fp64 as dn  # noqa: E402
 import path_fp64 as pf  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
@@ -42,7 +43,7 @@ _report = tl.reporter("path oi pbr", "test_gpu_path_oi_pbr")
 def scene(pt):
     """The groove at 24 x 20 (a partial tile) with `path_oi_pbr_fp64.table_scene` in front of it: a smooth metal icosphere, a flat PBR
     cube, a smooth glass icosphere and a flat diffuse cube in one table."""
-    s = tl.groove_with_objects(pt, pp.table_scene(), pp.merged)
+    s = tl.groove_with_objects(pt, pp.table_scene(), pob.merged)
     tracer = s["tracer"]
     assert tracer.stats["n_objects"] == 4 and tracer.stats["n_pbr_objects"] == 2 and tracer.stats["n_smooth_objects"] == 2
     assert tracer.stats["n_object_tris"] == 184 and tracer.pbr is not None
@@ -63,7 +64,7 @@ def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64):
         for seed in (0, 1, 2):
             got = s["tracer"].render(s["a"], s["r"], s["m"], s["env"], spp=1, max_depth=max_depth, seed=seed).cpu().numpy().astype(np.float64)
             assert np.isfinite(got).all()
-            ref, rec = pp.replay_oi(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], s["env"], tab, H, W, max_depth, seed, s["table"])
+            ref, rec = pob.replay_objects(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], s["env"], tab, H, W, max_depth, seed, s["table"])
             frac, err = _parity(got, ref)
             _report(f"per-path parity with PBR objects, max_depth {max_depth} seed {seed}: share of pixels within 1e-3",
                     f"{frac:.4f} ({int((err > 1e-3).sum())} flipped paths, max err {err.max():.3e})")

@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_light_fp64 as pl  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
@@ -45,7 +46,7 @@ _report = tl.reporter("path rough", "test_gpu_path_rough")
 def scene(pt):
     """The groove at 24 x 20 (a partial tile) with `path_rough_fp64.table_scene` in front of it: a smooth-flagged rough-glass
     icosphere (alpha 0.2), a flat rough-glass cube (alpha 0.05) around a small emitter quad, a diffuse cube, a clear-glass icosphere."""
-    s = tl.groove_with_objects(pt, pr.table_scene(), pr.merged)
+    s = tl.groove_with_objects(pt, pr.table_scene(), pob.merged)
     st = s["tracer"].stats
     assert st["n_objects"] == 5 and st["n_rough_objects"] == 2 and st["n_lights"] == 1 and st["n_smooth_objects"] == 2
     assert s["tracer"].rough and s["tracer"].lights is not None
@@ -67,7 +68,7 @@ def test_every_path_matches_the_fp64_restatement(pt, scene, oracle64, env_on):
         for seed in (0, 1, 2):
             got = s["tracer"].render(s["a"], s["r"], s["m"], env, spp=1, max_depth=max_depth, seed=seed).cpu().numpy().astype(np.float64)
             assert np.isfinite(got).all()
-            ref, rec = pr.replay_rough(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], env, tab, H, W, max_depth, seed, s["table"])
+            ref, rec = pob.replay_objects(oracle64, s["V"], s["T"], s["a"], s["r"], s["m"], env, tab, H, W, max_depth, seed, s["table"])
             assert rec["n_e"] == 1 + env_on
             frac, err = _parity(got, ref)
             _report(f"per-path parity with rough glass, envmap {'on' if env_on else 'zero'}, max_depth {max_depth} seed {seed}: share of pixels within 1e-3",
@@ -156,8 +157,8 @@ def test_lamp_inside_the_rough_sphere(pt):
     env = np.zeros((4, 8, 3), np.float32)
     vals = _device_means(pt, objects, env)
     Vs, Ts = pp.FAR_TRIANGLE
-    V, T, table = pr.merged(Vs, Ts, objects)
-    alone = pr.replay_mean(10, 12, 16, SEEDS, 16, V, T, env, pt.env_tables(env), table, emitter_sample=False)
+    V, T, table = pob.merged(Vs, Ts, objects)
+    alone = pob.replay_mean(10, 12, 16, SEEDS, 16, V, T, env, pt.env_tables(env), table, emitter_sample=False)
     assert (vals >= 0).all() and vals[:, inside].max() > 0 and inside.sum() >= 12
     se = np.sqrt(vals.var(0, ddof=1) / vals.shape[0] + alone.var(0, ddof=1) / alone.shape[0])
     excess = (np.abs(vals.mean(0) - alone.mean(0)) / (5 * se + 1e-3 * np.abs(alone.mean(0)) + 1e-300))[inside]

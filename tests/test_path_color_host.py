@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import path_color_fp64 as pc  # noqa: E402
 import path_fp64 as pf  # noqa: E402
 import path_light_fp64 as pl  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
@@ -144,7 +145,7 @@ def test_feature_colors_host_against_the_first_hit(path_lib):
     H, W = 20, 24
     objects = pc.table_scene()
     rm = _groove(H, W)[0]
-    V, T, table = pc.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], objects)
     Vm, Tm, tb, tint = path_lib.merge_objects(rm["vertices"], rm["triangles"], objects, colors=True)
     n_scene = rm["triangles"].shape[0]
     assert [t.kind for t in tb] == [0x302, 0x203, 2, 0x101] and tint.shape == (Tm.shape[0] - n_scene, 3, 3) and tint.dtype == np.float32
@@ -187,9 +188,9 @@ def test_restatement_affine_colours_in_a_furnace(path_lib):
     expected, covered = furnace_expected(objects, H, W)
     assert covered.sum() >= 12                                     # a handful of pixels and more
     Vs, Ts = pp.FAR_TRIANGLE
-    V, T, table = pc.merged(Vs, Ts, objects)
+    V, T, table = pob.merged(Vs, Ts, objects)
     env = np.zeros((4, 8, 3), np.float32)
-    vals = pc.replay_mean(H, W, 16, SEEDS, 2, V, T, env, path_lib.env_tables(env), table)
+    vals = pob.replay_mean(H, W, 16, SEEDS, 2, V, T, env, path_lib.env_tables(env), table)
     ok, excess = pl.within_five_sigma(vals, expected, covered)
     spread = float(expected[covered].max() - expected[covered].min())
     _report(f"affine colours in a furnace: worst |mean - L p rho| / (5 se + 1e-3) over {int(covered.sum())} pixels; the expectation's spread", f"{excess:.3f}; {spread:.3f}")
@@ -212,21 +213,24 @@ def furnace_expected(objects, H, W):
 
 
 # ---- 4: uniform colours ------------------------------------------------------------------------------------------------------------------------
+COLOUR_RECORD = ("colored_camera", "colored_indirect")             # what the record holds of the flags themselves, not of the paths
+
+
 def test_uniform_colours_are_the_uncoloured_object(path_lib, oracle64):
-    """With every corner (1, 1, 1) the restatement equals `path_rough_fp64`'s render of the unflagged table bit for bit."""
+    """With every corner (1, 1, 1) the restatement equals its render of the unflagged table bit for bit."""
     H, W = 20, 24
     rm, a, r, m, env = _groove(H, W)
     tab = path_lib.env_tables(env)
-    V, T, flagged = pc.merged(rm["vertices"], rm["triangles"], pc.table_scene(uniform=True))
-    _, _, plain = pr.merged(rm["vertices"], rm["triangles"], pc.table_scene(flagged=False))
+    V, T, flagged = pob.merged(rm["vertices"], rm["triangles"], pc.table_scene(uniform=True))
+    _, _, plain = pob.merged(rm["vertices"], rm["triangles"], pc.table_scene(flagged=False))
     for max_depth, seed in ((2, 0), (6, 1), (16, 2)):
-        got, rec = pc.replay_color(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, flagged)
-        ref, rec0 = pr.replay_rough(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, plain)
+        got, rec = pob.replay_objects(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, flagged)
+        ref, rec0 = pob.replay_objects(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, plain)
         assert np.array_equal(got, ref) and rec["colored_camera"][:, :2].any(0).all(), (max_depth, seed)
-        assert all(np.array_equal(rec0[k], rec[k]) for k in rec0 if isinstance(rec0[k], np.ndarray))
+        assert all(np.array_equal(rec0[k], rec[k]) for k in rec0 if isinstance(rec0[k], np.ndarray) and k not in COLOUR_RECORD)
     # and the colours do something: the coloured table differs on the coloured objects' pixels
-    _, _, coloured = pc.merged(rm["vertices"], rm["triangles"], pc.table_scene())
-    tinted, rec = pc.replay_color(oracle64, V, T, a, r, m, env, tab, H, W, 16, 2, coloured)
+    _, _, coloured = pob.merged(rm["vertices"], rm["triangles"], pc.table_scene())
+    tinted, rec = pob.replay_objects(oracle64, V, T, a, r, m, env, tab, H, W, 16, 2, coloured)
     on = rec["colored_camera"].any(-1).reshape(H, W)
     assert (np.abs(tinted - ref).max(-1)[on] > 0).mean() > 0.5
 
@@ -242,7 +246,7 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     rm, a, r, m, env = _groove(H, W)
     if not env_on:
         env = np.zeros_like(env)
-    V, T, table = pc.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], objects)
     Vm, Tm, tb = path_lib.merge_objects(rm["vertices"], rm["triangles"], objects)
     bvh = path_lib.build_bvh(Vm, Tm, rm["triangles"].shape[0])
 
@@ -254,8 +258,8 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     for max_depth in (2, 6, 16):
         for seed in (0, 1, 2):
             args = (oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, table)
-            L64, rec = pc.replay_color(*args)
-            L32, _ = pc.replay_color(*args, closest=closest)
+            L64, rec = pob.replay_objects(*args)
+            L32, _ = pob.replay_objects(*args, closest=closest)
             assert rec["colored_camera"][:, 0].any() and rec["colored_camera"][:, 1].any() and rec["colored_indirect"].any(), (max_depth, seed)
             if not env_on:                                          # this table holds no light: without the envmap there is no emitter, the
                 assert not L64.any() and not L32.any()              # criterion's denominator is 0 and both renders are black, exactly

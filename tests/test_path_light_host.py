@@ -1,7 +1,7 @@
 """Host side of emissive inserted objects ("Emissive inserted objects"): the exported symbols, the emitter
 choice, the area sampler and both pdfs the kernel runs (on the CPU), the light tables against fp64 numpy, the C ABI's refusals, the
-fp64 restatement `path_light_fp64.replay_lights` against closed forms (Lambert's polygon formula, the furnace box) and against
-`path_oi_pbr_fp64.replay_oi`, over the library's fp32 traversal, and the routing of `merge_objects` / `load_oi_scene`.  No GPU needed."""
+fp64 restatement `path_objects_fp64.replay_objects` against closed forms (Lambert's polygon formula, the furnace box) and against
+the recorded PBR restatement, over the library's fp32 traversal, and the routing of `merge_objects` / `load_oi_scene`.  No GPU needed."""
 import ctypes
 import json
 import os
@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_light_fp64 as pl  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_testlib as tl  # noqa: E402
@@ -236,8 +237,8 @@ def test_light_tables_against_fp64_and_refusals(path_lib):
 # ---- 3: the restatement against closed forms ----------------------------------------------------------------------------------------------
 def _closed_form(path_lib, objects, env, max_depth, expected, covered, label, H=10, W=12):
     Vs, Ts = pp.FAR_TRIANGLE
-    V, T, table = pl.merged(Vs, Ts, objects)
-    vals = pl.replay_mean(H, W, 16, SEEDS, max_depth, V, T, env, path_lib.env_tables(env), table)
+    V, T, table = pob.merged(Vs, Ts, objects)
+    vals = pob.replay_mean(H, W, 16, SEEDS, max_depth, V, T, env, path_lib.env_tables(env), table, chunk=4)
     ok, worst = pl.within_five_sigma(vals, expected, covered)
     _report(f"{label}: worst |mean - expected| / (5 se + 1e-3 expected) over {int(covered.sum())} pixels", f"{worst:.3f}")
     assert covered.sum() >= 12 and ok, (label, worst)
@@ -265,6 +266,8 @@ def test_restatement_in_the_furnace_box(path_lib, inner, max_depth, env_value):
 
 # ---- 4: routing and bits on the host -------------------------------------------------------------------------------------------------------
 def test_restatement_without_lights_is_the_pbr_restatement(oracle64, path_lib):
+    """On the PBR table the walk returns the bits the PBR restatement returned before the walks were folded into one
+    (`path_testlib.recorded_walk`)."""
     from materialist_amd import mesh
 
     H, W = 10, 12
@@ -272,10 +275,11 @@ def test_restatement_without_lights_is_the_pbr_restatement(oracle64, path_lib):
     rng = np.random.default_rng(11)
     a, r, m = pf.groove_maps(H, W, rng)
     env = pf.groove_env(rng)
-    V, T, table = pp.merged(rm["vertices"], rm["triangles"], pp.table_scene())
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], pp.table_scene())
     args = (oracle64, V, T, a, r, m, env, path_lib.env_tables(env), H, W, 6, 1, table)
-    ref, rec0 = pp.replay_oi(*args)
-    got, rec1 = pl.replay_lights(*args)
+    rec0 = tl.recorded_walk("pbr")
+    ref = rec0["L"]
+    got, rec1 = pob.replay_objects(*args)
     assert np.array_equal(ref, got) and rec1["n_e"] == 1
     assert all(np.array_equal(rec0[k], rec1[k]) for k in ("transmitted", "diffuse_object", "blocked_by_object", "fallback", "pbr_vertex"))
 
@@ -381,7 +385,7 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     a, r, m = pf.groove_maps(H, W, rng)
     env = pf.groove_env(rng) if env_on else np.zeros((8, 16, 3), np.float32)
     objects = pl.table_scene()
-    V, T, table = pl.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], objects)
     Vm, Tm, tb, corner, records, lt = path_lib.merge_objects(rm["vertices"], rm["triangles"], objects, normals=True, pbr=True, lights=True)
     n_scene = rm["triangles"].shape[0]
     assert [t.kind for t in tb] == [4, 4, 0x101, 3, 2] and lt["header"].n_lights == 2
@@ -396,8 +400,8 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     for max_depth in (2, 6, 16):
         for seed in (0, 1, 2):
             args = (oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, table)
-            L64, rec = pl.replay_lights(*args)
-            L32, _ = pl.replay_lights(*args, closest=closest)
+            L64, rec = pob.replay_objects(*args)
+            L32, _ = pob.replay_objects(*args, closest=closest)
             assert rec["n_e"] == 2 + env_on
             err = (np.abs(L32 - L64) / np.maximum(np.abs(L64), np.abs(L64).mean())).max(-1)
             assert int((err > 1e-3).sum()) == 0, (max_depth, seed, np.argwhere(err > 1e-3)[:10])

@@ -17,6 +17,7 @@ if ROOT not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
@@ -210,15 +211,17 @@ def test_a_flat_pbr_quad_is_the_depth_mesh_with_constant_maps(oracle64, path_lib
     env = pf.groove_env(np.random.default_rng(5))
     tab = path_lib.env_tables(env)
     Vs, Ts = pp.FAR_TRIANGLE
-    V, T, table = pp.merged(Vs, Ts, [{"vertices": Vq, "triangles": Tq, "bsdf": dict(const, type="pbr")}])
+    V, T, table = pob.merged(Vs, Ts, [{"vertices": Vq, "triangles": Tq, "bsdf": dict(const, type="pbr")}])
     for seed in (0, 1, 2):
         ref, _ = pf.replay(oracle64, Vq, Tq, a, r, m, env, tab, H, W, max_depth, seed)
-        got, rec = pp.replay_oi(oracle64, V, T, np.zeros_like(a), np.ones_like(r), np.ones_like(m), env, tab, H, W, max_depth, seed, table)
+        got, rec = pob.replay_objects(oracle64, V, T, np.zeros_like(a), np.ones_like(r), np.ones_like(m), env, tab, H, W, max_depth, seed, table)
         assert rec["pbr_vertex"].all() and not rec["pbr_smooth_vertex"].any() and not rec["fallback"].any()
         assert ref.any() and np.array_equal(got, ref), (max_depth, seed, np.abs(got - ref).max())
 
 
 def test_restatement_without_pbr_objects_is_the_smooth_restatement(oracle64, path_lib):
+    """On the smooth table the walk returns the bits the smooth restatement returned before the walks were folded into one
+    (`path_testlib.recorded_walk`)."""
     from materialist_amd import mesh
 
     H, W = 10, 12
@@ -226,10 +229,11 @@ def test_restatement_without_pbr_objects_is_the_smooth_restatement(oracle64, pat
     rng = np.random.default_rng(11)
     a, r, m = pf.groove_maps(H, W, rng)
     env = pf.groove_env(rng)
-    V, T, table = ps.merged(rm["vertices"], rm["triangles"], ps.table_scene())
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], ps.table_scene())
     args = (oracle64, V, T, a, r, m, env, path_lib.env_tables(env), H, W, 6, 1, table)
-    ref, rec0 = ps.replay_oi(*args)
-    got, rec1 = pp.replay_oi(*args)
+    rec0 = tl.recorded_walk("smooth")
+    ref = rec0["L"]
+    got, rec1 = pob.replay_objects(*args)
     assert np.array_equal(ref, got) and not rec1["pbr_vertex"].any()
     assert all(np.array_equal(rec0[k], rec1[k]) for k in ("transmitted", "diffuse_object", "blocked_by_object", "redo", "fallback"))
 
@@ -246,7 +250,7 @@ def table(path_lib):
     a, r, m = pf.groove_maps(H, W, rng)
     env = pf.groove_env(rng)
     objects = pp.table_scene()
-    V, T, tab = pp.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, tab = pob.merged(rm["vertices"], rm["triangles"], objects)
     return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "tab": path_lib.env_tables(env), "H": H, "W": W, "objects": objects, "V": V, "T": T,
             "table": tab}
 
@@ -277,8 +281,8 @@ def test_restatement_over_fp32_and_fp64_traversal(table, path_lib, oracle64):
     for max_depth in (6, 16):
         for seed in (0, 1, 2):
             args = (oracle64, g["V"], g["T"], g["a"], g["r"], g["m"], g["env"], g["tab"], g["H"], g["W"], max_depth, seed, g["table"])
-            L64, rec = pp.replay_oi(*args)
-            L32, _ = pp.replay_oi(*args, closest=closest, occluded=occluded)
+            L64, rec = pob.replay_objects(*args)
+            L32, _ = pob.replay_objects(*args, closest=closest, occluded=occluded)
             err = (np.abs(L32 - L64) / np.maximum(np.abs(L64), np.abs(L64).mean())).max(-1)
             differ.append(int((err > 1e-3).sum()))
             assert differ[-1] <= 0.01 * g["H"] * g["W"], (max_depth, seed, differ[-1])

@@ -15,6 +15,7 @@ if ROOT not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
 import path_testlib as tl  # noqa: E402
@@ -396,7 +397,7 @@ def table(path_lib):
     a, r, m = pf.groove_maps(H, W, rng)
     env = pf.groove_env(rng)
     objects = ps.table_scene()
-    V, T, tab = ps.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, tab = pob.merged(rm["vertices"], rm["triangles"], objects)
     return {"rm": rm, "a": a, "r": r, "m": m, "env": env, "tab": path_lib.env_tables(env), "H": H, "W": W, "objects": objects, "V": V, "T": T,
             "table": tab}
 
@@ -408,7 +409,7 @@ def test_restatement_without_normals_is_the_flat_restatement(table, oracle64):
     for seed, depth in ((0, 6), (4, 16)):
         args = (oracle64, V, T, g["a"], g["r"], g["m"], g["env"], g["tab"], g["H"], g["W"], depth, seed, tab)
         ref, rec0 = po.replay_oi(*args)
-        got, rec1 = ps.replay_oi(*args)
+        got, rec1 = pob.replay_objects(*args)
         assert np.array_equal(ref, got)
         assert all(np.array_equal(rec0[k], rec1[k]) for k in ("transmitted", "diffuse_object", "blocked_by_object"))
         assert not any(rec1[k].any() for k in ("smooth_transmitted", "smooth_diffuse", "redo", "fallback"))
@@ -437,8 +438,8 @@ def test_restatement_over_fp32_and_fp64_traversal(table, path_lib, oracle64):
     for max_depth in (6, 16):
         for seed in (0, 1, 2):
             args = (oracle64, g["V"], g["T"], g["a"], g["r"], g["m"], g["env"], g["tab"], g["H"], g["W"], max_depth, seed, g["table"])
-            L64, rec = ps.replay_oi(*args)
-            L32, _ = ps.replay_oi(*args, closest=closest, occluded=occluded)
+            L64, rec = pob.replay_objects(*args)
+            L32, _ = pob.replay_objects(*args, closest=closest, occluded=occluded)
             err = (np.abs(L32 - L64) / np.maximum(np.abs(L64), np.abs(L64).mean())).max(-1)
             differ.append(int((err > 1e-3).sum()))
             assert differ[-1] <= 0.01 * g["H"] * g["W"], (max_depth, seed, differ[-1])

@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import path_fp64 as pf  # noqa: E402
 import path_light_fp64 as pl  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
@@ -275,8 +276,8 @@ def test_pdf_integrates_and_samples_follow_it(alpha, ior, cos_o):
 # ---- 4: in expectation ---------------------------------------------------------------------------------------------------------------------
 def _means(path_lib, objects, env, **kw):
     Vs, Ts = pp.FAR_TRIANGLE
-    V, T, table = pr.merged(Vs, Ts, objects)
-    return pr.replay_mean(10, 12, 16, SEEDS, 16, V, T, env, path_lib.env_tables(env), table, **kw)
+    V, T, table = pob.merged(Vs, Ts, objects)
+    return pob.replay_mean(10, 12, 16, SEEDS, 16, V, T, env, path_lib.env_tables(env), table, **kw)
 
 
 def test_rough_sphere_in_a_constant_envmap(path_lib):
@@ -331,7 +332,7 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     rm, a, r, m, env = _groove(path_lib, H, W, objects)
     if not env_on:
         env = np.zeros_like(env)
-    V, T, table = pr.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], objects)
     Vm, Tm, tb, corner, records, lt = path_lib.merge_objects(rm["vertices"], rm["triangles"], objects, normals=True, pbr=True, lights=True)
     n_scene = rm["triangles"].shape[0]
     assert [t.kind for t in tb] == [0x105, 5, 4, 2, 0x101] and lt["header"].n_lights == 1
@@ -347,8 +348,8 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     for max_depth in (2, 6, 16):
         for seed in (0, 1, 2):
             args = (oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, table)
-            L64, rec = pr.replay_rough(*args)
-            L32, _ = pr.replay_rough(*args, closest=closest)
+            L64, rec = pob.replay_objects(*args)
+            L32, _ = pob.replay_objects(*args, closest=closest)
             assert rec["n_e"] == 1 + env_on
             err = (np.abs(L32 - L64) / np.maximum(np.abs(L64), np.abs(L64).mean())).max(-1)
             assert int((err > 1e-3).sum()) == 0, (max_depth, seed, np.argwhere(err > 1e-3)[:10])
@@ -359,14 +360,17 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
 
 
 def test_restatement_without_rough_objects_is_the_lights_restatement(oracle64, path_lib):
+    """On the lights table the walk returns the bits the lights restatement returned before the walks were folded into one
+    (`path_testlib.recorded_walk`), in the render and in every array of its record."""
     H, W = 10, 12
     rm, a, r, m, env = _groove(path_lib, H, W, None)
-    V, T, table = pl.merged(rm["vertices"], rm["triangles"], pl.table_scene())
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], pl.table_scene())
     args = (oracle64, V, T, a, r, m, env, path_lib.env_tables(env), H, W, 6, 1, table)
-    ref, rec0 = pl.replay_lights(*args)
-    got, rec1 = pr.replay_rough(*args)
+    rec0 = tl.recorded_walk("lights")
+    ref = rec0.pop("L")
+    got, rec1 = pob.replay_objects(*args)
     assert np.array_equal(ref, got) and rec1["n_e"] == 3
-    assert all(np.array_equal(rec0[k], rec1[k]) for k in rec0 if isinstance(rec0[k], np.ndarray))
+    assert len(rec0) == 12 and all(np.array_equal(rec0[k], rec1[k]) for k in rec0)
     assert not any(rec1[k].any() for k in pr.RECORD_KEYS)
 
 

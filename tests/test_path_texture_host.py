@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import path_color_fp64 as pc  # noqa: E402
 import path_fp64 as pf  # noqa: E402
 import path_light_fp64 as pl  # noqa: E402
+import path_objects_fp64 as pob  # noqa: E402
 import path_oi_fp64 as po  # noqa: E402
 import path_oi_pbr_fp64 as pp  # noqa: E402
 import path_oi_smooth_fp64 as ps  # noqa: E402
@@ -245,7 +246,7 @@ def test_feature_tints_host_against_the_first_hit(path_lib):
     H, W = 20, 24
     objects = px.table_scene()
     rm = _groove(H, W)[0]
-    V, T, table = px.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], objects)
     Vm, Tm, tb, tint, tex = path_lib.merge_objects(rm["vertices"], rm["triangles"], objects, colors=True, textures=True)
     n_scene = rm["triangles"].shape[0]
     assert [t.kind for t in tb] == [0x502, 0x403, 0x602, 2, 0x101]
@@ -318,13 +319,13 @@ def test_restatement_affine_texels_in_a_furnace(path_lib):
     st = px.furnace_st(q)
     assert np.abs(px.texture_fetch(px.furnace_texels(), st[:, 0], st[:, 1])[0] - px.furnace_value(st[:, 0], st[:, 1])).max() < 1e-6
     Vs, Ts = pp.FAR_TRIANGLE
-    V, T, table = px.merged(Vs, Ts, objects)
+    V, T, table = pob.merged(Vs, Ts, objects)
     # the library's tables of this scene are the restatement's: the quad's coordinates per corner and its 20 texels
     obj_uv, recs, texels = path_lib.merge_objects(Vs, Ts, objects, textures=True)[3]
     assert (recs[1].base_first, recs[1].base_w, recs[1].base_h, recs[1].orm_w) == (0, w, h, 0) and recs[0].base_w == 0
     assert np.array_equal(obj_uv[12:], table[1]["corner_uv"].astype(np.float32)) and np.array_equal(texels[:, :3].reshape(h, w, 3), table[1]["texture"].astype(np.float32))
     env = np.zeros((4, 8, 3), np.float32)
-    vals = px.replay_mean(H, W, 16, SEEDS, 2, V, T, env, path_lib.env_tables(env), table)
+    vals = pob.replay_mean(H, W, 16, SEEDS, 2, V, T, env, path_lib.env_tables(env), table)
     ok, excess = pl.within_five_sigma(vals, expected, covered)
     spread = float(expected[covered].max() - expected[covered].min())
     _report(f"affine texels in a furnace: worst |mean - L p T| / (5 se + 1e-3) over {int(covered.sum())} pixels; the expectation's spread", f"{excess:.3f}; {spread:.3f}")
@@ -332,24 +333,41 @@ def test_restatement_affine_texels_in_a_furnace(path_lib):
 
 
 # ---- uniform images -----------------------------------------------------------------------------------------------------------------------------
+# what the record holds of the flags and the fetches themselves, not of the paths
+TEXTURE_RECORD = ("textured_camera", "textured_indirect", "fetch_wraps_columns", "fetch_wraps_rows", "orm_roughness_floor")
+
+
 def test_uniform_images_are_the_untextured_object(path_lib, oracle64):
-    """With every image (1, 1, 1) the restatement equals `path_color_fp64`'s render of the unflagged table bit for bit."""
+    """With every image (1, 1, 1) the restatement equals its render of the unflagged table bit for bit."""
     H, W = 20, 24
     rm, a, r, m, env = _groove(H, W)
     tab = path_lib.env_tables(env)
-    V, T, flagged = px.merged(rm["vertices"], rm["triangles"], px.table_scene(uniform=True))
+    V, T, flagged = pob.merged(rm["vertices"], rm["triangles"], px.table_scene(uniform=True))
     lib_tex = path_lib.merge_objects(rm["vertices"], rm["triangles"], px.table_scene(uniform=True), textures=True)[3]
     assert np.all(lib_tex[2][:, :3] == 1.0) and np.all(lib_tex[2][:, 3] == 0.0) and lib_tex[2].shape[0] == 36   # the library's texels of this table: ones
-    _, _, plain = pc.merged(rm["vertices"], rm["triangles"], px.table_scene(flagged=False))
+    _, _, plain = pob.merged(rm["vertices"], rm["triangles"], px.table_scene(flagged=False))
     for max_depth, seed in ((2, 0), (6, 1), (16, 2)):
-        got, rec = px.replay_texture(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, flagged)
-        ref, rec0 = pc.replay_color(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, plain)
+        got, rec = pob.replay_objects(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, flagged)
+        ref, rec0 = pob.replay_objects(oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, plain)
         assert np.array_equal(got, ref) and rec["textured_camera"][:, :3].any(0).all(), (max_depth, seed)
-        assert all(np.array_equal(rec0[k], rec[k]) for k in rec0 if isinstance(rec0[k], np.ndarray))
-    _, _, textured = px.merged(rm["vertices"], rm["triangles"], px.table_scene())
-    tinted, rec = px.replay_texture(oracle64, V, T, a, r, m, env, tab, H, W, 16, 2, textured)
+        assert all(np.array_equal(rec0[k], rec[k]) for k in rec0 if isinstance(rec0[k], np.ndarray) and k not in TEXTURE_RECORD)
+    _, _, textured = pob.merged(rm["vertices"], rm["triangles"], px.table_scene())
+    tinted, rec = pob.replay_objects(oracle64, V, T, a, r, m, env, tab, H, W, 16, 2, textured)
     on = rec["textured_camera"].any(-1).reshape(H, W)
     assert (np.abs(tinted - ref).max(-1)[on] > 0).mean() > 0.5
+
+
+def test_restatement_is_the_recorded_texture_restatement(path_lib, oracle64):
+    """On the textured table (the groove at 12 x 10, max_depth 6, seed 1) the walk returns the bits the texture restatement returned
+    before the walks were folded into one (`path_testlib.recorded_walk`), in the render and in every array of its record."""
+    H, W = 10, 12
+    rm, a, r, m, env = _groove(H, W)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], px.table_scene())
+    rec0 = tl.recorded_walk("texture")
+    ref = rec0.pop("L")
+    got, rec = pob.replay_objects(oracle64, V, T, a, r, m, env, path_lib.env_tables(env), H, W, 6, 1, table)
+    assert ref.any() and np.array_equal(ref, got)
+    assert len(rec0) == 25 and all(np.array_equal(rec0[k], rec[k]) for k in rec0)
 
 
 # ---- (g): traversal agreement --------------------------------------------------------------------------------------------------------------------
@@ -366,7 +384,7 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     rm, a, r, m, env = _groove(H, W)
     if not env_on:
         env = np.zeros_like(env)
-    V, T, table = px.merged(rm["vertices"], rm["triangles"], objects)
+    V, T, table = pob.merged(rm["vertices"], rm["triangles"], objects)
     Vm, Tm, tb, tex = path_lib.merge_objects(rm["vertices"], rm["triangles"], objects, textures=True)
     assert tex is not None and [t.kind & path_lib.OBJECT_TEXTURED for t in tb] == [0x400, 0x400, 0x400, 0, 0]
     bvh = path_lib.build_bvh(Vm, Tm, rm["triangles"].shape[0])
@@ -379,8 +397,8 @@ def test_restatement_over_fp32_and_fp64_traversal(path_lib, oracle64, env_on):
     for max_depth in (2, 6, 16):
         for seed in (0, 1, 2):
             args = (oracle64, V, T, a, r, m, env, tab, H, W, max_depth, seed, table)
-            L64, rec = px.replay_texture(*args)
-            L32, _ = px.replay_texture(*args, closest=closest)
+            L64, rec = pob.replay_objects(*args)
+            L32, _ = pob.replay_objects(*args, closest=closest)
             assert rec["textured_camera"][:, :3].any(0).all() and all(rec[e].any() for e in EVENTS), (max_depth, seed, {e: int(rec[e].sum()) for e in EVENTS})
             if not env_on:                                          # this table holds no light: without the envmap there is no emitter, the
                 assert not L64.any() and not L32.any()              # criterion's denominator is 0 and both renders are black, exactly
