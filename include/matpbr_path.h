@@ -378,6 +378,42 @@ int matpbr_path_feature_tints_host(const void* nodes, const void* tris, int H, i
                                    int n_objects, long n_scene_tri, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
                                    const void* texels, long n_texels, float* out);
 
+/* The differential render ("Differential render"; Debevec 1998), forward only: what the inserted objects add to
+ * and take from a photograph of the scene.  Arguments: matpbr_path_render_objects_textures' without `out`, the table checked as that
+ * entry point checks it (level 7), then three sums and a count (DEVICE).  Per pixel and sample s of spp, with that render's random
+ * numbers: c_s = 1 where the camera ray's closest hit is an inserted triangle (id >= n_scene_tri), else 0; L_with,s is the sample's
+ * radiance as matpbr_path_render_objects_textures computes it; L_without,s is the same sample walked again from the camera ray with
+ * every triangle of id >= n_scene_tri skipped by every traversal and the envmap as the only emitter.  The second walk runs only for a
+ * sample with c_s = 0 that is touched: the table holds an object of kind 4, or a closest-hit or a shadow traversal of the first walk
+ * returned an inserted triangle.  Outputs, each a mean over spp: fg[H,W,3] = c_s L_with,s; delta[H,W,3] = L_with,s - L_without,s over
+ * the samples walked twice (an untouched sample adds nothing: delta is exactly 0 where none was); alpha[H,W] = c_s.  rewalked[H,W]
+ * (nullable) has the number of second walks ADDED to it, as `rays` has the rays of both walks.  Every split into launches gives the
+ * same bits.  Invalid arguments, besides that entry point's: n_objects == 0, fg, delta or alpha NULL. */
+int matpbr_path_render_objects_diff(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                    float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                    int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                    const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                    const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                    const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                    const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked);
+
+/* The differential render composited into the photograph: out[H,W,3] = max(0, (fg_sum + delta_sum) scale + (1 - alpha_sum scale) photo)
+ * per channel, where the sums are matpbr_path_render_objects_diff's outputs added over some frames and scale = 1 / (their number).
+ * Every product and sum is rounded on its own: where fg, delta and alpha are 0 the photograph comes through bit for bit (a photo >= 0),
+ * and the CPU twin gives the same bits.  DEVICE pointers.  Invalid: a NULL pointer, H or W <= 0, scale not finite or <= 0. */
+int matpbr_path_composite(const float* fg_sum, const float* delta_sum, const float* alpha_sum, const float* photo, int H, int W, float scale,
+                          float* out, void* stream);
+/* matpbr_path_composite on the CPU with the routine the kernel runs (every pointer HOST). */
+int matpbr_path_composite_host(const float* fg_sum, const float* delta_sum, const float* alpha_sum, const float* photo, int H, int W, float scale,
+                               float* out);
+
+/* matpbr_path_trace_host over the triangles of id < n_scene_tri alone (the differential render's second walk): a triangle of a larger
+ * id is skipped before its test.  any == 0: closest hit; any == 1: the shadow rays' traversal, which returns the first triangle it
+ * finds (t_hit is then that triangle's distance, not the closest).  With n_scene_tri >= the mesh's triangle count and any == 0 it is
+ * matpbr_path_trace_host, bit for bit.  Invalid, besides that entry point's: n_scene_tri < 0, any outside {0, 1}. */
+int matpbr_path_trace_scene_host(const void* nodes, const void* tris, const float* o, const float* d, long N, float tmin, float tmax,
+                                 float* t_hit, int32_t* tri_hit, long n_scene_tri, int any);
+
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;
  * `edit` is HOST memory, copied before the call returns.  Where the texel a vertex reads is masked, the BSDF is the glass of

@@ -10,10 +10,12 @@
 // One translation unit: this file holds PathArgs, the forward kernel, the backward kernels and the C ABI; path_bvh.hpp the BVH, its
 // traversals and the host builder; path_shading.hpp the RNG, the envmap sampler and the BSDF wrappers; path_objects.hpp the tables the
 // kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
-// path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser.
+// path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser; path_diff.hpp the differential render's table
+// and the composite.
 #include <type_traits>
 
 #include "path_denoise.hpp"
+#include "path_diff.hpp"
 
 namespace {
 
@@ -33,6 +35,10 @@ struct PathArgs {
 // spawn offset along the (camera-side) face normal, relative to the point's magnitude
 __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1.0f + fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]))); }
 
+// (DiffObjects) the id from which the traversals skip triangles: none in a sample's first trip, the inserted ones in its second
+template <class Objects> __device__ __forceinline__ int id_limit_of(const Objects&, bool) { return 0; }
+__device__ __forceinline__ int id_limit_of(const DiffObjects& ot, bool second) { return second ? ot.n_scene_tri : INT32_MAX; }
+
 // samples [s0, s1) of every pixel added to out (first: start from 0; last: divide by spp).  OBJ: the BVH holds inserted objects
 // (Objects = ObjTable, passed by value); EDIT: transparency editing (Objects = TransEdit, by value in the table's place).  With
 // NoObjects every `if (OBJ ...)`, `if (EDIT ...)` and `if (NRM ...)` below folds away and the walk is the depth mesh's alone, the code
@@ -49,10 +55,16 @@ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1
 // from the triangle's corners; every `if (COLOR ...)` folds away in the other eight.  TEX: COLOR with UV-textured objects (Objects =
 // TexObjects): at a vertex of a flagged object the reflectance or the albedo is multiplied by a base-colour image, a PBR object's
 // roughness and metallic by an orm image, at the coordinate interpolated from the triangle's corners; every `if (TEX ...)` folds away in
-// the other nine.
+// the other nine.  DIFF: TEX as the differential render walks it (Objects = DiffObjects; DESIGN.md section 1.4, "Differential render"):
+// a sample takes up to two trips through the sample loop's body, the same statements.  Trip 0 is TEX's walk; it records whether the camera
+// ray landed on an inserted triangle (`cov`) and whether any trace returned one (`touched`; a light in the table touches every
+// sample).  Trip 1 runs where touched && !cov: the same sample from the camera ray on, with every triangle of id >= n_scene_tri skipped
+// and the envmap as the only emitter.  The sums live in the table's buffers between samples, not in registers.  Every `if (DIFF ...)`
+// folds away in the other ten.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool TEX = std::is_same<Objects, TexObjects>::value;
+    constexpr bool DIFF = std::is_same<Objects, DiffObjects>::value;
+    constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF;
     constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
     constexpr bool LIGHT = std::is_same<Objects, LightObjects>::value || ROUGH;
@@ -70,16 +82,34 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     const bool have_tab = q.row_cdf[q.He] > 0.0f;   // an envmap of zero luminance has no emitter sampling
     int n_e = 1;   // (LIGHT) the emitters: the envmap where it has tables, then the lights
     if constexpr (LIGHT) n_e = (have_tab ? 1 : 0) + ot.lt.n;
-    const float n_ef = (float)n_e;
+    float n_ef = (float)n_e;
     float acc[3] = {0.0f, 0.0f, 0.0f};
-    if (!first) {
+    if constexpr (DIFF) {
+        if (first) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ot.fg[3 * pix + c] = ot.delta[3 * pix + c] = 0.0f;
+            ot.alpha[pix] = 0.0f;
+        }
+    } else if (!first) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[c] = q.out[3 * pix + c];
     }
     const uint32_t pix_hash = pcg_hash(q.seed_hash + (uint32_t)pix);
     uint32_t n_rays = 0;
+    // (DIFF) a sample takes up to two trips through the loop's body: trip 1 (`second`) repeats the iteration of `s` that trip 0 asked it for
+    bool second = false;
+    bool cov = false, touched = false;      // trip 0's record
+    float Lw[3] = {0.0f, 0.0f, 0.0f};       // trip 0's radiance, kept across trip 1
     for (int s = s0; s < s1; ++s) {
         const uint32_t base = pcg_hash(pix_hash + (uint32_t)s);
+        if constexpr (DIFF) {
+            if (!second) {
+                cov = false;
+                touched = ot.lt.n > 0;   // a light changes n_e, and through it every emitter sample
+            }
+            n_e = (have_tab ? 1 : 0) + (second ? 0 : ot.lt.n);   // trip 1: the envmap alone
+            n_ef = (float)n_e;
+        }
         float L[3] = {0.0f, 0.0f, 0.0f}, thr[3] = {1.0f, 1.0f, 1.0f};
         // camera ray through a uniformly jittered position of the pixel (box filter)
         const float x = (float)j - 0.5f + rng_u(base, 0, 0), y = (float)i - 0.5f + rng_u(base, 0, 1);
@@ -94,7 +124,14 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
         for (int depth = 0;; ++depth) {
             float t = FLT_MAX;
             ++n_rays;
-            const int k = trace<false>(q.nodes, q.tris, o, d, 0.0f, t, stk);
+            // (DIFF) the traversals skip the triangles from an id on: none in trip 0, the inserted ones in trip 1
+            const int k = trace<false, DIFF>(q.nodes, q.tris, o, d, 0.0f, t, stk, id_limit_of(ot, second));
+            if constexpr (DIFF) {
+                if (k >= 0 && tri_id(q.tris[3 * k]) >= ot.n_scene_tri) {   // trip 0 alone can meet one
+                    touched = true;
+                    if (depth == 0) cov = true;
+                }
+            }
             if (k < 0) {   // escaped: the envmap, MIS-weighted against emitter sampling after a BSDF sample
                 const int tx = env_texel(d, q.He, q.We);
                 const float w = depth == 0 || (OBJ && prev_delta)
@@ -307,7 +344,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                     if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
                         float ts = LIGHT ? ts_max : FLT_MAX;
                         ++n_rays;
-                        if (trace<true>(q.nodes, q.tris, po, wl, 0.0f, ts, stk) < 0) {
+                        const int ks = trace<true, DIFF>(q.nodes, q.tris, po, wl, 0.0f, ts, stk, id_limit_of(ot, second));   // the occluder
+                        if constexpr (DIFF) {
+                            if (ks >= 0 && tri_id(q.tris[3 * ks]) >= ot.n_scene_tri) touched = true;
+                        }
+                        if (ks < 0) {
                             const float w = mis_weight(pdf_e, pdf_b) / pdf_e;
 #pragma unroll
                             for (int c = 0; c < 3; ++c) L[c] += thr[c] * (f[c] * ((LIGHT ? Le[c] : q.env[3 * te + c]) * w));
@@ -355,12 +396,45 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
 #pragma unroll
             for (int c = 0; c < 3; ++c) { o[c] = po[c]; d[c] = wi[c]; }
         }
+        if constexpr (DIFF) {
+            if (!second) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += L[c];
+                for (int c = 0; c < 3; ++c) Lw[c] = L[c];
+                if (touched && !cov) {   // the same s once more
+                    second = true;
+                    --s;
+                    continue;
+                }
+            }
+            if (cov) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ot.fg[3 * pix + c] += Lw[c];
+                ot.alpha[pix] += 1.0f;
+            } else if (second) {   // an untouched sample adds nothing: no subtraction
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ot.delta[3 * pix + c] += Lw[c] - L[c];
+                if (ot.rewalked) ot.rewalked[pix] += 1u;
+            }
+            second = false;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += L[c];
+        }
     }
     const float sc = last ? 1.0f / (float)q.spp : 1.0f;
+    if constexpr (DIFF) {
+        if (last) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) q.out[3 * pix + c] = last ? acc[c] * sc : acc[c];
+            for (int c = 0; c < 3; ++c) {
+                ot.fg[3 * pix + c] *= sc;
+                ot.delta[3 * pix + c] *= sc;
+            }
+            ot.alpha[pix] *= sc;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q.out[3 * pix + c] = last ? acc[c] * sc : acc[c];
+    }
     if (q.rays) q.rays[pix] += n_rays;
 }
 // ---- backward pass ("Gradients") ------------------------------------------------------------------------
@@ -762,6 +836,23 @@ int launch_frame(const Frame& f, const PathArgs& q, const Table& table) {
     return MATPBR_PATH_OK;
 }
 
+// the widest table over what `s` holds: a member the scene does not have stays zero, and a kernel that takes a narrower table is
+// handed its part
+TexObjects tex_objects(const Scene& s) {
+    TexObjects ro{};
+    ro.t = s.ot;
+    ro.nrm = s.obj_nrm;
+    ro.n_scene_tri = s.n_scene_tri;
+    for (int k = 0; s.pbr && k < s.ot.n; ++k) ro.pbr[k] = s.pbr[k];
+    ro.lt = s.lt;
+    ro.col = s.obj_col;
+    ro.uv = s.obj_uv;
+    ro.texels = s.texels;
+    for (int k = 0; s.tex && k < s.ot.n; ++k)   // a record is copied where its object carries the flag: the others stay zero
+        if (s.ot.o[k].kind & MATPBR_PATH_OBJECT_TEXTURED) ro.tex[k] = s.tex[k];
+    return ro;
+}
+
 int render_common(const Frame& f, const Scene& s) {
     PathArgs q{};
     if (!f.out || !frame_args(f, q)) return MATPBR_PATH_ERR_INVALID_ARG;
@@ -773,21 +864,9 @@ int render_common(const Frame& f, const Scene& s) {
         case Kernel::ShadeNormals: return launch_frame(f, q, ShadeNormals{s.nrm});
         default: break;
     }
-    TexObjects ro{};   // the five kernels whose tables extend one another
-    ro.t = s.ot;
-    ro.nrm = s.obj_nrm;
-    ro.n_scene_tri = s.n_scene_tri;
-    for (int k = 0; s.pbr && k < s.ot.n; ++k) ro.pbr[k] = s.pbr[k];
+    const TexObjects ro = tex_objects(s);   // the five kernels whose tables extend one another
     if (s.kernel == Kernel::PbrObjects) return launch_frame<PbrObjects>(f, q, ro);
-    ro.lt = s.lt;
-    ro.col = s.obj_col;
-    if (s.kernel == Kernel::TexObjects) {   // a record is copied where its object carries the flag: the others stay zero
-        ro.uv = s.obj_uv;
-        ro.texels = s.texels;
-        for (int k = 0; k < s.ot.n; ++k)
-            if (s.ot.o[k].kind & MATPBR_PATH_OBJECT_TEXTURED) ro.tex[k] = s.tex[k];
-        return launch_frame(f, q, ro);
-    }
+    if (s.kernel == Kernel::TexObjects) return launch_frame(f, q, ro);
     return s.kernel == Kernel::LightObjects ? launch_frame<LightObjects>(f, q, ro) :
            s.kernel == Kernel::RoughObjects ? launch_frame<RoughObjects>(f, q, ro) : launch_frame<ColorObjects>(f, q, ro);
 }
@@ -822,18 +901,16 @@ bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept
 // the arguments it does not have; level 1's n_scene_tri = 0 lies below every range.  An argument is consulted only where the table needs
 // it: obj_nrm where an object is smooth, pbr where one is of kind 3, the light header and buffers where one is of kind 4.  The counts
 // alone choose the kernel.
-int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+bool objects_scene(int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                    const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
-                   const float* obj_col = nullptr, const float* obj_uv = nullptr, const MatpbrPathObjectTex* tex = nullptr,
-                   const void* texels = nullptr, long n_texels = 0) {
+                   const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex, const void* texels, long n_texels, Scene& s) {
     const unsigned accept = (level >= 2 ? kAcceptSmooth : 0u) | (level >= 3 ? kAcceptPbr : 0u) | (level >= 4 ? kAcceptLight : 0u) |
                             (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u) | (level >= 7 ? kAcceptTexture : 0u);
-    Scene s;
     ObjCounts n;
     if (!scene_table(objects, n_objects, accept, obj_nrm, n_scene_tri, pbr, s.ot, n) || (n.pbr > 0 && !pbr) || (n.color > 0 && !obj_col) ||
         (n.light > 0 && !light_table(lights, &s.ot, light_tris, light_cdf, s.lt)) ||
         (n.tex > 0 && !textures_valid(objects, n_objects, obj_uv, tex, texels, n_texels)))
-        return MATPBR_PATH_ERR_INVALID_ARG;
+        return false;
     s.kernel = n.tex > 0 ? Kernel::TexObjects : n.color > 0 ? Kernel::ColorObjects : n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
                n.smooth > 0 ? Kernel::SmoothObjects : n_objects > 0 ? Kernel::ObjTable : Kernel::NoObjects;
     s.obj_nrm = n.smooth > 0 ? obj_nrm : nullptr;
@@ -845,6 +922,15 @@ int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, i
         s.tex = tex;
         s.texels = static_cast<const float4*>(texels);
     }
+    return true;
+}
+int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                   const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
+                   const float* obj_col = nullptr, const float* obj_uv = nullptr, const MatpbrPathObjectTex* tex = nullptr,
+                   const void* texels = nullptr, long n_texels = 0) {
+    Scene s;
+    if (!objects_scene(level, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
+        return MATPBR_PATH_ERR_INVALID_ARG;
     return render_common(f, s);
 }
 
@@ -997,6 +1083,22 @@ int matpbr_path_trace_host(const void* nodes, const void* tris, const float* o, 
         int32_t id = -1;
         if (h >= 0) std::memcpy(&id, &T[3 * h].w, 4);
         tri_hit[k] = id;
+    }
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_trace_scene_host(const void* nodes, const void* tris, const float* o, const float* d, long N, float tmin, float tmax,
+                                 float* t_hit, int32_t* tri_hit, long n_scene_tri, int any) {
+    if (!nodes || !tris || !o || !d || !t_hit || !tri_hit || N < 0 || n_scene_tri < 0 || (any != 0 && any != 1)) return MATPBR_PATH_ERR_INVALID_ARG;
+    const float4 *Nd = static_cast<const float4*>(nodes), *T = static_cast<const float4*>(tris);
+    const int id_limit = (int)std::min(n_scene_tri, (long)INT32_MAX);
+    for (long k = 0; k < N; ++k) {
+        HostStack stk;
+        float t = tmax;
+        const int h = any ? trace<true, true>(Nd, T, o + 3 * k, d + 3 * k, tmin, t, stk, id_limit)
+                          : trace<false, true>(Nd, T, o + 3 * k, d + 3 * k, tmin, t, stk, id_limit);
+        t_hit[k] = t;
+        tri_hit[k] = h >= 0 ? tri_id(T[3 * h]) : -1;
     }
     return MATPBR_PATH_OK;
 }
@@ -1224,6 +1326,42 @@ int matpbr_path_render_objects_textures(const void* nodes, const void* tris, con
                                         const void* texels, long n_texels) {
     return render_objects(RENDER_FRAME, 7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels,
                           n_texels);
+}
+
+int matpbr_path_render_objects_diff(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                    float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                    int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                    const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                    const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                    const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                    const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked) {
+    float* const out = nullptr;   // the sums go to the table's buffers
+    const Frame f = RENDER_FRAME;
+    PathArgs q{};
+    Scene s;
+    if (!fg || !delta || !alpha || n_objects <= 0 || !frame_args(f, q) ||
+        !objects_scene(7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    DiffObjects dt{};
+    static_cast<TexObjects&>(dt) = tex_objects(s);
+    dt.fg = fg; dt.delta = delta; dt.alpha = alpha; dt.rewalked = rewalked;
+    return launch_frame(f, q, dt);
+}
+
+int matpbr_path_composite(const float* fg_sum, const float* delta_sum, const float* alpha_sum, const float* photo, int H, int W, float scale,
+                          float* out, void* stream) {
+    if (!composite_args_valid(fg_sum, delta_sum, alpha_sum, photo, H, W, scale, out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    const long P = (long)H * W;
+    hipLaunchKernelGGL(composite_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fg_sum, delta_sum, alpha_sum, photo, P,
+                       scale, out);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_composite_host(const float* fg_sum, const float* delta_sum, const float* alpha_sum, const float* photo, int H, int W, float scale,
+                               float* out) {
+    if (!composite_args_valid(fg_sum, delta_sum, alpha_sum, photo, H, W, scale, out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long p = 0; p < (long)H * W; ++p) composite_pixel(fg_sum, delta_sum, alpha_sum, photo, p, scale, out);
+    return MATPBR_PATH_OK;
 }
 
 int matpbr_path_object_texture_host(const float* tri, const float* uv, const float* o, const float* d, long N, const MatpbrPathObjectTex* tex,

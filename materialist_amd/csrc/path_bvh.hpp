@@ -51,8 +51,15 @@ __host__ __device__ inline bool box_hit(float lx, float ly, float lz, float hx, 
     return t0 <= t1;
 }
 
-// Moller-Trumbore on (v0, e1, e2); updates t / k where tmin < t' < t
-__host__ __device__ inline void tri_test(const float4* tris, int k, const float o[3], const float d[3], float tmin, float& t, int& hit) {
+// the id a triangle carries in tris[3 k].w: its index in the input mesh
+__host__ __device__ inline int tri_id(const float4& A) { return __builtin_bit_cast(int, A.w); }
+
+// Moller-Trumbore on (v0, e1, e2); updates t / k where tmin < t' < t.  FILTER: a triangle whose id is id_limit or more is skipped
+// before its test (the differential render's walk without the inserted objects, which follow the scene's triangles in the input mesh).
+template <bool FILTER = false>
+__host__ __device__ inline void tri_test(const float4* tris, int k, const float o[3], const float d[3], float tmin, float& t, int& hit,
+                                         int id_limit = 0) {
+    if (FILTER && tri_id(tris[3 * k]) >= id_limit) return;
     const float4 A = tris[3 * k], B = tris[3 * k + 1], C = tris[3 * k + 2];
     const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
     float pv[3];
@@ -73,10 +80,11 @@ __host__ __device__ inline void tri_test(const float4* tris, int k, const float 
 
 // Closest hit (ANY = false) or any hit (ANY = true, shadow rays) of the ray o + t d, tmin < t < t_in.  Returns the leaf-order index
 // of the triangle hit (-1: none) and its distance in t.  `stk` is the traversal stack (kStack entries): LDS on the device, an
-// array on the host.  Pushes beyond kStack are dropped: only a BVH deeper than the builder makes could reach that.
-template <bool ANY, class Stack>
+// array on the host.  Pushes beyond kStack are dropped: only a BVH deeper than the builder makes could reach that.  FILTER: tri_test's;
+// without it id_limit is not read and the routine is the one it was.
+template <bool ANY, bool FILTER = false, class Stack>
 __host__ __device__ inline int trace(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float o[3], const float d[3],
-                                     float tmin, float& t, Stack& stk) {
+                                     float tmin, float& t, Stack& stk, int id_limit = 0) {
     float inv[3], oi[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -93,12 +101,12 @@ __host__ __device__ inline int trace(const float4* __restrict__ nodes, const flo
         bool h0 = box_hit(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, inv, oi, tmin, t, tn0);
         bool h1 = box_hit(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, inv, oi, tmin, t, tn1);
         if (h0 && q3.z >= 0) {
-            for (int k = q3.x, e = q3.x + q3.z; k < e; ++k) tri_test(tris, k, o, d, tmin, t, hit);
+            for (int k = q3.x, e = q3.x + q3.z; k < e; ++k) tri_test<FILTER>(tris, k, o, d, tmin, t, hit, id_limit);
             h0 = false;
             if (ANY && hit >= 0) return hit;
         }
         if (h1 && q3.w >= 0) {
-            for (int k = q3.y, e = q3.y + q3.w; k < e; ++k) tri_test(tris, k, o, d, tmin, t, hit);
+            for (int k = q3.y, e = q3.y + q3.w; k < e; ++k) tri_test<FILTER>(tris, k, o, d, tmin, t, hit, id_limit);
             h1 = false;
             if (ANY && hit >= 0) return hit;
         }

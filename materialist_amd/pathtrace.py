@@ -5,8 +5,9 @@ Mitsuba's `path` integrator, `max_depth` 4, on the `.ply` mesh under the texel e
 49-52).  `PathTracer` is that render on the GPU: shadows, inter-reflection, the envmap's texels as the light.
 `PathTracer.render_bwd` is its backward pass (the fixed-seed estimator's derivative with the sampling detached) and `PathRenderFn`
 puts both behind autograd.  `PathTracer.features` and `PathTracer.denoise` are the opt-in denoiser (DESIGN.md section 1.4,
-"Denoiser"): first-hit features and a variance-guided a-trous filter over two half renders, forward only.  There is no fallback: a
-missing or failing library raises.
+"Denoiser"): first-hit features and a variance-guided a-trous filter over two half renders, forward only.  `PathTracer.render_diff`
+and `composite` are the differential render ("Differential render"): what inserted objects add to and take
+from a photograph of the scene, forward only.  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -117,6 +118,10 @@ SIGNATURES = {
                                                  ctypes.c_long, _P, _P]),
     "matpbr_path_feature_tints_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P, _P,
                                                       ctypes.c_long, _P]),
+    "matpbr_path_render_objects_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 4),
+    "matpbr_path_composite": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
+    "matpbr_path_composite_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
+    "matpbr_path_trace_scene_host": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_long, ctypes.c_float, ctypes.c_float, _P, _P, ctypes.c_long, ctypes.c_int]),
     "matpbr_path_render_trans": (ctypes.c_int, _RENDER + [_P, _P, _P]),
     "matpbr_path_trans_eval_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_long, _P, _P]),
     "matpbr_path_trans_lookup_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
@@ -152,13 +157,16 @@ ROUGH_SYMBOLS = ("matpbr_path_render_objects_rough", "matpbr_path_rough_sample_h
 COLOR_SYMBOLS = ("matpbr_path_render_objects_colors", "matpbr_path_object_color_host", "matpbr_path_feature_colors", "matpbr_path_feature_colors_host")
 # and (textured inserted objects)
 TEXTURE_SYMBOLS = ("matpbr_path_render_objects_textures", "matpbr_path_object_texture_host", "matpbr_path_feature_tints", "matpbr_path_feature_tints_host")
-LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS + TEXTURE_SYMBOLS
+# and (the differential render)
+DIFF_SYMBOLS = ("matpbr_path_render_objects_diff", "matpbr_path_composite", "matpbr_path_composite_host", "matpbr_path_trace_scene_host")
+LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS + TEXTURE_SYMBOLS + DIFF_SYMBOLS
 # the feature each of them came with, as `symbol` names it
 _FEATURE = {name: what for names, what in ((SMOOTH_SYMBOLS, "smooth inserted objects"), (DENOISE_SYMBOLS, "the denoiser"),
                                            (PBR_SYMBOLS, "PBR inserted objects"), (LIGHT_SYMBOLS, "emissive inserted objects"),
                                            (ROUGH_SYMBOLS, "rough dielectric inserted objects"),
                                            (COLOR_SYMBOLS, "vertex-coloured inserted objects"),
-                                           (TEXTURE_SYMBOLS, "textured inserted objects")) for name in names}
+                                           (TEXTURE_SYMBOLS, "textured inserted objects"),
+                                           (DIFF_SYMBOLS, "the differential render")) for name in names}
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
@@ -286,6 +294,19 @@ def trace_host(bvh: Dict[str, object], origins: np.ndarray, dirs: np.ndarray, tm
     k = np.empty(o.shape[0], np.int32)
     check(load().matpbr_path_trace_host(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), _ptr(o), _ptr(d), o.shape[0], tmin, tmax, _ptr(t), _ptr(k)),
           "matpbr_path_trace_host")
+    return t, k
+
+
+def trace_scene_host(bvh: Dict[str, object], origins: np.ndarray, dirs: np.ndarray, n_scene_tri: int, any: bool = False, tmin: float = 0.0,
+                     tmax: float = 3.0e38):
+    """`trace_host` over the triangles of id < `n_scene_tri` alone, the differential render's second walk: a triangle of a larger id is
+    skipped before its test.  `any`: the shadow rays' traversal, which returns the first triangle it finds (t is then its distance,
+    not the closest).  With `n_scene_tri` at the mesh's triangle count and `any` off it is `trace_host`, bit for bit."""
+    o, d = _rows(origins, 3), _rows(dirs, 3)
+    t = np.empty(o.shape[0], np.float32)
+    k = np.empty(o.shape[0], np.int32)
+    check(symbol("matpbr_path_trace_scene_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), _ptr(o), _ptr(d), o.shape[0], tmin, tmax, _ptr(t), _ptr(k),
+                                                 int(n_scene_tri), int(bool(any))), "matpbr_path_trace_scene_host")
     return t, k
 
 
@@ -969,6 +990,47 @@ def denoise(A, B, alb, geom, workspace: Optional[torch.Tensor] = None, **params)
     return out
 
 
+# ---- the differential render's composite ("Differential render") -------------------------------------------------
+def _composite_scale(scale: float) -> float:
+    sc = float(scale)
+    if not (np.isfinite(np.float32(sc)) and np.float32(sc) > 0):
+        raise ValueError(f"scale must be finite and positive (1 / the number of frames summed), got {scale}")
+    return sc
+
+
+def composite_host(fg, delta, alpha, photo, scale: float = 1.0) -> np.ndarray:
+    """`composite` on the CPU with the routine the kernel runs: fg, delta, photo [H,W,3], alpha [H,W] -> [H,W,3], the same bits."""
+    ph = np.asarray(photo)
+    if ph.ndim != 3 or ph.shape[2] != 3 or ph.shape[0] < 1 or ph.shape[1] < 1:
+        raise ValueError(f"photo must be [H,W,3], got {list(ph.shape)}")
+    H, W = ph.shape[:2]
+    sc = _composite_scale(scale)
+    f, d, al, p = _host_image(fg, (H, W, 3), "fg"), _host_image(delta, (H, W, 3), "delta"), _host_image(alpha, (H, W), "alpha"), _host_image(ph, (H, W, 3), "photo")
+    out = np.empty((H, W, 3), np.float32)
+    check(symbol("matpbr_path_composite_host")(_ptr(f), _ptr(d), _ptr(al), _ptr(p), H, W, sc, _ptr(out)), "matpbr_path_composite_host")
+    return out
+
+
+@torch.no_grad()
+def composite(fg, delta, alpha, photo, scale: float = 1.0) -> torch.Tensor:
+    """The differential render composited into the photograph, on the device (the current torch stream): max(0, (fg + delta) scale +
+    (1 - alpha scale) photo) per channel, every operation rounded on its own.  fg, delta, alpha: `PathTracer.render_diff`'s outputs,
+    or their sums over some frames with `scale` = 1 / (the number of frames); photo [H,W,3], linear.  Where fg, delta and alpha are 0
+    the photograph (>= 0) comes through bit for bit."""
+    shp = tuple(torch.as_tensor(photo).shape)
+    if len(shp) != 3 or shp[2] != 3 or shp[0] < 1 or shp[1] < 1:
+        raise ValueError(f"photo must be [H,W,3], got {list(shp)}")
+    H, W = shp[:2]
+    sc = _composite_scale(scale)
+    dev = _device_of(fg, delta, alpha, photo)
+    f, d, al, p = (_device_image(fg, (H, W, 3), "fg", dev), _device_image(delta, (H, W, 3), "delta", dev), _device_image(alpha, (H, W), "alpha", dev),
+                   _device_image(photo, (H, W, 3), "photo", dev))
+    out = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_composite")(f.data_ptr(), d.data_ptr(), al.data_ptr(), p.data_ptr(), H, W, sc, out.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream), "matpbr_path_composite")
+    return out
+
+
 class PathTracer:
     """One mesh in the renderer's frame (camera at the origin looking down -z, `fov_x_deg` horizontal field of view, H x W pixels).
     The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
@@ -1136,6 +1198,28 @@ class PathTracer:
             own = self.object_args()[:OBJECT_ENTRIES[entry]]
         check(symbol(entry, lib)(*args, *own), entry)
         return out
+
+    @torch.no_grad()
+    def render_diff(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
+                    seed: int = 0, spp_per_launch: int = 8, tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None) -> tuple:
+        """The differential render ("Differential render") with `render`'s arguments and random numbers ->
+        (fg [H,W,3], delta [H,W,3], alpha [H,W], rewalked [H,W] int32) on the device, the first three means over `spp`.  fg: the radiance
+        of the samples whose camera ray lands on an inserted object; alpha: their share; delta: what the objects add to and take from
+        the other samples, the sample's radiance minus the same sample's walked again without the objects, over the samples whose first
+        walk met an object (`rewalked` counts them; every sample that misses the objects, where the table holds a light).  Where
+        rewalked is 0, delta is exactly 0.  `composite` puts them into a photograph.  Every split into launches gives the same bits.  A
+        tracer without objects raises ValueError."""
+        if self.objects is None:
+            raise ValueError("render_diff renders what inserted objects change: build the PathTracer with `objects`")
+        fn = symbol("matpbr_path_render_objects_diff")
+        H, W, dev = self.H, self.W, self.device
+        inputs = self._inputs(albedo, roughness, metallic, envmap, tables)
+        fg, delta = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+        alpha, rewalked = torch.empty(H, W, device=dev, dtype=torch.float32), torch.zeros(H, W, device=dev, dtype=torch.int32)
+        check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), rays.data_ptr() if rays is not None else None,
+                 torch.cuda.current_stream(dev).cuda_stream, *self.object_args()[:9], *self._texture_args(), fg.data_ptr(), delta.data_ptr(),
+                 alpha.data_ptr(), rewalked.data_ptr()), "matpbr_path_render_objects_diff")
+        return fg, delta, alpha, rewalked
 
     @torch.no_grad()
     def features(self, normal=None) -> torch.Tensor:

@@ -446,10 +446,38 @@ def _object_uv(path: str, Uv: Optional[np.ndarray]) -> np.ndarray:
     return Uv
 
 
+def _oi_photo(scene_dir: str, photo_path: Optional[str], atrous: bool, env_scale: float) -> np.ndarray:
+    """The photograph `render_oi(composite=True)` composites into, linear float32 [H,W,3] of the maps' size; ValueError for what the
+    composite does not do or cannot read, before any GPU work."""
+    if atrous:
+        raise ValueError("composite knows no denoise='atrous': the filter takes a radiance image, and the composite adds a signed difference")
+    if float(env_scale) != 1.0:
+        raise ValueError(f"composite needs env_scale 1, got {env_scale}: the photograph was taken under the envmap as it is and is not dimmed")
+    path = photo_path if photo_path is not None else os.path.join(scene_dir, "gt_image.exr")
+    if not os.path.exists(path):
+        raise ValueError(f"composite needs the photograph: {path} does not exist (photo_path, or the gt_image.exr the pipeline writes)")
+    try:
+        img = np.asarray(load_image(path))
+    except Exception as e:
+        raise ValueError(f"{path}: cannot read the photograph: {e}") from None
+    if img.dtype.kind in "iu":
+        img = img.astype(np.float32) / float(np.iinfo(img.dtype).max)
+    img = np.asarray(img, dtype=np.float32)
+    if not path.endswith((".exr", ".hdr")):                                  # display values, as the pipeline reads its input
+        img = _loss.srgb_to_linear(torch.from_numpy(np.ascontiguousarray(img))).numpy()
+    H, W = read_exr(os.path.join(scene_dir, "best_results", "albedo.exr")).shape[:2]
+    if img.ndim != 3 or img.shape[2] < 3 or img.shape[:2] != (H, W):
+        raise ValueError(f"{path}: the photograph must be [{H},{W},3], the maps' size, got an array of shape {img.shape}")
+    img = np.ascontiguousarray(img[..., :3], dtype=np.float32)
+    if not (np.isfinite(img).all() and (img >= 0).all()):
+        raise ValueError(f"{path}: the photograph must be finite and >= 0")
+    return img
+
+
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
               denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
-              object_texture: Optional[str] = None) -> str:
+              object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None) -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -468,8 +496,15 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     "colors" holds.  A file without colours is a ValueError naming it.  `object_texture`: an image (a PNG of display values, or an
     .exr / .hdr of linear ones in [0, 1]) that textures oi2.ply over its file's per-vertex texture coordinates (DESIGN.md section 1.4,
     "Textured inserted objects"); with `objects_file` it is ignored and each entry's "texture" and "orm_texture" hold.  A file without
-    coordinates is a ValueError naming it."""
+    coordinates is a ValueError naming it.  `composite`: differential rendering ("Differential render"): the
+    objects, their shadows, bounce light and reflections are put into the photograph `photo_path` (default <scene_dir>/gt_image.exr,
+    linear, as `pipeline.py` writes it; a .png is decoded with `loss.srgb_to_linear`; [H,W,3] of the maps' size, finite and >= 0)
+    instead of re-rendering the fitted scene: the `n_iter` frames of `PathTracer.render_diff` are summed and composited once, into
+    mi_oic_<name>_<env>.exr / .png.  A pixel no sample of which met an object keeps the photograph's bits; through glass the
+    re-rendered scene shows, not the photograph.  With it `denoise="atrous"`, an `env_scale` other than 1 and a missing or wrongly
+    sized photograph are a ValueError before any GPU work."""
     from . import mesh as _mesh
+    from . import pathtrace as _pathtrace
 
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
     if objects_file is not None:
@@ -489,6 +524,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
         raise ValueError(f"object_colors must be 'none', 'vertex' or 'vertex_linear', got {object_colors!r}")
     atrous = _check_denoise(denoise, "path", spp)
     _scaled_env(np.zeros(0, np.float32), env_scale)
+    photo = _oi_photo(scene_dir, photo_path, atrous, env_scale) if composite else None
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
     for p, b, normals, colors, texture, orm_texture in have:
@@ -508,7 +544,13 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     pt = _path_tracer(scene_dir, save_name, mat, device, objects)
     env = _scaled_env(load_image(env_path), env_scale)
     tabs = pt.tables(env)
-    if atrous:
+    if composite:
+        sums = None
+        for i in range(n_iter):
+            frame = pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, spp, max_depth, seed + i, tables=tabs)[:3]
+            sums = frame if sums is None else tuple(x + y for x, y in zip(sums, frame))
+        img = _pathtrace.composite(*sums, torch.from_numpy(photo).to(device), 1.0 / n_iter)
+    elif atrous:
         geom = pt.features()
         half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs)
         tint = pt.feature_tints() if pt.stats["n_textured_objects"] else pt.feature_colors() if pt.stats["n_colored_objects"] else None
@@ -521,7 +563,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     env_id = os.path.basename(env_path)[:-4]
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
-    base = os.path.join(out_dir, f"mi_oi_{save_name}_{env_id}")              # (:233-236)
+    base = os.path.join(out_dir, f"mi_oi{'c' if composite else ''}_{save_name}_{env_id}")   # (:233-236)
     write_exr(base + ".exr", img.cpu().numpy())
     write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
     return base + ".png"

@@ -50,6 +50,13 @@ def parse_args(argv=None):
     ap.add_argument("--env_scale", type=float, default=1.0, metavar="S",
                     help="--integrator path and --mode oi: multiply the envmap by S before its sampling tables are built (1 = the same bits as "
                          "without it; 0 with an area light in --oi_scene = the night shot, lit by the lamp alone)")
+    ap.add_argument("--oi_composite", action="store_true",
+                    help="--mode oi: differential rendering (Debevec 1998): the photograph with the objects, their shadows, bounce light and "
+                         "reflections added, not a re-render of the fitted scene; pixels nothing reaches keep the photograph's bits.  Writes "
+                         "mi_oic_<name>_<env>.exr / .png.  Not with --denoise atrous or an --env_scale other than 1")
+    ap.add_argument("--oi_photo", type=str, default=None, metavar="PATH",
+                    help="--oi_composite: the photograph, of the maps' size (default <scene>/gt_image.exr, linear, as the pipeline writes it; a "
+                         ".png holds display values and is decoded as the pipeline decodes its input)")
     ap.add_argument("--oi_max_depth", type=int, default=16, help="--mode oi: Mitsuba's max_depth (a camera path through glass needs 5 to see light)")
     a = ap.parse_args(argv)
     if a.shading_normals == "map" and (a.integrator != "path" or a.mode == "oi"):
@@ -58,6 +65,14 @@ def parse_args(argv=None):
         ap.error("--env_scale must be finite and >= 0")
     if a.env_scale != 1.0 and a.mode != "oi" and a.integrator != "path":
         ap.error("--env_scale needs --integrator path (or --mode oi): the sh render projects the envmap as it is")
+    if a.oi_composite and a.mode != "oi":
+        ap.error("--oi_composite needs --mode oi")
+    if a.oi_photo is not None and not a.oi_composite:
+        ap.error("--oi_photo needs --oi_composite")
+    if a.oi_composite and a.denoise == "atrous":
+        ap.error("--oi_composite knows no --denoise atrous: the filter takes a radiance image, not a signed difference")
+    if a.oi_composite and a.env_scale != 1.0:
+        ap.error("--oi_composite needs --env_scale 1: the photograph was taken under the envmap as it is and is not dimmed")
     if a.denoise == "atrous":
         if a.mode != "oi" and a.integrator != "path":
             ap.error("--denoise atrous needs --integrator path (or --mode oi): the sh render is deterministic and has no noise to filter")
@@ -82,7 +97,8 @@ def main(argv=None):
     elif a.mode == "oi":
         print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
                                                  object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene,
-                                                 env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture))
+                                                 env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture,
+                                                 **({"composite": True, "photo_path": a.oi_photo} if a.oi_composite else {})))
     else:
         raise ValueError("Invalid mode")
 
