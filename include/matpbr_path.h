@@ -537,6 +537,51 @@ size_t matpbr_path_denoise_workspace_bytes(int H, int W);
 int matpbr_path_denoise(const float* A, const float* B, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm, float* out,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Denoiser for the differential render: the a-trous filter over matpbr_path_render_objects_diff's outputs ----
+ * Forward only, deterministic (no atomics), opt-in; added at version 3.  fgA, deltaA [H,W,3], alphaA [H,W] and the same for B: two sums
+ * of that entry point's outputs over the same number of frames, with independent seeds and equal spp; scale = 1 / (frames summed per
+ * half), finite and > 0; geom, alb and prm as matpbr_path_denoise takes them.
+ * A pixel's own layer is the object layer where id >= 1, else the scene layer.  abar = (0.5 (alphaA + alphaB)) scale; the own layer's
+ * coverage k is abar (object) or max(0, 1 - abar) (scene), its signal X is fg (object) or delta (scene); the other layer's signal and
+ * alpha are never filtered.
+ * prepare: g = scale / k; c0 = (0.5 (X_A + X_B)) g; v0 = the 3 x 3 binomial average of ((lum(X_A) - lum(X_B))^2 / 4) g_q^2 over the taps
+ * inside the image with the pixel's id and k_q > 0, normalised by the weights used; where k = 0, (c0, v0) = 0 and no quotient is
+ * formed.  cov[H,W] = k.
+ * level l: matpbr_path_denoise_level's with every tap weight, the centre's 9/64 included, multiplied by k_q, and
+ *   w_c = exp(-|lum(c_p) - lum(c_q)| / (sigma_c sqrt(max(v_p, 0)) + 1e-3 |lum(c_p)| + 1e-30));
+ * a pixel with k = 0 gives (0, 0, 0, 0).
+ * finish: own = k c_L; fg' = own on object pixels, else (0.5 (fgA + fgB)) scale; delta' = own on scene pixels, else
+ * (0.5 (deltaA + deltaB)) scale; alpha' = abar.  The picture is matpbr_path_composite(fg', delta', alpha', photo, 1).
+ * Where deltaA and deltaB are exactly 0 within Chebyshev distance 2 (2^levels - 1) + 1 of a scene pixel, delta' there is +0.
+ * DEVICE pointers, cv and geom 16-byte aligned; `prm` HOST.  Invalid argument: a null pointer, H or W <= 0, a bad prm, a level outside
+ * 0..7, a scale that is not finite and > 0, cv_out == cv_in. */
+int matpbr_path_denoise_diff_prepare(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB,
+                                     const float* alphaB, const float* geom, int H, int W, float scale, float* cv0, float* cov, void* stream);
+int matpbr_path_denoise_diff_level(const float* cv_in, const float* cov, const float* geom, const float* alb, int H, int W,
+                                   const MatpbrPathDenoise* prm, int level, float* cv_out, void* stream);
+int matpbr_path_denoise_diff_finish(const float* cv, const float* cov, const float* fgA, const float* deltaA, const float* alphaA, const float* fgB,
+                                    const float* deltaB, const float* alphaB, const float* geom, int H, int W, float scale, float* fg, float* delta,
+                                    float* alpha, void* stream);
+/* The same steps on the CPU with the per-pixel routines the kernels run (every pointer HOST). */
+int matpbr_path_denoise_diff_prepare_host(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB,
+                                          const float* alphaB, const float* geom, int H, int W, float scale, float* cv0, float* cov);
+int matpbr_path_denoise_diff_level_host(const float* cv_in, const float* cov, const float* geom, const float* alb, int H, int W,
+                                        const MatpbrPathDenoise* prm, int level, float* cv_out);
+int matpbr_path_denoise_diff_finish_host(const float* cv, const float* cov, const float* fgA, const float* deltaA, const float* alphaA,
+                                         const float* fgB, const float* deltaB, const float* alphaB, const float* geom, int H, int W, float scale,
+                                         float* fg, float* delta, float* alpha);
+
+/* Workspace of matpbr_path_denoise_diff: two [H,W,4] buffers and cov[H,W], in bytes (0 for a non-positive size). */
+size_t matpbr_path_denoise_diff_workspace_bytes(int H, int W);
+/* The chain: prepare, `levels` levels ping-ponging in `workspace` (16-byte aligned, used by the enqueued work until it has run), finish
+ * -> fg[H,W,3], delta[H,W,3], alpha[H,W].  Equal to the separate calls bit for bit.  The _host twin takes HOST pointers throughout. */
+int matpbr_path_denoise_diff(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB, const float* alphaB,
+                             const float* geom, const float* alb, int H, int W, float scale, const MatpbrPathDenoise* prm, float* fg, float* delta,
+                             float* alpha, void* workspace, size_t workspace_bytes, void* stream);
+int matpbr_path_denoise_diff_host(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB,
+                                  const float* alphaB, const float* geom, const float* alb, int H, int W, float scale, const MatpbrPathDenoise* prm,
+                                  float* fg, float* delta, float* alpha, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

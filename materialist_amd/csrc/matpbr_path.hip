@@ -1679,4 +1679,130 @@ int matpbr_path_denoise(const float* A, const float* B, const float* geom, const
     return MATPBR_PATH_OK;
 }
 
+// ---- the differential render's filter: the steps, their CPU twins and the chain (the twins and the chain share one walk each) ----------
+static bool diff_prepare_args(const DiffHalves& x, const float* geom, int H, int W, float scale, const float* cv0, const float* cov) {
+    return diff_halves_valid(x) && geom && cv0 && cov && denoise_size_valid(H, W) && diff_scale_valid(scale);
+}
+static bool diff_level_args(const float* cv_in, const float* cov, const float* geom, const float* alb, int H, int W, const MatpbrPathDenoise* prm,
+                            int level, const float* cv_out) {
+    return cv_in && cov && geom && alb && cv_out && cv_in != cv_out && denoise_size_valid(H, W) && denoise_params_valid(prm) && level >= 0 &&
+           level < kDnMaxLevels;
+}
+static bool diff_finish_args(const float* cv, const float* cov, const DiffHalves& x, const float* geom, int H, int W, float scale, const float* fg,
+                             const float* delta, const float* alpha) {
+    return cv && cov && diff_halves_valid(x) && geom && fg && delta && alpha && denoise_size_valid(H, W) && diff_scale_valid(scale);
+}
+static void diff_prepare_host(const DiffHalves& x, const float4* geom, int H, int W, float scale, float4* cv0, float* cov) {
+    for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j) cov[(long)i * W + j] = dd_prepare_pixel(x, geom, H, W, i, j, scale, cv0[(long)i * W + j]);
+}
+static void diff_level_host(const float4* cv, const float* cov, const float4* geom, const float* alb, int H, int W, int s,
+                            const MatpbrPathDenoise& prm, float4* cv_out) {
+    for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j) cv_out[(long)i * W + j] = dn_level_pixel<true>(cv, geom, alb, H, W, i, j, s, prm, cov);
+}
+static void diff_finish_host(const float4* cv, const float* cov, const DiffHalves& x, const float4* geom, int H, int W, float scale, float* fg,
+                             float* delta, float* alpha) {
+    for (long p = 0; p < (long)H * W; ++p) dd_finish_pixel(cv, cov, x, geom, p, scale, fg, delta, alpha);
+}
+
+int matpbr_path_denoise_diff_prepare(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB,
+                                     const float* alphaB, const float* geom, int H, int W, float scale, float* cv0, float* cov, void* stream) {
+    const DiffHalves x{fgA, deltaA, alphaA, fgB, deltaB, alphaB};
+    if (!diff_prepare_args(x, geom, H, W, scale, cv0, cov)) return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(denoise_diff_prepare_kernel, denoise_grid(H, W), dim3(kDnTileX, kDnTileY), 0, (hipStream_t)stream, x,
+                       reinterpret_cast<const float4*>(geom), H, W, scale, reinterpret_cast<float4*>(cv0), cov);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_denoise_diff_prepare_host(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB,
+                                          const float* alphaB, const float* geom, int H, int W, float scale, float* cv0, float* cov) {
+    const DiffHalves x{fgA, deltaA, alphaA, fgB, deltaB, alphaB};
+    if (!diff_prepare_args(x, geom, H, W, scale, cv0, cov)) return MATPBR_PATH_ERR_INVALID_ARG;
+    diff_prepare_host(x, reinterpret_cast<const float4*>(geom), H, W, scale, reinterpret_cast<float4*>(cv0), cov);
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_denoise_diff_level(const float* cv_in, const float* cov, const float* geom, const float* alb, int H, int W,
+                                   const MatpbrPathDenoise* prm, int level, float* cv_out, void* stream) {
+    if (!diff_level_args(cv_in, cov, geom, alb, H, W, prm, level, cv_out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(denoise_diff_level_kernel, denoise_grid(H, W), dim3(kDnTileX, kDnTileY), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(cv_in), cov, reinterpret_cast<const float4*>(geom), alb, H, W, 1 << level, *prm,
+                       reinterpret_cast<float4*>(cv_out));
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_denoise_diff_level_host(const float* cv_in, const float* cov, const float* geom, const float* alb, int H, int W,
+                                        const MatpbrPathDenoise* prm, int level, float* cv_out) {
+    if (!diff_level_args(cv_in, cov, geom, alb, H, W, prm, level, cv_out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    diff_level_host(reinterpret_cast<const float4*>(cv_in), cov, reinterpret_cast<const float4*>(geom), alb, H, W, 1 << level, *prm,
+                    reinterpret_cast<float4*>(cv_out));
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_denoise_diff_finish(const float* cv, const float* cov, const float* fgA, const float* deltaA, const float* alphaA, const float* fgB,
+                                    const float* deltaB, const float* alphaB, const float* geom, int H, int W, float scale, float* fg, float* delta,
+                                    float* alpha, void* stream) {
+    const DiffHalves x{fgA, deltaA, alphaA, fgB, deltaB, alphaB};
+    if (!diff_finish_args(cv, cov, x, geom, H, W, scale, fg, delta, alpha)) return MATPBR_PATH_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(denoise_diff_finish_kernel, denoise_grid(H, W), dim3(kDnTileX, kDnTileY), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(cv), cov, x, reinterpret_cast<const float4*>(geom), H, W, scale, fg, delta, alpha);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_denoise_diff_finish_host(const float* cv, const float* cov, const float* fgA, const float* deltaA, const float* alphaA,
+                                         const float* fgB, const float* deltaB, const float* alphaB, const float* geom, int H, int W, float scale,
+                                         float* fg, float* delta, float* alpha) {
+    const DiffHalves x{fgA, deltaA, alphaA, fgB, deltaB, alphaB};
+    if (!diff_finish_args(cv, cov, x, geom, H, W, scale, fg, delta, alpha)) return MATPBR_PATH_ERR_INVALID_ARG;
+    diff_finish_host(reinterpret_cast<const float4*>(cv), cov, x, reinterpret_cast<const float4*>(geom), H, W, scale, fg, delta, alpha);
+    return MATPBR_PATH_OK;
+}
+
+size_t matpbr_path_denoise_diff_workspace_bytes(int H, int W) {
+    return denoise_size_valid(H, W) ? (size_t)H * (size_t)W * (2 * sizeof(float4) + sizeof(float)) : 0;
+}
+
+static bool diff_chain_args(const DiffHalves& x, const float* geom, const float* alb, int H, int W, float scale, const MatpbrPathDenoise* prm,
+                            const float* fg, const float* delta, const float* alpha, const void* workspace, size_t workspace_bytes) {
+    return diff_halves_valid(x) && geom && alb && fg && delta && alpha && workspace && denoise_size_valid(H, W) && diff_scale_valid(scale) &&
+           denoise_params_valid(prm) && workspace_bytes >= matpbr_path_denoise_diff_workspace_bytes(H, W) && !((uintptr_t)workspace & 15);
+}
+
+int matpbr_path_denoise_diff(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB, const float* alphaB,
+                             const float* geom, const float* alb, int H, int W, float scale, const MatpbrPathDenoise* prm, float* fg, float* delta,
+                             float* alpha, void* workspace, size_t workspace_bytes, void* stream) {
+    const DiffHalves x{fgA, deltaA, alphaA, fgB, deltaB, alphaB};
+    if (!diff_chain_args(x, geom, alb, H, W, scale, prm, fg, delta, alpha, workspace, workspace_bytes)) return MATPBR_PATH_ERR_INVALID_ARG;
+    const MatpbrPathDenoise pr = *prm;
+    float4* ws[2] = {static_cast<float4*>(workspace), static_cast<float4*>(workspace) + (size_t)H * W};
+    float* cov = reinterpret_cast<float*>(ws[1] + (size_t)H * W);
+    const float4* g = reinterpret_cast<const float4*>(geom);
+    const dim3 grid = denoise_grid(H, W), block(kDnTileX, kDnTileY);
+    hipLaunchKernelGGL(denoise_diff_prepare_kernel, grid, block, 0, (hipStream_t)stream, x, g, H, W, scale, ws[0], cov);
+    if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    for (int l = 0; l < pr.levels; ++l) {
+        hipLaunchKernelGGL(denoise_diff_level_kernel, grid, block, 0, (hipStream_t)stream, (const float4*)ws[l & 1], (const float*)cov, g, alb, H, W,
+                           1 << l, pr, ws[(l + 1) & 1]);
+        if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(denoise_diff_finish_kernel, grid, block, 0, (hipStream_t)stream, (const float4*)ws[pr.levels & 1], (const float*)cov, x, g, H,
+                       W, scale, fg, delta, alpha);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_denoise_diff_host(const float* fgA, const float* deltaA, const float* alphaA, const float* fgB, const float* deltaB,
+                                  const float* alphaB, const float* geom, const float* alb, int H, int W, float scale, const MatpbrPathDenoise* prm,
+                                  float* fg, float* delta, float* alpha, void* workspace, size_t workspace_bytes) {
+    const DiffHalves x{fgA, deltaA, alphaA, fgB, deltaB, alphaB};
+    if (!diff_chain_args(x, geom, alb, H, W, scale, prm, fg, delta, alpha, workspace, workspace_bytes)) return MATPBR_PATH_ERR_INVALID_ARG;
+    float4* ws[2] = {static_cast<float4*>(workspace), static_cast<float4*>(workspace) + (size_t)H * W};
+    float* cov = reinterpret_cast<float*>(ws[1] + (size_t)H * W);
+    const float4* g = reinterpret_cast<const float4*>(geom);
+    diff_prepare_host(x, g, H, W, scale, ws[0], cov);
+    for (int l = 0; l < prm->levels; ++l) diff_level_host(ws[l & 1], cov, g, alb, H, W, 1 << l, *prm, ws[(l + 1) & 1]);
+    diff_finish_host(ws[prm->levels & 1], cov, x, g, H, W, scale, fg, delta, alpha);
+    return MATPBR_PATH_OK;
+}
+
 }  // extern "C"

@@ -225,18 +225,28 @@ __host__ __device__ inline float4 dn_prepare_pixel(const float* __restrict__ A, 
 // one a-trous level at stride s: the 5 x 5 taps p + s (di, dj), the centre with weight 9/64, every other tap with
 // h h [id_q == id_p] w_n w_x w_a w_c.  The centre's guides stay in registers; a tap outside the image reads
 // the centre's records and weighs nothing (no branch).  -> (sum w c / sum w, sum w^2 v / (sum w)^2)
+//
+// COV (the differential render's filter, "Denoiser for the differential render"): every tap weight, the centre's included, is
+// multiplied by the tap's coverage cov[q], the colour term's relative part takes |lum(c_p)|, and a pixel without coverage is
+// (0, 0, 0, 0).  Off, every `if constexpr (COV)` folds away and `cov` is not read.
+template <bool COV = false>
 __host__ __device__ inline float4 dn_level_pixel(const float4* __restrict__ cv, const float4* __restrict__ geom, const float* __restrict__ alb, int H,
-                                                 int W, int i, int j, int s, const MatpbrPathDenoise& prm) {
+                                                 int W, int i, int j, int s, const MatpbrPathDenoise& prm, const float* __restrict__ cov = nullptr) {
     const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     const long p = (long)i * W + j;
     const float4 cp = cv[p], xp = geom[2 * p], np_ = geom[2 * p + 1];
     const float ap[3] = {alb[3 * p], alb[3 * p + 1], alb[3 * p + 2]};
     const float lp = dn_lum(cp.x, cp.y, cp.z);
     const bool geo = np_.w != -1.0f;   // a pixel that hit nothing has no normal and no position to compare
-    const float inv_c = 1.0f / (prm.sigma_c * sqrtf(fmaxf(cp.w, 0.0f)) + 1e-3f * lp + 1e-30f);
+    float kp = 1.0f;
+    if constexpr (COV) {
+        kp = cov[p];
+        if (!(kp > 0.0f)) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    const float inv_c = 1.0f / (prm.sigma_c * sqrtf(fmaxf(cp.w, 0.0f)) + 1e-3f * (COV ? fabsf(lp) : lp) + 1e-30f);
     const float inv_a = 1.0f / (prm.sigma_a * prm.sigma_a);
     const float xs = prm.sigma_x * xp.w * (float)s;
-    const float w0 = h[2] * h[2];
+    const float w0 = COV ? (h[2] * h[2]) * kp : h[2] * h[2];
     float sw = w0, sc[3] = {w0 * cp.x, w0 * cp.y, w0 * cp.z}, sv = (w0 * w0) * cp.w;
 #pragma unroll
     for (int di = -2; di <= 2; ++di) {
@@ -255,7 +265,8 @@ __host__ __device__ inline float4 dn_level_pixel(const float4* __restrict__ cv, 
                 const float dist = fabsf(np_.x * (xq.x - xp.x) + np_.y * (xq.y - xp.y) + np_.z * (xq.z - xp.z));
                 e += dist * dn_rcp(xs * sqrtf((float)(di * di + dj * dj)) + 1e-30f);
             }
-            const float w = in && nq.w == np_.w ? (h[di + 2] * h[dj + 2]) * wn * dn_exp(-e) : 0.0f;
+            float w = in && nq.w == np_.w ? (h[di + 2] * h[dj + 2]) * wn * dn_exp(-e) : 0.0f;
+            if constexpr (COV) w *= cov[q];
             sw += w;
             sc[0] += w * cq.x; sc[1] += w * cq.y; sc[2] += w * cq.z;
             sv += (w * w) * cq.w;
@@ -288,6 +299,103 @@ __global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_level_kernel(cons
         cv_out[p] = r;
     }
 }
+
+// ---- the differential render's filter ("Denoiser for the differential render") ---------------------------------
+// Two halves of matpbr_path_render_objects_diff's sums.  A pixel's own layer is the object layer (id >= 1: signal fg, coverage the mean
+// alpha) or the scene layer (id 0 or -1: signal delta, coverage 1 - the mean alpha); the filter runs over the own layer's signal divided
+// by its coverage, with the coverage as every tap's confidence, and `finish` multiplies the coverage back.
+struct DiffHalves {
+    const float* fgA; const float* deltaA; const float* alphaA;
+    const float* fgB; const float* deltaB; const float* alphaB;
+};
+// the mean alpha of a pixel, (0.5 (alphaA + alphaB)) scale, and from it the own layer's coverage; each operation rounded on its own, so
+// the device and the CPU agree on which pixels have none
+__host__ __device__ inline float dd_alpha(const DiffHalves& x, long p, float scale) {
+#pragma clang fp contract(off)
+    return (0.5f * (x.alphaA[p] + x.alphaB[p])) * scale;
+}
+__host__ __device__ inline float dd_coverage(float abar, bool object) {
+#pragma clang fp contract(off)
+    return object ? abar : fmaxf(0.0f, 1.0f - abar);
+}
+
+// prepare: cv0 = ((X_A + X_B) / 2 g, v0) with g = scale / coverage, v0 dn_prepare_pixel's average of (lum(X_A) - lum(X_B))^2 / 4 g_q^2
+// over the taps that also have coverage; a pixel without coverage is (0, 0, 0, 0) and no quotient is formed for it.  -> its coverage
+__host__ __device__ inline float dd_prepare_pixel(const DiffHalves& x, const float4* __restrict__ geom, int H, int W, int i, int j, float scale,
+                                                  float4& cv0) {
+    const long p = (long)i * W + j;
+    const float idp = geom[2 * p + 1].w;
+    const bool object = idp >= 1.0f;
+    const float* __restrict__ A = object ? x.fgA : x.deltaA;
+    const float* __restrict__ B = object ? x.fgB : x.deltaB;
+    const float kp = dd_coverage(dd_alpha(x, p, scale), object);
+    cv0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!(kp > 0.0f)) return 0.0f;
+    float sv = 0.0f, sw = 0.0f;
+    for (int di = -1; di <= 1; ++di) {
+        for (int dj = -1; dj <= 1; ++dj) {
+            const int qi = i + di, qj = j + dj;
+            const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
+            const long q = in ? (long)qi * W + qj : p;   // a tap outside reads the centre and weighs nothing
+            const float kq = dd_coverage(dd_alpha(x, q, scale), object);
+            const bool use = in && geom[2 * q + 1].w == idp && kq > 0.0f;
+            const float g = use ? scale / kq : 0.0f;
+            const float dl = dn_lum(A[3 * q], A[3 * q + 1], A[3 * q + 2]) - dn_lum(B[3 * q], B[3 * q + 1], B[3 * q + 2]);
+            const float w = use ? (float)((2 - (di < 0 ? -di : di)) * (2 - (dj < 0 ? -dj : dj))) : 0.0f;
+            sv += w * ((dl * dl * 0.25f) * (g * g));
+            sw += w;
+        }
+    }
+    const float gp = scale / kp;
+    cv0 = make_float4((0.5f * (A[3 * p] + B[3 * p])) * gp, (0.5f * (A[3 * p + 1] + B[3 * p + 1])) * gp, (0.5f * (A[3 * p + 2] + B[3 * p + 2])) * gp,
+                      sv / sw);
+    return kp;
+}
+
+// finish: the own layer's filtered colour times its coverage; the other layer's mean and the mean alpha pass through
+__host__ __device__ inline void dd_finish_pixel(const float4* cv, const float* cov, const DiffHalves& x, const float4* geom, long p, float scale,
+                                                float* fg, float* delta, float* alpha) {
+    const bool object = geom[2 * p + 1].w >= 1.0f;
+    const float4 c = cv[p];
+    const float k = cov[p];
+    const float own[3] = {k * c.x, k * c.y, k * c.z};
+    for (int n = 0; n < 3; ++n) {
+        const float mf = (0.5f * (x.fgA[3 * p + n] + x.fgB[3 * p + n])) * scale, md = (0.5f * (x.deltaA[3 * p + n] + x.deltaB[3 * p + n])) * scale;
+        fg[3 * p + n] = object ? own[n] : mf;
+        delta[3 * p + n] = object ? md : own[n];
+    }
+    alpha[p] = dd_alpha(x, p, scale);
+}
+
+__global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_diff_prepare_kernel(const DiffHalves x, const float4* __restrict__ geom, int H, int W,
+                                                                                  float scale, float4* __restrict__ cv0, float* __restrict__ cov) {
+    const int j = blockIdx.x * kDnTileX + threadIdx.x, i = blockIdx.y * kDnTileY + threadIdx.y;
+    if (i >= H || j >= W) return;
+    float4 r;
+    const float k = dd_prepare_pixel(x, geom, H, W, i, j, scale, r);
+    cv0[(long)i * W + j] = r;
+    cov[(long)i * W + j] = k;
+}
+
+// denoise_level_kernel's second instantiation of dn_level_pixel
+__global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_diff_level_kernel(const float4* __restrict__ cv, const float* __restrict__ cov,
+                                                                                const float4* __restrict__ geom, const float* __restrict__ alb, int H,
+                                                                                int W, int s, const MatpbrPathDenoise prm, float4* __restrict__ cv_out) {
+    const int j = blockIdx.x * kDnTileX + threadIdx.x, i = blockIdx.y * kDnTileY + threadIdx.y;
+    if (i >= H || j >= W) return;
+    cv_out[(long)i * W + j] = dn_level_pixel<true>(cv, geom, alb, H, W, i, j, s, prm, cov);
+}
+
+__global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_diff_finish_kernel(const float4* cv, const float* cov, const DiffHalves x,
+                                                                                 const float4* geom, int H, int W, float scale, float* fg, float* delta,
+                                                                                 float* alpha) {
+    const int j = blockIdx.x * kDnTileX + threadIdx.x, i = blockIdx.y * kDnTileY + threadIdx.y;
+    if (i >= H || j >= W) return;
+    dd_finish_pixel(cv, cov, x, geom, (long)i * W + j, scale, fg, delta, alpha);
+}
+
+inline bool diff_halves_valid(const DiffHalves& x) { return x.fgA && x.deltaA && x.alphaA && x.fgB && x.deltaB && x.alphaB; }
+inline bool diff_scale_valid(float scale) { return std::isfinite(scale) && scale > 0.0f; }
 
 bool denoise_params_valid(const MatpbrPathDenoise* prm) {
     if (!prm || prm->levels < 1 || prm->levels > kDnMaxLevels) return false;

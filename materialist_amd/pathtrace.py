@@ -7,7 +7,8 @@ Mitsuba's `path` integrator, `max_depth` 4, on the `.ply` mesh under the texel e
 puts both behind autograd.  `PathTracer.features` and `PathTracer.denoise` are the opt-in denoiser (DESIGN.md section 1.4,
 "Denoiser"): first-hit features and a variance-guided a-trous filter over two half renders, forward only.  `PathTracer.render_diff`
 and `composite` are the differential render ("Differential render"): what inserted objects add to and take
-from a photograph of the scene, forward only.  There is no fallback: a missing or failing library raises.
+from a photograph of the scene, forward only; `PathTracer.denoise_diff` is its own a-trous filter over two halves of it ("Denoiser
+for the differential render").  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -139,6 +140,15 @@ SIGNATURES = {
     "matpbr_path_denoise_level_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "matpbr_path_denoise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "matpbr_path_denoise": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_size_t, _P]),
+    "matpbr_path_denoise_diff_prepare": (ctypes.c_int, [_P] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P, _P]),
+    "matpbr_path_denoise_diff_prepare_host": (ctypes.c_int, [_P] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
+    "matpbr_path_denoise_diff_level": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P, _P]),
+    "matpbr_path_denoise_diff_level_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
+    "matpbr_path_denoise_diff_finish": (ctypes.c_int, [_P] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P, _P, _P]),
+    "matpbr_path_denoise_diff_finish_host": (ctypes.c_int, [_P] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P, _P]),
+    "matpbr_path_denoise_diff_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "matpbr_path_denoise_diff": (ctypes.c_int, [_P] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "matpbr_path_denoise_diff_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_size_t]),
 }
 VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
@@ -159,14 +169,20 @@ COLOR_SYMBOLS = ("matpbr_path_render_objects_colors", "matpbr_path_object_color_
 TEXTURE_SYMBOLS = ("matpbr_path_render_objects_textures", "matpbr_path_object_texture_host", "matpbr_path_feature_tints", "matpbr_path_feature_tints_host")
 # and (the differential render)
 DIFF_SYMBOLS = ("matpbr_path_render_objects_diff", "matpbr_path_composite", "matpbr_path_composite_host", "matpbr_path_trace_scene_host")
-LATE_SYMBOLS = SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS + TEXTURE_SYMBOLS + DIFF_SYMBOLS
+# and (the differential render's denoiser)
+DIFF_DENOISE_SYMBOLS = ("matpbr_path_denoise_diff_prepare", "matpbr_path_denoise_diff_prepare_host", "matpbr_path_denoise_diff_level",
+                        "matpbr_path_denoise_diff_level_host", "matpbr_path_denoise_diff_finish", "matpbr_path_denoise_diff_finish_host",
+                        "matpbr_path_denoise_diff_workspace_bytes", "matpbr_path_denoise_diff", "matpbr_path_denoise_diff_host")
+LATE_SYMBOLS = (SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS + TEXTURE_SYMBOLS + DIFF_SYMBOLS +
+                DIFF_DENOISE_SYMBOLS)
 # the feature each of them came with, as `symbol` names it
 _FEATURE = {name: what for names, what in ((SMOOTH_SYMBOLS, "smooth inserted objects"), (DENOISE_SYMBOLS, "the denoiser"),
                                            (PBR_SYMBOLS, "PBR inserted objects"), (LIGHT_SYMBOLS, "emissive inserted objects"),
                                            (ROUGH_SYMBOLS, "rough dielectric inserted objects"),
                                            (COLOR_SYMBOLS, "vertex-coloured inserted objects"),
                                            (TEXTURE_SYMBOLS, "textured inserted objects"),
-                                           (DIFF_SYMBOLS, "the differential render")) for name in names}
+                                           (DIFF_SYMBOLS, "the differential render"),
+                                           (DIFF_DENOISE_SYMBOLS, "the differential render's denoiser")) for name in names}
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
@@ -1031,6 +1047,142 @@ def composite(fg, delta, alpha, photo, scale: float = 1.0) -> torch.Tensor:
     return out
 
 
+# ---- the differential render's denoiser ("Denoiser for the differential render") ----------------------------------
+# A, B: the (fg [H,W,3], delta [H,W,3], alpha [H,W]) triples of two sums of `PathTracer.render_diff`'s outputs over the same number of
+# frames, with independent seeds and equal spp; scale = 1 / (frames summed per half).
+def _halves(A, B, H: int, W: int, image) -> list:
+    """The six images of two triples, in the library's order, each checked and converted by `image(x, shape, what)`."""
+    if len(A) != 3 or len(B) != 3:
+        raise ValueError("A and B must be (fg, delta, alpha) triples")
+    return [image(x, (H, W, 3) if k < 2 else (H, W), f"{name}[{k}] ({('fg', 'delta', 'alpha')[k]})") for name, t in (("A", A), ("B", B))
+            for k, x in enumerate(t)]
+
+
+def _prm_ptr(prm: PathDenoise):
+    return ctypes.cast(ctypes.byref(prm), _P)
+
+
+def denoise_diff_prepare_host(A, B, geom, scale: float = 1.0) -> tuple:
+    """The filter's first step on the CPU with the routine the kernel runs -> (cv0 [H,W,4], cov [H,W]): the own layer's unpremultiplied
+    mean with the prefiltered variance of its luminance, and the own layer's coverage."""
+    H, W = _geom_shape(np.asarray(geom))
+    sc = _composite_scale(scale)
+    hs, g = _halves(A, B, H, W, _host_image), _host_image(geom, (H, W, 8), "geom")
+    cv, cov = np.empty((H, W, 4), np.float32), np.empty((H, W), np.float32)
+    check(symbol("matpbr_path_denoise_diff_prepare_host")(*map(_ptr, hs), _ptr(g), H, W, sc, _ptr(cv), _ptr(cov)), "matpbr_path_denoise_diff_prepare_host")
+    return cv, cov
+
+
+def denoise_diff_level_host(cv, cov, geom, alb, level: int, **params) -> np.ndarray:
+    """One a-trous level of the differential render's filter on the CPU with the routine the kernel runs -> cv [H,W,4]."""
+    prm = denoise_params(**params)
+    H, W = _geom_shape(np.asarray(geom))
+    if not 0 <= int(level) <= 7:
+        raise ValueError(f"level must lie in 0..7, got {level}")
+    c, k, g, al = (_host_image(cv, (H, W, 4), "cv"), _host_image(cov, (H, W), "cov"), _host_image(geom, (H, W, 8), "geom"),
+                   _host_image(alb, (H, W, 3), "alb"))
+    out = np.empty((H, W, 4), np.float32)
+    check(symbol("matpbr_path_denoise_diff_level_host")(_ptr(c), _ptr(k), _ptr(g), _ptr(al), H, W, _prm_ptr(prm), int(level), _ptr(out)),
+          "matpbr_path_denoise_diff_level_host")
+    return out
+
+
+def denoise_diff_finish_host(cv, cov, A, B, geom, scale: float = 1.0) -> tuple:
+    """The filter's last step on the CPU with the routine the kernel runs -> (fg', delta', alpha'): the own layer's filtered colour times
+    its coverage, the other layer's mean and the mean alpha as they are."""
+    H, W = _geom_shape(np.asarray(geom))
+    sc = _composite_scale(scale)
+    c, k, g = _host_image(cv, (H, W, 4), "cv"), _host_image(cov, (H, W), "cov"), _host_image(geom, (H, W, 8), "geom")
+    hs = _halves(A, B, H, W, _host_image)
+    fg, delta, alpha = np.empty((H, W, 3), np.float32), np.empty((H, W, 3), np.float32), np.empty((H, W), np.float32)
+    check(symbol("matpbr_path_denoise_diff_finish_host")(_ptr(c), _ptr(k), *map(_ptr, hs), _ptr(g), H, W, sc, _ptr(fg), _ptr(delta), _ptr(alpha)),
+          "matpbr_path_denoise_diff_finish_host")
+    return fg, delta, alpha
+
+
+def denoise_diff_host(A, B, alb, geom, scale: float = 1.0, **params) -> tuple:
+    """`denoise_diff` on the CPU with the routines the kernels run -> (fg', delta', alpha').  Equal to its separate steps bit for bit."""
+    prm = denoise_params(**params)
+    H, W = _geom_shape(np.asarray(geom))
+    sc = _composite_scale(scale)
+    hs, g, al = _halves(A, B, H, W, _host_image), _host_image(geom, (H, W, 8), "geom"), _host_image(alb, (H, W, 3), "alb")
+    nbytes = int(symbol("matpbr_path_denoise_diff_workspace_bytes")(H, W))
+    ws = np.empty(nbytes // 4, np.float32)
+    fg, delta, alpha = np.empty((H, W, 3), np.float32), np.empty((H, W, 3), np.float32), np.empty((H, W), np.float32)
+    check(symbol("matpbr_path_denoise_diff_host")(*map(_ptr, hs), _ptr(g), _ptr(al), H, W, sc, _prm_ptr(prm), _ptr(fg), _ptr(delta), _ptr(alpha),
+                                                  _ptr(ws), nbytes), "matpbr_path_denoise_diff_host")
+    return fg, delta, alpha
+
+
+@torch.no_grad()
+def denoise_diff_prepare(A, B, geom, scale: float = 1.0) -> tuple:
+    """`denoise_diff_prepare_host` on the device (the current torch stream) -> (cv0 [H,W,4], cov [H,W])."""
+    H, W = _geom_shape(torch.as_tensor(geom))
+    sc = _composite_scale(scale)
+    dev = _device_of(geom, *A, *B)
+    hs = _halves(A, B, H, W, lambda x, shape, what: _device_image(x, shape, what, dev))
+    g = _device_image(geom, (H, W, 8), "geom", dev)
+    cv, cov = torch.empty(H, W, 4, device=dev, dtype=torch.float32), torch.empty(H, W, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_denoise_diff_prepare")(*(h.data_ptr() for h in hs), g.data_ptr(), H, W, sc, cv.data_ptr(), cov.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream), "matpbr_path_denoise_diff_prepare")
+    return cv, cov
+
+
+@torch.no_grad()
+def denoise_diff_level(cv, cov, geom, alb, level: int, **params) -> torch.Tensor:
+    """`denoise_diff_level_host` on the device (the current torch stream) -> cv [H,W,4]."""
+    prm = denoise_params(**params)
+    H, W = _geom_shape(torch.as_tensor(geom))
+    if not 0 <= int(level) <= 7:
+        raise ValueError(f"level must lie in 0..7, got {level}")
+    dev = _device_of(geom, cv, cov, alb)
+    c, k = _device_image(cv, (H, W, 4), "cv", dev), _device_image(cov, (H, W), "cov", dev)
+    g, al = _device_image(geom, (H, W, 8), "geom", dev), _device_image(alb, (H, W, 3), "alb", dev)
+    out = torch.empty(H, W, 4, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_denoise_diff_level")(c.data_ptr(), k.data_ptr(), g.data_ptr(), al.data_ptr(), H, W, _prm_ptr(prm), int(level),
+                                                   out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "matpbr_path_denoise_diff_level")
+    return out
+
+
+@torch.no_grad()
+def denoise_diff_finish(cv, cov, A, B, geom, scale: float = 1.0) -> tuple:
+    """`denoise_diff_finish_host` on the device (the current torch stream) -> (fg', delta', alpha')."""
+    H, W = _geom_shape(torch.as_tensor(geom))
+    sc = _composite_scale(scale)
+    dev = _device_of(geom, cv, cov, *A, *B)
+    c, k, g = _device_image(cv, (H, W, 4), "cv", dev), _device_image(cov, (H, W), "cov", dev), _device_image(geom, (H, W, 8), "geom", dev)
+    hs = _halves(A, B, H, W, lambda x, shape, what: _device_image(x, shape, what, dev))
+    fg, delta = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+    alpha = torch.empty(H, W, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_denoise_diff_finish")(c.data_ptr(), k.data_ptr(), *(h.data_ptr() for h in hs), g.data_ptr(), H, W, sc, fg.data_ptr(),
+                                                    delta.data_ptr(), alpha.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+          "matpbr_path_denoise_diff_finish")
+    return fg, delta, alpha
+
+
+@torch.no_grad()
+def denoise_diff(A, B, alb, geom, scale: float = 1.0, workspace: Optional[torch.Tensor] = None, **params) -> tuple:
+    """The differential render's filter on the device (the current torch stream): the triples A and B, the albedo guide alb [H,W,3] and
+    the features geom [H,W,8] -> (fg', delta', alpha'), which `composite(fg', delta', alpha', photo, 1.0)` puts into the photograph.
+    Equal to `denoise_diff_prepare`, `levels` calls of `denoise_diff_level` and `denoise_diff_finish`, bit for bit.  `workspace`: a uint8
+    device tensor of at least matpbr_path_denoise_diff_workspace_bytes (default: allocated here)."""
+    prm = denoise_params(**params)
+    H, W = _geom_shape(torch.as_tensor(geom))
+    sc = _composite_scale(scale)
+    dev = _device_of(geom, alb, *A, *B)
+    hs = _halves(A, B, H, W, lambda x, shape, what: _device_image(x, shape, what, dev))
+    al, g = _device_image(alb, (H, W, 3), "alb", dev), _device_image(geom, (H, W, 8), "geom", dev)
+    nbytes = int(symbol("matpbr_path_denoise_diff_workspace_bytes")(H, W))
+    if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    fg, delta = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+    alpha = torch.empty(H, W, device=dev, dtype=torch.float32)
+    check(symbol("matpbr_path_denoise_diff")(*(h.data_ptr() for h in hs), g.data_ptr(), al.data_ptr(), H, W, sc, _prm_ptr(prm), fg.data_ptr(),
+                                             delta.data_ptr(), alpha.data_ptr(), workspace.data_ptr(), nbytes,
+                                             torch.cuda.current_stream(dev).cuda_stream), "matpbr_path_denoise_diff")
+    return fg, delta, alpha
+
+
 class PathTracer:
     """One mesh in the renderer's frame (camera at the origin looking down -z, `fov_x_deg` horizontal field of view, H x W pixels).
     The BVH is built once on the host and kept on the device; `render` takes the maps and the envmap of each frame.
@@ -1271,6 +1423,21 @@ class PathTracer:
             self._dn_ws = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
         to = lambda x: x.to(self.device) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x)).to(self.device)
         return denoise(to(A), to(B), to(alb), to(geom), workspace=self._dn_ws, **params)
+
+    @torch.no_grad()
+    def denoise_diff(self, A, B, alb, geom, scale: float = 1.0, **params) -> tuple:
+        """The a-trous filter over two halves of `render_diff` ("Denoiser for the differential render"): A and B
+        are (fg, delta, alpha) triples, each a sum over the same number of frames with independent seeds and equal spp, `scale` 1 / (the
+        frames summed per half) -> (fg', delta', alpha'), which `composite(fg', delta', alpha', photo, 1.0)` puts into the photograph.
+        Each pixel's own layer is filtered (fg where the camera ray through its centre lands on an object, delta elsewhere); the other
+        layer and alpha pass through as their means.  `params`: `denoise`'s.  Forward only."""
+        if tuple(torch.as_tensor(geom).shape) != (self.H, self.W, 8):
+            raise ValueError(f"geom must be [{self.H},{self.W},8], got {list(torch.as_tensor(geom).shape)}")
+        nbytes = int(symbol("matpbr_path_denoise_diff_workspace_bytes")(self.H, self.W))
+        if self._dn_ws is None or self._dn_ws.numel() < nbytes:
+            self._dn_ws = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        to = lambda x: x.to(self.device) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x)).to(self.device)
+        return denoise_diff(tuple(map(to, A)), tuple(map(to, B)), to(alb), to(geom), scale, workspace=self._dn_ws, **params)
 
     @torch.no_grad()
     def render_trans(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, mask, bg, ior: float = 1.2,

@@ -450,7 +450,8 @@ def _oi_photo(scene_dir: str, photo_path: Optional[str], atrous: bool, env_scale
     """The photograph `render_oi(composite=True)` composites into, linear float32 [H,W,3] of the maps' size; ValueError for what the
     composite does not do or cannot read, before any GPU work."""
     if atrous:
-        raise ValueError("composite knows no denoise='atrous': the filter takes a radiance image, and the composite adds a signed difference")
+        raise ValueError("composite knows no denoise='atrous': the filter takes a radiance image, and the composite adds a signed difference "
+                         "(composite_denoise=True runs the differential render's own filter)")
     if float(env_scale) != 1.0:
         raise ValueError(f"composite needs env_scale 1, got {env_scale}: the photograph was taken under the envmap as it is and is not dimmed")
     path = photo_path if photo_path is not None else os.path.join(scene_dir, "gt_image.exr")
@@ -477,7 +478,8 @@ def _oi_photo(scene_dir: str, photo_path: Optional[str], atrous: bool, env_scale
 def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
               denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
-              object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None) -> str:
+              object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None,
+              composite_denoise: bool = False) -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -502,7 +504,11 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     instead of re-rendering the fitted scene: the `n_iter` frames of `PathTracer.render_diff` are summed and composited once, into
     mi_oic_<name>_<env>.exr / .png.  A pixel no sample of which met an object keeps the photograph's bits; through glass the
     re-rendered scene shows, not the photograph.  With it `denoise="atrous"`, an `env_scale` other than 1 and a missing or wrongly
-    sized photograph are a ValueError before any GPU work."""
+    sized photograph are a ValueError before any GPU work.  `composite_denoise` (with `composite`, even `spp`): the differential
+    render's own a-trous filter ("Denoiser for the differential render"): each of the `n_iter` frames becomes
+    two `render_diff` calls of spp / 2, seeds seed + 2 i (summed into one half) and seed + 2 i + 1 (into the other), and
+    `PathTracer.denoise_diff` filters each pixel's own layer before the composite; a pixel farther than 63 pixels (5 levels) from
+    every touched one still keeps the photograph's bits.  The output names are `composite`'s."""
     from . import mesh as _mesh
     from . import pathtrace as _pathtrace
 
@@ -523,6 +529,10 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     if object_colors not in OI_COLORS:
         raise ValueError(f"object_colors must be 'none', 'vertex' or 'vertex_linear', got {object_colors!r}")
     atrous = _check_denoise(denoise, "path", spp)
+    if composite_denoise and not composite:
+        raise ValueError("composite_denoise needs composite=True: it filters the differential render (denoise='atrous' filters the plain one)")
+    if composite_denoise and (spp < 2 or spp % 2):
+        raise ValueError(f"composite_denoise splits every frame into two halves of spp / 2 samples: spp must be even, got {spp}")
     _scaled_env(np.zeros(0, np.float32), env_scale)
     photo = _oi_photo(scene_dir, photo_path, atrous, env_scale) if composite else None
     env_path = find_envmap_oi(save_name, env_path, input_path)
@@ -544,7 +554,17 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     pt = _path_tracer(scene_dir, save_name, mat, device, objects)
     env = _scaled_env(load_image(env_path), env_scale)
     tabs = pt.tables(env)
-    if composite:
+    if composite and composite_denoise:
+        halves = [None, None]
+        for i in range(n_iter):
+            for k in (0, 1):
+                frame = pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, seed + 2 * i + k, tables=tabs)[:3]
+                halves[k] = frame if halves[k] is None else tuple(x + y for x, y in zip(halves[k], frame))
+        geom = pt.features()
+        tint = pt.feature_tints() if pt.stats["n_textured_objects"] else pt.feature_colors() if pt.stats["n_colored_objects"] else None
+        guide = albedo_guide(geom, mat["albedo"], [h[1] for h in have], tint)
+        img = _pathtrace.composite(*pt.denoise_diff(halves[0], halves[1], guide, geom, 1.0 / n_iter), torch.from_numpy(photo).to(device), 1.0)
+    elif composite:
         sums = None
         for i in range(n_iter):
             frame = pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, spp, max_depth, seed + i, tables=tabs)[:3]

@@ -54,6 +54,11 @@ def parse_args(argv=None):
                     help="--mode oi: differential rendering (Debevec 1998): the photograph with the objects, their shadows, bounce light and "
                          "reflections added, not a re-render of the fitted scene; pixels nothing reaches keep the photograph's bits.  Writes "
                          "mi_oic_<name>_<env>.exr / .png.  Not with --denoise atrous or an --env_scale other than 1")
+    ap.add_argument("--oi_composite_denoise", action="store_true",
+                    help="--oi_composite: split every frame into two differential renders of spp/2 with independent seeds and pass each "
+                         "pixel's own layer (the object where it is seen, else what it adds to and takes from the scene) through the "
+                         "a-trous filter before the composite (needs an even --spp); pixels farther than the filter's reach from every "
+                         "touched one keep the photograph's bits")
     ap.add_argument("--oi_photo", type=str, default=None, metavar="PATH",
                     help="--oi_composite: the photograph, of the maps' size (default <scene>/gt_image.exr, linear, as the pipeline writes it; a "
                          ".png holds display values and is decoded as the pipeline decodes its input)")
@@ -70,7 +75,12 @@ def parse_args(argv=None):
     if a.oi_photo is not None and not a.oi_composite:
         ap.error("--oi_photo needs --oi_composite")
     if a.oi_composite and a.denoise == "atrous":
-        ap.error("--oi_composite knows no --denoise atrous: the filter takes a radiance image, not a signed difference")
+        ap.error("--oi_composite knows no --denoise atrous: the filter takes a radiance image, not a signed difference "
+                 "(--oi_composite_denoise runs the differential render's own filter)")
+    if a.oi_composite_denoise and not a.oi_composite:
+        ap.error("--oi_composite_denoise needs --oi_composite")
+    if a.oi_composite_denoise and (a.spp < 2 or a.spp % 2):
+        ap.error("--oi_composite_denoise splits every frame into two halves of spp/2 samples: --spp must be even")
     if a.oi_composite and a.env_scale != 1.0:
         ap.error("--oi_composite needs --env_scale 1: the photograph was taken under the envmap as it is and is not dimmed")
     if a.denoise == "atrous":
@@ -98,7 +108,8 @@ def main(argv=None):
         print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
                                                  object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene,
                                                  env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture,
-                                                 **({"composite": True, "photo_path": a.oi_photo} if a.oi_composite else {})))
+                                                 **({"composite": True, "photo_path": a.oi_photo} if a.oi_composite else {}),
+                                                 **({"composite_denoise": True} if a.oi_composite_denoise else {})))
     else:
         raise ValueError("Invalid mode")
 
