@@ -414,6 +414,40 @@ int matpbr_path_composite_host(const float* fg_sum, const float* delta_sum, cons
 int matpbr_path_trace_scene_host(const void* nodes, const void* tris, const float* o, const float* d, long N, float tmin, float tmax,
                                  float* t_hit, int32_t* tri_hit, long n_scene_tri, int any);
 
+/* The differential render with the photograph seen through inserted glass ("Seen through glass"), forward only.
+ * Arguments: matpbr_path_render_objects_diff's, then photo[H,W,3] (DEVICE; finite and >= 0 is the caller's contract) and
+ * through[H,W,3] (DEVICE).  A sample is see-through where c_s = 1, every vertex so far was a dielectric one (kind 1, flat or smooth)
+ * and the ray traced at depth k >= 1 lands on the front of a triangle of id < n_scene_tri at the point p.  It adds
+ * thr_k photo[texel(p)] to `through` (thr_k: the chain's throughput; texel: the one the depth mesh's vertex reads its maps at), before
+ * the max_depth test.  Where k + 1 < max_depth and the table holds an object of kind 4 or a traversal of the first walk after the
+ * landing trace returned an inserted triangle, the sample is walked again from the camera ray, the same chain, with every triangle of
+ * id >= n_scene_tri skipped from depth k on and the envmap as the only emitter, and fg takes L_with,s - L_tail,s; otherwise the two
+ * tails are the same arithmetic and fg takes nothing, with no subtraction: such a sample is exactly thr_k photo.  A chain that ends on a miss, on another kind of object, on a light, on the sheet's back or inside the
+ * glass at max_depth is not see-through, and every such sample keeps matpbr_path_render_objects_diff's rule.  through is a mean over
+ * spp as fg is; delta and alpha are matpbr_path_render_objects_diff's bits; rewalked counts both kinds of second walk.  The picture
+ * is matpbr_path_composite with fg + through in fg's place.  Every split into launches gives the same bits.  Invalid arguments,
+ * besides that entry point's: photo or through NULL. */
+int matpbr_path_render_objects_through(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                       float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                       int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                       const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                       const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                       const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                       const float* photo, float* through);
+/* The camera chain of matpbr_path_render_objects_through on the CPU (every pointer HOST), from the routines the kernel runs: the
+ * traversal of matpbr_path_trace_host, the dielectric samplers, the spawn offset and the texel lookup.  Lane l is sample sample[l] of
+ * pixel pixel[l] (a flat index into [H,W]) under seed seed[l].  objects, obj_nrm (nullable where no object is smooth) and n_scene_tri
+ * as the render takes them; the table may hold every kind and flag, and the chain reads the kind, the smooth flag and a dielectric's p.
+ * depth[l] = the landing depth k, -1 where the sample is not see-through; texel[l] = the flat texel the landing point projects to;
+ * thr[l,3] = thr_k; o[l,3], d[l,3] = the ray traced at depth k (-1 and zeros where depth is -1).  Invalid: a NULL pointer other than
+ * obj_nrm, N < 0, H or W <= 0, a bad fov, max_depth outside 1..16, n_objects == 0, a bad table, a pixel outside the image, a
+ * negative sample. */
+int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,
+                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                   const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N, int32_t* depth, int32_t* texel,
+                                   float* thr, float* o, float* d);
+
 /* matpbr_path_render with the depth mesh shading as TransBSDF (myutils/mi_plugin.py:1477-1771), forward only.  mask[H,W] (uint8,
  * DEVICE, non-zero = edited) and bg[H,W,3] (fp32, DEVICE, the photograph seen through the glass) are read by the enqueued work;
  * `edit` is HOST memory, copied before the call returns.  Where the texel a vertex reads is masked, the BSDF is the glass of

@@ -33,11 +33,16 @@ struct PathArgs {
 };
 
 // spawn offset along the (camera-side) face normal, relative to the point's magnitude
-__device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1.0f + fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]))); }
+__host__ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1e-5f * (1.0f + fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]))); }
 
 // (DiffObjects) the id from which the traversals skip triangles: none in a sample's first trip, the inserted ones in its second
 template <class Objects> __device__ __forceinline__ int id_limit_of(const Objects&, bool) { return 0; }
 __device__ __forceinline__ int id_limit_of(const DiffObjects& ot, bool second) { return second ? ot.n_scene_tri : INT32_MAX; }
+// (ThroughObjects) the second trip of a see-through sample replays its chain over every triangle and skips the inserted ones from its
+// landing depth `land` on; land = -1 (not see-through) skips them from the camera ray on, DiffObjects' rule
+__device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second, int depth, int land) {
+    return second && depth >= land ? ot.n_scene_tri : INT32_MAX;
+}
 
 // samples [s0, s1) of every pixel added to out (first: start from 0; last: divide by spp).  OBJ: the BVH holds inserted objects
 // (Objects = ObjTable, passed by value); EDIT: transparency editing (Objects = TransEdit, by value in the table's place).  With
@@ -60,10 +65,16 @@ __device__ __forceinline__ int id_limit_of(const DiffObjects& ot, bool second) {
 // ray landed on an inserted triangle (`cov`) and whether any trace returned one (`touched`; a light in the table touches every
 // sample).  Trip 1 runs where touched && !cov: the same sample from the camera ray on, with every triangle of id >= n_scene_tri skipped
 // and the envmap as the only emitter.  The sums live in the table's buffers between samples, not in registers.  Every `if (DIFF ...)`
-// folds away in the other ten.
+// folds away in the other ten.  THROUGH: DIFF with the photograph behind inserted glass (Objects = ThroughObjects; DESIGN.md section 1.4,
+// "Seen through glass").  Trip 0 follows the camera chain (`chain`: every vertex so far was a dielectric one); where it lands on the
+// depth mesh's front at depth >= 1 it adds thr photo[texel] to `through`, records the depth in `land` and starts `touched` afresh.  Trip 1
+// of such a sample runs where touched && land + 1 < max_depth: the same sample from the camera ray on, so the same chain, with the
+// inserted triangles skipped from depth `land` on and the envmap as the only emitter; fg takes trip 0 minus trip 1.  Every
+// `if (THROUGH ...)` folds away in the other eleven.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool DIFF = std::is_same<Objects, DiffObjects>::value;
+    constexpr bool THROUGH = std::is_same<Objects, ThroughObjects>::value;
+    constexpr bool DIFF = std::is_same<Objects, DiffObjects>::value || THROUGH;
     constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF;
     constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
@@ -89,6 +100,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
 #pragma unroll
             for (int c = 0; c < 3; ++c) ot.fg[3 * pix + c] = ot.delta[3 * pix + c] = 0.0f;
             ot.alpha[pix] = 0.0f;
+            if constexpr (THROUGH) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ot.through[3 * pix + c] = 0.0f;
+            }
         }
     } else if (!first) {
 #pragma unroll
@@ -100,12 +115,18 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     bool second = false;
     bool cov = false, touched = false;      // trip 0's record
     float Lw[3] = {0.0f, 0.0f, 0.0f};       // trip 0's radiance, kept across trip 1
+    bool chain = false;                     // (THROUGH) trip 0: every vertex so far was a dielectric one
+    int land = -1;                          // (THROUGH) trip 0's record: the depth at which the chain landed on the depth mesh's front
     for (int s = s0; s < s1; ++s) {
         const uint32_t base = pcg_hash(pix_hash + (uint32_t)s);
         if constexpr (DIFF) {
             if (!second) {
                 cov = false;
                 touched = ot.lt.n > 0;   // a light changes n_e, and through it every emitter sample
+                if constexpr (THROUGH) {
+                    chain = true;
+                    land = -1;
+                }
             }
             n_e = (have_tab ? 1 : 0) + (second ? 0 : ot.lt.n);   // trip 1: the envmap alone
             n_ef = (float)n_e;
@@ -125,11 +146,34 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             float t = FLT_MAX;
             ++n_rays;
             // (DIFF) the traversals skip the triangles from an id on: none in trip 0, the inserted ones in trip 1
-            const int k = trace<false, DIFF>(q.nodes, q.tris, o, d, 0.0f, t, stk, id_limit_of(ot, second));
+            int id_limit = id_limit_of(ot, second);
+            if constexpr (THROUGH) id_limit = id_limit_at(ot, second, depth, land);   // (THROUGH) a function of the depth
+            const int k = trace<false, DIFF>(q.nodes, q.tris, o, d, 0.0f, t, stk, id_limit);
             if constexpr (DIFF) {
-                if (k >= 0 && tri_id(q.tris[3 * k]) >= ot.n_scene_tri) {   // trip 0 alone can meet one
+                if (k >= 0 && tri_id(q.tris[3 * k]) >= ot.n_scene_tri) {   // trip 0 alone can meet one ((THROUGH) and trip 1's chain)
                     touched = true;
                     if (depth == 0) cov = true;
+                }
+            }
+            if constexpr (THROUGH) {
+                // the chain lands on the depth mesh: on its front the photograph at the point's texel is what arrives from there, added
+                // before the max_depth test as a light's emission is; `touched` then records what the objects change after the landing
+                if (!second && chain && depth >= 1 && k >= 0 && tri_id(q.tris[3 * k]) < ot.n_scene_tri) {
+                    chain = false;
+                    const float4 B = q.tris[3 * k + 1], C = q.tris[3 * k + 2];
+                    const float e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+                    float n[3];
+                    cross3(e1, e2, n);
+                    if (-dot3(n, d) * rsq(dot3(n, n)) > 0.0f) {
+                        float p[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) p[c] = fmaf(t, d[c], o[c]);
+                        const long tq = screen_texel(p, q.f_ndc, q.aspect, q.H, q.W);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) ot.through[3 * pix + c] += thr[c] * ot.photo[3 * tq + c];
+                        land = depth;
+                        touched = ot.lt.n > 0;
+                    }
                 }
             }
             if (k < 0) {   // escaped: the envmap, MIS-weighted against emitter sampling after a BSDF sample
@@ -196,6 +240,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             if constexpr (TEX) {
                 textured = (kind & MATPBR_PATH_OBJECT_TEXTURED) != 0;
                 kind &= ~MATPBR_PATH_OBJECT_TEXTURED;
+            }
+            if constexpr (THROUGH) {
+                if (!second) chain = chain && kind == MATPBR_PATH_BSDF_DIELECTRIC;   // rough glass and every other kind end the chain
             }
             // a hit on the back of a triangle ends the path (glass shades from both sides)
             const bool rough = ROUGH && kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC;   // (ROUGH) shades from both sides, like glass
@@ -344,7 +391,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                     if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
                         float ts = LIGHT ? ts_max : FLT_MAX;
                         ++n_rays;
-                        const int ks = trace<true, DIFF>(q.nodes, q.tris, po, wl, 0.0f, ts, stk, id_limit_of(ot, second));   // the occluder
+                        const int ks = trace<true, DIFF>(q.nodes, q.tris, po, wl, 0.0f, ts, stk, id_limit);   // the occluder
                         if constexpr (DIFF) {
                             if (ks >= 0 && tri_id(q.tris[3 * ks]) >= ot.n_scene_tri) touched = true;
                         }
@@ -400,15 +447,30 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             if (!second) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) Lw[c] = L[c];
-                if (touched && !cov) {   // the same s once more
+                if constexpr (THROUGH) {
+                    if (touched && (!cov || (land >= 0 && land + 1 < q.max_depth))) {   // the same s once more; (cov) the landing's tail
+                        second = true;
+                        --s;
+                        continue;
+                    }
+                } else if (touched && !cov) {   // the same s once more
                     second = true;
                     --s;
                     continue;
                 }
             }
             if (cov) {
+                if (THROUGH && second) {   // a see-through sample walked twice: what the objects change in the landing's light
 #pragma unroll
-                for (int c = 0; c < 3; ++c) ot.fg[3 * pix + c] += Lw[c];
+                    for (int c = 0; c < 3; ++c) ot.fg[3 * pix + c] += Lw[c] - L[c];
+                    if (ot.rewalked) ot.rewalked[pix] += 1u;
+                } else if (THROUGH && land >= 0) {
+                    // a see-through sample with an untouched tail: both tails are the same arithmetic, so it adds exactly nothing to fg
+                    // (a tail that max_depth cuts has Lw = 0: nothing is added along a dielectric chain)
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) ot.fg[3 * pix + c] += Lw[c];
+                }
                 ot.alpha[pix] += 1.0f;
             } else if (second) {   // an untouched sample adds nothing: no subtraction
 #pragma unroll
@@ -428,6 +490,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             for (int c = 0; c < 3; ++c) {
                 ot.fg[3 * pix + c] *= sc;
                 ot.delta[3 * pix + c] *= sc;
+                if constexpr (THROUGH) ot.through[3 * pix + c] *= sc;
             }
             ot.alpha[pix] *= sc;
         }
@@ -1346,6 +1409,119 @@ int matpbr_path_render_objects_diff(const void* nodes, const void* tris, const f
     static_cast<TexObjects&>(dt) = tex_objects(s);
     dt.fg = fg; dt.delta = delta; dt.alpha = alpha; dt.rewalked = rewalked;
     return launch_frame(f, q, dt);
+}
+
+int matpbr_path_render_objects_through(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                       float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                       int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                       const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                       const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                       const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                       const float* photo, float* through) {
+    float* const out = nullptr;   // the sums go to the table's buffers
+    const Frame f = RENDER_FRAME;
+    PathArgs q{};
+    Scene s;
+    if (!fg || !delta || !alpha || !photo || !through || n_objects <= 0 || !frame_args(f, q) ||
+        !objects_scene(7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    ThroughObjects tt{};
+    static_cast<TexObjects&>(tt) = tex_objects(s);
+    tt.fg = fg; tt.delta = delta; tt.alpha = alpha; tt.rewalked = rewalked;
+    tt.photo = photo; tt.through = through;
+    return launch_frame(f, q, tt);
+}
+
+int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,
+                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                   const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N, int32_t* depth, int32_t* texel,
+                                   float* thr, float* o, float* d) {
+    ObjTable ot{};
+    ObjCounts cnt;
+    if (!nodes || !tris || !pixel || !seed || !sample || !depth || !texel || !thr || !o || !d || N < 0 || H <= 0 || W <= 0 ||
+        !fov_valid(fov_x_deg) || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || n_objects <= 0 ||
+        !scene_table(objects, n_objects, kAcceptAll | kAcceptColor | kAcceptTexture, obj_nrm, n_scene_tri, nullptr, ot, cnt))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long l = 0; l < N; ++l)
+        if (pixel[l] < 0 || pixel[l] >= (long)H * W || sample[l] < 0) return MATPBR_PATH_ERR_INVALID_ARG;
+    const float4 *Nd = static_cast<const float4*>(nodes), *T = static_cast<const float4*>(tris);
+    const Camera cam = camera(H, W, fov_x_deg);
+    const uint32_t flags = MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_TEXTURED;
+    for (long l = 0; l < N; ++l) {
+        const int i = pixel[l] / W, j = pixel[l] % W;
+        const uint32_t base = pcg_hash(pcg_hash(pcg_hash(seed[l]) + (uint32_t)pixel[l]) + (uint32_t)sample[l]);
+        const float x = (float)j - 0.5f + rng_u(base, 0, 0), y = (float)i - 0.5f + rng_u(base, 0, 1);
+        float ro[3] = {0.0f, 0.0f, 0.0f}, rd[3] = {(x - cam.cx) / cam.f_pix, -(y - cam.cy) / cam.f_pix, -1.0f};
+        {
+            const float il = 1.0f / sqrtf(dot3h(rd, rd));
+            for (int c = 0; c < 3; ++c) rd[c] *= il;
+        }
+        float w[3] = {1.0f, 1.0f, 1.0f};
+        int found = -1;
+        long tq = -1;
+        for (int dp = 0;; ++dp) {
+            HostStack stk;
+            float t = FLT_MAX;
+            const int k = trace<false>(Nd, T, ro, rd, 0.0f, t, stk);
+            if (k < 0) break;   // the envmap
+            const int id = tri_id(T[3 * k]);
+            const float4 A = T[3 * k], B = T[3 * k + 1], C = T[3 * k + 2];
+            const float v0[3] = {A.x, A.y, A.z}, e1[3] = {B.x, B.y, B.z}, e2[3] = {C.x, C.y, C.z};
+            float n[3];
+            cross3(e1, e2, n);
+            {
+                const float il = 1.0f / sqrtf(dot3h(n, n));
+                for (int c = 0; c < 3; ++c) n[c] *= il;
+            }
+            const float wo[3] = {-rd[0], -rd[1], -rd[2]};
+            float p[3];
+            for (int c = 0; c < 3; ++c) p[c] = fmaf(t, rd[c], ro[c]);
+            if (id < n_scene_tri) {   // the depth mesh: a landing on its front at depth >= 1, else the chain's end
+                if (dp >= 1 && dot3h(n, wo) > 0.0f) {
+                    found = dp;
+                    tq = screen_texel(p, cam.f_ndc, cam.aspect, H, W);
+                }
+                break;
+            }
+            int kind = 0;
+            float op[3] = {0.0f, 0.0f, 0.0f};
+            object_match(ot, id, [&](int, const MatpbrPathObject& ob) {
+                kind = ob.kind;
+                op[0] = ob.p[0]; op[1] = ob.p[1]; op[2] = ob.p[2];
+            });
+            const bool smooth = (kind & MATPBR_PATH_OBJECT_SMOOTH) != 0;
+            kind &= ~(int)flags;
+            if (kind != MATPBR_PATH_BSDF_DIELECTRIC || dp + 1 >= max_depth) break;   // another kind, or still in the glass at max_depth
+            float wi[3], wgt[3], pdf_s;
+            int fl;
+            if (smooth) {
+                float ns[3], su, sv;
+                tri_uv(v0, e1, e2, ro, rd, su, sv);
+                smooth_normal(obj_nrm + 9 * (long)(id - n_scene_tri), su, sv, n, ns);
+                smooth_side(n, wo, ns);
+                object_sample_shading(kind, op, n, ns, wo, rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wi, wgt, pdf_s, fl);
+            } else {
+                object_sample(kind, op, n, wo, rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wi, wgt, pdf_s, fl);
+            }
+            const float eps = spawn_eps(p);
+            const float side = dot3h(n, wi) > 0.0f ? eps : -eps;   // spawn on the side the new ray leaves on
+            for (int c = 0; c < 3; ++c) {
+                w[c] *= wgt[c];
+                ro[c] = fmaf(side, n[c], p[c]);
+                rd[c] = wi[c];
+            }
+            if (!(w[0] > 0.0f || w[1] > 0.0f || w[2] > 0.0f)) break;
+        }
+        depth[l] = found;
+        texel[l] = (int32_t)tq;
+        for (int c = 0; c < 3; ++c) {
+            thr[3 * l + c] = found >= 0 ? w[c] : 0.0f;
+            o[3 * l + c] = found >= 0 ? ro[c] : 0.0f;
+            d[3 * l + c] = found >= 0 ? rd[c] : 0.0f;
+        }
+    }
+    return MATPBR_PATH_OK;
 }
 
 int matpbr_path_composite(const float* fg_sum, const float* delta_sum, const float* alpha_sum, const float* photo, int H, int W, float scale,

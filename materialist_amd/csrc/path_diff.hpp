@@ -14,6 +14,15 @@ struct DiffObjects : TexObjects {
     float* alpha;         // [H,W]
     uint32_t* rewalked;   // [H,W], nullable: second walks per pixel, added to
 };
+// DiffObjects with the photograph behind inserted glass ("Seen through glass").  A sample whose camera ray
+// lands on an object and leaves it through dielectric vertices alone lands on the depth mesh's front at depth k: there it adds
+// thr_k photo[screen_texel(p)] to `through`, and, where its walk met an inserted triangle after that landing (or the table holds a
+// light) and k + 1 < max_depth, it is walked again with the inserted triangles skipped from depth k on and the envmap as the only
+// emitter; fg then takes the difference of the two walks.
+struct ThroughObjects : DiffObjects {
+    const float* photo;   // [H,W,3], finite and >= 0
+    float* through;       // [H,W,3]
+};
 
 // out = max(0, (fg + delta) scale + (1 - alpha scale) photo) of one channel: every product and sum rounded on its own, so the device
 // and the CPU give the same bits

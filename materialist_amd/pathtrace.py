@@ -8,7 +8,8 @@ puts both behind autograd.  `PathTracer.features` and `PathTracer.denoise` are t
 "Denoiser"): first-hit features and a variance-guided a-trous filter over two half renders, forward only.  `PathTracer.render_diff`
 and `composite` are the differential render ("Differential render"): what inserted objects add to and take
 from a photograph of the scene, forward only; `PathTracer.denoise_diff` is its own a-trous filter over two halves of it ("Denoiser
-for the differential render").  There is no fallback: a missing or failing library raises.
+for the differential render"); `PathTracer.render_diff_through` is the differential render with the photograph shown, refracted,
+behind inserted clear glass ("Seen through glass").  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -120,6 +121,9 @@ SIGNATURES = {
     "matpbr_path_feature_tints_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P, _P,
                                                       ctypes.c_long, _P]),
     "matpbr_path_render_objects_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 4),
+    "matpbr_path_render_objects_through": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 6),
+    "matpbr_path_through_chain_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P,
+                                                      ctypes.c_long] + [_P] * 5),
     "matpbr_path_composite": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
     "matpbr_path_composite_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
     "matpbr_path_trace_scene_host": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_long, ctypes.c_float, ctypes.c_float, _P, _P, ctypes.c_long, ctypes.c_int]),
@@ -173,8 +177,10 @@ DIFF_SYMBOLS = ("matpbr_path_render_objects_diff", "matpbr_path_composite", "mat
 DIFF_DENOISE_SYMBOLS = ("matpbr_path_denoise_diff_prepare", "matpbr_path_denoise_diff_prepare_host", "matpbr_path_denoise_diff_level",
                         "matpbr_path_denoise_diff_level_host", "matpbr_path_denoise_diff_finish", "matpbr_path_denoise_diff_finish_host",
                         "matpbr_path_denoise_diff_workspace_bytes", "matpbr_path_denoise_diff", "matpbr_path_denoise_diff_host")
+# and (the photograph seen through inserted glass)
+THROUGH_SYMBOLS = ("matpbr_path_render_objects_through", "matpbr_path_through_chain_host")
 LATE_SYMBOLS = (SMOOTH_SYMBOLS + DENOISE_SYMBOLS + PBR_SYMBOLS + LIGHT_SYMBOLS + ROUGH_SYMBOLS + COLOR_SYMBOLS + TEXTURE_SYMBOLS + DIFF_SYMBOLS +
-                DIFF_DENOISE_SYMBOLS)
+                DIFF_DENOISE_SYMBOLS + THROUGH_SYMBOLS)
 # the feature each of them came with, as `symbol` names it
 _FEATURE = {name: what for names, what in ((SMOOTH_SYMBOLS, "smooth inserted objects"), (DENOISE_SYMBOLS, "the denoiser"),
                                            (PBR_SYMBOLS, "PBR inserted objects"), (LIGHT_SYMBOLS, "emissive inserted objects"),
@@ -182,11 +188,12 @@ _FEATURE = {name: what for names, what in ((SMOOTH_SYMBOLS, "smooth inserted obj
                                            (COLOR_SYMBOLS, "vertex-coloured inserted objects"),
                                            (TEXTURE_SYMBOLS, "textured inserted objects"),
                                            (DIFF_SYMBOLS, "the differential render"),
-                                           (DIFF_DENOISE_SYMBOLS, "the differential render's denoiser")) for name in names}
+                                           (DIFF_DENOISE_SYMBOLS, "the differential render's denoiser"),
+                                           (THROUGH_SYMBOLS, "the photograph seen through inserted glass")) for name in names}
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
-                  "matpbr_path_render_objects_textures": 13}
+                  "matpbr_path_render_objects_textures": 13, "matpbr_path_render_objects_through": 13}
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -324,6 +331,28 @@ def trace_scene_host(bvh: Dict[str, object], origins: np.ndarray, dirs: np.ndarr
     check(symbol("matpbr_path_trace_scene_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), _ptr(o), _ptr(d), o.shape[0], tmin, tmax, _ptr(t), _ptr(k),
                                                  int(n_scene_tri), int(bool(any))), "matpbr_path_trace_scene_host")
     return t, k
+
+
+def through_chain_host(bvh: Dict[str, object], table: Sequence[PathObject], n_scene_tri: int, H: int, W: int, pixels, seeds, samples,
+                       max_depth: int, obj_nrm: Optional[np.ndarray] = None, fov_x_deg: float = 35.0) -> dict:
+    """The camera chain of `PathTracer.render_diff_through` on the CPU with the routines the kernel runs ("Seen
+    through glass"): lane l is sample samples[l] of pixel pixels[l] (a flat index) under seeds[l], over the host BVH of the merged
+    mesh and `merge_objects`' table (`obj_nrm`: its corner normals, where an object is smooth) -> {"depth" [N] int32: the depth at
+    which the chain lands on the depth mesh's front, -1 where the sample is not see-through; "texel" [N] int32: the texel the landing
+    point projects to; "thr" [N,3]: the chain's throughput; "o", "d" [N,3]: the ray that lands}."""
+    pix = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+    sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), pix.shape))
+    smp = np.ascontiguousarray(np.broadcast_to(np.asarray(samples, dtype=np.int32), pix.shape))
+    tab, _ = _table_ptrs(table)
+    nrm = None if obj_nrm is None else np.ascontiguousarray(obj_nrm, dtype=np.float32)
+    N = pix.size
+    depth, texel = np.empty(N, np.int32), np.empty(N, np.int32)
+    thr, o, d = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
+    check(symbol("matpbr_path_through_chain_host")(_ptr(bvh["nodes"]), _ptr(bvh["tris"]), int(H), int(W), float(fov_x_deg), int(max_depth), tab,
+                                                   len(table), _ptr(nrm) if nrm is not None else None, int(n_scene_tri), _ptr(pix), _ptr(sd),
+                                                   _ptr(smp), N, _ptr(depth), _ptr(texel), _ptr(thr), _ptr(o), _ptr(d)),
+          "matpbr_path_through_chain_host")
+    return {"depth": depth, "texel": texel, "thr": thr, "o": o, "d": d}
 
 
 def env_tables(env: np.ndarray) -> Dict[str, object]:
@@ -1372,6 +1401,36 @@ class PathTracer:
                  torch.cuda.current_stream(dev).cuda_stream, *self.object_args()[:9], *self._texture_args(), fg.data_ptr(), delta.data_ptr(),
                  alpha.data_ptr(), rewalked.data_ptr()), "matpbr_path_render_objects_diff")
         return fg, delta, alpha, rewalked
+
+    @torch.no_grad()
+    def render_diff_through(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, photo, spp: int = 64,
+                            max_depth: int = 4, seed: int = 0, spp_per_launch: int = 8, tables: Optional[tuple] = None,
+                            rays: Optional[torch.Tensor] = None) -> tuple:
+        """`render_diff` with the photograph seen through inserted glass ("Seen through glass") ->
+        (fg [H,W,3], delta [H,W,3], alpha [H,W], through [H,W,3], rewalked [H,W] int32).  `photo` [H,W,3]: the photograph, linear, finite
+        and >= 0.  A sample whose camera ray lands on an object and leaves it through clear glass alone (smooth or flat dielectric
+        vertices) onto the depth mesh's front adds throughput x photo at the landing point's texel to `through`; its fg is then what
+        the objects change in the landing point's light (the sample minus its tail walked again without the objects, where that walk
+        met one; nothing where it met none), and may be negative.  Rough glass, chains that end on another object, on a light, on the
+        envmap or inside the glass at max_depth keep `render_diff`'s rule.  delta and alpha are `render_diff`'s bits; `rewalked`
+        counts both kinds of second walk.  The picture is `composite(fg + through, delta, alpha, photo)`.  Every split into launches
+        gives the same bits.  A tracer without objects, or a photograph of another shape, raises ValueError."""
+        if self.objects is None:
+            raise ValueError("render_diff_through renders what inserted objects change: build the PathTracer with `objects`")
+        ph = torch.as_tensor(photo)
+        if tuple(ph.shape) != (self.H, self.W, 3):
+            raise ValueError(f"photo must be [{self.H},{self.W},3], got {tuple(ph.shape)}")
+        fn = symbol("matpbr_path_render_objects_through")
+        H, W, dev = self.H, self.W, self.device
+        ph = ph.to(dev, torch.float32).contiguous()
+        inputs = self._inputs(albedo, roughness, metallic, envmap, tables)
+        fg, delta = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+        alpha, rewalked = torch.empty(H, W, device=dev, dtype=torch.float32), torch.zeros(H, W, device=dev, dtype=torch.int32)
+        through = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+        check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), rays.data_ptr() if rays is not None else None,
+                 torch.cuda.current_stream(dev).cuda_stream, *self.object_args()[:9], *self._texture_args(), fg.data_ptr(), delta.data_ptr(),
+                 alpha.data_ptr(), rewalked.data_ptr(), ph.data_ptr(), through.data_ptr()), "matpbr_path_render_objects_through")
+        return fg, delta, alpha, through, rewalked
 
     @torch.no_grad()
     def features(self, normal=None) -> torch.Tensor:

@@ -479,7 +479,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
               denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
               object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None,
-              composite_denoise: bool = False) -> str:
+              composite_denoise: bool = False, see_through: bool = False) -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -508,7 +508,15 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     render's own a-trous filter ("Denoiser for the differential render"): each of the `n_iter` frames becomes
     two `render_diff` calls of spp / 2, seeds seed + 2 i (summed into one half) and seed + 2 i + 1 (into the other), and
     `PathTracer.denoise_diff` filters each pixel's own layer before the composite; a pixel farther than 63 pixels (5 levels) from
-    every touched one still keeps the photograph's bits.  The output names are `composite`'s."""
+    every touched one still keeps the photograph's bits.  The output names are `composite`'s.  `see_through` (with `composite`; DESIGN.md
+    section 1.4, "Seen through glass"): behind clear glass the photograph shows, refracted, instead of the re-rendered scene: the
+    frames are `PathTracer.render_diff_through`'s, and fg + through (one fp32 addition) takes fg's place in the composite.  With
+    `composite_denoise` the halves' (fg, delta, alpha) pass the filter as they are and the mean of the halves' `through`,
+    (through_A + through_B) * (0.5 / n_iter), is added to the filtered fg: the filter's guides are the glass surface's and would blur
+    the refracted photograph.  Rough glass stays re-rendered.  Without `composite` it is a ValueError before any other work; with
+    `see_through=False` the code path, and so the bytes, are the ones without it."""
+    if see_through and not composite:
+        raise ValueError("see_through needs composite=True: it shows the photograph behind inserted glass in the differential composite")
     from . import mesh as _mesh
     from . import pathtrace as _pathtrace
 
@@ -554,21 +562,28 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     pt = _path_tracer(scene_dir, save_name, mat, device, objects)
     env = _scaled_env(load_image(env_path), env_scale)
     tabs = pt.tables(env)
+    diff = (lambda n, sd: pt.render_diff_through(mat["albedo"], mat["roughness"], mat["metallic"], env, photo, n, max_depth, sd, tables=tabs)[:4]) if see_through else \
+           (lambda n, sd: pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, n, max_depth, sd, tables=tabs)[:3])
     if composite and composite_denoise:
         halves = [None, None]
         for i in range(n_iter):
             for k in (0, 1):
-                frame = pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, seed + 2 * i + k, tables=tabs)[:3]
+                frame = diff(spp // 2, seed + 2 * i + k)
                 halves[k] = frame if halves[k] is None else tuple(x + y for x, y in zip(halves[k], frame))
         geom = pt.features()
         tint = pt.feature_tints() if pt.stats["n_textured_objects"] else pt.feature_colors() if pt.stats["n_colored_objects"] else None
         guide = albedo_guide(geom, mat["albedo"], [h[1] for h in have], tint)
-        img = _pathtrace.composite(*pt.denoise_diff(halves[0], halves[1], guide, geom, 1.0 / n_iter), torch.from_numpy(photo).to(device), 1.0)
+        fg, delta, alpha = pt.denoise_diff(halves[0][:3], halves[1][:3], guide, geom, 1.0 / n_iter)
+        if see_through:   # the refracted photograph does not pass the filter
+            fg = fg + (halves[0][3] + halves[1][3]) * (0.5 / n_iter)
+        img = _pathtrace.composite(fg, delta, alpha, torch.from_numpy(photo).to(device), 1.0)
     elif composite:
         sums = None
         for i in range(n_iter):
-            frame = pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, spp, max_depth, seed + i, tables=tabs)[:3]
+            frame = diff(spp, seed + i)
             sums = frame if sums is None else tuple(x + y for x, y in zip(sums, frame))
+        if see_through:
+            sums = (sums[0] + sums[3], sums[1], sums[2])
         img = _pathtrace.composite(*sums, torch.from_numpy(photo).to(device), 1.0 / n_iter)
     elif atrous:
         geom = pt.features()

@@ -59,6 +59,11 @@ def parse_args(argv=None):
                          "pixel's own layer (the object where it is seen, else what it adds to and takes from the scene) through the "
                          "a-trous filter before the composite (needs an even --spp); pixels farther than the filter's reach from every "
                          "touched one keep the photograph's bits")
+    ap.add_argument("--oi_see_through", action="store_true",
+                    help="--oi_composite: behind clear inserted glass (a dielectric object, flat or smooth) show the photograph, refracted, "
+                         "plus what the objects change in the light of the point seen, instead of the re-rendered fitted scene.  It does not "
+                         "cover rough (frosted) glass, which stays re-rendered, nor paths that leave the glass towards another object, a "
+                         "lamp or the envmap")
     ap.add_argument("--oi_photo", type=str, default=None, metavar="PATH",
                     help="--oi_composite: the photograph, of the maps' size (default <scene>/gt_image.exr, linear, as the pipeline writes it; a "
                          ".png holds display values and is decoded as the pipeline decodes its input)")
@@ -79,6 +84,8 @@ def parse_args(argv=None):
                  "(--oi_composite_denoise runs the differential render's own filter)")
     if a.oi_composite_denoise and not a.oi_composite:
         ap.error("--oi_composite_denoise needs --oi_composite")
+    if a.oi_see_through and not a.oi_composite:
+        ap.error("--oi_see_through needs --oi_composite")
     if a.oi_composite_denoise and (a.spp < 2 or a.spp % 2):
         ap.error("--oi_composite_denoise splits every frame into two halves of spp/2 samples: --spp must be even")
     if a.oi_composite and a.env_scale != 1.0:
@@ -109,7 +116,8 @@ def main(argv=None):
                                                  object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene,
                                                  env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture,
                                                  **({"composite": True, "photo_path": a.oi_photo} if a.oi_composite else {}),
-                                                 **({"composite_denoise": True} if a.oi_composite_denoise else {})))
+                                                 **({"composite_denoise": True} if a.oi_composite_denoise else {}),
+                                                 **({"see_through": True} if a.oi_see_through else {})))
     else:
         raise ValueError("Invalid mode")
 
