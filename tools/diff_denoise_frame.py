@@ -7,65 +7,24 @@ share of pixels that keep the photograph's bits with the filter and without.  Co
 `denoise` (matpbr_path_denoise, the yardstick) on the same geom and alb, one process, alternating, hip events, the best and the median
 of `--repeats` after a warm-up; the steps on their own; and (with `--isa`, the gfx950 assembly of matpbr_path.hip) the registers and the
 waves per SIMD of the filter's kernels.  Writes profiles/diff_denoise_frame.txt's lines to --out.  Needs a GPU: there is no fallback."""
-import argparse
-import os
-import re
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import object_frame_lib as fl  # puts the repository and tests/ on the path
 
-VGPRS_PER_SIMD, VGPR_GRANULE, MAX_WAVES = 512, 8, 8                      # gfx950: one file for arch and accumulation registers
+import path_oi_fp64 as po
+from materialist_amd import pathtrace as pt
+from materialist_amd.relight import albedo_guide
+
 KERNELS = ("denoise_prepare_kernel", "denoise_level_kernel", "denoise_diff_prepare_kernel", "denoise_diff_level_kernel", "denoise_diff_finish_kernel")
 
 
-def kernel_resources(isa_path):
-    """Per kernel of KERNELS: (VGPRs, allocated, waves per SIMD, scratch bytes, LDS bytes) from the assembly's .amdhsa_ directives."""
-    out = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", open(isa_path).read(), flags=re.S):
-        d = dict(re.findall(r"\.amdhsa_(\w+) (\S+)", m.group(2)))
-        for name in KERNELS:
-            if f"{len(name)}{name}E" in m.group(1):
-                v = int(d["next_free_vgpr"])
-                alloc = -(-v // VGPR_GRANULE) * VGPR_GRANULE
-                out[name] = (v, alloc, min(MAX_WAVES, VGPRS_PER_SIMD // alloc), int(d["private_segment_fixed_size"]), int(d["group_segment_fixed_size"]))
-    return out
-
-
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--isa", default=None, help="the gfx950 assembly of matpbr_path.hip: registers and waves per SIMD are read from it")
-    a_ = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("diff_denoise_frame.py needs a GPU")
-    import path_oi_fp64 as po
-    import path_oi_smooth_fp64 as ps
-    from materialist_amd import mesh, pathtrace as pt
-    from materialist_amd.relight import albedo_guide
-
-    dev = torch.device("cuda:0")
-    z = np.load(os.path.join(ROOT, "tests", "golden", "indoor2.npz"))
-    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-    a = t(z["ref_albedo_u8"].astype(np.float32) / 255.0)
-    r = t(z["ref_roughness_u8"].astype(np.float32)[..., None] / 255.0).clamp(0.07, 1.0)
-    m = t(z["ref_metallic_u8"].astype(np.float32)[..., None] / 255.0)
-    env = z["ref_envmap_f32"]
-    depth = z["depth_pred_f32"]
-    depth = 2 * depth.max() - depth
-    H, W = depth.shape
-    rm = mesh.reference_mesh(depth, 35.0)
-    z0 = 0.6 * float(depth[depth > 0].min())
-    Vs, Ts, _ = ps.icosphere((-0.10 * z0, 0.0, -z0), 0.09 * z0, 3)
-    Vc, Tc = po.cube((0.13 * z0, -0.05 * z0, -z0), 0.13 * z0, (0.3, 0.6, 0.2))
-    objects = [{"vertices": Vs, "triangles": Ts, "bsdf": po.DIFFUSE_08}, {"vertices": Vc, "triangles": Tc, "bsdf": po.DIFFUSE_08}]
-    tracer = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, 35.0, objects=objects)
-    alone = pt.PathTracer(rm["vertices"], rm["triangles"], H, W, 35.0)
+    a_ = fl.arguments(__doc__, "diff_denoise_frame.py", 7, argv, isa=True)
+    f = fl.indoor2_frame()
+    a, r, m, env, H, W = f.a, f.r, f.m, f.env, f.H, f.W
+    objects = [fl.sphere(f, po.DIFFUSE_08), f.cube]
+    tracer, alone = fl.tracer(f, objects), fl.tracer(f)
     tabs = tracer.tables(env)
     diff = lambda spp, seed: tracer.render_diff(a, r, m, env, spp=spp, max_depth=16, seed=seed, tables=tabs)[:3]
     photo = alone.render(a, r, m, env, spp=512, max_depth=16, seed=7, tables=alone.tables(env))
@@ -92,15 +51,6 @@ def main(argv=None):
                      f"over the touched pixels; keeps the photograph's bits in {keeps(den):.4f} of the pixels")
     # cost: the chains alternating, then the steps on their own
     dA, dB = A[1].abs(), B[1].abs()                                     # radiance-like inputs for the yardstick, the same geom and alb
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1), out
-
     cv, cov = pt.denoise_diff_prepare(A, B, geom, 1.0)
     cv0 = pt.denoise_prepare(dA, dB, geom)
     runs = [("denoise_diff (prepare + 5 levels + finish)", lambda: tracer.denoise_diff(A, B, guide, geom, 1.0)),
@@ -111,28 +61,14 @@ def main(argv=None):
     for l in (0, 2, 4):
         runs.append((f"denoise_diff_level {l}", lambda l=l: pt.denoise_diff_level(cv, cov, geom, guide, l)))
         runs.append((f"denoise_level {l}", lambda l=l: pt.denoise_level(cv0, geom, guide, l)))
-    for _, run in runs:
-        run()
-    torch.cuda.synchronize()
-    times = [[] for _ in runs]
-    for _ in range(a_.repeats):
-        for k, (_, run) in enumerate(runs):
-            times[k].append(timed(run)[0])
+    _, times, _ = fl.alternate(f, [lambda rays, run=run: run() for _, run in runs], a_.repeats, count_rays=False)
     lines.append(f"cost, hip events, one process, alternating, best of {a_.repeats} after a warm-up (median); the steps on their own include the "
                  "wrapper's allocation of their output")
     for k, (label, _) in enumerate(runs):
         lines.append(f"{label}: {min(times[k]) * 1e3:.1f} us ({float(np.median(times[k])) * 1e3:.1f})")
     lines.append(f"denoise_diff / denoise: best {min(times[0]) / min(times[1]):.3f}, median {np.median(times[0]) / np.median(times[1]):.3f}; per tap "
                  "the new level reads 64 B against 60 B")
-    if a_.isa:
-        for name, (v, alloc, waves, scratch, lds) in kernel_resources(a_.isa).items():
-            lines.append(f"{name}: {v} VGPRs ({alloc} allocated), {waves} waves per SIMD, scratch {scratch} B, LDS {lds} B per workgroup")
-    else:
-        lines.append("registers: no --isa given")
-    os.makedirs(os.path.dirname(os.path.abspath(a_.out)), exist_ok=True)
-    with open(a_.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+    fl.write_lines(a_.out, lines + fl.resource_lines(a_.isa, KERNELS, prefix="", label="{}"))
 
 
 if __name__ == "__main__":

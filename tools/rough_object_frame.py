@@ -5,76 +5,25 @@
 hip events, the best of `--repeats` timed frames after a warm-up of each.  Writes profiles/rough_object_frame.txt's lines to --out.
 Rough glass takes an emitter sample and a shadow ray at every vertex where clear glass takes none: it traces more rays.
 Needs a GPU: there is no fallback."""
-import argparse
-import os
-import sys
+import object_frame_lib as fl  # puts the repository and tests/ on the path
 
-import numpy as np
-import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import path_oi_fp64 as po
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--alpha", type=float, default=0.1)
-    a_ = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("rough_object_frame.py needs a GPU")
-    import path_oi_fp64 as po
-    import path_oi_smooth_fp64 as ps
-    from materialist_amd import mesh, pathtrace as pt
-
-    dev = torch.device("cuda:0")
-    z = np.load(os.path.join(ROOT, "tests", "golden", "indoor2.npz"))
-    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-    a = t(z["ref_albedo_u8"].astype(np.float32) / 255.0)
-    r = t(z["ref_roughness_u8"].astype(np.float32)[..., None] / 255.0).clamp(0.07, 1.0)
-    m = t(z["ref_metallic_u8"].astype(np.float32)[..., None] / 255.0)
-    env = z["ref_envmap_f32"]
-    depth = z["depth_pred_f32"]
-    depth = 2 * depth.max() - depth
-    H, W = depth.shape
-    rm = mesh.reference_mesh(depth, 35.0)
-    z0 = 0.6 * float(depth[depth > 0].min())
-    Vs, Ts, _ = ps.icosphere((-0.10 * z0, 0.0, -z0), 0.09 * z0, 3)
-    Vc, Tc = po.cube((0.13 * z0, -0.05 * z0, -z0), 0.13 * z0, (0.3, 0.6, 0.2))
-    assert Ts.shape[0] == 1280
-    cube = {"vertices": Vc, "triangles": Tc, "bsdf": po.DIFFUSE_08}
+    a_ = fl.arguments(__doc__, "rough_object_frame.py", 3, argv, alpha=0.1)
+    f = fl.indoor2_frame()
     cases = [("sphere as rough glass, 1.49 / 1.000277, alpha %g + diffuse cube (path_kernel<RoughObjects>)" % a_.alpha,
-              [{"vertices": Vs, "triangles": Ts, "bsdf": {"type": "roughdielectric", "int_ior": 1.49, "ext_ior": 1.000277, "alpha": a_.alpha}}, cube]),
-             ("sphere as clear glass, 1.49 / 1.000277 + diffuse cube (path_kernel<ObjTable>, the parent's kernel)",
-              [{"vertices": Vs, "triangles": Ts, "bsdf": po.GLASS}, cube])]
-    tracers = [pt.PathTracer(rm["vertices"], rm["triangles"], H, W, 35.0, objects=ob) for _, ob in cases]
-    tabs = tracers[0].tables(env)
-    kw = dict(spp=32, max_depth=16, seed=1, tables=tabs)
-    best, n_rays = [None, None], [0.0, 0.0]
-    for tr in tracers:                                                   # warm-up of each
-        assert bool(torch.isfinite(tr.render(a, r, m, env, **kw)).all())
-    torch.cuda.synchronize()
-    for _ in range(a_.repeats):
-        for k, tr in enumerate(tracers):                                 # alternating
-            rays = torch.zeros(H, W, dtype=torch.int32, device=dev)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            tr.render(a, r, m, env, rays=rays, **kw)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1)
-            best[k] = ms if best[k] is None else min(best[k], ms)
-            n_rays[k] = float(rays.to(torch.float64).sum())
-    lines = ["512x512 indoor2 frame, spp 32, max_depth 16, a 1280-triangle sphere and a 12-triangle cube in front of the depth mesh; hip events, one process, alternating"]
+              [fl.sphere(f, {"type": "roughdielectric", "int_ior": 1.49, "ext_ior": 1.000277, "alpha": a_.alpha}), f.cube]),
+             ("sphere as clear glass, 1.49 / 1.000277 + diffuse cube (path_kernel<ObjTable>, the parent's kernel)", [fl.sphere(f, po.GLASS), f.cube])]
+    tracers = [fl.tracer(f, ob) for _, ob in cases]
+    _, times, n_rays = fl.alternate(f, fl.render_runs(f, tracers), a_.repeats)
+    lines = [fl.HEADER]
     for k, (label, _) in enumerate(cases):
-        lines.append(f"{label}: {best[k]:.1f} ms (best of {a_.repeats} after a warm-up), {n_rays[k] / 1e6:.1f} Mrays, {n_rays[k] / 1e3 / best[k]:.0f} Mrays/s, "
+        best = min(times[k])
+        lines.append(f"{label}: {best:.1f} ms (best of {a_.repeats} after a warm-up), {n_rays[k] / 1e6:.1f} Mrays, {n_rays[k] / 1e3 / best:.0f} Mrays/s, "
                      f"n_rough_objects {tracers[k].stats['n_rough_objects']}")
-    os.makedirs(os.path.dirname(os.path.abspath(a_.out)), exist_ok=True)
-    with open(a_.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+    fl.write_lines(a_.out, lines)
 
 
 if __name__ == "__main__":
