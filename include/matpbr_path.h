@@ -435,6 +435,37 @@ int matpbr_path_render_objects_through(const void* nodes, const void* tris, cons
                                        const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
                                        const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
                                        const float* photo, float* through);
+/* The differential render that also keeps the radiance without the objects ("Ratio shadow transfer"), forward
+ * only.  Arguments: matpbr_path_render_objects_through's, then base[H,W,3] (DEVICE).  photo and through are both NULL or both
+ * non-NULL: NULL means matpbr_path_render_objects_diff's rule for every sample, non-NULL matpbr_path_render_objects_through's.
+ * base = (1 - c_s) L_without,s, a mean over spp as the other sums are: a sample with c_s = 0 adds its second walk's radiance where it
+ * was walked twice, else its first walk's, which met no inserted triangle and so is the same arithmetic as a walk without them (no
+ * second walk runs for it); a sample with c_s = 1 adds nothing.  base >= 0, and exactly 0 where alpha = 1.  fg, delta, alpha,
+ * through and rewalked are the bits of the entry whose rule holds, and base + delta = the mean of (1 - c_s) L_with,s up to rounding.
+ * The picture is matpbr_path_composite_ratio.  Every split into launches gives the same bits.  Invalid arguments, besides those
+ * entry points': base NULL, exactly one of photo and through NULL. */
+int matpbr_path_render_objects_ratio(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                     float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                     int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                     const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                     const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                     const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                     const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                     const float* photo, float* through, float* base);
+/* The differential render composited into the photograph with its shadows transferred as a ratio ("Ratio
+ * shadow transfer"): the sums are matpbr_path_render_objects_ratio's outputs added over some frames, scale = 1 / (their number),
+ * K = 1 - alpha_sum scale.  Per channel, where delta_sum < 0 and base_sum > 0 (the objects darken it): B = base_sum scale,
+ * D = delta_sum scale, g = max(0, B + D) / B in [0, 1], out = max(0, fg_sum scale + (K photo) g): the photograph is dimmed by the
+ * share of light the model loses, so the model's albedo cancels and the photograph's texture stays.  Elsewhere (the objects brighten
+ * the channel or leave it) out is matpbr_path_composite's, bit for bit: added light stays additive, its ratio having no bound where
+ * base is dark.  Every operation is rounded on its own and the division is the correctly rounded one: the CPU twin gives the same
+ * bits, and where fg, delta and alpha are 0 the photograph comes through bit for bit.  DEVICE pointers.  Invalid: a NULL pointer, H
+ * or W <= 0, scale not finite or <= 0. */
+int matpbr_path_composite_ratio(const float* fg_sum, const float* delta_sum, const float* base_sum, const float* alpha_sum, const float* photo, int H,
+                                int W, float scale, float* out, void* stream);
+/* matpbr_path_composite_ratio on the CPU with the routine the kernel runs (every pointer HOST). */
+int matpbr_path_composite_ratio_host(const float* fg_sum, const float* delta_sum, const float* base_sum, const float* alpha_sum, const float* photo,
+                                     int H, int W, float scale, float* out);
 /* The camera chain of matpbr_path_render_objects_through on the CPU (every pointer HOST), from the routines the kernel runs: the
  * traversal of matpbr_path_trace_host, the dielectric samplers, the spawn offset and the texel lookup.  Lane l is sample sample[l] of
  * pixel pixel[l] (a flat index into [H,W]) under seed seed[l].  objects, obj_nrm (nullable where no object is smooth) and n_scene_tri

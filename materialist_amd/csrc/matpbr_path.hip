@@ -38,6 +38,7 @@ __host__ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1
 // (DiffObjects) the id from which the traversals skip triangles: none in a sample's first trip, the inserted ones in its second
 template <class Objects> __device__ __forceinline__ int id_limit_of(const Objects&, bool) { return 0; }
 __device__ __forceinline__ int id_limit_of(const DiffObjects& ot, bool second) { return second ? ot.n_scene_tri : INT32_MAX; }
+__device__ __forceinline__ int id_limit_of(const RatioObjects& ot, bool second) { return id_limit_of(static_cast<const DiffObjects&>(ot), second); }
 // (ThroughObjects) the second trip of a see-through sample replays its chain over every triangle and skips the inserted ones from its
 // landing depth `land` on; land = -1 (not see-through) skips them from the camera ray on, DiffObjects' rule
 __device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second, int depth, int land) {
@@ -70,11 +71,15 @@ __device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second
 // depth mesh's front at depth >= 1 it adds thr photo[texel] to `through`, records the depth in `land` and starts `touched` afresh.  Trip 1
 // of such a sample runs where touched && land + 1 < max_depth: the same sample from the camera ray on, so the same chain, with the
 // inserted triangles skipped from depth `land` on and the envmap as the only emitter; fg takes trip 0 minus trip 1.  Every
-// `if (THROUGH ...)` folds away in the other eleven.
+// `if (THROUGH ...)` folds away in the other eleven.  BASE: DIFF or THROUGH with one more sum (Objects = RatioObjects,
+// RatioThroughObjects; DESIGN.md section 1.4, "Ratio shadow transfer"): a sample with cov false adds the radiance of its last trip, the
+// walk without the objects, to `base`.  DIFF, THROUGH and BASE are read off the table's type (DiffTraits), so the twelve kernels
+// without `base` are the code they were; every `if (BASE ...)` folds away in them.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
-    constexpr bool THROUGH = std::is_same<Objects, ThroughObjects>::value;
-    constexpr bool DIFF = std::is_same<Objects, DiffObjects>::value || THROUGH;
+    constexpr bool THROUGH = DiffTraits<Objects>::through;
+    constexpr bool DIFF = DiffTraits<Objects>::diff;
+    constexpr bool BASE = DiffTraits<Objects>::base;
     constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF;
     constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
@@ -103,6 +108,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             if constexpr (THROUGH) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) ot.through[3 * pix + c] = 0.0f;
+            }
+            if constexpr (BASE) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ot.base[3 * pix + c] = 0.0f;
             }
         }
     } else if (!first) {
@@ -477,6 +486,13 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 for (int c = 0; c < 3; ++c) ot.delta[3 * pix + c] += Lw[c] - L[c];
                 if (ot.rewalked) ot.rewalked[pix] += 1u;
             }
+            if constexpr (BASE) {
+                // the walk without the objects of a sample that misses them: trip 1's L, or trip 0's where it met none (then L is Lw)
+                if (!cov) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) ot.base[3 * pix + c] += L[c];
+                }
+            }
             second = false;
         } else {
 #pragma unroll
@@ -491,6 +507,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 ot.fg[3 * pix + c] *= sc;
                 ot.delta[3 * pix + c] *= sc;
                 if constexpr (THROUGH) ot.through[3 * pix + c] *= sc;
+                if constexpr (BASE) ot.base[3 * pix + c] *= sc;
             }
             ot.alpha[pix] *= sc;
         }
@@ -1433,6 +1450,36 @@ int matpbr_path_render_objects_through(const void* nodes, const void* tris, cons
     return launch_frame(f, q, tt);
 }
 
+int matpbr_path_render_objects_ratio(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                     float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                     int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                     const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                     const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                     const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                     const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                     const float* photo, float* through, float* base) {
+    float* const out = nullptr;   // the sums go to the table's buffers
+    const Frame f = RENDER_FRAME;
+    PathArgs q{};
+    Scene s;
+    if (!fg || !delta || !alpha || !base || (photo == nullptr) != (through == nullptr) || n_objects <= 0 || !frame_args(f, q) ||
+        !objects_scene(7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    if (!photo) {   // matpbr_path_render_objects_diff's rule
+        RatioObjects rt{};
+        static_cast<TexObjects&>(rt) = tex_objects(s);
+        rt.fg = fg; rt.delta = delta; rt.alpha = alpha; rt.rewalked = rewalked;
+        rt.base = base;
+        return launch_frame(f, q, rt);
+    }
+    RatioThroughObjects rt{};
+    static_cast<TexObjects&>(rt) = tex_objects(s);
+    rt.fg = fg; rt.delta = delta; rt.alpha = alpha; rt.rewalked = rewalked;
+    rt.photo = photo; rt.through = through;
+    rt.base = base;
+    return launch_frame(f, q, rt);
+}
+
 int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,
                                    const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                    const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N, int32_t* depth, int32_t* texel,
@@ -1537,6 +1584,22 @@ int matpbr_path_composite_host(const float* fg_sum, const float* delta_sum, cons
                                float* out) {
     if (!composite_args_valid(fg_sum, delta_sum, alpha_sum, photo, H, W, scale, out)) return MATPBR_PATH_ERR_INVALID_ARG;
     for (long p = 0; p < (long)H * W; ++p) composite_pixel(fg_sum, delta_sum, alpha_sum, photo, p, scale, out);
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_composite_ratio(const float* fg_sum, const float* delta_sum, const float* base_sum, const float* alpha_sum, const float* photo, int H,
+                                int W, float scale, float* out, void* stream) {
+    if (!base_sum || !composite_args_valid(fg_sum, delta_sum, alpha_sum, photo, H, W, scale, out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    const long P = (long)H * W;
+    hipLaunchKernelGGL(composite_ratio_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fg_sum, delta_sum, base_sum,
+                       alpha_sum, photo, P, scale, out);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_composite_ratio_host(const float* fg_sum, const float* delta_sum, const float* base_sum, const float* alpha_sum, const float* photo,
+                                     int H, int W, float scale, float* out) {
+    if (!base_sum || !composite_args_valid(fg_sum, delta_sum, alpha_sum, photo, H, W, scale, out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long p = 0; p < (long)H * W; ++p) composite_ratio_pixel(fg_sum, delta_sum, base_sum, alpha_sum, photo, p, scale, out);
     return MATPBR_PATH_OK;
 }
 

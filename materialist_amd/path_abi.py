@@ -109,6 +109,9 @@ SIGNATURES = {
                                                       ctypes.c_long, _P]),
     "matpbr_path_render_objects_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 4),
     "matpbr_path_render_objects_through": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 6),
+    "matpbr_path_render_objects_ratio": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 7),
+    "matpbr_path_composite_ratio": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
+    "matpbr_path_composite_ratio_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
     "matpbr_path_through_chain_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P,
                                                       ctypes.c_long] + [_P] * 5),
     "matpbr_path_composite": (ctypes.c_int, [_P] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
@@ -168,6 +171,10 @@ FEATURE_SYMBOLS = {
  THROUGH_SYMBOLS) = FEATURE_SYMBOLS.values()
 LATE_SYMBOLS = sum(FEATURE_SYMBOLS.values(), ())
 _FEATURE = {name: what for what, names in FEATURE_SYMBOLS.items() for name in names}
+# ratio shadow transfer's symbols ("Ratio shadow transfer"), added at version 3 as well: a group of its own beside
+# the ten above, which stay the partition of LATE_SYMBOLS they were
+RATIO_SYMBOLS = ("matpbr_path_render_objects_ratio", "matpbr_path_composite_ratio", "matpbr_path_composite_ratio_host")
+RATIO_FEATURE = "ratio shadow transfer"
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
@@ -188,7 +195,7 @@ def load() -> ctypes.CDLL:
         _build.build_path_library()
         lib = ctypes.CDLL(_build.PATH_LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if name in LATE_SYMBOLS and not hasattr(lib, name):
+            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS) and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -202,7 +209,7 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        what = _FEATURE.get(name, "smooth inserted objects")
+        what = RATIO_FEATURE if name in RATIO_SYMBOLS else _FEATURE.get(name, "smooth inserted objects")
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 

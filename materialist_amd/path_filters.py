@@ -1,5 +1,5 @@
 """The image-space steps around the path render: the a-trous denoiser ("Denoiser"), the differential render's
-composite ("Differential render") and its own denoiser ("Denoiser for the differential render").  Each step is written once, over a
+composite ("Differential render", "Ratio shadow transfer") and its own denoiser ("Denoiser for the differential render").  Each step is written once, over a
 side: `_HOST` runs it on numpy arrays through the library's `*_host` entry (the routine the kernel runs, for the tests), `_Device`
 on torch tensors through the kernel on the current torch stream.  The public `NAME_host` and `NAME` are the two calls of that body."""
 from itertools import chain
@@ -164,15 +164,17 @@ def _composite_scale(scale: float) -> float:
     return sc
 
 
-def _composite(side, fg, delta, alpha, photo, scale):
+def _composite(side, fg, delta, alpha, photo, scale, base=None):
+    """`composite`; with `base`, `composite_ratio`: the entry of that name takes it after delta."""
     shp = tuple(side.raw(photo).shape)
     if len(shp) != 3 or shp[2] != 3 or shp[0] < 1 or shp[1] < 1:
         raise ValueError(f"photo must be [H,W,3], got {list(shp)}")
     H, W = shp[:2]
     sc = _composite_scale(scale)
-    images = side.images([(fg, (H, W, 3), "fg"), (delta, (H, W, 3), "delta"), (alpha, (H, W), "alpha"), (photo, (H, W, 3), "photo")])
+    specs = [(fg, (H, W, 3), "fg"), (delta, (H, W, 3), "delta"), (base, (H, W, 3), "base"), (alpha, (H, W), "alpha"), (photo, (H, W, 3), "photo")]
+    images = side.images(specs if base is not None else specs[:2] + specs[3:])
     out = side.empty(H, W, 3)
-    _run(side, "matpbr_path_composite", images, (H, W, sc), (out,))
+    _run(side, "matpbr_path_composite" + ("_ratio" if base is not None else ""), images, (H, W, sc), (out,))
     return out
 
 
@@ -188,6 +190,29 @@ def composite(fg, delta, alpha, photo, scale: float = 1.0) -> torch.Tensor:
     or their sums over some frames with `scale` = 1 / (the number of frames); photo [H,W,3], linear.  Where fg, delta and alpha are 0
     the photograph (>= 0) comes through bit for bit."""
     return _composite(_Device(fg, delta, alpha, photo), fg, delta, alpha, photo, scale)
+
+
+def _ratio_base(base):
+    if base is None:
+        raise ValueError("base must be [H,W,3], got None")
+    return base
+
+
+def composite_ratio_host(fg, delta, base, alpha, photo, scale: float = 1.0) -> np.ndarray:
+    """`composite_ratio` on the CPU with the routine the kernel runs: fg, delta, base, photo [H,W,3], alpha [H,W] -> [H,W,3], the same
+    bits."""
+    return _composite(_HOST, fg, delta, alpha, photo, scale, _ratio_base(base))
+
+
+@torch.no_grad()
+def composite_ratio(fg, delta, base, alpha, photo, scale: float = 1.0) -> torch.Tensor:
+    """The differential render composited into the photograph with its shadows transferred as a ratio ("Ratio
+    shadow transfer"), on the device (the current torch stream).  fg, delta, base, alpha: `PathTracer.render_diff_ratio`'s outputs, or
+    their sums over some frames with `scale` = 1 / (the number of frames); photo [H,W,3], linear.  Per channel, where delta < 0 < base
+    (the objects darken it) the photograph's share is multiplied by g = max(0, base + delta) / base: max(0, fg scale + ((1 - alpha
+    scale) photo) g); elsewhere the channel carries `composite`'s bits.  Where fg, delta and alpha are 0 the photograph (>= 0) comes
+    through bit for bit."""
+    return _composite(_Device(fg, delta, base, alpha, photo), fg, delta, alpha, photo, scale, _ratio_base(base))
 
 
 # ---- the differential render's denoiser (DESIGN.md section 1.4, "Denoiser for the differential render") ----------------------------------

@@ -11,7 +11,8 @@ puts both behind autograd.  `PathTracer.features` and `PathTracer.denoise` are t
 and `composite` are the differential render ("Differential render"): what inserted objects add to and take
 from a photograph of the scene, forward only; `PathTracer.denoise_diff` is its own a-trous filter over two halves of it ("Denoiser
 for the differential render"); `PathTracer.render_diff_through` is the differential render with the photograph shown, refracted,
-behind inserted clear glass ("Seen through glass").  There is no fallback: a missing or failing library raises.
+behind inserted clear glass ("Seen through glass"); `PathTracer.render_diff_ratio` and `composite_ratio` transfer the shadows as a
+ratio of the model's radiance with and without the objects ("Ratio shadow transfer").  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -211,22 +212,26 @@ class PathTracer:
         tracer without objects raises ValueError."""
         return self._render_diff("matpbr_path_render_objects_diff", (albedo, roughness, metallic, envmap), spp, max_depth, seed, spp_per_launch, tables, rays)
 
-    def _render_diff(self, entry: str, maps, spp, max_depth, seed, spp_per_launch, tables, rays, photo=None) -> tuple:
+    def _render_diff(self, entry: str, maps, spp, max_depth, seed, spp_per_launch, tables, rays, photo=None, ratio=False) -> tuple:
         """`render_diff` through the library's `entry`; with `photo`, `render_diff_through`: the photograph and `through` follow the four
-        outputs in the call, and `through` comes back before `rewalked`."""
+        outputs in the call, and `through` comes back before `rewalked`.  `ratio`: `render_diff_ratio`: the entry takes photo and
+        through (NULL without `photo`) and then `base`, which comes back after `delta`."""
         if self.objects is None:
-            raise ValueError(f"render_diff{'' if photo is None else '_through'} renders what inserted objects change: build the PathTracer with `objects`")
+            raise ValueError(f"render_diff{'_ratio' if ratio else '' if photo is None else '_through'} renders what inserted objects change: "
+                             f"build the PathTracer with `objects`")
         if photo is not None and tuple(torch.as_tensor(photo).shape) != (self.H, self.W, 3):
             raise ValueError(f"photo must be [{self.H},{self.W},3], got {tuple(torch.as_tensor(photo).shape)}")
         fn = symbol(entry)
         H, W, dev = self.H, self.W, self.device
         own = () if photo is None else (torch.as_tensor(photo).to(dev, torch.float32).contiguous(), torch.empty(H, W, 3, device=dev, dtype=torch.float32))
+        base = (torch.empty(H, W, 3, device=dev, dtype=torch.float32),) if ratio else ()
         inputs = self._inputs(*maps, tables)
         fg, delta = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
         alpha, rewalked = torch.empty(H, W, device=dev, dtype=torch.float32), torch.zeros(H, W, device=dev, dtype=torch.int32)
+        tail = (*own, *base) if own or not ratio else (None, None, *base)
         check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), _dptr(rays), torch.cuda.current_stream(dev).cuda_stream,
-                 *self.object_args()[:9], *self._texture_args(), *(x.data_ptr() for x in (fg, delta, alpha, rewalked, *own))), entry)
-        return (fg, delta, alpha, *own[1:], rewalked)
+                 *self.object_args()[:9], *self._texture_args(), *(_dptr(x) for x in (fg, delta, alpha, rewalked, *tail))), entry)
+        return (fg, delta, *base, alpha, *own[1:], rewalked)
 
     @torch.no_grad()
     def render_diff_through(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, photo, spp: int = 64,
@@ -243,6 +248,20 @@ class PathTracer:
         gives the same bits.  A tracer without objects, or a photograph of another shape, raises ValueError."""
         return self._render_diff("matpbr_path_render_objects_through", (albedo, roughness, metallic, envmap), spp, max_depth, seed, spp_per_launch,
                                  tables, rays, photo)
+
+    @torch.no_grad()
+    def render_diff_ratio(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,
+                          seed: int = 0, spp_per_launch: int = 8, tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None,
+                          photo=None) -> tuple:
+        """`render_diff` that also keeps the radiance without the objects ("Ratio shadow transfer") ->
+        (fg, delta, base [H,W,3], alpha, rewalked); with `photo` [H,W,3], `render_diff_through` with it -> (fg, delta, base, alpha,
+        through, rewalked).  base: the mean over `spp` of the radiance without the objects of the samples whose camera ray misses
+        them: the second walk's where a sample was walked twice, else its only walk's, which met no object (no further walk runs).
+        base >= 0, exactly 0 where alpha = 1, and base + delta is the radiance with the objects of those samples.  The other outputs
+        are `render_diff`'s (`render_diff_through`'s) bits.  `composite_ratio` puts them into a photograph.  Every split into launches
+        gives the same bits.  A tracer without objects, or a photograph of another shape, raises ValueError."""
+        return self._render_diff("matpbr_path_render_objects_ratio", (albedo, roughness, metallic, envmap), spp, max_depth, seed, spp_per_launch,
+                                 tables, rays, photo, ratio=True)
 
     def _first_hit(self, entry: str, channels: int, hidden: int, *own) -> torch.Tensor:
         """[H,W,channels] on the device from the first-hit entry `entry`: it takes the BVH, the camera, the table without the flags

@@ -406,6 +406,7 @@ def load_oi_scene(path: str) -> List[dict]:
 
 
 OI_COLORS = ("none", "vertex", "vertex_linear")
+OI_SHADOWS = ("additive", "ratio")   # render_oi's `shadows`: how the differential composite transfers what the objects darken
 
 
 def _object_colors(path: str, C: Optional[np.ndarray], colors: str) -> np.ndarray:
@@ -479,7 +480,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
               denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
               object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None,
-              composite_denoise: bool = False, see_through: bool = False) -> str:
+              composite_denoise: bool = False, see_through: bool = False, shadows: str = "additive") -> str:
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -514,7 +515,17 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     `composite_denoise` the halves' (fg, delta, alpha) pass the filter as they are and the mean of the halves' `through`,
     (through_A + through_B) * (0.5 / n_iter), is added to the filtered fg: the filter's guides are the glass surface's and would blur
     the refracted photograph.  Rough glass stays re-rendered.  Without `composite` it is a ValueError before any other work; with
-    `see_through=False` the code path, and so the bytes, are the ones without it."""
+    `see_through=False` the code path, and so the bytes, are the ones without it.  `shadows` (with `composite`; DESIGN.md section 1.4,
+    "Ratio shadow transfer"): "additive" (default) adds the model's difference to the photograph; "ratio" dims the photograph by the
+    share of light the model loses, per channel, where the objects darken it, and stays additive where they brighten it: the frames
+    are `PathTracer.render_diff_ratio`'s (with the photograph when `see_through`), `base` is summed with the others, and the picture
+    is `composite_ratio`.  With `composite_denoise`, `base` passes `PathTracer.denoise_diff` a second time in delta's place beside a
+    zero fg, which gives it delta's coverage weighting.  The output names are `composite`'s.  "ratio" without `composite`, or another
+    value, is a ValueError before any other work; with "additive" the code path, and so the bytes, are the ones without it."""
+    if shadows not in OI_SHADOWS:
+        raise ValueError(f"shadows must be 'additive' or 'ratio', got {shadows!r}")
+    if shadows == "ratio" and not composite:
+        raise ValueError("shadows='ratio' needs composite=True: it transfers the differential render's shadows into the photograph as a ratio")
     if see_through and not composite:
         raise ValueError("see_through needs composite=True: it shows the photograph behind inserted glass in the differential composite")
     from . import mesh as _mesh
@@ -564,6 +575,12 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     tabs = pt.tables(env)
     diff = (lambda n, sd: pt.render_diff_through(mat["albedo"], mat["roughness"], mat["metallic"], env, photo, n, max_depth, sd, tables=tabs)[:4]) if see_through else \
            (lambda n, sd: pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, n, max_depth, sd, tables=tabs)[:3])
+    ratio = shadows == "ratio"
+    if ratio:   # (fg, delta, alpha[, through], base): the additive frame's order, base last
+        def diff(n, sd):
+            fg, delta, base, alpha, *through, _ = pt.render_diff_ratio(mat["albedo"], mat["roughness"], mat["metallic"], env, n, max_depth, sd, tables=tabs,
+                                                                       photo=photo if see_through else None)
+            return (fg, delta, alpha, *through, base)
     if composite and composite_denoise:
         halves = [None, None]
         for i in range(n_iter):
@@ -574,17 +591,22 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
         tint = pt.feature_tints() if pt.stats["n_textured_objects"] else pt.feature_colors() if pt.stats["n_colored_objects"] else None
         guide = albedo_guide(geom, mat["albedo"], [h[1] for h in have], tint)
         fg, delta, alpha = pt.denoise_diff(halves[0][:3], halves[1][:3], guide, geom, 1.0 / n_iter)
+        if ratio:   # base in delta's place beside a zero fg: delta's coverage weighting
+            zero = torch.zeros_like(halves[0][0])
+            base = pt.denoise_diff((zero, halves[0][-1], halves[0][2]), (zero, halves[1][-1], halves[1][2]), guide, geom, 1.0 / n_iter)[1]
         if see_through:   # the refracted photograph does not pass the filter
             fg = fg + (halves[0][3] + halves[1][3]) * (0.5 / n_iter)
-        img = _pathtrace.composite(fg, delta, alpha, torch.from_numpy(photo).to(device), 1.0)
+        img = _pathtrace.composite_ratio(fg, delta, base, alpha, torch.from_numpy(photo).to(device), 1.0) if ratio else \
+            _pathtrace.composite(fg, delta, alpha, torch.from_numpy(photo).to(device), 1.0)
     elif composite:
         sums = None
         for i in range(n_iter):
             frame = diff(spp, seed + i)
             sums = frame if sums is None else tuple(x + y for x, y in zip(sums, frame))
         if see_through:
-            sums = (sums[0] + sums[3], sums[1], sums[2])
-        img = _pathtrace.composite(*sums, torch.from_numpy(photo).to(device), 1.0 / n_iter)
+            sums = (sums[0] + sums[3], sums[1], sums[2], *sums[4:])
+        img = _pathtrace.composite_ratio(sums[0], sums[1], sums[3], sums[2], torch.from_numpy(photo).to(device), 1.0 / n_iter) if ratio else \
+            _pathtrace.composite(*sums, torch.from_numpy(photo).to(device), 1.0 / n_iter)
     elif atrous:
         geom = pt.features()
         half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs)

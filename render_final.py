@@ -64,6 +64,10 @@ def parse_args(argv=None):
                          "plus what the objects change in the light of the point seen, instead of the re-rendered fitted scene.  It does not "
                          "cover rough (frosted) glass, which stays re-rendered, nor paths that leave the glass towards another object, a "
                          "lamp or the envmap")
+    ap.add_argument("--oi_shadows", choices=["additive", "ratio"], default="additive",
+                    help="--oi_composite: how what the objects darken reaches the photograph: additive = the model's difference is added "
+                         "(the default); ratio = the photograph is dimmed, per channel, by the share of light the model loses, so a badly "
+                         "fitted albedo cancels and the photograph's texture stays inside a shadow (what the objects brighten stays additive)")
     ap.add_argument("--oi_photo", type=str, default=None, metavar="PATH",
                     help="--oi_composite: the photograph, of the maps' size (default <scene>/gt_image.exr, linear, as the pipeline writes it; a "
                          ".png holds display values and is decoded as the pipeline decodes its input)")
@@ -86,6 +90,8 @@ def parse_args(argv=None):
         ap.error("--oi_composite_denoise needs --oi_composite")
     if a.oi_see_through and not a.oi_composite:
         ap.error("--oi_see_through needs --oi_composite")
+    if a.oi_shadows != "additive" and not a.oi_composite:
+        ap.error("--oi_shadows ratio needs --oi_composite")
     if a.oi_composite_denoise and (a.spp < 2 or a.spp % 2):
         ap.error("--oi_composite_denoise splits every frame into two halves of spp/2 samples: --spp must be even")
     if a.oi_composite and a.env_scale != 1.0:
@@ -117,7 +123,8 @@ def main(argv=None):
                                                  env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture,
                                                  **({"composite": True, "photo_path": a.oi_photo} if a.oi_composite else {}),
                                                  **({"composite_denoise": True} if a.oi_composite_denoise else {}),
-                                                 **({"see_through": True} if a.oi_see_through else {})))
+                                                 **({"see_through": True} if a.oi_see_through else {}),
+                                                 **({"shadows": a.oi_shadows} if a.oi_shadows != "additive" else {})))
     else:
         raise ValueError("Invalid mode")
 
