@@ -647,6 +647,59 @@ int matpbr_path_denoise_diff_host(const float* fgA, const float* deltaA, const f
                                   const float* alphaB, const float* geom, const float* alb, int H, int W, float scale, const MatpbrPathDenoise* prm,
                                   float* fg, float* delta, float* alpha, void* workspace, size_t workspace_bytes);
 
+/* ---- Moving inserted objects ("Moving inserted objects"): a grafted BVH whose object side is moved and refitted
+ * on the device from a rest pose; added at version 3.  The render, feature, denoise and composite entry points take the moved buffers as
+ * they take any: the node, triangle, corner-normal and light-record layouts are the ones above. */
+
+/* The pose of one object, a similarity p' = R (s (p - c)) + c + t: R row-major, rows orthonormal to 1e-5 with det > 0 (no mirror: it would
+ * flip the winding), s > 0, everything finite.  Exactly (R = 1, s = 1, t = 0) leaves the object at rest: its records are copied.  Corner
+ * normals turn by R alone and are not renormalised, which the 1e-5 covers: |R n| stays within 2e-5 of 1 and every reader of the corner
+ * normals normalises after interpolating. */
+typedef struct MatpbrPathXform {
+    float R[9];
+    float s;
+    float t[3];
+    float c[3];
+} MatpbrPathXform;
+
+/* matpbr_path_bvh_build_objects with the two sides kept apart.  Node 0 is the graft root: slot 0 the depth mesh's subtree (triangles
+ * [0, n_scene_tri), at least one, which name vertices below n_scene_vert alone: the depth mesh's own, referenced or not), slot 1 the inserted triangles' ([n_scene_tri, n_tri), at least one); a side of 4 triangles or fewer is the slot's
+ * leaf.  The nodes follow as [scene nodes][object nodes] from *first_object_node on, a child always behind its parent; `tris` is [scene
+ * triangles in their leaf order][object triangles in theirs], ids the merged mesh's.  Each side is built by matpbr_path_bvh_build's
+ * builder capped one level lower, so *depth <= MATPBR_PATH_MAX_BVH_DEPTH; the scene side's topology and boxes are those of
+ * matpbr_path_bvh_build over the scene alone, renumbered (where that build stays above level 40).  rest_tris[n_tri - n_scene_tri]: the
+ * object triangles' records, the rest pose every move starts from.  node_level[max_nodes]: the level of each object node (the object
+ * subtree's root is 1), *object_depth the deepest slot level of that side.  *pad = 1e-6 S, S the largest coordinate magnitude of the mesh
+ * and `reach` (>= 0: the largest any later pose will have).  The object side's boxes are matpbr_path_objects_move's refit of the rest
+ * pose: a move by the identity reproduces this build byte for byte.  max_nodes >= 1 + max(1, n_scene_tri) + max(1, n_tri - n_scene_tri).
+ * Host only. */
+int matpbr_path_bvh_build_grafted(const double* vert, long n_vert, long n_scene_vert, const int32_t* tri, long n_tri, long n_scene_tri, double reach,
+                                  void* nodes, long max_nodes, void* tris, void* rest_tris, int32_t* node_level, long* n_nodes, int* depth, long* n_leaves,
+                                  long* first_object_node, int* object_depth, float* pad);
+
+/* 0 when matpbr_path_objects_move would take every one of xform[n_objects] (HOST), else MATPBR_PATH_ERR_INVALID_ARG. */
+int matpbr_path_xform_check_host(const MatpbrPathXform* xform, int n_objects);
+
+/* Moves the objects of a grafted BVH to the poses xform[n_objects] (HOST, copied before return; object k's is xform[k]) and refits the
+ * object nodes, always from the rest pose.  Triangle k of the object side: tris[n_scene_tri + k] = (v0', id) (e1', 0) (e2', 0) of
+ * rest_tris[k], v0' = p'(v0), e' = R (s e), evaluated in fp64 and rounded once; a smooth object's corner normals obj_nrm = R rest_nrm (both
+ * [n_object_tri,3,3], input order; NULL when no object is smooth); the light records light_tris = the same transform of rest_light_tris
+ * (both [n_light_tri,3] float4, `lights` the header they came with, HOST; NULL and 0 without lights), bit-equal to the moved triangles of
+ * the same ids.  Refit: a leaf slot's box is the min / max over its triangles of v0', fl(v0' + e1'), fl(v0' + e2') in fp32 widened by pad,
+ * an inner slot's the union of its child's two boxes, bottom-up by node_level[n_object_nodes] (DEVICE) from object_depth, slot 1 of node
+ * 0 last.  The scene's nodes and triangles are not written.  The caller keeps every pose within the reach pad was built for and scales
+ * lights->area by s^2.  DEVICE pointers, nodes / tris / rest_tris / the light records 16-byte aligned; two launches on `stream`.  Invalid
+ * argument: a null or misaligned pointer, a range outside the object triangles or overlapping another, a bad xform, a smooth object
+ * without both normal buffers, a header that does not match the table.  The _host twin takes HOST pointers and gives the same bytes. */
+int matpbr_path_objects_move(void* nodes, void* tris, const void* rest_tris, long n_scene_tri, long n_object_tri, long first_object_node,
+                             long n_object_nodes, const int32_t* node_level, int object_depth, const MatpbrPathObject* objects, int n_objects,
+                             const MatpbrPathXform* xform, float pad, const float* rest_nrm, float* obj_nrm, const void* rest_light_tris,
+                             void* light_tris, long n_light_tri, const MatpbrPathLights* lights, void* stream);
+int matpbr_path_objects_move_host(void* nodes, void* tris, const void* rest_tris, long n_scene_tri, long n_object_tri, long first_object_node,
+                                  long n_object_nodes, const int32_t* node_level, int object_depth, const MatpbrPathObject* objects, int n_objects,
+                                  const MatpbrPathXform* xform, float pad, const float* rest_nrm, float* obj_nrm, const void* rest_light_tris,
+                                  void* light_tris, long n_light_tri, const MatpbrPathLights* lights);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,11 +11,12 @@
 // traversals and the host builder; path_shading.hpp the RNG, the envmap sampler and the BSDF wrappers; path_objects.hpp the tables the
 // kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
 // path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser; path_diff.hpp the differential render's table
-// and the composite.
+// and the composite; path_move.hpp the grafted BVH's move and refit of the inserted objects.
 #include <type_traits>
 
 #include "path_denoise.hpp"
 #include "path_diff.hpp"
+#include "path_move.hpp"
 
 namespace {
 
@@ -1105,49 +1106,165 @@ int matpbr_path_bvh_build_objects(const double* vert, long n_vert, const int32_t
     for (long k = 0; k < 3 * n_tri; ++k)
         if (tri[k] < 0 || tri[k] >= n_vert) return MATPBR_PATH_ERR_INVALID_ARG;
     const int N = (int)n_tri;
-    double S = 0.0;   // scene scale: boxes are padded by 1e-6 of it so that fp32 rounding of (v0, e1, e2) stays inside
-    for (long k = 0; k < 3 * n_vert; ++k) S = std::max(S, std::fabs(vert[k]));
-    const float pad = (float)(1e-6 * S);
+    const float pad = (float)(1e-6 * mesh_scale(vert, n_vert));
     Builder bld;
     bld.nodes = static_cast<BNode*>(nodes);
     bld.max_nodes = max_nodes;
-    bld.tb.resize(N);
-    bld.cen.resize(3 * (size_t)N);
-    bld.idx.resize(N);
-    for (int t = 0; t < N; ++t) {
-        Box b;
-        for (int c = 0; c < 3; ++c) {
-            double lo = DBL_MAX, hi = -DBL_MAX;
-            for (int v = 0; v < 3; ++v) { lo = std::min(lo, vert[3 * (long)tri[3 * t + v] + c]); hi = std::max(hi, vert[3 * (long)tri[3 * t + v] + c]); }
-            b.lo[c] = (float)lo - pad;
-            b.hi[c] = (float)hi + pad;
-            bld.cen[3 * t + c] = (float)(0.5 * (lo + hi));
-        }
-        bld.tb[t] = b;
-        bld.idx[t] = t;
-    }
+    builder_load(bld, vert, tri, 0, N, pad);
     if (!bld.build(N)) return MATPBR_PATH_ERR_CAPACITY;
     float4* T = static_cast<float4*>(tris);
-    for (int k = 0; k < N; ++k) {
-        const int t = bld.idx[k];
-        const double* v0 = vert + 3 * (long)tri[3 * t];
-        const double* v1 = vert + 3 * (long)tri[3 * t + 1];
-        const double* v2 = vert + 3 * (long)tri[3 * t + 2];
-        double e1[3], e2[3];
-        for (int c = 0; c < 3; ++c) { e1[c] = v1[c] - v0[c]; e2[c] = v2[c] - v0[c]; }
-        const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
-        // depth mesh: e1 x e2 faces the camera at the origin; an inserted mesh keeps its winding (e1 x e2 = its outward normal)
-        if (t < n_scene_tri && nx * v0[0] + ny * v0[1] + nz * v0[2] > 0.0) std::swap(e1, e2);
-        int32_t id = t;
-        float idf;
-        std::memcpy(&idf, &id, 4);
-        T[3 * k] = make_float4((float)v0[0], (float)v0[1], (float)v0[2], idf);
-        T[3 * k + 1] = make_float4((float)e1[0], (float)e1[1], (float)e1[2], 0.0f);
-        T[3 * k + 2] = make_float4((float)e2[0], (float)e2[1], (float)e2[2], 0.0f);
-    }
+    for (int k = 0; k < N; ++k) tri_record(vert, tri, bld.idx[k], n_scene_tri, T + 3 * k);
     *n_nodes = bld.n_nodes;
     *depth = bld.depth;
     *n_leaves = bld.n_leaves;
+    return MATPBR_PATH_OK;
+}
+
+// ---- moving inserted objects ("Moving inserted objects") ----------------------------------------------------
+int matpbr_path_bvh_build_grafted(const double* vert, long n_vert, long n_scene_vert, const int32_t* tri, long n_tri, long n_scene_tri, double reach,
+                                  void* nodes, long max_nodes, void* tris, void* rest_tris, int32_t* node_level, long* n_nodes, int* depth, long* n_leaves,
+                                  long* first_object_node, int* object_depth, float* pad) {
+    if (!vert || !tri || !nodes || !tris || !rest_tris || !node_level || !n_nodes || !depth || !n_leaves || !first_object_node || !object_depth ||
+        !pad || n_vert <= 0 || n_scene_vert < 1 || n_scene_vert > n_vert || n_tri < 2 || n_tri > INT32_MAX / 3 || n_scene_tri < 1 || n_scene_tri >= n_tri || !(reach >= 0.0) || !std::isfinite(reach))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    const long n_object_tri = n_tri - n_scene_tri;
+    if (max_nodes < 1 + std::max(1L, n_scene_tri) + std::max(1L, n_object_tri)) return MATPBR_PATH_ERR_CAPACITY;
+    for (long k = 0; k < 3 * n_tri; ++k)
+        if (tri[k] < 0 || tri[k] >= n_vert) return MATPBR_PATH_ERR_INVALID_ARG;
+    // the scene side is padded as matpbr_path_bvh_build pads the scene alone: by the scale of the scene's own vertices, the first
+    // n_scene_vert of the merged mesh, which are all a scene triangle may name; the object side by the scale of everything, every
+    // announced pose included
+    for (long k = 0; k < 3 * n_scene_tri; ++k)
+        if (tri[k] >= n_scene_vert) return MATPBR_PATH_ERR_INVALID_ARG;
+    const float scene_pad = (float)(1e-6 * mesh_scale(vert, n_scene_vert));
+    *pad = (float)(1e-6 * std::max(mesh_scale(vert, n_vert), reach));
+    BNode* out = static_cast<BNode*>(nodes);
+    float4 *T = static_cast<float4*>(tris), *rest = static_cast<float4*>(rest_tris);
+    std::memset(&out[0], 0, sizeof(BNode));
+    long used = 1, leaves = 0;
+    int deepest = 1;
+    // one side: a sub-build capped one level below the whole tree's cap, renumbered behind node 0; slot `slot` of node 0 is its root, or
+    // its leaf when it holds kLeafMax triangles or fewer
+    auto side = [&](int slot, long first, long count, float side_pad, std::vector<int32_t>* levels, int* side_depth) -> bool {
+        std::vector<BNode> sub((size_t)std::max(1L, count));
+        Builder bld;
+        bld.nodes = sub.data();
+        bld.max_nodes = (long)sub.size();
+        bld.level_cap = kMaxBvhDepth - 1;
+        bld.levels = levels;
+        builder_load(bld, vert, tri, first, (int)count, side_pad);
+        if (!bld.build((int)count)) return false;
+        for (long k = 0; k < count; ++k) tri_record(vert, tri, first + bld.idx[k], n_scene_tri, T + 3 * (first + k));
+        BNode& root = out[0];
+        if (count <= kLeafMax) {   // the sub-build's root holds the one leaf in its slot 0
+            for (int c = 0; c < 6; ++c) root.b[6 * slot + c] = sub[0].b[c];
+            root.child[slot] = (int32_t)first;
+            root.count[slot] = (int32_t)count;
+            leaves += 1;
+            *side_depth = 1;
+            return true;
+        }
+        const long base = used;
+        for (long q = 0; q < bld.n_nodes; ++q) {
+            BNode nd = sub[q];
+            for (int s = 0; s < 2; ++s) nd.child[s] += (int32_t)(nd.count[s] < 0 ? base : first);
+            out[base + q] = nd;
+        }
+        float b[6];
+        union_box(sub[0], b);
+        for (int c = 0; c < 6; ++c) root.b[6 * slot + c] = b[c];
+        root.child[slot] = (int32_t)base;
+        root.count[slot] = -1;
+        used += bld.n_nodes;
+        leaves += bld.n_leaves;
+        *side_depth = bld.depth + 1;
+        return true;
+    };
+    int scene_depth = 1;
+    std::vector<int32_t> levels;
+    if (!side(0, 0, n_scene_tri, scene_pad, nullptr, &scene_depth)) return MATPBR_PATH_ERR_CAPACITY;
+    *first_object_node = used;
+    if (!side(1, n_scene_tri, n_object_tri, *pad, &levels, object_depth)) return MATPBR_PATH_ERR_CAPACITY;
+    const long n_object_nodes = used - *first_object_node;
+    if (n_object_nodes > 0) {
+        node_level[0] = 1;   // the object subtree's root; the builder recorded its other nodes' levels below it
+        for (long q = 1; q < n_object_nodes; ++q) node_level[q] = levels[q - 1] + 1;
+    }
+    deepest = std::max(scene_depth, *object_depth);
+    std::memcpy(rest, T + 3 * n_scene_tri, (size_t)n_object_tri * 3 * sizeof(float4));
+    // the object boxes are the refit rule's: the build ends with the refit of the rest pose, so that a move by the identity reproduces it
+    for (long i = 0; i < n_object_nodes; ++i) refit_leaf_slots(out, *first_object_node + i, T, *pad);
+    for (int level = *object_depth - 1; level >= 1; --level)
+        for (long i = 0; i < n_object_nodes; ++i)
+            if (node_level[i] == level) refit_inner_slots(out, *first_object_node + i);
+    refit_graft_slot(out, T, *pad);
+    *n_nodes = used;
+    *depth = deepest;
+    *n_leaves = leaves;
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_xform_check_host(const MatpbrPathXform* xform, int n_objects) {
+    if (!xform || n_objects < 1 || n_objects > MATPBR_PATH_MAX_OBJECTS) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int k = 0; k < n_objects; ++k)
+        if (!xform_ok(xform[k])) return MATPBR_PATH_ERR_INVALID_ARG;
+    return MATPBR_PATH_OK;
+}
+
+namespace {
+bool move_args_valid(const void* nodes, const void* tris, const void* rest_tris, long n_scene_tri, long n_object_tri, long first_object_node,
+                     long n_object_nodes, const int32_t* node_level, int object_depth, float pad, const void* rest_light_tris, const void* light_tris,
+                     long n_light_tri) {
+    return nodes && tris && rest_tris && !((uintptr_t)nodes & 15) && !((uintptr_t)tris & 15) && !((uintptr_t)rest_tris & 15) && n_scene_tri >= 0 &&
+           n_object_tri >= 1 && n_scene_tri + n_object_tri <= INT32_MAX / 3 && first_object_node >= 1 && n_object_nodes >= 0 &&
+           first_object_node + n_object_nodes <= INT32_MAX && (n_object_nodes == 0 || node_level) && object_depth >= 1 &&
+           object_depth <= kMaxBvhDepth && pad >= 0.0f && std::isfinite(pad) && n_light_tri >= 0 && n_light_tri <= INT32_MAX / 3 &&
+           (n_light_tri == 0 || (rest_light_tris && light_tris && !((uintptr_t)rest_light_tris & 15) && !((uintptr_t)light_tris & 15)));
+}
+}  // namespace
+
+int matpbr_path_objects_move(void* nodes, void* tris, const void* rest_tris, long n_scene_tri, long n_object_tri, long first_object_node,
+                             long n_object_nodes, const int32_t* node_level, int object_depth, const MatpbrPathObject* objects, int n_objects,
+                             const MatpbrPathXform* xform, float pad, const float* rest_nrm, float* obj_nrm, const void* rest_light_tris,
+                             void* light_tris, long n_light_tri, const MatpbrPathLights* lights, void* stream) {
+    MoveTable mt;
+    if (!move_args_valid(nodes, tris, rest_tris, n_scene_tri, n_object_tri, first_object_node, n_object_nodes, node_level, object_depth, pad,
+                         rest_light_tris, light_tris, n_light_tri) ||
+        !move_table(objects, n_objects, xform, n_scene_tri, n_object_tri, rest_nrm, obj_nrm, lights, n_light_tri, mt))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    const long n = n_object_tri + n_light_tri;
+    hipLaunchKernelGGL(objects_move_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mt,
+                       static_cast<const float4*>(rest_tris), static_cast<float4*>(tris), n_scene_tri, n_object_tri, rest_nrm, obj_nrm,
+                       static_cast<const float4*>(rest_light_tris), static_cast<float4*>(light_tris), n_light_tri);
+    if (hipGetLastError() != hipSuccess) return MATPBR_PATH_ERR_LAUNCH;
+    hipLaunchKernelGGL(objects_refit_kernel, dim3(1), dim3(kRefitBlock), 0, (hipStream_t)stream, static_cast<BNode*>(nodes),
+                       static_cast<const float4*>(tris), first_object_node, n_object_nodes, node_level, object_depth, pad);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_objects_move_host(void* nodes, void* tris, const void* rest_tris, long n_scene_tri, long n_object_tri, long first_object_node,
+                                  long n_object_nodes, const int32_t* node_level, int object_depth, const MatpbrPathObject* objects, int n_objects,
+                                  const MatpbrPathXform* xform, float pad, const float* rest_nrm, float* obj_nrm, const void* rest_light_tris,
+                                  void* light_tris, long n_light_tri, const MatpbrPathLights* lights) {
+    MoveTable mt;
+    if (!move_args_valid(nodes, tris, rest_tris, n_scene_tri, n_object_tri, first_object_node, n_object_nodes, node_level, object_depth, pad,
+                         rest_light_tris, light_tris, n_light_tri) ||
+        !move_table(objects, n_objects, xform, n_scene_tri, n_object_tri, rest_nrm, obj_nrm, lights, n_light_tri, mt))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    BNode* nd = static_cast<BNode*>(nodes);
+    // the CPU walks the caller's nodes: every child an object node names must be an object node or an object triangle range
+    if (nd[0].count[1] < 0 ? nd[0].child[1] != first_object_node : (nd[0].child[1] < n_scene_tri || (long)nd[0].child[1] + nd[0].count[1] > n_scene_tri + n_object_tri))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long i = 0; i < n_object_nodes; ++i)
+        for (int s = 0; s < 2; ++s) {
+            const BNode& q = nd[first_object_node + i];
+            if (q.count[s] < 0 ? (q.child[s] <= first_object_node + i || q.child[s] >= first_object_node + n_object_nodes)
+                               : (q.child[s] < n_scene_tri || (long)q.child[s] + q.count[s] > n_scene_tri + n_object_tri))
+                return MATPBR_PATH_ERR_INVALID_ARG;
+        }
+    objects_move_host(mt, nd, static_cast<float4*>(tris), static_cast<const float4*>(rest_tris), n_scene_tri, n_object_tri, first_object_node,
+                      n_object_nodes, node_level, object_depth, pad, rest_nrm, obj_nrm, static_cast<const float4*>(rest_light_tris),
+                      static_cast<float4*>(light_tris), n_light_tri);
     return MATPBR_PATH_OK;
 }
 

@@ -244,6 +244,8 @@ struct Builder {
     BNode* nodes;
     long max_nodes, n_nodes = 0, n_leaves = 0;
     int depth = 0;
+    int level_cap = kMaxBvhDepth;           // the deepest level a slot may have: a range that reaches it becomes a leaf whatever its size
+    std::vector<int32_t>* levels = nullptr; // when set: the level of every node but the root, in node order (the grafted build's refit walks by it)
 
     Box range_box(int b, int e) const {
         Box r;
@@ -319,7 +321,7 @@ struct Builder {
             } else {
                 for (int c = 0; c < 3; ++c) { nd.b[6 * it.slot + c] = bx.lo[c]; nd.b[6 * it.slot + 3 + c] = bx.hi[c]; }
             }
-            if (it.e - it.b <= kLeafMax || it.level >= kMaxBvhDepth) {
+            if (it.e - it.b <= kLeafMax || it.level >= level_cap) {
                 nd.child[it.slot] = it.b;
                 nd.count[it.slot] = it.e - it.b;
                 ++n_leaves;
@@ -330,6 +332,7 @@ struct Builder {
             nd.child[it.slot] = (int32_t)q;
             nd.count[it.slot] = -1;
             std::memset(&nodes[q], 0, sizeof(BNode));
+            if (levels) levels->push_back(it.level);
             const int m = split(it.b, it.e);
             work.push_back({q, 1, m, it.e, it.level + 1});
             work.push_back({q, 0, it.b, m, it.level + 1});
@@ -337,4 +340,49 @@ struct Builder {
         return true;
     }
 };
+
+// scene scale: the largest coordinate magnitude; boxes are padded by 1e-6 of it so that fp32 rounding of (v0, e1, e2) stays inside
+inline double mesh_scale(const double* vert, long n_vert) {
+    double S = 0.0;
+    for (long k = 0; k < 3 * n_vert; ++k) S = std::max(S, std::fabs(vert[k]));
+    return S;
+}
+
+// the builder's input: padded box and centroid of triangles [first, first + N) of the mesh, as its triangles 0 .. N - 1
+inline void builder_load(Builder& bld, const double* vert, const int32_t* tri, long first, int N, float pad) {
+    bld.tb.resize(N);
+    bld.cen.resize(3 * (size_t)N);
+    bld.idx.resize(N);
+    for (int t = 0; t < N; ++t) {
+        const int32_t* ix = tri + 3 * (first + t);
+        Box b;
+        for (int c = 0; c < 3; ++c) {
+            double lo = DBL_MAX, hi = -DBL_MAX;
+            for (int v = 0; v < 3; ++v) { lo = std::min(lo, vert[3 * (long)ix[v] + c]); hi = std::max(hi, vert[3 * (long)ix[v] + c]); }
+            b.lo[c] = (float)lo - pad;
+            b.hi[c] = (float)hi + pad;
+            bld.cen[3 * t + c] = (float)(0.5 * (lo + hi));
+        }
+        bld.tb[t] = b;
+        bld.idx[t] = t;
+    }
+}
+
+// the record (v0, id) (e1, 0) (e2, 0) of triangle t of the mesh: v0, e1, e2 formed in fp64, stored fp32
+inline void tri_record(const double* vert, const int32_t* tri, long t, long n_scene_tri, float4* out) {
+    const double* v0 = vert + 3 * (long)tri[3 * t];
+    const double* v1 = vert + 3 * (long)tri[3 * t + 1];
+    const double* v2 = vert + 3 * (long)tri[3 * t + 2];
+    double e1[3], e2[3];
+    for (int c = 0; c < 3; ++c) { e1[c] = v1[c] - v0[c]; e2[c] = v2[c] - v0[c]; }
+    const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+    // depth mesh: e1 x e2 faces the camera at the origin; an inserted mesh keeps its winding (e1 x e2 = its outward normal)
+    if (t < n_scene_tri && nx * v0[0] + ny * v0[1] + nz * v0[2] > 0.0) std::swap(e1, e2);
+    const int32_t id = (int32_t)t;
+    float idf;
+    std::memcpy(&idf, &id, 4);
+    out[0] = make_float4((float)v0[0], (float)v0[1], (float)v0[2], idf);
+    out[1] = make_float4((float)e1[0], (float)e1[1], (float)e1[2], 0.0f);
+    out[2] = make_float4((float)e2[0], (float)e2[1], (float)e2[2], 0.0f);
+}
 }  // namespace

@@ -57,6 +57,11 @@ class PathLights(ctypes.Structure):
                 ("n_tri", ctypes.c_int32 * MAX_OBJECTS), ("area", ctypes.c_float * MAX_OBJECTS)]
 
 
+class PathXform(ctypes.Structure):
+    """MatpbrPathXform (include/matpbr_path.h): one object's pose, p' = R (s (p - c)) + c + t."""
+    _fields_ = [("R", ctypes.c_float * 9), ("s", ctypes.c_float), ("t", ctypes.c_float * 3), ("c", ctypes.c_float * 3)]
+
+
 class PathTransEdit(ctypes.Structure):
     """MatpbrPathTransEdit (include/matpbr_path.h): the scalars of a transparency edit."""
     _fields_ = [("ior", ctypes.c_float), ("spec_trans", ctypes.c_float), ("refract_distance", ctypes.c_float), ("reserved", ctypes.c_float)]
@@ -143,6 +148,12 @@ SIGNATURES = {
     "matpbr_path_denoise_diff_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "matpbr_path_denoise_diff": (ctypes.c_int, [_P] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "matpbr_path_denoise_diff_host": (ctypes.c_int, [_P] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_size_t]),
+    "matpbr_path_bvh_build_grafted": (ctypes.c_int, [_P, ctypes.c_long, ctypes.c_long, _P, ctypes.c_long, ctypes.c_long, ctypes.c_double, _P, ctypes.c_long] + [_P] * 9),
+    "matpbr_path_xform_check_host": (ctypes.c_int, [_P, ctypes.c_int]),
+    "matpbr_path_objects_move": (ctypes.c_int, [_P] * 3 + [ctypes.c_long] * 4 + [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_float] + [_P] * 4 +
+                                 [ctypes.c_long, _P, _P]),
+    "matpbr_path_objects_move_host": (ctypes.c_int, [_P] * 3 + [ctypes.c_long] * 4 + [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_float] + [_P] * 4 +
+                                      [ctypes.c_long, _P]),
 }
 VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
@@ -175,6 +186,9 @@ _FEATURE = {name: what for what, names in FEATURE_SYMBOLS.items() for name in na
 # the ten above, which stay the partition of LATE_SYMBOLS they were
 RATIO_SYMBOLS = ("matpbr_path_render_objects_ratio", "matpbr_path_composite_ratio", "matpbr_path_composite_ratio_host")
 RATIO_FEATURE = "ratio shadow transfer"
+# moving inserted objects' symbols ("Moving inserted objects"), added at version 3 as well: a third group beside them
+MOVE_SYMBOLS = ("matpbr_path_bvh_build_grafted", "matpbr_path_xform_check_host", "matpbr_path_objects_move", "matpbr_path_objects_move_host")
+MOVE_FEATURE = "moving inserted objects"
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
@@ -195,7 +209,7 @@ def load() -> ctypes.CDLL:
         _build.build_path_library()
         lib = ctypes.CDLL(_build.PATH_LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS) and not hasattr(lib, name):
+            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS) and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -209,7 +223,7 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        what = RATIO_FEATURE if name in RATIO_SYMBOLS else _FEATURE.get(name, "smooth inserted objects")
+        what = RATIO_FEATURE if name in RATIO_SYMBOLS else MOVE_FEATURE if name in MOVE_SYMBOLS else _FEATURE.get(name, "smooth inserted objects")
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 

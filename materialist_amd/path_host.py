@@ -41,6 +41,34 @@ def trace_scene_host(bvh: Dict[str, object], origins: np.ndarray, dirs: np.ndarr
     return _trace("matpbr_path_trace_scene_host", bvh, origins, dirs, tmin, tmax, int(n_scene_tri), int(bool(any)))
 
 
+def moved_light_areas(lights: dict, records) -> list:
+    """A light's area under its object's similarity, (float)((double) area_rest s s), for every light of `light_tables`' dict at rest."""
+    head = lights["header"]
+    return [float(np.float32(float(head.area[l]) * float(records[head.object[l]].s) * float(records[head.object[l]].s))) for l in range(head.n_lights)]
+
+
+def objects_move_host(bvh: Dict[str, object], table: Sequence[PathObject], n_scene_tri: int, records, rest_nrm: Optional[np.ndarray] = None,
+                      lights: Optional[dict] = None) -> dict:
+    """`PathTracer.move_objects` on the CPU with the routines the kernels run ("Moving inserted objects"):
+    `build_bvh_grafted`'s dict, `merge_objects`' table, `xform_records`' poses, the rest corner normals and the rest `light_tables` ->
+    {"nodes", "tris": moved copies (the dict is `bvh` with them, so `trace_host` takes it), "obj_nrm", "light_tris": moved copies or None,
+    "area": the lights' areas}.  The rest pose is not written.  PathError where the library refuses."""
+    out = dict(bvh)
+    out["nodes"], out["tris"] = np.array(bvh["nodes"], copy=True), np.array(bvh["tris"], copy=True)
+    n_obj = bvh["rest_tris"].size // 48
+    nrm = None if rest_nrm is None else np.ascontiguousarray(rest_nrm, dtype=np.float32)
+    out["obj_nrm"] = None if nrm is None else np.zeros_like(nrm)
+    ltris, head, n_light = (None, None, 0) if lights is None else _light_args(lights)
+    moved_l = None if lights is None else _aligned_texels(np.zeros((3 * n_light, 4), np.float32)).reshape(-1)   # 16-byte aligned records
+    tab, _ = _table_ptrs(table)
+    _call("matpbr_path_objects_move_host", out["nodes"], out["tris"], bvh["rest_tris"], int(n_scene_tri), n_obj, bvh["first_object_node"],
+          bvh["n_object_nodes"], np.ascontiguousarray(bvh["node_level"], dtype=np.int32), bvh["object_depth"], tab, len(table),
+          ctypes.cast(records, ctypes.c_void_p), float(bvh["pad"]), nrm, out["obj_nrm"], ltris, moved_l, n_light, head)
+    out["light_tris"] = None if lights is None else moved_l.reshape(-1, 3, 4).copy()
+    out["area"] = [] if lights is None else moved_light_areas(lights, records)
+    return out
+
+
 def through_chain_host(bvh: Dict[str, object], table: Sequence[PathObject], n_scene_tri: int, H: int, W: int, pixels, seeds, samples,
                        max_depth: int, obj_nrm: Optional[np.ndarray] = None, fov_x_deg: float = 35.0) -> dict:
     """The camera chain of `PathTracer.render_diff_through` on the CPU with the routines the kernel runs ("Seen

@@ -10,8 +10,8 @@ import numpy as np
 
 from .path_abi import (BSDF_AREA, BSDF_DIELECTRIC, BSDF_DIFFUSE, BSDF_PBR, BSDF_ROUGH_DIELECTRIC, MAX_OBJECTS, NODE_BYTES, OBJECT_COLORED,
                        OBJECT_SMOOTH, OBJECT_TEXTURED, PBR_DEFAULTS, PBR_MIN_ROUGHNESS, ROUGH_MIN_ALPHA, ROUGH_MIN_CONTRAST, TEXTURE_MAX_SIDE,
-                       TEXTURE_MAX_UV, TRI_BYTES, PathLights, PathObject, PathObjectPbr, PathObjectTex, _ptr, _ref, _table_ptrs, _uncolored, check,
-                       load, symbol)
+                       TEXTURE_MAX_UV, TRI_BYTES, PathLights, PathObject, PathObjectPbr, PathObjectTex, PathXform, _ptr, _ref, _table_ptrs, _uncolored,
+                       check, load, symbol)
 
 
 def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional[int] = None) -> Dict[str, object]:
@@ -34,6 +34,135 @@ def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional
     check(code, name)
     return {"nodes": nodes[: n_nodes.value * NODE_BYTES].copy(), "tris": tris, "n_nodes": n_nodes.value, "depth": depth.value,
             "n_leaves": n_leaves.value, "build_s": build_s}
+
+
+def build_bvh_grafted(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: int, reach: Optional[float] = None,
+                      n_scene_vert: Optional[int] = None) -> Dict[str, object]:
+    """The grafted host BVH of a merged mesh ("Moving inserted objects"; `matpbr_path_bvh_build_grafted`): node 0's
+    slot 0 is the depth mesh's subtree (triangles below `n_scene_tri`), slot 1 the inserted triangles' -> `build_bvh`'s dict plus
+    {"rest_tris" uint8 [n_object_tri*48]: the object triangles' records, the rest pose; "node_level" int32 [n_object_nodes];
+    "first_object_node", "n_object_nodes", "object_depth", "pad": 1e-6 of "reach", the largest coordinate magnitude of the mesh and of
+    `reach`, which announces the farthest pose a later move will ask for}.  `n_scene_vert`: the depth mesh's vertex count (the merged
+    mesh lists its vertices first; the scene side is padded by their scale); None: the vertices the scene's triangles name, which is
+    the same count unless the depth mesh ends in vertices no triangle uses."""
+    lib = load()
+    V = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    T = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+    n_scene, n_obj = int(n_scene_tri), T.shape[0] - int(n_scene_tri)
+    if n_scene < 1 or n_obj < 1:
+        raise ValueError(f"a grafted BVH needs the scene's triangles and inserted ones behind them: {T.shape[0]} triangles, n_scene_tri {n_scene_tri}")
+    nv_scene = int(T[:n_scene].max()) + 1 if n_scene_vert is None else int(n_scene_vert)
+    far = 0.0 if reach is None else float(reach)
+    if not (np.isfinite(far) and far >= 0):
+        raise ValueError(f"reach must be finite and >= 0, got {reach}")
+    cap = 1 + max(1, n_scene) + max(1, n_obj)
+    nodes = np.zeros(cap * NODE_BYTES, dtype=np.uint8)
+    tris, rest = np.zeros(T.shape[0] * TRI_BYTES, dtype=np.uint8), np.zeros(n_obj * TRI_BYTES, dtype=np.uint8)
+    level = np.zeros(cap, dtype=np.int32)
+    n_nodes, depth, n_leaves, first, obj_depth, pad = (ctypes.c_long(0), ctypes.c_int(0), ctypes.c_long(0), ctypes.c_long(0), ctypes.c_int(0),
+                                                       ctypes.c_float(0))
+    t0 = time.perf_counter()
+    code = symbol("matpbr_path_bvh_build_grafted", lib)(_ptr(V), V.shape[0], nv_scene, _ptr(T), T.shape[0], n_scene, far, _ptr(nodes), cap, _ptr(tris), _ptr(rest),
+                                                        _ptr(level), _ref(n_nodes), _ref(depth), _ref(n_leaves), _ref(first), _ref(obj_depth), _ref(pad))
+    build_s = time.perf_counter() - t0
+    check(code, "matpbr_path_bvh_build_grafted")
+    n_object_nodes = n_nodes.value - first.value
+    return {"nodes": nodes[: n_nodes.value * NODE_BYTES].copy(), "tris": tris, "n_nodes": n_nodes.value, "depth": depth.value,
+            "n_leaves": n_leaves.value, "build_s": build_s, "rest_tris": rest, "node_level": level[:n_object_nodes].copy(),
+            "first_object_node": first.value, "n_object_nodes": n_object_nodes, "object_depth": obj_depth.value, "pad": pad.value,
+            "reach": max(far, float(np.abs(V).max()))}
+
+
+XFORM_KEYS = ("scale", "rotate", "translate", "pivot")
+
+
+def rotation(axis, deg: float) -> np.ndarray:
+    """The rotation by `deg` degrees about `axis` (any length but zero), 3 x 3 float64 (Rodrigues); ValueError when bad."""
+    try:
+        a, ang = np.asarray(axis, dtype=np.float64), float(deg)
+    except (TypeError, ValueError):
+        raise ValueError(f"a rotation needs an axis of 3 numbers and an angle in degrees, got {axis!r} and {deg!r}") from None
+    if a.shape != (3,) or not np.isfinite(a).all() or not np.isfinite(ang):
+        raise ValueError(f"a rotation needs a finite axis of 3 numbers and a finite angle, got {axis!r} and {deg!r}")
+    ln = float(np.linalg.norm(a))
+    if not ln > 0:
+        raise ValueError("a rotation's axis must not be zero")
+    x, y, z = a / ln
+    K = np.array([[0, -z, y], [z, 0, -x], [-y, x, 0]])
+    th = np.radians(ang)
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def similarity(transform: Optional[dict], pivot=None) -> tuple:
+    """A placement {"scale": s (1), "rotate": 3 x 3 or {"axis", "deg"} (none), "translate" (0), "pivot" (`pivot`, else 0)} ->
+    (R [3,3], s, t [3], c [3]) in float64, p' = R (s (p - c)) + c + t; None is the identity about `pivot`.  ValueError for an unknown key,
+    a value of the wrong shape, a non-finite one, a scale that is not positive or a zero axis.  Whether R is a rotation is the library's
+    to say (`check_xforms`)."""
+    tr = {} if transform is None else transform
+    if not isinstance(tr, dict):
+        raise ValueError(f"a transform must be a dict with keys of {XFORM_KEYS}, got {type(tr).__name__}")
+    extra = sorted(set(tr) - set(XFORM_KEYS))
+    if extra:
+        raise ValueError(f"transform: unknown key {extra[0]!r} (known: {', '.join(repr(k) for k in XFORM_KEYS)})")
+    rot = tr.get("rotate")
+    if rot is None:
+        R = np.eye(3)
+    elif isinstance(rot, dict):
+        extra = sorted(set(rot) - {"axis", "deg"})
+        if extra or "axis" not in rot or "deg" not in rot:
+            raise ValueError(f"transform: 'rotate' must be a 3 x 3 matrix or {{'axis': [x, y, z], 'deg': a}}, got {rot!r}")
+        R = rotation(rot["axis"], rot["deg"])
+    else:
+        try:
+            R = np.array(rot, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"transform: 'rotate' must be a 3 x 3 matrix or {{'axis': [x, y, z], 'deg': a}}, got {rot!r}") from None
+        if R.shape != (3, 3):
+            raise ValueError(f"transform: 'rotate' must be 3 x 3, got shape {R.shape}")
+    try:
+        s = float(tr.get("scale", 1.0))
+        t = np.array(tr.get("translate", (0.0, 0.0, 0.0)), dtype=np.float64)
+        c = np.array(tr.get("pivot") if tr.get("pivot") is not None else (pivot if pivot is not None else (0.0, 0.0, 0.0)), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"transform: 'scale' must be a number, 'translate' and 'pivot' 3 numbers, got {tr!r}") from None
+    if t.shape != (3,) or c.shape != (3,):
+        raise ValueError(f"transform: 'translate' and 'pivot' must be 3 numbers, got shapes {t.shape} and {c.shape}")
+    if not (np.isfinite(R).all() and np.isfinite(s) and np.isfinite(t).all() and np.isfinite(c).all()):
+        raise ValueError(f"transform: every value must be finite, got {tr!r}")
+    if not s > 0:
+        raise ValueError(f"transform: 'scale' must be positive, got {s}")
+    return R, s, t, c
+
+
+def apply_similarity(sim: tuple, points: np.ndarray, vectors: bool = False) -> np.ndarray:
+    """p' = R (s (p - c)) + c + t of points [..., 3] in float64; `vectors`: R p alone (normals)."""
+    R, s, t, c = sim
+    P = np.asarray(points, dtype=np.float64)
+    return P @ R.T if vectors else (s * (P - c)) @ R.T + (c + t)
+
+
+def xform_records(sims: Sequence[tuple]):
+    """The similarities as the library takes them: a PathXform array (fp32)."""
+    return (PathXform * len(sims))(*(PathXform((ctypes.c_float * 9)(*R.reshape(-1)), s, (ctypes.c_float * 3)(*t), (ctypes.c_float * 3)(*c))
+                                     for R, s, t, c in sims))
+
+
+def check_xforms(records) -> None:
+    """ValueError unless the library takes every record (`matpbr_path_xform_check_host`): finite, scale > 0, R's rows orthonormal to
+    1e-5, det R > 0.  Names the first record it refuses."""
+    fn = symbol("matpbr_path_xform_check_host")
+    for k in range(len(records)):
+        if fn(ctypes.cast(ctypes.byref(records[k]), ctypes.c_void_p), 1) != 0:
+            x = records[k]
+            raise ValueError(f"transform of object {k}: every value must be finite, the scale positive and 'rotate' a rotation (rows orthonormal "
+                             f"to 1e-5, no mirror), got R = {[round(v, 6) for v in x.R]}, scale = {x.s}")
+
+
+def pose_extent(sim: tuple, lo: np.ndarray, hi: np.ndarray) -> float:
+    """The largest coordinate magnitude of the box [lo, hi] under a similarity: that of its eight corners, which bounds the magnitude of
+    everything inside the box (a coordinate is linear, so its extremes over the moved box lie at corners)."""
+    corners = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], dtype=np.float64)
+    return float(np.abs(apply_similarity(sim, corners)).max())
 
 
 def env_tables(env: np.ndarray) -> Dict[str, object]:

@@ -16,6 +16,7 @@ ratio of the model's radiance with and without the objects ("Ratio shadow transf
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -59,13 +60,21 @@ class PathTracer:
     (base colour, linear, in [0, 1], row 0 the top row) and, a pbr one, "orm_texture" [h,w,3] ("Textured inserted
     objects"; `stats["n_textured_objects"]` counts them): the reflectance or the albedo is multiplied by the base colour, the roughness
     and the metallic by the orm image's g and b, each read with bilinear filtering and repeat wrapping at the coordinate interpolated
-    at the hit.  A tracer with objects renders forward only."""
+    at the hit.  A tracer with objects renders forward only.  `movable=True` (with objects; DESIGN.md section 1.4, "Moving inserted
+    objects"; `stats["movable"]`): the BVH is grafted, the depth mesh's subtree and the objects' under one root, and the objects' rest
+    pose stays on the device, so that `move_objects` places them anew without a rebuild (two launches; well under a millisecond for a small mesh); `reach`: the largest coordinate magnitude any
+    later pose will have (default, and at least: the rest scene's; `stats["reach"]`), for which the boxes are padded.  `movable=False`
+    is the merged BVH and the static route."""
 
     def __init__(self, vertices: np.ndarray, triangles: np.ndarray, H: int, W: int, fov_x_deg: float = 35.0, device="cuda",
-                 objects: Optional[Sequence[dict]] = None):
+                 objects: Optional[Sequence[dict]] = None, movable: bool = False, reach: Optional[float] = None):
+        if movable and not objects:
+            raise ValueError("movable=True moves inserted objects: build the PathTracer with `objects`")
         self.H, self.W, self.fov = int(H), int(W), float(fov_x_deg)
         self.device = torch.device(device)
+        self._move: Optional[dict] = None             # what `move_objects` needs of a movable tracer: the rest pose on the device, the refit's tables
         n_scene = int(np.asarray(triangles).reshape(-1, 3).shape[0])
+        n_scene_vert = int(np.asarray(vertices).reshape(-1, 3).shape[0])
         self.objects = None
         self.obj_nrm: Optional[torch.Tensor] = None   # corner normals of the inserted triangles, when some object is smooth
         self.n_scene_tris = n_scene
@@ -98,10 +107,25 @@ class PathTracer:
                 self.pbr = (PathObjectPbr * len(scene.records))(*scene.records)   # the entry points from the lights' on take the records beside the table as well
             if scene.obj_nrm is not None:
                 self.obj_nrm = torch.from_numpy(scene.obj_nrm).to(self.device)
-            bvh = build_bvh(vertices, triangles, n_scene)
+            if movable:
+                symbol("matpbr_path_objects_move")    # a library built before the feature: PathError now, not at the first move
+                bvh = build_bvh_grafted(vertices, triangles, n_scene, reach, n_scene_vert)
+            else:
+                bvh = build_bvh(vertices, triangles, n_scene)
         else:
             bvh = build_bvh(vertices, triangles)
         self.stats = {k: bvh[k] for k in ("n_nodes", "depth", "n_leaves", "build_s")}
+        if movable:
+            dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+            boxes = [(np.asarray(ob["vertices"], np.float64).min(0), np.asarray(ob["vertices"], np.float64).max(0)) for ob in objects]
+            self._move = {"rest_tris": dev(bvh["rest_tris"]), "node_level": dev(bvh["node_level"]), "first_object_node": bvh["first_object_node"],
+                          "n_object_nodes": bvh["n_object_nodes"], "object_depth": bvh["object_depth"], "pad": bvh["pad"], "boxes": boxes,
+                          "rest_nrm": None if self.obj_nrm is None else self.obj_nrm.clone(),
+                          "rest_light_tris": None if self.lights is None else self.lights[1].clone(),
+                          "rest_lights": None if self.lights is None else scene.lights}
+            self.reach = bvh["reach"]                 # the largest coordinate magnitude a pose may have: the boxes' padding was sized for it
+            self.stats["movable"] = True
+            self.stats["reach"] = self.reach
         self.stats["n_tris"] = int(np.asarray(triangles).reshape(-1, 3).shape[0])
         self.stats["n_objects"] = len(self.objects) if self.objects is not None else 0
         self.stats["n_object_tris"] = self.stats["n_tris"] - n_scene
@@ -168,6 +192,53 @@ class PathTracer:
             return None, None, None, 0
         uv, rec, texels = self.textures
         return (uv.data_ptr(), *_tex_ptrs(self.objects, rec, texels))
+
+    def poses(self, transforms: Sequence[Optional[dict]]):
+        """`move_objects`' argument checked, before any device work -> the PathXform records: one entry per object, each None or a
+        placement `similarity` takes (the default pivot is the centre of the object's rest bounding box); every record one the library
+        takes (`check_xforms`); every pose within `reach`.  ValueError otherwise, also on a tracer that is not movable."""
+        if self._move is None:
+            raise ValueError("move_objects needs a movable tracer: build the PathTracer with `objects` and movable=True")
+        n = len(self.objects)
+        if transforms is None or len(transforms) != n:
+            raise ValueError(f"transforms must hold one entry per object ({n}), each a dict or None, got {None if transforms is None else len(transforms)}")
+        boxes = self._move["boxes"]
+        records = xform_records([similarity(tr, pivot=0.5 * (lo + hi)) for tr, (lo, hi) in zip(transforms, boxes)])
+        check_xforms(records)
+        for k, (x, (lo, hi)) in enumerate(zip(records, boxes)):
+            sim = (np.array(x.R, np.float64).reshape(3, 3), float(x.s), np.array(x.t, np.float64), np.array(x.c, np.float64))
+            far = pose_extent(sim, lo, hi)
+            if not far <= self.reach:
+                raise ValueError(f"the pose of object {k} reaches a coordinate of magnitude {far:.6g}, beyond this tracer's reach {self.reach:.6g}: "
+                                 f"the boxes' padding was sized for it; build the PathTracer with reach={far:.6g} or more")
+        return records
+
+    @torch.no_grad()
+    def move_objects(self, transforms: Sequence[Optional[dict]]) -> None:
+        """Moves the inserted objects of a movable tracer ("Moving inserted objects"): `transforms` holds one entry
+        per object, None for an object left at rest or {"scale": s, "rotate": 3 x 3 or {"axis": (x, y, z), "deg": a}, "translate": (x, y, z),
+        "pivot": (x, y, z)}, every part optional: p' = R (s (p - pivot)) + pivot + translate, the pivot by default the centre of the
+        object's rest bounding box.  Always from the rest pose the tracer was built with, never from the last pose.  Everything is
+        checked first (`poses`); then the move and the refit of the object nodes are enqueued on the current stream and a light's area
+        becomes (float)((double) area_rest s s).  Every other method sees the moved scene from then on."""
+        records = self.poses(transforms)
+        mv, dev = self._move, self.device
+        head, ltris = (None, None) if self.lights is None else self.lights[:2]
+        n_obj = self.stats["n_object_tris"]
+        if head is not None:
+            rest = mv["rest_lights"]["header"]
+            moved = PathLights.from_buffer_copy(rest)
+            for l, area in enumerate(moved_light_areas(mv["rest_lights"], records)):
+                moved.area[l] = area
+            head = moved
+        check(symbol("matpbr_path_objects_move")(
+            self.nodes.data_ptr(), self.tris.data_ptr(), mv["rest_tris"].data_ptr(), self.n_scene_tris, n_obj, mv["first_object_node"],
+            mv["n_object_nodes"], mv["node_level"].data_ptr(), mv["object_depth"], _table_ptrs(self.objects)[0], len(self.objects),
+            ctypes.cast(records, ctypes.c_void_p), mv["pad"], _dptr(mv["rest_nrm"]), _dptr(self.obj_nrm), _dptr(mv["rest_light_tris"]), _dptr(ltris),
+            0 if ltris is None else int(ltris.shape[0]), None if head is None else _ref(head), torch.cuda.current_stream(dev).cuda_stream),
+            "matpbr_path_objects_move")
+        if head is not None:
+            self.lights = (head, *self.lights[1:])
 
     @torch.no_grad()
     def render(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, spp: int = 64, max_depth: int = 4,

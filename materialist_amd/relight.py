@@ -177,9 +177,10 @@ def _scene_normal(scene_dir: str, mat: Dict[str, torch.Tensor], save_name: str, 
     return ops.normals_from_depth(torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(device))
 
 
-def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], device, objects=None):
+def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], device, objects=None, **movable):
     """PathTracer on the scene's `<save_name>.ply`; without one, the mesh the pipeline would write (depthPred.exr -> 2 max - d,
-    mesh_mask.png pixels removed, mesh.reference_mesh: inverse_img_w_mi.py:721-727).  `objects`: PathTracer's inserted meshes."""
+    mesh_mask.png pixels removed, mesh.reference_mesh: inverse_img_w_mi.py:721-727).  `objects`: PathTracer's inserted meshes;
+    `movable`: its `movable` and `reach`."""
     from . import mesh as _mesh
     from .pathtrace import PathTracer
     from .render import DEFAULT_FOV
@@ -196,7 +197,7 @@ def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], d
             depth[mm.numpy()] = 0.0
         rm = _mesh.reference_mesh(depth, DEFAULT_FOV)
         V, T = rm["vertices"], rm["triangles"]
-    return PathTracer(V, T, H, W, DEFAULT_FOV, device=device, objects=objects)
+    return PathTracer(V, T, H, W, DEFAULT_FOV, device=device, objects=objects, **movable)
 
 
 def _check_integrator(integrator: str, shading_normals: str = "face") -> None:
@@ -340,9 +341,12 @@ def load_oi_scene(path: str) -> List[dict]:
     display values, decoded to linear as `loss.srgb_to_linear` decodes) or "vertex_linear" (the file's values as written, what Mitsuba's
     `mesh_attribute` does; DESIGN.md section 1.4, "Vertex-coloured inserted objects"); "texture": "wood.png" (a diffuse or pbr object
     only) and "orm_texture": "wood_orm.png" (a pbr object only) name images relative to the file, read over the ply's per-vertex texture
-    coordinates ("Textured inserted objects")
-    -> [{"ply": absolute path, "bsdf", "normals", "colors", "texture": absolute path or None, "orm_texture"}], nothing read yet but the
-    list.  ValueError naming
+    coordinates ("Textured inserted objects"); "transform": {"scale": 1, "rotate": {"axis": [x, y, z], "deg": a}, "translate": [x, y, z], "pivot": [x, y, z]} places the mesh
+    (every part optional, the pivot by default the centre of its bounding box) and "motion": {"spin": {"axis": [x, y, z],
+    "deg_per_frame": a}, "slide": [dx, dy, dz]} moves it from frame to frame of `render_oi(frames=N)` (`oi_pose`; DESIGN.md section 1.4,
+    "Moving inserted objects")
+    -> [{"ply": absolute path, "bsdf", "normals", "colors", "texture": absolute path or None, "orm_texture", "transform": the dict or
+    None, "motion"}], nothing read yet but the list.  ValueError naming
     the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
     import json
 
@@ -367,9 +371,10 @@ def load_oi_scene(path: str) -> List[dict]:
         where = f"{path}: objects[{k}]"
         if not isinstance(ob, dict):
             raise ValueError(f"{where} must be an object with 'ply' and 'bsdf'")
-        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors", "texture", "orm_texture"})
+        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors", "texture", "orm_texture", "transform", "motion"})
         if extra:
-            raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals', 'colors', 'texture', 'orm_texture')")
+            raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals', 'colors', 'texture', 'orm_texture', 'transform', "
+                             f"'motion')")
         if not isinstance(ob.get("ply"), str) or not ob["ply"]:
             raise ValueError(f"{where}: 'ply' must name a mesh file")
         ply = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob["ply"]))
@@ -401,8 +406,60 @@ def load_oi_scene(path: str) -> List[dict]:
             images[key] = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob[key]))
             if not os.path.isfile(images[key]):
                 raise ValueError(f"{where}: no such {key}: {images[key]}")
-        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals, "colors": colors, **images})
+        transform, motion = ob.get("transform"), ob.get("motion")
+        try:
+            oi_pose(transform, motion, 1)
+        except ValueError as e:
+            raise ValueError(f"{where}: {e}") from None
+        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals, "colors": colors, **images, "transform": transform, "motion": motion})
     return out
+
+
+def oi_pose(transform: Optional[dict], motion: Optional[dict], frame: int, pivot=None) -> tuple:
+    """An object list entry's pose at frame `frame` -> `pathtrace.similarity`'s (R, s, t, c) in float64.  "transform": {"scale",
+    "rotate": {"axis", "deg"}, "translate", "pivot"} places the object (every part optional; the pivot by default `pivot`, the centre of
+    the mesh's bounding box); "motion": {"spin": {"axis", "deg_per_frame"}, "slide": [dx, dy, dz]} turns and slides it per frame: the
+    rotation is spin(frame deg_per_frame) o rotate, the translation translate + frame slide, about the same pivot.  ValueError for an
+    unknown sub-key, a zero axis, a scale that is not positive or a value that is not finite."""
+    from .pathtrace import rotation, similarity
+
+    if transform is not None and not isinstance(transform, dict):
+        raise ValueError(f"'transform' must be an object with keys of 'scale', 'rotate', 'translate', 'pivot', got {transform!r}")
+    if transform is not None and not isinstance(transform.get("rotate", {}), dict):
+        raise ValueError(f"'transform': 'rotate' must be {{\"axis\": [x, y, z], \"deg\": a}}, got {transform['rotate']!r}")
+    R, s, t, c = similarity(transform, pivot)
+    if motion is None:
+        return R, s, t, c
+    if not isinstance(motion, dict):
+        raise ValueError(f"'motion' must be an object with keys of 'spin', 'slide', got {motion!r}")
+    extra = sorted(set(motion) - {"spin", "slide"})
+    if extra:
+        raise ValueError(f"'motion': unknown key {extra[0]!r} (known: 'spin', 'slide')")
+    spin = motion.get("spin")
+    if spin is not None:
+        if not isinstance(spin, dict) or set(spin) != {"axis", "deg_per_frame"}:
+            raise ValueError(f"'motion': 'spin' must be {{\"axis\": [x, y, z], \"deg_per_frame\": a}}, got {spin!r}")
+        try:
+            R = rotation(spin["axis"], frame * float(spin["deg_per_frame"])) @ R
+        except TypeError:
+            raise ValueError(f"'motion': 'spin' needs a number of degrees per frame, got {spin['deg_per_frame']!r}") from None
+    if motion.get("slide") is not None:
+        try:
+            slide = np.array(motion["slide"], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"'motion': 'slide' must be 3 numbers, got {motion['slide']!r}") from None
+        if slide.shape != (3,) or not np.isfinite(slide).all():
+            raise ValueError(f"'motion': 'slide' must be 3 finite numbers, got {motion['slide']!r}")
+        t = t + frame * slide
+    return R, s, t, c
+
+
+def _oi_moves(motion: Optional[dict]) -> bool:
+    """Whether an entry's "motion" changes its pose from frame to frame."""
+    if not motion:
+        return False
+    spin, slide = motion.get("spin"), motion.get("slide")
+    return bool(spin is not None and float(spin["deg_per_frame"]) != 0.0) or bool(slide is not None and np.any(np.asarray(slide, np.float64) != 0))
 
 
 OI_COLORS = ("none", "vertex", "vertex_linear")
@@ -480,7 +537,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
               denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
               object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None,
-              composite_denoise: bool = False, see_through: bool = False, shadows: str = "additive") -> str:
+              composite_denoise: bool = False, see_through: bool = False, shadows: str = "additive", frames: int = 1):
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -521,7 +578,13 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     are `PathTracer.render_diff_ratio`'s (with the photograph when `see_through`), `base` is summed with the others, and the picture
     is `composite_ratio`.  With `composite_denoise`, `base` passes `PathTracer.denoise_diff` a second time in delta's place beside a
     zero fg, which gives it delta's coverage weighting.  The output names are `composite`'s.  "ratio" without `composite`, or another
-    value, is a ValueError before any other work; with "additive" the code path, and so the bytes, are the ones without it."""
+    value, is a ValueError before any other work; with "additive" the code path, and so the bytes, are the ones without it.  An entry of
+    `objects_file` may carry "transform" and "motion" (`load_oi_scene`, `oi_pose`; DESIGN.md section 1.4, "Moving inserted objects").
+    `frames` 1 (default): a still; a "transform" is baked into the vertices and normals on the host in fp64 before the meshes are merged
+    (the identity leaves the file's bytes), and "motion" is ignored with a printed line.  `frames` > 1: a video: one movable tracer, per
+    frame `PathTracer.move_objects` to the frame's poses and then the very branch a still runs for the options given, the feature guides
+    computed anew -> <out>/oi_animation/frame_%04d.png, mi_oi[c]_<name>_<env>.mp4 and .gif, and the dict of paths
+    `render_rolling_envmap` returns.  `frames` > 1 without an `objects_file` in which an object moves is a ValueError."""
     if shadows not in OI_SHADOWS:
         raise ValueError(f"shadows must be 'additive' or 'ratio', got {shadows!r}")
     if shadows == "ratio" and not composite:
@@ -532,9 +595,17 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     from . import pathtrace as _pathtrace
 
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
+    if frames < 1:
+        raise ValueError(f"frames must be at least 1, got {frames}")
+    placed = None                                       # per object (its "transform", its "motion"), with an object list
     if objects_file is not None:
-        have = [(e["ply"], e["bsdf"], e["normals"], e["colors"], e["texture"], e["orm_texture"]) for e in load_oi_scene(objects_file)]
-    else:
+        entries = load_oi_scene(objects_file)
+        have = [(e["ply"], e["bsdf"], e["normals"], e["colors"], e["texture"], e["orm_texture"]) for e in entries]
+        placed = [(e["transform"], e["motion"]) for e in entries]
+    if frames > 1 and not (placed and any(_oi_moves(mo) for _, mo in placed)):
+        raise ValueError(f"frames={frames} would render {frames} equal frames: give an objects_file in which an object has a \"motion\" "
+                         f"(\"spin\" with a deg_per_frame other than 0, or a \"slide\" other than 0)")
+    if objects_file is None:
         plys = [os.path.join(scene_dir, "oi.ply"), os.path.join(scene_dir, "oi2.ply")]
         bsdfs = [{"type": "dielectric", "int_ior": OI_INT_IOR, "ext_ior": OI_EXT_IOR}, {"type": "diffuse", "reflectance": (OI_REFLECTANCE,) * 3}]
         have = [(p, b, object_normals, c, t, None) for p, b, c, t in zip(plys, bsdfs, ("none", object_colors), (None, object_texture))
@@ -556,8 +627,18 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     photo = _oi_photo(scene_dir, photo_path, atrous, env_scale) if composite else None
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
-    for p, b, normals, colors, texture, orm_texture in have:
+    for k, (p, b, normals, colors, texture, orm_texture) in enumerate(have):
         V, T, Nn, Cc, Uv = _mesh.read_ply_any(p, normals=True, colors=True, uv=True)
+        if normals == "vertex" and Nn is None:
+            Nn = _mesh.angle_weighted_normals(V, T)
+        transform, motion = placed[k] if placed else (None, None)
+        if frames == 1 and motion is not None:
+            print(f"{p}: \"motion\" is ignored for a still (frames=1)")
+        if frames == 1 and transform is not None:     # the static route: the placement baked into the vertices and normals, fp64
+            sim = oi_pose(transform, None, 0, pivot=0.5 * (np.asarray(V, np.float64).min(0) + np.asarray(V, np.float64).max(0)))
+            if not (np.array_equal(sim[0], np.eye(3)) and sim[1] == 1.0 and not sim[2].any()):   # the identity leaves the file's bytes
+                V = _pathtrace.apply_similarity(sim, V)
+                Nn = None if Nn is None else _pathtrace.apply_similarity(sim, Nn, vectors=True)
         objects.append({"vertices": V, "triangles": T, "bsdf": b})
         if texture is not None or orm_texture is not None:
             objects[-1]["uv"] = _object_uv(p, Uv)
@@ -568,14 +649,61 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
         if colors != "none":
             objects[-1]["colors"] = _object_colors(p, Cc, colors)
         if normals == "vertex":
-            objects[-1]["normals"] = Nn if Nn is not None else _mesh.angle_weighted_normals(V, T)
+            objects[-1]["normals"] = Nn
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
-    pt = _path_tracer(scene_dir, save_name, mat, device, objects)
     env = _scaled_env(load_image(env_path), env_scale)
+    env_id = os.path.basename(env_path)[:-4]
+    out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
+    base = os.path.join(out_dir, f"mi_oi{'c' if composite else ''}_{save_name}_{env_id}")   # (:233-236)
+    image = lambda pt, tabs: _oi_image(pt, tabs, mat, env, photo, [h[1] for h in have], spp, n_iter, max_depth, seed, device, atrous, composite,
+                                       composite_denoise, see_through, shadows == "ratio")
+    if frames > 1:
+        return _oi_animation(scene_dir, save_name, mat, device, objects, placed, frames, env, image, out_dir, base)
+    pt = _path_tracer(scene_dir, save_name, mat, device, objects)
+    img = image(pt, pt.tables(env))
+    os.makedirs(out_dir, exist_ok=True)
+    write_exr(base + ".exr", img.cpu().numpy())
+    write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
+    return base + ".png"
+
+
+def _oi_animation(scene_dir: str, save_name: str, mat, device, objects, placed, frames: int, env, image, out_dir: str, base: str) -> Dict[str, object]:
+    """`render_oi(frames > 1)`: one movable tracer over the files' meshes as they are (the rest pose), `reach` the farthest any frame's pose
+    carries a corner of a rest bounding box; per frame `move_objects` to the frame's poses and then `image(pt, tabs)`, the branch a still
+    runs -> <out>/oi_animation/frame_%04d.png, `base`.mp4 and .gif, as `render_rolling_envmap` writes its own."""
+    from . import pathtrace as _pathtrace
+
+    boxes = [(np.asarray(ob["vertices"], np.float64).min(0), np.asarray(ob["vertices"], np.float64).max(0)) for ob in objects]
+    sims = [[oi_pose(tr, mo, f, pivot=0.5 * (lo + hi)) for (tr, mo), (lo, hi) in zip(placed, boxes)] for f in range(frames)]
+    reach = max(_pathtrace.pose_extent(sim, lo, hi) for per_frame in sims for sim, (lo, hi) in zip(per_frame, boxes))
+    pt = _path_tracer(scene_dir, save_name, mat, device, objects, movable=True, reach=reach * (1 + 1e-6))   # the poses are rounded to fp32 on their way
     tabs = pt.tables(env)
+    anim_dir = os.path.join(out_dir, "oi_animation")
+    os.makedirs(anim_dir, exist_ok=True)
+    paths, imgs = [], []
+    for f in range(frames):
+        pt.move_objects([{"rotate": R, "scale": s, "translate": t, "pivot": c} for R, s, t, c in sims[f]])
+        srgb = _loss.linear_to_srgb(image(pt, tabs).clamp_min(0)).clamp(0, 1).cpu().numpy()
+        paths.append(os.path.join(anim_dir, f"frame_{f:04d}.png"))
+        write_png(paths[-1], srgb)
+        imgs.append((srgb * 255 + 0.5).astype(np.uint8))
+    from PIL import Image
+
+    from .video_mp4 import write_mp4
+
+    pil = [Image.fromarray(i) for i in imgs]
+    pil[0].save(base + ".gif", save_all=True, append_images=pil[1:], duration=100, loop=0)
+    return {"animation_dir": anim_dir, "frames": paths, "gif": base + ".gif", "mp4": write_mp4(base + ".mp4", imgs, fps=10)}
+
+
+def _oi_image(pt, tabs, mat, env, photo, bsdfs, spp: int, n_iter: int, max_depth: int, seed: int, device, atrous: bool, composite: bool,
+              composite_denoise: bool, see_through: bool, ratio: bool) -> torch.Tensor:
+    """One picture of `render_oi` from the tracer as it stands: the branch its options select (plain, denoise="atrous", composite,
+    composite_denoise, see_through, shadows="ratio"), the feature guides computed now."""
+    from . import pathtrace as _pathtrace
+
     diff = (lambda n, sd: pt.render_diff_through(mat["albedo"], mat["roughness"], mat["metallic"], env, photo, n, max_depth, sd, tables=tabs)[:4]) if see_through else \
            (lambda n, sd: pt.render_diff(mat["albedo"], mat["roughness"], mat["metallic"], env, n, max_depth, sd, tables=tabs)[:3])
-    ratio = shadows == "ratio"
     if ratio:   # (fg, delta, alpha[, through], base): the additive frame's order, base last
         def diff(n, sd):
             fg, delta, base, alpha, *through, _ = pt.render_diff_ratio(mat["albedo"], mat["roughness"], mat["metallic"], env, n, max_depth, sd, tables=tabs,
@@ -589,7 +717,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
                 halves[k] = frame if halves[k] is None else tuple(x + y for x, y in zip(halves[k], frame))
         geom = pt.features()
         tint = pt.feature_tints() if pt.stats["n_textured_objects"] else pt.feature_colors() if pt.stats["n_colored_objects"] else None
-        guide = albedo_guide(geom, mat["albedo"], [h[1] for h in have], tint)
+        guide = albedo_guide(geom, mat["albedo"], bsdfs, tint)
         fg, delta, alpha = pt.denoise_diff(halves[0][:3], halves[1][:3], guide, geom, 1.0 / n_iter)
         if ratio:   # base in delta's place beside a zero fg: delta's coverage weighting
             zero = torch.zeros_like(halves[0][0])
@@ -611,19 +739,13 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
         geom = pt.features()
         half = lambda sd: pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp // 2, max_depth, sd, tables=tabs)
         tint = pt.feature_tints() if pt.stats["n_textured_objects"] else pt.feature_colors() if pt.stats["n_colored_objects"] else None
-        img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], [h[1] for h in have], tint))
+        img = _denoised(pt, half, n_iter, seed, geom, albedo_guide(geom, mat["albedo"], bsdfs, tint))
     else:
         img = torch.zeros_like(mat["albedo"])
         for i in range(n_iter):
             img += pt.render(mat["albedo"], mat["roughness"], mat["metallic"], env, spp, max_depth, seed + i, tables=tabs)
         img /= n_iter
-    env_id = os.path.basename(env_path)[:-4]
-    out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
-    os.makedirs(out_dir, exist_ok=True)
-    base = os.path.join(out_dir, f"mi_oi{'c' if composite else ''}_{save_name}_{env_id}")   # (:233-236)
-    write_exr(base + ".exr", img.cpu().numpy())
-    write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
-    return base + ".png"
+    return img
 
 
 TRANS_ALBEDO, TRANS_ROUGHNESS, TRANS_METALLIC = 0.7, 0.3, 0.0   # the maps inside the mask (trans_edit.py:25-28)

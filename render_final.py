@@ -71,6 +71,10 @@ def parse_args(argv=None):
     ap.add_argument("--oi_photo", type=str, default=None, metavar="PATH",
                     help="--oi_composite: the photograph, of the maps' size (default <scene>/gt_image.exr, linear, as the pipeline writes it; a "
                          ".png holds display values and is decoded as the pipeline decodes its input)")
+    ap.add_argument("--oi_frames", type=int, default=1, metavar="N",
+                    help="--mode oi with --oi_scene: N > 1 renders a video of the objects whose entry carries a \"motion\" ({\"spin\": {\"axis\": "
+                         "[x, y, z], \"deg_per_frame\": a}, \"slide\": [dx, dy, dz]}), each frame with the options given, into "
+                         "<out>/oi_animation/frame_%%04d.png and mi_oi[c]_<name>_<env>.mp4 / .gif; 1 = a still, a \"transform\" baked in")
     ap.add_argument("--oi_max_depth", type=int, default=16, help="--mode oi: Mitsuba's max_depth (a camera path through glass needs 5 to see light)")
     a = ap.parse_args(argv)
     if a.shading_normals == "map" and (a.integrator != "path" or a.mode == "oi"):
@@ -96,6 +100,10 @@ def parse_args(argv=None):
         ap.error("--oi_composite_denoise splits every frame into two halves of spp/2 samples: --spp must be even")
     if a.oi_composite and a.env_scale != 1.0:
         ap.error("--oi_composite needs --env_scale 1: the photograph was taken under the envmap as it is and is not dimmed")
+    if a.oi_frames < 1:
+        ap.error("--oi_frames must be at least 1")
+    if a.oi_frames > 1 and (a.mode != "oi" or a.oi_scene is None):
+        ap.error("--oi_frames N > 1 needs --mode oi and an --oi_scene in which an object has a \"motion\"")
     if a.denoise == "atrous":
         if a.mode != "oi" and a.integrator != "path":
             ap.error("--denoise atrous needs --integrator path (or --mode oi): the sh render is deterministic and has no noise to filter")
@@ -118,13 +126,18 @@ def main(argv=None):
                                             **it)
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
-        print("Wrote file to", relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
-                                                 object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene,
-                                                 env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture,
-                                                 **({"composite": True, "photo_path": a.oi_photo} if a.oi_composite else {}),
-                                                 **({"composite_denoise": True} if a.oi_composite_denoise else {}),
-                                                 **({"see_through": True} if a.oi_see_through else {}),
-                                                 **({"shadows": a.oi_shadows} if a.oi_shadows != "additive" else {})))
+        res = relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
+                                object_normals=a.oi_normals, denoise=a.denoise, objects_file=a.oi_scene,
+                                env_scale=a.env_scale, object_colors=a.oi_colors, object_texture=a.oi_texture,
+                                **({"composite": True, "photo_path": a.oi_photo} if a.oi_composite else {}),
+                                **({"composite_denoise": True} if a.oi_composite_denoise else {}),
+                                **({"see_through": True} if a.oi_see_through else {}),
+                                **({"shadows": a.oi_shadows} if a.oi_shadows != "additive" else {}),
+                                **({"frames": a.oi_frames} if a.oi_frames != 1 else {}))
+        if a.oi_frames > 1:
+            print(f"Animation saved to {res['mp4']}\nIndividual frames saved to {res['animation_dir']}")
+        else:
+            print("Wrote file to", res)
     else:
         raise ValueError("Invalid mode")
 
