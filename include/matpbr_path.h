@@ -69,6 +69,12 @@ enum {
  * matpbr_path_render_objects_textures and matpbr_path_feature_tints take it; to every other entry point it is an unknown kind. */
 #define MATPBR_PATH_OBJECT_TEXTURED 0x400
 
+/* OR-ed into MatpbrPathObject.kind beside MATPBR_PATH_OBJECT_SMOOTH: the volume behind the object's interface holds a homogeneous
+ * medium, a MatpbrPathObjectMedium record beside the table ("Media inside glass").  Valid on kinds 1 and 5 only.
+ * Only matpbr_path_render_objects_media and matpbr_path_render_objects_diff_media take it; to every other entry point it is an unknown
+ * kind. */
+#define MATPBR_PATH_OBJECT_MEDIUM 0x800
+
 /* One inserted mesh: triangles [first_tri, first_tri + n_tri) of the mesh handed to matpbr_path_bvh_build_objects (ids at or
  * above its n_scene_tri), outward winding. */
 typedef struct MatpbrPathObject {
@@ -96,6 +102,16 @@ typedef struct MatpbrPathObjectTex {
     int32_t orm_first, orm_w, orm_h;    /* glTF's occlusion (ignored), roughness, metallic */
     int32_t reserved[2];
 } MatpbrPathObjectTex;
+
+/* The medium inside an object that carries MATPBR_PATH_OBJECT_MEDIUM, one record per object beside the table (read for flagged objects
+ * only): absorption per channel and grey scattering, both per scene unit, and the Henyey-Greenstein asymmetry.  Valid: sigma_a[c] and
+ * sigma_s finite and >= 0 (all zero is valid: the medium multiplies by exactly 1), |g| <= 0.99, reserved == 0. */
+typedef struct MatpbrPathObjectMedium {
+    float sigma_a[3];
+    float sigma_s;
+    float g;
+    float reserved[3];
+} MatpbrPathObjectMedium;
 
 /* Transparency editing ("Transparency editing"): the reference's TransBSDF where the mask is set. */
 typedef struct MatpbrPathTransEdit {
@@ -699,6 +715,59 @@ int matpbr_path_objects_move_host(void* nodes, void* tris, const void* rest_tris
                                   long n_object_nodes, const int32_t* node_level, int object_depth, const MatpbrPathObject* objects, int n_objects,
                                   const MatpbrPathXform* xform, float pad, const float* rest_nrm, float* obj_nrm, const void* rest_light_tris,
                                   void* light_tris, long n_light_tri, const MatpbrPathLights* lights);
+
+/* ---- Media inside glass ("Media inside glass"): a homogeneous absorbing and scattering medium behind the
+ * interface of an object of kind 1 or 5 whose kind carries MATPBR_PATH_OBJECT_MEDIUM; forward only; added at version 3.
+ * The path carries one integer med, an object index or -1 (-1 at the camera).  After the BSDF sample at a vertex on a flagged object k,
+ * med = k where ng . wi < 0 (ng the outward face normal: the ray leaves into the object), else -1; a vertex on anything else leaves med
+ * as it is; a traversal that skips the inserted triangles reads med as -1; a ray that escapes with med >= 0 (an open mesh) takes the
+ * envmap unattenuated.  A segment with med >= 0 whose trace hit at t: where sigma_s > 0, s = -logf(1 - u9) / sigma_s (u9: dim 9 of the
+ * depth; dims 9-11 are the medium's) and, where s < t, the depth is a medium vertex at o + s d: thr[c] *= expf(-sigma_a[c] s), the
+ * max_depth test as at a surface, no emitter sample, the new direction from Henyey-Greenstein about d by dims 10, 11 with weight 1
+ * (|g| < 1e-3: cos = 1 - 2 u, else cos = (1 + g^2 - ((1 - g^2) / (1 - g + 2 g u))^2) / (2 g); phi = 2 pi u; the diffuse sampler's frame),
+ * no spawn offset, med unchanged, and whatever the ray meets next takes MIS weight 1.  Otherwise thr[c] *= expf(-sigma_a[c] t) and the
+ * surface vertex runs as without a medium. */
+
+/* matpbr_path_render_objects_textures where an object of kind 1 or 5 may carry MATPBR_PATH_OBJECT_MEDIUM (with or without the smooth
+ * flag).  media (HOST, one record per object, copied before the call returns).  This is level 8 of the table in DESIGN.md section 1.4,
+ * "The object entries": without a flagged object it launches matpbr_path_render_objects_textures' kernel choice and gives its bits
+ * (media may be NULL then), and so it does where no flagged object's record has a coefficient above 0 (such a medium multiplies by
+ * exactly 1: the table is walked without the flag).  Invalid arguments, besides that entry point's: the flag on kind 2, 3 or 4, a flagged object with media ==
+ * NULL or with a record that is not valid (MatpbrPathObjectMedium). */
+int matpbr_path_render_objects_media(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                     float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                     int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                     const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                     const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                     const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                     const void* texels, long n_texels, const MatpbrPathObjectMedium* media);
+
+/* The differential family with media: matpbr_path_render_objects_ratio's arguments, then media as above.  photo and through are both
+ * NULL or both non-NULL, and base may be NULL as well: the four shapes are matpbr_path_render_objects_diff (neither), _through (photo),
+ * _ratio without and with photo (base).  Without a flagged object, or where no flagged object's record has a coefficient above 0, it
+ * launches the existing kernel of the same shape and gives its bits.  With one: trip 0's records (c_s, touched, the chain, the landing) are taken after the scatter decision and only where the
+ * segment reached its hit; a medium vertex ends the see-through chain; the segment's attenuation is in thr_k before thr_k photo[texel]
+ * is added to `through`; a segment that reaches a triangle of id < n_scene_tri with med >= 0 (a mesh that pokes through the scene)
+ * touches the sample.  A pixel that no sample touches keeps the photograph's bits.  Invalid arguments, besides
+ * matpbr_path_render_objects_ratio's (base aside) and matpbr_path_render_objects_media's: exactly one of photo and through NULL. */
+int matpbr_path_render_objects_diff_media(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                          float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                          int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                          const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                          const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                          const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                          const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                          const float* photo, float* through, float* base, const MatpbrPathObjectMedium* media);
+
+/* One segment inside a medium on the CPU, with the routine the kernel runs: the record `medium` (checked), per lane the traced
+ * distance t[N] and u9[N] -> scattered[N] (1: the segment ends at a medium vertex), dist[N] (s there, else t), weight[N,3] =
+ * expf(-sigma_a dist).  u9 is read only where sigma_s > 0. */
+int matpbr_path_medium_segment_host(const MatpbrPathObjectMedium* medium, const float* t, const float* u9, long N, int32_t* scattered,
+                                    float* dist, float* weight);
+
+/* The phase sampler on the CPU, with the routine the kernel runs: g (|g| <= 0.99), propagation directions d[N,3] (unit length),
+ * u[N,2] = dims 10, 11 -> wi[N,3]. */
+int matpbr_path_phase_sample_host(float g, const float* d, const float* u, long N, float* wi);
 
 #ifdef __cplusplus
 }

@@ -11,11 +11,12 @@
 // traversals and the host builder; path_shading.hpp the RNG, the envmap sampler and the BSDF wrappers; path_objects.hpp the tables the
 // kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
 // path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser; path_diff.hpp the differential render's table
-// and the composite; path_move.hpp the grafted BVH's move and refit of the inserted objects.
+// and the composite; path_media.hpp the media inside glass objects; path_move.hpp the grafted BVH's move and refit of the inserted objects.
 #include <type_traits>
 
 #include "path_denoise.hpp"
 #include "path_diff.hpp"
+#include "path_media.hpp"
 #include "path_move.hpp"
 
 namespace {
@@ -40,6 +41,9 @@ __host__ __device__ __forceinline__ float spawn_eps(const float p[3]) { return 1
 template <class Objects> __device__ __forceinline__ int id_limit_of(const Objects&, bool) { return 0; }
 __device__ __forceinline__ int id_limit_of(const DiffObjects& ot, bool second) { return second ? ot.n_scene_tri : INT32_MAX; }
 __device__ __forceinline__ int id_limit_of(const RatioObjects& ot, bool second) { return id_limit_of(static_cast<const DiffObjects&>(ot), second); }
+template <class Diff> __device__ __forceinline__ int id_limit_of(const MediumDiff<Diff>& ot, bool second) {
+    return id_limit_of(static_cast<const DiffObjects&>(ot), second);
+}
 // (ThroughObjects) the second trip of a see-through sample replays its chain over every triangle and skips the inserted ones from its
 // landing depth `land` on; land = -1 (not see-through) skips them from the camera ray on, DiffObjects' rule
 __device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second, int depth, int land) {
@@ -75,13 +79,17 @@ __device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second
 // `if (THROUGH ...)` folds away in the other eleven.  BASE: DIFF or THROUGH with one more sum (Objects = RatioObjects,
 // RatioThroughObjects; DESIGN.md section 1.4, "Ratio shadow transfer"): a sample with cov false adds the radiance of its last trip, the
 // walk without the objects, to `base`.  DIFF, THROUGH and BASE are read off the table's type (DiffTraits), so the twelve kernels
-// without `base` are the code they were; every `if (BASE ...)` folds away in them.
+// without `base` are the code they were; every `if (BASE ...)` folds away in them.  MEDIUM: TEX or a table of the DIFF family with media
+// inside glass objects (Objects = MediumObjects, MediumDiff<...>; DESIGN.md section 1.4, "Media inside glass"): the path carries `med`,
+// the object whose medium the ray is in, and a segment with med >= 0 is attenuated and may end at a medium vertex.  Read off the
+// table's type (MediumTraits); every `if (MEDIUM ...)` folds away in the sixteen kernels without media.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
     constexpr bool THROUGH = DiffTraits<Objects>::through;
     constexpr bool DIFF = DiffTraits<Objects>::diff;
     constexpr bool BASE = DiffTraits<Objects>::base;
-    constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF;
+    constexpr bool MEDIUM = MediumTraits<Objects>::medium;
+    constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF || MEDIUM;
     constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
     constexpr bool LIGHT = std::is_same<Objects, LightObjects>::value || ROUGH;
@@ -152,6 +160,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
         }
         float prev_pdf = 0.0f;
         bool prev_delta = false;   // (OBJ) the ray left a delta vertex: no emitter sample competed with it
+        int med = -1;              // (MEDIUM) the object whose medium the ray is in; -1: none, as at the camera
         for (int depth = 0;; ++depth) {
             float t = FLT_MAX;
             ++n_rays;
@@ -159,6 +168,34 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             int id_limit = id_limit_of(ot, second);
             if constexpr (THROUGH) id_limit = id_limit_at(ot, second, depth, land);   // (THROUGH) a function of the depth
             const int k = trace<false, DIFF>(q.nodes, q.tris, o, d, 0.0f, t, stk, id_limit);
+            int med_seg = -1;   // (MEDIUM) the medium of this segment: a traversal that skips the inserted triangles is in none
+            if constexpr (MEDIUM) {
+                med_seg = DIFF && id_limit != INT32_MAX ? -1 : med;
+                // a ray that escapes inside a medium (an open mesh) drops it without attenuation; else the trace gave t: the flight is
+                // sampled from sigma_s alone and the absorption over the distance flown is an analytic weight
+                if (med_seg >= 0 && k >= 0) {
+                    const MatpbrPathObjectMedium mr = medium_of(ot, med_seg);
+                    float dist, tw[3];
+                    const bool scattered = medium_segment(mr, t, mr.sigma_s > 0.0f ? rng_u(base, depth, 9) : 0.0f, dist, tw);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) thr[c] *= tw[c];
+                    if (scattered) {   // a medium vertex at o + s d: no emitter sample (the boundary is a dielectric), no spawn offset
+                        if constexpr (THROUGH) {
+                            if (!second) chain = false;
+                        }
+                        if (depth + 1 >= q.max_depth) break;
+                        float wi[3];
+                        phase_sample(mr.g, d, rng_u(base, depth, 10), rng_u(base, depth, 11), wi);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            o[c] = fmaf(dist, d[c], o[c]);
+                            d[c] = wi[c];
+                        }
+                        prev_delta = true;   // whatever the ray meets next takes MIS weight 1
+                        continue;
+                    }
+                }
+            }
             if constexpr (DIFF) {
                 if (k >= 0 && tri_id(q.tris[3 * k]) >= ot.n_scene_tri) {   // trip 0 alone can meet one ((THROUGH) and trip 1's chain)
                     touched = true;
@@ -185,6 +222,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                         touched = ot.lt.n > 0;
                     }
                 }
+            }
+            if constexpr (DIFF && MEDIUM) {   // a mesh that pokes through the scene: the segment reached the scene inside a medium
+                if (med_seg >= 0 && k >= 0 && tri_id(q.tris[3 * k]) < ot.n_scene_tri) touched = true;
             }
             if (k < 0) {   // escaped: the envmap, MIS-weighted against emitter sampling after a BSDF sample
                 const int tx = env_texel(d, q.He, q.We);
@@ -250,6 +290,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             if constexpr (TEX) {
                 textured = (kind & MATPBR_PATH_OBJECT_TEXTURED) != 0;
                 kind &= ~MATPBR_PATH_OBJECT_TEXTURED;
+            }
+            int med_obj = -1;   // (MEDIUM) the vertex lies on this object, whose kind carries the medium flag
+            if constexpr (MEDIUM) {
+                if (kind & MATPBR_PATH_OBJECT_MEDIUM) med_obj = medium_index(ot.t, __float_as_int(q.tris[3 * k].w));
+                kind &= ~MATPBR_PATH_OBJECT_MEDIUM;
             }
             if constexpr (THROUGH) {
                 if (!second) chain = chain && kind == MATPBR_PATH_BSDF_DIELECTRIC;   // rough glass and every other kind end the chain
@@ -424,6 +469,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 else
                     object_sample(kind, op, n, wo, rng_u(base, depth, 6), rng_u(base, depth, 7), rng_u(base, depth, 8), wi, wgt, pdf_s, flags);
                 prev_delta = (flags & kFlagDelta) != 0;
+                if constexpr (MEDIUM) {   // the side the ray leaves on decides: into the object, its medium; out of it, none
+                    if (med_obj >= 0) med = dot3(n, wi) < 0.0f ? med_obj : -1;
+                }
                 const float side = dot3(n, wi) > 0.0f ? eps : -eps;   // spawn on the side the new ray leaves on
 #pragma unroll
                 for (int c = 0; c < 3; ++c) po[c] = fmaf(side, n[c], p[c]);
@@ -888,7 +936,7 @@ bool frame_args(const Frame& f, PathArgs& q) {
 }
 
 // the path_kernel instantiation a render launches; it also says which members of `Scene` the launch reads
-enum class Kernel { NoObjects, ObjTable, SmoothObjects, PbrObjects, LightObjects, RoughObjects, ColorObjects, TexObjects, TransEdit, ShadeNormals };
+enum class Kernel { NoObjects, ObjTable, SmoothObjects, PbrObjects, LightObjects, RoughObjects, ColorObjects, TexObjects, MediumObjects, TransEdit, ShadeNormals };
 // what a render hands its kernel besides the frame, checked
 struct Scene {
     Kernel kernel = Kernel::NoObjects;
@@ -901,6 +949,7 @@ struct Scene {
     const float* obj_uv = nullptr;              // set where some object is textured, with its records and the texels
     const MatpbrPathObjectTex* tex = nullptr;
     const float4* texels = nullptr;
+    const MatpbrPathObjectMedium* media = nullptr;   // set where some object holds a medium
     TransEdit edit{};
     const float* nrm = nullptr;
 };
@@ -933,6 +982,12 @@ TexObjects tex_objects(const Scene& s) {
         if (s.ot.o[k].kind & MATPBR_PATH_OBJECT_TEXTURED) ro.tex[k] = s.tex[k];
     return ro;
 }
+// the medium records of `s` into a table that carries them: a record is copied where its object carries the flag, the others stay zero
+template <class Table>
+void media_into(const Scene& s, Table& t) {
+    for (int k = 0; s.media && k < s.ot.n; ++k)
+        if (s.ot.o[k].kind & MATPBR_PATH_OBJECT_MEDIUM) t.med[k] = s.media[k];
+}
 
 int render_common(const Frame& f, const Scene& s) {
     PathArgs q{};
@@ -948,6 +1003,12 @@ int render_common(const Frame& f, const Scene& s) {
     const TexObjects ro = tex_objects(s);   // the five kernels whose tables extend one another
     if (s.kernel == Kernel::PbrObjects) return launch_frame<PbrObjects>(f, q, ro);
     if (s.kernel == Kernel::TexObjects) return launch_frame(f, q, ro);
+    if (s.kernel == Kernel::MediumObjects) {
+        MediumObjects mo{};
+        static_cast<TexObjects&>(mo) = ro;
+        media_into(s, mo);
+        return launch_frame(f, q, mo);
+    }
     return s.kernel == Kernel::LightObjects ? launch_frame<LightObjects>(f, q, ro) :
            s.kernel == Kernel::RoughObjects ? launch_frame<RoughObjects>(f, q, ro) : launch_frame<ColorObjects>(f, q, ro);
 }
@@ -975,24 +1036,34 @@ bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept
     return true;
 }
 
-// The seven object entries are the seven levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
+// The eight object entries are the eight levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
 // admits kinds 1 and 2, level 2 the smooth flag on them, level 3 kind 3, level 4 kind 4, level 5 kind 5, level 6 the colour flag on
 // kinds 2 and 3 (obj_col is consulted where an object carries it), level 7 the texture flag on them (obj_uv, tex and texels are consulted
-// where an object carries it, and its record is checked against n_texels).  An entry passes null / 0 for
+// where an object carries it, and its record is checked against n_texels), level 8 the medium flag on kinds 1 and 5 (media is consulted
+// where an object carries it, and its record is checked; its kernel is chosen first).  An entry passes null / 0 for
 // the arguments it does not have; level 1's n_scene_tri = 0 lies below every range.  An argument is consulted only where the table needs
 // it: obj_nrm where an object is smooth, pbr where one is of kind 3, the light header and buffers where one is of kind 4.  The counts
 // alone choose the kernel.
 bool objects_scene(int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                    const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
-                   const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex, const void* texels, long n_texels, Scene& s) {
+                   const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex, const void* texels, long n_texels, Scene& s,
+                   const MatpbrPathObjectMedium* media = nullptr) {
     const unsigned accept = (level >= 2 ? kAcceptSmooth : 0u) | (level >= 3 ? kAcceptPbr : 0u) | (level >= 4 ? kAcceptLight : 0u) |
-                            (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u) | (level >= 7 ? kAcceptTexture : 0u);
+                            (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u) | (level >= 7 ? kAcceptTexture : 0u) |
+                            (level >= 8 ? kAcceptMedium : 0u);
     ObjCounts n;
     if (!scene_table(objects, n_objects, accept, obj_nrm, n_scene_tri, pbr, s.ot, n) || (n.pbr > 0 && !pbr) || (n.color > 0 && !obj_col) ||
         (n.light > 0 && !light_table(lights, &s.ot, light_tris, light_cdf, s.lt)) ||
-        (n.tex > 0 && !textures_valid(objects, n_objects, obj_uv, tex, texels, n_texels)))
+        (n.tex > 0 && !textures_valid(objects, n_objects, obj_uv, tex, texels, n_texels)) ||
+        (n.medium > 0 && !media_valid(objects, n_objects, media)))
         return false;
-    s.kernel = n.tex > 0 ? Kernel::TexObjects : n.color > 0 ? Kernel::ColorObjects : n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
+    // records without a coefficient anywhere are no medium: the table goes on without the flag, to the kernel it had without it
+    if (n.medium > 0 && !media_any(objects, n_objects, media)) {
+        for (int k = 0; k < n_objects; ++k) s.ot.o[k].kind &= ~MATPBR_PATH_OBJECT_MEDIUM;
+        n.medium = 0;
+    }
+    s.media = n.medium > 0 ? media : nullptr;
+    s.kernel = n.medium > 0 ? Kernel::MediumObjects : n.tex > 0 ? Kernel::TexObjects : n.color > 0 ? Kernel::ColorObjects : n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
                n.smooth > 0 ? Kernel::SmoothObjects : n_objects > 0 ? Kernel::ObjTable : Kernel::NoObjects;
     s.obj_nrm = n.smooth > 0 ? obj_nrm : nullptr;
     s.n_scene_tri = (int32_t)n_scene_tri;
@@ -1008,9 +1079,9 @@ bool objects_scene(int level, const MatpbrPathObject* objects, int n_objects, co
 int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                    const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
                    const float* obj_col = nullptr, const float* obj_uv = nullptr, const MatpbrPathObjectTex* tex = nullptr,
-                   const void* texels = nullptr, long n_texels = 0) {
+                   const void* texels = nullptr, long n_texels = 0, const MatpbrPathObjectMedium* media = nullptr) {
     Scene s;
-    if (!objects_scene(level, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
+    if (!objects_scene(level, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s, media))
         return MATPBR_PATH_ERR_INVALID_ARG;
     return render_common(f, s);
 }
@@ -1595,6 +1666,62 @@ int matpbr_path_render_objects_ratio(const void* nodes, const void* tris, const 
     rt.photo = photo; rt.through = through;
     rt.base = base;
     return launch_frame(f, q, rt);
+}
+
+int matpbr_path_render_objects_media(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                     float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                     int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
+                                     const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                     const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                     const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                     const void* texels, long n_texels, const MatpbrPathObjectMedium* media) {
+    return render_objects(RENDER_FRAME, 8, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels,
+                          n_texels, media);
+}
+
+int matpbr_path_render_objects_diff_media(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                          float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                          int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                          const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                          const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                          const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                          const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                          const float* photo, float* through, float* base, const MatpbrPathObjectMedium* media) {
+    float* const out = nullptr;   // the sums go to the table's buffers
+    const Frame f = RENDER_FRAME;
+    PathArgs q{};
+    Scene s;
+    if (!fg || !delta || !alpha || (photo == nullptr) != (through == nullptr) || n_objects <= 0 || !frame_args(f, q) ||
+        !objects_scene(8, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s, media))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    // the shape's table filled, and launched as it is or, where an object holds a medium, with the records behind it
+    auto launch = [&](auto table) {
+        using Table = decltype(table);
+        static_cast<TexObjects&>(table) = tex_objects(s);
+        table.fg = fg; table.delta = delta; table.alpha = alpha; table.rewalked = rewalked;
+        if constexpr (DiffTraits<Table>::through) { table.photo = photo; table.through = through; }
+        if constexpr (DiffTraits<Table>::base) table.base = base;
+        if (!s.media) return launch_frame(f, q, table);
+        MediumDiff<Table> mt{};
+        static_cast<Table&>(mt) = table;
+        media_into(s, mt);
+        return launch_frame(f, q, mt);
+    };
+    if (base) return photo ? launch(RatioThroughObjects{}) : launch(RatioObjects{});
+    return photo ? launch(ThroughObjects{}) : launch(DiffObjects{});
+}
+
+int matpbr_path_medium_segment_host(const MatpbrPathObjectMedium* medium, const float* t, const float* u9, long N, int32_t* scattered,
+                                    float* dist, float* weight) {
+    if (!medium || !t || !u9 || !scattered || !dist || !weight || N < 0 || !medium_valid(*medium)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) scattered[k] = medium_segment(*medium, t[k], u9[k], dist[k], weight + 3 * k) ? 1 : 0;
+    return MATPBR_PATH_OK;
+}
+
+int matpbr_path_phase_sample_host(float g, const float* d, const float* u, long N, float* wi) {
+    if (!d || !u || !wi || N < 0 || !(fabsf(g) <= 0.99f)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long k = 0; k < N; ++k) phase_sample(g, d + 3 * k, u[2 * k], u[2 * k + 1], wi + 3 * k);
+    return MATPBR_PATH_OK;
 }
 
 int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,

@@ -463,12 +463,14 @@ bool rough_valid(const float p[3]) {
 // MATPBR_PATH_OBJECT_SMOOTH; kAcceptPbr kind MATPBR_PATH_BSDF_PBR (its p[] is ignored; its record is checked where `pbr` is given);
 // kAcceptLight kind MATPBR_PATH_BSDF_AREA (never with the smooth flag; p = radiance, finite and >= 0); kAcceptRough kind
 // MATPBR_PATH_BSDF_ROUGH_DIELECTRIC (rough_valid); kAcceptColor a kind 2 or 3 that carries MATPBR_PATH_OBJECT_COLORED (on another kind
-// the flag is refused); kAcceptTexture the same for MATPBR_PATH_OBJECT_TEXTURED (its record is path_textures.hpp's to check).  A kind
-// outside the mask is an unknown kind.  kAcceptAll is what the entries before the colour flag admit.
-enum : unsigned { kAcceptSmooth = 1u, kAcceptPbr = 2u, kAcceptLight = 4u, kAcceptRough = 8u, kAcceptAll = 15u, kAcceptColor = 16u, kAcceptTexture = 32u };
-// how many objects of a checked table are smooth, of kind 3, of kind 4, of kind 5, coloured, textured
+// the flag is refused); kAcceptTexture the same for MATPBR_PATH_OBJECT_TEXTURED (its record is path_textures.hpp's to check); kAcceptMedium
+// a kind 1 or 5 that carries MATPBR_PATH_OBJECT_MEDIUM (on another kind the flag is refused; its record is path_media.hpp's to check).
+// A kind outside the mask is an unknown kind.  kAcceptAll is what the entries before the colour flag admit.
+enum : unsigned { kAcceptSmooth = 1u, kAcceptPbr = 2u, kAcceptLight = 4u, kAcceptRough = 8u, kAcceptAll = 15u, kAcceptColor = 16u, kAcceptTexture = 32u,
+                  kAcceptMedium = 64u };
+// how many objects of a checked table are smooth, of kind 3, of kind 4, of kind 5, coloured, textured, filled with a medium
 struct ObjCounts {
-    int smooth = 0, pbr = 0, light = 0, rough = 0, color = 0, tex = 0;
+    int smooth = 0, pbr = 0, light = 0, rough = 0, color = 0, tex = 0, medium = 0;
 };
 bool object_table(const MatpbrPathObject* objects, int n_objects, unsigned accept, const MatpbrPathObjectPbr* pbr, ObjTable& ot,
                   ObjCounts* counts = nullptr) {
@@ -490,6 +492,12 @@ bool object_table(const MatpbrPathObject* objects, int n_objects, unsigned accep
             if (base != MATPBR_PATH_BSDF_DIFFUSE && base != MATPBR_PATH_BSDF_PBR) return false;
             plain.kind &= ~MATPBR_PATH_OBJECT_COLORED;
             ++c.color;
+        }
+        if ((accept & kAcceptMedium) && (plain.kind & MATPBR_PATH_OBJECT_MEDIUM)) {
+            const int base = plain.kind & ~(MATPBR_PATH_OBJECT_MEDIUM | MATPBR_PATH_OBJECT_SMOOTH);
+            if (base != MATPBR_PATH_BSDF_DIELECTRIC && base != MATPBR_PATH_BSDF_ROUGH_DIELECTRIC) return false;
+            plain.kind &= ~MATPBR_PATH_OBJECT_MEDIUM;
+            ++c.medium;
         }
         if ((accept & kAcceptLight) && plain.kind == MATPBR_PATH_BSDF_AREA) {
             for (int j = 0; j < 3; ++j)

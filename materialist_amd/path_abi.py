@@ -30,6 +30,8 @@ OBJECT_SMOOTH = 0x100          # MATPBR_PATH_OBJECT_SMOOTH, OR-ed into PathObjec
 OBJECT_COLORED = 0x200         # MATPBR_PATH_OBJECT_COLORED, OR-ed into the kind of a diffuse or pbr object ("Vertex-coloured inserted objects")
 OBJECT_TEXTURED = 0x400        # MATPBR_PATH_OBJECT_TEXTURED, OR-ed into the kind of a diffuse or pbr object ("Textured inserted objects")
 OBJECT_FLAGS = OBJECT_SMOOTH | OBJECT_COLORED | OBJECT_TEXTURED
+OBJECT_MEDIUM = 0x800          # MATPBR_PATH_OBJECT_MEDIUM, OR-ed into the kind of a dielectric or roughdielectric object ("Media inside glass")
+MEDIUM_MAX_G = 0.99            # |g| of the Henyey-Greenstein phase function at most this
 TEXTURE_MAX_SIDE = 8192        # w, h of an image
 TEXTURE_MAX_UV = 64.0          # |s|, |t| of a corner: a coordinate's fractional part keeps 17 bits or more
 
@@ -49,6 +51,12 @@ class PathObjectTex(ctypes.Structure):
     (w = 0: no such image)."""
     _fields_ = [("base_first", ctypes.c_int32), ("base_w", ctypes.c_int32), ("base_h", ctypes.c_int32), ("orm_first", ctypes.c_int32),
                 ("orm_w", ctypes.c_int32), ("orm_h", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class PathObjectMedium(ctypes.Structure):
+    """MatpbrPathObjectMedium (include/matpbr_path.h): absorption per channel, grey scattering (both per scene unit) and the
+    Henyey-Greenstein asymmetry of the medium inside one glass object."""
+    _fields_ = [("sigma_a", ctypes.c_float * 3), ("sigma_s", ctypes.c_float), ("g", ctypes.c_float), ("reserved", ctypes.c_float * 3)]
 
 
 class PathLights(ctypes.Structure):
@@ -115,6 +123,10 @@ SIGNATURES = {
     "matpbr_path_render_objects_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 4),
     "matpbr_path_render_objects_through": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 6),
     "matpbr_path_render_objects_ratio": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 7),
+    "matpbr_path_render_objects_media": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long, _P]),
+    "matpbr_path_render_objects_diff_media": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 8),
+    "matpbr_path_medium_segment_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_long, _P, _P, _P]),
+    "matpbr_path_phase_sample_host": (ctypes.c_int, [ctypes.c_float, _P, _P, ctypes.c_long, _P]),
     "matpbr_path_composite_ratio": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
     "matpbr_path_composite_ratio_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
     "matpbr_path_through_chain_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P,
@@ -189,10 +201,16 @@ RATIO_FEATURE = "ratio shadow transfer"
 # moving inserted objects' symbols ("Moving inserted objects"), added at version 3 as well: a third group beside them
 MOVE_SYMBOLS = ("matpbr_path_bvh_build_grafted", "matpbr_path_xform_check_host", "matpbr_path_objects_move", "matpbr_path_objects_move_host")
 MOVE_FEATURE = "moving inserted objects"
+# media inside glass objects' symbols ("Media inside glass"), added at version 3 as well: a fourth group beside them
+MEDIUM_SYMBOLS = ("matpbr_path_render_objects_media", "matpbr_path_render_objects_diff_media", "matpbr_path_medium_segment_host",
+                  "matpbr_path_phase_sample_host")
+MEDIUM_FEATURE = "media inside glass objects"
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
                   "matpbr_path_render_objects_textures": 13, "matpbr_path_render_objects_through": 13}
+# level 8 takes the thirteen of level 7 and then the medium records (`PathTracer.media_arg`), which `object_args()` does not hold
+MEDIA_ENTRY = "matpbr_path_render_objects_media"
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -209,7 +227,7 @@ def load() -> ctypes.CDLL:
         _build.build_path_library()
         lib = ctypes.CDLL(_build.PATH_LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS) and not hasattr(lib, name):
+            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS or name in MEDIUM_SYMBOLS) and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -223,7 +241,8 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        what = RATIO_FEATURE if name in RATIO_SYMBOLS else MOVE_FEATURE if name in MOVE_SYMBOLS else _FEATURE.get(name, "smooth inserted objects")
+        what = (RATIO_FEATURE if name in RATIO_SYMBOLS else MOVE_FEATURE if name in MOVE_SYMBOLS else MEDIUM_FEATURE if name in MEDIUM_SYMBOLS
+                else _FEATURE.get(name, "smooth inserted objects"))
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 
@@ -272,7 +291,9 @@ def _table_ptrs(table, records=None) -> tuple:
 def _uncolored(table, flags: int = OBJECT_COLORED | OBJECT_TEXTURED):
     """`table` as the entry points from before the colour flag take it (the features, the light tables: they need the kind and the smooth
     flag only): the same table where no object carries OBJECT_COLORED or OBJECT_TEXTURED, else copies without them.  `flags`: the
-    flags to hide (the colour guide takes the colour flag and not the texture flag)."""
+    flags to hide (the colour guide takes the colour flag and not the texture flag).  OBJECT_MEDIUM is always hidden: a medium changes
+    no geometry and no first-hit guide, and only the two entries that render it take its flag."""
+    flags |= OBJECT_MEDIUM
     if table is None or not any(t.kind & flags for t in table):
         return table
     return [PathObject(t.kind & ~flags, t.first_tri, t.n_tri, t.p) for t in table]

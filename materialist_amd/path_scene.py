@@ -8,10 +8,10 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .path_abi import (BSDF_AREA, BSDF_DIELECTRIC, BSDF_DIFFUSE, BSDF_PBR, BSDF_ROUGH_DIELECTRIC, MAX_OBJECTS, NODE_BYTES, OBJECT_COLORED,
-                       OBJECT_SMOOTH, OBJECT_TEXTURED, PBR_DEFAULTS, PBR_MIN_ROUGHNESS, ROUGH_MIN_ALPHA, ROUGH_MIN_CONTRAST, TEXTURE_MAX_SIDE,
-                       TEXTURE_MAX_UV, TRI_BYTES, PathLights, PathObject, PathObjectPbr, PathObjectTex, PathXform, _ptr, _ref, _table_ptrs, _uncolored,
-                       check, load, symbol)
+from .path_abi import (BSDF_AREA, BSDF_DIELECTRIC, BSDF_DIFFUSE, BSDF_PBR, BSDF_ROUGH_DIELECTRIC, MAX_OBJECTS, MEDIUM_MAX_G, NODE_BYTES, OBJECT_COLORED,
+                       OBJECT_MEDIUM, OBJECT_SMOOTH, OBJECT_TEXTURED, PBR_DEFAULTS, PBR_MIN_ROUGHNESS, ROUGH_MIN_ALPHA, ROUGH_MIN_CONTRAST, TEXTURE_MAX_SIDE,
+                       TEXTURE_MAX_UV, TRI_BYTES, PathLights, PathObject, PathObjectMedium, PathObjectPbr, PathObjectTex, PathXform, _ptr, _ref, _table_ptrs,
+                       _uncolored, check, load, symbol)
 
 
 def build_bvh(vertices: np.ndarray, triangles: np.ndarray, n_scene_tri: Optional[int] = None) -> Dict[str, object]:
@@ -176,14 +176,65 @@ def env_tables(env: np.ndarray) -> Dict[str, object]:
     return {"row_cdf": row, "col_cdf": col, "pdf": pdf, "total": total.value}
 
 
+MEDIUM_KEYS = ("sigma_a", "scatter", "g", "color", "at")
+
+
+def object_medium(bsdf: dict) -> Optional[tuple]:
+    """The "medium" of a glass object's bsdf dict ("Media inside glass") -> (sigma_a0, sigma_a1, sigma_a2, sigma_s,
+    g) in float64, None without the key.  Either {"sigma_a": scalar or 3 values (0), "scatter": sigma_s (0), "g": g (0)}, every coefficient
+    per scene unit, finite and >= 0, |g| <= 0.99; or {"color": scalar or 3 values in (0, 1], "at": d > 0, "scatter", "g"}: the colour white
+    light has after the distance d inside the object, sigma_a = -ln(color) / d.  ValueError for another bsdf type than 'dielectric' and
+    'roughdielectric', for both forms at once, for an unknown sub-key or a value out of range."""
+    med = bsdf.get("medium") if isinstance(bsdf, dict) else None
+    if med is None:
+        return None
+    if bsdf.get("type") not in ("dielectric", "roughdielectric"):
+        raise ValueError(f"medium: a medium fills a 'dielectric' or a 'roughdielectric' object; a {bsdf.get('type')!r} object takes none (drop 'medium')")
+    if not isinstance(med, dict):
+        raise ValueError(f"medium must be a dict with keys of {MEDIUM_KEYS}, got {type(med).__name__}")
+    extra = sorted(set(med) - set(MEDIUM_KEYS))
+    if extra:
+        raise ValueError(f"medium: unknown key {extra[0]!r} (known: {', '.join(repr(k) for k in MEDIUM_KEYS)})")
+    friendly, plain = "color" in med or "at" in med, "sigma_a" in med
+    if friendly and plain:
+        raise ValueError("medium: give either 'sigma_a' or 'color' with 'at', not both")
+    try:
+        if friendly:
+            if "color" not in med or "at" not in med:
+                raise ValueError("medium: 'color' and 'at' go together: the colour of white light after the distance 'at' inside the object")
+            col, at = np.asarray(med["color"], dtype=np.float64), float(med["at"])
+            if col.shape not in ((), (1,), (3,)) or not ((col > 0) & (col <= 1)).all():
+                raise ValueError(f"medium: color must be a scalar or 3 values in (0, 1], got {med['color']!r}")
+            if not (np.isfinite(at) and at > 0):
+                raise ValueError(f"medium: 'at' must be finite and > 0, got {med['at']!r}")
+            sa = -np.log(np.broadcast_to(col, (3,))) / at + 0.0          # + 0.0: a white channel gives +0, not -0
+        else:
+            sa = np.asarray(med.get("sigma_a", 0.0), dtype=np.float64)
+            if sa.shape not in ((), (1,), (3,)):
+                raise ValueError(f"medium: sigma_a must be a scalar or 3 values, got shape {sa.shape}")
+            sa = np.broadcast_to(sa, (3,))
+        ss, g = float(med.get("scatter", 0.0)), float(med.get("g", 0.0))
+    except TypeError:
+        raise ValueError(f"medium: every value must be a number or 3 numbers, got {med!r}") from None
+    with np.errstate(over="ignore"):
+        ok = np.isfinite(np.asarray([*sa, ss], np.float32)).all()    # the bounds as the library sees them: the record is fp32
+    if not (ok and (sa >= 0).all() and ss >= 0):
+        raise ValueError(f"medium: sigma_a and scatter must be finite and >= 0, got {sa.tolist()} and {ss}")
+    if not abs(np.float32(g)) <= np.float32(MEDIUM_MAX_G):
+        raise ValueError(f"medium: g must lie in [-{MEDIUM_MAX_G}, {MEDIUM_MAX_G}], got {g}")
+    return (*(float(x) for x in sa), ss, g)
+
+
 def object_bsdf(bsdf: dict) -> tuple:
     """{"type": "dielectric", "int_ior", "ext_ior"} | {"type": "diffuse", "reflectance"} -> (kind, (p0, p1, p2));
     {"type": "pbr", "albedo": scalar or 3 values (0.8), "roughness" (0.5), "metallic" (0)} -> (BSDF_PBR, (a0, a1, a2, r, m));
     {"type": "area", "radiance": scalar or 3 values, finite and >= 0 (1)} -> (BSDF_AREA, (r, g, b)): an area light.
     {"type": "roughdielectric", "int_ior" (1.49), "ext_ior" (1.000277), "alpha" (0.1): the GGX width in [0.02, 1]} ->
     (BSDF_ROUGH_DIELECTRIC, (int_ior, ext_ior, alpha)): rough glass; the indices' ratio stays at least 0.01 away from 1.
-    ValueError when bad."""
+    A dielectric or roughdielectric dict may carry "medium" (`object_medium` returns its record; the kind returned here stays bare); on
+    another type it is refused.  ValueError when bad."""
     kind = bsdf.get("type") if isinstance(bsdf, dict) else None
+    object_medium(bsdf)
     if kind == "roughdielectric":
         try:
             p = (float(bsdf.get("int_ior", 1.49)), float(bsdf.get("ext_ior", 1.000277)), float(bsdf.get("alpha", 0.1)))
@@ -359,6 +410,7 @@ class MergedScene:
     obj_col: Optional[np.ndarray]       # corner colours [Nt - scene's Nt, 3, 3] float32 (zero without "colors"); None: no object is coloured
     textures: Optional[tuple]           # (obj_uv [Nt - scene's Nt, 3, 2] float32, [PathObjectTex] one per object, texels [n, 4] float32); None: no object is textured
     counts: Dict[str, int]              # the objects of each kind, under `PathTracer.stats`' keys (COUNT_KEYS)
+    media: Optional[List[PathObjectMedium]] = None   # one per object (zero unless it holds a medium); None: no object holds one
 
 
 def merge_scene(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], lights: bool = False, symbol=symbol) -> MergedScene:
@@ -373,10 +425,13 @@ def merge_scene(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[d
     tex: List[PathObjectTex] = []
     texels: List[np.ndarray] = []
     records: List[PathObjectPbr] = []
+    media: List[PathObjectMedium] = []
     counts = dict.fromkeys(COUNT_KEYS, 0)
     nv, nt = V[0].shape[0], T[0].shape[0]
     for k, ob in enumerate(objects):
         bare, p = object_bsdf(ob.get("bsdf"))
+        med = object_medium(ob.get("bsdf"))
+        media.append(PathObjectMedium((ctypes.c_float * 3)(*med[:3]), med[3], med[4]) if med is not None else PathObjectMedium())
         records.append(PathObjectPbr((ctypes.c_float * 3)(*p[:3]), p[3], p[4]) if bare == BSDF_PBR else PathObjectPbr())
         if bare == BSDF_PBR:
             p = (0.0, 0.0, 0.0)
@@ -397,7 +452,8 @@ def merge_scene(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[d
         tex.append(rec)
         texels += images
         corner["uv"].append(_corner_uv(k, ob, Vo, To) if images else np.zeros((To.shape[0], 3, 2)))
-        kind = bare | (OBJECT_SMOOTH if smooth else 0) | (OBJECT_COLORED if colored else 0) | (OBJECT_TEXTURED if images else 0)
+        kind = bare | (OBJECT_SMOOTH if smooth else 0) | (OBJECT_COLORED if colored else 0) | (OBJECT_TEXTURED if images else 0) | \
+            (OBJECT_MEDIUM if med is not None else 0)
         for key, one in zip(COUNT_KEYS, (smooth, bare == BSDF_PBR, bare == BSDF_AREA, bare == BSDF_ROUGH_DIELECTRIC, colored, bool(images))):
             counts[key] += one
         V.append(Vo)
@@ -408,7 +464,8 @@ def merge_scene(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[d
     joined = lambda key, count: np.ascontiguousarray(np.concatenate(corner[key]), dtype=np.float32) if counts[count] else None
     return MergedScene(Vm, Tm, table, joined("normals", "n_smooth_objects"), records, light_tables(Vm, Tm, table, records, symbol) if lights else None,
                        joined("colors", "n_colored_objects"),
-                       (joined("uv", "n_textured_objects"), tex, np.ascontiguousarray(np.concatenate(texels))) if texels else None, counts)
+                       (joined("uv", "n_textured_objects"), tex, np.ascontiguousarray(np.concatenate(texels))) if texels else None, counts,
+                       media if any(t.kind & OBJECT_MEDIUM for t in table) else None)
 
 
 def merge_objects(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[dict], normals: bool = False, pbr: bool = False,

@@ -12,7 +12,8 @@ and `composite` are the differential render ("Differentia
 from a photograph of the scene, forward only; `PathTracer.denoise_diff` is its own a-trous filter over two halves of it ("Denoiser
 for the differential render"); `PathTracer.render_diff_through` is the differential render with the photograph shown, refracted,
 behind inserted clear glass ("Seen through glass"); `PathTracer.render_diff_ratio` and `composite_ratio` transfer the shadows as a
-ratio of the model's radiance with and without the objects ("Ratio shadow transfer").  There is no fallback: a missing or failing library raises.
+ratio of the model's radiance with and without the objects ("Ratio shadow transfer").  A glass object may hold a homogeneous medium
+("Media inside glass"): `render` and the three differential renders then take the entries that know it.  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -60,7 +61,12 @@ class PathTracer:
     (base colour, linear, in [0, 1], row 0 the top row) and, a pbr one, "orm_texture" [h,w,3] ("Textured inserted
     objects"; `stats["n_textured_objects"]` counts them): the reflectance or the albedo is multiplied by the base colour, the roughness
     and the metallic by the orm image's g and b, each read with bilinear filtering and repeat wrapping at the coordinate interpolated
-    at the hit.  A tracer with objects renders forward only.  `movable=True` (with objects; DESIGN.md section 1.4, "Moving inserted
+    at the hit.  A dielectric or roughdielectric bsdf may carry "medium": {"sigma_a": (r, g, b), "scatter": sigma_s, "g": g} or {"color":
+    (r, g, b), "at": d, ...} ("Media inside glass"; `stats["n_medium_objects"]` counts them): a homogeneous medium
+    behind the interface, chromatic absorption and grey scattering with a Henyey-Greenstein phase function, the coefficients per scene
+    unit.  `move_objects` leaves them per scene unit, so an object scaled by s is optically s times thicker.  A dense medium of high
+    albedo loses the energy of the paths that max_depth (16 at the most) cuts, as Mitsuba does at the same max_depth.
+    A tracer with objects renders forward only.  `movable=True` (with objects; DESIGN.md section 1.4, "Moving inserted
     objects"; `stats["movable"]`): the BVH is grafted, the depth mesh's subtree and the objects' under one root, and the objects' rest
     pose stays on the device, so that `move_objects` places them anew without a rebuild (two launches; well under a millisecond for a small mesh); `reach`: the largest coordinate magnitude any
     later pose will have (default, and at least: the rest scene's; `stats["reach"]`), for which the boxes are padded.  `movable=False`
@@ -83,6 +89,7 @@ class PathTracer:
         self.rough = False                            # some object is of kind BSDF_ROUGH_DIELECTRIC: `render` takes the rough entry point
         self.obj_col: Optional[torch.Tensor] = None   # corner colours of the inserted triangles, when some object is coloured
         self.textures = None                          # (obj_uv, PathObjectTex records, texels on the device), when some object is textured
+        self.media = None                             # the PathObjectMedium records, when some glass object holds a medium
         counts = dict.fromkeys(COUNT_KEYS, 0)
         if objects:
             scene = merge_scene(vertices, triangles, objects, lights=True, symbol=symbol)
@@ -92,6 +99,10 @@ class PathTracer:
                                 (counts["n_smooth_objects"], "normals"), (counts["n_colored_objects"], "colors"), (scene.textures, "textures")):
                 if have:                              # a library built before the feature: PathError now, not at the first render
                     symbol("matpbr_path_render_objects_" + level)
+            if scene.media is not None:
+                for name in ("matpbr_path_render_objects_media", "matpbr_path_render_objects_diff_media"):
+                    symbol(name)
+                self.media = (PathObjectMedium * len(scene.media))(*scene.media)
             if scene.obj_col is not None:
                 symbol("matpbr_path_feature_colors")
                 self.obj_col = torch.from_numpy(scene.obj_col).to(self.device)
@@ -103,7 +114,7 @@ class PathTracer:
                 lt = scene.lights
                 self.lights = (lt["header"], torch.from_numpy(lt["tris"]).to(self.device), torch.from_numpy(lt["cdf"]).to(self.device))
             self.rough = counts["n_rough_objects"] > 0
-            if any(counts[key] for key in COUNT_KEYS if key != "n_smooth_objects"):
+            if any(counts[key] for key in COUNT_KEYS if key != "n_smooth_objects") or self.media is not None:
                 self.pbr = (PathObjectPbr * len(scene.records))(*scene.records)   # the entry points from the lights' on take the records beside the table as well
             if scene.obj_nrm is not None:
                 self.obj_nrm = torch.from_numpy(scene.obj_nrm).to(self.device)
@@ -130,6 +141,7 @@ class PathTracer:
         self.stats["n_objects"] = len(self.objects) if self.objects is not None else 0
         self.stats["n_object_tris"] = self.stats["n_tris"] - n_scene
         self.stats.update(counts)
+        self.stats["n_medium_objects"] = sum(1 for t in self.objects if t.kind & OBJECT_MEDIUM) if self.objects is not None else 0
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -193,6 +205,11 @@ class PathTracer:
         uv, rec, texels = self.textures
         return (uv.data_ptr(), *_tex_ptrs(self.objects, rec, texels))
 
+    def media_arg(self):
+        """The PathObjectMedium records as the two entries with media take them, after the thirteen object arguments (and, in the
+        differential family, the outputs); None on a tracer without a medium."""
+        return ctypes.cast(self.media, _P) if self.media is not None else None
+
     def poses(self, transforms: Sequence[Optional[dict]]):
         """`move_objects`' argument checked, before any device work -> the PathXform records: one entry per object, each None or a
         placement `similarity` takes (the default pivot is the centre of the object's rest bounding box); every record one the library
@@ -220,7 +237,8 @@ class PathTracer:
         "pivot": (x, y, z)}, every part optional: p' = R (s (p - pivot)) + pivot + translate, the pivot by default the centre of the
         object's rest bounding box.  Always from the rest pose the tracer was built with, never from the last pose.  Everything is
         checked first (`poses`); then the move and the refit of the object nodes are enqueued on the current stream and a light's area
-        becomes (float)((double) area_rest s s).  Every other method sees the moved scene from then on."""
+        becomes (float)((double) area_rest s s).  A medium's coefficients stay per scene unit: an object scaled by s is optically s times
+        thicker.  Every other method sees the moved scene from then on."""
         records = self.poses(transforms)
         mv, dev = self._move, self.device
         head, ltris = (None, None) if self.lights is None else self.lights[:2]
@@ -233,7 +251,7 @@ class PathTracer:
             head = moved
         check(symbol("matpbr_path_objects_move")(
             self.nodes.data_ptr(), self.tris.data_ptr(), mv["rest_tris"].data_ptr(), self.n_scene_tris, n_obj, mv["first_object_node"],
-            mv["n_object_nodes"], mv["node_level"].data_ptr(), mv["object_depth"], _table_ptrs(self.objects)[0], len(self.objects),
+            mv["n_object_nodes"], mv["node_level"].data_ptr(), mv["object_depth"], _table_ptrs(_uncolored(self.objects, 0))[0], len(self.objects),
             ctypes.cast(records, ctypes.c_void_p), mv["pad"], _dptr(mv["rest_nrm"]), _dptr(self.obj_nrm), _dptr(mv["rest_light_tris"]), _dptr(ltris),
             0 if ltris is None else int(ltris.shape[0]), None if head is None else _ref(head), torch.cuda.current_stream(dev).cuda_stream),
             "matpbr_path_objects_move")
@@ -268,6 +286,8 @@ class PathTracer:
                     entry = name
                     break
             own = self.object_args()[:OBJECT_ENTRIES[entry]]
+            if self.media is not None:                # level 8, only where a medium exists: every other tracer keeps its route
+                entry, own = MEDIA_ENTRY, (*self.object_args()[:9], *self._texture_args(), self.media_arg())
         check(symbol(entry, lib)(*args, *own), entry)
         return out
 
@@ -300,8 +320,12 @@ class PathTracer:
         fg, delta = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
         alpha, rewalked = torch.empty(H, W, device=dev, dtype=torch.float32), torch.zeros(H, W, device=dev, dtype=torch.int32)
         tail = (*own, *base) if own or not ratio else (None, None, *base)
+        if self.media is not None:                    # the superset entry, only where a medium exists: photo, through and base nullable, then the records
+            entry = "matpbr_path_render_objects_diff_media"
+            fn = symbol(entry)
+            tail = (*(own or (None, None)), *(base or (None,)), self.media)
         check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), _dptr(rays), torch.cuda.current_stream(dev).cuda_stream,
-                 *self.object_args()[:9], *self._texture_args(), *(_dptr(x) for x in (fg, delta, alpha, rewalked, *tail))), entry)
+                 *self.object_args()[:9], *self._texture_args(), *(ctypes.cast(x, _P) if isinstance(x, ctypes.Array) else _dptr(x) for x in (fg, delta, alpha, rewalked, *tail))), entry)
         return (fg, delta, *base, alpha, *own[1:], rewalked)
 
     @torch.no_grad()

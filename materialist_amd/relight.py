@@ -344,13 +344,16 @@ def load_oi_scene(path: str) -> List[dict]:
     coordinates ("Textured inserted objects"); "transform": {"scale": 1, "rotate": {"axis": [x, y, z], "deg": a}, "translate": [x, y, z], "pivot": [x, y, z]} places the mesh
     (every part optional, the pivot by default the centre of its bounding box) and "motion": {"spin": {"axis": [x, y, z],
     "deg_per_frame": a}, "slide": [dx, dy, dz]} moves it from frame to frame of `render_oi(frames=N)` (`oi_pose`; DESIGN.md section 1.4,
-    "Moving inserted objects")
+    "Moving inserted objects"); "medium" (a dielectric or roughdielectric object only) fills the glass with a homogeneous medium
+    ("Media inside glass"): {"sigma_a": [r, g, b], "scatter": sigma_s, "g": g}, the coefficients per scene unit, or
+    {"color": [r, g, b], "at": d, "scatter", "g"}, the colour in (0, 1] white light has after the distance d > 0 inside the object
+    (sigma_a = -ln(color) / d); it travels in the entry's "bsdf" as PathTracer takes it
     -> [{"ply": absolute path, "bsdf", "normals", "colors", "texture": absolute path or None, "orm_texture", "transform": the dict or
     None, "motion"}], nothing read yet but the list.  ValueError naming
     the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
     import json
 
-    from .pathtrace import object_bsdf
+    from .pathtrace import object_bsdf, object_medium
 
     try:
         with open(path) as f:
@@ -371,10 +374,10 @@ def load_oi_scene(path: str) -> List[dict]:
         where = f"{path}: objects[{k}]"
         if not isinstance(ob, dict):
             raise ValueError(f"{where} must be an object with 'ply' and 'bsdf'")
-        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors", "texture", "orm_texture", "transform", "motion"})
+        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors", "texture", "orm_texture", "transform", "motion", "medium"})
         if extra:
             raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals', 'colors', 'texture', 'orm_texture', 'transform', "
-                             f"'motion')")
+                             f"'motion', 'medium')")
         if not isinstance(ob.get("ply"), str) or not ob["ply"]:
             raise ValueError(f"{where}: 'ply' must name a mesh file")
         ply = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob["ply"]))
@@ -384,6 +387,15 @@ def load_oi_scene(path: str) -> List[dict]:
             object_bsdf(ob.get("bsdf"))
         except (ValueError, TypeError) as e:
             raise ValueError(f"{where}: bad bsdf: {e}") from None
+        bsdf = ob["bsdf"]
+        if ob.get("medium") is not None:
+            if "medium" in bsdf:
+                raise ValueError(f"{where}: 'medium' is given twice, as the entry's key and inside its 'bsdf'")
+            bsdf = dict(bsdf, medium=ob["medium"])
+            try:
+                object_medium(bsdf)
+            except (ValueError, TypeError) as e:
+                raise ValueError(f"{where}: bad medium: {e}") from None
         normals = ob.get("normals", "flat")
         if normals not in ("flat", "vertex"):
             raise ValueError(f"{where}: 'normals' must be 'flat' or 'vertex', got {normals!r}")
@@ -411,7 +423,7 @@ def load_oi_scene(path: str) -> List[dict]:
             oi_pose(transform, motion, 1)
         except ValueError as e:
             raise ValueError(f"{where}: {e}") from None
-        out.append({"ply": ply, "bsdf": ob["bsdf"], "normals": normals, "colors": colors, **images, "transform": transform, "motion": motion})
+        out.append({"ply": ply, "bsdf": bsdf, "normals": normals, "colors": colors, **images, "transform": transform, "motion": motion})
     return out
 
 
@@ -537,7 +549,8 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
               spp: int = 64, n_iter: int = 10, max_depth: int = 16, seed: int = 0, device="cuda", object_normals: str = "flat",
               denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
               object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None,
-              composite_denoise: bool = False, see_through: bool = False, shadows: str = "additive", frames: int = 1):
+              composite_denoise: bool = False, see_through: bool = False, shadows: str = "additive", frames: int = 1, tint=None,
+              tint_at: Optional[float] = None):
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -584,7 +597,10 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     (the identity leaves the file's bytes), and "motion" is ignored with a printed line.  `frames` > 1: a video: one movable tracer, per
     frame `PathTracer.move_objects` to the frame's poses and then the very branch a still runs for the options given, the feature guides
     computed anew -> <out>/oi_animation/frame_%04d.png, mi_oi[c]_<name>_<env>.mp4 and .gif, and the dict of paths
-    `render_rolling_envmap` returns.  `frames` > 1 without an `objects_file` in which an object moves is a ValueError."""
+    `render_rolling_envmap` returns.  `frames` > 1 without an `objects_file` in which an object moves is a ValueError.  `tint` (r, g, b in
+    (0, 1]; without `objects_file`): oi.ply, the glass, holds an absorbing medium ("Media inside glass") that gives
+    white light this colour after the distance `tint_at` (default: the largest side of the mesh's bounding box); an entry of
+    `objects_file` says "medium" itself, and with one `tint` is a ValueError, as is `tint_at` without `tint`."""
     if shadows not in OI_SHADOWS:
         raise ValueError(f"shadows must be 'additive' or 'ratio', got {shadows!r}")
     if shadows == "ratio" and not composite:
@@ -605,9 +621,22 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     if frames > 1 and not (placed and any(_oi_moves(mo) for _, mo in placed)):
         raise ValueError(f"frames={frames} would render {frames} equal frames: give an objects_file in which an object has a \"motion\" "
                          f"(\"spin\" with a deg_per_frame other than 0, or a \"slide\" other than 0)")
+    if tint is None and tint_at is not None:
+        raise ValueError("tint_at needs tint: it is the distance at which the glass has the tint's colour")
+    if tint is not None and objects_file is not None:
+        raise ValueError("tint colours oi.ply, the default glass: an entry of objects_file says \"medium\" itself")
     if objects_file is None:
         plys = [os.path.join(scene_dir, "oi.ply"), os.path.join(scene_dir, "oi2.ply")]
         bsdfs = [{"type": "dielectric", "int_ior": OI_INT_IOR, "ext_ior": OI_EXT_IOR}, {"type": "diffuse", "reflectance": (OI_REFLECTANCE,) * 3}]
+        if tint is not None:
+            if not os.path.exists(plys[0]):
+                raise FileNotFoundError(f"tint colours the glass object, {plys[0]}, which does not exist")
+            at = tint_at
+            if at is None:                                # the largest side of the mesh's bounding box
+                Vg = np.asarray(_mesh.read_ply_any(plys[0], normals=True, colors=True, uv=True)[0], np.float64)
+                at = float((Vg.max(0) - Vg.min(0)).max())
+            bsdfs[0]["medium"] = {"color": [float(x) for x in tint], "at": at}
+            _pathtrace.object_medium(bsdfs[0])           # ValueError now, before any other work
         have = [(p, b, object_normals, c, t, None) for p, b, c, t in zip(plys, bsdfs, ("none", object_colors), (None, object_texture))
                 if os.path.exists(p)]
         if not have:

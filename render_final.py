@@ -47,6 +47,13 @@ def parse_args(argv=None):
                     help='--mode oi: an object list, {"objects": [{"ply": path relative to the file, "bsdf": {"type": "pbr", "albedo": [r, g, b], '
                          '"roughness": r, "metallic": m} (or a "dielectric" or "diffuse" one, or {"type": "roughdielectric", "int_ior": n, "ext_ior": n, "alpha": a}, frosted glass, or {"type": "area", "radiance": [r, g, b]}, a lamp), "normals": "flat" or "vertex"}, ...]}, at most 8 '
                          "objects; with it <scene>/oi.ply and <scene>/oi2.ply are not looked for and --oi_normals is ignored")
+    ap.add_argument("--oi_tint", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="--mode oi without --oi_scene: tint oi.ply, the glass, with an absorbing medium inside it: the colour, each channel in "
+                         "(0, 1], that white light has after --oi_tint_at inside the glass (an --oi_scene entry says \"medium\": {\"color\": [r, g, b], "
+                         "\"at\": d} or {\"sigma_a\": [r, g, b], \"scatter\": s, \"g\": g} itself, on a dielectric or roughdielectric object)")
+    ap.add_argument("--oi_tint_at", type=float, default=None, metavar="D",
+                    help="--oi_tint: the distance, in scene units, at which the glass has that colour (default: the largest side of the "
+                         "mesh's bounding box)")
     ap.add_argument("--env_scale", type=float, default=1.0, metavar="S",
                     help="--integrator path and --mode oi: multiply the envmap by S before its sampling tables are built (1 = the same bits as "
                          "without it; 0 with an area light in --oi_scene = the night shot, lit by the lamp alone)")
@@ -100,6 +107,12 @@ def parse_args(argv=None):
         ap.error("--oi_composite_denoise splits every frame into two halves of spp/2 samples: --spp must be even")
     if a.oi_composite and a.env_scale != 1.0:
         ap.error("--oi_composite needs --env_scale 1: the photograph was taken under the envmap as it is and is not dimmed")
+    if a.oi_tint is not None and (a.mode != "oi" or a.oi_scene is not None):
+        ap.error("--oi_tint needs --mode oi without --oi_scene (an --oi_scene entry says \"medium\" itself)")
+    if a.oi_tint is not None and not all(0 < c <= 1 for c in a.oi_tint):
+        ap.error("--oi_tint: every channel must lie in (0, 1]")
+    if a.oi_tint_at is not None and (a.oi_tint is None or not (0 < a.oi_tint_at < float("inf"))):
+        ap.error("--oi_tint_at needs --oi_tint and must be finite and > 0")
     if a.oi_frames < 1:
         ap.error("--oi_frames must be at least 1")
     if a.oi_frames > 1 and (a.mode != "oi" or a.oi_scene is None):
@@ -133,7 +146,8 @@ def main(argv=None):
                                 **({"composite_denoise": True} if a.oi_composite_denoise else {}),
                                 **({"see_through": True} if a.oi_see_through else {}),
                                 **({"shadows": a.oi_shadows} if a.oi_shadows != "additive" else {}),
-                                **({"frames": a.oi_frames} if a.oi_frames != 1 else {}))
+                                **({"frames": a.oi_frames} if a.oi_frames != 1 else {}),
+                                **({"tint": a.oi_tint, "tint_at": a.oi_tint_at} if a.oi_tint is not None else {}))
         if a.oi_frames > 1:
             print(f"Animation saved to {res['mp4']}\nIndividual frames saved to {res['animation_dir']}")
         else:
