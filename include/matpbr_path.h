@@ -75,6 +75,13 @@ enum {
  * kind. */
 #define MATPBR_PATH_OBJECT_MEDIUM 0x800
 
+/* OR-ed into MatpbrPathObject.kind beside the four flags above: a vertex on the object keeps the camera chain of the see-through rule
+ * alive, so that what the object reflects (or, through rough glass, transmits) of the depth mesh is the photograph (DESIGN.md section
+ * 1.4, "Reflected in inserted objects").  Valid on kinds 2, 3 and 5 only: kind 4 has no BSDF, and on kind 1 the see-through rule holds
+ * already.  Only matpbr_path_render_objects_reflect and matpbr_path_reflect_chain_host take it; to every other entry point it is an
+ * unknown kind. */
+#define MATPBR_PATH_OBJECT_PHOTO 0x1000
+
 /* One inserted mesh: triangles [first_tri, first_tri + n_tri) of the mesh handed to matpbr_path_bvh_build_objects (ids at or
  * above its n_scene_tri), outward winding. */
 typedef struct MatpbrPathObject {
@@ -758,6 +765,45 @@ int matpbr_path_render_objects_diff_media(const void* nodes, const void* tris, c
                                           const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
                                           const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
                                           const float* photo, float* through, float* base, const MatpbrPathObjectMedium* media);
+
+/* ---- Reflected in inserted objects ("Reflected in inserted objects"): the see-through rule along chains that
+ * pass objects whose kind carries MATPBR_PATH_OBJECT_PHOTO; forward only; added at version 3. */
+
+/* matpbr_path_render_objects_diff_media with photo and through required (base and media nullable with that entry's meaning), where an
+ * object of kind 2, 3 or 5 may carry MATPBR_PATH_OBJECT_PHOTO.  Level 9 of the table in DESIGN.md section 1.4, "The object entries":
+ * without a flagged object it launches the existing kernel of the same shape and gives its bits.  With one, the walk is that
+ * entry's but for the chain: a vertex keeps the chain alive where its object is of kind 1 or carries the flag (a medium vertex still
+ * ends it).  A flagged vertex is not delta: its emitter sample, with shadow ray and MIS weight, is taken as ever and stays in the
+ * sample's radiance, and so do the envmap a chain ray escapes to and the light it meets; a flagged vertex whose path ends (a one-sided
+ * back hit, a kind-3 sample below the face, a throughput of zero) does not land.  The landing is unchanged: depth k >= 1, the front of
+ * a triangle of id < n_scene_tri, thr_k photo[texel(p)] added to `through` before the max_depth test, thr_k now with the flagged
+ * vertices' weights f cos / pdf and no MIS weight (the depth mesh is no emitter).  With L_chain,s the radiance gathered at depths below
+ * k, a see-through sample adds fg_s = L_chain,s + (L_tailwith,s - L_tail,s): the bracket only where the touch rule asks for the second
+ * walk, else L_chain,s exactly.  The second walk replays the chain with the same dims 6, 7, 8 over every triangle and takes no emitter
+ * sample (and traces no shadow ray) at depths below k; from k on it is matpbr_path_render_objects_through's.  The photograph gives the
+ * radiance p sends to the camera and is used for whatever direction the chain arrives from: the diffuse assumption of "Seen through
+ * glass".  delta, alpha and base are the unflagged table's bits; rewalked counts both kinds of second walk.  Every split into launches
+ * gives the same bits.  Invalid arguments, besides that entry point's: photo or through NULL, the flag on kind 1 or 4. */
+int matpbr_path_render_objects_reflect(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                       float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                       int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                       const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                       const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                       const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                       const float* photo, float* through, float* base, const MatpbrPathObjectMedium* media);
+
+/* The camera chain of matpbr_path_render_objects_reflect on the CPU (every pointer HOST): matpbr_path_through_chain_host's arguments
+ * with pbr (one record per object, nullable where no flagged object is of kind 3) after n_scene_tri, and its outputs.  One body serves
+ * both: on a table without the flag the two give the same bits.  A flagged vertex runs the samplers the kernel runs (the diffuse and
+ * the rough dielectric one, about the interpolated normal where the object is smooth); at kind 3 the depth mesh's sampler is restated
+ * with plain divisions and square roots, the device's being hardware instructions, so thr agrees with the kernel's to rounding, not to
+ * the bit.  A flagged object may not carry the colour or the texture flag here, and no object a medium.  Invalid: that entry's, a
+ * flagged object of kind 1 or 4, a flagged coloured or textured object, a flagged object of kind 3 with pbr NULL or a bad record. */
+int matpbr_path_reflect_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,
+                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                   const MatpbrPathObjectPbr* pbr, const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N,
+                                   int32_t* depth, int32_t* texel, float* thr, float* o, float* d);
 
 /* One segment inside a medium on the CPU, with the routine the kernel runs: the record `medium` (checked), per lane the traced
  * distance t[N] and u9[N] -> scattered[N] (1: the segment ends at a medium vertex), dist[N] (s there, else t), weight[N,3] =

@@ -11,13 +11,15 @@
 // traversals and the host builder; path_shading.hpp the RNG, the envmap sampler and the BSDF wrappers; path_objects.hpp the tables the
 // kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
 // path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser; path_diff.hpp the differential render's table
-// and the composite; path_media.hpp the media inside glass objects; path_move.hpp the grafted BVH's move and refit of the inserted objects.
+// and the composite; path_media.hpp the media inside glass objects; path_move.hpp the grafted BVH's move and refit of the inserted objects;
+// path_reflect.hpp the see-through tables whose chain passes flagged objects.
 #include <type_traits>
 
 #include "path_denoise.hpp"
 #include "path_diff.hpp"
 #include "path_media.hpp"
 #include "path_move.hpp"
+#include "path_reflect.hpp"
 
 namespace {
 
@@ -82,13 +84,19 @@ __device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second
 // without `base` are the code they were; every `if (BASE ...)` folds away in them.  MEDIUM: TEX or a table of the DIFF family with media
 // inside glass objects (Objects = MediumObjects, MediumDiff<...>; DESIGN.md section 1.4, "Media inside glass"): the path carries `med`,
 // the object whose medium the ray is in, and a segment with med >= 0 is attenuated and may end at a medium vertex.  Read off the
-// table's type (MediumTraits); every `if (MEDIUM ...)` folds away in the sixteen kernels without media.
+// table's type (MediumTraits); every `if (MEDIUM ...)` folds away in the sixteen kernels without media.  REFLECT: THROUGH whose chain also
+// passes the vertices of objects that carry MATPBR_PATH_OBJECT_PHOTO (Objects = Reflect<...> of the four see-through shapes; DESIGN.md
+// section 1.4, "Reflected in inserted objects").  Such a vertex is not delta: its emitter sample stays in the sample's radiance.  At the
+// landing trip 0 commits the radiance gathered so far, the chain's, to fg and starts L afresh, so that Lw is the tail's as it is along
+// a dielectric chain; trip 1 replays the chain without emitter samples below `land`, so that its L is the tail's as well.  Read off the
+// table's type (ReflectTraits); every `if (REFLECT ...)` folds away in the twenty kernels without it.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
     constexpr bool THROUGH = DiffTraits<Objects>::through;
     constexpr bool DIFF = DiffTraits<Objects>::diff;
     constexpr bool BASE = DiffTraits<Objects>::base;
     constexpr bool MEDIUM = MediumTraits<Objects>::medium;
+    constexpr bool REFLECT = ReflectTraits<Objects>::reflect;
     constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF || MEDIUM;
     constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
@@ -218,6 +226,13 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                         const long tq = screen_texel(p, q.f_ndc, q.aspect, q.H, q.W);
 #pragma unroll
                         for (int c = 0; c < 3; ++c) ot.through[3 * pix + c] += thr[c] * ot.photo[3 * tq + c];
+                        if constexpr (REFLECT) {   // the chain's own light goes to fg here: from now on L is the tail's
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                ot.fg[3 * pix + c] += L[c];
+                                L[c] = 0.0f;
+                            }
+                        }
                         land = depth;
                         touched = ot.lt.n > 0;
                     }
@@ -242,8 +257,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             bool textured = false;        // (TEX) the object's images are read at its interpolated corner coordinates
             float bu = 0.0f, bv = 0.0f;   // (COLOR) u, v of the winning triangle, formed once for the texture, the colour and the smooth normal
             if constexpr (LIGHT) {   // the table lookup moves ahead of the max_depth test: a light's emission is added as the envmap's escape term is
-                const LightLookup f = light_lookup<TEX     ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_TEXTURED :
-                                                   COLOR ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED : MATPBR_PATH_OBJECT_SMOOTH>(
+                const LightLookup f = light_lookup<(REFLECT ? MATPBR_PATH_OBJECT_PHOTO : 0) |
+                                                   (TEX     ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_TEXTURED :
+                                                    COLOR ? MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_COLORED : MATPBR_PATH_OBJECT_SMOOTH)>(
                     ot, __float_as_int(q.tris[3 * k].w));
                 kind = f.kind;
                 op[0] = f.p0; op[1] = f.p1; op[2] = f.p2;
@@ -296,8 +312,14 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 if (kind & MATPBR_PATH_OBJECT_MEDIUM) med_obj = medium_index(ot.t, __float_as_int(q.tris[3 * k].w));
                 kind &= ~MATPBR_PATH_OBJECT_MEDIUM;
             }
+            bool photo_obj = false;   // (REFLECT) the vertex lies on an object that carries the photo flag
+            if constexpr (REFLECT) {
+                photo_obj = (kind & MATPBR_PATH_OBJECT_PHOTO) != 0;
+                kind &= ~MATPBR_PATH_OBJECT_PHOTO;
+            }
             if constexpr (THROUGH) {
-                if (!second) chain = chain && kind == MATPBR_PATH_BSDF_DIELECTRIC;   // rough glass and every other kind end the chain
+                // rough glass and every other kind end the chain; (REFLECT) a flagged object of any kind keeps it
+                if (!second) chain = chain && (kind == MATPBR_PATH_BSDF_DIELECTRIC || (REFLECT && photo_obj));
             }
             // a hit on the back of a triangle ends the path (glass shades from both sides)
             const bool rough = ROUGH && kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC;   // (ROUGH) shades from both sides, like glass
@@ -392,7 +414,8 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
 #pragma unroll
             for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
             // emitter sample with a shadow ray (none at a delta vertex)
-            if (((ROUGH ? n_e > 0 : LIGHT) || have_tab) && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC)) {
+            // (REFLECT) trip 1 takes none below the landing: the chain's own light is not the tail's
+            if (((ROUGH ? n_e > 0 : LIGHT) || have_tab) && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !(REFLECT && second && depth < land)) {
                 float wl[3], pdf_e;
                 int te = 0;
                 float Le[3] = {0.0f, 0.0f, 0.0f}, ts_max = FLT_MAX;   // (LIGHT) the chosen emitter's radiance, the shadow ray's reach
@@ -950,6 +973,7 @@ struct Scene {
     const MatpbrPathObjectTex* tex = nullptr;
     const float4* texels = nullptr;
     const MatpbrPathObjectMedium* media = nullptr;   // set where some object holds a medium
+    int n_photo = 0;                                 // how many objects carry MATPBR_PATH_OBJECT_PHOTO
     TransEdit edit{};
     const float* nrm = nullptr;
 };
@@ -1020,7 +1044,7 @@ bool textures_valid(const MatpbrPathObject* objects, int n_objects, const float*
     if (!obj_uv || !tex || !texels || ((uintptr_t)texels & 15) || n_texels < 1) return false;
     for (int k = 0; k < n_objects; ++k) {
         if (!(objects[k].kind & MATPBR_PATH_OBJECT_TEXTURED)) continue;
-        const int base = objects[k].kind & ~(MATPBR_PATH_OBJECT_TEXTURED | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_SMOOTH);
+        const int base = objects[k].kind & ~(MATPBR_PATH_OBJECT_TEXTURED | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_SMOOTH | MATPBR_PATH_OBJECT_PHOTO);
         if (!tex_valid(tex[k], base == MATPBR_PATH_BSDF_PBR, n_texels)) return false;
     }
     return true;
@@ -1040,7 +1064,8 @@ bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept
 // admits kinds 1 and 2, level 2 the smooth flag on them, level 3 kind 3, level 4 kind 4, level 5 kind 5, level 6 the colour flag on
 // kinds 2 and 3 (obj_col is consulted where an object carries it), level 7 the texture flag on them (obj_uv, tex and texels are consulted
 // where an object carries it, and its record is checked against n_texels), level 8 the medium flag on kinds 1 and 5 (media is consulted
-// where an object carries it, and its record is checked; its kernel is chosen first).  An entry passes null / 0 for
+// where an object carries it, and its record is checked; its kernel is chosen first), level 9 the photo flag on kinds 2, 3 and 5 (it
+// chooses no kernel here: matpbr_path_render_objects_reflect reads n_photo).  An entry passes null / 0 for
 // the arguments it does not have; level 1's n_scene_tri = 0 lies below every range.  An argument is consulted only where the table needs
 // it: obj_nrm where an object is smooth, pbr where one is of kind 3, the light header and buffers where one is of kind 4.  The counts
 // alone choose the kernel.
@@ -1050,7 +1075,7 @@ bool objects_scene(int level, const MatpbrPathObject* objects, int n_objects, co
                    const MatpbrPathObjectMedium* media = nullptr) {
     const unsigned accept = (level >= 2 ? kAcceptSmooth : 0u) | (level >= 3 ? kAcceptPbr : 0u) | (level >= 4 ? kAcceptLight : 0u) |
                             (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u) | (level >= 7 ? kAcceptTexture : 0u) |
-                            (level >= 8 ? kAcceptMedium : 0u);
+                            (level >= 8 ? kAcceptMedium : 0u) | (level >= 9 ? kAcceptPhoto : 0u);
     ObjCounts n;
     if (!scene_table(objects, n_objects, accept, obj_nrm, n_scene_tri, pbr, s.ot, n) || (n.pbr > 0 && !pbr) || (n.color > 0 && !obj_col) ||
         (n.light > 0 && !light_table(lights, &s.ot, light_tris, light_cdf, s.lt)) ||
@@ -1063,6 +1088,7 @@ bool objects_scene(int level, const MatpbrPathObject* objects, int n_objects, co
         n.medium = 0;
     }
     s.media = n.medium > 0 ? media : nullptr;
+    s.n_photo = n.photo;
     s.kernel = n.medium > 0 ? Kernel::MediumObjects : n.tex > 0 ? Kernel::TexObjects : n.color > 0 ? Kernel::ColorObjects : n.rough > 0 ? Kernel::RoughObjects : n.light > 0 ? Kernel::LightObjects : n.pbr > 0 ? Kernel::PbrObjects :
                n.smooth > 0 ? Kernel::SmoothObjects : n_objects > 0 ? Kernel::ObjTable : Kernel::NoObjects;
     s.obj_nrm = n.smooth > 0 ? obj_nrm : nullptr;
@@ -1711,6 +1737,44 @@ int matpbr_path_render_objects_diff_media(const void* nodes, const void* tris, c
     return photo ? launch(ThroughObjects{}) : launch(DiffObjects{});
 }
 
+int matpbr_path_render_objects_reflect(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                       float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                       int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                       const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
+                                       const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
+                                       const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
+                                       const float* photo, float* through, float* base, const MatpbrPathObjectMedium* media) {
+    float* const out = nullptr;   // the sums go to the table's buffers
+    const Frame f = RENDER_FRAME;
+    PathArgs q{};
+    Scene s;
+    if (!fg || !delta || !alpha || !photo || !through || n_objects <= 0 || !frame_args(f, q) ||
+        !objects_scene(9, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s, media))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    // the shape's table filled as matpbr_path_render_objects_diff_media fills it, then launched as it is or, where an object carries
+    // the photo flag, as the table of the kernel whose chain passes it
+    auto launch_as = [&](auto table) {
+        if (s.n_photo == 0) return launch_frame(f, q, table);
+        Reflect<decltype(table)> rt{};
+        static_cast<decltype(table)&>(rt) = table;
+        return launch_frame(f, q, rt);
+    };
+    auto launch = [&](auto table) {
+        using Table = decltype(table);
+        static_cast<TexObjects&>(table) = tex_objects(s);
+        table.fg = fg; table.delta = delta; table.alpha = alpha; table.rewalked = rewalked;
+        table.photo = photo; table.through = through;
+        if constexpr (DiffTraits<Table>::base) table.base = base;
+        if (!s.media) return launch_as(table);
+        MediumDiff<Table> mt{};
+        static_cast<Table&>(mt) = table;
+        media_into(s, mt);
+        return launch_as(mt);
+    };
+    return base ? launch(RatioThroughObjects{}) : launch(ThroughObjects{});
+}
+
 int matpbr_path_medium_segment_host(const MatpbrPathObjectMedium* medium, const float* t, const float* u9, long N, int32_t* scattered,
                                     float* dist, float* weight) {
     if (!medium || !t || !u9 || !scattered || !dist || !weight || N < 0 || !medium_valid(*medium)) return MATPBR_PATH_ERR_INVALID_ARG;
@@ -1724,16 +1788,22 @@ int matpbr_path_phase_sample_host(float g, const float* d, const float* u, long 
     return MATPBR_PATH_OK;
 }
 
-int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,
-                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
-                                   const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N, int32_t* depth, int32_t* texel,
-                                   float* thr, float* o, float* d) {
+// the camera chain of both CPU entries below, one body: `reflect` admits the photo flag, and a vertex on a flagged object then keeps
+// the chain as the kernels of Reflect<...> keep it (its BSDF sample by dims 6, 7, 8; no emitter sample changes the chain)
+static int chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth, const MatpbrPathObject* objects,
+                      int n_objects, const float* obj_nrm, long n_scene_tri, const MatpbrPathObjectPbr* pbr, bool reflect, const int32_t* pixel,
+                      const uint32_t* seed, const int32_t* sample, long N, int32_t* depth, int32_t* texel, float* thr, float* o, float* d) {
     ObjTable ot{};
     ObjCounts cnt;
     if (!nodes || !tris || !pixel || !seed || !sample || !depth || !texel || !thr || !o || !d || N < 0 || H <= 0 || W <= 0 ||
         !fov_valid(fov_x_deg) || max_depth < 1 || max_depth > MATPBR_PATH_MAX_MAX_DEPTH || n_objects <= 0 ||
-        !scene_table(objects, n_objects, kAcceptAll | kAcceptColor | kAcceptTexture, obj_nrm, n_scene_tri, nullptr, ot, cnt))
+        !scene_table(objects, n_objects, kAcceptAll | kAcceptColor | kAcceptTexture | (reflect ? kAcceptPhoto : 0u), obj_nrm, n_scene_tri, pbr, ot, cnt))
         return MATPBR_PATH_ERR_INVALID_ARG;
+    for (int k = 0; k < n_objects; ++k) {   // a flagged object: its record where it is of kind 3; no colour or image multiplies its weight here
+        if (!(objects[k].kind & MATPBR_PATH_OBJECT_PHOTO)) continue;
+        if (objects[k].kind & (MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_TEXTURED)) return MATPBR_PATH_ERR_INVALID_ARG;
+        if ((objects[k].kind & 0xff) == MATPBR_PATH_BSDF_PBR && !pbr) return MATPBR_PATH_ERR_INVALID_ARG;
+    }
     for (long l = 0; l < N; ++l)
         if (pixel[l] < 0 || pixel[l] >= (long)H * W || sample[l] < 0) return MATPBR_PATH_ERR_INVALID_ARG;
     const float4 *Nd = static_cast<const float4*>(nodes), *T = static_cast<const float4*>(tris);
@@ -1775,28 +1845,42 @@ int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, i
                 }
                 break;
             }
-            int kind = 0;
+            int kind = 0, obj = -1;
             float op[3] = {0.0f, 0.0f, 0.0f};
-            object_match(ot, id, [&](int, const MatpbrPathObject& ob) {
+            object_match(ot, id, [&](int k, const MatpbrPathObject& ob) {
                 kind = ob.kind;
+                obj = k;
                 op[0] = ob.p[0]; op[1] = ob.p[1]; op[2] = ob.p[2];
             });
             const bool smooth = (kind & MATPBR_PATH_OBJECT_SMOOTH) != 0;
-            kind &= ~(int)flags;
-            if (kind != MATPBR_PATH_BSDF_DIELECTRIC || dp + 1 >= max_depth) break;   // another kind, or still in the glass at max_depth
-            float wi[3], wgt[3], pdf_s;
+            const bool photo_obj = (kind & MATPBR_PATH_OBJECT_PHOTO) != 0;   // set only where `reflect` admitted it
+            kind &= ~(int)(flags | MATPBR_PATH_OBJECT_PHOTO);
+            // another kind without the flag, or still on the chain at max_depth
+            if (!(kind == MATPBR_PATH_BSDF_DIELECTRIC || photo_obj) || dp + 1 >= max_depth) break;
+            // a flagged object of kind 2 or 3 seen from behind ends the path, as every one-sided vertex does
+            if (kind != MATPBR_PATH_BSDF_DIELECTRIC && kind != MATPBR_PATH_BSDF_ROUGH_DIELECTRIC && !(dot3h(n, wo) > 0.0f)) break;
+            float wi[3], wgt[3], pdf_s, ns[3] = {n[0], n[1], n[2]};
             int fl;
             if (smooth) {
-                float ns[3], su, sv;
+                float su, sv;
                 tri_uv(v0, e1, e2, ro, rd, su, sv);
                 smooth_normal(obj_nrm + 9 * (long)(id - n_scene_tri), su, sv, n, ns);
                 smooth_side(n, wo, ns);
-                object_sample_shading(kind, op, n, ns, wo, rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wi, wgt, pdf_s, fl);
-            } else {
-                object_sample(kind, op, n, wo, rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wi, wgt, pdf_s, fl);
             }
             const float eps = spawn_eps(p);
-            const float side = dot3h(n, wi) > 0.0f ? eps : -eps;   // spawn on the side the new ray leaves on
+            float side = eps;
+            if (kind == MATPBR_PATH_BSDF_PBR) {   // the depth mesh's sampler on the record's constants; the ray leaves on the face's front
+                path_sample_host(rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wo, ns, pbr[obj].a, pbr[obj].r, pbr[obj].m, wi, wgt, pdf_s);
+                if (!(dot3h(n, wi) > 0.0f)) break;   // a reflection that leaves below the object's face carries nothing
+            } else {
+                if (kind == MATPBR_PATH_BSDF_ROUGH_DIELECTRIC)
+                    rough_sample(op, n, ns, wo, rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wi, wgt, pdf_s, fl);
+                else if (smooth)
+                    object_sample_shading(kind, op, n, ns, wo, rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wi, wgt, pdf_s, fl);
+                else
+                    object_sample(kind, op, n, wo, rng_u(base, dp, 6), rng_u(base, dp, 7), rng_u(base, dp, 8), wi, wgt, pdf_s, fl);
+                side = dot3h(n, wi) > 0.0f ? eps : -eps;   // spawn on the side the new ray leaves on
+            }
             for (int c = 0; c < 3; ++c) {
                 w[c] *= wgt[c];
                 ro[c] = fmaf(side, n[c], p[c]);
@@ -1813,6 +1897,22 @@ int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, i
         }
     }
     return MATPBR_PATH_OK;
+}
+
+int matpbr_path_through_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,
+                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                   const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N, int32_t* depth, int32_t* texel,
+                                   float* thr, float* o, float* d) {
+    return chain_host(nodes, tris, H, W, fov_x_deg, max_depth, objects, n_objects, obj_nrm, n_scene_tri, nullptr, false, pixel, seed, sample, N, depth,
+                      texel, thr, o, d);
+}
+
+int matpbr_path_reflect_chain_host(const void* nodes, const void* tris, int H, int W, float fov_x_deg, int max_depth,
+                                   const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
+                                   const MatpbrPathObjectPbr* pbr, const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N,
+                                   int32_t* depth, int32_t* texel, float* thr, float* o, float* d) {
+    return chain_host(nodes, tris, H, W, fov_x_deg, max_depth, objects, n_objects, obj_nrm, n_scene_tri, pbr, true, pixel, seed, sample, N, depth,
+                      texel, thr, o, d);
 }
 
 int matpbr_path_composite(const float* fg_sum, const float* delta_sum, const float* alpha_sum, const float* photo, int H, int W, float scale,

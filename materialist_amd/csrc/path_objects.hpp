@@ -464,13 +464,15 @@ bool rough_valid(const float p[3]) {
 // kAcceptLight kind MATPBR_PATH_BSDF_AREA (never with the smooth flag; p = radiance, finite and >= 0); kAcceptRough kind
 // MATPBR_PATH_BSDF_ROUGH_DIELECTRIC (rough_valid); kAcceptColor a kind 2 or 3 that carries MATPBR_PATH_OBJECT_COLORED (on another kind
 // the flag is refused); kAcceptTexture the same for MATPBR_PATH_OBJECT_TEXTURED (its record is path_textures.hpp's to check); kAcceptMedium
-// a kind 1 or 5 that carries MATPBR_PATH_OBJECT_MEDIUM (on another kind the flag is refused; its record is path_media.hpp's to check).
+// a kind 1 or 5 that carries MATPBR_PATH_OBJECT_MEDIUM (on another kind the flag is refused; its record is path_media.hpp's to check);
+// kAcceptPhoto a kind 2, 3 or 5 that carries MATPBR_PATH_OBJECT_PHOTO (on another kind the flag is refused).
 // A kind outside the mask is an unknown kind.  kAcceptAll is what the entries before the colour flag admit.
 enum : unsigned { kAcceptSmooth = 1u, kAcceptPbr = 2u, kAcceptLight = 4u, kAcceptRough = 8u, kAcceptAll = 15u, kAcceptColor = 16u, kAcceptTexture = 32u,
-                  kAcceptMedium = 64u };
-// how many objects of a checked table are smooth, of kind 3, of kind 4, of kind 5, coloured, textured, filled with a medium
+                  kAcceptMedium = 64u, kAcceptPhoto = 128u };
+// how many objects of a checked table are smooth, of kind 3, of kind 4, of kind 5, coloured, textured, filled with a medium, flagged to
+// keep the see-through chain
 struct ObjCounts {
-    int smooth = 0, pbr = 0, light = 0, rough = 0, color = 0, tex = 0, medium = 0;
+    int smooth = 0, pbr = 0, light = 0, rough = 0, color = 0, tex = 0, medium = 0, photo = 0;
 };
 bool object_table(const MatpbrPathObject* objects, int n_objects, unsigned accept, const MatpbrPathObjectPbr* pbr, ObjTable& ot,
                   ObjCounts* counts = nullptr) {
@@ -481,6 +483,13 @@ bool object_table(const MatpbrPathObject* objects, int n_objects, unsigned accep
     for (int k = 0; k < n_objects; ++k) {
         MatpbrPathObject plain = objects[k];
         bool range_alone = false;   // kinds 3, 4, 5 are checked as a diffuse object of reflectance 0: the range alone
+        if ((accept & kAcceptPhoto) && (plain.kind & MATPBR_PATH_OBJECT_PHOTO)) {
+            const int base = plain.kind & ~(MATPBR_PATH_OBJECT_PHOTO | MATPBR_PATH_OBJECT_MEDIUM | MATPBR_PATH_OBJECT_TEXTURED | MATPBR_PATH_OBJECT_COLORED |
+                                            MATPBR_PATH_OBJECT_SMOOTH);
+            if (base != MATPBR_PATH_BSDF_DIFFUSE && base != MATPBR_PATH_BSDF_PBR && base != MATPBR_PATH_BSDF_ROUGH_DIELECTRIC) return false;
+            plain.kind &= ~MATPBR_PATH_OBJECT_PHOTO;
+            ++c.photo;
+        }
         if ((accept & kAcceptTexture) && (plain.kind & MATPBR_PATH_OBJECT_TEXTURED)) {
             const int base = plain.kind & ~(MATPBR_PATH_OBJECT_TEXTURED | MATPBR_PATH_OBJECT_COLORED | MATPBR_PATH_OBJECT_SMOOTH);
             if (base != MATPBR_PATH_BSDF_DIFFUSE && base != MATPBR_PATH_BSDF_PBR) return false;

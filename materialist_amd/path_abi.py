@@ -31,6 +31,7 @@ OBJECT_COLORED = 0x200         # MATPBR_PATH_OBJECT_COLORED, OR-ed into the kind
 OBJECT_TEXTURED = 0x400        # MATPBR_PATH_OBJECT_TEXTURED, OR-ed into the kind of a diffuse or pbr object ("Textured inserted objects")
 OBJECT_FLAGS = OBJECT_SMOOTH | OBJECT_COLORED | OBJECT_TEXTURED
 OBJECT_MEDIUM = 0x800          # MATPBR_PATH_OBJECT_MEDIUM, OR-ed into the kind of a dielectric or roughdielectric object ("Media inside glass")
+OBJECT_PHOTO = 0x1000          # MATPBR_PATH_OBJECT_PHOTO, OR-ed into the kind of a diffuse, pbr or roughdielectric object ("Reflected in inserted objects")
 MEDIUM_MAX_G = 0.99            # |g| of the Henyey-Greenstein phase function at most this
 TEXTURE_MAX_SIDE = 8192        # w, h of an image
 TEXTURE_MAX_UV = 64.0          # |s|, |t| of a corner: a coordinate's fractional part keeps 17 bits or more
@@ -125,6 +126,9 @@ SIGNATURES = {
     "matpbr_path_render_objects_ratio": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 7),
     "matpbr_path_render_objects_media": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long, _P]),
     "matpbr_path_render_objects_diff_media": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 8),
+    "matpbr_path_render_objects_reflect": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 8),
+    "matpbr_path_reflect_chain_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P,
+                                                      ctypes.c_long] + [_P] * 5),
     "matpbr_path_medium_segment_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_phase_sample_host": (ctypes.c_int, [ctypes.c_float, _P, _P, ctypes.c_long, _P]),
     "matpbr_path_composite_ratio": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
@@ -205,6 +209,10 @@ MOVE_FEATURE = "moving inserted objects"
 MEDIUM_SYMBOLS = ("matpbr_path_render_objects_media", "matpbr_path_render_objects_diff_media", "matpbr_path_medium_segment_host",
                   "matpbr_path_phase_sample_host")
 MEDIUM_FEATURE = "media inside glass objects"
+# the symbols of the photograph reflected in inserted objects ("Reflected in inserted objects"), added at version 3
+# as well: a fifth group beside them
+REFLECT_SYMBOLS = ("matpbr_path_render_objects_reflect", "matpbr_path_reflect_chain_host")
+REFLECT_FEATURE = "the photograph reflected in inserted objects"
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
@@ -227,7 +235,7 @@ def load() -> ctypes.CDLL:
         _build.build_path_library()
         lib = ctypes.CDLL(_build.PATH_LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS or name in MEDIUM_SYMBOLS) and not hasattr(lib, name):
+            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS or name in MEDIUM_SYMBOLS or name in REFLECT_SYMBOLS) and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -242,7 +250,7 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
         what = (RATIO_FEATURE if name in RATIO_SYMBOLS else MOVE_FEATURE if name in MOVE_SYMBOLS else MEDIUM_FEATURE if name in MEDIUM_SYMBOLS
-                else _FEATURE.get(name, "smooth inserted objects"))
+                else REFLECT_FEATURE if name in REFLECT_SYMBOLS else _FEATURE.get(name, "smooth inserted objects"))
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 
@@ -292,8 +300,9 @@ def _uncolored(table, flags: int = OBJECT_COLORED | OBJECT_TEXTURED):
     """`table` as the entry points from before the colour flag take it (the features, the light tables: they need the kind and the smooth
     flag only): the same table where no object carries OBJECT_COLORED or OBJECT_TEXTURED, else copies without them.  `flags`: the
     flags to hide (the colour guide takes the colour flag and not the texture flag).  OBJECT_MEDIUM is always hidden: a medium changes
-    no geometry and no first-hit guide, and only the two entries that render it take its flag."""
-    flags |= OBJECT_MEDIUM
+    no geometry and no first-hit guide, and only the two entries that render it take its flag.  So is OBJECT_PHOTO, which only
+    matpbr_path_render_objects_reflect takes."""
+    flags |= OBJECT_MEDIUM | OBJECT_PHOTO
     if table is None or not any(t.kind & flags for t in table):
         return table
     return [PathObject(t.kind & ~flags, t.first_tri, t.n_tri, t.p) for t in table]
@@ -318,3 +327,11 @@ def _aligned_texels(texels) -> np.ndarray:
     out = buf[off:off + a.size].reshape(-1, 4)
     out[...] = a
     return out
+
+
+def _unflagged(table):
+    """`table` as every entry but matpbr_path_render_objects_reflect takes it: the same table where no object carries OBJECT_PHOTO, else
+    a copy without it (every other flag stays)."""
+    if table is None or not any(t.kind & OBJECT_PHOTO for t in table):
+        return table
+    return [PathObject(t.kind & ~OBJECT_PHOTO, t.first_tri, t.n_tri, t.p) for t in table]

@@ -89,6 +89,25 @@ def through_chain_host(bvh: Dict[str, object], table: Sequence[PathObject], n_sc
     return {"depth": depth, "texel": texel, "thr": thr, "o": o, "d": d}
 
 
+def reflect_chain_host(bvh: Dict[str, object], table: Sequence[PathObject], n_scene_tri: int, H: int, W: int, pixels, seeds, samples,
+                       max_depth: int, obj_nrm: Optional[np.ndarray] = None, records=None, fov_x_deg: float = 35.0) -> dict:
+    """`through_chain_host` for the chain that also passes the objects carrying OBJECT_PHOTO ("Reflected in
+    inserted objects"; `matpbr_path_reflect_chain_host`): the same lanes and outputs, `thr` now with the flagged vertices' BSDF weights.
+    `records`: `merge_objects`' PathObjectPbr records, needed where a flagged object is of kind BSDF_PBR.  On a table without the flag it
+    gives `through_chain_host`'s bits."""
+    pix = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+    sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), pix.shape))
+    smp = np.ascontiguousarray(np.broadcast_to(np.asarray(samples, dtype=np.int32), pix.shape))
+    tab, rec = _table_ptrs(table, records)
+    nrm = None if obj_nrm is None else np.ascontiguousarray(obj_nrm, dtype=np.float32)
+    N = pix.size
+    depth, texel = np.empty(N, np.int32), np.empty(N, np.int32)
+    thr, o, d = _out(N, 3, 3, 3)
+    _call("matpbr_path_reflect_chain_host", bvh["nodes"], bvh["tris"], int(H), int(W), float(fov_x_deg), int(max_depth), tab, len(table), nrm,
+          int(n_scene_tri), rec, pix, sd, smp, N, depth, texel, thr, o, d)
+    return {"depth": depth, "texel": texel, "thr": thr, "o": o, "d": d}
+
+
 def env_sample_host(tables: Dict[str, object], u: np.ndarray):
     """The render's emitter sampler on the CPU: u [N,4] -> (dir [N,3], pdf [N], texel [N] = row*We + col)."""
     U = _rows(u, 4)

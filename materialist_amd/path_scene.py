@@ -9,7 +9,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .path_abi import (BSDF_AREA, BSDF_DIELECTRIC, BSDF_DIFFUSE, BSDF_PBR, BSDF_ROUGH_DIELECTRIC, MAX_OBJECTS, MEDIUM_MAX_G, NODE_BYTES, OBJECT_COLORED,
-                       OBJECT_MEDIUM, OBJECT_SMOOTH, OBJECT_TEXTURED, PBR_DEFAULTS, PBR_MIN_ROUGHNESS, ROUGH_MIN_ALPHA, ROUGH_MIN_CONTRAST, TEXTURE_MAX_SIDE,
+                       OBJECT_MEDIUM, OBJECT_PHOTO, OBJECT_SMOOTH, OBJECT_TEXTURED, PBR_DEFAULTS, PBR_MIN_ROUGHNESS, ROUGH_MIN_ALPHA, ROUGH_MIN_CONTRAST, TEXTURE_MAX_SIDE,
                        TEXTURE_MAX_UV, TRI_BYTES, PathLights, PathObject, PathObjectMedium, PathObjectPbr, PathObjectTex, PathXform, _ptr, _ref, _table_ptrs,
                        _uncolored, check, load, symbol)
 
@@ -225,6 +225,25 @@ def object_medium(bsdf: dict) -> Optional[tuple]:
     return (*(float(x) for x in sa), ss, g)
 
 
+PHOTO_TYPES = ("diffuse", "pbr", "roughdielectric")
+
+
+def object_photo(ob: dict) -> bool:
+    """The "photo" key of an inserted object ("Reflected in inserted objects") -> whether the see-through chain
+    passes the object's vertices; False without the key.  ValueError for a value that is not a bool, and for True on an object whose
+    bsdf type is 'area' (it has no BSDF) or 'dielectric' (the see-through rule holds for it already)."""
+    photo = ob.get("photo") if isinstance(ob, dict) else None
+    if photo is None:
+        return False
+    if not isinstance(photo, (bool, np.bool_)):
+        raise ValueError(f"photo must be true or false, got {photo!r}")
+    kind = ob["bsdf"].get("type") if isinstance(ob.get("bsdf"), dict) else None
+    if photo and kind not in PHOTO_TYPES:
+        why = "has no BSDF" if kind == "area" else "is see-through already (see_through shows the photograph behind it)" if kind == "dielectric" else "takes none"
+        raise ValueError(f"photo: the photograph is reflected in a 'diffuse', a 'pbr' or a 'roughdielectric' object; a {kind!r} object {why} (drop 'photo')")
+    return bool(photo)
+
+
 def object_bsdf(bsdf: dict) -> tuple:
     """{"type": "dielectric", "int_ior", "ext_ior"} | {"type": "diffuse", "reflectance"} -> (kind, (p0, p1, p2));
     {"type": "pbr", "albedo": scalar or 3 values (0.8), "roughness" (0.5), "metallic" (0)} -> (BSDF_PBR, (a0, a1, a2, r, m));
@@ -431,6 +450,10 @@ def merge_scene(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[d
     for k, ob in enumerate(objects):
         bare, p = object_bsdf(ob.get("bsdf"))
         med = object_medium(ob.get("bsdf"))
+        try:
+            photo = object_photo(ob)
+        except ValueError as e:
+            raise ValueError(f"object {k}: {e}") from None
         media.append(PathObjectMedium((ctypes.c_float * 3)(*med[:3]), med[3], med[4]) if med is not None else PathObjectMedium())
         records.append(PathObjectPbr((ctypes.c_float * 3)(*p[:3]), p[3], p[4]) if bare == BSDF_PBR else PathObjectPbr())
         if bare == BSDF_PBR:
@@ -453,7 +476,7 @@ def merge_scene(vertices: np.ndarray, triangles: np.ndarray, objects: Sequence[d
         texels += images
         corner["uv"].append(_corner_uv(k, ob, Vo, To) if images else np.zeros((To.shape[0], 3, 2)))
         kind = bare | (OBJECT_SMOOTH if smooth else 0) | (OBJECT_COLORED if colored else 0) | (OBJECT_TEXTURED if images else 0) | \
-            (OBJECT_MEDIUM if med is not None else 0)
+            (OBJECT_MEDIUM if med is not None else 0) | (OBJECT_PHOTO if photo else 0)
         for key, one in zip(COUNT_KEYS, (smooth, bare == BSDF_PBR, bare == BSDF_AREA, bare == BSDF_ROUGH_DIELECTRIC, colored, bool(images))):
             counts[key] += one
         V.append(Vo)

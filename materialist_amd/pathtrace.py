@@ -13,7 +13,9 @@ from a photograph of the scene, forward only; `PathTracer.denoise_diff` is its o
 for the differential render"); `PathTracer.render_diff_through` is the differential render with the photograph shown, refracted,
 behind inserted clear glass ("Seen through glass"); `PathTracer.render_diff_ratio` and `composite_ratio` transfer the shadows as a
 ratio of the model's radiance with and without the objects ("Ratio shadow transfer").  A glass object may hold a homogeneous medium
-("Media inside glass"): `render` and the three differential renders then take the entries that know it.  There is no fallback: a missing or failing library raises.
+("Media inside glass"): `render` and the three differential renders then take the entries that know it.  A diffuse, pbr or
+roughdielectric object may carry "photo": True ("Reflected in inserted objects"): `render_diff_through` and `render_diff_ratio` with a
+photograph then show the photograph in what the object reflects.  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 
 from .path_abi import *      # noqa: F401,F403
-from .path_abi import _FEATURE, _P, _aligned_texels, _ptr, _ref, _rows, _same_rows, _table_ptrs, _tex_ptrs, _uncolored  # noqa: F401
+from .path_abi import _FEATURE, _P, _aligned_texels, _ptr, _ref, _rows, _same_rows, _table_ptrs, _tex_ptrs, _uncolored, _unflagged  # noqa: F401
 from .path_filters import *  # noqa: F401,F403
 from .path_host import *     # noqa: F401,F403
 from .path_host import _host_image  # noqa: F401
@@ -66,6 +68,9 @@ class PathTracer:
     behind the interface, chromatic absorption and grey scattering with a Henyey-Greenstein phase function, the coefficients per scene
     unit.  `move_objects` leaves them per scene unit, so an object scaled by s is optically s times thicker.  A dense medium of high
     albedo loses the energy of the paths that max_depth (16 at the most) cuts, as Mitsuba does at the same max_depth.
+    An object of bsdf type diffuse, pbr or roughdielectric may carry "photo": True ("Reflected in inserted
+    objects"; `stats["n_photo_objects"]` counts them): the camera chain of `render_diff_through` (and of `render_diff_ratio` with a
+    photograph) passes its vertices, so that the depth mesh it reflects is the photograph.  Every other method renders it as without the key.
     A tracer with objects renders forward only.  `movable=True` (with objects; DESIGN.md section 1.4, "Moving inserted
     objects"; `stats["movable"]`): the BVH is grafted, the depth mesh's subtree and the objects' under one root, and the objects' rest
     pose stays on the device, so that `move_objects` places them anew without a rebuild (two launches; well under a millisecond for a small mesh); `reach`: the largest coordinate magnitude any
@@ -90,6 +95,7 @@ class PathTracer:
         self.obj_col: Optional[torch.Tensor] = None   # corner colours of the inserted triangles, when some object is coloured
         self.textures = None                          # (obj_uv, PathObjectTex records, texels on the device), when some object is textured
         self.media = None                             # the PathObjectMedium records, when some glass object holds a medium
+        self.reflect = False                          # some object carries OBJECT_PHOTO: the see-through renders take the entry that knows it
         counts = dict.fromkeys(COUNT_KEYS, 0)
         if objects:
             scene = merge_scene(vertices, triangles, objects, lights=True, symbol=symbol)
@@ -103,6 +109,9 @@ class PathTracer:
                 for name in ("matpbr_path_render_objects_media", "matpbr_path_render_objects_diff_media"):
                     symbol(name)
                 self.media = (PathObjectMedium * len(scene.media))(*scene.media)
+            if any(t.kind & OBJECT_PHOTO for t in scene.table):
+                symbol("matpbr_path_render_objects_reflect")
+                self.reflect = True
             if scene.obj_col is not None:
                 symbol("matpbr_path_feature_colors")
                 self.obj_col = torch.from_numpy(scene.obj_col).to(self.device)
@@ -142,6 +151,7 @@ class PathTracer:
         self.stats["n_object_tris"] = self.stats["n_tris"] - n_scene
         self.stats.update(counts)
         self.stats["n_medium_objects"] = sum(1 for t in self.objects if t.kind & OBJECT_MEDIUM) if self.objects is not None else 0
+        self.stats["n_photo_objects"] = sum(1 for t in self.objects if t.kind & OBJECT_PHOTO) if self.objects is not None else 0
         self.stats["bytes"] = int(bvh["nodes"].nbytes + bvh["tris"].nbytes)
         self.nodes = torch.from_numpy(bvh["nodes"]).to(self.device)
         self.tris = torch.from_numpy(bvh["tris"]).to(self.device)
@@ -187,12 +197,14 @@ class PathTracer:
             raise ValueError(f"normal must be [{self.H},{self.W},3], got {tuple(nrm.shape)}")
         return nrm.to(self.device, torch.float32).contiguous()
 
-    def object_args(self) -> tuple:
+    def object_args(self, photo_flag: bool = False) -> tuple:
         """(table, n_objects, obj_nrm, n_scene_tri, records, lights header, light_tris, light_cdf, obj_col, obj_uv, texture records, texels,
         n_texels): the object arguments of a forward entry point after `stream`, as the C ABI takes them, None where the tracer has
         none.  An entry takes the first OBJECT_ENTRIES[its name] of them.  The last four are there on a tracer with a textured object
-        only, the one whose `render` takes the entry that reads them: a tracer without one returns the nine values it always has."""
-        table, records = _table_ptrs(self.objects, self.pbr)
+        only, the one whose `render` takes the entry that reads them: a tracer without one returns the nine values it always has.
+        `photo_flag`: the table with OBJECT_PHOTO where an object carries it, for matpbr_path_render_objects_reflect alone; every other
+        entry takes the table without it."""
+        table, records = _table_ptrs(self.objects if photo_flag else _unflagged(self.objects), self.pbr)
         head, ltris, lcdf = self.lights if self.lights is not None else (None, None, None)
         return (table, len(self.objects) if self.objects is not None else 0, _dptr(self.obj_nrm), self.n_scene_tris, records,
                 _ref(head) if head is not None else None, _dptr(ltris), _dptr(lcdf), _dptr(self.obj_col),
@@ -324,8 +336,13 @@ class PathTracer:
             entry = "matpbr_path_render_objects_diff_media"
             fn = symbol(entry)
             tail = (*(own or (None, None)), *(base or (None,)), self.media)
+        reflect = self.reflect and bool(own)          # a flagged object and a photograph: the one entry that sees the flag; nullable base and records
+        if reflect:
+            entry = "matpbr_path_render_objects_reflect"
+            fn = symbol(entry)
+            tail = (*own, *(base or (None,)), self.media)
         check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), _dptr(rays), torch.cuda.current_stream(dev).cuda_stream,
-                 *self.object_args()[:9], *self._texture_args(), *(ctypes.cast(x, _P) if isinstance(x, ctypes.Array) else _dptr(x) for x in (fg, delta, alpha, rewalked, *tail))), entry)
+                 *self.object_args(reflect)[:9], *self._texture_args(), *(ctypes.cast(x, _P) if isinstance(x, ctypes.Array) else _dptr(x) for x in (fg, delta, alpha, rewalked, *tail))), entry)
         return (fg, delta, *base, alpha, *own[1:], rewalked)
 
     @torch.no_grad()
@@ -340,7 +357,10 @@ class PathTracer:
         met one; nothing where it met none), and may be negative.  Rough glass, chains that end on another object, on a light, on the
         envmap or inside the glass at max_depth keep `render_diff`'s rule.  delta and alpha are `render_diff`'s bits; `rewalked`
         counts both kinds of second walk.  The picture is `composite(fg + through, delta, alpha, photo)`.  Every split into launches
-        gives the same bits.  A tracer without objects, or a photograph of another shape, raises ValueError."""
+        gives the same bits.  A tracer without objects, or a photograph of another shape, raises ValueError.  Where an object carries
+        "photo": True ("Reflected in inserted objects") the chain also passes its vertices, which are not delta:
+        fg then holds the light the chain itself gathered (emitter samples, the envmap, lights) besides the tail's difference, and
+        `through` the photograph weighted by the chain's BSDF weights, noisy where the object is rough."""
         return self._render_diff("matpbr_path_render_objects_through", (albedo, roughness, metallic, envmap), spp, max_depth, seed, spp_per_launch,
                                  tables, rays, photo)
 

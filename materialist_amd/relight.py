@@ -347,13 +347,15 @@ def load_oi_scene(path: str) -> List[dict]:
     "Moving inserted objects"); "medium" (a dielectric or roughdielectric object only) fills the glass with a homogeneous medium
     ("Media inside glass"): {"sigma_a": [r, g, b], "scatter": sigma_s, "g": g}, the coefficients per scene unit, or
     {"color": [r, g, b], "at": d, "scatter", "g"}, the colour in (0, 1] white light has after the distance d > 0 inside the object
-    (sigma_a = -ln(color) / d); it travels in the entry's "bsdf" as PathTracer takes it
+    (sigma_a = -ln(color) / d); it travels in the entry's "bsdf" as PathTracer takes it; "photo": true or false (a diffuse, pbr or
+    roughdielectric object only; DESIGN.md section 1.4, "Reflected in inserted objects") says whether `render_oi(reflect_photo=True)`
+    shows the photograph in what the object reflects (without the key the option decides)
     -> [{"ply": absolute path, "bsdf", "normals", "colors", "texture": absolute path or None, "orm_texture", "transform": the dict or
-    None, "motion"}], nothing read yet but the list.  ValueError naming
+    None, "motion", "photo": the bool or None}], nothing read yet but the list.  ValueError naming
     the file and the entry: unknown key, missing ply, bad bsdf, too many objects."""
     import json
 
-    from .pathtrace import object_bsdf, object_medium
+    from .pathtrace import object_bsdf, object_medium, object_photo
 
     try:
         with open(path) as f:
@@ -374,10 +376,10 @@ def load_oi_scene(path: str) -> List[dict]:
         where = f"{path}: objects[{k}]"
         if not isinstance(ob, dict):
             raise ValueError(f"{where} must be an object with 'ply' and 'bsdf'")
-        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors", "texture", "orm_texture", "transform", "motion", "medium"})
+        extra = sorted(set(ob) - {"ply", "bsdf", "normals", "colors", "texture", "orm_texture", "transform", "motion", "medium", "photo"})
         if extra:
             raise ValueError(f"{where}: unknown key {extra[0]!r} (known: 'ply', 'bsdf', 'normals', 'colors', 'texture', 'orm_texture', 'transform', "
-                             f"'motion', 'medium')")
+                             f"'motion', 'medium', 'photo')")
         if not isinstance(ob.get("ply"), str) or not ob["ply"]:
             raise ValueError(f"{where}: 'ply' must name a mesh file")
         ply = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(path)), ob["ply"]))
@@ -396,6 +398,13 @@ def load_oi_scene(path: str) -> List[dict]:
                 object_medium(bsdf)
             except (ValueError, TypeError) as e:
                 raise ValueError(f"{where}: bad medium: {e}") from None
+        if "photo" in ob:
+            try:
+                if ob["photo"] is None:
+                    raise ValueError("photo must be true or false, got None")
+                object_photo({"bsdf": bsdf, "photo": ob["photo"]})
+            except (ValueError, TypeError) as e:
+                raise ValueError(f"{where}: bad photo: {e}") from None
         normals = ob.get("normals", "flat")
         if normals not in ("flat", "vertex"):
             raise ValueError(f"{where}: 'normals' must be 'flat' or 'vertex', got {normals!r}")
@@ -423,7 +432,8 @@ def load_oi_scene(path: str) -> List[dict]:
             oi_pose(transform, motion, 1)
         except ValueError as e:
             raise ValueError(f"{where}: {e}") from None
-        out.append({"ply": ply, "bsdf": bsdf, "normals": normals, "colors": colors, **images, "transform": transform, "motion": motion})
+        out.append({"ply": ply, "bsdf": bsdf, "normals": normals, "colors": colors, **images, "transform": transform, "motion": motion,
+                    "photo": ob.get("photo")})
     return out
 
 
@@ -550,7 +560,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
               denoise: str = "off", objects_file: Optional[str] = None, env_scale: float = 1.0, object_colors: str = "none",
               object_texture: Optional[str] = None, composite: bool = False, photo_path: Optional[str] = None,
               composite_denoise: bool = False, see_through: bool = False, shadows: str = "additive", frames: int = 1, tint=None,
-              tint_at: Optional[float] = None):
+              tint_at: Optional[float] = None, reflect_photo: bool = False):
     """render_final.py:100-141,207-237,263-288: the scene with `<scene_dir>/oi.ply` inserted as acrylic glass (smooth dielectric,
     1.49 / 1.000277) and `<scene_dir>/oi2.ply` as a diffuse object of reflectance 0.8, path traced with `max_depth` 16 ->
     mi_oi_<name>_<env>.exr / .png.  Either mesh may be missing (the reference needs both); both missing is a FileNotFoundError.
@@ -600,7 +610,16 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     `render_rolling_envmap` returns.  `frames` > 1 without an `objects_file` in which an object moves is a ValueError.  `tint` (r, g, b in
     (0, 1]; without `objects_file`): oi.ply, the glass, holds an absorbing medium ("Media inside glass") that gives
     white light this colour after the distance `tint_at` (default: the largest side of the mesh's bounding box); an entry of
-    `objects_file` says "medium" itself, and with one `tint` is a ValueError, as is `tint_at` without `tint`."""
+    `objects_file` says "medium" itself, and with one `tint` is a ValueError, as is `tint_at` without `tint`.  `reflect_photo` (with
+    `composite`; it implies `see_through`; DESIGN.md section 1.4, "Reflected in inserted objects"): what a diffuse, pbr or roughdielectric
+    object reflects of the depth mesh is the photograph, not the re-rendered scene: every such object whose entry of `objects_file` does
+    not say "photo" itself carries "photo": True (of the default pair, oi2.ply), and `PathTracer.render_diff_through` /
+    `render_diff_ratio` follow the camera chain through its vertices.  With `composite_denoise` `through` by-passes the filter as it
+    does behind glass, so on a rough flagged object it carries its unfiltered noise.  Without `composite` it is a ValueError before any
+    other work; with `reflect_photo=False` and no entry that says "photo": true the code path, and so the bytes, are the ones without it."""
+    if reflect_photo and not composite:
+        raise ValueError("reflect_photo needs composite=True: it shows the photograph in what inserted objects reflect, in the differential composite")
+    see_through = see_through or reflect_photo
     if shadows not in OI_SHADOWS:
         raise ValueError(f"shadows must be 'additive' or 'ratio', got {shadows!r}")
     if shadows == "ratio" and not composite:
@@ -616,7 +635,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     placed = None                                       # per object (its "transform", its "motion"), with an object list
     if objects_file is not None:
         entries = load_oi_scene(objects_file)
-        have = [(e["ply"], e["bsdf"], e["normals"], e["colors"], e["texture"], e["orm_texture"]) for e in entries]
+        have = [(e["ply"], e["bsdf"], e["normals"], e["colors"], e["texture"], e["orm_texture"], e["photo"]) for e in entries]
         placed = [(e["transform"], e["motion"]) for e in entries]
     if frames > 1 and not (placed and any(_oi_moves(mo) for _, mo in placed)):
         raise ValueError(f"frames={frames} would render {frames} equal frames: give an objects_file in which an object has a \"motion\" "
@@ -637,7 +656,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
                 at = float((Vg.max(0) - Vg.min(0)).max())
             bsdfs[0]["medium"] = {"color": [float(x) for x in tint], "at": at}
             _pathtrace.object_medium(bsdfs[0])           # ValueError now, before any other work
-        have = [(p, b, object_normals, c, t, None) for p, b, c, t in zip(plys, bsdfs, ("none", object_colors), (None, object_texture))
+        have = [(p, b, object_normals, c, t, None, None) for p, b, c, t in zip(plys, bsdfs, ("none", object_colors), (None, object_texture))
                 if os.path.exists(p)]
         if not have:
             raise FileNotFoundError(f"object insertion needs {plys[0]} (glass) or {plys[1]} (diffuse); neither exists")
@@ -656,7 +675,7 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
     photo = _oi_photo(scene_dir, photo_path, atrous, env_scale) if composite else None
     env_path = find_envmap_oi(save_name, env_path, input_path)
     objects = []
-    for k, (p, b, normals, colors, texture, orm_texture) in enumerate(have):
+    for k, (p, b, normals, colors, texture, orm_texture, flagged) in enumerate(have):
         V, T, Nn, Cc, Uv = _mesh.read_ply_any(p, normals=True, colors=True, uv=True)
         if normals == "vertex" and Nn is None:
             Nn = _mesh.angle_weighted_normals(V, T)
@@ -669,6 +688,8 @@ def render_oi(save_name: str, env_path: Optional[str] = None, input_path: Option
                 V = _pathtrace.apply_similarity(sim, V)
                 Nn = None if Nn is None else _pathtrace.apply_similarity(sim, Nn, vectors=True)
         objects.append({"vertices": V, "triangles": T, "bsdf": b})
+        if flagged if flagged is not None else (reflect_photo and b.get("type") in _pathtrace.PHOTO_TYPES):
+            objects[-1]["photo"] = True
         if texture is not None or orm_texture is not None:
             objects[-1]["uv"] = _object_uv(p, Uv)
         if texture is not None:

@@ -71,6 +71,12 @@ def parse_args(argv=None):
                          "plus what the objects change in the light of the point seen, instead of the re-rendered fitted scene.  It does not "
                          "cover rough (frosted) glass, which stays re-rendered, nor paths that leave the glass towards another object, a "
                          "lamp or the envmap")
+    ap.add_argument("--oi_reflect_photo", action="store_true",
+                    help="--oi_composite (implies --oi_see_through): what an inserted diffuse, pbr or rough-glass object reflects of the scene "
+                         "is the photograph, not the re-rendered fitted scene: a chrome ball mirrors the room as photographed.  It holds for "
+                         "every such object whose --oi_scene entry does not say \"photo\": false (of the default pair, oi2.ply).  The "
+                         "photograph is taken as the light a point sends in every direction, and with --oi_composite_denoise the reflected "
+                         "photograph is not filtered")
     ap.add_argument("--oi_shadows", choices=["additive", "ratio"], default="additive",
                     help="--oi_composite: how what the objects darken reaches the photograph: additive = the model's difference is added "
                          "(the default); ratio = the photograph is dimmed, per channel, by the share of light the model loses, so a badly "
@@ -101,6 +107,8 @@ def parse_args(argv=None):
         ap.error("--oi_composite_denoise needs --oi_composite")
     if a.oi_see_through and not a.oi_composite:
         ap.error("--oi_see_through needs --oi_composite")
+    if a.oi_reflect_photo and not a.oi_composite:
+        ap.error("--oi_reflect_photo needs --oi_composite")
     if a.oi_shadows != "additive" and not a.oi_composite:
         ap.error("--oi_shadows ratio needs --oi_composite")
     if a.oi_composite_denoise and (a.spp < 2 or a.spp % 2):
@@ -147,7 +155,8 @@ def main(argv=None):
                                 **({"see_through": True} if a.oi_see_through else {}),
                                 **({"shadows": a.oi_shadows} if a.oi_shadows != "additive" else {}),
                                 **({"frames": a.oi_frames} if a.oi_frames != 1 else {}),
-                                **({"tint": a.oi_tint, "tint_at": a.oi_tint_at} if a.oi_tint is not None else {}))
+                                **({"tint": a.oi_tint, "tint_at": a.oi_tint_at} if a.oi_tint is not None else {}),
+                                **({"reflect_photo": True} if a.oi_reflect_photo else {}))
         if a.oi_frames > 1:
             print(f"Animation saved to {res['mp4']}\nIndividual frames saved to {res['animation_dir']}")
         else:
