@@ -805,6 +805,27 @@ int matpbr_path_reflect_chain_host(const void* nodes, const void* tris, int H, i
                                    const MatpbrPathObjectPbr* pbr, const int32_t* pixel, const uint32_t* seed, const int32_t* sample, long N,
                                    int32_t* depth, int32_t* texel, float* thr, float* o, float* d);
 
+/* ---- Material edits in the photograph ("Material edits in the photograph"): the differential render of edited
+ * maps; no inserted objects, the envmap the only emitter; forward only; added at version 3. */
+
+/* matpbr_path_render's arguments up to spp_per_launch (a, r, m: the fitted maps), rays and stream as there, then the edited maps
+ * a_e[H,W,3], r_e[H,W], m_e[H,W], mask[H,W] (uint8, non-zero = edited), nrm[H,W,3] (nullable: the shading-normal map of
+ * matpbr_path_render_normals, which is not edited), and the outputs delta[H,W,3], base[H,W,3], rewalked[H,W] (nullable, added to).
+ * Every pointer DEVICE.  Sample s of a pixel is walked as matpbr_path_render (matpbr_path_render_normals) walks it, but a vertex
+ * whose texel is masked reads its material from the edited maps; the first such read marks the sample touched.  A touched sample
+ * is walked again from the camera ray on, with the same random numbers, on the fitted maps alone.  delta = the mean over spp of
+ * (first walk - second walk) of the touched samples; base = the mean over spp of the radiance on the fitted maps of every sample,
+ * the second walk's or the only one's (no subtraction is performed for an untouched sample); rewalked counts the second walks.
+ * Where rewalked is 0, delta has all-zero bits.  base + delta is the edited scene's radiance.  The first walk samples by the edited
+ * maps, so the two walks may part at the first masked vertex.  The pictures are matpbr_path_composite (fg and alpha zero) and
+ * matpbr_path_composite_ratio.  Every split into launches gives the same bits.  Invalid arguments, besides matpbr_path_render's:
+ * a NULL edited map, mask, delta or base. */
+int matpbr_path_render_edit_diff(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                 float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                 int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                 const float* a_e, const float* r_e, const float* m_e, const uint8_t* mask, const float* nrm, float* delta,
+                                 float* base, uint32_t* rewalked);
+
 /* One segment inside a medium on the CPU, with the routine the kernel runs: the record `medium` (checked), per lane the traced
  * distance t[N] and u9[N] -> scattered[N] (1: the segment ends at a medium vertex), dist[N] (s there, else t), weight[N,3] =
  * expf(-sigma_a dist).  u9 is read only where sigma_s > 0. */

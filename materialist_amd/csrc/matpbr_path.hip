@@ -12,11 +12,12 @@
 // kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
 // path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser; path_diff.hpp the differential render's table
 // and the composite; path_media.hpp the media inside glass objects; path_move.hpp the grafted BVH's move and refit of the inserted objects;
-// path_reflect.hpp the see-through tables whose chain passes flagged objects.
+// path_reflect.hpp the see-through tables whose chain passes flagged objects; path_mapedit.hpp the table of the walk over edited maps.
 #include <type_traits>
 
 #include "path_denoise.hpp"
 #include "path_diff.hpp"
+#include "path_mapedit.hpp"
 #include "path_media.hpp"
 #include "path_move.hpp"
 #include "path_reflect.hpp"
@@ -89,7 +90,13 @@ __device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second
 // section 1.4, "Reflected in inserted objects").  Such a vertex is not delta: its emitter sample stays in the sample's radiance.  At the
 // landing trip 0 commits the radiance gathered so far, the chain's, to fg and starts L afresh, so that Lw is the tail's as it is along
 // a dielectric chain; trip 1 replays the chain without emitter samples below `land`, so that its L is the tail's as well.  Read off the
-// table's type (ReflectTraits); every `if (REFLECT ...)` folds away in the twenty kernels without it.
+// table's type (ReflectTraits); every `if (REFLECT ...)` folds away in the twenty kernels without it.  MAPEDIT: the depth mesh's walk, or
+// NRM's, over edited maps (Objects = MapEdit<NoObjects>, MapEdit<ShadeNormals>; DESIGN.md section 1.4, "Material edits in the
+// photograph"), with DIFF's two trips and none of its tables.  Trip 0 reads the edited maps where the texel a vertex reads is masked and
+// records the first such read in `touched`; trip 1 runs where touched: the same sample from the camera ray on, on the fitted maps
+// alone.  delta takes trip 0 minus trip 1; the radiance on the fitted maps, trip 1's or the only trip's, takes the render's own sum
+// (`acc`, q.out).  Nothing of trip 0 but Lw and touched reaches trip 1.  Read off the table's type (MapEditTraits); every
+// `if (MAPEDIT ...)` folds away in every kernel without it.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
     constexpr bool THROUGH = DiffTraits<Objects>::through;
@@ -97,6 +104,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     constexpr bool BASE = DiffTraits<Objects>::base;
     constexpr bool MEDIUM = MediumTraits<Objects>::medium;
     constexpr bool REFLECT = ReflectTraits<Objects>::reflect;
+    constexpr bool MAPEDIT = MapEditTraits<Objects>::mapedit;
     constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF || MEDIUM;
     constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
@@ -105,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value || PBR;
     constexpr bool OBJ = std::is_same<Objects, ObjTable>::value || SMOOTH;
     constexpr bool EDIT = std::is_same<Objects, TransEdit>::value;
-    constexpr bool NRM = std::is_same<Objects, ShadeNormals>::value;
+    constexpr bool NRM = std::is_same<Objects, ShadeNormals>::value || std::is_same<Objects, MapEdit<ShadeNormals>>::value;
     __shared__ int s_stack[kStack * kBlock];
     const int tid = threadIdx.y * kTileX + threadIdx.x;
     const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
@@ -117,7 +125,17 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     if constexpr (LIGHT) n_e = (have_tab ? 1 : 0) + ot.lt.n;
     float n_ef = (float)n_e;
     float acc[3] = {0.0f, 0.0f, 0.0f};
-    if constexpr (DIFF) {
+    float dacc[3] = {0.0f, 0.0f, 0.0f};   // (MAPEDIT) delta's sum, in registers within a launch as acc is
+    uint32_t n_second = 0;                // (MAPEDIT) second walks of this launch
+    if constexpr (MAPEDIT) {
+        if (!first) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                acc[c] = q.out[3 * pix + c];
+                dacc[c] = ot.delta[3 * pix + c];
+            }
+        }
+    } else if constexpr (DIFF) {
         if (first) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) ot.fg[3 * pix + c] = ot.delta[3 * pix + c] = 0.0f;
@@ -156,6 +174,9 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             }
             n_e = (have_tab ? 1 : 0) + (second ? 0 : ot.lt.n);   // trip 1: the envmap alone
             n_ef = (float)n_e;
+        }
+        if constexpr (MAPEDIT) {
+            if (!second) touched = false;
         }
         float L[3] = {0.0f, 0.0f, 0.0f}, thr[3] = {1.0f, 1.0f, 1.0f};
         // camera ray through a uniformly jittered position of the pixel (box filter)
@@ -333,7 +354,17 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             const float sx = (ndc0 + 1.0f) * 0.5f * (float)q.W, sy = (ndc1 + 1.0f) * 0.5f * (float)q.H;
             const int tx = (int)fminf(fmaxf(floorf(sx), 0.0f), (float)(q.W - 1)), ty = (int)fminf(fmaxf(floorf(sy), 0.0f), (float)(q.H - 1));
             const long tp = OBJ && kind != 0 ? 0 : (long)ty * q.W + tx;   // an object reads no texel
-            float av[3] = {q.a[3 * tp], q.a[3 * tp + 1], q.a[3 * tp + 2]}, rv = q.r[tp], mv = q.m[tp];
+            float av[3] = {0.0f, 0.0f, 0.0f}, rv = 0.0f, mv = 0.0f;
+            if constexpr (MAPEDIT) {   // trip 0 reads the edited maps at a masked texel; the first such read asks for trip 1
+                const bool edited = !second && ot.mask[tp] != 0;
+                touched = touched || edited;
+                const float *pa = edited ? ot.a_e : q.a, *pr = edited ? ot.r_e : q.r, *pm = edited ? ot.m_e : q.m;
+                av[0] = pa[3 * tp]; av[1] = pa[3 * tp + 1]; av[2] = pa[3 * tp + 2];
+                rv = pr[tp]; mv = pm[tp];
+            } else {
+                av[0] = q.a[3 * tp]; av[1] = q.a[3 * tp + 1]; av[2] = q.a[3 * tp + 2];
+                rv = q.r[tp]; mv = q.m[tp];
+            }
             const bool pbr = PBR && kind == MATPBR_PATH_BSDF_PBR;   // (PBR) the depth mesh's branch on the object's constants
             if constexpr (PBR) {
                 if (pbr) { av[0] = oa[0]; av[1] = oa[1]; av[2] = oa[2]; rv = o_r; mv = o_m; }
@@ -566,6 +597,22 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 }
             }
             second = false;
+        } else if constexpr (MAPEDIT) {
+            if (!second && touched) {   // the same s once more, on the fitted maps
+#pragma unroll
+                for (int c = 0; c < 3; ++c) Lw[c] = L[c];
+                second = true;
+                --s;
+                continue;
+            }
+            if (second) {   // an untouched sample adds nothing: no subtraction
+#pragma unroll
+                for (int c = 0; c < 3; ++c) dacc[c] += Lw[c] - L[c];
+                ++n_second;
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += L[c];   // the fitted maps' radiance: trip 1's, or the only trip's, which read no edited texel
+            second = false;
         } else {
 #pragma unroll
             for (int c = 0; c < 3; ++c) acc[c] += L[c];
@@ -586,6 +633,11 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) q.out[3 * pix + c] = last ? acc[c] * sc : acc[c];
+    }
+    if constexpr (MAPEDIT) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ot.delta[3 * pix + c] = last ? dacc[c] * sc : dacc[c];
+        if (ot.rewalked) ot.rewalked[pix] += n_second;
     }
     if (q.rays) q.rays[pix] += n_rays;
 }
@@ -2021,6 +2073,26 @@ int matpbr_path_render_normals(const void* nodes, const void* tris, const float*
     s.kernel = nrm ? Kernel::ShadeNormals : Kernel::NoObjects;
     s.nrm = nrm;
     return render_common(RENDER_FRAME, s);
+}
+
+int matpbr_path_render_edit_diff(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                                 float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                                 int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                                 const float* a_e, const float* r_e, const float* m_e, const uint8_t* mask, const float* nrm, float* delta,
+                                 float* base, uint32_t* rewalked) {
+    float* const out = base;   // the radiance on the fitted maps is the render's own sum
+    const Frame f = RENDER_FRAME;
+    PathArgs q{};
+    if (!a_e || !r_e || !m_e || !mask || !delta || !base || !frame_args(f, q)) return MATPBR_PATH_ERR_INVALID_ARG;
+    if (nrm) {
+        MapEdit<ShadeNormals> t{};
+        t.nrm = nrm;
+        t.a_e = a_e; t.r_e = r_e; t.m_e = m_e; t.mask = mask; t.delta = delta; t.rewalked = rewalked;
+        return launch_frame(f, q, t);
+    }
+    MapEdit<NoObjects> t{};
+    t.a_e = a_e; t.r_e = r_e; t.m_e = m_e; t.mask = mask; t.delta = delta; t.rewalked = rewalked;
+    return launch_frame(f, q, t);
 }
 
 int matpbr_path_eval_normal_grad_host(const float* n, const float* wo, const float* wi, const float* a, const float* r, const float* m,

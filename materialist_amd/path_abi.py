@@ -129,6 +129,7 @@ SIGNATURES = {
     "matpbr_path_render_objects_reflect": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 8),
     "matpbr_path_reflect_chain_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P,
                                                       ctypes.c_long] + [_P] * 5),
+    "matpbr_path_render_edit_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P] * 8),
     "matpbr_path_medium_segment_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_phase_sample_host": (ctypes.c_int, [ctypes.c_float, _P, _P, ctypes.c_long, _P]),
     "matpbr_path_composite_ratio": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
@@ -213,6 +214,10 @@ MEDIUM_FEATURE = "media inside glass objects"
 # as well: a fifth group beside them
 REFLECT_SYMBOLS = ("matpbr_path_render_objects_reflect", "matpbr_path_reflect_chain_host")
 REFLECT_FEATURE = "the photograph reflected in inserted objects"
+# the symbol of material edits in the photograph ("Material edits in the photograph"), added at version 3 as well: a
+# sixth group beside them
+MAPEDIT_SYMBOLS = ("matpbr_path_render_edit_diff",)
+MAPEDIT_FEATURE = "material edits in the photograph"
 # the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
 OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
                   "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
@@ -235,7 +240,8 @@ def load() -> ctypes.CDLL:
         _build.build_path_library()
         lib = ctypes.CDLL(_build.PATH_LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS or name in MEDIUM_SYMBOLS or name in REFLECT_SYMBOLS) and not hasattr(lib, name):
+            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS or name in MEDIUM_SYMBOLS or name in REFLECT_SYMBOLS or
+                    name in MAPEDIT_SYMBOLS) and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -250,7 +256,8 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
         what = (RATIO_FEATURE if name in RATIO_SYMBOLS else MOVE_FEATURE if name in MOVE_SYMBOLS else MEDIUM_FEATURE if name in MEDIUM_SYMBOLS
-                else REFLECT_FEATURE if name in REFLECT_SYMBOLS else _FEATURE.get(name, "smooth inserted objects"))
+                else REFLECT_FEATURE if name in REFLECT_SYMBOLS else MAPEDIT_FEATURE if name in MAPEDIT_SYMBOLS
+                else _FEATURE.get(name, "smooth inserted objects"))
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 

@@ -1,5 +1,5 @@
 """The image-space steps around the path render: the a-trous denoiser ("Denoiser"), the differential render's
-composite ("Differential render", "Ratio shadow transfer") and its own denoiser ("Denoiser for the differential render").  Each step is written once, over a
+composite ("Differential render", "Ratio shadow transfer", "Material edits in the photograph") and its own denoiser ("Denoiser for the differential render").  Each step is written once, over a
 side: `_HOST` runs it on numpy arrays through the library's `*_host` entry (the routine the kernel runs, for the tests), `_Device`
 on torch tensors through the kernel on the current torch stream.  The public `NAME_host` and `NAME` are the two calls of that body."""
 from itertools import chain
@@ -213,6 +213,33 @@ def composite_ratio(fg, delta, base, alpha, photo, scale: float = 1.0) -> torch.
     scale) photo) g); elsewhere the channel carries `composite`'s bits.  Where fg, delta and alpha are 0 the photograph (>= 0) comes
     through bit for bit."""
     return _composite(_Device(fg, delta, base, alpha, photo), fg, delta, alpha, photo, scale, _ratio_base(base))
+
+
+def _composite_edit(side, zeros, delta, photo, base):
+    """`composite` (with `base`, `composite_ratio`) of a differential render without inserted objects: fg and alpha are zeros of the
+    photograph's frame, made by `zeros(shape)` once every shape is known to be right."""
+    shp = tuple(side.raw(photo).shape)
+    if len(shp) != 3 or shp[2] != 3 or shp[0] < 1 or shp[1] < 1:
+        raise ValueError(f"photo must be [H,W,3], got {list(shp)}")
+    for x, what in ((delta, "delta"), (base, "base")):
+        if x is not None and tuple(side.raw(x).shape) != shp:
+            raise ValueError(f"{what} must be {list(shp)}, got {list(side.raw(x).shape)}")
+    return _composite(side, zeros(shp), delta, zeros(shp[:2]), photo, 1.0, base)
+
+
+def composite_edit_host(delta, photo, base=None) -> np.ndarray:
+    """`composite_edit` on the CPU with the routines the kernels run -> [H,W,3], the same bits."""
+    return _composite_edit(_HOST, lambda s: np.zeros(s, np.float32), delta, photo, base)
+
+
+@torch.no_grad()
+def composite_edit(delta, photo, base=None) -> torch.Tensor:
+    """`PathTracer.render_edit_diff`'s outputs composited into the photograph ("Material edits in the
+    photograph"), on the device: `composite` with fg and alpha zero, max(0, photo + delta) (additive); with `base`, `composite_ratio`
+    with them zero: where the edit darkens a channel (delta < 0 < base) the photograph is multiplied by max(0, base + delta) / base, so
+    the fit's albedo cancels.  Where delta is 0 the photograph (>= 0) comes through bit for bit."""
+    where = (delta, photo) if base is None else (delta, photo, base)
+    return _composite_edit(_Device(*where), lambda s: torch.zeros(s, dtype=torch.float32, device=_device_of(*where)), delta, photo, base)
 
 
 # ---- the differential render's denoiser (DESIGN.md section 1.4, "Denoiser for the differential render") ----------------------------------

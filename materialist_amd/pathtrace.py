@@ -15,7 +15,9 @@ behind inserted clear glass ("Seen through glass"); `PathTracer.render_diff_rati
 ratio of the model's radiance with and without the objects ("Ratio shadow transfer").  A glass object may hold a homogeneous medium
 ("Media inside glass"): `render` and the three differential renders then take the entries that know it.  A diffuse, pbr or
 roughdielectric object may carry "photo": True ("Reflected in inserted objects"): `render_diff_through` and `render_diff_ratio` with a
-photograph then show the photograph in what the object reflects.  There is no fallback: a missing or failing library raises.
+photograph then show the photograph in what the object reflects.  `PathTracer.render_edit_diff`, `edit_mask` and `composite_edit`
+put a material edit into the photograph ("Material edits in the photograph"): the differential render of edited maps on a tracer
+without objects.  There is no fallback: a missing or failing library raises.
 """
 from __future__ import annotations
 
@@ -42,6 +44,21 @@ _OBJECT_ROUTES = (("textures", "matpbr_path_render_objects_textures"), ("obj_col
 
 def _dptr(t):
     return t.data_ptr() if t is not None else None
+
+
+def edit_mask(fitted, edited) -> torch.Tensor:
+    """bool [H,W]: the texels where the maps `edited` = (a_e, r_e, m_e) differ from `fitted` = (a, r, m) in the bits of any of their five
+    float32 values (albedo [H,W,3], roughness and metallic [H,W] or [H,W,1]; tensors or arrays), on the device of `fitted`'s albedo.
+    Bitwise, so -0.0 differs from 0.0 and a NaN equals itself: a texel is masked exactly where a walk could read another value."""
+    a = torch.as_tensor(fitted[0])
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise ValueError(f"albedo must be [H,W,3], got {tuple(a.shape)}")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    out = torch.zeros(H, W, dtype=torch.bool, device=a.device)
+    for x, y, c in zip(fitted, edited, (3, 1, 1)):
+        x, y = (torch.as_tensor(t).to(a.device, torch.float32).reshape(H, W, c).contiguous().view(torch.int32) for t in (x, y))
+        out |= (x != y).any(-1)
+    return out
 
 
 class PathTracer:
@@ -377,6 +394,39 @@ class PathTracer:
         gives the same bits.  A tracer without objects, or a photograph of another shape, raises ValueError."""
         return self._render_diff("matpbr_path_render_objects_ratio", (albedo, roughness, metallic, envmap), spp, max_depth, seed, spp_per_launch,
                                  tables, rays, photo, ratio=True)
+
+    @torch.no_grad()
+    def render_edit_diff(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, edited, mask=None, spp: int = 64,
+                         max_depth: int = 4, seed: int = 0, spp_per_launch: int = 8, tables: Optional[tuple] = None,
+                         rays: Optional[torch.Tensor] = None, normal=None) -> tuple:
+        """The differential render of edited maps ("Material edits in the photograph") with `render`'s arguments
+        and random numbers -> (delta [H,W,3], base [H,W,3], rewalked [H,W] int32) on the device, the first two means over `spp`.
+        albedo, roughness, metallic: the fitted maps; `edited` = (a_e, r_e, m_e): the edited ones; `mask` [H,W] (non-zero = edited):
+        where a vertex reads the edited maps, by default `edit_mask` of the two, the texels any of whose five floats differs.  A sample
+        is walked on the edited maps inside the mask; where it read a masked texel it is walked again on the fitted maps alone, and
+        delta takes the difference (`rewalked` counts those samples).  base: the fitted scene's radiance of every sample; base + delta:
+        the edited scene's.  Where rewalked is 0, delta is exactly 0.  `composite_edit` puts them into a photograph.  `normal`: the
+        shading-normal map of `render`, which is not edited.  Every split into launches gives the same bits.  A tracer with objects
+        raises ValueError."""
+        if self.objects is not None:
+            raise ValueError("render_edit_diff knows no inserted objects: build the PathTracer without `objects`")
+        if edited is None or len(edited) != 3:
+            raise ValueError("edited must be the three edited maps (albedo, roughness, metallic)")
+        H, W, dev = self.H, self.W, self.device
+        if mask is not None and tuple(torch.as_tensor(mask).shape) != (H, W):
+            raise ValueError(f"mask must be [{H},{W}], got {tuple(torch.as_tensor(mask).shape)}")
+        fn = symbol("matpbr_path_render_edit_diff")
+        nrm = self._normal(normal, "render_edit_diff") if normal is not None else None
+        inputs = self._inputs(albedo, roughness, metallic, envmap, tables)
+        ae, re, me = (torch.as_tensor(x).to(dev, torch.float32).reshape(H, W, c).contiguous() for x, c in zip(edited, (3, 1, 1)))
+        mk = edit_mask(inputs[:3], (ae, re, me)) if mask is None else torch.as_tensor(mask) != 0
+        mk = mk.to(dev, torch.uint8).contiguous()
+        delta, base = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+        rewalked = torch.zeros(H, W, device=dev, dtype=torch.int32)
+        check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), _dptr(rays), torch.cuda.current_stream(dev).cuda_stream,
+                 ae.data_ptr(), re.data_ptr(), me.data_ptr(), mk.data_ptr(), _dptr(nrm), delta.data_ptr(), base.data_ptr(), rewalked.data_ptr()),
+              "matpbr_path_render_edit_diff")
+        return delta, base, rewalked
 
     def _first_hit(self, entry: str, channels: int, hidden: int, *own) -> torch.Tensor:
         """[H,W,channels] on the device from the first-hit entry `entry`: it takes the BVH, the camera, the table without the flags

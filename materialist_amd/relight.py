@@ -200,6 +200,14 @@ def _path_tracer(scene_dir: str, save_name: str, mat: Dict[str, torch.Tensor], d
     return PathTracer(V, T, H, W, DEFAULT_FOV, device=device, objects=objects, **movable)
 
 
+def edit_mask(fitted, edited) -> torch.Tensor:
+    """bool [H,W]: the texels where the edited maps (a_e, r_e, m_e) differ from the fitted ones (a, r, m) in the bits of any of their five
+    floats: the mask `PathTracer.render_edit_diff` derives when it is given none (`pathtrace.edit_mask`)."""
+    from .pathtrace import edit_mask as _edit_mask
+
+    return _edit_mask(fitted, edited)
+
+
 def _check_integrator(integrator: str, shading_normals: str = "face") -> None:
     if integrator not in ("sh", "path"):
         raise ValueError(f"integrator must be 'sh' or 'path', got {integrator!r}")
@@ -272,20 +280,44 @@ def _denoised(pt, render_half, iters: int, seed: int, geom: torch.Tensor, guide:
 
 def render_real(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
                 spp: int = 64, device="cuda", edit: Optional[Dict[str, object]] = None, integrator: str = "sh", max_depth: int = 4,
-                seed: int = 0, shading_normals: str = "face", denoise: str = "off", env_scale: float = 1.0) -> str:
+                seed: int = 0, shading_normals: str = "face", denoise: str = "off", env_scale: float = 1.0, composite: bool = False,
+                photo_path: Optional[str] = None, transfer: str = "additive") -> str:
     """render_final.py:148-203,241-260: one re-render under `env_path` -> mi_<name>_<env>_<edit flag>.exr / .png.
     integrator "sh": the deterministic render (SH25 light, direct, unshadowed); "path": the path tracer, `max_depth` / `seed`, shading
     with the mesh's face normals or, with `shading_normals="map"`, with best_results/normal.exr whatever the scene is called.
     `denoise="atrous"` (path only, even `spp`): two renders of spp / 2, seeds `seed` and `seed + 1`, through the a-trous filter.
-    `env_scale` (path only): the envmap is multiplied by it before its tables are built; 1 gives the same bits as without it."""
+    `env_scale` (path only): the envmap is multiplied by it before its tables are built; 1 gives the same bits as without it.
+    `composite=True` ("Material edits in the photograph"; path only, with an edit, env_scale 1, denoise "off"):
+    the photograph (`photo_path`, default <scene>/gt_image.exr, as `render_oi` reads it) with what the edit changes, not a re-render of
+    the fitted scene: pixels no edited texel reaches keep the photograph's bits -> mi_ec_<name>_<env>_<edit flag>.exr / .png.
+    `transfer`: "additive" adds the model's difference; "ratio" dims the photograph, per channel, by the share of light the model
+    loses where the edit darkens it, so that the fit's albedo cancels."""
     _check_integrator(integrator, shading_normals)
     _scaled_env(np.zeros(0, np.float32), env_scale, integrator)
     atrous = _check_denoise(denoise, integrator, spp)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
+    if transfer not in ("additive", "ratio"):
+        raise ValueError(f"transfer must be 'additive' or 'ratio', got {transfer!r}")
+    if not composite and (photo_path is not None or transfer != "additive"):
+        raise ValueError("photo_path and transfer need composite=True")
+    if composite:
+        if integrator != "path":
+            raise ValueError("composite needs integrator='path': the differential render of edited maps is the path tracer's")
+        if not any((edit or {}).get(key) is not None for key in ("albedo", "roughness", "metallic")):
+            raise ValueError("composite needs an edit (albedo, roughness or metallic): without one the picture is the photograph")
+        photo = _oi_photo(scene_dir, photo_path, atrous, env_scale)
     env_path = find_envmap(save_name, env_path, input_path)
     mat = load_estimated_brdf(os.path.join(scene_dir, "best_results"), device)
+    fitted = tuple(mat[key].clone() for key in ("albedo", "roughness", "metallic")) if composite else None
     edit_flag = apply_edit(mat, edit)
-    if atrous:
+    if composite:
+        from .pathtrace import composite_edit
+
+        delta, fit, _ = _path_tracer(scene_dir, save_name, mat, device).render_edit_diff(
+            *fitted, load_image(env_path), (mat["albedo"], mat["roughness"], mat["metallic"]), None, spp, max_depth, seed,
+            normal=mat["normal"] if shading_normals == "map" else None)
+        img = composite_edit(delta, torch.from_numpy(photo).to(delta.device), fit if transfer == "ratio" else None)
+    elif atrous:
         pt = _path_tracer(scene_dir, save_name, mat, device)
         nrm = mat["normal"] if shading_normals == "map" else None
         env = _scaled_env(load_image(env_path), env_scale)
@@ -303,7 +335,7 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
     env_id = os.path.basename(env_path)[:-4]
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
-    base = os.path.join(out_dir, f"mi_{save_name}_{env_id}_{edit_flag}")   # (:199-202)
+    base = os.path.join(out_dir, f"mi_{'ec_' if composite else ''}{save_name}_{env_id}_{edit_flag}")   # (:199-202)
     write_exr(base + ".exr", img.cpu().numpy())
     write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
     return base + ".png"

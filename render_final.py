@@ -22,6 +22,16 @@ def parse_args(argv=None):
                     help="HSV shift of the albedo inside best_results/mask.png (the reference's `edit` dict, hard-wired to None in its CLI)")
     ap.add_argument("--edit_roughness", type=float, default=None, help="constant roughness inside the mask")
     ap.add_argument("--edit_metallic", type=float, default=None, help="constant metallic inside the mask")
+    ap.add_argument("--edit_composite", action="store_true",
+                    help="--mode real --integrator path with an --edit_*: differential rendering of the edit: the photograph with what the "
+                         "edited maps change, inter-reflection included, not a re-render of the fitted scene; pixels no edited texel reaches "
+                         "keep the photograph's bits.  Writes mi_ec_<name>_<env>_<edit flag>.exr / .png.  Not with --denoise atrous or an "
+                         "--env_scale other than 1")
+    ap.add_argument("--edit_photo", type=str, default=None, metavar="PATH",
+                    help="--edit_composite: the photograph, of the maps' size (default <scene>/gt_image.exr, linear; a .png holds display values)")
+    ap.add_argument("--edit_transfer", choices=["additive", "ratio"], default=None,
+                    help="--edit_composite: additive (the default) = the model's difference is added to the photograph; ratio = where the edit "
+                         "darkens a channel the photograph is dimmed by the share of light the model loses, so a badly fitted albedo cancels")
     ap.add_argument("--integrator", choices=("sh", "path"), default="sh",
                     help="sh: the deterministic render (direct light under SH25, no shadows); path: the path tracer on the scene's .ply "
                          "(Mitsuba's `path` as the reference renders its final images: shadows, inter-reflection, the envmap's texels); "
@@ -115,6 +125,21 @@ def parse_args(argv=None):
         ap.error("--oi_composite_denoise splits every frame into two halves of spp/2 samples: --spp must be even")
     if a.oi_composite and a.env_scale != 1.0:
         ap.error("--oi_composite needs --env_scale 1: the photograph was taken under the envmap as it is and is not dimmed")
+    if a.edit_composite and a.mode != "real":
+        ap.error("--edit_composite needs --mode real (--mode oi composites inserted objects with --oi_composite; a rolling envmap relights "
+                 "every pixel, which is no edit)")
+    if a.edit_composite and a.integrator != "path":
+        ap.error("--edit_composite needs --integrator path")
+    if a.edit_composite and a.edit_albedo is None and a.edit_roughness is None and a.edit_metallic is None:
+        ap.error("--edit_composite needs an edit: --edit_albedo, --edit_roughness or --edit_metallic")
+    if a.edit_composite and a.denoise == "atrous":
+        ap.error("--edit_composite knows no --denoise atrous: the filter takes a radiance image, not a signed difference")
+    if a.edit_composite and a.env_scale != 1.0:
+        ap.error("--edit_composite needs --env_scale 1: the photograph was taken under the envmap as it is and is not dimmed")
+    if a.edit_photo is not None and not a.edit_composite:
+        ap.error("--edit_photo needs --edit_composite")
+    if a.edit_transfer is not None and not a.edit_composite:
+        ap.error("--edit_transfer needs --edit_composite")
     if a.oi_tint is not None and (a.mode != "oi" or a.oi_scene is not None):
         ap.error("--oi_tint needs --mode oi without --oi_scene (an --oi_scene entry says \"medium\" itself)")
     if a.oi_tint is not None and not all(0 < c <= 1 for c in a.oi_tint):
@@ -141,7 +166,8 @@ def main(argv=None):
     it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed, "shading_normals": a.shading_normals, "denoise": a.denoise,
           "env_scale": a.env_scale}
     if a.mode == "real":
-        print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it))
+        ec = {"composite": True, "photo_path": a.edit_photo, "transfer": a.edit_transfer or "additive"} if a.edit_composite else {}
+        print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it, **ec))
     elif a.mode == "rolling":
         res = relight.render_rolling_envmap(a.save_name, a.env_path, a.frames, a.rotation_step, a.input_path, a.save_path, a.spp, edit=edit,
                                             **it)
