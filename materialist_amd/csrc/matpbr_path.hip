@@ -1102,17 +1102,39 @@ bool textures_valid(const MatpbrPathObject* objects, int n_objects, const float*
     return true;
 }
 
-// The table of an entry point that knows n_scene_tri, with the rules those entries share: n_scene_tri an int32 >= 0, no range starts
-// below it, and corner normals are given where an object is smooth.
-bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept, const float* obj_nrm, long n_scene_tri,
-                 const MatpbrPathObjectPbr* pbr, ObjTable& ot, ObjCounts& n) {
-    if (!object_table(objects, n_objects, accept, pbr, ot, &n) || n_scene_tri < 0 || n_scene_tri > INT32_MAX || (n.smooth > 0 && !obj_nrm)) return false;
+// n_scene_tri against a checked table: an int32 >= 0, and no range starts below it
+bool ranges_above(const MatpbrPathObject* objects, int n_objects, long n_scene_tri) {
+    if (n_scene_tri < 0 || n_scene_tri > INT32_MAX) return false;
     for (int k = 0; k < n_objects; ++k)
         if (objects[k].first_tri < n_scene_tri) return false;
     return true;
 }
+// The table of an entry point that knows n_scene_tri, with the rules those entries share: n_scene_tri as `ranges_above` has it, and
+// corner normals are given where an object is smooth.
+bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept, const float* obj_nrm, long n_scene_tri,
+                 const MatpbrPathObjectPbr* pbr, ObjTable& ot, ObjCounts& n) {
+    return object_table(objects, n_objects, accept, pbr, ot, &n) && ranges_above(objects, n_objects, n_scene_tri) && !(n.smooth > 0 && !obj_nrm);
+}
 
-// The eight object entries are the eight levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
+// the object arguments of an entry point, as the C ABI receives them and in its order: an entry leaves what it does not have null / 0
+struct ObjectArgs {
+    const MatpbrPathObject* objects;
+    int n_objects;
+    const float* obj_nrm = nullptr;
+    long n_scene_tri = 0;
+    const MatpbrPathObjectPbr* pbr = nullptr;
+    const MatpbrPathLights* lights = nullptr;
+    const void* light_tris = nullptr;
+    const float* light_cdf = nullptr;
+    const float* obj_col = nullptr;
+    const float* obj_uv = nullptr;
+    const MatpbrPathObjectTex* tex = nullptr;
+    const void* texels = nullptr;
+    long n_texels = 0;
+    const MatpbrPathObjectMedium* media = nullptr;
+};
+
+// The nine object entries are the nine levels of this one rule (the table in DESIGN.md section 1.4, "The object entries"): level 1
 // admits kinds 1 and 2, level 2 the smooth flag on them, level 3 kind 3, level 4 kind 4, level 5 kind 5, level 6 the colour flag on
 // kinds 2 and 3 (obj_col is consulted where an object carries it), level 7 the texture flag on them (obj_uv, tex and texels are consulted
 // where an object carries it, and its record is checked against n_texels), level 8 the medium flag on kinds 1 and 5 (media is consulted
@@ -1121,10 +1143,8 @@ bool scene_table(const MatpbrPathObject* objects, int n_objects, unsigned accept
 // the arguments it does not have; level 1's n_scene_tri = 0 lies below every range.  An argument is consulted only where the table needs
 // it: obj_nrm where an object is smooth, pbr where one is of kind 3, the light header and buffers where one is of kind 4.  The counts
 // alone choose the kernel.
-bool objects_scene(int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
-                   const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
-                   const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex, const void* texels, long n_texels, Scene& s,
-                   const MatpbrPathObjectMedium* media = nullptr) {
+bool objects_scene(int level, const ObjectArgs& o, Scene& s) {
+    const auto [objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, media] = o;
     const unsigned accept = (level >= 2 ? kAcceptSmooth : 0u) | (level >= 3 ? kAcceptPbr : 0u) | (level >= 4 ? kAcceptLight : 0u) |
                             (level >= 5 ? kAcceptRough : 0u) | (level >= 6 ? kAcceptColor : 0u) | (level >= 7 ? kAcceptTexture : 0u) |
                             (level >= 8 ? kAcceptMedium : 0u) | (level >= 9 ? kAcceptPhoto : 0u);
@@ -1154,14 +1174,52 @@ bool objects_scene(int level, const MatpbrPathObject* objects, int n_objects, co
     }
     return true;
 }
-int render_objects(const Frame& f, int level, const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
-                   const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf,
-                   const float* obj_col = nullptr, const float* obj_uv = nullptr, const MatpbrPathObjectTex* tex = nullptr,
-                   const void* texels = nullptr, long n_texels = 0, const MatpbrPathObjectMedium* media = nullptr) {
+int render_objects(const Frame& f, int level, const ObjectArgs& o) {
     Scene s;
-    if (!objects_scene(level, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s, media))
+    return objects_scene(level, o, s) ? render_common(f, s) : MATPBR_PATH_ERR_INVALID_ARG;
+}
+
+// the outputs of a differential entry, and the photograph it may read: an entry leaves what it does not have null
+struct DiffOut {
+    float *fg, *delta, *alpha;
+    uint32_t* rewalked;
+    const float* photo = nullptr;
+    float *through = nullptr, *base = nullptr;
+};
+// The five differential entries are this one function (the second table in DESIGN.md section 1.4, "The object entries"): fg, delta and
+// alpha always, photo and through both or neither (`need_photo`: both), base where `need_base`, at least one object.  (photo, base)
+// choose the table; it is launched with the medium records behind it where `objects_scene` left them, and, at level 9 where an object
+// carries the photo flag, as the table of the kernel whose chain passes it.
+int render_diff(const Frame& f, int level, const ObjectArgs& o, const DiffOut& d, bool need_photo, bool need_base) {
+    PathArgs q{};
+    Scene s;
+    if (!d.fg || !d.delta || !d.alpha || (need_photo && !d.photo) || (d.photo == nullptr) != (d.through == nullptr) || (need_base && !d.base) ||
+        o.n_objects <= 0 || !frame_args(f, q) || !objects_scene(level, o, s))
         return MATPBR_PATH_ERR_INVALID_ARG;
-    return render_common(f, s);
+    auto launch_as = [&](const auto& table) {
+        using Table = std::decay_t<decltype(table)>;
+        if constexpr (DiffTraits<Table>::through)
+            if (level >= 9 && s.n_photo > 0) {
+                Reflect<Table> rt{};
+                static_cast<Table&>(rt) = table;
+                return launch_frame(f, q, rt);
+            }
+        return launch_frame(f, q, table);
+    };
+    auto launch = [&](auto table) {
+        using Table = decltype(table);
+        static_cast<TexObjects&>(table) = tex_objects(s);
+        table.fg = d.fg; table.delta = d.delta; table.alpha = d.alpha; table.rewalked = d.rewalked;
+        if constexpr (DiffTraits<Table>::through) { table.photo = d.photo; table.through = d.through; }
+        if constexpr (DiffTraits<Table>::base) table.base = d.base;
+        if (!s.media) return launch_as(table);
+        MediumDiff<Table> mt{};
+        static_cast<Table&>(mt) = table;
+        media_into(s, mt);
+        return launch_as(mt);
+    };
+    if (d.base) return d.photo ? launch(RatioThroughObjects{}) : launch(RatioObjects{});
+    return d.photo ? launch(ThroughObjects{}) : launch(DiffObjects{});
 }
 
 // the arguments both feature entry points share, checked and packed: `q` arrives with the caller's pointers and sizes
@@ -1185,11 +1243,8 @@ bool feature_colors_args(const MatpbrPathObject* objects, int n_objects, long n_
                          unsigned accept = kAcceptAll | kAcceptColor, int* n_tex = nullptr) {
     ObjCounts n;
     if (!q.nodes || !q.tris || !q.out || !denoise_size_valid(q.H, q.W) || !fov_valid(fov_x_deg) ||
-        !object_table(objects, n_objects, accept, nullptr, ot, &n) || n_scene_tri < 0 || n_scene_tri > INT32_MAX ||
-        (n.color > 0 && !q.obj_col))
+        !object_table(objects, n_objects, accept, nullptr, ot, &n) || !ranges_above(objects, n_objects, n_scene_tri) || (n.color > 0 && !q.obj_col))
         return false;
-    for (int k = 0; k < n_objects; ++k)
-        if (objects[k].first_tri < n_scene_tri) return false;
     q.n_scene_tri = (int32_t)n_scene_tri;
     const Camera c = camera(q.H, q.W, fov_x_deg);   // the render's
     q.f_pix = c.f_pix; q.cx = c.cx; q.cy = c.cy;
@@ -1215,6 +1270,8 @@ bool feature_tints_args(const MatpbrPathObject* objects, int n_objects, long n_s
 
 // the Frame of a render entry point, from the names every one of them gives its first 21 parameters
 #define RENDER_FRAME Frame{nodes, tris, a, r, m, H, W, fov_x_deg, env, row_cdf, col_cdf, env_pdf, He, We, spp, max_depth, seed, spp_per_launch, out, rays, stream}
+// the ObjectArgs of an entry point from level 7 up, from the names every one of them gives the thirteen; `media` is the entry's to add
+#define OBJECT_ARGS ObjectArgs{objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels}
 
 }  // namespace
 
@@ -1529,14 +1586,14 @@ int matpbr_path_render_objects(const void* nodes, const void* tris, const float*
                                float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
                                int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                                const MatpbrPathObject* objects, int n_objects) {
-    return render_objects(RENDER_FRAME, 1, objects, n_objects, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+    return render_objects(RENDER_FRAME, 1, {objects, n_objects});
 }
 
 int matpbr_path_render_objects_normals(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
                                        float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
                                        int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                                        const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri) {
-    return render_objects(RENDER_FRAME, 2, objects, n_objects, obj_nrm, n_scene_tri, nullptr, nullptr, nullptr, nullptr);
+    return render_objects(RENDER_FRAME, 2, {objects, n_objects, obj_nrm, n_scene_tri});
 }
 
 int matpbr_path_object_normal_host(const float* tri, const float* nrm, const float* o, const float* d, long N, float* u, float* v, float* ns) {
@@ -1570,7 +1627,7 @@ int matpbr_path_render_objects_pbr(const void* nodes, const void* tris, const fl
                                    int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, float* out, uint32_t* rays, void* stream,
                                    const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                    const MatpbrPathObjectPbr* pbr) {
-    return render_objects(RENDER_FRAME, 3, objects, n_objects, obj_nrm, n_scene_tri, pbr, nullptr, nullptr, nullptr);
+    return render_objects(RENDER_FRAME, 3, {objects, n_objects, obj_nrm, n_scene_tri, pbr});
 }
 
 int matpbr_path_light_tables(const double* vert, long n_vert, const int32_t* tri, long n_tri, const MatpbrPathObject* objects, int n_objects,
@@ -1589,7 +1646,7 @@ int matpbr_path_render_objects_lights(const void* nodes, const void* tris, const
                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                       const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
                                       const float* light_cdf) {
-    return render_objects(RENDER_FRAME, 4, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf);
+    return render_objects(RENDER_FRAME, 4, {objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf});
 }
 
 int matpbr_path_light_sample_host(const MatpbrPathLights* lights, const void* light_tris, const float* light_cdf, long n_light_tri, int have_env,
@@ -1641,7 +1698,7 @@ int matpbr_path_render_objects_rough(const void* nodes, const void* tris, const 
                                      const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                      const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
                                      const float* light_cdf) {
-    return render_objects(RENDER_FRAME, 5, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf);
+    return render_objects(RENDER_FRAME, 5, {objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf});
 }
 
 int matpbr_path_render_objects_colors(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -1650,7 +1707,7 @@ int matpbr_path_render_objects_colors(const void* nodes, const void* tris, const
                                       const MatpbrPathObject* objects, int n_objects, const float* obj_nrm, long n_scene_tri,
                                       const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
                                       const float* light_cdf, const float* obj_col) {
-    return render_objects(RENDER_FRAME, 6, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col);
+    return render_objects(RENDER_FRAME, 6, {objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col});
 }
 
 int matpbr_path_object_color_host(const float* tri, const float* col, const float* o, const float* d, long N, float* u, float* v, float* c) {
@@ -1670,8 +1727,7 @@ int matpbr_path_render_objects_textures(const void* nodes, const void* tris, con
                                         const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
                                         const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
                                         const void* texels, long n_texels) {
-    return render_objects(RENDER_FRAME, 7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels,
-                          n_texels);
+    return render_objects(RENDER_FRAME, 7, OBJECT_ARGS);
 }
 
 int matpbr_path_render_objects_diff(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -1682,16 +1738,7 @@ int matpbr_path_render_objects_diff(const void* nodes, const void* tris, const f
                                     const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
                                     const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked) {
     float* const out = nullptr;   // the sums go to the table's buffers
-    const Frame f = RENDER_FRAME;
-    PathArgs q{};
-    Scene s;
-    if (!fg || !delta || !alpha || n_objects <= 0 || !frame_args(f, q) ||
-        !objects_scene(7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
-        return MATPBR_PATH_ERR_INVALID_ARG;
-    DiffObjects dt{};
-    static_cast<TexObjects&>(dt) = tex_objects(s);
-    dt.fg = fg; dt.delta = delta; dt.alpha = alpha; dt.rewalked = rewalked;
-    return launch_frame(f, q, dt);
+    return render_diff(RENDER_FRAME, 7, OBJECT_ARGS, {fg, delta, alpha, rewalked}, false, false);
 }
 
 int matpbr_path_render_objects_through(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -1703,17 +1750,7 @@ int matpbr_path_render_objects_through(const void* nodes, const void* tris, cons
                                        const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
                                        const float* photo, float* through) {
     float* const out = nullptr;   // the sums go to the table's buffers
-    const Frame f = RENDER_FRAME;
-    PathArgs q{};
-    Scene s;
-    if (!fg || !delta || !alpha || !photo || !through || n_objects <= 0 || !frame_args(f, q) ||
-        !objects_scene(7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
-        return MATPBR_PATH_ERR_INVALID_ARG;
-    ThroughObjects tt{};
-    static_cast<TexObjects&>(tt) = tex_objects(s);
-    tt.fg = fg; tt.delta = delta; tt.alpha = alpha; tt.rewalked = rewalked;
-    tt.photo = photo; tt.through = through;
-    return launch_frame(f, q, tt);
+    return render_diff(RENDER_FRAME, 7, OBJECT_ARGS, {fg, delta, alpha, rewalked, photo, through}, true, false);
 }
 
 int matpbr_path_render_objects_ratio(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -1725,25 +1762,7 @@ int matpbr_path_render_objects_ratio(const void* nodes, const void* tris, const 
                                      const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
                                      const float* photo, float* through, float* base) {
     float* const out = nullptr;   // the sums go to the table's buffers
-    const Frame f = RENDER_FRAME;
-    PathArgs q{};
-    Scene s;
-    if (!fg || !delta || !alpha || !base || (photo == nullptr) != (through == nullptr) || n_objects <= 0 || !frame_args(f, q) ||
-        !objects_scene(7, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s))
-        return MATPBR_PATH_ERR_INVALID_ARG;
-    if (!photo) {   // matpbr_path_render_objects_diff's rule
-        RatioObjects rt{};
-        static_cast<TexObjects&>(rt) = tex_objects(s);
-        rt.fg = fg; rt.delta = delta; rt.alpha = alpha; rt.rewalked = rewalked;
-        rt.base = base;
-        return launch_frame(f, q, rt);
-    }
-    RatioThroughObjects rt{};
-    static_cast<TexObjects&>(rt) = tex_objects(s);
-    rt.fg = fg; rt.delta = delta; rt.alpha = alpha; rt.rewalked = rewalked;
-    rt.photo = photo; rt.through = through;
-    rt.base = base;
-    return launch_frame(f, q, rt);
+    return render_diff(RENDER_FRAME, 7, OBJECT_ARGS, {fg, delta, alpha, rewalked, photo, through, base}, false, true);
 }
 
 int matpbr_path_render_objects_media(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -1753,8 +1772,9 @@ int matpbr_path_render_objects_media(const void* nodes, const void* tris, const 
                                      const MatpbrPathObjectPbr* pbr, const MatpbrPathLights* lights, const void* light_tris,
                                      const float* light_cdf, const float* obj_col, const float* obj_uv, const MatpbrPathObjectTex* tex,
                                      const void* texels, long n_texels, const MatpbrPathObjectMedium* media) {
-    return render_objects(RENDER_FRAME, 8, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels,
-                          n_texels, media);
+    ObjectArgs o = OBJECT_ARGS;
+    o.media = media;
+    return render_objects(RENDER_FRAME, 8, o);
 }
 
 int matpbr_path_render_objects_diff_media(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -1766,27 +1786,9 @@ int matpbr_path_render_objects_diff_media(const void* nodes, const void* tris, c
                                           const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
                                           const float* photo, float* through, float* base, const MatpbrPathObjectMedium* media) {
     float* const out = nullptr;   // the sums go to the table's buffers
-    const Frame f = RENDER_FRAME;
-    PathArgs q{};
-    Scene s;
-    if (!fg || !delta || !alpha || (photo == nullptr) != (through == nullptr) || n_objects <= 0 || !frame_args(f, q) ||
-        !objects_scene(8, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s, media))
-        return MATPBR_PATH_ERR_INVALID_ARG;
-    // the shape's table filled, and launched as it is or, where an object holds a medium, with the records behind it
-    auto launch = [&](auto table) {
-        using Table = decltype(table);
-        static_cast<TexObjects&>(table) = tex_objects(s);
-        table.fg = fg; table.delta = delta; table.alpha = alpha; table.rewalked = rewalked;
-        if constexpr (DiffTraits<Table>::through) { table.photo = photo; table.through = through; }
-        if constexpr (DiffTraits<Table>::base) table.base = base;
-        if (!s.media) return launch_frame(f, q, table);
-        MediumDiff<Table> mt{};
-        static_cast<Table&>(mt) = table;
-        media_into(s, mt);
-        return launch_frame(f, q, mt);
-    };
-    if (base) return photo ? launch(RatioThroughObjects{}) : launch(RatioObjects{});
-    return photo ? launch(ThroughObjects{}) : launch(DiffObjects{});
+    ObjectArgs o = OBJECT_ARGS;
+    o.media = media;
+    return render_diff(RENDER_FRAME, 8, o, {fg, delta, alpha, rewalked, photo, through, base}, false, false);
 }
 
 int matpbr_path_render_objects_reflect(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
@@ -1798,33 +1800,9 @@ int matpbr_path_render_objects_reflect(const void* nodes, const void* tris, cons
                                        const void* texels, long n_texels, float* fg, float* delta, float* alpha, uint32_t* rewalked,
                                        const float* photo, float* through, float* base, const MatpbrPathObjectMedium* media) {
     float* const out = nullptr;   // the sums go to the table's buffers
-    const Frame f = RENDER_FRAME;
-    PathArgs q{};
-    Scene s;
-    if (!fg || !delta || !alpha || !photo || !through || n_objects <= 0 || !frame_args(f, q) ||
-        !objects_scene(9, objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf, obj_col, obj_uv, tex, texels, n_texels, s, media))
-        return MATPBR_PATH_ERR_INVALID_ARG;
-    // the shape's table filled as matpbr_path_render_objects_diff_media fills it, then launched as it is or, where an object carries
-    // the photo flag, as the table of the kernel whose chain passes it
-    auto launch_as = [&](auto table) {
-        if (s.n_photo == 0) return launch_frame(f, q, table);
-        Reflect<decltype(table)> rt{};
-        static_cast<decltype(table)&>(rt) = table;
-        return launch_frame(f, q, rt);
-    };
-    auto launch = [&](auto table) {
-        using Table = decltype(table);
-        static_cast<TexObjects&>(table) = tex_objects(s);
-        table.fg = fg; table.delta = delta; table.alpha = alpha; table.rewalked = rewalked;
-        table.photo = photo; table.through = through;
-        if constexpr (DiffTraits<Table>::base) table.base = base;
-        if (!s.media) return launch_as(table);
-        MediumDiff<Table> mt{};
-        static_cast<Table&>(mt) = table;
-        media_into(s, mt);
-        return launch_as(mt);
-    };
-    return base ? launch(RatioThroughObjects{}) : launch(ThroughObjects{});
+    ObjectArgs o = OBJECT_ARGS;
+    o.media = media;
+    return render_diff(RENDER_FRAME, 9, o, {fg, delta, alpha, rewalked, photo, through, base}, true, false);
 }
 
 int matpbr_path_medium_segment_host(const MatpbrPathObjectMedium* medium, const float* t, const float* u9, long N, int32_t* scattered,
@@ -2084,15 +2062,13 @@ int matpbr_path_render_edit_diff(const void* nodes, const void* tris, const floa
     const Frame f = RENDER_FRAME;
     PathArgs q{};
     if (!a_e || !r_e || !m_e || !mask || !delta || !base || !frame_args(f, q)) return MATPBR_PATH_ERR_INVALID_ARG;
-    if (nrm) {
-        MapEdit<ShadeNormals> t{};
-        t.nrm = nrm;
+    auto launch = [&](auto base_table) {   // the edit's table over the render's own
+        MapEdit<decltype(base_table)> t{};
+        static_cast<decltype(base_table)&>(t) = base_table;
         t.a_e = a_e; t.r_e = r_e; t.m_e = m_e; t.mask = mask; t.delta = delta; t.rewalked = rewalked;
         return launch_frame(f, q, t);
-    }
-    MapEdit<NoObjects> t{};
-    t.a_e = a_e; t.r_e = r_e; t.m_e = m_e; t.mask = mask; t.delta = delta; t.rewalked = rewalked;
-    return launch_frame(f, q, t);
+    };
+    return nrm ? launch(ShadeNormals{nrm}) : launch(NoObjects{});
 }
 
 int matpbr_path_eval_normal_grad_host(const float* n, const float* wo, const float* wi, const float* a, const float* r, const float* m,

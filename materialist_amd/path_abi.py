@@ -87,7 +87,23 @@ class PathDenoise(ctypes.Structure):
 _FRAME = [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [_P] * 4 + [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int]
 _RENDER = _FRAME + [_P] * 3
 _RENDER_BWD = _FRAME + [_P] * 6 + [ctypes.c_size_t, _P, _P]
+# the thirteen object arguments (`PathTracer.object_args()`): objects, n_objects, obj_nrm, n_scene_tri, pbr, lights, light_tris, light_cdf,
+# obj_col, obj_uv, tex, texels, n_texels
+_OBJECTS = [_P, ctypes.c_int, _P, ctypes.c_long] + [_P] * 8 + [ctypes.c_long]
+# the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
+OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
+                  "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
+                  "matpbr_path_render_objects_textures": 13, "matpbr_path_render_objects_through": 13}
+# level 8 takes the thirteen of level 7 and then the medium records (`PathTracer.media_arg`), which `object_args()` does not hold
+MEDIA_ENTRY = "matpbr_path_render_objects_media"
+# the differential family -> how many of (photo, through, base, media) each takes after rays, stream, the thirteen object arguments and
+# fg, delta, alpha, rewalked
+DIFF_ENTRIES = {"matpbr_path_render_objects_diff": 0, "matpbr_path_render_objects_through": 2, "matpbr_path_render_objects_ratio": 3,
+                "matpbr_path_render_objects_diff_media": 4, "matpbr_path_render_objects_reflect": 4}
 SIGNATURES = {
+    **{name: (ctypes.c_int, _RENDER + _OBJECTS[:n]) for name, n in OBJECT_ENTRIES.items() if name not in DIFF_ENTRIES},
+    MEDIA_ENTRY: (ctypes.c_int, _RENDER + _OBJECTS + [_P]),
+    **{name: (ctypes.c_int, _FRAME + [_P, _P] + _OBJECTS + [_P] * (4 + n)) for name, n in DIFF_ENTRIES.items()},
     "matpbr_path_version": (ctypes.c_int, []),
     "matpbr_path_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "matpbr_path_bvh_size": (ctypes.c_int, [ctypes.c_long, _P]),
@@ -97,36 +113,23 @@ SIGNATURES = {
     "matpbr_path_env_tables": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
     "matpbr_path_env_sample_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_render": (ctypes.c_int, _RENDER),
-    "matpbr_path_render_objects": (ctypes.c_int, _RENDER + [_P, ctypes.c_int]),
     "matpbr_path_object_sample_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 4),
-    "matpbr_path_render_objects_normals": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long]),
     "matpbr_path_object_normal_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
-    "matpbr_path_render_objects_pbr": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P]),
     "matpbr_path_object_lookup_host": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_long, _P, _P, _P, _P]),
     "matpbr_path_light_tables": (ctypes.c_int, [_P, ctypes.c_long, _P, ctypes.c_long, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_long, _P]),
-    "matpbr_path_render_objects_lights": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P]),
     "matpbr_path_light_sample_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_long, ctypes.c_int, _P, _P, ctypes.c_long] + [_P] * 7),
     "matpbr_path_light_pdf_host": (ctypes.c_int, [_P, _P, ctypes.c_long, ctypes.c_int, _P, _P, _P, _P, ctypes.c_long, _P, _P]),
-    "matpbr_path_render_objects_rough": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P]),
     "matpbr_path_rough_sample_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
     "matpbr_path_rough_eval_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 2),
     "matpbr_path_object_sample_shading_host": (ctypes.c_int, [_P] * 5 + [ctypes.c_long] + [_P] * 4),
-    "matpbr_path_render_objects_colors": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P]),
     "matpbr_path_object_color_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long] + [_P] * 3),
     "matpbr_path_feature_colors": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_feature_colors_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P]),
-    "matpbr_path_render_objects_textures": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long]),
     "matpbr_path_object_texture_host": (ctypes.c_int, [_P] * 4 + [ctypes.c_long, _P, _P, ctypes.c_long] + [_P] * 5),
     "matpbr_path_feature_tints": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P, _P,
                                                  ctypes.c_long, _P, _P]),
     "matpbr_path_feature_tints_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, ctypes.c_int, ctypes.c_long, _P, _P, _P, _P,
                                                       ctypes.c_long, _P]),
-    "matpbr_path_render_objects_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 4),
-    "matpbr_path_render_objects_through": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 6),
-    "matpbr_path_render_objects_ratio": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 7),
-    "matpbr_path_render_objects_media": (ctypes.c_int, _RENDER + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long, _P]),
-    "matpbr_path_render_objects_diff_media": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 8),
-    "matpbr_path_render_objects_reflect": (ctypes.c_int, _FRAME + [_P, _P] + [_P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long] + [_P] * 8),
     "matpbr_path_reflect_chain_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P,
                                                       ctypes.c_long] + [_P] * 5),
     "matpbr_path_render_edit_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P] * 8),
@@ -175,7 +178,9 @@ SIGNATURES = {
 VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
 # the symbols added at version 3, by the feature each group came with, as `symbol` names it, in the order the features were merged: a
-# version-3 library built before one of them loads, and `symbol` names what it lacks
+# version-3 library built before one of them loads, and `symbol` names what it lacks.  The first ten groups are the partition of
+# LATE_SYMBOLS; the five after them ("Ratio shadow transfer", "Moving inserted objects", "Media inside glass",
+# "Reflected in inserted objects", "Material edits in the photograph") stand beside it
 FEATURE_SYMBOLS = {
     "smooth inserted objects": ("matpbr_path_render_objects_normals", "matpbr_path_object_normal_host", "matpbr_path_object_sample_shading_host"),
     "the denoiser": ("matpbr_path_features", "matpbr_path_features_host", "matpbr_path_denoise_prepare", "matpbr_path_denoise_prepare_host",
@@ -194,36 +199,19 @@ FEATURE_SYMBOLS = {
                                            "matpbr_path_denoise_diff_finish_host", "matpbr_path_denoise_diff_workspace_bytes", "matpbr_path_denoise_diff",
                                            "matpbr_path_denoise_diff_host"),
     "the photograph seen through inserted glass": ("matpbr_path_render_objects_through", "matpbr_path_through_chain_host"),
+    "ratio shadow transfer": ("matpbr_path_render_objects_ratio", "matpbr_path_composite_ratio", "matpbr_path_composite_ratio_host"),
+    "moving inserted objects": ("matpbr_path_bvh_build_grafted", "matpbr_path_xform_check_host", "matpbr_path_objects_move",
+                                "matpbr_path_objects_move_host"),
+    "media inside glass objects": ("matpbr_path_render_objects_media", "matpbr_path_render_objects_diff_media", "matpbr_path_medium_segment_host",
+                                   "matpbr_path_phase_sample_host"),
+    "the photograph reflected in inserted objects": ("matpbr_path_render_objects_reflect", "matpbr_path_reflect_chain_host"),
+    "material edits in the photograph": ("matpbr_path_render_edit_diff",),
 }
 (SMOOTH_SYMBOLS, DENOISE_SYMBOLS, PBR_SYMBOLS, LIGHT_SYMBOLS, ROUGH_SYMBOLS, COLOR_SYMBOLS, TEXTURE_SYMBOLS, DIFF_SYMBOLS, DIFF_DENOISE_SYMBOLS,
- THROUGH_SYMBOLS) = FEATURE_SYMBOLS.values()
-LATE_SYMBOLS = sum(FEATURE_SYMBOLS.values(), ())
-_FEATURE = {name: what for what, names in FEATURE_SYMBOLS.items() for name in names}
-# ratio shadow transfer's symbols ("Ratio shadow transfer"), added at version 3 as well: a group of its own beside
-# the ten above, which stay the partition of LATE_SYMBOLS they were
-RATIO_SYMBOLS = ("matpbr_path_render_objects_ratio", "matpbr_path_composite_ratio", "matpbr_path_composite_ratio_host")
-RATIO_FEATURE = "ratio shadow transfer"
-# moving inserted objects' symbols ("Moving inserted objects"), added at version 3 as well: a third group beside them
-MOVE_SYMBOLS = ("matpbr_path_bvh_build_grafted", "matpbr_path_xform_check_host", "matpbr_path_objects_move", "matpbr_path_objects_move_host")
-MOVE_FEATURE = "moving inserted objects"
-# media inside glass objects' symbols ("Media inside glass"), added at version 3 as well: a fourth group beside them
-MEDIUM_SYMBOLS = ("matpbr_path_render_objects_media", "matpbr_path_render_objects_diff_media", "matpbr_path_medium_segment_host",
-                  "matpbr_path_phase_sample_host")
-MEDIUM_FEATURE = "media inside glass objects"
-# the symbols of the photograph reflected in inserted objects ("Reflected in inserted objects"), added at version 3
-# as well: a fifth group beside them
-REFLECT_SYMBOLS = ("matpbr_path_render_objects_reflect", "matpbr_path_reflect_chain_host")
-REFLECT_FEATURE = "the photograph reflected in inserted objects"
-# the symbol of material edits in the photograph ("Material edits in the photograph"), added at version 3 as well: a
-# sixth group beside them
-MAPEDIT_SYMBOLS = ("matpbr_path_render_edit_diff",)
-MAPEDIT_FEATURE = "material edits in the photograph"
-# the object entry points, one per level of DESIGN.md section 1.4, "The object entries" -> how many of `PathTracer.object_args()` each takes
-OBJECT_ENTRIES = {"matpbr_path_render_objects": 2, "matpbr_path_render_objects_normals": 4, "matpbr_path_render_objects_pbr": 5,
-                  "matpbr_path_render_objects_lights": 8, "matpbr_path_render_objects_rough": 8, "matpbr_path_render_objects_colors": 9,
-                  "matpbr_path_render_objects_textures": 13, "matpbr_path_render_objects_through": 13}
-# level 8 takes the thirteen of level 7 and then the medium records (`PathTracer.media_arg`), which `object_args()` does not hold
-MEDIA_ENTRY = "matpbr_path_render_objects_media"
+ THROUGH_SYMBOLS, RATIO_SYMBOLS, MOVE_SYMBOLS, MEDIUM_SYMBOLS, REFLECT_SYMBOLS, MAPEDIT_SYMBOLS) = FEATURE_SYMBOLS.values()
+_FEATURE_OF = {name: what for what, names in FEATURE_SYMBOLS.items() for name in names}   # every late symbol -> its feature
+_FEATURE = {name: what for name, what in _FEATURE_OF.items() if what in list(FEATURE_SYMBOLS)[:10]}
+LATE_SYMBOLS = tuple(_FEATURE)
 DENOISE_DEFAULTS = {"levels": 5, "sigma_n": 32.0, "sigma_x": 1.0, "sigma_a": 0.1, "sigma_c": 4.0}
 
 
@@ -240,8 +228,7 @@ def load() -> ctypes.CDLL:
         _build.build_path_library()
         lib = ctypes.CDLL(_build.PATH_LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if (name in LATE_SYMBOLS or name in RATIO_SYMBOLS or name in MOVE_SYMBOLS or name in MEDIUM_SYMBOLS or name in REFLECT_SYMBOLS or
-                    name in MAPEDIT_SYMBOLS) and not hasattr(lib, name):
+            if name in _FEATURE_OF and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -255,9 +242,7 @@ def symbol(name: str, lib: Optional[ctypes.CDLL] = None):
     """The library's function `name`; PathError naming it when the loaded library was built before it existed."""
     lib = load() if lib is None else lib
     if not hasattr(lib, name):
-        what = (RATIO_FEATURE if name in RATIO_SYMBOLS else MOVE_FEATURE if name in MOVE_SYMBOLS else MEDIUM_FEATURE if name in MEDIUM_SYMBOLS
-                else REFLECT_FEATURE if name in REFLECT_SYMBOLS else MAPEDIT_FEATURE if name in MAPEDIT_SYMBOLS
-                else _FEATURE.get(name, "smooth inserted objects"))
+        what = _FEATURE_OF.get(name, "smooth inserted objects")
         raise PathError(f"libmatpbr_path.so has no {name}: it was built before {what}; rebuild it (build.build_path_library)")
     return getattr(lib, name)
 

@@ -34,14 +34,6 @@ from .path_host import *     # noqa: F401,F403
 from .path_host import _host_image  # noqa: F401
 from .path_scene import *    # noqa: F401,F403
 
-# the attribute a tracer with objects holds (not None, not False) -> the entry point its `render` takes, the first that applies, and
-# matpbr_path_render_objects when none does ("The object entries"); OBJECT_ENTRIES says how many of
-# `object_args()` the entry takes
-_OBJECT_ROUTES = (("textures", "matpbr_path_render_objects_textures"), ("obj_col", "matpbr_path_render_objects_colors"),
-                  ("rough", "matpbr_path_render_objects_rough"), ("lights", "matpbr_path_render_objects_lights"),
-                  ("pbr", "matpbr_path_render_objects_pbr"), ("obj_nrm", "matpbr_path_render_objects_normals"))
-
-
 def _dptr(t):
     return t.data_ptr() if t is not None else None
 
@@ -239,6 +231,22 @@ class PathTracer:
         differential family, the outputs); None on a tracer without a medium."""
         return ctypes.cast(self.media, _P) if self.media is not None else None
 
+    def _render_entry(self, nrm) -> tuple:
+        """(the entry point `render` takes, its own arguments after `stream`) ("The object entries").  A tracer with
+        objects takes level 8 where a medium exists, else the entry of the first attribute it holds (not None, not False), from the
+        textures down, else matpbr_path_render_objects; OBJECT_ENTRIES says how many of `object_args()` that entry takes."""
+        if nrm is not None:
+            return "matpbr_path_render_normals", (nrm.data_ptr(),)
+        if self.objects is None:
+            return "matpbr_path_render", ()
+        if self.media is not None:
+            return MEDIA_ENTRY, (*self.object_args()[:9], *self._texture_args(), self.media_arg())
+        for attr, level in (("textures", "textures"), ("obj_col", "colors"), ("rough", "rough"), ("lights", "lights"), ("pbr", "pbr"), ("obj_nrm", "normals")):
+            if getattr(self, attr) is not None and getattr(self, attr) is not False:
+                entry = "matpbr_path_render_objects_" + level
+                return entry, self.object_args()[:OBJECT_ENTRIES[entry]]
+        return "matpbr_path_render_objects", self.object_args()[:2]
+
     def poses(self, transforms: Sequence[Optional[dict]]):
         """`move_objects`' argument checked, before any device work -> the PathXform records: one entry per object, each None or a
         placement `similarity` takes (the default pivot is the centre of the object's rest bounding box); every record one the library
@@ -304,19 +312,7 @@ class PathTracer:
         lib = load()
         args = (*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), out.data_ptr(), rays.data_ptr() if rays is not None else None,
                 torch.cuda.current_stream(dev).cuda_stream)
-        if nrm is not None:
-            entry, own = "matpbr_path_render_normals", (nrm.data_ptr(),)
-        elif self.objects is None:
-            entry, own = "matpbr_path_render", ()
-        else:
-            entry = "matpbr_path_render_objects"
-            for attr, name in _OBJECT_ROUTES:
-                if getattr(self, attr) is not None and getattr(self, attr) is not False:
-                    entry = name
-                    break
-            own = self.object_args()[:OBJECT_ENTRIES[entry]]
-            if self.media is not None:                # level 8, only where a medium exists: every other tracer keeps its route
-                entry, own = MEDIA_ENTRY, (*self.object_args()[:9], *self._texture_args(), self.media_arg())
+        entry, own = self._render_entry(nrm)
         check(symbol(entry, lib)(*args, *own), entry)
         return out
 
@@ -341,6 +337,12 @@ class PathTracer:
                              f"build the PathTracer with `objects`")
         if photo is not None and tuple(torch.as_tensor(photo).shape) != (self.H, self.W, 3):
             raise ValueError(f"photo must be [{self.H},{self.W},3], got {tuple(torch.as_tensor(photo).shape)}")
+        symbol(entry)                                 # a library built before the method's own feature: PathError naming it
+        reflect = self.reflect and photo is not None  # a flagged object and a photograph: the one entry that sees the flag
+        if reflect:
+            entry = "matpbr_path_render_objects_reflect"
+        elif self.media is not None:                  # the superset entry, only where a medium exists
+            entry = "matpbr_path_render_objects_diff_media"
         fn = symbol(entry)
         H, W, dev = self.H, self.W, self.device
         own = () if photo is None else (torch.as_tensor(photo).to(dev, torch.float32).contiguous(), torch.empty(H, W, 3, device=dev, dtype=torch.float32))
@@ -348,18 +350,10 @@ class PathTracer:
         inputs = self._inputs(*maps, tables)
         fg, delta = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
         alpha, rewalked = torch.empty(H, W, device=dev, dtype=torch.float32), torch.zeros(H, W, device=dev, dtype=torch.int32)
-        tail = (*own, *base) if own or not ratio else (None, None, *base)
-        if self.media is not None:                    # the superset entry, only where a medium exists: photo, through and base nullable, then the records
-            entry = "matpbr_path_render_objects_diff_media"
-            fn = symbol(entry)
-            tail = (*(own or (None, None)), *(base or (None,)), self.media)
-        reflect = self.reflect and bool(own)          # a flagged object and a photograph: the one entry that sees the flag; nullable base and records
-        if reflect:
-            entry = "matpbr_path_render_objects_reflect"
-            fn = symbol(entry)
-            tail = (*own, *(base or (None,)), self.media)
+        # the four outputs, then as many of (photo, through, base, media) as the entry takes, None where this call has none
+        tail = (*map(_dptr, (fg, delta, alpha, rewalked, *(own or (None, None)), *(base or (None,)))), self.media_arg())[:4 + DIFF_ENTRIES[entry]]
         check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), _dptr(rays), torch.cuda.current_stream(dev).cuda_stream,
-                 *self.object_args(reflect)[:9], *self._texture_args(), *(ctypes.cast(x, _P) if isinstance(x, ctypes.Array) else _dptr(x) for x in (fg, delta, alpha, rewalked, *tail))), entry)
+                 *self.object_args(reflect)[:9], *self._texture_args(), *tail), entry)
         return (fg, delta, *base, alpha, *own[1:], rewalked)
 
     @torch.no_grad()

@@ -79,11 +79,12 @@ def raw_args(tracer, maps, spp, max_depth, seed, spp_per_launch, out):
 
 
 def object_tail(tracer, entry="matpbr_path_render_objects_rough"):
-    """The object arguments of the forward entry point `entry` after `stream`, for calls past `PathTracer.render`: the prefix of
-    `PathTracer.object_args()` it takes (all eight by default)."""
+    """The object arguments of the forward entry point `entry` after `stream`, for calls past `PathTracer.render`: the prefix it takes
+    (all eight by default) of the tracer's nine object arguments, its four texture arguments and its medium records."""
     from materialist_amd import pathtrace
 
-    return tracer.object_args()[:pathtrace.OBJECT_ENTRIES[entry]]
+    full = (*tracer.object_args()[:9], *tracer._texture_args(), tracer.media_arg())
+    return full[:len(full) if entry == pathtrace.MEDIA_ENTRY else pathtrace.OBJECT_ENTRIES[entry]]
 
 
 def groove_with_objects(pt, objects, merged):

@@ -1,8 +1,9 @@
-"""The refusals of libmatpbr_path.so's entry points that take the common arguments of a frame (include/matpbr_path.h): the eight forward
-renders, the two backward passes and `matpbr_path_features`, each with every term of the validity condition broken in turn, and the
-five object entries with every rule of their level ("The object entries").  Every case is invalid in exactly
-one respect and returns MATPBR_PATH_ERR_INVALID_ARG; every other pointer is a non-null dummy, which a refusing call never reads.
-Validation precedes every launch, so no GPU is needed."""
+"""The refusals of libmatpbr_path.so's entry points that take the common arguments of a frame (include/matpbr_path.h): the eleven forward
+renders, the five differential renders of inserted objects, `matpbr_path_render_edit_diff`, the two backward passes and
+`matpbr_path_features`, each with every term of the validity condition broken in turn, and the thirteen object entries (forward levels
+1 to 8 and the differential family at levels 7, 8 and 9) with every rule of their level ("The object
+entries").  Every case is invalid in exactly one respect and returns MATPBR_PATH_ERR_INVALID_ARG; every other pointer is a non-null
+dummy, which a refusing call never reads.  Validation precedes every launch, so no GPU is needed."""
 import ctypes
 import os
 import sys
@@ -22,21 +23,42 @@ COMMON = ("nodes", "tris", "a", "r", "m", "H", "W", "fov", "env", "row_cdf", "co
           "spp_per_launch")
 OBJECTS = ("objects", "n_objects", "obj_nrm", "n_scene_tri")
 LIGHTS = ("pbr", "lights", "light_tris", "light_cdf")
+TAIL = OBJECTS + LIGHTS + ("obj_col", "obj_uv", "tex", "texels", "n_texels")   # the thirteen object arguments of level 7
 FORWARD = {"matpbr_path_render": (), "matpbr_path_render_objects": OBJECTS[:2], "matpbr_path_render_objects_normals": OBJECTS,
            "matpbr_path_render_objects_pbr": OBJECTS + ("pbr",), "matpbr_path_render_objects_lights": OBJECTS + LIGHTS,
            "matpbr_path_render_objects_rough": OBJECTS + LIGHTS, "matpbr_path_render_trans": ("mask", "bg", "edit"),
-           "matpbr_path_render_normals": ("nrm",)}
-# the object entries: their level, which is also the highest kind they admit (levels 1 and 2: kind 2)
+           "matpbr_path_render_normals": ("nrm",), "matpbr_path_render_objects_colors": TAIL[:9],
+           "matpbr_path_render_objects_textures": TAIL, "matpbr_path_render_objects_media": TAIL + ("media",)}
+# the differential family: what each entry takes after fg, delta, alpha, rewalked
+DIFF = {"matpbr_path_render_objects_diff": (), "matpbr_path_render_objects_through": ("photo", "through"),
+        "matpbr_path_render_objects_ratio": ("photo", "through", "base"),
+        "matpbr_path_render_objects_diff_media": ("photo", "through", "base", "media"),
+        "matpbr_path_render_objects_reflect": ("photo", "through", "base", "media")}
+EDIT_DIFF = "matpbr_path_render_edit_diff"
+# the object entries: their level; up to level 5 it is also the highest kind they admit (levels 1 and 2: kind 2)
 LEVEL = {"matpbr_path_render_objects": 1, "matpbr_path_render_objects_normals": 2, "matpbr_path_render_objects_pbr": 3,
-         "matpbr_path_render_objects_lights": 4, "matpbr_path_render_objects_rough": 5}
+         "matpbr_path_render_objects_lights": 4, "matpbr_path_render_objects_rough": 5, "matpbr_path_render_objects_colors": 6,
+         "matpbr_path_render_objects_textures": 7, "matpbr_path_render_objects_media": 8, "matpbr_path_render_objects_diff": 7,
+         "matpbr_path_render_objects_through": 7, "matpbr_path_render_objects_ratio": 7, "matpbr_path_render_objects_diff_media": 8,
+         "matpbr_path_render_objects_reflect": 9}
+# the pointers an entry requires besides the frame's (every other pointer after the frame is nullable or consulted only where the table needs it)
+REQUIRED = {"matpbr_path_render_objects_diff": ("fg", "delta", "alpha"),
+            "matpbr_path_render_objects_through": ("fg", "delta", "alpha", "photo", "through"),
+            "matpbr_path_render_objects_ratio": ("fg", "delta", "alpha", "base"), "matpbr_path_render_objects_diff_media": ("fg", "delta", "alpha"),
+            "matpbr_path_render_objects_reflect": ("fg", "delta", "alpha", "photo", "through"),
+            EDIT_DIFF: ("a_e", "r_e", "m_e", "mask", "delta", "base")}
+BOTH_OR_NEITHER = ("matpbr_path_render_objects_ratio", "matpbr_path_render_objects_diff_media")   # photo and through
+COLORED, TEXTURED, MEDIUM, PHOTO = 0x200, 0x400, 0x800, 0x1000   # MATPBR_PATH_OBJECT_*
+DIFFUSE_KIND = 2                                                 # MATPBR_PATH_BSDF_DIFFUSE: it may carry every flag but the medium's
 BACKWARD = {"matpbr_path_render_bwd": (), "matpbr_path_render_bwd_normals": ("nrm", "d_n")}
 FEATURES = "matpbr_path_features"
 ORDER = {name: COMMON + ("out", "rays", "stream") + tail for name, tail in FORWARD.items()}
 ORDER.update({name: COMMON + ("d_out", "d_a", "d_r", "d_m", "d_env", "workspace", "workspace_bytes", "rays", "stream") + tail
               for name, tail in BACKWARD.items()})
+ORDER.update({name: COMMON + ("rays", "stream") + TAIL + ("fg", "delta", "alpha", "rewalked") + tail for name, tail in DIFF.items()})
+ORDER[EDIT_DIFF] = COMMON + ("rays", "stream", "a_e", "r_e", "m_e", "mask", "nrm", "delta", "base", "rewalked")
 ORDER[FEATURES] = ("nodes", "tris", "H", "W", "fov") + OBJECTS + ("nrm_map", "geom", "stream")
-WITH_TABLE = ("matpbr_path_render_objects_normals", "matpbr_path_render_objects_pbr", "matpbr_path_render_objects_lights",
-              "matpbr_path_render_objects_rough", FEATURES)
+WITH_TABLE = tuple(name for name, names in ORDER.items() if "n_scene_tri" in names)   # the entries that know n_scene_tri
 _RAW = np.zeros(18, np.float64)
 DUMMY = _RAW[(-_RAW.ctypes.data % 16) // 8:][:16]   # what every pointer of a call points at: 16-byte aligned, as light_tris must be
 N_TRI = 20                                          # the triangles of every object of a table
@@ -54,12 +76,13 @@ def _workspace_bytes(path_lib, entry, c):
 
 
 def _scene(path_lib, kinds):
-    """A valid table of N_TRI-triangle objects of `kinds`, one after the other from triangle 1, its records and its light header (the
-    kind-4 objects in order, records contiguous from 0, area 1) -> [table, records, header]."""
+    """A valid table of N_TRI-triangle objects of `kinds`, one after the other from triangle 1, its records, its light header (the
+    kind-4 objects in order, records contiguous from 0, area 1), its texture records (one 2 x 2 base-colour image at texel 0) and its
+    medium records -> [table, records, header, tex, media]."""
     p = {path_lib.BSDF_DIELECTRIC: (1.5, 1.0, 0.0), path_lib.BSDF_DIFFUSE: (0.5, 0.5, 0.5), path_lib.BSDF_PBR: (0.0, 0.0, 0.0),
          path_lib.BSDF_AREA: (0.5, 0.5, 0.5), path_lib.BSDF_ROUGH_DIELECTRIC: (1.5, 1.0, 0.1)}
     table = (path_lib.PathObject * len(kinds))(*(path_lib.PathObject(kind, 1 + N_TRI * k, N_TRI,
-                                                                     (ctypes.c_float * 3)(*p[kind & ~path_lib.OBJECT_SMOOTH]))
+                                                                     (ctypes.c_float * 3)(*p[kind & 0xFF]))
                                                  for k, kind in enumerate(kinds)))
     records = (path_lib.PathObjectPbr * len(kinds))(*(path_lib.PathObjectPbr((ctypes.c_float * 3)(0.5, 0.5, 0.5), 0.5, 0.0) for _ in kinds))
     header = path_lib.PathLights()
@@ -68,21 +91,24 @@ def _scene(path_lib, kinds):
             l = header.n_lights
             header.object[l], header.first[l], header.n_tri[l], header.area[l] = k, N_TRI * l, N_TRI, 1.0
             header.n_lights += 1
-    return [table, records, header]
+    tex = (path_lib.PathObjectTex * len(kinds))(*(path_lib.PathObjectTex(0, 2, 2, 0, 0, 0) for _ in kinds))
+    media = (path_lib.PathObjectMedium * len(kinds))(*(path_lib.PathObjectMedium((ctypes.c_float * 3)(0.1, 0.2, 0.3), 0.5, 0.0) for _ in kinds))
+    return [table, records, header, tex, media]
 
 
 def _scene_args(c, scene):
     """The arguments of `scene` among those the entry of `c` takes."""
-    table, records, header = scene
+    table, records, header, tex, media = scene
     c["keep"].append(scene)
     args = {"objects": ctypes.cast(table, ctypes.c_void_p), "n_objects": len(table), "pbr": ctypes.cast(records, ctypes.c_void_p),
-            "lights": ctypes.cast(ctypes.byref(header), ctypes.c_void_p)}
+            "lights": ctypes.cast(ctypes.byref(header), ctypes.c_void_p), "tex": ctypes.cast(tex, ctypes.c_void_p),
+            "media": ctypes.cast(media, ctypes.c_void_p)}
     return {k: v for k, v in args.items() if k in c}
 
 
 def _own_kind(path_lib, entry):
     """The kind of the one object of the entry's valid call: the highest it admits."""
-    return max(LEVEL.get(entry, 2), path_lib.BSDF_DIFFUSE)
+    return max(min(LEVEL.get(entry, 2), path_lib.BSDF_ROUGH_DIELECTRIC), path_lib.BSDF_DIFFUSE)
 
 
 def _valid(path_lib, entry):
@@ -98,6 +124,8 @@ def _valid(path_lib, entry):
         c.update(_scene_args(c, _scene(path_lib, [_own_kind(path_lib, entry)])))
     if "n_scene_tri" in c:
         c.update(n_scene_tri=1)
+    if "n_texels" in c:
+        c.update(n_texels=4)   # the 2 x 2 image of `_scene`'s texture records
     if "edit" in c:
         c.update(edit=ctypes.cast(ctypes.byref(c["keep"][0]), ctypes.c_void_p))
     if entry == FEATURES:
@@ -132,9 +160,10 @@ def _smooth(path_lib, entry, c):
 
 
 def _set(what, index, field, value):
-    """spoil: table / records / header [index] . field = value (a header's field is an array over the lights; index None: a scalar)."""
-    def spoil(table, records, header):
-        target = {"table": table, "records": records}.get(what)
+    """spoil: table / records / tex / media / header [index] . field = value (a header's field is an array over the lights; index None:
+    a scalar)."""
+    def spoil(table, records, header, tex, media):
+        target = {"table": table, "records": records, "tex": tex, "media": media}.get(what)
         if target is not None:
             if isinstance(field, tuple):
                 getattr(target[index], field[0])[field[1]] = value
@@ -197,19 +226,40 @@ ROUGH_CASES = {
     "kind 5 with equal indices": _table_case(spoil=_set("table", 0, ("p", 1), 1.5)),
     "kind 5 with a zero index": _table_case(spoil=_set("table", 0, ("p", 0), 0.0)),
 }
+# a flag above an entry's level: the flag, on a kind that may carry it -> the first level that admits it
+FLAG_CASES = {"the colour flag": (DIFFUSE_KIND | COLORED, 6), "the texture flag": (DIFFUSE_KIND | TEXTURED, 7), "the medium flag": (1 | MEDIUM, 8),
+              "the photo flag": (DIFFUSE_KIND | PHOTO, 9)}
+# each flag's own rules at the entries that admit it: the last object of the table carries the flag, beside valid arguments for it
+COLOR_CASES = {"a coloured object without obj_col": _table_case([DIFFUSE_KIND | COLORED], obj_col=None)}
+TEXTURE_CASES = {
+    "a textured object without obj_uv": _table_case([DIFFUSE_KIND | TEXTURED], obj_uv=None),
+    "a textured object without tex": _table_case([DIFFUSE_KIND | TEXTURED], tex=None),
+    "a textured object without texels": _table_case([DIFFUSE_KIND | TEXTURED], texels=None),
+    "a textured object with texels 4 bytes off their alignment": _table_case([DIFFUSE_KIND | TEXTURED], texels=lambda p, e, c: c["texels"] + 4),
+}
+MEDIUM_CASES = {
+    "a medium flag with media = NULL": _table_case([1 | MEDIUM], media=None),
+    "a medium with a negative sigma_s": _table_case([1 | MEDIUM], spoil=_set("media", -1, "sigma_s", -1.0)),
+    "a medium with g = 1": _table_case([1 | MEDIUM], spoil=_set("media", -1, "g", 1.0)),
+}
 
 
 def _cases():
     out = []
     for entry, names in ORDER.items():
         cases = {f"{k} = NULL": {k: None} for k in names
-                 if k in ("nodes", "tris", "a", "r", "m", "env", "row_cdf", "col_cdf", "env_pdf", "out", "d_out", "workspace", "geom")}
+                 if k in ("nodes", "tris", "a", "r", "m", "env", "row_cdf", "col_cdf", "env_pdf", "out", "d_out", "workspace", "geom") +
+                 REQUIRED.get(entry, ())}
         cases.update({k: v for k, v in {**SIZES, **DEPTHS}.items() if next(iter(v)) in names})
         cases.update(FOVS)
         if entry in BACKWARD:
             cases.update(BACKWARD_CASES)
         if entry == "matpbr_path_render_bwd_normals":
             cases["d_n without nrm"] = {"nrm": None, "d_n": DUMMY.ctypes.data}
+        if entry in BOTH_OR_NEITHER:
+            cases.update({"photo without through": {"through": None}, "through without photo": {"photo": None}})
+        if entry in DIFF:
+            cases["n_objects = 0"] = {"n_objects": 0}
         if entry in WITH_TABLE:
             cases.update(TABLE_CASES)
         if entry in LEVEL:
@@ -223,8 +273,15 @@ def _cases():
                 cases.update(PBR_CASES)
             if level >= 4:
                 cases.update(LIGHT_CASES)
-            if level == 5:
+            if level >= 5:
                 cases.update(ROUGH_CASES)
+            cases.update({what: _table_case([kind]) for what, (kind, first) in FLAG_CASES.items() if level < first})
+            if level >= 6:
+                cases.update(COLOR_CASES)
+            if level >= 7:
+                cases.update(TEXTURE_CASES)
+            if level >= 8:
+                cases.update(MEDIUM_CASES)
         out += [pytest.param(entry, patch, id=f"{entry[len('matpbr_path_'):]}: {what}") for what, patch in cases.items()]
     return out
 
@@ -250,4 +307,27 @@ def test_the_valid_backward_call_the_cases_start_from_is_accepted(path_lib, entr
 def test_the_argument_orders_are_the_bindings(path_lib):
     for entry, names in ORDER.items():
         assert len(names) == len(path_lib.SIGNATURES[entry][1]), entry
-    assert len(ORDER) == 11
+    assert len(ORDER) == 20
+
+
+# the argument lists of the thirteen object entries as path_abi.SIGNATURES spelled them one by one before it derived them from one object
+# tail: P void pointer, i int, l long, f float, u uint32
+_FRAME_TYPES = "PPPPPiifPPPPiiiiui"
+_TAIL_TYPES = "PiPlPPPPPPPPl"
+SPELLED = {"matpbr_path_render_objects": _FRAME_TYPES + "PPP" + "Pi", "matpbr_path_render_objects_normals": _FRAME_TYPES + "PPP" + "PiPl",
+           "matpbr_path_render_objects_pbr": _FRAME_TYPES + "PPP" + "PiPlP", "matpbr_path_render_objects_lights": _FRAME_TYPES + "PPP" + "PiPlPPPP",
+           "matpbr_path_render_objects_rough": _FRAME_TYPES + "PPP" + "PiPlPPPP", "matpbr_path_render_objects_colors": _FRAME_TYPES + "PPP" + "PiPlPPPPP",
+           "matpbr_path_render_objects_textures": _FRAME_TYPES + "PPP" + _TAIL_TYPES, "matpbr_path_render_objects_media": _FRAME_TYPES + "PPP" + _TAIL_TYPES + "P",
+           "matpbr_path_render_objects_diff": _FRAME_TYPES + "PP" + _TAIL_TYPES + "PPPP",
+           "matpbr_path_render_objects_through": _FRAME_TYPES + "PP" + _TAIL_TYPES + "PPPPPP",
+           "matpbr_path_render_objects_ratio": _FRAME_TYPES + "PP" + _TAIL_TYPES + "PPPPPPP",
+           "matpbr_path_render_objects_diff_media": _FRAME_TYPES + "PP" + _TAIL_TYPES + "PPPPPPPP",
+           "matpbr_path_render_objects_reflect": _FRAME_TYPES + "PP" + _TAIL_TYPES + "PPPPPPPP"}
+
+
+def test_the_derived_signatures_are_the_lists_they_replace(path_lib):
+    types = {"P": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "u": ctypes.c_uint32}
+    assert set(SPELLED) == set(LEVEL) == set(path_lib.OBJECT_ENTRIES) | set(path_lib.DIFF_ENTRIES) | {path_lib.MEDIA_ENTRY}
+    for entry, spelled in SPELLED.items():
+        assert path_lib.SIGNATURES[entry] == (ctypes.c_int, [types[t] for t in spelled]), entry
+    assert path_lib.DIFF_ENTRIES == {name: len(tail) for name, tail in DIFF.items()}
