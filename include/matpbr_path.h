@@ -826,6 +826,39 @@ int matpbr_path_render_edit_diff(const void* nodes, const void* tris, const floa
                                  const float* a_e, const float* r_e, const float* m_e, const uint8_t* mask, const float* nrm, float* delta,
                                  float* base, uint32_t* rewalked);
 
+/* ---- Relighting in the photograph ("Relighting in the photograph"): one walk under two environments and the
+ * quotient composite; no inserted objects, the envmaps the only emitters; forward only; added at version 3. */
+
+/* matpbr_path_render's arguments up to spp_per_launch (env and its tables: environment A, the fitted light), rays and stream as
+ * there, then environment B, the new light, with its own size and its own tables of matpbr_path_env_tables: env_b[He_b,We_b,3],
+ * row_cdf_b[He_b+1], col_cdf_b[He_b,We_b+1], env_pdf_b[He_b,We_b]; nrm[H,W,3] (nullable: the shading-normal map of
+ * matpbr_path_render_normals); and the outputs base[H,W,3], relit[H,W,3].  Every pointer DEVICE.  Sample s of a pixel is walked
+ * once, as matpbr_path_render (matpbr_path_render_normals) walks it: no decision of that walk reads the envmap.  At every vertex the
+ * emitter sample is taken once per environment that has tables (row_cdf[He] > 0), from the same dims 2-5, each with its own shadow
+ * ray and MIS weight; at an escape each environment is read at its own texel with its own MIS weight.  base = the mean over spp of
+ * the radiance under A, relit = under B: each is what matpbr_path_render gives with that environment, up to the rounding of its
+ * sums.  The instructions that read an environment are the same for A and B, so where B is A (the same values, the pointers may
+ * differ) relit has base's bits.  rays counts the closest-hit rays once and each environment's shadow rays.  Every split into
+ * launches gives the same bits.  Invalid arguments, besides matpbr_path_render's: a NULL env_b, row_cdf_b, col_cdf_b, env_pdf_b,
+ * base or relit, He_b or We_b <= 0. */
+int matpbr_path_render_relight(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                               const float* env_b, const float* row_cdf_b, const float* col_cdf_b, const float* env_pdf_b, int He_b, int We_b,
+                               const float* nrm, float* base, float* relit);
+/* The quotient image: the sums are matpbr_path_render_relight's outputs added over some frames, scale = 1 / (their number).  Per
+ * channel B0 = base_sum scale, B1 = relit_sum scale, g = (B1 + floor) / (B0 + floor), out = max(0, photo g): the photograph times
+ * the model's radiance under the new light over that under the fitted one, in which the model's albedo cancels to first order.
+ * floor > 0 bounds the quotient where the model is dark: g <= (B1 + floor) / floor.  Every operation is rounded on its own and the
+ * division is the correctly rounded one: the CPU twin gives the same bits, and where relit_sum has base_sum's bits g is exactly 1 and
+ * the photograph (>= 0) comes through bit for bit.  DEVICE pointers.  Invalid: a NULL pointer, H or W <= 0, scale or floor not
+ * finite or <= 0. */
+int matpbr_path_composite_relight(const float* base_sum, const float* relit_sum, const float* photo, int H, int W, float scale, float floor,
+                                  float* out, void* stream);
+/* matpbr_path_composite_relight on the CPU with the routine the kernel runs (every pointer HOST). */
+int matpbr_path_composite_relight_host(const float* base_sum, const float* relit_sum, const float* photo, int H, int W, float scale, float floor,
+                                       float* out);
+
 /* One segment inside a medium on the CPU, with the routine the kernel runs: the record `medium` (checked), per lane the traced
  * distance t[N] and u9[N] -> scattered[N] (1: the segment ends at a medium vertex), dist[N] (s there, else t), weight[N,3] =
  * expf(-sigma_a dist).  u9 is read only where sigma_s > 0. */

@@ -79,7 +79,8 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 PATH_LIB_PATH = os.path.join(_HERE, "libmatpbr_path.so")
 PATH_SOURCES = ["matpbr_path.hip"]
 PATH_HEADERS = [os.path.join("..", "..", "include", "matpbr_path.h"), "matpbr_device.hpp", "path_bvh.hpp", "path_shading.hpp", "path_objects.hpp",
-                "path_denoise.hpp", "path_lights.hpp", "path_textures.hpp", "path_diff.hpp", "path_media.hpp", "path_move.hpp", "path_reflect.hpp", "path_mapedit.hpp"]
+                "path_denoise.hpp", "path_lights.hpp", "path_textures.hpp", "path_diff.hpp", "path_media.hpp", "path_move.hpp", "path_reflect.hpp", "path_mapedit.hpp",
+                "path_relight.hpp"]
 
 
 def path_is_stale() -> bool:

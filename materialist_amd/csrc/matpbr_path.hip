@@ -12,7 +12,8 @@
 // kernels take by value, their lookups, samplers and checks; path_lights.hpp the emissive objects' tables, sampler and pdfs;
 // path_textures.hpp the image textures of inserted objects; path_denoise.hpp the denoiser; path_diff.hpp the differential render's table
 // and the composite; path_media.hpp the media inside glass objects; path_move.hpp the grafted BVH's move and refit of the inserted objects;
-// path_reflect.hpp the see-through tables whose chain passes flagged objects; path_mapedit.hpp the table of the walk over edited maps.
+// path_reflect.hpp the see-through tables whose chain passes flagged objects; path_mapedit.hpp the table of the walk over edited maps;
+// path_relight.hpp the table of the walk under two environments and the quotient composite.
 #include <type_traits>
 
 #include "path_denoise.hpp"
@@ -21,6 +22,7 @@
 #include "path_media.hpp"
 #include "path_move.hpp"
 #include "path_reflect.hpp"
+#include "path_relight.hpp"
 
 namespace {
 
@@ -96,7 +98,15 @@ __device__ __forceinline__ int id_limit_at(const ThroughObjects& ot, bool second
 // records the first such read in `touched`; trip 1 runs where touched: the same sample from the camera ray on, on the fitted maps
 // alone.  delta takes trip 0 minus trip 1; the radiance on the fitted maps, trip 1's or the only trip's, takes the render's own sum
 // (`acc`, q.out).  Nothing of trip 0 but Lw and touched reaches trip 1.  Read off the table's type (MapEditTraits); every
-// `if (MAPEDIT ...)` folds away in every kernel without it.
+// `if (MAPEDIT ...)` folds away in every kernel without it.  RELIGHT: the depth mesh's walk, or NRM's, under two environments (Objects =
+// Relight<NoObjects>, Relight<ShadeNormals>; DESIGN.md section 1.4, "Relighting in the photograph"): one trip per sample, as the
+// render's.  No decision of that walk reads the envmap, so the closest hit, the texel, the BSDF sample, the throughput and the stop
+// rules are computed once; the statements that do read it, the emitter sample at a vertex and the lookup at an escape, are the
+// depth mesh's alone (no object, light or edit rule applies) and stand in blocks of their own: one body run twice (`e` = 0: PathArgs'
+// environment into L; 1: the table's into L1), a loop that is not unrolled with the pointers, the sizes and the sum chosen by
+// wave-uniform selects, so both environments get the same instructions and L1 has L's bits where the environments are equal.  L goes
+// to the render's own sum (`acc`, q.out), L1 to a second register sum (`racc`, relit).  Read off the table's type (RelightTraits);
+// every `if (RELIGHT ...)` folds away in every kernel without it, whose statements are untouched.
 template <class Objects>
 __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, int s1, int first, int last, const Objects ot) {
     constexpr bool THROUGH = DiffTraits<Objects>::through;
@@ -105,6 +115,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     constexpr bool MEDIUM = MediumTraits<Objects>::medium;
     constexpr bool REFLECT = ReflectTraits<Objects>::reflect;
     constexpr bool MAPEDIT = MapEditTraits<Objects>::mapedit;
+    constexpr bool RELIGHT = RelightTraits<Objects>::relight;
     constexpr bool TEX = std::is_same<Objects, TexObjects>::value || DIFF || MEDIUM;
     constexpr bool COLOR = std::is_same<Objects, ColorObjects>::value || TEX;
     constexpr bool ROUGH = std::is_same<Objects, RoughObjects>::value || COLOR;
@@ -113,7 +124,8 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     constexpr bool SMOOTH = std::is_same<Objects, SmoothObjects>::value || PBR;
     constexpr bool OBJ = std::is_same<Objects, ObjTable>::value || SMOOTH;
     constexpr bool EDIT = std::is_same<Objects, TransEdit>::value;
-    constexpr bool NRM = std::is_same<Objects, ShadeNormals>::value || std::is_same<Objects, MapEdit<ShadeNormals>>::value;
+    constexpr bool NRM = std::is_same<Objects, ShadeNormals>::value || std::is_same<Objects, MapEdit<ShadeNormals>>::value ||
+                         std::is_same<Objects, Relight<ShadeNormals>>::value;
     __shared__ int s_stack[kStack * kBlock];
     const int tid = threadIdx.y * kTileX + threadIdx.x;
     const int j = blockIdx.x * kTileX + threadIdx.x, i = blockIdx.y * kTileY + threadIdx.y;
@@ -121,13 +133,24 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
     LdsStack stk{s_stack + tid};
     const long pix = (long)i * q.W + j;
     const bool have_tab = q.row_cdf[q.He] > 0.0f;   // an envmap of zero luminance has no emitter sampling
+    bool have_tab_b = false;                        // (RELIGHT) the same of the table's environment
+    if constexpr (RELIGHT) have_tab_b = ot.row_cdf_b[ot.He_b] > 0.0f;
     int n_e = 1;   // (LIGHT) the emitters: the envmap where it has tables, then the lights
     if constexpr (LIGHT) n_e = (have_tab ? 1 : 0) + ot.lt.n;
     float n_ef = (float)n_e;
     float acc[3] = {0.0f, 0.0f, 0.0f};
     float dacc[3] = {0.0f, 0.0f, 0.0f};   // (MAPEDIT) delta's sum, in registers within a launch as acc is
     uint32_t n_second = 0;                // (MAPEDIT) second walks of this launch
-    if constexpr (MAPEDIT) {
+    float racc[3] = {0.0f, 0.0f, 0.0f};   // (RELIGHT) relit's sum, in registers within a launch as acc is
+    if constexpr (RELIGHT) {
+        if (!first) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                acc[c] = q.out[3 * pix + c];
+                racc[c] = ot.relit[3 * pix + c];
+            }
+        }
+    } else if constexpr (MAPEDIT) {
         if (!first) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -179,6 +202,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             if (!second) touched = false;
         }
         float L[3] = {0.0f, 0.0f, 0.0f}, thr[3] = {1.0f, 1.0f, 1.0f};
+        float L1[3] = {0.0f, 0.0f, 0.0f};   // (RELIGHT) the sample's radiance under the table's environment
         // camera ray through a uniformly jittered position of the pixel (box filter)
         const float x = (float)j - 0.5f + rng_u(base, 0, 0), y = (float)i - 0.5f + rng_u(base, 0, 1);
         float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {(x - q.cx) / q.f_pix, -(y - q.cy) / q.f_pix, -1.0f};
@@ -263,6 +287,23 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
                 if (med_seg >= 0 && k >= 0 && tri_id(q.tris[3 * k]) < ot.n_scene_tri) touched = true;
             }
             if (k < 0) {   // escaped: the envmap, MIS-weighted against emitter sampling after a BSDF sample
+                if constexpr (RELIGHT) {   // each environment at its own texel, with its own weight against the shared prev_pdf
+#pragma nounroll
+                    for (int e = 0; e < 2; ++e) {
+                        const float* const env = e ? ot.env_b : q.env;
+                        const float* const env_pdf = e ? ot.env_pdf_b : q.env_pdf;
+                        const int tx = env_texel(d, e ? ot.He_b : q.He, e ? ot.We_b : q.We);
+                        const float w = depth == 0 ? 1.0f : mis_weight(prev_pdf, (e ? have_tab_b : have_tab) ? env_pdf[tx] : 0.0f);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            float Ls = e ? L1[c] : L[c];   // this environment's sum
+                            Ls += thr[c] * (env[3 * tx + c] * w);
+                            L[c] = e ? L[c] : Ls;
+                            L1[c] = e ? Ls : L1[c];
+                        }
+                    }
+                    break;
+                }
                 const int tx = env_texel(d, q.He, q.We);
                 const float w = depth == 0 || (OBJ && prev_delta)
                                     ? 1.0f
@@ -446,7 +487,36 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
             for (int c = 0; c < 3; ++c) po[c] = fmaf(eps, n[c], p[c]);
             // emitter sample with a shadow ray (none at a delta vertex)
             // (REFLECT) trip 1 takes none below the landing: the chain's own light is not the tail's
-            if (((ROUGH ? n_e > 0 : LIGHT) || have_tab) && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !(REFLECT && second && depth < land)) {
+            // (RELIGHT) one per environment that has tables, from the same dims 2-5, each with its own shadow ray and MIS weight
+            if constexpr (RELIGHT) {
+#pragma nounroll
+                for (int e = 0; e < 2; ++e) {
+                    if (!(e ? have_tab_b : have_tab)) continue;
+                    const float* const env = e ? ot.env_b : q.env;
+                    float wl[3], pdf_e;
+                    const int te = env_sample(e ? ot.row_cdf_b : q.row_cdf, e ? ot.col_cdf_b : q.col_cdf, e ? ot.env_pdf_b : q.env_pdf,
+                                              e ? ot.He_b : q.He, e ? ot.We_b : q.We, rng_u(base, depth, 2), rng_u(base, depth, 3),
+                                              rng_u(base, depth, 4), rng_u(base, depth, 5), wl, pdf_e);
+                    if (pdf_e > 0.0f && dot3(n, wl) > 0.0f) {
+                        float f[3], pdf_b;
+                        path_eval(wl, wo, NRM ? ns : n, av, rv, mv, f, pdf_b);
+                        if (f[0] > 0.0f || f[1] > 0.0f || f[2] > 0.0f) {
+                            float ts = FLT_MAX;
+                            ++n_rays;
+                            if (trace<true, false>(q.nodes, q.tris, po, wl, 0.0f, ts, stk, id_limit) < 0) {   // no occluder
+                                const float w = mis_weight(pdf_e, pdf_b) / pdf_e;
+#pragma unroll
+                                for (int c = 0; c < 3; ++c) {
+                                    float Ls = e ? L1[c] : L[c];   // this environment's sum
+                                    Ls += thr[c] * (f[c] * (env[3 * te + c] * w));
+                                    L[c] = e ? L[c] : Ls;
+                                    L1[c] = e ? Ls : L1[c];
+                                }
+                            }
+                        }
+                    }
+                }
+            } else if (((ROUGH ? n_e > 0 : LIGHT) || have_tab) && !(OBJ && kind == MATPBR_PATH_BSDF_DIELECTRIC) && !(REFLECT && second && depth < land)) {
                 float wl[3], pdf_e;
                 int te = 0;
                 float Le[3] = {0.0f, 0.0f, 0.0f}, ts_max = FLT_MAX;   // (LIGHT) the chosen emitter's radiance, the shadow ray's reach
@@ -616,6 +686,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
         } else {
 #pragma unroll
             for (int c = 0; c < 3; ++c) acc[c] += L[c];
+            if constexpr (RELIGHT) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) racc[c] += L1[c];
+            }
         }
     }
     const float sc = last ? 1.0f / (float)q.spp : 1.0f;
@@ -638,6 +712,10 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const PathArgs q, int s0, 
 #pragma unroll
         for (int c = 0; c < 3; ++c) ot.delta[3 * pix + c] = last ? dacc[c] * sc : dacc[c];
         if (ot.rewalked) ot.rewalked[pix] += n_second;
+    }
+    if constexpr (RELIGHT) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ot.relit[3 * pix + c] = last ? racc[c] * sc : racc[c];
     }
     if (q.rays) q.rays[pix] += n_rays;
 }
@@ -2069,6 +2147,41 @@ int matpbr_path_render_edit_diff(const void* nodes, const void* tris, const floa
         return launch_frame(f, q, t);
     };
     return nrm ? launch(ShadeNormals{nrm}) : launch(NoObjects{});
+}
+
+int matpbr_path_render_relight(const void* nodes, const void* tris, const float* a, const float* r, const float* m, int H, int W,
+                               float fov_x_deg, const float* env, const float* row_cdf, const float* col_cdf, const float* env_pdf, int He,
+                               int We, int spp, int max_depth, uint32_t seed, int spp_per_launch, uint32_t* rays, void* stream,
+                               const float* env_b, const float* row_cdf_b, const float* col_cdf_b, const float* env_pdf_b, int He_b, int We_b,
+                               const float* nrm, float* base, float* relit) {
+    float* const out = base;   // the radiance under the frame's own environment is the render's own sum
+    const Frame f = RENDER_FRAME;
+    PathArgs q{};
+    if (!env_b || !row_cdf_b || !col_cdf_b || !env_pdf_b || He_b <= 0 || We_b <= 0 || !base || !relit || !frame_args(f, q))
+        return MATPBR_PATH_ERR_INVALID_ARG;
+    auto launch = [&](auto base_table) {   // the second environment's table over the render's own
+        Relight<decltype(base_table)> t{};
+        static_cast<decltype(base_table)&>(t) = base_table;
+        t.env_b = env_b; t.row_cdf_b = row_cdf_b; t.col_cdf_b = col_cdf_b; t.env_pdf_b = env_pdf_b; t.He_b = He_b; t.We_b = We_b; t.relit = relit;
+        return launch_frame(f, q, t);
+    };
+    return nrm ? launch(ShadeNormals{nrm}) : launch(NoObjects{});
+}
+
+int matpbr_path_composite_relight(const float* base_sum, const float* relit_sum, const float* photo, int H, int W, float scale, float floor,
+                                  float* out, void* stream) {
+    if (!composite_relight_args_valid(base_sum, relit_sum, photo, H, W, scale, floor, out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    const long P = (long)H * W;
+    hipLaunchKernelGGL(composite_relight_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, base_sum, relit_sum, photo, P,
+                       scale, floor, out);
+    return hipGetLastError() == hipSuccess ? MATPBR_PATH_OK : MATPBR_PATH_ERR_LAUNCH;
+}
+
+int matpbr_path_composite_relight_host(const float* base_sum, const float* relit_sum, const float* photo, int H, int W, float scale, float floor,
+                                       float* out) {
+    if (!composite_relight_args_valid(base_sum, relit_sum, photo, H, W, scale, floor, out)) return MATPBR_PATH_ERR_INVALID_ARG;
+    for (long p = 0; p < (long)H * W; ++p) composite_relight_pixel(base_sum, relit_sum, photo, p, scale, floor, out);
+    return MATPBR_PATH_OK;
 }
 
 int matpbr_path_eval_normal_grad_host(const float* n, const float* wo, const float* wi, const float* a, const float* r, const float* m,

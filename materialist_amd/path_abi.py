@@ -133,6 +133,9 @@ SIGNATURES = {
     "matpbr_path_reflect_chain_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_long, _P, _P, _P, _P,
                                                       ctypes.c_long] + [_P] * 5),
     "matpbr_path_render_edit_diff": (ctypes.c_int, _FRAME + [_P, _P] + [_P] * 8),
+    "matpbr_path_render_relight": (ctypes.c_int, _FRAME + [_P, _P] + [_P] * 4 + [ctypes.c_int, ctypes.c_int] + [_P] * 3),
+    "matpbr_path_composite_relight": (ctypes.c_int, [_P] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _P, _P]),
+    "matpbr_path_composite_relight_host": (ctypes.c_int, [_P] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _P]),
     "matpbr_path_medium_segment_host": (ctypes.c_int, [_P, _P, _P, ctypes.c_long, _P, _P, _P]),
     "matpbr_path_phase_sample_host": (ctypes.c_int, [ctypes.c_float, _P, _P, ctypes.c_long, _P]),
     "matpbr_path_composite_ratio": (ctypes.c_int, [_P] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _P, _P]),
@@ -179,8 +182,8 @@ VERSION = 3
 MAX_BWD_ENV_TEXELS = 1024
 # the symbols added at version 3, by the feature each group came with, as `symbol` names it, in the order the features were merged: a
 # version-3 library built before one of them loads, and `symbol` names what it lacks.  The first ten groups are the partition of
-# LATE_SYMBOLS; the five after them ("Ratio shadow transfer", "Moving inserted objects", "Media inside glass",
-# "Reflected in inserted objects", "Material edits in the photograph") stand beside it
+# LATE_SYMBOLS; the six after them ("Ratio shadow transfer", "Moving inserted objects", "Media inside glass",
+# "Reflected in inserted objects", "Material edits in the photograph", "Relighting in the photograph") stand beside it
 FEATURE_SYMBOLS = {
     "smooth inserted objects": ("matpbr_path_render_objects_normals", "matpbr_path_object_normal_host", "matpbr_path_object_sample_shading_host"),
     "the denoiser": ("matpbr_path_features", "matpbr_path_features_host", "matpbr_path_denoise_prepare", "matpbr_path_denoise_prepare_host",
@@ -206,9 +209,10 @@ FEATURE_SYMBOLS = {
                                    "matpbr_path_phase_sample_host"),
     "the photograph reflected in inserted objects": ("matpbr_path_render_objects_reflect", "matpbr_path_reflect_chain_host"),
     "material edits in the photograph": ("matpbr_path_render_edit_diff",),
+    "relighting in the photograph": ("matpbr_path_render_relight", "matpbr_path_composite_relight", "matpbr_path_composite_relight_host"),
 }
 (SMOOTH_SYMBOLS, DENOISE_SYMBOLS, PBR_SYMBOLS, LIGHT_SYMBOLS, ROUGH_SYMBOLS, COLOR_SYMBOLS, TEXTURE_SYMBOLS, DIFF_SYMBOLS, DIFF_DENOISE_SYMBOLS,
- THROUGH_SYMBOLS, RATIO_SYMBOLS, MOVE_SYMBOLS, MEDIUM_SYMBOLS, REFLECT_SYMBOLS, MAPEDIT_SYMBOLS) = FEATURE_SYMBOLS.values()
+ THROUGH_SYMBOLS, RATIO_SYMBOLS, MOVE_SYMBOLS, MEDIUM_SYMBOLS, REFLECT_SYMBOLS, MAPEDIT_SYMBOLS, RELIGHT_SYMBOLS) = FEATURE_SYMBOLS.values()
 _FEATURE_OF = {name: what for what, names in FEATURE_SYMBOLS.items() for name in names}   # every late symbol -> its feature
 _FEATURE = {name: what for name, what in _FEATURE_OF.items() if what in list(FEATURE_SYMBOLS)[:10]}
 LATE_SYMBOLS = tuple(_FEATURE)

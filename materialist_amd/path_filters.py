@@ -1,5 +1,6 @@
 """The image-space steps around the path render: the a-trous denoiser ("Denoiser"), the differential render's
-composite ("Differential render", "Ratio shadow transfer", "Material edits in the photograph") and its own denoiser ("Denoiser for the differential render").  Each step is written once, over a
+composite ("Differential render", "Ratio shadow transfer", "Material edits in the photograph"), the quotient composite ("Relighting in the
+photograph") and the differential render's own denoiser ("Denoiser for the differential render").  Each step is written once, over a
 side: `_HOST` runs it on numpy arrays through the library's `*_host` entry (the routine the kernel runs, for the tests), `_Device`
 on torch tensors through the kernel on the current torch stream.  The public `NAME_host` and `NAME` are the two calls of that body."""
 from itertools import chain
@@ -240,6 +241,46 @@ def composite_edit(delta, photo, base=None) -> torch.Tensor:
     the fit's albedo cancels.  Where delta is 0 the photograph (>= 0) comes through bit for bit."""
     where = (delta, photo) if base is None else (delta, photo, base)
     return _composite_edit(_Device(*where), lambda s: torch.zeros(s, dtype=torch.float32, device=_device_of(*where)), delta, photo, base)
+
+
+# ---- the quotient composite (DESIGN.md section 1.4, "Relighting in the photograph") -----------------------------------------------------
+RELIGHT_FLOOR = 0.01   # the default floor over the frame's mean model radiance: where a channel is that dark the ratio starts to give way
+
+
+def _composite_relight(side, base, relit, photo, scale, floor):
+    shp = tuple(side.raw(photo).shape)
+    if len(shp) != 3 or shp[2] != 3 or shp[0] < 1 or shp[1] < 1:
+        raise ValueError(f"photo must be [H,W,3], got {list(shp)}")
+    H, W = shp[:2]
+    sc = _composite_scale(scale)
+    if floor is not None and not (np.isfinite(np.float32(floor)) and np.float32(floor) > 0):
+        raise ValueError(f"floor must be finite and positive, got {floor}")
+    b, r, p = side.images([(base, (H, W, 3), "base"), (relit, (H, W, 3), "relit"), (photo, (H, W, 3), "photo")])
+    if floor is None:   # in fp64 over all pixels and channels, then one rounding to float32
+        mean = float(b.mean(dtype=np.float64)) if isinstance(b, np.ndarray) else float(b.double().mean())
+        floor = float(np.float32(RELIGHT_FLOOR * sc * mean))
+        if not (np.isfinite(floor) and floor > 0):
+            raise ValueError(f"the default floor is {RELIGHT_FLOOR} x mean(base scale) = {floor}: base has no light to take a ratio over; pass floor")
+    out = side.empty(H, W, 3)
+    _run(side, "matpbr_path_composite_relight", (b, r, p), (H, W, sc, float(floor)), (out,))
+    return out
+
+
+def composite_relight_host(base, relit, photo, scale: float = 1.0, floor: Optional[float] = None) -> np.ndarray:
+    """`composite_relight` on the CPU with the routine the kernel runs: base, relit, photo [H,W,3] -> [H,W,3], the same bits for the
+    same `floor`."""
+    return _composite_relight(_HOST, base, relit, photo, scale, floor)
+
+
+@torch.no_grad()
+def composite_relight(base, relit, photo, scale: float = 1.0, floor: Optional[float] = None) -> torch.Tensor:
+    """`PathTracer.render_relight`'s outputs composited into the photograph ("Relighting in the photograph"),
+    on the device (the current torch stream): the quotient image max(0, photo g), g = (relit scale + floor) / (base scale + floor) per
+    channel, every operation rounded on its own.  base, relit: the radiance under the fitted and under the new light, or their sums
+    over some frames with `scale` = 1 / (the number of frames); photo [H,W,3], linear.  `floor` > 0 bounds g where the model is
+    dark; None: RELIGHT_FLOOR (0.01) x the mean of base scale over all pixels and channels.  Where relit has base's bits the
+    photograph (>= 0) comes through bit for bit."""
+    return _composite_relight(_Device(base, relit, photo), base, relit, photo, scale, floor)
 
 
 # ---- the differential render's denoiser (DESIGN.md section 1.4, "Denoiser for the differential render") ----------------------------------

@@ -17,7 +17,9 @@ ratio of the model's radiance with and without the objects ("Ratio shadow transf
 roughdielectric object may carry "photo": True ("Reflected in inserted objects"): `render_diff_through` and `render_diff_ratio` with a
 photograph then show the photograph in what the object reflects.  `PathTracer.render_edit_diff`, `edit_mask` and `composite_edit`
 put a material edit into the photograph ("Material edits in the photograph"): the differential render of edited maps on a tracer
-without objects.  There is no fallback: a missing or failing library raises.
+without objects.  `PathTracer.render_relight` and `composite_relight` put a new light into the photograph ("Relighting in the
+photograph"): one walk under the fitted and the new envmap, and the quotient image.  There is no fallback: a missing or failing
+library raises.
 """
 from __future__ import annotations
 
@@ -421,6 +423,31 @@ class PathTracer:
                  ae.data_ptr(), re.data_ptr(), me.data_ptr(), mk.data_ptr(), _dptr(nrm), delta.data_ptr(), base.data_ptr(), rewalked.data_ptr()),
               "matpbr_path_render_edit_diff")
         return delta, base, rewalked
+
+    @torch.no_grad()
+    def render_relight(self, albedo: torch.Tensor, roughness: torch.Tensor, metallic: torch.Tensor, envmap, new_envmap, spp: int = 64,
+                       max_depth: int = 4, seed: int = 0, spp_per_launch: int = 8, tables: Optional[tuple] = None,
+                       new_tables: Optional[tuple] = None, rays: Optional[torch.Tensor] = None, normal=None) -> tuple:
+        """One walk under two environments ("Relighting in the photograph") with `render`'s arguments and random
+        numbers -> (base [H,W,3], relit [H,W,3]) on the device, the means over `spp` of the radiance under `envmap` (the fitted light)
+        and under `new_envmap` [He_b,We_b,3], which may have another size.  Each is what `render` gives under that envmap up to the
+        rounding of its sums; the closest hits, the texels and the BSDF samples are computed once, and both estimators run on the same
+        paths.  Where `new_envmap` has `envmap`'s values relit has base's bits.  `composite_relight` puts them into a photograph.
+        `tables`, `new_tables`: what `tables(envmap)`, `tables(new_envmap)` returned (default: built now).  `rays`: the closest-hit
+        rays once and each environment's shadow rays.  `normal`: the shading-normal map of `render`.  Every split into launches gives
+        the same bits.  A tracer with objects raises ValueError."""
+        if self.objects is not None:
+            raise ValueError("render_relight knows no inserted objects: build the PathTracer without `objects`")
+        H, W, dev = self.H, self.W, self.device
+        fn = symbol("matpbr_path_render_relight")
+        nrm = self._normal(normal, "render_relight") if normal is not None else None
+        inputs = self._inputs(albedo, roughness, metallic, envmap, tables)
+        env_b, row_b, col_b, pdf_b = self._inputs(*inputs[:3], new_envmap, new_tables)[3:]
+        base, relit = torch.empty(H, W, 3, device=dev, dtype=torch.float32), torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+        check(fn(*self._frame(*inputs, spp, max_depth, seed, spp_per_launch), _dptr(rays), torch.cuda.current_stream(dev).cuda_stream,
+                 env_b.data_ptr(), row_b.data_ptr(), col_b.data_ptr(), pdf_b.data_ptr(), int(env_b.shape[0]), int(env_b.shape[1]), _dptr(nrm),
+                 base.data_ptr(), relit.data_ptr()), "matpbr_path_render_relight")
+        return base, relit
 
     def _first_hit(self, entry: str, channels: int, hidden: int, *own) -> torch.Tensor:
         """[H,W,channels] on the device from the first-hit entry `entry`: it takes the BVH, the camera, the table without the flags

@@ -12,6 +12,9 @@ reference's final images come from: the `.ply` mesh, shadows, inter-reflection, 
 roll the envmap's texel columns.  `denoise="atrous"` passes a path-traced image through the project's denoiser (DESIGN.md section 1.4,
 "Denoiser"): every render of `spp` samples becomes two of `spp / 2` with independent seeds, and one variance-guided a-trous filter
 runs over their sums, guided by the first-hit features and the albedo.  The default, "off", leaves every output as it was.
+`relight_composite=True` (path only; DESIGN.md section 1.4, "Relighting in the photograph") writes the photograph under the new light
+instead of a re-render of the fitted scene: the photograph times the model's radiance under the new envmap over its radiance under the
+fitted one, both from one walk (`PathTracer.render_relight`, `composite_relight`).
 """
 from __future__ import annotations
 
@@ -278,10 +281,42 @@ def _denoised(pt, render_half, iters: int, seed: int, geom: torch.Tensor, guide:
     return pt.denoise(A, B, guide, geom)
 
 
+def _check_relight_composite(integrator: str, edit: Optional[Dict[str, object]], edit_composite: bool, floor: Optional[float]) -> None:
+    """ValueError for what relighting in the photograph does not do, before any GPU work."""
+    if integrator != "path":
+        raise ValueError("relight_composite needs integrator='path': the walk under two envmaps is the path tracer's (the 'sh' render has "
+                         "no shadows to transfer)")
+    if edit_composite:
+        raise ValueError("relight_composite knows no edit composite: one picture takes one transfer, the edit's difference or the light's ratio")
+    if any((edit or {}).get(key) is not None for key in ("albedo", "roughness", "metallic")):
+        raise ValueError("relight_composite knows no material edit: the photograph shows the materials as they are, and the ratio of two "
+                         "lights over edited maps would not put the edit into it")
+    if floor is not None and not (np.isfinite(floor) and floor > 0):
+        raise ValueError(f"relight_floor must be finite and > 0, got {floor}")
+
+
+def _relit_photo(pt, mat: Dict[str, torch.Tensor], env_a, tabs_a, env_b, nrm, spp: int, max_depth: int, seed: int, guides, photo: torch.Tensor,
+                 floor: Optional[float]) -> torch.Tensor:
+    """The photograph under `env_b`: `PathTracer.render_relight` of the fitted maps under the fitted envmap `env_a` and under `env_b`, and
+    `composite_relight`.  `guides`: None, or the a-trous filter's (geom, albedo guide): then two walks of spp / 2, seeds `seed` and
+    `seed + 1`, and the two radiances pass `PathTracer.denoise` one after the other with the same guides before the composite."""
+    from .pathtrace import composite_relight
+
+    maps = (mat["albedo"], mat["roughness"], mat["metallic"])
+    tabs_b = pt.tables(env_b)
+    if guides is None:
+        base, relit = pt.render_relight(*maps, env_a, env_b, spp, max_depth, seed, tables=tabs_a, new_tables=tabs_b, normal=nrm)
+    else:
+        halves = [pt.render_relight(*maps, env_a, env_b, spp // 2, max_depth, seed + k, tables=tabs_a, new_tables=tabs_b, normal=nrm) for k in (0, 1)]
+        base, relit = (pt.denoise(halves[0][k], halves[1][k], guides[1], guides[0]) for k in (0, 1))
+    return composite_relight(base, relit, photo, floor=floor)
+
+
 def render_real(save_name: str, env_path: Optional[str] = None, input_path: Optional[str] = None, save_path: Optional[str] = None,
                 spp: int = 64, device="cuda", edit: Optional[Dict[str, object]] = None, integrator: str = "sh", max_depth: int = 4,
                 seed: int = 0, shading_normals: str = "face", denoise: str = "off", env_scale: float = 1.0, composite: bool = False,
-                photo_path: Optional[str] = None, transfer: str = "additive") -> str:
+                photo_path: Optional[str] = None, transfer: str = "additive", relight_composite: bool = False,
+                relight_photo: Optional[str] = None, relight_floor: Optional[float] = None) -> str:
     """render_final.py:148-203,241-260: one re-render under `env_path` -> mi_<name>_<env>_<edit flag>.exr / .png.
     integrator "sh": the deterministic render (SH25 light, direct, unshadowed); "path": the path tracer, `max_depth` / `seed`, shading
     with the mesh's face normals or, with `shading_normals="map"`, with best_results/normal.exr whatever the scene is called.
@@ -291,7 +326,13 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
     the photograph (`photo_path`, default <scene>/gt_image.exr, as `render_oi` reads it) with what the edit changes, not a re-render of
     the fitted scene: pixels no edited texel reaches keep the photograph's bits -> mi_ec_<name>_<env>_<edit flag>.exr / .png.
     `transfer`: "additive" adds the model's difference; "ratio" dims the photograph, per channel, by the share of light the model
-    loses where the edit darkens it, so that the fit's albedo cancels."""
+    loses where the edit darkens it, so that the fit's albedo cancels.
+    `relight_composite=True` ("Relighting in the photograph"; path only, no edit, not with `composite`): the
+    photograph (`relight_photo`, default <scene>/gt_image.exr) under the new light: environment A is the fitted best_results/envmap.hdr,
+    B is `env_path` times `env_scale`, and the picture is the photograph times the model's radiance under B over that under A, both from
+    one walk -> mi_rc_<name>_<env>_.exr / .png.  Without an `env_path` and with `env_scale` 1 B is A and the picture the photograph: a
+    ValueError.  `relight_floor` > 0: `composite_relight`'s floor (default: 0.01 x the frame's mean radiance under A).  With
+    `denoise="atrous"`: two walks of spp / 2, seeds `seed` and `seed + 1`, and both radiances pass the a-trous filter before the ratio."""
     _check_integrator(integrator, shading_normals)
     _scaled_env(np.zeros(0, np.float32), env_scale, integrator)
     atrous = _check_denoise(denoise, integrator, spp)
@@ -300,6 +341,15 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
         raise ValueError(f"transfer must be 'additive' or 'ratio', got {transfer!r}")
     if not composite and (photo_path is not None or transfer != "additive"):
         raise ValueError("photo_path and transfer need composite=True")
+    if not relight_composite and (relight_photo is not None or relight_floor is not None):
+        raise ValueError("relight_photo and relight_floor need relight_composite=True")
+    if relight_composite:
+        _check_relight_composite(integrator, edit, composite, relight_floor)
+        if env_path is None and float(env_scale) == 1.0:
+            raise ValueError("relight_composite needs a new light, an env_path or an env_scale other than 1: under the fitted envmap the "
+                             "picture is the photograph")
+        photo = _oi_photo(scene_dir, relight_photo, False, 1.0)
+        fitted_env_path = find_envmap(save_name, None, input_path)
     if composite:
         if integrator != "path":
             raise ValueError("composite needs integrator='path': the differential render of edited maps is the path tracer's")
@@ -317,6 +367,13 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
             *fitted, load_image(env_path), (mat["albedo"], mat["roughness"], mat["metallic"]), None, spp, max_depth, seed,
             normal=mat["normal"] if shading_normals == "map" else None)
         img = composite_edit(delta, torch.from_numpy(photo).to(delta.device), fit if transfer == "ratio" else None)
+    elif relight_composite:
+        pt = _path_tracer(scene_dir, save_name, mat, device)
+        nrm = mat["normal"] if shading_normals == "map" else None
+        env_a = load_image(fitted_env_path)
+        geom = pt.features(normal=nrm) if atrous else None
+        img = _relit_photo(pt, mat, env_a, pt.tables(env_a), _scaled_env(load_image(env_path), env_scale), nrm, spp, max_depth, seed,
+                           (geom, albedo_guide(geom, mat["albedo"])) if atrous else None, torch.from_numpy(photo).to(pt.device), relight_floor)
     elif atrous:
         pt = _path_tracer(scene_dir, save_name, mat, device)
         nrm = mat["normal"] if shading_normals == "map" else None
@@ -335,7 +392,7 @@ def render_real(save_name: str, env_path: Optional[str] = None, input_path: Opti
     env_id = os.path.basename(env_path)[:-4]
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
     os.makedirs(out_dir, exist_ok=True)
-    base = os.path.join(out_dir, f"mi_{'ec_' if composite else ''}{save_name}_{env_id}_{edit_flag}")   # (:199-202)
+    base = os.path.join(out_dir, f"mi_{'ec_' if composite else 'rc_' if relight_composite else ''}{save_name}_{env_id}_{edit_flag}")   # (:199-202)
     write_exr(base + ".exr", img.cpu().numpy())
     write_png(base + ".png", _loss.linear_to_srgb(img.clamp_min(0)).cpu().numpy())
     return base + ".png"
@@ -888,15 +945,26 @@ def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int =
                           input_path: Optional[str] = None, save_path: Optional[str] = None, spp: int = 64, device="cuda",
                           write_frames: bool = True, edit: Optional[Dict[str, object]] = None, integrator: str = "sh",
                           max_depth: int = 4, seed: int = 0, shading_normals: str = "face", denoise: str = "off",
-                          env_scale: float = 1.0) -> Dict[str, object]:
+                          env_scale: float = 1.0, relight_composite: bool = False, relight_photo: Optional[str] = None,
+                          relight_floor: Optional[float] = None) -> Dict[str, object]:
     """render_final.py:300-418: `frames` renders, the envmap rolled by int(angle/360*W) columns per frame.  integrator "sh": the
     rolled light is the SH rotation of the projected envmap; "path": the path tracer renders the rolled texels themselves (`shading_normals` as in `render_real`).
     `denoise="atrous"` (path only, even `spp`): every frame is two renders of spp / 2, seeds `seed` and `seed + 1`, through the a-trous
-    filter; the features are computed once for all frames.  `env_scale` (path only): the envmap is multiplied by it first."""
+    filter; the features are computed once for all frames.  `env_scale` (path only): the envmap is multiplied by it first.
+    `relight_composite=True` ("Relighting in the photograph"; path only, no edit): every frame is the photograph
+    (`relight_photo`, default <scene>/gt_image.exr) under the rolled envmap: environment A is the fitted best_results/envmap.hdr, B the
+    frame's rolled envmap, as in `render_real` -> <out>/rolling_rc_animation/frame_%04d.png and rolling_rc_<name>_<env>.mp4 / .gif.  Without
+    an `env_path` (and with `env_scale` 1) frame 0 is the photograph, bit for bit."""
     _check_integrator(integrator, shading_normals)
     _scaled_env(np.zeros(0, np.float32), env_scale, integrator)
     atrous = _check_denoise(denoise, integrator, spp)
     scene_dir = os.path.join(input_path if input_path is not None else OUT_DIR, save_name)
+    if not relight_composite and (relight_photo is not None or relight_floor is not None):
+        raise ValueError("relight_photo and relight_floor need relight_composite=True")
+    if relight_composite:
+        _check_relight_composite(integrator, edit, False, relight_floor)
+        photo = _oi_photo(scene_dir, relight_photo, False, 1.0)
+        fitted_env_path = find_envmap(save_name, None, input_path)
     env_path = find_envmap(save_name, env_path, input_path)
     env = _scaled_env(load_image(env_path), env_scale, integrator)
     We = env.shape[1]
@@ -907,7 +975,15 @@ def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int =
     if integrator == "path":
         pt = _path_tracer(scene_dir, save_name, mat, device)
         nrm = mat["normal"] if shading_normals == "map" else None
-        if atrous:
+        if relight_composite:
+            env_a = load_image(fitted_env_path)
+            tabs_a = pt.tables(env_a)                                # A does not roll: one set for all frames, as the features are
+            geom = pt.features(normal=nrm) if atrous else None
+            guides = (geom, albedo_guide(geom, mat["albedo"])) if atrous else None
+            photo_t = torch.from_numpy(photo).to(pt.device)
+            render_frame = lambda f: _relit_photo(pt, mat, env_a, tabs_a, np.roll(env, shifts[f], axis=1), nrm, spp, max_depth, seed, guides,
+                                                  photo_t, relight_floor)
+        elif atrous:
             geom = pt.features(normal=nrm)                           # the camera and the mesh do not move: one set for all frames
             guide = albedo_guide(geom, mat["albedo"])
 
@@ -926,7 +1002,8 @@ def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int =
         rl = Relighter(mat, _scene_normal(scene_dir, mat, save_name, device), spp, mesh_mask=_mesh_mask(scene_dir))
         render_frames = lambda f0, f1: rl.frames(np.stack(lights[f0:f1]))
     out_dir = os.path.join(save_path if save_path else OUT_DIR, save_name)
-    anim_dir = os.path.join(out_dir, "rolling_envmap_animation")
+    tag = "rolling_rc" if relight_composite else "rolling_envmap"
+    anim_dir = os.path.join(out_dir, f"{tag}_animation")
     os.makedirs(anim_dir, exist_ok=True)
     env_id = os.path.basename(env_path)[:-4]
     paths: List[str] = []
@@ -946,8 +1023,8 @@ def render_rolling_envmap(save_name: str, env_path: Optional[str], frames: int =
 
         from .video_mp4 import write_mp4
 
-        gif_path = os.path.join(out_dir, f"rolling_envmap_{save_name}_{env_id}.gif")     # render_final.py:405-414 writes both
+        gif_path = os.path.join(out_dir, f"{tag}_{save_name}_{env_id}.gif")     # render_final.py:405-414 writes both
         pil = [Image.fromarray(i) for i in imgs]
         pil[0].save(gif_path, save_all=True, append_images=pil[1:], duration=100, loop=0)
-        mp4_path = write_mp4(os.path.join(out_dir, f"rolling_envmap_{save_name}_{env_id}.mp4"), imgs, fps=10)
+        mp4_path = write_mp4(os.path.join(out_dir, f"{tag}_{save_name}_{env_id}.mp4"), imgs, fps=10)
     return {"animation_dir": anim_dir, "frames": paths, "gif": gif_path, "mp4": mp4_path if imgs else None}

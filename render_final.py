@@ -32,6 +32,17 @@ def parse_args(argv=None):
     ap.add_argument("--edit_transfer", choices=["additive", "ratio"], default=None,
                     help="--edit_composite: additive (the default) = the model's difference is added to the photograph; ratio = where the edit "
                          "darkens a channel the photograph is dimmed by the share of light the model loses, so a badly fitted albedo cancels")
+    ap.add_argument("--relight_composite", action="store_true",
+                    help="--mode real or rolling with --integrator path: relighting in the photograph: the photograph times the model's "
+                         "radiance under the new envmap (--env_path times --env_scale; a rolling frame's rolled envmap) over its radiance "
+                         "under the fitted best_results/envmap.hdr, both from one walk, not a re-render of the fitted scene.  Writes "
+                         "mi_rc_<name>_<env>_.exr / .png, or rolling_rc_<name>_<env>.mp4 / .gif and their frames.  Not with an --edit_* flag, "
+                         "--edit_composite or --mode oi")
+    ap.add_argument("--relight_photo", type=str, default=None, metavar="PATH",
+                    help="--relight_composite: the photograph, of the maps' size (default <scene>/gt_image.exr, linear; a .png holds display values)")
+    ap.add_argument("--relight_floor", type=float, default=None, metavar="F",
+                    help="--relight_composite: the radiance added to both sides of the ratio, which bounds it where the model is dark "
+                         "(default: 0.01 x the frame's mean radiance under the fitted envmap)")
     ap.add_argument("--integrator", choices=("sh", "path"), default="sh",
                     help="sh: the deterministic render (direct light under SH25, no shadows); path: the path tracer on the scene's .ply "
                          "(Mitsuba's `path` as the reference renders its final images: shadows, inter-reflection, the envmap's texels); "
@@ -140,6 +151,8 @@ def parse_args(argv=None):
         ap.error("--edit_photo needs --edit_composite")
     if a.edit_transfer is not None and not a.edit_composite:
         ap.error("--edit_transfer needs --edit_composite")
+    if (a.relight_photo is not None or a.relight_floor is not None) and not a.relight_composite:
+        ap.error("--relight_photo and --relight_floor need --relight_composite")
     if a.oi_tint is not None and (a.mode != "oi" or a.oi_scene is not None):
         ap.error("--oi_tint needs --mode oi without --oi_scene (an --oi_scene entry says \"medium\" itself)")
     if a.oi_tint is not None and not all(0 < c <= 1 for c in a.oi_tint):
@@ -165,12 +178,16 @@ def main(argv=None):
     edit = {"albedo": a.edit_albedo, "roughness": a.edit_roughness, "metallic": a.edit_metallic}
     it = {"integrator": a.integrator, "max_depth": a.max_depth, "seed": a.seed, "shading_normals": a.shading_normals, "denoise": a.denoise,
           "env_scale": a.env_scale}
+    rc = {"relight_composite": True, "relight_photo": a.relight_photo, "relight_floor": a.relight_floor} if a.relight_composite else {}
+    if a.relight_composite and a.mode == "oi":
+        raise ValueError("--relight_composite knows no --mode oi: inserted objects and lights are not in the walk under two envmaps "
+                         "(--oi_composite puts objects into the photograph under the fitted light)")
     if a.mode == "real":
         ec = {"composite": True, "photo_path": a.edit_photo, "transfer": a.edit_transfer or "additive"} if a.edit_composite else {}
-        print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it, **ec))
+        print("Wrote file to", relight.render_real(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, edit=edit, **it, **ec, **rc))
     elif a.mode == "rolling":
         res = relight.render_rolling_envmap(a.save_name, a.env_path, a.frames, a.rotation_step, a.input_path, a.save_path, a.spp, edit=edit,
-                                            **it)
+                                            **it, **rc)
         print(f"Animation saved to {res['gif']}\nIndividual frames saved to {res['animation_dir']}")
     elif a.mode == "oi":
         res = relight.render_oi(a.save_name, a.env_path, a.input_path, a.save_path, a.spp, a.oi_iters, a.oi_max_depth, a.seed,
